@@ -2,6 +2,7 @@
 """bench.py -- BASELINE.json's metric on MI355X: ADC queries/sec + encode vectors/sec.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|pq|opq|deep|sift1b] [--k K] [--nq NQ]
+                    [--full] [--dump-outputs DIR]
 
 Workloads (BASELINE.json `configs`):
   pq      SIFT1M-shape PQ  m=8 h=256: quantize_pq + linscan_pq            (config 2; default at N = 1)
@@ -23,7 +24,16 @@ backend nccl == RCCL); started under torch.distributed.run it uses the ranks it 
 N-GPU search inside ONE process through the library's multi-device index (rq_index_create_sharded: what a Julia
 session gets) instead.
 
-Rank 0 prints ONE JSON line (contract in the task description) with two extra objects:
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value`, `unit`, `ms_per_step` (the
+milliseconds of one timed step), `higher_is_better`, `dtype` and the config; the objects of the other measurements and
+checks (`encode`, `roofline`, `cpu_baseline`, `checks`, ...) are null.
+`--dump-outputs DIR` also writes what the timed call returned in its last step as DIR/<name>.npy (float32 / float64, at
+most 48 MiB: a fixed seeded sample of the query rows when the whole answer is larger, their numbers in query_rows.npy);
+the inputs are generated from fixed seeds, so two builds can be compared output for output.
+
+`--full` adds everything else the benchmark measures and checks (what follows); the encode is then timed in its own
+bracket, otherwise it runs once, untimed, to produce the codes the scan reads.  With `--full`, rank 0 prints ONE JSON line
+(contract in the task description) with two extra objects:
   roofline      the dominant kernel (adc_scan_kernel) against the resource that binds it -- the LDS gather pipe:
                 algorithmic bytes nq*n*m per launch / kernel time vs 256 CU x 256 B/clk x 2.4 GHz; the HBM side
                 (the same bytes vs 8 TB/s, and the PMC-measured traffic) is reported next to it
@@ -69,6 +79,10 @@ def parse():
     ap.add_argument("--no-ab", action="store_true", help="skip the prepared-base / arrival-order comparison runs (profiling: every "
                     "scan launch of the run is then the headline's kernel on ordered rows)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check besides the headline (encode timing, "
+                    "roofline, CPU baseline, recall, answer checks, host path, row-order comparison, single-GPU anchors, inproc leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path returned in its last step "
+                    "as DIR/<name>.npy (float32 / float64, a fixed seeded sample when larger than 48 MiB)")
     return ap.parse_args()
 
 
@@ -105,6 +119,49 @@ def timed(fn, steps, warmup, barrier):
     torch.cuda.synchronize()
     wall_ms = (time.perf_counter() - t0) * 1e3
     return e0.elapsed_time(e1), wall_ms
+
+
+DUMP_BUDGET = 48 << 20       # bytes of array data --dump-outputs writes at most
+DUMP_SEED = 20240611         # the sample of rows is the same in every run
+
+
+def dump_rows(n, row_bytes):
+    """the rows of an n-row output that --dump-outputs writes: all of them, or a fixed seeded sample (ascending) that fits"""
+    import numpy as np
+    if n * row_bytes <= DUMP_BUDGET:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, max(1, DUMP_BUDGET // row_bytes), replace=False))
+
+
+def as_u32(a):
+    """ids as the uint32 values they are (the library returns them as int32 bit patterns)"""
+    import numpy as np
+    a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    return a.view(np.uint32) if a.dtype.itemsize == 4 and a.dtype.kind in "iu" else a
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy for every (name, array); float32 stays float32, everything else becomes float64"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays:
+        a = np.asarray(a)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64)))
+
+
+def dump_scan(dirname, dists, ids):
+    """the answer of one search step: dists [nq][k] f32, ids [nq][k] (uint32 values, written as float64 so ids up to 2^53 stay
+    exact), and the query rows they belong to"""
+    import numpy as np
+    nq, k = dists.shape
+    rows = dump_rows(nq, k * (4 + 8) + 8)
+    if hasattr(dists, "cpu"):
+        import torch
+        sel = torch.from_numpy(rows).to(dists.device)
+        dists, ids = dists.index_select(0, sel).cpu().numpy(), ids.index_select(0, sel)
+    else:
+        dists, ids = np.asarray(dists)[rows], np.asarray(ids)[rows]
+    dump_outputs(dirname, [("dists", dists), ("ids", as_u32(ids)), ("query_rows", rows)])
 
 
 def lib_build():
@@ -212,84 +269,93 @@ def train_bench(a):
     prof = _lib.train_profile()
     iters = max(1.0, prof["iterations"])
     ms_step = prof["loop_ms"] / iters
-    rq.set_tuning("TRAIN_PROFILE", 1)
-    try:
-        run(niter)
-        fine = _lib.train_profile()
-    finally:
-        rq.set_tuning("TRAIN_PROFILE", 0)
-    fi = max(1.0, fine["iterations"])
-    per_iter = {k: round(fine[k] / fi, 4) for k in ("qerror_ms", "gram_ms", "svd_ms", "rotate_ms", "update_centers_ms", "encode_ms",
-                                                    "reconstruct_ms", "converge_ms") if fine[k] > 0}
-    # (train_pq: qerror / reconstruct run ONCE after the loop; their entries are that one call's time / iterations)
-    # every device phase of the LOOP against its own roof (algorithmic bytes / flops per iteration, SURVEY 8d's style).  Phases
-    # that run once after the loop (train_pq: the final qerror / reconstruct) are not loop phases and get no roof.
-    GB = 1e9
-    once = set() if opq else {"qerror_ms", "reconstruct_ms"}
-    shapes = {"rotate_ms": ("mfma", 2.0 * d * d * n), "gram_ms": ("mfma", 2.0 * d * d * n), "encode_ms": ("mfma", 2.0 * d * h * n),
-              "update_centers_ms": ("hbm", (4.0 * d + m) * n), "reconstruct_ms": ("hbm", (4.0 * d + m) * n),
-              # qerror: X and the n x d reconstruction, or X and the codes when CB is gathered inside the kernel (no reconstruct phase)
-              "qerror_ms": ("hbm", (8.0 * d if "reconstruct_ms" in per_iter else 4.0 * d + m) * n)}
-    roofs = {}
-    for k, (bound, work) in shapes.items():
-        if k not in per_iter or k in once:
-            continue
-        t = per_iter[k] * 1e-3
-        if bound == "mfma":
-            ach = work / t / 1e12
-            roofs[k[:-3]] = {"bound": "mfma", "achieved": round(ach, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / FP32_PEAK_TFLOPS, 4)}
-        else:
-            ach = work / t / GB
-            roofs[k[:-3]] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4)}
-    if "update_centers" in roofs:
-        # the segment sums run as one-hot products on the bf16 matrix cores (csrc/rq_train.hip: centers_mfma_kernel): 4 MFMAs
-        # of 16 x 16 x 32 per (32 rows, 16-dimension block, 16-code tile); the HBM roof above is the algorithmic one
-        units = sum((sz + 15) // 16 for sz in [d // m + (1 if i < d % m else 0) for i in range(m)])
-        mf = 4 * 2.0 * 16 * 16 * 32 * ((h + 15) // 16) * units * (n / 32.0) / (per_iter["update_centers_ms"] * 1e-3) / 1e12
-        roofs["update_centers"]["bf16_mfma"] = {"issued_TFLOPs": round(mf, 1), "peak": 2500.0, "frac": round(mf / 2500.0, 4)}
-    if "encode" in roofs:
-        # the assignment step is the split encode kernel: its products run as a FILTER on the bf16 matrix cores (3 K = 16 MFMAs per
-        # 32 x 32 tile at sub = 16), so it is priced by the bf16 work it issues against the bf16 peak; the f32-equivalent figure
-        # (2 d h flop per vector against the f32 matrix peak, SURVEY 8d's yardstick) rides along and may pass 1
-        bf = 2.0 * 16 * 256 * (2 if d // m <= 8 else 3) * m * n / (per_iter["encode_ms"] * 1e-3) / 1e12
-        f32eq = roofs["encode"]
-        roofs["encode"] = {"bound": "mfma", "achieved": round(bf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(bf / 2500.0, 4),
-                           "dtype": "bf16 (filter) + f32 VALU re-evaluation of the candidates; the VALU epilogue binds",
-                           "f32_equivalent": {"achieved": f32eq["achieved"], "peak": f32eq["peak"], "frac": f32eq["frac"]}}
-    dev_phases = {k: v for k, v in per_iter.items() if k not in ("svd_ms", "converge_ms") and k not in once}
-    dom = max(dev_phases, key=dev_phases.get)[:-3] if dev_phases else None
-    roof = dict(roofs.get(dom, {}), kernel=dom, traffic=None, per_phase=roofs,
-                note="the dominant throughput phase of an iteration; svd_ms is the d x d polar factor on the device (scaled "
-                     "Newton-Schulz, %.1f steps of two grid-synchronised d^3 products in double per iteration: latency-bound, "
-                     "no roof applies)" % (prof["ns_steps"] / iters)) if dom else None
-    # CPU baseline: the numpy/oracle restatement of the same loop (oracle/train_oracle.py) on a bounded sample
-    cpu = None
-    if not a.no_cpu:
-        from oracle import oracle, train_oracle as to
-        ns = min(n, 100_000)
-        Xs = X[:ns]
-        off = to.offsets(d, m)
-        rngc = np.random.default_rng(0)
-        C0 = [Xs[rngc.choice(ns, h, replace=False)][:, off[i]:off[i + 1]].copy() for i in range(m)]
-        t0 = time.perf_counter()
+    if a.dump_outputs:
+        # what the timed call returned: C (and R), the codes (a fixed sample of rows when large) and the objective / error
+        C, B = out[0], out[1]
+        rows = dump_rows(B.shape[0], B.shape[1] * 8 + 8)
+        extra = [("R", out[2]), ("objective", out[3])] if opq else [("error", np.array([out[2]]))]
+        dump_outputs(a.dump_outputs, [("codebooks", np.concatenate([np.asarray(c, dtype=np.float32).reshape(-1) for c in C])),
+                                      ("codes", B[rows]), ("code_rows", rows)] + extra)
+    fine = per_iter = roof = cpu = obj = None
+    if a.full:
+        rq.set_tuning("TRAIN_PROFILE", 1)
+        try:
+            run(niter)
+            fine = _lib.train_profile()
+        finally:
+            rq.set_tuning("TRAIN_PROFILE", 0)
+        fi = max(1.0, fine["iterations"])
+        per_iter = {k: round(fine[k] / fi, 4) for k in ("qerror_ms", "gram_ms", "svd_ms", "rotate_ms", "update_centers_ms", "encode_ms",
+                                                        "reconstruct_ms", "converge_ms") if fine[k] > 0}
+        # (train_pq: qerror / reconstruct run ONCE after the loop; their entries are that one call's time / iterations)
+        # every device phase of the LOOP against its own roof (algorithmic bytes / flops per iteration, SURVEY 8d's style).  Phases
+        # that run once after the loop (train_pq: the final qerror / reconstruct) are not loop phases and get no roof.
+        GB = 1e9
+        once = set() if opq else {"qerror_ms", "reconstruct_ms"}
+        shapes = {"rotate_ms": ("mfma", 2.0 * d * d * n), "gram_ms": ("mfma", 2.0 * d * d * n), "encode_ms": ("mfma", 2.0 * d * h * n),
+                  "update_centers_ms": ("hbm", (4.0 * d + m) * n), "reconstruct_ms": ("hbm", (4.0 * d + m) * n),
+                  # qerror: X and the n x d reconstruction, or X and the codes when CB is gathered inside the kernel (no reconstruct phase)
+                  "qerror_ms": ("hbm", (8.0 * d if "reconstruct_ms" in per_iter else 4.0 * d + m) * n)}
+        roofs = {}
+        for k, (bound, work) in shapes.items():
+            if k not in per_iter or k in once:
+                continue
+            t = per_iter[k] * 1e-3
+            if bound == "mfma":
+                ach = work / t / 1e12
+                roofs[k[:-3]] = {"bound": "mfma", "achieved": round(ach, 2), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / FP32_PEAK_TFLOPS, 4)}
+            else:
+                ach = work / t / GB
+                roofs[k[:-3]] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4)}
+        if "update_centers" in roofs:
+            # the segment sums run as one-hot products on the bf16 matrix cores (csrc/rq_train.hip: centers_mfma_kernel): 4 MFMAs
+            # of 16 x 16 x 32 per (32 rows, 16-dimension block, 16-code tile); the HBM roof above is the algorithmic one
+            units = sum((sz + 15) // 16 for sz in [d // m + (1 if i < d % m else 0) for i in range(m)])
+            mf = 4 * 2.0 * 16 * 16 * 32 * ((h + 15) // 16) * units * (n / 32.0) / (per_iter["update_centers_ms"] * 1e-3) / 1e12
+            roofs["update_centers"]["bf16_mfma"] = {"issued_TFLOPs": round(mf, 1), "peak": 2500.0, "frac": round(mf / 2500.0, 4)}
+        if "encode" in roofs:
+            # the assignment step is the split encode kernel: its products run as a FILTER on the bf16 matrix cores (3 K = 16 MFMAs per
+            # 32 x 32 tile at sub = 16), so it is priced by the bf16 work it issues against the bf16 peak; the f32-equivalent figure
+            # (2 d h flop per vector against the f32 matrix peak, SURVEY 8d's yardstick) rides along and may pass 1
+            bf = 2.0 * 16 * 256 * (2 if d // m <= 8 else 3) * m * n / (per_iter["encode_ms"] * 1e-3) / 1e12
+            f32eq = roofs["encode"]
+            roofs["encode"] = {"bound": "mfma", "achieved": round(bf, 1), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(bf / 2500.0, 4),
+                               "dtype": "bf16 (filter) + f32 VALU re-evaluation of the candidates; the VALU epilogue binds",
+                               "f32_equivalent": {"achieved": f32eq["achieved"], "peak": f32eq["peak"], "frac": f32eq["frac"]}}
+        dev_phases = {k: v for k, v in per_iter.items() if k not in ("svd_ms", "converge_ms") and k not in once}
+        dom = max(dev_phases, key=dev_phases.get)[:-3] if dev_phases else None
+        roof = dict(roofs.get(dom, {}), kernel=dom, traffic=None, per_phase=roofs,
+                    note="the dominant throughput phase of an iteration; svd_ms is the d x d polar factor on the device (scaled "
+                         "Newton-Schulz, %.1f steps of two grid-synchronised d^3 products in double per iteration: latency-bound, "
+                         "no roof applies)" % (prof["ns_steps"] / iters)) if dom else None
+        # CPU baseline: the numpy/oracle restatement of the same loop (oracle/train_oracle.py) on a bounded sample
+        cpu = None
+        if not a.no_cpu:
+            from oracle import oracle, train_oracle as to
+            ns = min(n, 100_000)
+            Xs = X[:ns]
+            off = to.offsets(d, m)
+            rngc = np.random.default_rng(0)
+            C0 = [Xs[rngc.choice(ns, h, replace=False)][:, off[i]:off[i + 1]].copy() for i in range(m)]
+            t0 = time.perf_counter()
+            if opq:
+                to.train_opq(Xs, m, h, 1, np.eye(d, dtype=np.float32), C0, fast=True)      # niter = 1 -> 2 loop iterations
+                its = 2
+            else:
+                codes = oracle.encode_pq(Xs, np.concatenate([c.reshape(-1) for c in C0]), m, h)
+                C1 = to.update_centers_fast(C0, Xs, codes, off, h)
+                oracle.encode_pq(Xs, np.concatenate([c.reshape(-1) for c in C1]), m, h)
+                its = 2
+            dt = time.perf_counter() - t0
+            ms_it = dt / its * 1e3 * (n / ns)
+            cpu = {"value": round(n / (ms_it * 1e-3), 1), "unit": "vectors x iterations / s", "cores": os.cpu_count() or 1, "kind": "port",
+                   "ms_per_iteration_scaled": round(ms_it, 1),
+                   "sample": "%d iterations of oracle/train_oracle.py (numpy + the C oracle's encode, all host cores) on the first %d of the %d "
+                             "vectors (%.1f s), time scaled by %g" % (its, ns, n, dt, n / ns)}
+        obj = None
         if opq:
-            to.train_opq(Xs, m, h, 1, np.eye(d, dtype=np.float32), C0, fast=True)      # niter = 1 -> 2 loop iterations
-            its = 2
-        else:
-            codes = oracle.encode_pq(Xs, np.concatenate([c.reshape(-1) for c in C0]), m, h)
-            C1 = to.update_centers_fast(C0, Xs, codes, off, h)
-            oracle.encode_pq(Xs, np.concatenate([c.reshape(-1) for c in C1]), m, h)
-            its = 2
-        dt = time.perf_counter() - t0
-        ms_it = dt / its * 1e3 * (n / ns)
-        cpu = {"value": round(n / (ms_it * 1e-3), 1), "unit": "vectors x iterations / s", "cores": os.cpu_count() or 1, "kind": "port",
-               "ms_per_iteration_scaled": round(ms_it, 1),
-               "sample": "%d iterations of oracle/train_oracle.py (numpy + the C oracle's encode, all host cores) on the first %d of the %d "
-                         "vectors (%.1f s), time scaled by %g" % (its, ns, n, dt, n / ns)}
-    obj = None
-    if opq:
-        o = np.asarray(out[3], dtype=np.float64)
-        obj = {"first": float(o[0]), "last": float(o[-1]), "monotone_non_increasing": bool((np.diff(o) <= 1e-3 * o[:-1]).all())}
+            o = np.asarray(out[3], dtype=np.float64)
+            obj = {"first": float(o[0]), "last": float(o[-1]), "monotone_non_increasing": bool((np.diff(o) <= 1e-3 * o[:-1]).all())}
     line = {
         "metric": "%s training throughput (vectors x iterations / s)" % a.workload, "value": round(n / (ms_step * 1e-3), 1),
         "unit": "vectors x iterations / s", "n_gpus": 1, "steps": int(iters), "warmup": a.warmup, "ms_per_step": round(ms_step, 4),
@@ -298,11 +364,11 @@ def train_bench(a):
                    "n": n, "d": d, "m": m, "h": h, "generator": "splitmix64 (rayuela.jl_amd/synth.py)", "parallelism": "single GPU"},
         "per_iteration_ms": per_iter,
         "outside_the_loop_ms": {"x_upload": round(prof["h2d_ms"] or fine["h2d_ms"], 2), "init": round(fine["init_ms"], 2),
-                                "results_download": round(fine["d2h_ms"], 2), "whole_call_wall": round(wall * 1e3, 1)},
-        "profiled_loop_ms_per_step": round(fine["loop_ms"] / fi, 4),
+                                "results_download": round(fine["d2h_ms"], 2), "whole_call_wall": round(wall * 1e3, 1)} if a.full else None,
+        "profiled_loop_ms_per_step": round(fine["loop_ms"] / fi, 4) if a.full else None,
         "polar_factor": {"newton_schulz_steps_per_iteration": round(prof["ns_steps"] / iters, 2),
                          "jacobi_sweeps_per_iteration": round(prof["jacobi_sweeps"] / iters, 2),
-                         "host_fallbacks": int(prof["host_polar"])} if opq else None,
+                         "host_fallbacks": int(prof["host_polar"])} if opq and a.full else None,
         "objective": obj,
         "roofline": roof, "cpu_baseline": cpu,
     }
@@ -415,7 +481,10 @@ def main():
             enc = lambda: rqd.encode_opq(X, R, Ccat, m, h, out=codes)   # noqa: E731
         else:
             enc = lambda: rqd.encode_pq(X, Ccat, m, h, out=codes)       # noqa: E731
-        enc_ms, _ = timed(enc, a.steps, a.warmup, barrier)
+        if a.full:
+            enc_ms, _ = timed(enc, a.steps, a.warmup, barrier)
+        else:
+            enc()          # the codes the scan reads (timed in its own bracket with --full)
 
     # ---- (a) ADC scan + top-k over the whole base ------------------------------------------------------------------
     res = {}
@@ -451,6 +520,8 @@ def main():
         def scan():
             res["r"] = ix.search(Qs, K)
     scan_ms, scan_wall = timed(scan, a.steps, a.warmup, barrier)
+    if a.dump_outputs and rank == 0:
+        dump_scan(a.dump_outputs, *res["r"])          # the answer of the last timed step
     ix_info = ix_lib.info() if ix_lib is not None else None
     if os.environ.get("RQ_SCAN_STATS") and rank == 0:      # development aid: the scan kernel's phase / filter counters
         from rayuela_jl_amd import _lib
@@ -464,7 +535,7 @@ def main():
     kern_ms = None
     kern_base = None
     order_info = None
-    if not a.inproc:
+    if a.full and not a.inproc:
         kl = min(K, n_local)
         kout = torch.empty((nq, kl), dtype=torch.int64, device=device)
         ks = max(2, min(a.steps, 10))
@@ -615,29 +686,31 @@ def main():
                   "roofline": enc_roof}
 
     # ---- checks on the returned answer (size-independent) ----------------------------------------------------------
-    rd, ri = res["r"]
-    rd_h = rd.cpu().numpy() if hasattr(rd, "cpu") else rd
-    ri_h = (ri.cpu().numpy() if hasattr(ri, "cpu") else ri).view(np.uint32)
-    checks = {"ascending": bool((np.diff(rd_h, axis=1) >= 0).all()), "ids_in_range": bool(ri_h.max() < n),
-              "ids_unique_per_query": bool(all(len(np.unique(ri_h[q])) == K for q in range(min(nq, 64))))}
-    if big:
-        # regenerate the returned rows' codes from the hash (no device read) and redo their ADC sums on the host
-        from oracle import oracle
-        nchk = min(nq, 32)
-        qh = Qs[:nchk].cpu().numpy()
-        lut = np.stack([oracle.adc_lut(np.stack(C), qh[q]) for q in range(nchk)])       # [nchk][m][256], f32 like the reference
-        ids64 = ri_h[:nchk].astype(np.uint64)
-        e = ids64[:, :, None] * np.uint64(m) + np.arange(m, dtype=np.uint64)[None, None, :]
-        cb = (synth.splitmix64(e ^ np.uint64(synth.SEED_BASE)) >> np.uint64(56)).astype(np.int64)
-        acc = np.take_along_axis(lut[:, 0, :], cb[:, :, 0], axis=1)
-        for kk in range(1, m):                                                          # sequential f32 sum, :85-87
-            acc = acc + np.take_along_axis(lut[:, kk, :], cb[:, :, kk], axis=1)
-        checks["returned_dists_recomputed_bit_exact"] = bool(np.array_equal(acc.view(np.uint32), rd_h[:nchk].view(np.uint32)))
-        checks["queries_checked"] = nchk
+    checks = None
+    if a.full:
+        rd, ri = res["r"]
+        rd_h = rd.cpu().numpy() if hasattr(rd, "cpu") else rd
+        ri_h = (ri.cpu().numpy() if hasattr(ri, "cpu") else ri).view(np.uint32)
+        checks = {"ascending": bool((np.diff(rd_h, axis=1) >= 0).all()), "ids_in_range": bool(ri_h.max() < n),
+                  "ids_unique_per_query": bool(all(len(np.unique(ri_h[q])) == K for q in range(min(nq, 64))))}
+        if big:
+            # regenerate the returned rows' codes from the hash (no device read) and redo their ADC sums on the host
+            from oracle import oracle
+            nchk = min(nq, 32)
+            qh = Qs[:nchk].cpu().numpy()
+            lut = np.stack([oracle.adc_lut(np.stack(C), qh[q]) for q in range(nchk)])       # [nchk][m][256], f32 like the reference
+            ids64 = ri_h[:nchk].astype(np.uint64)
+            e = ids64[:, :, None] * np.uint64(m) + np.arange(m, dtype=np.uint64)[None, None, :]
+            cb = (synth.splitmix64(e ^ np.uint64(synth.SEED_BASE)) >> np.uint64(56)).astype(np.int64)
+            acc = np.take_along_axis(lut[:, 0, :], cb[:, :, 0], axis=1)
+            for kk in range(1, m):                                                          # sequential f32 sum, :85-87
+                acc = acc + np.take_along_axis(lut[:, kk, :], cb[:, :, kk], axis=1)
+            checks["returned_dists_recomputed_bit_exact"] = bool(np.array_equal(acc.view(np.uint32), rd_h[:nchk].view(np.uint32)))
+            checks["queries_checked"] = nchk
 
     # ---- recall (sanity + parity: ids are bit-exact, so recall is identical by construction) ------------------------
     recall = None
-    if world == 1 and not a.inproc and X is not None:
+    if a.full and world == 1 and not a.inproc and X is not None:
         nrec = min(nq, 1000)
         best = torch.full((nrec,), float("inf"), device=device)
         arg = torch.zeros((nrec,), dtype=torch.long, device=device)
@@ -655,7 +728,7 @@ def main():
 
     # ---- CPU baseline on this box's host cores (rank 0, N = 1 only) -----------------------------------------------
     cpu = None
-    if ngpu == 1 and not a.no_cpu:
+    if a.full and ngpu == 1 and not a.no_cpu:
         from oracle import oracle
         nb = min(n, 20_000_000)            # sift1b: the reference is timed on the first 2e7 rows of the base
         codes_h = (codes[:nb] if codes is not None else rqd.synth_codes(nb, m, synth.SEED_BASE, device=device)).cpu().numpy()
@@ -750,7 +823,7 @@ def main():
 
     # ---- what a Julia ccall pays: the same calls on HOST arrays (PCIe in both directions inside the timed region) ----
     host = None
-    if ngpu == 1 and X is not None and not a.no_host and not a.inproc:
+    if a.full and ngpu == 1 and X is not None and not a.no_host and not a.inproc:
         Xh, Qh = X.cpu().numpy(), Q.cpu().numpy()
         Rh = None if R is None else R.cpu().numpy()
         best_e = best_s = 1e30
@@ -776,7 +849,7 @@ def main():
 
     # ---- sift1b at N > 1: the same workload on ONE GPU (rank 0 alone), so the line carries its own scaling anchor ---
     ref1 = None
-    if big and ngpu > 1 and not a.no_ref1 and n * m <= 64 * (1 << 30):
+    if a.full and big and ngpu > 1 and not a.no_ref1 and n * m <= 64 * (1 << 30):
         try:
             if ix_lib is not None:
                 ix_lib.close()
@@ -800,7 +873,7 @@ def main():
     # series of `bench.py --gpus 1, 2, 4, 8` runs has its single-GPU anchor in the N = 1 line (the headline `value`
     # stays BASELINE's SIFT1M-shape metric; efficiency over N is  value(N) / (N * scale_anchor_1gpu.value)) ----------
     anchor = None
-    if ngpu == 1 and a.workload == "auto" and not a.inproc and not a.no_ref1 and a.n == 0 and a.k == 0 and a.nq == 0 and m == 8:
+    if a.full and ngpu == 1 and a.workload == "auto" and not a.inproc and not a.no_ref1 and a.n == 0 and a.k == 0 and a.nq == 0 and m == 8:
         try:
             nA, nqA, kA = 1_000_000_000, 1024, 100
             whole = rqd.synth_codes(nA, m, synth.SEED_BASE, row0=0, device=device)
@@ -828,7 +901,7 @@ def main():
     # 0) -- the path a Julia session takes (host code stays Julia: julia/RayuelaHIP.jl holds one handle), timed on the wall
     # clock after the torch.distributed ranks are done with the GPUs.  `value` above is the one-process-per-GPU harness.
     inproc_leg = None
-    if world > 1:
+    if a.full and world > 1:
         try:
             ndev = torch.cuda.device_count()
             devs = [i % ndev for i in range(world)] if debug_gloo else list(range(world))
@@ -889,7 +962,7 @@ def main():
         "checks": checks,
         "host_path": host,
         "row_order": order_info if (world == 1 and not big) else
-                     ({"index_prepare_ms_once": round(ix.order_ms, 3)} if (not a.inproc and ix.order_ms is not None) else None),
+                     ({"index_prepare_ms_once": round(ix.order_ms, 3)} if (a.full and not a.inproc and ix.order_ms is not None) else None),
         "same_workload_1gpu": ref1,
         "inproc": inproc_leg,
         "scale_anchor_1gpu": anchor,

@@ -171,8 +171,26 @@ def recall_case():
     print("recall_tiny", recall)
 
 
+def live_ref_case():
+    """live_ref.npz: the compiled reference's answers for the generated inputs of tests/test_oracle_scan.py and
+    tests/test_oracle_aq.py (checked against the live reference too wherever oracle/_ref is built)"""
+    import test_oracle_aq as ta
+    import test_oracle_scan as ts
+    out = {}
+    for key, codes, centers, queries, K in [ts.live_case(*c) for c in ts.LIVE_CASES] + [ts.chunked_case()]:
+        out[key + "_d"], out[key + "_i"] = oracle.ref_linscan_aqd_query(codes, centers, queries, K)
+    for key, fn, args in ta.aq_live_case(oracle):
+        out[key + "_d"], out[key + "_i"] = fn(*args, use_ref=True)
+    np.savez_compressed(os.path.join(OUT, "live_ref.npz"), **out)
+    print("live_ref", sorted(out))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) >= 2 and sys.argv[1] == "live":
+        assert oracle.ref_available() and oracle.ref_aq_available(), "build oracle/_ref first: make -C oracle ref"
+        live_ref_case()
+        sys.exit(0)
     if len(sys.argv) < 2 or sys.argv[1] == "rvq":
         rvq_case("rvq_sift_mini", 600, 128, 4, 256, "sift")
         rvq_case("rvq_deep_mini", 500, 96, 3, 100, "deep")
@@ -192,3 +210,4 @@ if __name__ == "__main__":
     assert oracle.ref_aq_available(), "make -C oracle ref"
     aq_case("aq_mini_m8", 3000, 8, 32, 6, [1, 100, 1000], seed=41)
     aq_case("aq_mini_m4", 1500, 4, 16, 5, [10, 1500], seed=42)
+    live_ref_case()

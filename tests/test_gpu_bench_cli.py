@@ -11,6 +11,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -48,7 +49,7 @@ def test_driver_command_shape_one_process_per_gpu(ngpu, rows):
     answer identical to one scan of the whole base on one GPU.  N = 8 is the driver's SCALE command with eight ranks on
     the one device of the test box (1e6-row shards: above the ordering threshold, so every rank orders its shard)."""
     nq, k = 64, 100
-    line = _run(["--gpus", str(ngpu), "--rows", str(rows), "--nq", str(nq), "--k", str(k), "--steps", "2", "--warmup", "1"],
+    line = _run(["--full", "--gpus", str(ngpu), "--rows", str(rows), "--nq", str(nq), "--k", str(k), "--steps", "2", "--warmup", "1"],
                 {"RQ_BENCH_BACKEND": "gloo"})
     _common(line, ngpu, rows, nq, k)
     assert line["debug_backend"] and "gloo" in line["debug_backend"]      # flagged as not-a-measurement
@@ -69,7 +70,7 @@ def test_driver_command_shape_one_process_per_gpu(ngpu, rows):
 def test_inproc_logical_shards_through_the_library_index():
     """`--inproc --devices 0,0,0,0`: the in-library sharded index (rq_index_create_sharded) with four logical shards."""
     rows, nq, k = 4_000_000, 64, 100
-    line = _run(["--inproc", "--devices", "0,0,0,0", "--workload", "sift1b", "--rows", str(rows), "--nq", str(nq), "--k", str(k),
+    line = _run(["--full", "--inproc", "--devices", "0,0,0,0", "--workload", "sift1b", "--rows", str(rows), "--nq", str(nq), "--k", str(k),
                  "--steps", "2", "--warmup", "1"])
     _common(line, 4, rows, nq, k)
     assert line["logical_shards"]
@@ -84,7 +85,7 @@ def test_inproc_eight_logical_shards_over_the_rccl_transport():
     rank 0 (= the same device) through the library's ncclCommInitAll clique and ONE grouped ncclSend / ncclRecv -- the
     transport an 8-GPU node uses, carrying 7 lists (VERDICT r3 Next #7)."""
     rows, nq, k = 8_000_000, 64, 100
-    line = _run(["--inproc", "--devices", "0,0,0,0,0,0,0,0", "--workload", "sift1b", "--rows", str(rows), "--nq", str(nq),
+    line = _run(["--full", "--inproc", "--devices", "0,0,0,0,0,0,0,0", "--workload", "sift1b", "--rows", str(rows), "--nq", str(nq),
                  "--k", str(k), "--steps", "2", "--warmup", "1"], {"RQ_EXCHANGE_SELFTEST": "1"})
     _common(line, 8, rows, nq, k)
     assert "rq_index_create_sharded over 8 shard(s)" in line["config"]["parallelism"]
@@ -103,10 +104,10 @@ def test_world_size_mismatch_is_an_error_not_a_silent_single_gpu_run():
 
 
 def test_default_command_shape_single_gpu_contract():
-    """`python bench.py --steps K --warmup W` at N = 1 (the driver's BENCH run, shrunk): ONE JSON line carrying the contract's
+    """`python bench.py --full --steps K --warmup W` at N = 1 (the driver's BENCH run, shrunk): ONE JSON line carrying the contract's
     fields plus `roofline` and `cpu_baseline`, the GPU answer equal to the compiled reference (or the oracle port) bit for
     bit, codes equal to the oracle's."""
-    line = _run(["--rows", "200000", "--nq", "512", "--k", "100", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
+    line = _run(["--full", "--rows", "200000", "--nq", "512", "--k", "100", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line, key
@@ -137,3 +138,25 @@ def test_default_command_shape_single_gpu_contract():
     assert line["checks"]["ascending"] and line["checks"]["ids_unique_per_query"]
     assert line["host_path"]["same_answer_as_resident"] is True
     assert line["recall"]["r@1"] > 0.2
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_answer(tmp_path):
+    """A plain `python bench.py --steps K --warmup W --dump-outputs DIR`: the headline fields, the other measurements null, and
+    the answer of the last timed step as .npy files; a second run with the same arguments writes the same arrays."""
+    rows, nq, k = 200_000, 512, 100
+    outs = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        line = _run(["--rows", str(rows), "--nq", str(nq), "--k", str(k), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "queries/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["metric"] == "ADC queries/sec (linscan_pq, exact top-%d)" % k
+        for key in ("encode", "roofline", "cpu_baseline", "recall", "checks", "host_path", "row_order", "scale_anchor_1gpu"):
+            assert line[key] is None, key
+        dists, ids, qrows = (np.load(str(out / (name + ".npy"))) for name in ("dists", "ids", "query_rows"))
+        assert dists.dtype == np.float32 and ids.dtype == np.float64 and dists.shape == ids.shape == (nq, k)
+        assert np.array_equal(qrows, np.arange(nq))
+        assert (np.diff(dists, axis=1) >= 0).all() and ids.min() >= 0 and ids.max() < rows
+        assert all(len(np.unique(ids[q])) == k for q in range(nq))
+        outs.append((dists, ids))
+    assert np.array_equal(outs[0][0].view(np.uint32), outs[1][0].view(np.uint32)) and np.array_equal(outs[0][1], outs[1][1])

@@ -2,7 +2,7 @@
 # (and optionally 1e9 rows).  usage (GPU box): bash tools/pace_sweep.sh [rows]   -> gpurun_out/pace/summary.md
 R=$PWD; O=$R/gpurun_out/pace; mkdir -p $O
 ROWS=${1:-125000000}
-B="--workload sift1b --rows $ROWS --no-cpu --no-ab --no-ref1 --steps 3 --warmup 1"
+B="--full --workload sift1b --rows $ROWS --no-cpu --no-ab --no-ref1 --steps 3 --warmup 1"
 echo "| setting | ms per step (events, un-profiled) | FETCH_SIZE x 2 (GB / launch) | WRITE_SIZE (GB / launch) | x code bytes |" > $O/summary.md
 echo "|---|---|---|---|---|" >> $O/summary.md
 for cfg in "off:RQ_SCAN_PACE=0" "lag0:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=0" "lag1:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=1" "lag2:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=2" "lag4:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=4" "lag8:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=8" "lag2v4:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=2 RQ_SCAN_PACE_VOTES=4" "lag2_slack0:RQ_SCAN_PACE=1 RQ_SCAN_PACE_LAG=2 RQ_SCAN_XCD_SLACK=0" $PACE_EXTRA; do
