@@ -216,8 +216,8 @@ int rq_dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *c
 int rq_scan_row_width(int m);
 /* host-only (tests): the key of that order for n rows x m bytes -- out[0..7] bits per leading code byte, [8] total,
  * [9] rows per lane group, [10] rows per shuffle granule, [11] padded row width; cap >= 12.  With cap >= 14 also [12] the number
- * of tables the greedy balance deals the rows of a sort bucket over (round 6: 8- and 16-byte rows, 1e5 ... 3e6 rows; the key then
- * covers one table less; 0: plain sort) and [13] the wavefronts per workgroup that run it. */
+ * of tables the greedy balance deals the rows of a sort bucket over (round 6: 8- and 16-byte rows from ~7.9e5 rows = ~7.4e5 sorted
+ * rows up to ~6e6 (m = 8) / ~4.4e6 (m = 16); the key then covers one table less; 0: plain sort -- the same predicate as the launch) and [13] the wavefronts per workgroup that run it. */
 int rq_order_plan(int64_t n, int m, int *out, int cap);
 int64_t rq_order_bytes(int64_t n, int m);
 int rq_dev_order_rows(void *ordered, const uint8_t **codes_out, const uint32_t **perm_out, const uint8_t *codes,
@@ -360,6 +360,9 @@ void rq_host_free(void *p);
  *   others (SCAN_SAMPLE, SCAN_SRANK_MUL, SCAN_SLACK, SCAN_SS_MIN_K, SCAN_TAIL_SLICES, SCAN_MIN_ROWS, ENC_DIRECT,
  *   ROT_V2, HOST_OVERLAP, SCAN_STATS) are experiment switches documented where they are read */
 int rq_set_tuning(const char *key, int value);
+/* Drops the value rq_set_tuning stored for `key` (NULL: for every key): the knob reads env RQ_<KEY> again, else its code default.
+ * Storing the default is NOT the same -- it hides the environment, and a few knobs tell "unset" from any stored value. */
+int rq_reset_tuning(const char *key);
 /* Diagnostics (pure host code): 1 if a raw-pointer PQ scan of n rows (m = 8 wide), nq queries and k neighbours puts a scratch copy
  * of the base into bank-aware row order inside the call (csrc/rq_order.hip: from ORDER_MIN_NQ queries on, below ORDER_MAX_K
  * neighbours, ORDER_MIN_ROWS rows up) -- 2 if that order is also BALANCED (the greedy pass of rq_order.hip, from ORDER_GREEDY_MIN_NQ

@@ -5,7 +5,7 @@ defaults and index bases as src/PQ.jl, src/OPQ.jl, src/Linscan.jl), implemented 
 the C ABI of librayuela_hip.so (include/rayuela_hip.h).  The Julia drop-in files that bind the same
 ABI with `ccall` live in julia/.  No CPU fallback exists: without the HIP library every call raises.
 """
-from ._lib import RayuelaHipError, lib, lib_path, set_tuning, last_timing  # noqa: F401
+from ._lib import RayuelaHipError, lib, lib_path, set_tuning, reset_tuning, last_timing  # noqa: F401
 from .utils import splitarray, cat_codebooks  # noqa: F401
 from .xvecs import fvecs_read, ivecs_read, bvecs_read, fvecs_write, ivecs_write  # noqa: F401
 from .PQ import quantize_pq, quantize_pq_u8  # noqa: F401

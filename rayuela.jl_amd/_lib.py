@@ -90,6 +90,7 @@ SIGNATURES = {
     "rq_index_search": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
     "rq_index_destroy": (None, [_vp]),
     "rq_set_tuning": (_i32, [C.c_char_p, _i32]),
+    "rq_reset_tuning": (_i32, [C.c_char_p]),
     "rq_scan_stats": (_i32, [_vp]),
     "rq_scan_orders_in_call": (_i32, [_i64, _i64, _i32]),
     "rq_scan_finish_stats": (_i32, [_vp]),
@@ -135,6 +136,12 @@ def check(status):
 
 def set_tuning(key, value):
     check(lib().rq_set_tuning(key.encode(), int(value)))
+
+
+def reset_tuning(key=None):
+    """Forget what set_tuning stored for `key` (None: every key): the knob reads RQ_<KEY> from the environment again, else
+    the library's default."""
+    check(lib().rq_reset_tuning(None if key is None else key.encode()))
 
 
 def scan_plan(n, nq, m, d, k, num_cu=256):

@@ -44,17 +44,17 @@ void forgive_oom() {
   (void)hipGetLastError();
 }
 
-// ---- tuning knobs: env RQ_<KEY>, or rq_set_tuning() ---------------------------------------------
-struct Knob { char key[32]; int value; };
-static Knob g_knobs[64];
-static int g_nknobs = 0;
+// ---- tuning knobs: rq_set_tuning() over env RQ_<KEY> over the code default; rq_reset_tuning() drops a set value --------
+struct Knob { std::string key; int value; };
+// no cap: one entry per key ever set (the code reads ~70); never destroyed, so tuning() stays safe in exit-time teardown
+static std::vector<Knob> &g_knobs = *new std::vector<Knob>();
 static std::mutex g_mu;
 
 int tuning(const char *key, int dflt) {
   {
     std::lock_guard<std::mutex> lk(g_mu);
-    for (int i = 0; i < g_nknobs; ++i)
-      if (!strcmp(g_knobs[i].key, key)) return g_knobs[i].value;
+    for (const Knob &kb : g_knobs)
+      if (kb.key == key) return kb.value;
   }
   std::string env = std::string("RQ_") + key;
   const char *v = getenv(env.c_str());
@@ -804,13 +804,19 @@ int rq_set_device(int device) {
 }
 
 int rq_set_tuning(const char *key, int value) {
+  if (!key || !*key) return fail(RQ_EINVAL, "rq_set_tuning: empty key");
   std::lock_guard<std::mutex> lk(g_mu);
-  for (int i = 0; i < g_nknobs; ++i)
-    if (!strcmp(g_knobs[i].key, key)) { g_knobs[i].value = value; return RQ_OK; }
-  if (g_nknobs >= 64) return fail(RQ_EINVAL, "too many tuning keys");
-  strncpy(g_knobs[g_nknobs].key, key, 31);
-  g_knobs[g_nknobs].key[31] = 0;
-  g_knobs[g_nknobs++].value = value;
+  for (Knob &kb : g_knobs)
+    if (kb.key == key) { kb.value = value; return RQ_OK; }
+  g_knobs.push_back(Knob{key, value});
+  return RQ_OK;
+}
+
+int rq_reset_tuning(const char *key) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!key) { g_knobs.clear(); return RQ_OK; }
+  for (size_t i = 0; i < g_knobs.size(); ++i)
+    if (g_knobs[i].key == key) { g_knobs.erase(g_knobs.begin() + i); break; }
   return RQ_OK;
 }
 
@@ -1318,9 +1324,8 @@ int rq_order_plan(int64_t n, int m, int *out, int cap) {
   for (int c = 0; c < 8; ++c) out[c] = nb[c];
   out[8] = total; out[9] = ot.group; out[10] = ot.gran; out[11] = mp;
   if (cap >= 14) {          // [12] tables the greedy balance deals over (0: plain sort), [13] wavefronts per workgroup that balance
-    uint32_t gp[4] = {0, 0, 0, 0};
-    const int64_t ns = n - order_sample_rows(n, ot.blk, nullptr);
-    const bool on = total > 0 && order_greedy_plan(ns, mp, total + 3, gp) && tuning("ORDER_BITS", 0) <= 0;
+    uint32_t gp[4];
+    const bool on = order_greedy_runs(n, mp, ot, total, gp);     // (order_rows_launch asks the same)
     out[12] = on ? (int)gp[0] : 0;
     out[13] = on ? (int)gp[1] : 0;
   }

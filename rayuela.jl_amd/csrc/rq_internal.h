@@ -120,6 +120,7 @@ struct OrderTiling { int rpt, gran, group, cbits, blk; };                    // 
 void scan_order_tiling(int mp, OrderTiling *t);
 void order_set_call_queries(int64_t nq);   // > 0: the ordering that follows serves ONE scan of nq queries (greedy balance only if it pays)
 bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4]);
+bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4]);  // the launch's balance predicate
 int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]);  // key layout; returns the total bits (0: no ordering)
 size_t order_scratch_bytes(int64_t n, int total_bits);
 int order_sample_stride();                                               // ORDER_SAMPLE_STRIDE (16; < 2: no sample blocks)

@@ -531,6 +531,19 @@ int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]) {
   return total;
 }
 
+// Does order_rows_launch balance (order_fine_greedy_kernel) a base of n rows whose key order_key_bits made `total` bits long?  Only
+// where order_key_bits gave up a table's bits for it -- the full budget of the sorted rows, not `total`, decides.  The one
+// predicate of the launch and of rq_order_plan.  gp: order_greedy_plan's out.
+bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4]) {
+  gp[0] = gp[1] = gp[2] = gp[3] = 0;
+  if (total <= 0) return false;
+  const int64_t ns = n - order_sample_rows(n, t.blk, nullptr);
+  int budget = tuning("ORDER_BITS", 0);
+  if (budget <= 0) budget = (int)std::floor(std::log2((double)ns / (double)t.group) + 0.5);
+  budget = std::min(budget, 24);
+  return total == budget - 3 && order_greedy_plan(ns, mp, budget, gp);
+}
+
 size_t order_scratch_bytes(int64_t n, int total_bits) {
   const size_t nbins = (size_t)1 << total_bits;
   const size_t ntiles = (nbins + ORDER_SCAN_TILE - 1) / ORDER_SCAN_TILE;
@@ -545,14 +558,8 @@ int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t 
   const int total = order_key_bits(n, mp, t, p.nb);
   if (total <= 0 || total > 24) return fail(RQ_EINVAL, "order_rows: nothing to order (n=%lld)", (long long)n);
   p.gfree = 0; p.gwaves = 0; p.glist = 0;
-  bool greedy_on = false;
-  {   // did order_key_bits shorten the key for the greedy balance?  (same arithmetic: the budget of the sorted rows)
-    const int64_t ns = n - order_sample_rows(n, t.blk, nullptr);
-    int budget = tuning("ORDER_BITS", 0);
-    if (budget <= 0) budget = (int)std::floor(std::log2((double)ns / (double)t.group) + 0.5);
-    budget = std::min(budget, 24);
-    greedy_on = order_greedy_plan(ns, mp, budget, nullptr) && total == budget - 3;
-  }
+  uint32_t gp[4];
+  const bool greedy_on = order_greedy_runs(n, mp, t, total, gp);
   p.src = src; p.dst = dst; p.perm = perm;
   p.n = (uint32_t)n; p.mp = mp;
   p.ncoord = 0;
@@ -586,8 +593,7 @@ int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t 
     RQ_HIP(hipMemsetAsync(q.ctot, 0, 2 * ORDER_COARSE * 4, stream));
     hipLaunchKernelGGL(order_coarse_count_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q);
     hipLaunchKernelGGL(order_coarse_scatter_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q);
-    uint32_t gp[4];
-    if (greedy_on && order_greedy_plan((int64_t)p.nsorted, mp, total + 3, gp)) {
+    if (greedy_on) {
       // the free tables: the last gfree bytes of the row (the key covers the leading ones; a partly covered byte is balanced too)
       p.gfree = (int)gp[0];
       p.gwaves = gp[1]; p.glist = gp[2];

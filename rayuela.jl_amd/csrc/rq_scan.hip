@@ -991,7 +991,9 @@ static void plan_for(ScanPlan &pl, int64_t n, int64_t nq, int d, int K, int num_
   if (slack_i <= 0) slack_i = std::max(std::min(std::max(4 * K, 2048), 16384), K + K / 2);
   const uint32_t slack = (uint32_t)slack_i;
   pl.trigger = (uint32_t)K + slack;
-  pl.sample = (uint32_t)tuning("SCAN_SAMPLE", 16384);
+  // SCAN_SAMPLE: -1 = unset (16384 rows; the retune samples SCAN_SAMPLE_RT), 0 = no sampled threshold, > 0 rules both samples
+  const int sample = tuning("SCAN_SAMPLE", -1);
+  pl.sample = sample < 0 ? 16384u : (uint32_t)sample;
   // + 2048: rows waiting in the pre-filter's queues (< 128 per wavefront) are appended outside their block
   pl.cap = pl.trigger + 2 * Cfg::VP * Cfg::BLK + 2048;
   pl.p2 = next_pow2((uint32_t)K);
@@ -1225,7 +1227,7 @@ int scan_launch(const ScanPlan &pl, float *dists, uint32_t *ids, uint64_t *keys,
   p.cap = pl.cap; p.trigger = pl.trigger; p.p2 = pl.p2; p.scratch_keys = pl.scratch_keys;
   p.sample = pl.sample;
   p.sample_rt = (uint32_t)tuning("SCAN_SAMPLE_RT", 4096);
-  if (tuning("SCAN_SAMPLE", 0) > 0) p.sample_rt = pl.sample;      // an explicit SCAN_SAMPLE rules both
+  if (tuning("SCAN_SAMPLE", -1) > 0) p.sample_rt = pl.sample;     // an explicit SCAN_SAMPLE rules both
   p.srank_mul = (uint32_t)tuning("SCAN_SRANK_MUL", 2);
   p.retune_z = tuning("SCAN_RETUNE_Z", 6);
   p.retune_min_k = tuning("SCAN_RETUNE_MIN_K", 1);

@@ -124,14 +124,11 @@ def test_order_plan_host_logic():
     # of a sort bucket are dealt over its lane groups by the uncovered tables: 12 bits + 4 tables at SIFT1M shape
     p = plan(1_000_000, 8)
     assert p[:8] == [3, 3, 3, 3, 0, 0, 0, 0] and p[8] == 12 and p[9] == 32 and p[11] == 8 and p[12] == 4 and p[13] == 16
-    from rayuela_jl_amd import set_tuning
-    set_tuning("ORDER_GREEDY", 0)
-    try:
+    from switch_table import switches
+    with switches(ORDER_GREEDY=0):
         p = plan(1_000_000, 8)
         assert p[:8] == [3, 3, 3, 3, 3, 0, 0, 0] and p[8] == 15 and p[12] == 0
         assert plan(1_000_000, 16)[:8] == [3, 3, 3, 3, 3, 0, 0, 0]     # m = 16: 5 of 16 tables
-    finally:
-        set_tuning("ORDER_GREEDY", 1)
     p = plan(1_000_000, 16)
     assert p[:8] == [3, 3, 3, 3, 0, 0, 0, 0] and p[12] == 12 and 8 <= p[13] <= 16
     assert plan(1_000_000, 4)[12] == 0                             # 4-byte rows: the key covers every table already

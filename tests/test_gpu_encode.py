@@ -3,6 +3,8 @@ oracle.  Bar: codes bit-exact, rotated vectors bit-exact (the MFMA k-loop is the
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +29,8 @@ def test_quantize_pq_matches_golden(rq, name, waves):
     g = golden(name)
     m, h = int(g["m"]), int(g["h"])
     C = _split(g["C"], g["X"].shape[1], m, h)
-    rq.set_tuning("ENC_WAVES", waves)
-    try:
+    with switches(ENC_WAVES=waves):
         B = rq.quantize_pq(g["X"], C)
-    finally:
-        rq.set_tuning("ENC_WAVES", 16)
     assert B.dtype == np.int16 and B.shape == g["codes"].shape
     assert np.array_equal(B, g["codes"].astype(np.int16) + 1)       # one-based (src/PQ.jl:45-47)
     assert np.array_equal(rq.quantize_pq_u8(g["X"], C), g["codes"])
@@ -144,11 +143,8 @@ def test_host_path_pipelined_chunks_and_device_list(rq, oracle, monkeypatch):
     assert np.array_equal(rq.quantize_pq(X, C), ref.astype(np.int16) + 1)
     assert np.array_equal(rq.quantize_opq(X, R, C), ref_o.astype(np.int16) + 1)
     monkeypatch.delenv("RAYUELA_HIP_DEVICES")
-    rq.set_tuning("HOST_OVERLAP", 0)
-    try:
+    with switches(HOST_OVERLAP=0):
         assert np.array_equal(rq.quantize_pq_u8(X, C), ref)
-    finally:
-        rq.set_tuning("HOST_OVERLAP", 1)
 
 
 def test_resident_dataset_encodes_match_the_host_calls(rq, oracle):
@@ -171,11 +167,8 @@ def _enc_both(rq, oracle, X, C, m, h):
     Ccat = np.concatenate([np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in C])
     ref = oracle.encode_pq(X, Ccat, m, h)
     got = rq.quantize_pq_u8(X, C)
-    rq.set_tuning("ENC_SPLIT", 0)
-    try:
+    with switches(ENC_SPLIT=0):
         old = rq.quantize_pq_u8(X, C)
-    finally:
-        rq.set_tuning("ENC_SPLIT", 1)
     return got, old, ref
 
 
@@ -200,11 +193,8 @@ def test_split_encode_more_sub_quantizers_than_one_launch_holds(rq, oracle, sub)
     cent = rng.integers(0, 24, (64, m * sub)).astype(np.float32)
     X = cent[rng.integers(0, 64, n)] + rng.integers(-2, 3, (n, m * sub)).astype(np.float32)
     C = [np.ascontiguousarray(X[rng.choice(n, h, replace=False)][:, i * sub:(i + 1) * sub]) for i in range(m)]
-    rq.set_tuning("ENC_STATS", 1)
-    try:
+    with switches(ENC_STATS=1):
         got, old, ref = _enc_both(rq, oracle, X, C, m, h)
-    finally:
-        rq.set_tuning("ENC_STATS", 0)
     assert np.array_equal(got, ref) and np.array_equal(old, ref)
 
 
@@ -246,11 +236,8 @@ def test_split_encode_hostile_inputs(rq, oracle, case, waves):
         base = rng.standard_normal((1, m * sub)).astype(np.float32) * 1000
         X = base + rng.standard_normal((n, m * sub)).astype(np.float32)
         C = [base[:, i * sub:(i + 1) * sub] + rng.standard_normal((h, sub)).astype(np.float32) for i in range(m)]
-    rq.set_tuning("ENC_SPLIT_WAVES", waves)
-    try:
+    with switches(ENC_SPLIT_WAVES=waves):
         got, old, ref = _enc_both(rq, oracle, np.ascontiguousarray(X), C, m, h)
-    finally:
-        rq.set_tuning("ENC_SPLIT_WAVES", 0)
     assert np.array_equal(old, ref), case
     assert np.array_equal(got, ref), (case, int((got != ref).sum()))
 
@@ -279,14 +266,11 @@ def test_share_of_pairs_that_take_the_exact_pass(rq):
     from rayuela_jl_amd import device as rqd, _lib
 
     def share(X, Cl, m):
-        rq.set_tuning("ENC_STATS", 1)
-        try:
+        with switches(ENC_STATS=1):
             rqd.encode_pq(torch.from_numpy(X).cuda(), torch.from_numpy(synth.cat_codebooks(Cl)).cuda(), m, 256)
             torch.cuda.synchronize()
             out = (C.c_uint64 * 2)()
             _lib.check(_lib.lib().rq_last_encode_stats(C.cast(out, C.c_void_p)))
-        finally:
-            rq.set_tuning("ENC_STATS", 0)
         assert out[0] == X.shape[0] * m
         return out[1] / out[0]
     Xs = synth.sift_like(200_000, 128, seed=3)
@@ -312,9 +296,6 @@ def test_encode_in_pieces_of_rows_equals_one_piece(rq, oracle):
     Ccat = synth.cat_codebooks(C)
     ref = oracle.encode_pq(X, Ccat, m, 256)
     Xd, Cd = torch.from_numpy(X).cuda(), torch.from_numpy(Ccat).cuda()
-    rq.set_tuning("ENC_CHUNK_ROWS", 4096)
-    try:
+    with switches(ENC_CHUNK_ROWS=4096):
         got = rqd.encode_pq(Xd, Cd, m, 256).cpu().numpy()
-    finally:
-        rq.set_tuning("ENC_CHUNK_ROWS", 1 << 22)
     assert np.array_equal(got, ref)

@@ -14,6 +14,8 @@ The observed numbers are printed (pytest -s) and quoted in DESIGN.md section 4.2
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 pytestmark = pytest.mark.gpu
 
 E_K = 2.0 ** -14
@@ -138,15 +140,12 @@ def test_filter_error_and_margin_walk_at_full_size(rq, oracle, shape):
     ref = torch.from_numpy(oracle.encode_pq(Xh, Ccat, m, h)).to(dev)
     Cd = torch.from_numpy(Ccat).to(dev)
     first_bad, table = None, []
-    try:
-        for milli in (3000, 1500, 750, 375, 188, 94, 47, 23, 12, 6, 0):
-            rq.set_tuning("ENC_SPLIT_DELTA_MILLI", milli)
+    for milli in (3000, 1500, 750, 375, 188, 94, 47, 23, 12, 6, 0):
+        with switches(ENC_SPLIT_DELTA_MILLI=milli):
             bad = int((rqd.encode_pq(X, Cd, m, h) != ref).sum())
-            table.append((milli / 1000.0, bad))
-            if bad and first_bad is None:
-                first_bad = milli
-    finally:
-        rq.set_tuning("ENC_SPLIT_DELTA_MILLI", 3000)
+        table.append((milli / 1000.0, bad))
+        if bad and first_bad is None:
+            first_bad = milli
     print("margin walk %s shape (numerator of DELTA_REL, codes that differ from the oracle of %d): %s" % (shape, n * m, table))
     print("   -> first failing numerator %s: safety factor of the shipped 3.0 >= %s" % (
         None if first_bad is None else first_bad / 1000.0, "inf" if not first_bad else "%.0fx" % (3000.0 / first_bad)))

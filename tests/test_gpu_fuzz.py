@@ -3,6 +3,8 @@ oracle -- ragged sizes, every supported m, tiny and huge k relative to n, duplic
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 pytestmark = pytest.mark.gpu
 
 
@@ -65,21 +67,15 @@ def test_scan_prefilter_on_hostile_tables(rq, oracle, style, m, K):
     assert np.array_equal(i0, i1), (style, m, K)
     assert _eq_bits(d0, d1), (style, m, K)
     # the same answer with the filter switched off (tuning knob): it is an accelerator, not part of the result
-    rq.set_tuning("SCAN_FILTER", 0)
-    try:
+    with switches(SCAN_FILTER=0):
         d2, i2 = rq.linscan_aqd_query(codes, centers, queries, K)
-    finally:
-        rq.set_tuning("SCAN_FILTER", 1)
     assert np.array_equal(i1, i2) and _eq_bits(d1, d2)
     from rayuela_jl_amd import _lib
     assert (_lib.lib().rq_last_scan_kernel() or b"").decode().startswith("adc_scan_kernel<%d, false, false" % m)      # the knob did switch it off
     if m == 8:
         # ... and with the other byte-table variant (6-bit entries, two sum sets: the library's choice for k >= 8192)
-        rq.set_tuning("SCAN_FINE_MIN_K", 1)
-        try:
+        with switches(SCAN_FINE_MIN_K=1):
             d3, i3 = rq.linscan_aqd_query(codes, centers, queries, K)
-        finally:
-            rq.set_tuning("SCAN_FINE_MIN_K", 0)
         assert np.array_equal(i1, i3) and _eq_bits(d1, d3)
 
 
@@ -122,11 +118,8 @@ def test_lsq_prefilter_on_hostile_tables(rq, oracle, style, m, K):
     d1, i1 = rq.linscan_lsq(codes, queries, C, norms, R, K)
     assert np.array_equal(i0.astype(np.int64), i1.astype(np.int64)), (style, m, K)
     assert _eq_bits(d0, d1), (style, m, K)
-    rq.set_tuning("SCAN_FILTER_LSQ", 0)
-    try:
+    with switches(SCAN_FILTER_LSQ=0):
         d2, i2 = rq.linscan_lsq(codes, queries, C, norms, R, K)
-    finally:
-        rq.set_tuning("SCAN_FILTER_LSQ", 1)
     assert np.array_equal(i1, i2) and _eq_bits(d1, d2)
 
 

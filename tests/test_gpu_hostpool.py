@@ -5,6 +5,8 @@ import gc
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 pytestmark = pytest.mark.gpu
 
 
@@ -33,11 +35,8 @@ def test_large_results_are_pinned_and_correct(rq, oracle):
     gc.collect()
     assert np.array_equal(keep, ref)
     # with the pool switched off the answer is the same, in numpy-owned memory
-    rq.set_tuning("HOST_PIN", 0)
-    try:
+    with switches(HOST_PIN=0):
         d2, i2 = rq.linscan_pq(codes, queries, C, 8 * m, k)
-    finally:
-        rq.set_tuning("HOST_PIN", 1)
     assert not isinstance(d2.base, _lib._PinnedBlock)
     assert np.array_equal(i2, idx) and _eq_bits(d2[5:7], ref)
     del keep
@@ -50,8 +49,7 @@ def test_large_results_are_pinned_and_correct(rq, oracle):
 
 def test_pool_limit_falls_back_to_plain_arrays(rq):
     from rayuela_jl_amd import _lib
-    rq.set_tuning("HOST_PIN_MAX_MB", 16)
-    try:
+    with switches(HOST_PIN_MAX_MB=16):
         a = _lib.result_empty((2 << 20,), np.float32)        # 8 MB
         b = _lib.result_empty((2 << 20,), np.float32)        # 8 MB: the limit is reached
         c = _lib.result_empty((2 << 20,), np.float32)
@@ -60,8 +58,6 @@ def test_pool_limit_falls_back_to_plain_arrays(rq):
         a[:] = 1.0
         b[:] = 2.0
         assert float(a.sum()) == float(2 << 20) and float(b[-1]) == 2.0
-    finally:
-        rq.set_tuning("HOST_PIN_MAX_MB", 0)
     del a, b, c
     gc.collect()
     assert _lib.lib().rq_release_workspaces() == 0     # also drops the idle page-locked buffers
@@ -84,11 +80,8 @@ def test_large_results_take_the_chunked_copy_path(rq):
     Q = rng.standard_normal((nq, m * sub)).astype(np.float32)
     B = synth.random_codes(n, m, seed=3)
     d0, i0 = rq.linscan_pq(B, Q, C, 8 * m, K)
-    rq.set_tuning("HOST_DIRECT_MAX_MB", 1)
-    try:
+    with switches(HOST_DIRECT_MAX_MB=1):
         d1, i1 = rq.linscan_pq(B, Q, C, 8 * m, K)
         ts = rq.last_timing()
-    finally:
-        rq.set_tuning("HOST_DIRECT_MAX_MB", 0)
     assert np.array_equal(i0, i1) and np.array_equal(d0.view(np.uint32), d1.view(np.uint32))
     assert ts["d2h_ms"] > 0.0          # copies happened (the direct path reports 0)

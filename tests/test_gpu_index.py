@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -193,8 +195,7 @@ def test_rccl_transport_selftest_on_one_gpu(rq):
     m = g["codes"].shape[1]
     d = g["queries"].shape[1]
     C = [g["centers"][i] for i in range(m)]
-    rq.set_tuning("EXCHANGE_SELFTEST", 1)
-    try:
+    with switches(EXCHANGE_SELFTEST=1):
         with rq.Index(C, d, devices=[0, 0, 0, 0]) as ix:
             ix.set_codes(g["codes"])
             info = ix.info()
@@ -203,8 +204,6 @@ def test_rccl_transport_selftest_on_one_gpu(rq):
             for K in g["Ks"]:
                 dists, ids = ix.search(g["queries"], int(K), id_base=0)
                 assert np.array_equal(ids, g["ids_K%d" % K]) and _eq_bits(dists, g["dists_K%d" % K]), K
-    finally:
-        rq.set_tuning("EXCHANGE_SELFTEST", 0)
 
 
 @pytest.mark.parametrize("selftest", [0, 1])
@@ -216,9 +215,7 @@ def test_query_chunk_pipeline(rq, chunks, selftest):
     m = g["codes"].shape[1]
     d = g["queries"].shape[1]
     C = [g["centers"][i] for i in range(m)]
-    rq.set_tuning("IDX_QCHUNKS", chunks)
-    rq.set_tuning("EXCHANGE_SELFTEST", selftest)
-    try:
+    with switches(IDX_QCHUNKS=chunks, EXCHANGE_SELFTEST=selftest):
         with rq.Index(C, d, devices=[0, 0, 0]) as ix:
             ix.set_codes(g["codes"])
             if selftest and ix.info()["exchange"] != "rccl":
@@ -234,9 +231,6 @@ def test_query_chunk_pipeline(rq, chunks, selftest):
             dists, ids = ix.search(g["queries"], 20, id_base=0)
             d1, i1 = rq.linscan_aqd_query(g["codes"][:n_small], g["centers"], g["queries"], 20)
             assert np.array_equal(ids, i1) and _eq_bits(dists, d1)
-    finally:
-        rq.set_tuning("IDX_QCHUNKS", 0)
-        rq.set_tuning("EXCHANGE_SELFTEST", 0)
 
 
 def test_torch_distributed_rccl_collectives_at_world_size_one(rq):

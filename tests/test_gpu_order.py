@@ -4,6 +4,8 @@ sums, the k smallest (dist, id) pairs) -- ids are original row numbers, ties inc
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 pytestmark = pytest.mark.gpu
 
 
@@ -11,21 +13,9 @@ def _eq_bits(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
 
 
-class _Tuning:
-    def __init__(self, rq, **kv):
-        self.rq, self.kv = rq, kv
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            self.rq.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        defaults = {"SCAN_ORDER": 1, "ORDER_MIN_ROWS": 65536, "ORDER_MIN_NQ": 2048, "ORDER_BITS": 0, "ORDER_GRAN": 0,
-                    "ORDER_SHUFFLE": 1, "SCAN_SRANK_MUL": 2, "SCAN_SLACK": 0, "SCAN_SLICES": 0, "SCAN_FILTER": 1,
-                    "SCAN_RETUNE_Z": 6, "INDEX_ORDER": 1, "SCAN_XCD_MIN_MB": 0, "SCAN_WINDOW_MB": 0, "ORDER_SAMPLE_STRIDE": 16,
-                    "SCAN_STATS": 0, "SCAN_BUCKET_FINISH": 1, "SCAN_SS_MAP": 1, "ORDER_GREEDY": 1, "ORDER_GREEDY_MIN_NQ": 16384}
-        for k in self.kv:
-            self.rq.set_tuning(k, defaults[k])
+def _Tuning(rq, **kv):
+    """The switches for a `with` block, reset (not restored by value) on exit."""
+    return switches(**kv)
 
 
 def _lds_passes(codes, rpt):

@@ -3,6 +3,8 @@ and vs the pinned oracle.  Bar: ids AND distances bit-exact (deps/src/linscan_aq
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -28,16 +30,13 @@ def test_legacy_symbol_matches_reference_golden(rq, name):
 @pytest.mark.parametrize("name", ["scan_sift_mini", "scan_dups"])
 def test_row_slices_merge_to_the_same_answer(rq, name, slices):
     g = golden(name)
-    rq.set_tuning("SCAN_SLICES", slices)
-    try:
+    with switches(SCAN_SLICES=slices):
         for K in g["Ks"]:
             if K * slices > g["codes"].shape[0]:
                 continue
             dists, ids = rq.linscan_aqd_query(g["codes"], g["centers"], g["queries"], int(K))
             assert np.array_equal(ids, g["ids_K%d" % K]), (name, K, slices)
             assert _eq_bits(dists, g["dists_K%d" % K])
-    finally:
-        rq.set_tuning("SCAN_SLICES", 0)
 
 
 def test_linscan_pq_julia_conventions(rq):
@@ -101,12 +100,8 @@ def test_threshold_strategies_are_all_exact(rq, oracle, knob, value):
     queries = rng.standard_normal((nq, m * sub)).astype(np.float32)
     codes = synth.random_codes(n, m, seed=123)
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
-    default = {"SCAN_SAMPLE": 16384, "SCAN_SRANK_MUL": 2, "SCAN_SLACK": 0}[knob]
-    rq.set_tuning(knob, value)
-    try:
+    with switches(**{knob: value}):
         d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
-    finally:
-        rq.set_tuning(knob, default)
     assert np.array_equal(i0, i1)
     assert _eq_bits(d0, d1)
 
@@ -156,11 +151,8 @@ def test_large_k_sample_sort_paths(rq, oracle, K):
     codes[1000:1400] = codes[7]          # a run of identical rows: equal distances, ordered by id
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
     for slices in (0, 1, 3, 8):          # 8 slices of 5625 rows: shorter than K = 10000
-        rq.set_tuning("SCAN_SLICES", slices)
-        try:
+        with switches(SCAN_SLICES=slices):
             d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
-        finally:
-            rq.set_tuning("SCAN_SLICES", 0)
         assert np.array_equal(i0, i1), (K, slices)
         assert _eq_bits(d0, d1), (K, slices)
     cen, qs = torch.from_numpy(centers).cuda(), torch.from_numpy(queries).cuda()
@@ -332,14 +324,11 @@ def test_second_threshold_estimate_and_its_fallback(rq, oracle, z):
     centers = rng.standard_normal((m, 256, sub)).astype(np.float32)
     queries = rng.standard_normal((nq, m * sub)).astype(np.float32)
     codes = synth.random_codes(n, m, seed=9)
-    rq.set_tuning("SCAN_RETUNE_Z", z)
-    try:
+    with switches(SCAN_RETUNE_Z=z):
         for K in (300, 1000, 3000):
             d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
             d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
             assert np.array_equal(i0, i1) and _eq_bits(d0, d1), (z, K)
-    finally:
-        rq.set_tuning("SCAN_RETUNE_Z", 6)
 
 
 @pytest.mark.parametrize("z", [6, -2])
@@ -362,9 +351,7 @@ def test_capacity_cut_after_second_estimate(rq, oracle, filt, z):
     queries = rng.standard_normal((nq, m * sub)).astype(np.float32)
     codes = synth.random_codes(n, m, seed=21)
     knobs = {"SCAN_SLACK": 1, "SCAN_SLICES": 1, "SCAN_STATS": 1, "SCAN_FILTER": filt, "SCAN_RETUNE_Z": z}
-    for k_, v in knobs.items():
-        rq.set_tuning(k_, v)
-    try:
+    with switches(**knobs):
         for K in (100, 1000):
             d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
             d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
@@ -372,9 +359,6 @@ def test_capacity_cut_after_second_estimate(rq, oracle, filt, z):
             assert np.array_equal(i0, i1) and _eq_bits(d0, d1), (K, filt, z, st)
             # the path under test ran: in-stream cuts happened; a too-tight estimate was caught and redone exactly
             assert st["n_cuts"] > 0 and (z == 6 or st["n_fallbacks"] > 0), st
-    finally:
-        for k_, v in {"SCAN_SLACK": 0, "SCAN_SLICES": 0, "SCAN_STATS": 0, "SCAN_FILTER": 1, "SCAN_RETUNE_Z": 6}.items():
-            rq.set_tuning(k_, v)
 
 
 @pytest.mark.parametrize("m,sub,K,nq", [(8, 4, 100, 100), (8, 4, 1000, 24), (16, 2, 100, 40), (8, 4, 3000, 16)])
@@ -390,32 +374,20 @@ def test_xcd_window_plan_on_a_small_base(rq, oracle, m, sub, K, nq):
     queries = rng.standard_normal((nq, m * sub)).astype(np.float32)
     codes = synth.random_codes(n, m, seed=5)
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
-    try:
-        rq.set_tuning("SCAN_XCD_MIN_MB", 1)
-        rq.set_tuning("SCAN_WINDOW_MB", 1)
+    with switches(SCAN_XCD_MIN_MB=1, SCAN_WINDOW_MB=1):
         plan = _lib.scan_plan(n, nq, m, m * sub, K)
         assert plan["xcd"] == 1 and plan["whole"] == 0 and plan["slices"] >= 16, plan
         for slack in (-1, 0, 1 << 20):
-            rq.set_tuning("SCAN_XCD_SLACK", slack)
-            d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
+            with switches(SCAN_XCD_SLACK=slack):
+                d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
             assert np.array_equal(i0, i1) and _eq_bits(d0, d1), (m, K, slack)
         # round 6: chunk pacing inside the rounds (SCAN_PACE; a speed hint -- bounded spins, no data depends on it): strict, loose,
         # coarse chunks; with and without item pacing.  (The call site is compiled in with -DRQ_SCAN_PACE_BUILD=1 only -- the shipped
         # library ignores the knob, a variant build runs the paced kernel through these same assertions.)
         for lag, votes, slack in ((0, 1, -1), (2, 1, 1 << 20), (1, 3, 0)):
-            rq.set_tuning("SCAN_PACE", 1)
-            rq.set_tuning("SCAN_PACE_LAG", lag)
-            rq.set_tuning("SCAN_PACE_VOTES", votes)
-            rq.set_tuning("SCAN_XCD_SLACK", slack)
-            d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
+            with switches(SCAN_PACE=1, SCAN_PACE_LAG=lag, SCAN_PACE_VOTES=votes, SCAN_XCD_SLACK=slack):
+                d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
             assert np.array_equal(i0, i1) and _eq_bits(d0, d1), (m, K, "pace", lag, votes, slack)
-    finally:
-        rq.set_tuning("SCAN_XCD_MIN_MB", 0)
-        rq.set_tuning("SCAN_WINDOW_MB", 0)
-        rq.set_tuning("SCAN_XCD_SLACK", -1)
-        rq.set_tuning("SCAN_PACE", 0)
-        rq.set_tuning("SCAN_PACE_LAG", 2)
-        rq.set_tuning("SCAN_PACE_VOTES", 1)
     assert _lib.scan_plan(n, nq, m, m * sub, K)["xcd"] == 0            # 24-48 MB of codes: the ordinary plan
 
 
@@ -437,13 +409,8 @@ def test_bucket_finish_equals_select_and_sort(rq, oracle, mode, n, m, sub, nq, K
     queries = rng.standard_normal((nq, m * sub)).astype(np.float32)
     codes = synth.random_codes(n, m, seed=n + K)
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
-    rq.set_tuning("SCAN_BUCKET_FINISH", mode)
-    rq.set_tuning("SCAN_SLICES", slices)
-    try:
+    with switches(SCAN_BUCKET_FINISH=mode, SCAN_SLICES=slices):
         d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
-    finally:
-        rq.set_tuning("SCAN_BUCKET_FINISH", 1)
-        rq.set_tuning("SCAN_SLICES", 0)
     assert np.array_equal(i0, i1)
     assert _eq_bits(d0, d1)
 
@@ -461,11 +428,8 @@ def test_bucket_finish_gives_up_on_mass_ties_and_stays_exact(rq, oracle, distinc
     codes = np.ascontiguousarray(pool[rng.integers(0, distinct, n)])
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
     for mode in (1, 2):
-        rq.set_tuning("SCAN_BUCKET_FINISH", mode)
-        try:
+        with switches(SCAN_BUCKET_FINISH=mode):
             d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
-        finally:
-            rq.set_tuning("SCAN_BUCKET_FINISH", 1)
         assert np.array_equal(i0, i1), (distinct, mode)
         assert _eq_bits(d0, d1)
 
@@ -488,10 +452,7 @@ def test_large_k_map_buckets_and_their_splitter_fallback(rq, oracle, distinct):
         codes = synth.random_codes(n, m, seed=77)
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries, K)
     for use_map in (1, 0):
-        rq.set_tuning("SCAN_SS_MAP", use_map)
-        try:
+        with switches(SCAN_SS_MAP=use_map):
             d1, i1 = rq.linscan_aqd_query(codes, centers, queries, K)
-        finally:
-            rq.set_tuning("SCAN_SS_MAP", 1)
         assert np.array_equal(i0, i1), (distinct, use_map)
         assert _eq_bits(d0, d1)

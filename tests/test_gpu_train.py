@@ -4,6 +4,8 @@ curve (stated here, per the north star's float bar); reconstruction is exact."""
 import numpy as np
 import pytest
 
+from switch_table import switches
+
 pytestmark = pytest.mark.gpu
 
 
@@ -228,11 +230,8 @@ def test_train_pq_with_kmeanspp_beats_uniform_seeding_on_clustered_data(rq):
     X = (centres[np.repeat(np.arange(ncl), per)] + rng.standard_normal((ncl * per, d))).astype(np.float32)
     X = X[rng.permutation(X.shape[0])]
     _, _, e_pp = rq.train_pq(X, 4, 64, niter=2, seed=5)
-    rq.set_tuning("TRAIN_KMPP", 0)
-    try:
+    with switches(TRAIN_KMPP=0):
         _, _, e_uni = rq.train_pq(X, 4, 64, niter=2, seed=5)
-    finally:
-        rq.set_tuning("TRAIN_KMPP", 1)
     assert e_pp < e_uni
 
 
@@ -329,12 +328,9 @@ def test_train_opq_newton_schulz_and_jacobi_agree(rq):
     a = rq.train_opq(X, 8, 64, 5, "natural", seed=2)
     pa = _lib.train_profile()
     assert pa["ns_steps"] > 0 and pa["jacobi_sweeps"] == 0 and pa["host_polar"] == 0
-    rq.set_tuning("TRAIN_GPU_POLAR", 2)
-    try:
+    with switches(TRAIN_GPU_POLAR=2):
         b = rq.train_opq(X, 8, 64, 5, "natural", seed=2)
         pb = _lib.train_profile()
-    finally:
-        rq.set_tuning("TRAIN_GPU_POLAR", 1)
     assert pb["ns_steps"] == 0 and pb["jacobi_sweeps"] > 0
     assert np.abs(a[2] - b[2]).max() < 2e-3               # the rotations (chaotic over iterations: codes flip on 1e-7 differences)
     assert np.allclose(a[3], b[3], rtol=2e-4)             # the objective curves
@@ -361,13 +357,10 @@ def test_update_centers_kernels_agree(rq, n, d, m, h):
     Xd, cd = torch.from_numpy(X).cuda(), torch.from_numpy(codes).cuda()
     outs = []
     for mfma in (0, 1):
-        rq.set_tuning("TRAIN_CENTERS_MFMA", mfma)
-        try:
+        with switches(TRAIN_CENTERS_MFMA=mfma):
             Cd = torch.from_numpy(C0.copy()).cuda()
             cnt = rqd.update_centers(Cd, Xd, cd, m, h)
             outs.append((Cd.cpu().numpy(), cnt.cpu().numpy()))
-        finally:
-            rq.set_tuning("TRAIN_CENTERS_MFMA", 1)
     assert np.array_equal(outs[0][1], outs[1][1])
     assert np.allclose(outs[0][0], outs[1][0], rtol=1e-5, atol=1e-4)
     # against float64
