@@ -6,9 +6,12 @@ m = 16) exactly as in `bench.py --workload opq|deep`; k = 1000 (LDS cut + bitoni
 default, src/Linscan.jl:10: sample-sort finish and, at m = 8, the FINE 6-bit filter tables).  Data, codebooks and
 rotation come from bench.py's generators.  Checked: the pinned oracle (the compiled reference when oracle/_ref is there)
 on 64 sampled queries, bit for bit, and on ALL queries the size-independent properties -- ascending (dist, id) order,
-unique in-range ids, and every returned distance recomputed on the device as the sequential-f32 ADC sum of that row."""
+unique in-range ids, and every returned distance recomputed on the device as the sequential-f32 ADC sum of that row; and
+every query certified to be exactly the reference's top-k (tests/exact_topk.py)."""
 import numpy as np
 import pytest
+
+import exact_topk as xt
 
 pytestmark = pytest.mark.gpu
 
@@ -81,6 +84,8 @@ def test_whole_item_scan_at_full_size(rq, oracle, wl, K):
         for k in range(1, m):
             acc = acc + torch.gather(lut[sl, k, :], 1, rows[:, :, k])
         assert torch.equal(acc, dists[sl]), (wl, K, q0)
+    # every query certified complete: exactly the reference's top-k set, not only a consistent list (tests/exact_topk.py)
+    assert xt.certify(dists, ids, K, xt.adc_lut(centers, Qs), codes, n) == nq, (wl, K)
     # the pinned oracle on 64 queries spread over the batch (first and last group included)
     sel = np.unique(np.concatenate([np.arange(0, nq, nq // 62), [nq - 1, nq - 8]]))[:64]
     fn = oracle.ref_linscan_aqd_query if oracle.ref_available() else oracle.linscan_aqd_query

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import exact_topk as xt
 from switch_table import switches
 
 from conftest import golden
@@ -264,9 +265,11 @@ def test_torch_distributed_rccl_collectives_at_world_size_one(rq):
 def test_row_ids_beyond_2_to_31_with_logical_shards(rq, oracle):
     """2.2e9 rows (17.6 GB of synthetic codes) on ONE device as two logical shards: per-shard row counts stay below
     2^31 (the kernels' limit), global ids are uint32 up to 4.29e9.  Size-independent check: every returned distance
-    is recomputed from the hash-generated code of the returned id; the lists must be ascending and cross 2^31."""
+    is recomputed from the hash-generated code of the returned id; the lists must be ascending and cross 2^31; and every
+    query is certified to be exactly the reference's top-k over all rows (tests/exact_topk.py)."""
     import torch
     import rayuela_jl_amd.synth as synth
+    from rayuela_jl_amd import device as rqd
     if torch.cuda.mem_get_info(0)[0] < 30 * (1 << 30):
         pytest.skip("needs 30 GB of free device memory")
     m, d, n, nq, k = 8, 32, 2_200_000_000, 8, 64
@@ -286,3 +289,10 @@ def test_row_ids_beyond_2_to_31_with_logical_shards(rq, oracle):
     for kk in range(1, m):
         acc = acc + np.take_along_axis(lut[:, kk, :], cb[:, :, kk], axis=1)
     assert _eq_bits(acc, dists)
+    # distinct ids, and all 8 queries certified over all 2.2e9 rows, the codes regenerated chunk by chunk the way
+    # rq_index_set_codes_synth fills each shard (synth_codes_launch from the shard's first global row)
+    assert all(len(np.unique(ids[q])) == k for q in range(nq))
+    r0 = 2 ** 31 - 3000                     # the device generator against the host hash, across 2^31 first
+    assert np.array_equal(rqd.synth_codes(6000, m, 777, row0=r0).cpu().numpy(), synth.random_codes(6000, m, 777, row0=r0))
+    lut_t = xt.adc_lut(torch.from_numpy(np.stack(C)).cuda(), torch.from_numpy(Q).cuda())
+    assert xt.certify(dists, ids, k, lut_t, lambda row0, count: rqd.synth_codes(count, m, 777, row0=row0), n) == nq

@@ -3,6 +3,7 @@ and vs the pinned oracle.  Bar: ids AND distances bit-exact (deps/src/linscan_aq
 import numpy as np
 import pytest
 
+import exact_topk as xt
 from switch_table import switches
 
 from conftest import golden
@@ -253,7 +254,7 @@ def test_argument_errors_are_reported(rq):
 
 def test_large_base_many_slices(rq, oracle):
     """SIFT1B-shape proxy on one GPU: 2e8 rows (1.6 GB of codes), few queries -> the planner cuts the
-    base in row slices and merges them; ids above 2^27; oracle on two queries."""
+    base in row slices and merges them; ids above 2^27; every query certified, the oracle on two."""
     import torch
     import rayuela_jl_amd.synth as synth
     from rayuela_jl_amd import device as rqd
@@ -268,6 +269,8 @@ def test_large_base_many_slices(rq, oracle):
     dd = dists[:, 1:] - dists[:, :-1]
     assert bool((dd >= 0).all())
     assert bool((ids64 < n).all())
+    # all 24 queries certified to be exactly the reference's top-k (tests/exact_topk.py)
+    assert xt.certify(dists, ids, K, xt.adc_lut(cen, qs), codes_t, n) == nq
     codes = codes_t.cpu().numpy()
     sel = [0, 23]
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries[sel], K)
@@ -277,7 +280,7 @@ def test_large_base_many_slices(rq, oracle):
 
 def test_full_size_sift1m_properties(rq, oracle):
     """BASELINE.json size (n=1e6, m=8, nq=1e4 is the bench; here 512 queries, K=1000): size-independent
-    properties on everything + the oracle on a few queries."""
+    properties and the top-k certificate on everything + the oracle on a few queries."""
     import torch
     import rayuela_jl_amd.synth as synth
     from rayuela_jl_amd import device as rqd
@@ -306,6 +309,8 @@ def test_full_size_sift1m_properties(rq, oracle):
     for k in range(m):
         acc = acc + torch.gather(lut[:, k, :], 1, rows[:, :, k])
     assert torch.equal(acc, dists)
+    # all 512 queries certified to be exactly the reference's top-k (tests/exact_topk.py)
+    assert xt.certify(dists, ids, K, xt.adc_lut(cen, qs), codes_t, n) == nq
     # oracle on a handful of queries
     sel = [0, 17, 255, 511]
     d0, i0 = oracle.linscan_aqd_query(codes, centers, queries[sel], K)
