@@ -46,7 +46,7 @@ extern "C" {
 #define RQ_EUNSUPPORTED (-2) /* shape outside what the kernels cover (h>256, LUT > LDS, ...) */
 #define RQ_ENODEVICE (-3)   /* no gfx950 device visible */
 
-#define RQ_MAX_K 65536      /* largest k the scan returns */
+#define RQ_MAX_K 65536      /* largest k served by the candidate-buffer scan; larger k take the bulk path */
 
 const char *rq_version(void);              /* "rayuela-hip <ver> (gfx950) build <sha1 of the kernel sources, 12 hex digits>" */
 const char *rq_last_error(void);
@@ -177,7 +177,8 @@ const char *rq_last_encode_kernel(void);
  * pass re-evaluated (1.5 % on SIFT-like, 0.5 % on Deep-like bench data).  Zeros when ENC_STATS was off. */
 int rq_last_encode_stats(uint64_t *out2);
 /* The scan kernel instantiation the calling thread's last linscan launched, spelled as rocprofv3 prints it
- * ("adc_scan_kernel<8, false, true, false>"); "" before the first scan.  bench.py replays committed PMC traffic figures
+ * ("adc_scan_kernel<8, false, true, false>"; the bulk path's distance kernel: "adc_bulk_keys_kernel<8, false>");
+ * "" before the first scan.  bench.py replays committed PMC traffic figures
  * only for the very instantiation (and library build) they were measured on. */
 const char *rq_last_scan_kernel(void);
 /* Test aid (no reference counterpart): rq_dev_encode_pq through the split kernel (even sub-space widths <= 16), which also
@@ -191,7 +192,10 @@ int rq_dev_encode_opq(uint8_t *codes, const float *X, const float *R, const floa
 /* Per-query ADC look-up tables lut [nq][m][256] (deps/src/linscan_aqd.cpp:66-74); test aid. */
 int rq_dev_adc_lut(float *lut, const float *centers, const float *queries, int64_t nq, int m,
                    int subdim, void *stream);
-/* The ADC scan + exact top-k over one resident shard of n rows (1 <= m <= 64, h = 256, k <= RQ_MAX_K).
+/* The ADC scan + exact top-k over one resident shard of n rows (1 <= m <= 64, h = 256, 1 <= k <= n < 2^31).
+ * k <= RQ_MAX_K runs the candidate-buffer scan (adc_scan_kernel); RQ_MAX_K < k <= n the bulk path (rq_bulk.hip: one key per
+ * row and query, radix select, radix sort; same answer, bit for bit), whose scratch is at most 2 GiB per device and stream --
+ * 8 n + 16 k bytes per query of a batch; a single query that needs more fails with the out-of-memory error.
  *   dists/ids [nq][k] (may both be NULL when keys != NULL)
  *   keys      [nq][k] uint64 or NULL: sorted packed (ordered-dist << 32 | id) per query, the
  *             form exchanged between shards/GPUs and consumed by rq_dev_merge_topk
@@ -314,7 +318,8 @@ int rq_dev_polar_factor(float *Rimg, const float *G, int d, int method, int *sta
  *   rq_index_set_codes_synth SIFT1B-shape synthetic base generated on the devices:
  *                            code[i][j] = splitmix64(seed ^ (i*m+j)) >> 56
  *   rq_index_search[_opq]    linscan_pq / linscan_opq (src/Linscan.jl:5-26, 93-103) against the resident base;
- *                            host pointers, synchronous, 1 <= k <= min(n, RQ_MAX_K)
+ *                            host pointers, synchronous, 1 <= k <= n (k > RQ_MAX_K: bulk path, merged across shards by
+ *                            the bulk select, queries in chunks whose lists take at most 256 MiB per buffer)
  *   rq_index_info            out[0] shards, [1] distinct devices, [2] exchange (0 none, 1 peer copies, 2 RCCL),
  *                            [3] rows, [4..] rows per shard (as many as fit in cap)
  * The host-pointer calls rq_linscan_pq / rq_linscan_opq / linscan_aqd_query build such an index for the
@@ -387,7 +392,8 @@ int rq_scan_finish_stats(unsigned long long *out8);
  * m sub-quantizers, dimension d, k neighbours on a device with num_cu compute units.  out[0] queries per group,
  * [1] groups, [2] groups scanned as whole-base items, [3] row slices of the remaining groups, [4] rows per slice,
  * [5] workgroups launched, [6] candidate capacity per query, [7] bit 0: sample-sort finish (k > 1024), bit 1: big base --
- * row windows handed out per XCD (L2 affinity). */
+ * row windows handed out per XCD (L2 affinity), bit 2: k > RQ_MAX_K takes the bulk path -- then [2] = [1], [3] = 1, [4] = n,
+ * [5] is the distance kernel's grid and [6] the queries per bulk batch (0: one query does not fit the scratch budget). */
 int rq_scan_plan(int64_t n, int64_t nq, int m, int d, int k, int num_cu, int64_t *out8);
 
 /* Milliseconds spent in the last host-pointer call on this thread: total wall, H2D, kernels

@@ -145,12 +145,13 @@ def reset_tuning(key=None):
 
 
 def scan_plan(n, nq, m, d, k, num_cu=256):
-    """The planner's decision (host code only): dict of qg, groups, whole, slices, rows_per_slice, grid, cap, bigk, xcd."""
+    """The planner's decision (host code only): dict of qg, groups, whole, slices, rows_per_slice, grid, cap, bigk, xcd, bulk.
+    bulk = 1: k > RQ_MAX_K takes the bulk top-k path (grid: its distance kernel, cap: queries per batch)."""
     out = (C.c_int64 * 8)()
     check(lib().rq_scan_plan(n, nq, m, d, k, num_cu, C.cast(out, C.c_void_p)))
     keys = ("qg", "groups", "whole", "slices", "rows_per_slice", "grid", "cap", "flags")
     p = dict(zip(keys, [int(x) for x in out]))
-    p["bigk"], p["xcd"] = p["flags"] & 1, (p["flags"] >> 1) & 1
+    p["bigk"], p["xcd"], p["bulk"] = p["flags"] & 1, (p["flags"] >> 1) & 1, (p["flags"] >> 2) & 1
     return p
 
 

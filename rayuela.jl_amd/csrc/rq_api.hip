@@ -395,7 +395,7 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
   if (lut_mode < LUT_PQ || lut_mode > LUT_CQ) return fail(RQ_EINVAL, "lut_mode=%d", lut_mode);
   if (m < 1 || d < 1 || (lut_mode == LUT_PQ && (d < m || d % m != 0)))
     return fail(RQ_EINVAL, "scan needs d %% m == 0 (src/Linscan.jl:23 Cint(d/m)); got d=%d m=%d", d, m);
-  if (k < 1 || k > RQ_MAX_K) return fail(RQ_EUNSUPPORTED, "k=%d outside [1, %d]", k, RQ_MAX_K);
+  if (k < 1) return fail(RQ_EUNSUPPORTED, "k=%d outside [1, n]", k);
   if (k > n) return fail(RQ_EINVAL, "k=%d > n=%lld (undefined in the reference, deps/src/linscan_aqd.cpp:91)", k, (long long)n);
   if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "row ids overflow uint32");
   if (id_base != 0 && id_base != 1) return fail(RQ_EINVAL, "id_base must be 0 or 1");
@@ -414,6 +414,11 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
     RQ_TRY(pad_codes_launch((uint8_t *)padded, codes, n, m, mp, stream));
     codes = (const uint8_t *)padded;
   }
+  // k beyond the candidate buffers of the scan: the bulk path (rq_bulk.hip) -- every row's key, radix select, radix sort.
+  // No in-call ordering (ORDER_MAX_K is far below) and no LSQ norm pre-filter; an ordered base keeps its perm for the ids.
+  if (k > RQ_MAX_K)
+    return bulk_scan(dists, ids, keys, codes, centers, queries, n, nq, m, d, k, id_offset, id_base, stream, lut_mode, row_bias,
+                     perm, di.num_cu);
   // Bank-aware row order (rq_order.hip).  `perm` given: `codes` is an ordered base already, rows padded to mp bytes
   // (order_base: index handles, rq_dev_order_rows, the host-pointer calls).  Otherwise the call orders a copy itself when
   // that pays: the four small kernels cost ~40 us at 1e6 rows, a scan of nq queries gains ~15 % of its time -- from
@@ -546,6 +551,30 @@ static bool use_direct_results(const float *dists, const uint32_t *ids, int64_t 
          host_pool_owns(ids, (size_t)nq * k * 4);
 }
 
+// k > RQ_MAX_K on host pointers (bulk path): the results travel through a device buffer of at most BULK_HOST_RESULT_BYTES,
+// one query chunk at a time, never nq * k * 8 bytes at once.  scan(dd, di, q0, nqc) scans queries [q0, q0 + nqc) into dd/di.
+template <class ScanFn>
+static int bulk_fetch(float *dists, uint32_t *ids, int64_t nq, int k, ScanFn scan) {
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(BULK_HOST_RESULT_BYTES / ((size_t)k * 8))));
+  DevBuf dd, di;
+  RQ_TRY(dd.alloc((size_t)chunk * k * 4));
+  RQ_TRY(di.alloc((size_t)chunk * k * 4));
+  Timer t2;
+  double d2h = 0;
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int64_t nqc = std::min(chunk, nq - q0);
+    RQ_TRY(scan(dd.as<float>(), di.as<uint32_t>(), q0, nqc));
+    RQ_HIP(hipDeviceSynchronize());
+    Timer t3;
+    RQ_HIP(hipMemcpy(dists + (size_t)q0 * k, dd.p, (size_t)nqc * k * 4, hipMemcpyDeviceToHost));
+    RQ_HIP(hipMemcpy(ids + (size_t)q0 * k, di.p, (size_t)nqc * k * 4, hipMemcpyDeviceToHost));
+    d2h += t3.ms();
+  }
+  g_t_kernel = t2.ms() - d2h;
+  g_t_d2h = d2h;
+  return RQ_OK;
+}
+
 static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const float *centers,
                         const float *queries, const float *R, int64_t n, int64_t nq, int m, int d, int k,
                         int id_base) {
@@ -574,8 +603,9 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
   DevBuf dcodes, dcent, dq, dr, drq, dd, di_;
   const size_t cb = (size_t)n * m, ce = (size_t)m * 256 * (d / m) * 4, qb = (size_t)nq * d * 4;
   RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce)); RQ_TRY(dq.alloc(qb));
-  const bool direct = use_direct_results(dists, ids, nq, k);
-  if (!direct) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
+  const bool bulk = k > RQ_MAX_K;
+  const bool direct = !bulk && use_direct_results(dists, ids, nq, k);
+  if (!direct && !bulk) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
   Timer t1;
   RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dcent.p, centers, ce, hipMemcpyHostToDevice));
@@ -604,6 +634,14 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
   }
   ScanBase sbase;
   sbase.perm = perm;
+  if (bulk) {
+    RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
+      return dev_linscan(bd, bi, nullptr, cdev, cen, qdev + (size_t)q0 * d, n, nqc, m, d, k, 0, id_base, nullptr, LUT_PQ, nullptr,
+                         &sbase);
+    }));
+    g_t_total = tt.ms();
+    return RQ_OK;
+  }
   RQ_TRY(scan_and_fetch(dists, ids, direct ? nullptr : ddp, dip, nq, k, [&](int64_t q0, int64_t nqc, hipStream_t stream) {
     return dev_linscan(ddp + (size_t)q0 * k, dip + (size_t)q0 * k, nullptr, cdev, cen, qdev + (size_t)q0 * d, n, nqc, m,
                        d, k, 0, id_base, stream, LUT_PQ, nullptr, &sbase);
@@ -636,8 +674,9 @@ static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, co
   DevBuf dcodes, dcb, dq, dn, dr, drq, dd, di_;
   const size_t cb = (size_t)n * m, ce = (size_t)m * 256 * d * 4, qb = (size_t)nq * d * 4;
   RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcb.alloc(ce)); RQ_TRY(dq.alloc(qb));
-  const bool direct = use_direct_results(dists, ids, nq, k);
-  if (!direct) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
+  const bool bulk = k > RQ_MAX_K;
+  const bool direct = !bulk && use_direct_results(dists, ids, nq, k);
+  if (!direct && !bulk) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
   Timer t1;
   RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dcb.p, codebooks, ce, hipMemcpyHostToDevice));
@@ -661,6 +700,13 @@ static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, co
   const uint8_t *cdev = dcodes.as<uint8_t>();
   const float *cbk = dcb.as<float>();
   const float *nrm = dbnorms ? dn.as<float>() : nullptr;
+  if (bulk) {
+    RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
+      return dev_linscan(bd, bi, nullptr, cdev, cbk, qdev + (size_t)q0 * d, n, nqc, m, d, k, 0, id_base, nullptr, lut_mode, nrm);
+    }));
+    g_t_total = tt.ms();
+    return RQ_OK;
+  }
   RQ_TRY(scan_and_fetch(dists, ids, direct ? nullptr : ddp, dip, nq, k, [&](int64_t q0, int64_t nqc, hipStream_t stream) {
     return dev_linscan(ddp + (size_t)q0 * k, dip + (size_t)q0 * k, nullptr, cdev, cbk, qdev + (size_t)q0 * d, n, nqc, m,
                        d, k, 0, id_base, stream, lut_mode, nrm);
@@ -822,6 +868,16 @@ int rq_reset_tuning(const char *key) {
 
 int rq_scan_plan(int64_t n, int64_t nq, int m, int d, int k, int num_cu, int64_t *out8) {
   if (!out8 || n < 1 || nq < 1 || k < 1 || num_cu < 1) return fail(RQ_EINVAL, "rq_scan_plan: bad arguments");
+  if (k > RQ_MAX_K) {
+    // bulk path (rq_bulk.hip): [2] whole = groups, [3] 1 slice, [4] all rows, [5] grid of the distance kernel, [6] queries per
+    // batch (0: one query does not fit the scratch budget); flags bit 0 keeps its meaning (k > SCAN_SS_MIN_K), bit 2 = bulk
+    if (scan_padded_m(m) < 0) return fail(RQ_EUNSUPPORTED, "the ADC scan kernels cover 1 <= m <= 64 sub-quantizers");
+    int64_t qg, groups, grid, batch;
+    bulk_plan(n, nq, m, k, num_cu, &qg, &groups, &grid, &batch);
+    out8[0] = qg; out8[1] = groups; out8[2] = groups; out8[3] = 1; out8[4] = n; out8[5] = grid; out8[6] = batch;
+    out8[7] = (k > tuning("SCAN_SS_MIN_K", 1024) ? 1 : 0) | 4;
+    return RQ_OK;
+  }
   ScanPlan pl;
   RQ_TRY(scan_plan(pl, n, nq, m, d, k, num_cu, tuning("SCAN_SLICES", 0)));
   out8[0] = pl.qg; out8[1] = pl.ngroups; out8[2] = pl.whole; out8[3] = pl.nslices; out8[4] = pl.rows_per_slice;
@@ -1029,8 +1085,9 @@ int rq_lsq_search(rq_lsq_index *handle, float *dists, uint32_t *ids, const float
   DevBuf dq, dr, drq, dd, di_;
   const size_t qb = (size_t)nq * d * 4;
   RQ_TRY(dq.alloc(qb));
-  const bool direct = use_direct_results(dists, ids, nq, k);
-  if (!direct) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
+  const bool bulk = k > RQ_MAX_K;
+  const bool direct = !bulk && use_direct_results(dists, ids, nq, k);
+  if (!direct && !bulk) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
   Timer t1;
   RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
   const float *qdev = dq.as<float>();
@@ -1042,6 +1099,17 @@ int rq_lsq_search(rq_lsq_index *handle, float *dists, uint32_t *ids, const float
   if (R) {
     RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, di.num_cu, nullptr));
     qdev = drq.as<float>();
+  }
+  if (bulk) {
+    ScanBase sb;
+    sb.padded = true;
+    sb.perm = ix->perm;
+    RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
+      return dev_linscan(bd, bi, nullptr, ix->perm ? ix->ocodes : ix->codes, ix->cb, qdev + (size_t)q0 * d, ix->n, nqc, ix->m, d,
+                         k, 0, id_base, nullptr, LUT_LSQ, ix->norms, &sb);
+    }));
+    g_t_total = tt.ms();
+    return RQ_OK;
   }
   float *ddp = direct ? dists : dd.as<float>();
   uint32_t *dip = direct ? ids : di_.as<uint32_t>();
@@ -1382,7 +1450,7 @@ int rq_dev_linscan_ordered(float *dists, uint32_t *ids, uint64_t *keys, const ui
 int rq_dev_merge_topk(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *keys_in, int64_t nq, int P,
                       int k, int id_base, void *stream) {
   if (nq <= 0) return RQ_OK;
-  if (P < 1 || k < 1 || k > RQ_MAX_K) return fail(RQ_EINVAL, "merge: P=%d k=%d", P, k);
+  if (P < 1 || k < 1) return fail(RQ_EINVAL, "merge: P=%d k=%d", P, k);
   return merge_launch(dists, ids, keys_out, keys_in, nq, P, k, id_base, (hipStream_t)stream);
 }
 

@@ -355,10 +355,26 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
                  int k, int id_base) {
   if (!ix || ix->n < 1) return fail(RQ_EINVAL, "index has no codes");
   if (nq <= 0) return RQ_OK;
-  if (k < 1 || k > RQ_MAX_K) return fail(RQ_EUNSUPPORTED, "k=%d outside [1, %d]", k, RQ_MAX_K);
+  if (k < 1) return fail(RQ_EUNSUPPORTED, "k=%d outside [1, n]", k);
   if (k > ix->n) return fail(RQ_EINVAL, "k=%d > n=%lld (undefined in the reference, deps/src/linscan_aqd.cpp:91)", k, (long long)ix->n);
   if (id_base != 0 && id_base != 1) return fail(RQ_EINVAL, "id_base must be 0 or 1");
   if (!dists || !ids || !queries_host) return fail(RQ_EINVAL, "index search: NULL argument");
+  {
+    // bulk path (k > RQ_MAX_K): results, gathered and interleaved lists ((2 P + 1) x nq x k x 8 bytes on the root device)
+    // are bounded by query chunks of at most BULK_HOST_RESULT_BYTES of each
+    const int64_t per_q = (int64_t)k * 8 * (2 * (int64_t)ix->shards.size() + 1);
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)BULK_HOST_RESULT_BYTES / per_q);
+    if (k > RQ_MAX_K && nq > chunk) {
+      Clock tc;
+      for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const int64_t nqc = std::min(chunk, nq - q0);
+        RQ_TRY(index_search(ix, dists + (size_t)q0 * k, ids + (size_t)q0 * k, queries_host + (size_t)q0 * ix->d, R_host, nqc,
+                            k, id_base));
+      }
+      set_timing(tc.ms(), 0, 0, 0);
+      return RQ_OK;
+    }
+  }
   std::lock_guard<std::mutex> lk(ix->mu);
   SavedDevice saved;
   Clock tt;

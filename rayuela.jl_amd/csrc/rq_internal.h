@@ -54,7 +54,7 @@ int aux_streams(hipStream_t *compute, hipStream_t *transfer);
 // counters of the big-base scan: 8 XCDs x SCAN_PACE_SLOTS x {chunks done, members}
 constexpr int SCAN_PACE_SLOTS = 64;
 constexpr size_t WS_COUNTER_BYTES = 256 + 8 * SCAN_PACE_SLOTS * 8;
-enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_SLOTS = 10 };
+enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_SLOTS = 11 };
 
 // Per-device launch lock (recursive): held while a call looks up scratch, resets the work counter and
 // launches, so two host threads cannot interleave those sequences on one device.
@@ -96,6 +96,7 @@ int scan_launch(const ScanPlan &pl, float *dists, uint32_t *ids, uint64_t *keys,
                 hipStream_t stream, int lut_mode = 0, const float *row_bias = nullptr, uint8_t *norm_buf = nullptr,
                 const uint32_t *perm = nullptr, bool norm_ready = false);
 const char *last_scan_kernel_name();      // which instantiation the calling thread's last scan_launch chose
+void set_last_scan_kernel(const char *name);
 size_t lsq_norm_bytes(int64_t n);      // LSQ pre-filter: bytes of a base's prepared norm buffer
 int lsq_norm_prepare(uint8_t *norm_buf, const uint8_t *codes, const float *centers, const float *row_bias, int64_t n,
                      int mp, int m_real, int d, hipStream_t stream);
@@ -132,6 +133,19 @@ int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t 
 int interleave_keys_launch(uint64_t *dst, const uint64_t *src, int64_t nq, int P, int k, size_t pstride, hipStream_t stream);
 int scan_padded_m(int m);   // smallest tiled row width >= m (2,4,8,16,32,64) or -1
 int pad_codes_launch(uint8_t *dst, const uint8_t *src, int64_t n, int m, int mp, hipStream_t stream);
+// ---- bulk top-k (rq_bulk.hip): RQ_MAX_K < k <= n ------------------------------------------------------------------
+// Scratch of one bulk call per device and stream (WS_BULK): keys of a query batch + the select / sort buffers.  The batch
+// is sized to fit; a query that does not fit alone is an out-of-memory error.
+constexpr size_t BULK_SCRATCH_BYTES = (size_t)2 << 30;
+// host-pointer calls with k > RQ_MAX_K: device result buffers of at most this many bytes, the queries in chunks
+constexpr size_t BULK_HOST_RESULT_BYTES = (size_t)256 << 20;
+int bulk_scan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *codes, const float *centers, const float *queries,
+              int64_t n, int64_t nq, int m, int d, int k, uint32_t id_offset, int id_base, hipStream_t stream, int lut_mode,
+              const float *row_bias, const uint32_t *perm, int num_cu);
+int bulk_merge(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *keys_in, int64_t nq, int P, int K,
+               int id_base, hipStream_t stream);
+// rq_scan_plan's view of a bulk call: queries per group, groups, grid of the distance kernel, queries per batch
+void bulk_plan(int64_t n, int64_t nq, int m, int k, int num_cu, int64_t *qg, int64_t *groups, int64_t *grid, int64_t *batch);
 int merge_launch(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *keys_in, int64_t nq,
                  int P, int K, int id_base, hipStream_t stream);
 int lut_launch(float *lut, const float *centers, const float *queries, int64_t nq, int m, int sub,

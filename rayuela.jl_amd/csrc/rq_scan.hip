@@ -932,6 +932,7 @@ __global__ void synth_codes_kernel(uint8_t *codes, size_t nbytes, uint64_t seed,
 // ------------------------------------------------------------------------------------------
 static thread_local char g_last_scan_kernel[64] = "";      // the calling thread's last scan launch (template arguments as rocprofv3 prints them)
 const char *last_scan_kernel_name() { return g_last_scan_kernel; }
+void set_last_scan_kernel(const char *name) { snprintf(g_last_scan_kernel, sizeof(g_last_scan_kernel), "%s", name); }
 
 template <int M>
 static int launch_scan(ScanParams &p, const ScanPlan &plan, hipStream_t stream) {
@@ -1273,6 +1274,8 @@ int scan_launch(const ScanPlan &pl, float *dists, uint32_t *ids, uint64_t *keys,
 
 int merge_launch(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *keys_in, int64_t nq,
                  int P, int K, int id_base, hipStream_t stream) {
+  // K beyond the scan's cap (full rankings over shards): the bulk select + sort of rq_bulk.hip over the P * K keys
+  if (P > 1 && K > RQ_MAX_K) return bulk_merge(dists, ids, keys_out, keys_in, nq, P, K, id_base, stream);
   MergeParams p;
   p.keys_in = keys_in; p.nq = (uint32_t)nq; p.P = (uint32_t)P; p.K = K; p.id_base = id_base;
   p.p2 = next_pow2((uint32_t)K);
