@@ -115,6 +115,23 @@ int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n
 int rq_dev_encode_rvq(uint8_t *codes, float *Xr, const float *codebooks, int64_t n, int d, int m, int h,
                       uint32_t *counts, void *stream);
 
+/* ---- LSQ encoding: encoding_icm (src/LSQ.jl:272-302) / encode_icm_cuda (src/LSQ_GPU.jl:218-264) -------------------
+ * Iterated local search around ICM, contract in DESIGN.md section 2.  X [n][d], C [m][h][d] (m full-dimensional codebooks,
+ * one codeword per row), codes [n][m] uint8 zero-based.  1 <= m <= 16, 2 <= h <= 256, d >= 1, 0 <= npert <= m,
+ * ilsiter, icmiter, t0 >= 0, nsplits >= 1 (the minimum number of row chunks).  ILS iterations t0 .. t0+ilsiter-1 run, so a
+ * checkpointed run continues the same random stream; results depend on neither nsplits nor the chunking.  codes_out may
+ * alias codes_in; cost_out [n] (may be NULL) receives each row's final veccost.  Arguments (codes < h included) are checked
+ * before any encode work; errors through rq_last_error.  Non-finite inputs give unspecified but in-range codes. */
+int rq_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,
+                  int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
+                  int64_t t0, int nsplits);
+/* device pointers, queued on `stream` (with h < 256 the code range check reads one flag back first) */
+int rq_dev_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,
+                      int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
+                      int64_t t0, int nsplits, void *stream);
+/* milliseconds of this thread's last rq_encode_icm: unaries (hipEvent, summed over chunks) and the whole call */
+int rq_last_icm_timing(double *unary_ms, double *total_ms);
+
 /* ---- host-pointer entry points (what the julia/ shims ccall) ----------------------------------
  * rq_encode_*: X is uploaded in ~128 MB chunks while the previous chunk is encoded (the call is PCIe-bound).  With
  * RAYUELA_HIP_DEVICES listing several devices the rows are split over them, one host thread and one PCIe link

@@ -17,6 +17,7 @@ module RayuelaHIP
 import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
+export encoding_icm, encode_icm_cuda
 export HipIndex, set_codes!, set_codes_synth!, search, HipDataset, quantize
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
@@ -386,6 +387,57 @@ function quantize(ds::HipDataset, C::Vector{Matrix{Float32}}; R::Union{Nothing,M
     (Ptr{Cvoid}, Ptr{Cuchar}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Cint, Cint),
     ds.h, C_NULL, B, R === nothing ? C_NULL : R, _cat_codebooks(C), Cint(m), Cint(h)))
   return B
+end
+
+# ---- LSQ encoding (src/LSQ.jl:272-302, src/LSQ_GPU.jl:218-264): ILS around ICM on the device (rq_encode_icm) ----------
+# Codes are Int16 one-based m x n like the reference; the random stream is counter-based (`seed`), so results depend on
+# neither nsplits nor checkpoints (DESIGN.md section 2).
+function _encode_icm!(out::Matrix{UInt8}, B0::Matrix{UInt8}, cost, X::Matrix{Float32}, C::Vector{Matrix{Float32}},
+                      ilsiter, icmiter, npert, randord, seed, t0, nsplits)
+  d, n = size(X)
+  m    = length(C)
+  h    = size(C[1], 2)
+  _check(ccall((:rq_encode_icm, librayuela_hip), Cint,
+    (Ptr{UInt8}, Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Cint,
+     UInt64, Int64, Cint),
+    out, B0, cost === nothing ? C_NULL : cost, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(ilsiter),
+    Cint(icmiter), Cint(npert), Cint(randord ? 1 : 0), UInt64(seed), Int64(t0), Cint(nsplits)))
+  return out
+end
+
+function encoding_icm(X::Matrix{Float32}, oldB::Matrix{Int16}, C::Vector{Matrix{Float32}}, ilsiter::Integer,
+                      icmiter::Integer, randord::Bool, npert::Integer, cpp::Bool=true, V::Bool=false; seed::Integer=0)
+  h = size(C[1], 2)
+  cpp && h != 256 && throw(ArgumentError("encoding_icm with cpp=true requires h = 256 codewords; got h=$h"))
+  B0  = convert(Matrix{UInt8}, oldB .- Int16(1))
+  out = similar(B0)
+  _encode_icm!(out, B0, nothing, X, C, ilsiter, icmiter, npert, randord, seed, 0, 1)
+  B = convert(Matrix{Int16}, out) .+ Int16(1)
+  copyto!(oldB, B)
+  return B
+end
+
+function encode_icm_cuda(RX::Matrix{Float32}, B::Matrix{Int16}, C::Vector{Matrix{Float32}}, ilsiters::Vector{Int64},
+                         icmiter::Integer, npert::Integer, randord::Bool, nsplits::Integer=2, V::Bool=false;
+                         seed::Integer=0)
+  cur  = convert(Matrix{UInt8}, B .- Int16(1))
+  cost = Vector{Float32}(undef, size(RX, 2))
+  Bs   = Vector{Matrix{Int16}}(undef, length(ilsiters))
+  objs = zeros(Float32, length(ilsiters))
+  done = 0
+  for stop in sort(unique(ilsiters))
+    nxt = similar(cur)
+    _encode_icm!(nxt, cur, cost, RX, C, stop - done, icmiter, npert, randord, seed, done, nsplits)
+    cur, done = nxt, stop
+    for (i, s) in enumerate(ilsiters)
+      if s == stop
+        Bs[i]   = convert(Matrix{Int16}, cur) .+ Int16(1)
+        objs[i] = Float32(sum(Float64.(cost)) / length(cost))
+      end
+    end
+    V && println(" ILS iteration $stop/$(maximum(ilsiters)) done")
+  end
+  return Bs, objs
 end
 
 end # module

@@ -1,0 +1,142 @@
+"""Host mirror of the LSQ encoder: encoding_icm (src/LSQ.jl:272-302), encode_icm_cuda (src/LSQ_GPU.jl:218-264),
+veccost / qerror (src/qerrors.jl) for full-dimensional codebooks.
+
+Iterated local search around ICM on the device (rq_encode_icm); the contract is DESIGN.md section 2.  Codebooks C are an
+m-long list of (h, d) arrays (memory image of Julia's d-by-h matrices) or one (m, h, d) array; codes are (n, m) Int16
+one-based like the reference's m-by-n matrices.  Random numbers are counter-based (`seed`), keyed by the global row index
+and the ILS iteration, so results depend on neither nsplits nor checkpoints."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .utils import _as_f32
+
+MAX_M = 16
+
+
+def _stack(C):
+    if isinstance(C, np.ndarray) and C.ndim == 3:
+        Cs = np.ascontiguousarray(_as_f32(C, "C"))
+    else:
+        Cs = [np.ascontiguousarray(_as_f32(c, "C[i]")) for c in C]
+        if not Cs or len({c.shape for c in Cs}) != 1:
+            raise ValueError("all LSQ codebooks must be d x h")
+        Cs = np.ascontiguousarray(np.stack(Cs, axis=0))
+    return Cs
+
+
+def _check(X, Cs, codes0, ilsiter, icmiter, npert, nsplits, t0, one_based):
+    """Every argument check runs here, before the library (and the device) is touched."""
+    n, d = X.shape
+    m, h, d2 = Cs.shape
+    if d2 != d:
+        raise ValueError("codebooks are %d-dimensional, data is %d-dimensional" % (d2, d))
+    if not 1 <= m <= MAX_M:
+        raise ValueError("LSQ encoding covers 1 <= m <= %d codebooks; got m=%d" % (MAX_M, m))
+    if not 2 <= h <= 256:
+        raise ValueError("LSQ encoding covers 2 <= h <= 256 codewords; got h=%d" % h)
+    for name, v in (("ilsiter", ilsiter), ("icmiter", icmiter), ("t0", t0)):
+        if int(v) < 0:
+            raise ValueError("%s must be >= 0; got %d" % (name, v))
+    if not 0 <= int(npert) <= m:
+        raise ValueError("npert must be in 0..m=%d; got %d" % (m, npert))
+    if int(nsplits) < 1:
+        raise ValueError("nsplits must be >= 1; got %d" % nsplits)
+    B = np.asarray(codes0)
+    if B.shape != (n, m):
+        raise ValueError("codes must be (n, m) = (%d, %d); got %s" % (n, m, B.shape))
+    lo = 1 if one_based else 0
+    if B.size and (B.min() < lo or B.max() > h - 1 + lo):
+        raise ValueError("codes must be in %d..%d" % (lo, h - 1 + lo))
+    return n, d, m, h
+
+
+def encode_icm_u8(X, codes0, C, ilsiter, icmiter, npert, randord, seed=0, t0=0, nsplits=1, with_cost=False):
+    """Zero-based uint8 codes in and out: ILS iterations t0 .. t0+ilsiter-1.  with_cost -> (codes, per-row veccost)."""
+    X = _as_f32(X, "X")
+    Cs = _stack(C)
+    n, d, m, h = _check(X, Cs, codes0, ilsiter, icmiter, npert, nsplits, t0, one_based=False)
+    B = np.ascontiguousarray(codes0, dtype=np.uint8)
+    out = np.empty((n, m), dtype=np.uint8)
+    cost = np.empty(n, dtype=np.float32) if with_cost else None
+    _lib.check(_lib.lib().rq_encode_icm(out.ctypes.data, B.ctypes.data, None if cost is None else cost.ctypes.data,
+                                        X.ctypes.data, Cs.ctypes.data, n, d, m, h, int(ilsiter), int(icmiter),
+                                        int(npert), 1 if randord else 0, int(seed) & ((1 << 64) - 1), int(t0),
+                                        int(nsplits)))
+    return (out, cost) if with_cost else out
+
+
+def encoding_icm(X, oldB, C, ilsiter, icmiter, randord, npert, cpp=True, V=False, seed=0):
+    """encoding_icm(X, oldB, C, ilsiter, icmiter, randord, npert, cpp=true, V=false) -> B     (src/LSQ.jl:272-302)
+
+    X (n, d) float32, oldB (n, m) Int16 one-based, C m-long list of (h, d) codebooks.  Returns B (n, m) Int16 one-based
+    and, like the reference, writes it into oldB too.  cpp=True requires h = 256 (the reference's C++ path is built
+    for H = 256); both settings run the same device kernel."""
+    X = _as_f32(X, "X")
+    Cs = _stack(C)
+    if not (isinstance(oldB, np.ndarray) and oldB.dtype == np.int16):
+        raise TypeError("oldB must be an Int16 numpy array (it is updated in place)")
+    if cpp and Cs.shape[1] != 256:
+        raise ValueError("encoding_icm with cpp=true requires h = 256 codewords; got h=%d" % Cs.shape[1])
+    _check(X, Cs, oldB, ilsiter, icmiter, npert, 1, 0, one_based=True)
+    codes = encode_icm_u8(X, (oldB - 1).astype(np.uint8), Cs, ilsiter, icmiter, npert, randord, seed=seed)
+    B = codes.astype(np.int16) + 1
+    oldB[...] = B
+    if V:
+        print(" ILS encoding: %d iterations done" % ilsiter)
+    return B
+
+
+def encode_icm_cuda(RX, B, C, ilsiters, icmiter, npert, randord, nsplits=2, V=False, seed=0):
+    """encode_icm_cuda(RX, B, C, ilsiters, icmiter, npert, randord, nsplits=2, V=false) -> Bs, objs
+                                                                                   (src/LSQ_GPU.jl:218-264)
+    Runs max(ilsiters) ILS iterations; Bs[i] (Int16 one-based) are the codes after ilsiters[i] iterations and objs[i]
+    their qerror (mean veccost).  B is left untouched.  Each checkpoint continues the previous call's random stream
+    (t0), so the result equals one uninterrupted run."""
+    X = _as_f32(RX, "RX")
+    Cs = _stack(C)
+    its = [int(i) for i in ilsiters]
+    if not its or min(its) < 1:
+        raise ValueError("ilsiters must list positive iteration counts")
+    B = np.asarray(B)
+    _check(X, Cs, B, max(its), icmiter, npert, nsplits, 0, one_based=True)
+    cur = (B - 1).astype(np.uint8)
+    Bs, objs = [None] * len(its), np.zeros(len(its), dtype=np.float32)
+    done = 0
+    for stop in sorted(set(its)):
+        cur, cost = encode_icm_u8(X, cur, Cs, stop - done, icmiter, npert, randord, seed=seed, t0=done,
+                                  nsplits=nsplits, with_cost=True)
+        done = stop
+        obj = float(np.mean(cost, dtype=np.float64))
+        for i, s in enumerate(its):
+            if s == stop:
+                Bs[i] = cur.astype(np.int16) + 1
+                objs[i] = obj
+        if V:
+            print(" ILS iteration %d/%d done, qerror %e" % (stop, max(its), obj))
+    return Bs, objs
+
+
+def veccost(X, B, C):
+    """Per-row squared reconstruction error (src/qerrors.jl:36-66), B (n, m) Int16 one-based; the device's order of
+    the f32 sums.  Runs the encode kernel with zero iterations."""
+    X = _as_f32(X, "X")
+    Cs = _stack(C)
+    B = np.asarray(B)
+    _check(X, Cs, B, 0, 0, 0, 1, 0, one_based=True)
+    _, cost = encode_icm_u8(X, (B - 1).astype(np.uint8), Cs, 0, 0, 0, False, with_cost=True)
+    return cost
+
+
+def qerror(X, B, C):
+    """Mean veccost (src/qerrors.jl)."""
+    return float(np.mean(veccost(X, B, C), dtype=np.float64))
+
+
+def last_timing():
+    """{unary_ms, total_ms} of this thread's last host-pointer encode (rq_last_icm_timing)."""
+    u, t = ctypes.c_double(0), ctypes.c_double(0)
+    _lib.check(_lib.lib().rq_last_icm_timing(ctypes.cast(ctypes.byref(u), ctypes.c_void_p),
+                                             ctypes.cast(ctypes.byref(t), ctypes.c_void_p)))
+    return dict(unary_ms=u.value, total_ms=t.value)

@@ -48,6 +48,10 @@ SIGNATURES = {
     "rq_encode_rvq_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_train_rvq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_uint64]),
     "rq_dev_encode_rvq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "rq_encode_icm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i64, _i32]),
+    "rq_dev_encode_icm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i64,
+                                 _i32, _vp]),
+    "rq_last_icm_timing": (_i32, [_vp, _vp]),
     "rq_dataset_upload": (_vp, [_vp, _i64, _i32]),
     "rq_dataset_encode": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),
     "rq_dataset_free": (None, [_vp]),
