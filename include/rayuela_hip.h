@@ -132,6 +132,33 @@ int rq_dev_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float *cost_o
 /* milliseconds of this thread's last rq_encode_icm: unaries (hipEvent, summed over chunks) and the whole call */
 int rq_last_icm_timing(double *unary_ms, double *total_ms);
 
+/* ---- LSQ codebook update: update_codebooks(X, B, h, V, "fastbin") (src/codebook_update.jl:235-277) ->
+ * update_codebooks_fast_bin (:175-206) -> fast_bin_matmul (:96-170).  Contract in DESIGN.md section 2.
+ * X [n][d] f32, codes [n][m] uint8 zero-based, 1 <= m <= 16, 2 <= h <= 256, d >= 1, 0 <= n <= 2^32 - 1, rho finite > 0
+ * (the reference's default is 1e-4).  A = B'B + rho I is [mh][mh] f64 with row / column i*h + a (exact integer counts;
+ * the diagonal is fl64(count + rho)), b = B'X is [mh][d] f64 (each entry an f64 sum from +0 over the rows in ascending
+ * order).  C [m][h][d] = (float) A^-1 b, solved in f64 on the device (Cholesky), bitwise reproducible; unused codes get
+ * zero codewords.  Arguments (codes < h included) are checked before any other work; errors through rq_last_error. */
+int rq_update_codebooks_lsq(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho);
+/* device pointers, queued on `stream` (with h < 256 the code range check reads one flag back first) */
+int rq_dev_update_codebooks_lsq(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
+                                double rho, void *stream);
+/* fast_bin_matmul (src/codebook_update.jl:96-170): the normal equations A [mh][mh] and b [mh][d] alone (device) */
+int rq_dev_lsq_normal_eq(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
+                         double rho, void *stream);
+/* train_lsq (src/LSQ.jl:323-372) / train_lsq_cuda (src/LSQ_GPU.jl:267-319), device-resident: C = update(R'X, codes),
+ * C_i <- R C_i, encode; then niter times { obj[iter] = qerror; C = update(X, codes); encode }, rho = 1e-4.  Encode call e
+ * (0 = the initial one) runs ILS iterations e*ilsiter .. (e+1)*ilsiter - 1 of one `seed` stream (rq_encode_icm), so the
+ * result depends on neither nsplits nor the chunking.  C [m][h][d] out; codes [n][m] in: start codes, out: final codes;
+ * obj [niter] f64 out (mean veccost after the previous encode; NaN when n = 0, a mean of no rows); R [d][d] memory image
+ * of Julia's R, NULL = identity. */
+int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h,
+                 int niter, int ilsiter, int icmiter, int npert, int randord, uint64_t seed, int nsplits);
+/* milliseconds of this thread's last rq_update_codebooks_lsq / rq_train_lsq by phase (hipEvents; the device entries leave
+ * zeros), summed over a training call's updates: {counts, sort, b, assemble A, solve, other training work (R'X, the rotation
+ * back, the obj means), encodes (training)}; cap entries written */
+int rq_last_lsq_timing(double *ms, int cap);
+
 /* ---- host-pointer entry points (what the julia/ shims ccall) ----------------------------------
  * rq_encode_*: X is uploaded in ~128 MB chunks while the previous chunk is encoded (the call is PCIe-bound).  With
  * RAYUELA_HIP_DEVICES listing several devices the rows are split over them, one host thread and one PCIe link

@@ -17,7 +17,7 @@ module RayuelaHIP
 import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
-export encoding_icm, encode_icm_cuda
+export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export HipIndex, set_codes!, set_codes_synth!, search, HipDataset, quantize
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
@@ -438,6 +438,61 @@ function encode_icm_cuda(RX::Matrix{Float32}, B::Matrix{Int16}, C::Vector{Matrix
     V && println(" ILS iteration $stop/$(maximum(ilsiters)) done")
   end
   return Bs, objs
+end
+
+# ---- LSQ codebook update (src/codebook_update.jl:175-206, :235-277) and training (src/LSQ.jl:323-372,
+# src/LSQ_GPU.jl:267-319): the normal equations and their f64 solve run on the device (DESIGN.md section 2) ----------
+_split_codebooks(Cc::Matrix{Float32}, m, h) = [Cc[:, (i - 1) * h + 1:i * h] for i = 1:m]
+
+function update_codebooks_fast_bin(X::Matrix{Float32}, B::Matrix{Int16}, h::Integer, V::Bool=false, rho::Float64=1e-4)
+  d, n  = size(X)
+  m     = size(B, 1)
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  _check(ccall((:rq_update_codebooks_lsq, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{UInt8}, Int64, Cint, Cint, Cint, Cdouble),
+    Cc, X, codes, Int64(n), Cint(d), Cint(m), Cint(h), Float64(rho)))
+  V && println("Doing fast bin codebook update... done.")
+  return _split_codebooks(Cc, m, h)
+end
+
+function update_codebooks(X::Matrix{Float32}, B::Matrix{Int16}, h::Integer, V::Bool=false,
+                          method::AbstractString="fastbin")
+  method in ["fast", "fastbin", "lsmr", "lsqr", "naive"] || error("Codebook update method unknown")
+  method == "fastbin" || throw(ArgumentError("codebook update method \"$method\" is not supported; only \"fastbin\" is"))
+  return update_codebooks_fast_bin(X, B, h, V)
+end
+
+function _train_lsq(X::Matrix{Float32}, m, h, R::Matrix{Float32}, B::Matrix{Int16}, niter, ilsiter, icmiter, randord,
+                    npert, seed, nsplits)
+  d, n  = size(X)
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  obj   = zeros(Float64, max(niter, 1))
+  _check(ccall((:rq_train_lsq, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Cint,
+     Cint, UInt64, Cint),
+    Cc, codes, obj, X, R, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), Cint(ilsiter), Cint(icmiter), Cint(npert),
+    Cint(randord ? 1 : 0), UInt64(seed), Cint(nsplits)))
+  return _split_codebooks(Cc, m, h), convert(Matrix{Int16}, codes) .+ Int16(1), convert(Vector{Float32}, obj[1:niter])
+end
+
+function train_lsq(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Float32}, B::Matrix{Int16},
+                   C::Vector{Matrix{Float32}}, niter::Integer, ilsiter::Integer, icmiter::Integer, randord::Bool,
+                   npert::Integer, cpp::Bool=true, V::Bool=true; seed::Integer=0)
+  cpp && h != 256 && throw(ArgumentError("train_lsq with cpp=true requires h = 256 codewords; got h=$h"))
+  Cn, Bn, obj = _train_lsq(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, 1)
+  copyto!(B, Bn)          # the final codes land in B, as encoding_icm's do
+  V && for (it, o) in enumerate(obj); println("$it $o"); end
+  return Cn, Bn, obj
+end
+
+function train_lsq_cuda(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Float32}, B::Matrix{Int16},
+                        C::Vector{Matrix{Float32}}, niter::Integer, ilsiter::Integer, icmiter::Integer, randord::Bool,
+                        npert::Integer, nsplits::Integer=1, V::Bool=false; seed::Integer=0)
+  Cn, Bn, obj = _train_lsq(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits)
+  V && for (it, o) in enumerate(obj); println("$it $o"); end
+  return Cn, Bn, obj
 end
 
 end # module

@@ -134,6 +134,80 @@ def qerror(X, B, C):
     return float(np.mean(veccost(X, B, C), dtype=np.float64))
 
 
+def train_lsq_u8(X, codes0, m, h, R, niter, ilsiter, icmiter, randord, npert, seed=0, nsplits=1):
+    """The device-resident training loop (rq_train_lsq) on zero-based uint8 codes: (C (m, h, d), codes, obj float64).
+    R None = identity (no rotation)."""
+    X = _as_f32(X, "X")
+    n, d = X.shape
+    B = np.asarray(codes0)
+    _check(X, np.empty((m, h, d), np.float32), B, ilsiter, icmiter, npert, nsplits, 0, one_based=False)
+    if int(niter) < 0:
+        raise ValueError("niter must be >= 0; got %d" % niter)
+    if R is not None:
+        R = _as_f32(R, "R")
+        if R.shape != (d, d):
+            raise ValueError("R must be (d, d) = (%d, %d); got %s" % (d, d, R.shape))
+    codes = np.array(B, dtype=np.uint8, order="C")
+    C = np.empty((m, h, d), dtype=np.float32)
+    obj = np.zeros(int(niter), dtype=np.float64)
+    _lib.check(_lib.lib().rq_train_lsq(C.ctypes.data, codes.ctypes.data, obj.ctypes.data if niter else None,
+                                       X.ctypes.data, None if R is None else R.ctypes.data, n, d, m, h, int(niter),
+                                       int(ilsiter), int(icmiter), int(npert), 1 if randord else 0,
+                                       int(seed) & ((1 << 64) - 1), int(nsplits)))
+    return C, codes, obj
+
+
+def _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits, V, label):
+    X = _as_f32(X, "X")
+    B = np.asarray(B)
+    if B.dtype != np.int16:
+        raise TypeError("B must be an Int16 array of one-based codes")
+    n, d = X.shape
+    _check(X, np.empty((m, h, d), np.float32), B, ilsiter, icmiter, npert, nsplits, 0, one_based=True)
+    if V:
+        print("Training %s with %d codebooks, %d perturbations, %d icm iterations and random order = %s"
+              % (label, m, npert, icmiter, bool(randord)))
+    C, codes, obj = train_lsq_u8(X, (B - 1).astype(np.uint8), m, h, R, niter, ilsiter, icmiter, randord, npert,
+                                 seed=seed, nsplits=nsplits)
+    if V:
+        for it, o in enumerate(obj, 1):
+            print("%3d %e " % (it, o))
+    return list(C), codes.astype(np.int16) + 1, obj.astype(np.float32)
+
+
+def train_lsq(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, cpp=True, V=True, seed=0):
+    """train_lsq(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, cpp=true, V=true) -> C, B, obj
+                                                                                          (src/LSQ.jl:323-372)
+    X (n, d) float32, R (d, d) memory image of Julia's R (None = identity), B (n, m) Int16 one-based start codes; the C
+    argument is ignored (the reference overwrites it, :348).  Returns C (m-long list of (h, d)), B (Int16 one-based) and
+    obj (niter,) float32, obj[iter] = qerror before iteration iter's update (NaN when n = 0).  Like encoding_icm, the final codes are also
+    written into B.  cpp=True requires h = 256; both settings run the same device loop (rq_train_lsq)."""
+    if not (isinstance(B, np.ndarray) and B.dtype == np.int16):
+        raise TypeError("B must be an Int16 numpy array (it is updated in place)")
+    if cpp and h != 256:
+        raise ValueError("train_lsq with cpp=true requires h = 256 codewords; got h=%d" % h)
+    Cn, Bn, obj = _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, 1, V, "LSQ")
+    B[...] = Bn
+    return Cn, Bn, obj
+
+
+def train_lsq_cuda(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, nsplits=1, V=False, seed=0):
+    """train_lsq_cuda(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, nsplits=1, V=false) -> C, B, obj
+                                                                                          (src/LSQ_GPU.jl:267-319)
+    As train_lsq, but B is left untouched (encode_icm_cuda returns new codes); the result does not depend on nsplits."""
+    return _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits, V, "LSQ GPU")
+
+
+def last_lsq_timing():
+    """Phase milliseconds of this thread's last host-pointer LSQ update or training call (rq_last_lsq_timing), summed
+    over a training call's updates; the device entries leave zeros.  other_ms: a training call's R'X, rotation back and
+    obj means; encode_ms: its encodes."""
+    out = (ctypes.c_double * 7)()
+    _lib.check(_lib.lib().rq_last_lsq_timing(ctypes.cast(out, ctypes.c_void_p), 7))
+    return dict(zip(["count_ms", "sort_ms", "b_ms", "assemble_ms", "solve_ms", "other_ms", "encode_ms"],
+                    [float(v) for v in out]))
+
+
 def last_timing():
     """{unary_ms, total_ms} of this thread's last host-pointer encode (rq_last_icm_timing)."""
     u, t = ctypes.c_double(0), ctypes.c_double(0)

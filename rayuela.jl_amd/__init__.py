@@ -16,7 +16,8 @@ from .RVQ import quantize_rvq, quantize_rvq_u8  # noqa: F401
 from .PQ import train_pq, kmpp_seeds  # noqa: F401,E402
 from .OPQ import train_opq  # noqa: F401,E402
 from .RVQ import train_rvq  # noqa: F401,E402
-from .LSQ import encoding_icm, encode_icm_cuda, veccost, qerror  # noqa: F401,E402
+from .LSQ import encoding_icm, encode_icm_cuda, veccost, qerror, train_lsq, train_lsq_cuda  # noqa: F401,E402
+from .codebook_update import update_codebooks, update_codebooks_fast_bin  # noqa: F401,E402
 from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_aqd_query, LsqIndex,  # noqa: F401
                       linscan_aqd_query_extra_byte, eval_recall)
 
@@ -25,4 +26,5 @@ from . import h5results  # noqa: F401,E402  (libhdf5 is looked up lazily, on fir
 from . import datasets  # noqa: F401,E402
 
 __all__ = ["quantize_pq", "quantize_opq", "linscan_pq", "linscan_opq", "linscan_lsq", "linscan_cq",
-           "encoding_icm", "encode_icm_cuda", "eval_recall", "splitarray"]
+           "encoding_icm", "encode_icm_cuda", "train_lsq", "train_lsq_cuda", "update_codebooks",
+           "update_codebooks_fast_bin", "eval_recall", "splitarray"]

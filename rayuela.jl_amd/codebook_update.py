@@ -1,0 +1,75 @@
+"""Host mirror of the LSQ codebook update (src/codebook_update.jl): update_codebooks (:235-277) with the "fastbin"
+method, update_codebooks_fast_bin (:175-206) and its normal equations fast_bin_matmul (:96-170).
+
+The normal equations (B'B + rho I) C = B'X of the one-hot codes are built and solved in f64 on the device
+(rq_update_codebooks_lsq); the contract is DESIGN.md section 2.  X is (n, d) float32, B (n, m) Int16 one-based like the
+reference's m-by-n matrices; the result is an m-long list of (h, d) codebooks (memory image of Julia's d-by-h
+matrices)."""
+import numpy as np
+
+from . import _lib
+from .utils import _as_f32
+
+MAX_M = 16
+METHODS = ("fast", "fastbin", "lsmr", "lsqr", "naive")      # src/codebook_update.jl:242
+
+
+def _check_update(n, d, codes_shape, m, h, rho):
+    """Every argument check of the update runs here, before the library (and the device) is touched."""
+    if len(codes_shape) != 2 or codes_shape[0] != n:
+        raise ValueError("codes must be (n, m) with n = %d rows; got %s" % (n, tuple(codes_shape)))
+    if not 1 <= m <= MAX_M:
+        raise ValueError("the LSQ update covers 1 <= m <= %d codebooks; got m=%d" % (MAX_M, m))
+    if not 2 <= int(h) <= 256:
+        raise ValueError("the LSQ update covers 2 <= h <= 256 codewords; got h=%d" % h)
+    if d < 1:
+        raise ValueError("d must be >= 1; got %d" % d)
+    if n > 2 ** 32 - 1:
+        raise ValueError("n=%d rows exceed the update's 32-bit counters" % n)
+    rho = float(rho)
+    if not (np.isfinite(rho) and rho > 0):
+        raise ValueError("rho must be finite and > 0; got %r" % rho)
+    return rho
+
+
+def update_codebooks_u8(X, codes, h, rho=1e-4):
+    """Zero-based uint8 codes (n, m) -> codebooks as one (m, h, d) float32 array."""
+    X = _as_f32(X, "X")
+    codes = np.asarray(codes)
+    n, d = X.shape
+    m = codes.shape[1] if codes.ndim == 2 else -1
+    rho = _check_update(n, d, codes.shape, m, h, rho)
+    if codes.size and (codes.min() < 0 or codes.max() > h - 1):
+        raise ValueError("codes must be in 0..%d" % (h - 1))
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    C = np.empty((m, h, d), dtype=np.float32)
+    _lib.check(_lib.lib().rq_update_codebooks_lsq(C.ctypes.data, X.ctypes.data, codes.ctypes.data, n, d, m, int(h), rho))
+    return C
+
+
+def update_codebooks_fast_bin(X, B, h, V=False, rho=1e-4):
+    """update_codebooks_fast_bin(X, B, h, V=false, rho=1e-4) -> C       (src/codebook_update.jl:175-206)
+
+    X (n, d) float32, B (n, m) Int16 one-based.  Returns an m-long list of (h, d) float32 codebooks."""
+    X = _as_f32(X, "X")
+    B = np.asarray(B)
+    n, d = X.shape
+    m = B.shape[1] if B.ndim == 2 else -1
+    _check_update(n, d, B.shape, m, h, rho)
+    if B.size and (B.min() < 1 or B.max() > h):
+        raise ValueError("codes must be in 1..%d" % h)
+    C = update_codebooks_u8(X, (B - 1).astype(np.uint8), h, rho)
+    if V:
+        print("Doing fast bin codebook update... done.")
+    return list(C)
+
+
+def update_codebooks(X, B, h, V=False, method="fastbin"):
+    """update_codebooks(X, B, h, V=false, method="fastbin") -> C       (src/codebook_update.jl:235-277)
+
+    Only "fastbin" runs here; any other method raises ValueError naming it."""
+    if method not in METHODS:
+        raise ValueError("Codebook update method unknown: %r" % (method,))
+    if method != "fastbin":
+        raise ValueError("codebook update method %r is not supported; only \"fastbin\" is" % (method,))
+    return update_codebooks_fast_bin(X, B, h, V)

@@ -280,6 +280,27 @@ __global__ __launch_bounds__(256) void icm_code_range_kernel(unsigned int *bad, 
     if (codes[i] >= h) { atomicOr(bad, 1u); return; }
 }
 
+}  // namespace
+
+// codes < h on the device: one flag word, read back before any other work is queued
+int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t s, const char *who) {
+  if (h >= 256 || n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  void *wf = nullptr;
+  RQ_TRY(workspace(WS_TMP, 256, &wf, s));
+  RQ_HIP(hipMemsetAsync(wf, 0, 4, s));
+  const int64_t nelem = n * m;
+  const int grid = (int)std::min<int64_t>((nelem + 255) / 256, 4096);
+  hipLaunchKernelGGL(icm_code_range_kernel, dim3(grid), dim3(256), 0, s, (unsigned int *)wf, codes, nelem, h);
+  RQ_HIP(hipGetLastError());
+  unsigned int bad = 0;
+  RQ_HIP(hipMemcpyAsync(&bad, wf, 4, hipMemcpyDeviceToHost, s));
+  RQ_HIP(hipStreamSynchronize(s));
+  if (bad) return fail(RQ_EINVAL, "%s: a code is >= h=%d", who, h);
+  return RQ_OK;
+}
+
 int icm_check_args(const void *codes_out, const void *codes_in, const void *X, const void *C, int64_t n, int d, int m,
                    int h, int ilsiter, int icmiter, int npert, int64_t t0, int nsplits) {
   if (m < 1 || m > ICM_MAX_M) return fail(RQ_EINVAL, "encode_icm: m=%d outside 1..%d", m, ICM_MAX_M);
@@ -357,6 +378,8 @@ int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out,
   return rc;
 }
 
+namespace {
+
 struct IcmBuf {
   void *p = nullptr;
   ~IcmBuf() { if (p) (void)hipFree(p); }
@@ -380,21 +403,7 @@ extern "C" int rq_dev_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, fl
   RQ_TRY(icm_check_args(codes_out, codes_in, X, C, n, d, m, h, ilsiter, icmiter, npert, t0, nsplits));
   if (n == 0) return RQ_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (h < 256) {   // codes < h: one flag word, read back before any encode work is queued
-    DeviceInfo di;
-    RQ_TRY(device_info(&di));
-    void *wf = nullptr;
-    RQ_TRY(workspace(WS_TMP, 256, &wf, s));
-    RQ_HIP(hipMemsetAsync(wf, 0, 4, s));
-    const int64_t nelem = n * m;
-    const int grid = (int)std::min<int64_t>((nelem + 255) / 256, 4096);
-    hipLaunchKernelGGL(icm_code_range_kernel, dim3(grid), dim3(256), 0, s, (unsigned int *)wf, codes_in, nelem, h);
-    RQ_HIP(hipGetLastError());
-    unsigned int bad = 0;
-    RQ_HIP(hipMemcpyAsync(&bad, wf, 4, hipMemcpyDeviceToHost, s));
-    RQ_HIP(hipStreamSynchronize(s));
-    if (bad) return fail(RQ_EINVAL, "encode_icm: a code is >= h=%d", h);
-  }
+  RQ_TRY(dev_code_range(codes_in, n, m, h, s, "encode_icm"));
   return icm_encode_dev(codes_out, codes_in, cost_out, X, C, n, d, m, h, ilsiter, icmiter, npert, randord, seed, t0,
                         nsplits, s, nullptr);
 }

@@ -1,0 +1,627 @@
+// rq_lsq.hip -- LSQ codebook update (src/codebook_update.jl:96-206 fast_bin_matmul / update_codebooks_fast_bin, the
+// "fastbin" method of update_codebooks :235-277) and the LSQ training loop (src/LSQ.jl:323-372 train_lsq,
+// src/LSQ_GPU.jl:267-319 train_lsq_cuda) on gfx950; contract in DESIGN.md section 2.
+//
+// The normal equations (B'B + rho I) C = B'X of the one-hot code matrix B:
+//   lsq_tile_hist_kernel   per (tile of LSQ_TILE rows, codebook): LDS histogram of the codes (integer atomics)
+//   lsq_scan_kernel        per codebook: exclusive scan over (code, tile) -> each tile's first slot per code, and the
+//                          segment bounds segs[i][a] (segs[i][a+1] - segs[i][a] = count_i(a))
+//   lsq_scatter_kernel     per (tile, codebook): stable counting sort of the row ids by code (ballot match per wavefront)
+//   lsq_pair_kernel        pair counts of codebooks i < j into a u32 mh x mh matrix (integer atomics: exact, order-free)
+//   lsq_bsum_kernel        b[(i,a)][k] = sum over the rows of segment (i,a), ascending, in f64 from +0, lanes over k
+//   lsq_assemble_kernel    A = the full symmetric matrix, fl64(count + rho) on the diagonal
+// The solve: blocked right-looking Cholesky A = L L' (NB = 64; one-workgroup diagonal factor, a row-per-thread panel
+// solve and an f64 SYRK/GEMM update of the trailing matrix), forward and back substitution with d right-hand sides,
+// then C = (float) A^-1 b in the [m][h][d] image rq_encode_icm reads.  Every sum runs in a fixed order and no float
+// atomic is used, so the result is bitwise reproducible.
+#include "rq_internal.h"
+
+#include <math.h>
+
+#include <vector>
+
+namespace rq {
+
+namespace {
+
+constexpr int LSQ_MAX_M = 16;
+constexpr int LSQ_TILE = 4096;   // rows per tile of the bucket sort
+constexpr int NB = 64;           // Cholesky block
+constexpr int GT = 64;           // output tile of the GEMM update
+constexpr int KC = 32;           // K chunk of the GEMM update staged in LDS
+
+// ---- counting sort of the row ids by code, per codebook ------------------------------------------------------------
+__global__ __launch_bounds__(256) void lsq_tile_hist_kernel(uint32_t *th, const uint8_t *codes, int64_t n, int m, int h,
+                                                            int ntiles) {
+  __shared__ uint32_t hist[256];
+  const int tile = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
+  hist[tid] = 0;
+  __syncthreads();
+  const int64_t r0 = (int64_t)tile * LSQ_TILE, r1 = std::min<int64_t>(n, r0 + LSQ_TILE);
+  for (int64_t r = r0 + tid; r < r1; r += 256) atomicAdd(&hist[codes[r * m + i]], 1u);
+  __syncthreads();
+  if (tid < h) th[((size_t)i * h + tid) * ntiles + tile] = hist[tid];
+}
+
+// th[i] (h x ntiles, code-major) -> exclusive prefix sums in place; segs[i][a] = first slot of code a, segs[i][h] = n
+__global__ __launch_bounds__(256) void lsq_scan_kernel(uint32_t *th, uint32_t *segs, int64_t n, int h, int ntiles) {
+  __shared__ uint32_t part[256];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  uint32_t *t = th + (size_t)i * h * ntiles;
+  const int64_t L = (int64_t)h * ntiles, chunk = (L + 255) / 256;
+  const int64_t beg = std::min<int64_t>(L, tid * chunk), end = std::min<int64_t>(L, beg + chunk);
+  uint32_t s = 0;
+  for (int64_t j = beg; j < end; ++j) s += t[j];
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t run = 0;
+    for (int q = 0; q < 256; ++q) {
+      const uint32_t v = part[q];
+      part[q] = run;
+      run += v;
+    }
+  }
+  __syncthreads();
+  uint32_t run = part[tid];
+  for (int64_t j = beg; j < end; ++j) {
+    const uint32_t v = t[j];
+    t[j] = run;
+    if (j % ntiles == 0) segs[(size_t)i * (h + 1) + j / ntiles] = run;
+    run += v;
+  }
+  if (tid == 0) segs[(size_t)i * (h + 1) + h] = (uint32_t)n;
+}
+
+// Rows of a tile in passes of 256 (4 wavefronts x 64 lanes, ascending); a lane's slot = the code's running slot + the
+// counts of the same code in earlier wavefronts of the pass + its rank among the lanes of its wavefront with that code.
+__global__ __launch_bounds__(256) void lsq_scatter_kernel(uint32_t *sorted, const uint32_t *th, const uint8_t *codes,
+                                                          int64_t n, int m, int h, int ntiles) {
+  __shared__ uint32_t run[256];
+  __shared__ uint32_t wc[4][256];
+  const int tile = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  if (tid < h) run[tid] = th[((size_t)i * h + tid) * ntiles + tile];
+  for (int q = 0; q < 4; ++q) wc[q][tid] = 0;
+  __syncthreads();
+  uint32_t *out = sorted + (size_t)i * n;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int64_t r0 = (int64_t)tile * LSQ_TILE, r1 = std::min<int64_t>(n, r0 + LSQ_TILE);
+  for (int64_t p0 = r0; p0 < r1; p0 += 256) {
+    const int64_t r = p0 + tid;
+    const bool valid = r < r1;
+    const int c = valid ? (int)codes[r * m + i] : 0;
+    uint64_t mask = __ballot(valid);
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+      const bool on = (c >> bit) & 1;
+      const uint64_t bb = __ballot(valid && on);
+      mask &= on ? bb : ~bb;
+    }
+    const uint32_t rank = (uint32_t)__popcll(mask & lt);
+    if (valid && rank == 0) wc[w][c] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (valid) {
+      uint32_t pos = run[c] + rank;
+      for (int q = 0; q < w; ++q) pos += wc[q][c];
+      out[pos] = (uint32_t)r;
+    }
+    __syncthreads();
+    if (tid < h) {
+      run[tid] += wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
+      wc[0][tid] = wc[1][tid] = wc[2][tid] = wc[3][tid] = 0;
+    }
+    __syncthreads();
+  }
+}
+
+// ---- A -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lsq_pair_kernel(uint32_t *P, const uint8_t *codes, int64_t n, int m, int h) {
+  const int mh = m * h;
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+    int b[LSQ_MAX_M];
+#pragma unroll
+    for (int i = 0; i < LSQ_MAX_M; ++i) b[i] = i < m ? i * h + (int)codes[r * m + i] : 0;
+#pragma unroll
+    for (int i = 0; i < LSQ_MAX_M; ++i)
+#pragma unroll
+      for (int j = i + 1; j < LSQ_MAX_M; ++j)
+        if (j < m) atomicAdd(&P[(size_t)b[i] * mh + b[j]], 1u);
+  }
+}
+
+__global__ __launch_bounds__(256) void lsq_assemble_kernel(double *A, const uint32_t *P, const uint32_t *segs, int m,
+                                                           int h, double rho) {
+  const int mh = m * h;
+  const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+  if (c >= mh) return;
+  const int i = r / h, a = r - i * h, j = c / h;
+  double v;
+  if (i == j) {
+    const uint32_t *s = segs + (size_t)i * (h + 1);
+    v = (r == c) ? (double)(s[a + 1] - s[a]) + rho : 0.0;
+  } else {
+    v = (double)(i < j ? P[(size_t)r * mh + c] : P[(size_t)c * mh + r]);
+  }
+  A[(size_t)r * mh + c] = v;
+}
+
+// ---- b -------------------------------------------------------------------------------------------------------------
+// one workgroup per (codebook, code) segment; thread t sums dims t, t + blockDim, ... over the segment's rows in order
+__global__ __launch_bounds__(256) void lsq_bsum_kernel(double *b, const float *X, const uint32_t *sorted,
+                                                       const uint32_t *segs, int64_t n, int d, int h) {
+  const int seg = blockIdx.x, i = seg / h, a = seg - i * h;
+  const uint32_t beg = segs[(size_t)i * (h + 1) + a], end = segs[(size_t)i * (h + 1) + a + 1];
+  const uint32_t *ids = sorted + (size_t)i * n;
+  for (int k = threadIdx.x; k < d; k += blockDim.x) {
+    double acc = 0.0;
+    int64_t j = beg;
+    for (; j + 8 <= (int64_t)end; j += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = X[(size_t)ids[j + u] * d + k];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc = acc + (double)v[u];
+    }
+    for (; j < (int64_t)end; ++j) acc = acc + (double)X[(size_t)ids[j] * d + k];
+    b[(size_t)seg * d + k] = acc;
+  }
+}
+
+// ---- the SPD solve -------------------------------------------------------------------------------------------------
+// A[k..k+nb) x [k..k+nb) (lower triangle) <- its Cholesky factor; one workgroup, the block in LDS
+__global__ __launch_bounds__(256) void lsq_chol_diag_kernel(double *A, int mh, int k, int nb) {
+  __shared__ double T[NB][NB + 1];
+  const int tid = threadIdx.x;
+  for (int e = tid; e < nb * nb; e += 256) {
+    const int r = e / nb, c = e - r * nb;
+    T[r][c] = c <= r ? A[(size_t)(k + r) * mh + k + c] : 0.0;
+  }
+  __syncthreads();
+  for (int j = 0; j < nb; ++j) {
+    if (tid == 0) T[j][j] = sqrt(T[j][j]);
+    __syncthreads();
+    if (tid > j && tid < nb) T[tid][j] = T[tid][j] / T[j][j];
+    __syncthreads();
+    for (int e = tid; e < nb * nb; e += 256) {
+      const int r = e / nb, c = e - r * nb;
+      if (c > j && c <= r) T[r][c] = __builtin_fma(-T[r][j], T[c][j], T[r][c]);
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < nb * nb; e += 256) {
+    const int r = e / nb, c = e - r * nb;
+    if (c <= r) A[(size_t)(k + r) * mh + k + c] = T[r][c];
+  }
+}
+
+// the panel below the diagonal block: row t of this workgroup solves x L_kk' = a (sequential in the column index)
+__global__ __launch_bounds__(64) void lsq_chol_panel_kernel(double *A, int mh, int k, int nb) {
+  __shared__ double L[NB][NB];
+  __shared__ double PT[NB][64];   // PT[col][row]: lane-consecutive rows, no bank conflicts
+  const int t = threadIdx.x;
+  const int i0 = k + nb + blockIdx.x * 64;
+  for (int e = t; e < nb * nb; e += 64) {
+    const int r = e / nb, c = e - r * nb;
+    L[r][c] = A[(size_t)(k + r) * mh + k + c];
+  }
+  const int rows = std::min(64, mh - i0);
+  for (int e = t; e < rows * nb; e += 64) {
+    const int r = e / nb, c = e - r * nb;
+    PT[c][r] = A[(size_t)(i0 + r) * mh + k + c];
+  }
+  __syncthreads();
+  if (t < rows) {
+    for (int j = 0; j < nb; ++j) {
+      double x = PT[j][t];
+      for (int l = 0; l < j; ++l) x = __builtin_fma(-PT[l][t], L[j][l], x);
+      PT[j][t] = x / L[j][j];
+    }
+  }
+  __syncthreads();
+  for (int e = t; e < rows * nb; e += 64) {
+    const int r = e / nb, c = e - r * nb;
+    A[(size_t)(i0 + r) * mh + k + c] = PT[c][r];
+  }
+}
+
+// D(i, j) -= sum_{kk < K} P(i, kk) Q(j, kk), i < M, j < N (lower: j <= i only); P(i, kk) = P[i * ps0 + kk * ps1],
+// Q likewise.  64 x 64 outputs per workgroup, 4 x 4 per thread, the K sum in ascending kk from +0, then one subtraction.
+__global__ __launch_bounds__(256) void lsq_gemm_sub_kernel(double *D, int64_t ldd, int M, int N, const double *P,
+                                                           int64_t ps0, int64_t ps1, const double *Q, int64_t qs0,
+                                                           int64_t qs1, int K, int lower) {
+  __shared__ double Ps[KC][GT];
+  __shared__ double Qs[KC][GT];
+  const int i0 = blockIdx.y * GT, j0 = blockIdx.x * GT;
+  if (lower && j0 > i0 + GT - 1) return;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  double acc[4][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
+  for (int k0 = 0; k0 < K; k0 += KC) {
+    for (int e = tid; e < KC * GT; e += 256) {
+      int kk, ii;
+      if (ps1 == 1) { kk = e % KC; ii = e / KC; } else { ii = e % GT; kk = e / GT; }
+      Ps[kk][ii] = (i0 + ii < M && k0 + kk < K) ? P[(int64_t)(i0 + ii) * ps0 + (int64_t)(k0 + kk) * ps1] : 0.0;
+      int kq, jj;
+      if (qs1 == 1) { kq = e % KC; jj = e / KC; } else { jj = e % GT; kq = e / GT; }
+      Qs[kq][jj] = (j0 + jj < N && k0 + kq < K) ? Q[(int64_t)(j0 + jj) * qs0 + (int64_t)(k0 + kq) * qs1] : 0.0;
+    }
+    __syncthreads();
+    const int kn = std::min(KC, K - k0);
+    for (int kk = 0; kk < kn; ++kk) {
+      double p[4], q[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) p[u] = Ps[kk][ty + 16 * u];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) q[v] = Qs[kk][tx + 16 * v];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[u][v] = __builtin_fma(p[u], q[v], acc[u][v]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int i = i0 + ty + 16 * u, j = j0 + tx + 16 * v;
+      if (i < M && j < N && (!lower || j <= i)) D[(int64_t)i * ldd + j] -= acc[u][v];
+    }
+}
+
+// Y[k..k+nb) <- L_kk^-1 Y[k..k+nb) (fwd) or L_kk'^-1 Y[k..k+nb) (!fwd); thread t owns column j0 + t
+__global__ __launch_bounds__(64) void lsq_trsv_block_kernel(double *Y, const double *A, int mh, int d, int k, int nb,
+                                                            int fwd) {
+  __shared__ double L[NB][NB];
+  __shared__ double Ys[NB][64];
+  const int t = threadIdx.x, j = blockIdx.x * 64 + t;
+  for (int e = t; e < nb * nb; e += 64) {
+    const int r = e / nb, c = e - r * nb;
+    L[r][c] = A[(size_t)(k + r) * mh + k + c];
+  }
+  const bool ok = j < d;
+  for (int r = 0; r < nb; ++r) Ys[r][t] = ok ? Y[(size_t)(k + r) * d + j] : 0.0;
+  __syncthreads();
+  if (fwd) {
+    for (int r = 0; r < nb; ++r) {
+      double x = Ys[r][t];
+      for (int l = 0; l < r; ++l) x = __builtin_fma(-L[r][l], Ys[l][t], x);
+      Ys[r][t] = x / L[r][r];
+    }
+  } else {
+    for (int r = nb - 1; r >= 0; --r) {
+      double x = Ys[r][t];
+      for (int l = r + 1; l < nb; ++l) x = __builtin_fma(-L[l][r], Ys[l][t], x);
+      Ys[r][t] = x / L[r][r];
+    }
+  }
+  if (ok)
+    for (int r = 0; r < nb; ++r) Y[(size_t)(k + r) * d + j] = Ys[r][t];
+}
+
+__global__ __launch_bounds__(256) void lsq_to_f32_kernel(float *C, const double *Y, int64_t cnt) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (int64_t)gridDim.x * 256)
+    C[e] = (float)Y[e];
+}
+
+// obj = mean of the per-row costs: f64, each thread a strided sum in row order, then a fixed LDS tree
+__global__ __launch_bounds__(1024) void lsq_mean_kernel(double *out, const float *cost, int64_t n) {
+  __shared__ double part[1024];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int64_t r = tid; r < n; r += 1024) s = s + (double)cost[r];
+  part[tid] = s;
+  __syncthreads();
+  for (int off = 512; off >= 1; off >>= 1) {
+    if (tid < off) part[tid] = part[tid] + part[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) *out = part[0] / (double)n;
+}
+
+int lsq_check(const void *out0, const void *out1, const void *X, const void *codes, int64_t n, int d, int m, int h,
+              double rho, const char *who) {
+  if (m < 1 || m > LSQ_MAX_M) return fail(RQ_EINVAL, "%s: m=%d outside 1..%d", who, m, LSQ_MAX_M);
+  if (h < 2 || h > 256) return fail(RQ_EINVAL, "%s: h=%d outside 2..256", who, h);
+  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
+  if (n < 0 || n > (int64_t)UINT32_MAX)
+    return fail(RQ_EINVAL, "%s: n=%lld outside 0..%u (the u32 counters)", who, (long long)n, UINT32_MAX);
+  if (!(rho > 0.0) || !isfinite(rho)) return fail(RQ_EINVAL, "%s: rho=%g must be finite and > 0", who, rho);
+  if (!out0 || !out1) return fail(RQ_EINVAL, "%s: null output pointer", who);
+  if (n > 0 && (!X || !codes)) return fail(RQ_EINVAL, "%s: null pointer", who);
+  return RQ_OK;
+}
+
+// Phase clock of the host-pointer entries (which synchronise anyway): hipEvents between the phases of the calling
+// thread's last call, read at its end.  The device entries queue no events and leave the clock at zero.
+// PH_OTHER: what a training call queues besides the updates and encodes (R'X, the rotation back, the obj means)
+enum { PH_COUNT, PH_SORT, PH_B, PH_ASSEMBLE, PH_SOLVE, PH_OTHER, PH_ENCODE, PH_N };
+thread_local double g_lsq_ms[PH_N] = {0};
+
+struct PhaseClock {
+  bool on;
+  hipStream_t s;
+  std::vector<std::pair<int, hipEvent_t>> marks;   // (phase ending here, event)
+  hipEvent_t first = nullptr;
+  PhaseClock(hipStream_t st, bool want) : on(want), s(st) {
+    if (on && hipEventCreate(&first) == hipSuccess) (void)hipEventRecord(first, s);
+    else on = false;
+  }
+  void mark(int phase) {
+    if (!on) return;
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return;
+    (void)hipEventRecord(e, s);
+    marks.push_back({phase, e});
+  }
+  // accumulate the intervals into g_lsq_ms (interval = previous mark .. this mark)
+  void collect() {
+    if (!on) return;
+    (void)hipStreamSynchronize(s);
+    hipEvent_t prev = first;
+    for (auto &pe : marks) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) g_lsq_ms[pe.first] += ms;
+      prev = pe.second;
+    }
+  }
+  ~PhaseClock() {
+    for (auto &pe : marks) (void)hipEventDestroy(pe.second);
+    if (first) (void)hipEventDestroy(first);
+  }
+};
+
+// A [mh][mh], b [mh][d] f64 (device pointers; arguments checked, codes in range)
+int normal_eq_dev(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
+                  hipStream_t s, PhaseClock &clk) {
+  const int mh = m * h;
+  const int ntiles = (int)std::max<int64_t>(1, (n + LSQ_TILE - 1) / LSQ_TILE);
+  const size_t pair_bytes = (size_t)mh * mh * 4, th_bytes = (size_t)m * h * ntiles * 4;
+  const size_t seg_bytes = ((size_t)m * (h + 1) * 4 + 255) & ~(size_t)255;
+  const size_t sort_bytes = (size_t)m * n * 4;
+  void *ws = nullptr;
+  RQ_TRY(workspace(WS_LSQ_S, pair_bytes + th_bytes + seg_bytes + sort_bytes, &ws, s));
+  uint32_t *P = (uint32_t *)ws, *th = P + pair_bytes / 4, *segs = th + th_bytes / 4, *sorted = segs + seg_bytes / 4;
+  RQ_HIP(hipMemsetAsync(P, 0, pair_bytes, s));
+  RQ_HIP(hipMemsetAsync(th, 0, th_bytes, s));
+  if (n > 0 && m > 1) {
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(lsq_pair_kernel, dim3(grid), dim3(256), 0, s, P, codes, n, m, h);
+    RQ_HIP(hipGetLastError());
+  }
+  clk.mark(PH_COUNT);
+  if (n > 0) {
+    hipLaunchKernelGGL(lsq_tile_hist_kernel, dim3(ntiles, m), dim3(256), 0, s, th, codes, n, m, h, ntiles);
+    RQ_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(lsq_scan_kernel, dim3(m), dim3(256), 0, s, th, segs, n, h, ntiles);
+  RQ_HIP(hipGetLastError());
+  if (n > 0) {
+    hipLaunchKernelGGL(lsq_scatter_kernel, dim3(ntiles, m), dim3(256), 0, s, sorted, th, codes, n, m, h, ntiles);
+    RQ_HIP(hipGetLastError());
+  }
+  clk.mark(PH_SORT);
+  const int bt = d <= 64 ? 64 : d <= 128 ? 128 : 256;
+  hipLaunchKernelGGL(lsq_bsum_kernel, dim3(mh), dim3(bt), 0, s, b, X, sorted, segs, n, d, h);
+  RQ_HIP(hipGetLastError());
+  clk.mark(PH_B);
+  hipLaunchKernelGGL(lsq_assemble_kernel, dim3((mh + 255) / 256, mh), dim3(256), 0, s, A, P, segs, m, h, rho);
+  RQ_HIP(hipGetLastError());
+  clk.mark(PH_ASSEMBLE);
+  return RQ_OK;
+}
+
+#define LSQ_LAUNCH(...)                 \
+  do {                                  \
+    hipLaunchKernelGGL(__VA_ARGS__);    \
+    RQ_HIP(hipGetLastError());          \
+  } while (0)
+
+// A <- its Cholesky factor (lower), Y [mh][d] <- A^-1 Y
+int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
+  for (int k = 0; k < mh; k += NB) {
+    const int nb = std::min(NB, mh - k), rest = mh - k - nb;
+    LSQ_LAUNCH(lsq_chol_diag_kernel, dim3(1), dim3(256), 0, s, A, mh, k, nb);
+    if (rest > 0) {
+      LSQ_LAUNCH(lsq_chol_panel_kernel, dim3((rest + 63) / 64), dim3(64), 0, s, A, mh, k, nb);
+      double *pan = A + (size_t)(k + nb) * mh + k;
+      const unsigned tiles = (unsigned)((rest + GT - 1) / GT);
+      LSQ_LAUNCH(lsq_gemm_sub_kernel, dim3(tiles, tiles), dim3(256), 0, s, pan + nb, (int64_t)mh, rest, rest,
+                 (const double *)pan, (int64_t)mh, (int64_t)1, (const double *)pan, (int64_t)mh, (int64_t)1, nb, 1);
+    }
+  }
+  const unsigned cgrid = (unsigned)((d + 63) / 64), ntile = (unsigned)((d + GT - 1) / GT);
+  for (int k = 0; k < mh; k += NB) {   // L y = b
+    const int nb = std::min(NB, mh - k), rest = mh - k - nb;
+    LSQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 1);
+    if (rest > 0)
+      LSQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((rest + GT - 1) / GT)), dim3(256), 0, s,
+                 Y + (size_t)(k + nb) * d, (int64_t)d, rest, d, (const double *)(A + (size_t)(k + nb) * mh + k),
+                 (int64_t)mh, (int64_t)1, (const double *)(Y + (size_t)k * d), (int64_t)1, (int64_t)d, nb, 0);
+  }
+  for (int k = ((mh - 1) / NB) * NB; k >= 0; k -= NB) {   // L' x = y
+    const int nb = std::min(NB, mh - k);
+    LSQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 0);
+    if (k > 0)
+      LSQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((k + GT - 1) / GT)), dim3(256), 0, s, Y, (int64_t)d, k, d,
+                 (const double *)(A + (size_t)k * mh), (int64_t)1, (int64_t)mh, (const double *)(Y + (size_t)k * d),
+                 (int64_t)1, (int64_t)d, nb, 0);
+  }
+  return RQ_OK;
+}
+
+// C [m][h][d] f32 <- the fastbin update of (X, codes) (device pointers; arguments checked, codes in range)
+int update_dev(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho, hipStream_t s,
+               PhaseClock &clk) {
+  const int mh = m * h;
+  void *wa = nullptr, *wb = nullptr;
+  RQ_TRY(workspace(WS_LSQ_A, (size_t)mh * mh * 8, &wa, s));
+  RQ_TRY(workspace(WS_LSQ_B, (size_t)mh * d * 8, &wb, s));
+  double *A = (double *)wa, *b = (double *)wb;
+  RQ_TRY(normal_eq_dev(A, b, X, codes, n, d, m, h, rho, s, clk));
+  RQ_TRY(spd_solve_dev(A, b, mh, d, s));
+  const int64_t cnt = (int64_t)mh * d;
+  LSQ_LAUNCH(lsq_to_f32_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, s, C,
+             (const double *)b, cnt);
+  clk.mark(PH_SOLVE);
+  return RQ_OK;
+}
+
+struct LsqBuf {
+  void *p = nullptr;
+  ~LsqBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t bytes) {
+    RQ_HIP(hipMalloc(&p, bytes ? bytes : 16));
+    return RQ_OK;
+  }
+};
+
+void lsq_clock_reset() {
+  for (int q = 0; q < PH_N; ++q) g_lsq_ms[q] = 0;
+}
+
+}  // namespace
+
+}  // namespace rq
+
+using namespace rq;
+
+extern "C" int rq_dev_lsq_normal_eq(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m,
+                                    int h, double rho, void *stream) {
+  RQ_TRY(lsq_check(A, b, X, codes, n, d, m, h, rho, "lsq_normal_eq"));
+  hipStream_t s = (hipStream_t)stream;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  RQ_TRY(dev_code_range(codes, n, m, h, s, "lsq_normal_eq"));
+  lsq_clock_reset();
+  PhaseClock clk(s, false);
+  RQ_TRY(normal_eq_dev(A, b, X, codes, n, d, m, h, rho, s, clk));
+  return RQ_OK;
+}
+
+extern "C" int rq_dev_update_codebooks_lsq(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m,
+                                           int h, double rho, void *stream) {
+  RQ_TRY(lsq_check(C, C, X, codes, n, d, m, h, rho, "update_codebooks_lsq"));
+  hipStream_t s = (hipStream_t)stream;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  RQ_TRY(dev_code_range(codes, n, m, h, s, "update_codebooks_lsq"));
+  lsq_clock_reset();
+  PhaseClock clk(s, false);
+  RQ_TRY(update_dev(C, X, codes, n, d, m, h, rho, s, clk));
+  return RQ_OK;
+}
+
+extern "C" int rq_update_codebooks_lsq(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
+                                       double rho) {
+  RQ_TRY(lsq_check(C, C, X, codes, n, d, m, h, rho, "update_codebooks_lsq"));
+  for (int64_t e = 0; e < n * m; ++e)
+    if (codes[e] >= h)
+      return fail(RQ_EINVAL, "update_codebooks_lsq: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
+                  (long long)(e % m), h);
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  LsqBuf dX, dcodes, dC;
+  RQ_TRY(dX.alloc((size_t)n * d * 4));
+  RQ_TRY(dcodes.alloc((size_t)n * m));
+  RQ_TRY(dC.alloc((size_t)m * h * d * 4));
+  if (n > 0) {
+    RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
+  }
+  lsq_clock_reset();
+  PhaseClock clk(nullptr, true);
+  RQ_TRY(update_dev((float *)dC.p, (const float *)dX.p, (const uint8_t *)dcodes.p, n, d, m, h, rho, nullptr, clk));
+  clk.collect();
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(C, dC.p, (size_t)m * h * d * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+extern "C" int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m,
+                            int h, int niter, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
+                            int nsplits) {
+  RQ_TRY(lsq_check(C, codes ? codes : (const void *)C, X, codes, n, d, m, h, 1e-4, "train_lsq"));
+  if (!codes) return fail(RQ_EINVAL, "train_lsq: null codes");
+  if (niter < 0) return fail(RQ_EINVAL, "train_lsq: niter=%d < 0", niter);
+  if (niter > 0 && !obj) return fail(RQ_EINVAL, "train_lsq: null obj");
+  if ((int64_t)ilsiter * ((int64_t)niter + 1) > INT32_MAX)
+    return fail(RQ_EINVAL, "train_lsq: ilsiter * (niter + 1) overflows the ILS iteration counter");
+  RQ_TRY(icm_check_args(codes, codes, X, C, n, d, m, h, ilsiter, icmiter, npert, 0, nsplits));
+  for (int64_t e = 0; e < n * m; ++e)
+    if (codes[e] >= h)
+      return fail(RQ_EINVAL, "train_lsq: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
+                  (long long)(e % m), h);
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  const int mh = m * h;
+  const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4;
+  LsqBuf dX, dRX, dR, dC, dC2, dcodes, dcost, dobj;
+  RQ_TRY(dX.alloc(xb));
+  RQ_TRY(dcodes.alloc((size_t)n * m));
+  RQ_TRY(dC.alloc(cb));
+  RQ_TRY(dcost.alloc((size_t)n * 4));
+  RQ_TRY(dobj.alloc((size_t)(niter + 1) * 8));
+  if (n > 0) {
+    RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
+  }
+  const float *Xd = (const float *)dX.p;
+  uint8_t *B = (uint8_t *)dcodes.p;
+  float *Cd = (float *)dC.p, *cost = (float *)dcost.p;
+  double *objd = (double *)dobj.p;
+  const hipStream_t s = nullptr;
+  lsq_clock_reset();
+  PhaseClock clk(s, true);
+  // C = update(R'X, B); C_i <- R C_i   (src/LSQ.jl:345-350)
+  if (R) {
+    std::vector<float> Rt((size_t)d * d);
+    for (int i = 0; i < d; ++i)
+      for (int k = 0; k < d; ++k) Rt[(size_t)i * d + k] = R[(size_t)k * d + i];
+    RQ_TRY(dRX.alloc(xb));
+    RQ_TRY(dR.alloc((size_t)d * d * 4 * 2));
+    RQ_TRY(dC2.alloc(cb));
+    float *Rd = (float *)dR.p, *Rtd = Rd + (size_t)d * d;
+    RQ_HIP(hipMemcpy(Rd, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(Rtd, Rt.data(), (size_t)d * d * 4, hipMemcpyHostToDevice));
+    RQ_TRY(rotate_launch((float *)dRX.p, Rd, Xd, d, n, di.num_cu, s));
+    clk.mark(PH_OTHER);
+    RQ_TRY(update_dev((float *)dC2.p, (const float *)dRX.p, B, n, d, m, h, 1e-4, s, clk));
+    RQ_TRY(rotate_launch(Cd, Rtd, (const float *)dC2.p, d, mh, di.num_cu, s));
+    clk.mark(PH_OTHER);
+  } else {
+    RQ_TRY(update_dev(Cd, Xd, B, n, d, m, h, 1e-4, s, clk));
+  }
+  // encode call e runs ILS iterations e * ilsiter .. (e + 1) * ilsiter - 1 of one stream
+  RQ_TRY(icm_encode_dev(B, B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed, 0, nsplits, s, nullptr));
+  clk.mark(PH_ENCODE);
+  for (int it = 1; it <= niter; ++it) {
+    // obj[iter] = qerror(X, B, C): the mean of the previous encode's per-row costs (NaN when n = 0: a mean of no rows)
+    LSQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, objd + (it - 1), (const float *)cost, n);
+    clk.mark(PH_OTHER);
+    RQ_TRY(update_dev(Cd, Xd, B, n, d, m, h, 1e-4, s, clk));
+    RQ_TRY(icm_encode_dev(B, B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed,
+                          (int64_t)it * ilsiter, nsplits, s, nullptr));
+    clk.mark(PH_ENCODE);
+  }
+  clk.collect();
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(C, Cd, cb, hipMemcpyDeviceToHost));
+  if (n > 0) RQ_HIP(hipMemcpy(codes, B, (size_t)n * m, hipMemcpyDeviceToHost));
+  if (niter > 0) RQ_HIP(hipMemcpy(obj, objd, (size_t)niter * 8, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+extern "C" int rq_last_lsq_timing(double *ms, int cap) {
+  if (!ms) return fail(RQ_EINVAL, "rq_last_lsq_timing: null pointer");
+  for (int q = 0; q < cap && q < PH_N; ++q) ms[q] = g_lsq_ms[q];
+  return RQ_OK;
+}

@@ -261,6 +261,37 @@ def gram_codes(X, codes, Ccat, h):
     return G
 
 
+def _lsq_shapes(X, codes, h, rho):
+    from .codebook_update import _check_update
+    n, d = X.shape
+    m = codes.shape[1] if codes.dim() == 2 else -1
+    rho = _check_update(n, d, tuple(codes.shape), m, h, rho)
+    return n, d, m, rho
+
+
+def lsq_normal_eq(X, codes, h, rho=1e-4):
+    """fast_bin_matmul (src/codebook_update.jl:96-170) on the device: (A [mh][mh], b [mh][d]) float64 tensors, A = B'B + rho I
+    and b = B'X of the zero-based uint8 codes [n][m]."""
+    n, d, m, rho = _lsq_shapes(X, codes, h, rho)
+    A = torch.empty((m * h, m * h), dtype=torch.float64, device=X.device)
+    b = torch.empty((m * h, d), dtype=torch.float64, device=X.device)
+    _lib.check(_lib.lib().rq_dev_lsq_normal_eq(_chk(A, torch.float64, "A"), _chk(b, torch.float64, "b"),
+                                               _chk(X, torch.float32, "X"), _chk(codes, torch.uint8, "codes"),
+                                               n, d, m, h, rho, _stream()))
+    return A, b
+
+
+def update_codebooks_lsq(X, codes, h, rho=1e-4, out=None):
+    """update_codebooks_fast_bin (src/codebook_update.jl:175-206) on the device: C [m][h][d] float32 = (float) A^-1 b."""
+    n, d, m, rho = _lsq_shapes(X, codes, h, rho)
+    out = torch.empty((m, h, d), dtype=torch.float32, device=X.device) if out is None else out
+    if out.numel() != m * h * d:
+        raise ValueError("out must hold m * h * d = %d floats" % (m * h * d))
+    _lib.check(_lib.lib().rq_dev_update_codebooks_lsq(_chk(out, torch.float32, "C"), _chk(X, torch.float32, "X"),
+                                                      _chk(codes, torch.uint8, "codes"), n, d, m, h, rho, _stream()))
+    return out
+
+
 def gram(X, CB):
     """G = X' CB, [d][d] with G[a][b] = sum_j X[j][a] CB[j][b]."""
     n, d = X.shape
