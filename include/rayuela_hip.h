@@ -159,6 +159,48 @@ int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *X, const fl
  * back, the obj means), encodes (training)}; cap entries written */
 int rq_last_lsq_timing(double *ms, int cap);
 
+/* ---- Chain quantization (src/ChainQ.jl).  Contract in DESIGN.md section 2 ("Chain quantization").
+ * Layouts as for LSQ: X [n][d], C [m][h][d] (m full-dimensional codebooks, one codeword per row; a trained chain quantizer
+ * is zero outside rq_chain_dims, but any C is accepted), codes [n][m] uint8 zero-based.  1 <= m <= 16, 2 <= h <= 256, d >= 1.
+ *
+ * quantize_chainq (src/ChainQ.jl:305-348; replaces quantize_chainq_cuda! :204-285 with the viterbi_forward / vec_add
+ * kernels of src/CudaUtilsModule.jl, and viterbi_encoding, deps/src/encode_icm.cpp:63-152): the exact minimiser of the
+ * chain energy sum_i U_i[b_i] + sum_i T_i[b_{i+1}][b_i] by the Viterbi recursion, all in f32, lowest index on ties.  The
+ * codes are a pure function of (X, C): they depend on neither nsplits (the minimum number of row chunks, >= 1) nor the
+ * chunking.  Arguments are checked before any device work; errors through rq_last_error.  Non-finite inputs give
+ * unspecified but in-range codes. */
+int rq_quantize_chainq(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int nsplits);
+/* device pointers, queued on `stream`; no n-sized array goes to the host */
+int rq_dev_quantize_chainq(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int nsplits,
+                           void *stream);
+/* get_cbdims_chain (src/codebook_update.jl:280-294): codebook i of a chain quantizer covers dimensions lo[i] .. hi[i]-1
+ * (zero-based, half open; lo, hi hold m ints); part i of splitarray(1:d, m-1) is lo[i+1] .. hi[i]-1.  2 <= m <= 16,
+ * d >= m - 1. */
+int rq_chain_dims(int d, int m, int *lo, int *hi);
+/* update_codebooks_chain_bin (src/codebook_update.jl:367-412): A, b as rq_dev_lsq_normal_eq; for i = 0 .. m-2 the
+ * 2h x 2h block A[ih:(i+2)h, ih:(i+2)h] is solved (f64 Cholesky on the device where the reference calls getrf / getrs)
+ * against b[ih:(i+2)h, part i]; rows 0..h-1 go to C_i, rows h..2h-1 to C_{i+1}, everything else in C is an exact zero.
+ * 2 <= m <= 16, d >= m - 1, rho finite and > 0.  Bitwise reproducible.  Arguments (codes < h included) are checked
+ * before any other work. */
+int rq_update_codebooks_chain(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho);
+/* device pointers, queued on `stream` (with h < 256 the code range check reads one flag back first) */
+int rq_dev_update_codebooks_chain(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
+                                  double rho, void *stream);
+/* CB [n][d] = sum_i C_i[codes[.][i]]: f32 adds from +0 in codebook order (the CB of src/ChainQ.jl:411-412), device pointers */
+int rq_dev_reconstruct_aq(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream);
+/* train_chainq (src/ChainQ.jl:373-431), device-resident: RX = R'X; C = chain update(RX, codes); codes = viterbi(RX, C);
+ * then niter + 1 rounds { obj[iter] = qerror(RX, codes, C); CB = reconstruct; R = polar factor of X CB' (where the
+ * reference takes an SVD); RX = R'X; C = chain update; codes = viterbi }, rho = 1e-4.  No random numbers.  C [m][h][d]
+ * out; codes [n][m] in: start codes, out: final codes; R [d][d] memory image of Julia's R, in: start rotation, out: final;
+ * obj [niter + 1] f64 out.  n >= 1, 2 <= m <= 16, m - 1 <= d <= 1024 (the device polar factor); a rank-deficient X CB' is
+ * reported as RQ_EUNSUPPORTED. */
+int rq_train_chainq(float *C, uint8_t *codes, float *R, double *obj, const float *X, int64_t n, int d, int m, int h,
+                    int niter);
+/* milliseconds of this thread's last host-pointer chain call by phase (hipEvents; the device entries leave zeros), summed
+ * over a training call: {unaries, pair tables + self-products, forward pass + back trace, codebook updates, rotation work
+ * (R'X, reconstruction, qerror, X CB', polar factor)}; cap entries written */
+int rq_last_chainq_timing(double *ms, int cap);
+
 /* ---- host-pointer entry points (what the julia/ shims ccall) ----------------------------------
  * rq_encode_*: X is uploaded in ~128 MB chunks while the previous chunk is encoded (the call is PCIe-bound).  With
  * RAYUELA_HIP_DEVICES listing several devices the rows are split over them, one host thread and one PCIe link

@@ -18,6 +18,7 @@ import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
+export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
 export HipIndex, set_codes!, set_codes_synth!, search, HipDataset, quantize
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
@@ -493,6 +494,55 @@ function train_lsq_cuda(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Fl
   Cn, Bn, obj = _train_lsq(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits)
   V && for (it, o) in enumerate(obj); println("$it $o"); end
   return Cn, Bn, obj
+end
+
+# ---- Chain quantization (src/ChainQ.jl:305-348, :373-431; src/codebook_update.jl:280-294, :367-412): the Viterbi
+# recursion, the chain-structured codebook update and the training loop run on the device (DESIGN.md section 2).  These
+# shims follow the LSQ ones above and, like them, have not been run (no Julia was available).
+function quantize_chainq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, use_cuda::Bool=false, use_cpp::Bool=false)
+  start_time = time_ns()
+  d, n  = size(X)
+  m     = length(C)
+  h     = size(C[1], 2)
+  codes = Matrix{UInt8}(undef, m, n)
+  _check(ccall((:rq_quantize_chainq, librayuela_hip), Cint,
+    (Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+    codes, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(1)))
+  return convert(Matrix{Int16}, codes) .+ Int16(1), (time_ns() - start_time) / 1e9
+end
+
+function get_cbdims_chain(d::Integer, m::Integer)
+  lo = Vector{Cint}(undef, m)
+  hi = Vector{Cint}(undef, m)
+  _check(ccall((:rq_chain_dims, librayuela_hip), Cint, (Cint, Cint, Ptr{Cint}, Ptr{Cint}), Cint(d), Cint(m), lo, hi))
+  return [Int(lo[i]) + 1:Int(hi[i]) for i = 1:m]
+end
+
+function update_codebooks_chain_bin(X::Matrix{Float32}, B::Matrix{Int16}, h::Integer, V::Bool=false, rho::Float64=1e-4)
+  start_time = time_ns()
+  d, n  = size(X)
+  m     = size(B, 1)
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  _check(ccall((:rq_update_codebooks_chain, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{UInt8}, Int64, Cint, Cint, Cint, Cdouble),
+    Cc, X, codes, Int64(n), Cint(d), Cint(m), Cint(h), Float64(rho)))
+  return _split_codebooks(Cc, m, h), (time_ns() - start_time) / 1e9
+end
+
+function train_chainq(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Float32}, B::Matrix{Int16},
+                      C::Vector{Matrix{Float32}}, niter::Integer, V::Bool=false)
+  V && println("Training a chain quantizer")
+  d, n  = size(X)
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  Rn    = copy(R)
+  obj   = zeros(Float64, niter + 1)
+  _check(ccall((:rq_train_chainq, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+    Cc, codes, Rn, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter)))
+  V && for (it, o) in enumerate(obj); println("$(it - 1) $o"); end
+  return _split_codebooks(Cc, m, h), convert(Matrix{Int16}, codes) .+ Int16(1), Rn, convert(Vector{Float32}, obj)
 end
 
 end # module

@@ -57,6 +57,14 @@ SIGNATURES = {
     "rq_dev_lsq_normal_eq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _vp]),
     "rq_train_lsq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i32]),
     "rq_last_lsq_timing": (_i32, [_vp, _i32]),
+    "rq_quantize_chainq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_dev_quantize_chainq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "rq_chain_dims": (_i32, [_i32, _i32, _vp, _vp]),
+    "rq_update_codebooks_chain": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double]),
+    "rq_dev_update_codebooks_chain": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _vp]),
+    "rq_dev_reconstruct_aq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_train_chainq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_last_chainq_timing": (_i32, [_vp, _i32]),
     "rq_dataset_upload": (_vp, [_vp, _i64, _i32]),
     "rq_dataset_encode": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),
     "rq_dataset_free": (None, [_vp]),

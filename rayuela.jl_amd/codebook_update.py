@@ -4,11 +4,16 @@ method, update_codebooks_fast_bin (:175-206) and its normal equations fast_bin_m
 The normal equations (B'B + rho I) C = B'X of the one-hot codes are built and solved in f64 on the device
 (rq_update_codebooks_lsq); the contract is DESIGN.md section 2.  X is (n, d) float32, B (n, m) Int16 one-based like the
 reference's m-by-n matrices; the result is an m-long list of (h, d) codebooks (memory image of Julia's d-by-h
-matrices)."""
+matrices).
+
+update_codebooks_chain_bin (:367-412) and get_cbdims_chain (:280-294) are the chain-structured update of ChainQ: the same
+normal equations, solved per pair of adjacent codebooks over that pair's part of the dimensions (rq_update_codebooks_chain)."""
+import time
+
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32
+from .utils import _as_f32, splitarray
 
 MAX_M = 16
 METHODS = ("fast", "fastbin", "lsmr", "lsqr", "naive")      # src/codebook_update.jl:242
@@ -73,3 +78,60 @@ def update_codebooks(X, B, h, V=False, method="fastbin"):
     if method != "fastbin":
         raise ValueError("codebook update method %r is not supported; only \"fastbin\" is" % (method,))
     return update_codebooks_fast_bin(X, B, h, V)
+
+
+def get_cbdims_chain(d, m):
+    """get_cbdims_chain(d, m) -> odims       (src/codebook_update.jl:280-294)
+
+    The dimensions each of the m codebooks of a chain quantizer covers, as m zero-based Python ranges (the reference's
+    one-based UnitRanges minus one): parts i-1 and i of splitarray(range(d), m - 1)."""
+    d, m = int(d), int(m)
+    if not 2 <= m <= MAX_M:
+        raise ValueError("a chain has 2 <= m <= %d codebooks; got m=%d" % (MAX_M, m))
+    if d < m - 1:
+        raise ValueError("d=%d < m - 1 = %d leaves a chain part empty" % (d, m - 1))
+    sub = splitarray(range(d), m - 1)
+    return [sub[0]] + [range(sub[i - 1][0], sub[i][-1] + 1) for i in range(1, m - 1)] + [sub[-1]]
+
+
+def _check_chain_update(n, d, codes_shape, m, h, rho):
+    """Every argument check of the chain update runs here, before the library (and the device) is touched."""
+    rho = _check_update(n, d, codes_shape, m, h, rho)
+    if m < 2:
+        raise ValueError("the chain update needs m >= 2 codebooks; got m=%d" % m)
+    if d < m - 1:
+        raise ValueError("d=%d < m - 1 = %d leaves a chain part empty" % (d, m - 1))
+    return rho
+
+
+def update_codebooks_chain_u8(X, codes, h, rho=1e-4):
+    """Zero-based uint8 codes (n, m) -> chain codebooks as one (m, h, d) float32 array (zero outside get_cbdims_chain)."""
+    X = _as_f32(X, "X")
+    codes = np.asarray(codes)
+    n, d = X.shape
+    m = codes.shape[1] if codes.ndim == 2 else -1
+    rho = _check_chain_update(n, d, codes.shape, m, h, rho)
+    if codes.size and (codes.min() < 0 or codes.max() > h - 1):
+        raise ValueError("codes must be in 0..%d" % (h - 1))
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    C = np.empty((m, h, d), dtype=np.float32)
+    _lib.check(_lib.lib().rq_update_codebooks_chain(C.ctypes.data, X.ctypes.data, codes.ctypes.data, n, d, m, int(h), rho))
+    return C
+
+
+def update_codebooks_chain_bin(X, B, h, V=False, rho=1e-4):
+    """update_codebooks_chain_bin(X, B, h, V=false, rho=1e-4) -> C, elapsed       (src/codebook_update.jl:367-412)
+
+    X (n, d) float32, B (n, m) Int16 one-based.  Returns an m-long list of (h, d) float32 codebooks and the seconds spent."""
+    start = time.perf_counter()
+    X = _as_f32(X, "X")
+    B = np.asarray(B)
+    n, d = X.shape
+    m = B.shape[1] if B.ndim == 2 else -1
+    _check_chain_update(n, d, B.shape, m, h, rho)
+    if B.size and (B.min() < 1 or B.max() > h):
+        raise ValueError("codes must be in 1..%d" % h)
+    C = update_codebooks_chain_u8(X, (B - 1).astype(np.uint8), h, rho)
+    if V:
+        print("Doing chain bin codebook update... done.")
+    return list(C), time.perf_counter() - start

@@ -63,9 +63,12 @@ __global__ __launch_bounds__(256) void icm_sqnorm_kernel(float *sa, const float 
 // chain of every output runs k = 0..d-1 in order (an odd d pads one zero pair: fma(0, 0, acc) = acc).
 constexpr int UN_WAVES = 4;
 using icm_f32x16 = float __attribute__((ext_vector_type(16)));
+// RANGE (the chain encoder, rq_chain.hip): rng[2i], rng[2i+1] = the dimensions [lo, hi) outside which codebook i is zero; the
+// chain then runs over the tile's codebooks' ranges only.  A skipped term is fma(+-0, x, acc) = acc for finite x: same bits.
+template <bool RANGE>
 __global__ __launch_bounds__(UN_WAVES * 64) void icm_unary_kernel(float *U, const float *X, const float *C,
                                                                 const float *sa, int64_t nrows, int d, int m, int h,
-                                                                int HS) {
+                                                                int HS, const int *rng) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = lane & 31, hi = lane >> 5;
   const int mh = m * h;
@@ -82,13 +85,25 @@ __global__ __launch_bounds__(UN_WAVES * 64) void icm_unary_kernel(float *U, cons
 #pragma unroll
   for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
   const int KF = d >> 1;   // full k pairs
+  int kb = 0, ke = KF;
+  bool tail = d & 1;
+  if constexpr (RANGE) {
+    int lo = d, hi = 0;
+    for (int i = (ct * 32) / h; i <= std::min(ct * 32 + 31, mh - 1) / h; ++i) {
+      lo = std::min(lo, rng[2 * i]);
+      hi = std::max(hi, rng[2 * i + 1]);
+    }
+    kb = lo >> 1;
+    ke = std::min(KF, (hi + 1) >> 1);
+    tail = tail && hi > 2 * KF;
+  }
 #pragma unroll 8
-  for (int kk = 0; kk < KF; ++kk) {
+  for (int kk = kb; kk < ke; ++kk) {
     const float a = cw_ok ? ap[2 * kk] : 0.0f;
     const float b = bp[2 * kk];
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
   }
-  if (d & 1) {
+  if (tail) {
     const float a = (cw_ok && hi == 0) ? ap[2 * KF] : 0.0f;
     const float b = hi == 0 ? bp[2 * KF] : 0.0f;
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
@@ -348,8 +363,8 @@ int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out,
     const int64_t nr = std::min(chunk, n - r0);
     const int ctiles = (m * h + 31) / 32;
     if (unary_ms) (void)hipEventRecord(ev[0], stream);
-    hipLaunchKernelGGL(icm_unary_kernel, dim3((unsigned)((nr + 31) / 32), (ctiles + UN_WAVES - 1) / UN_WAVES),
-                       dim3(UN_WAVES * 64), 0, stream, U, X + (size_t)r0 * d, C, sa, nr, d, m, h, HS);
+    hipLaunchKernelGGL(icm_unary_kernel<false>, dim3((unsigned)((nr + 31) / 32), (ctiles + UN_WAVES - 1) / UN_WAVES),
+                       dim3(UN_WAVES * 64), 0, stream, U, X + (size_t)r0 * d, C, sa, nr, d, m, h, HS, (const int *)nullptr);
     if (hipGetLastError() != hipSuccess) { rc = fail(RQ_EINVAL, "encode_icm: unary launch failed"); break; }
     if (unary_ms) {
       (void)hipEventRecord(ev[1], stream);
@@ -376,6 +391,25 @@ int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out,
   if (ev[0]) (void)hipEventDestroy(ev[0]);
   if (ev[1]) (void)hipEventDestroy(ev[1]);
   return rc;
+}
+
+// The unaries of one chunk of rows, and the self-products they need, for the other users of the LSQ encoding contract
+// (rq_chain.hip): U [nrows][m][HS] with HS = 64 * ceil(h / 64), sa [m * h]; rng [m][2] (device) or null = every dimension.
+int icm_sqnorm_launch(float *sa, const float *C, int m, int h, int d, hipStream_t stream) {
+  hipLaunchKernelGGL(icm_sqnorm_kernel, dim3((m * h + 255) / 256), dim3(256), 0, stream, sa, C, m * h, d);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
+int icm_unary_launch(float *U, const float *X, const float *C, const float *sa, int64_t nrows, int d, int m, int h, int HS,
+                     const int *rng, hipStream_t stream) {
+  if (nrows <= 0) return RQ_OK;
+  const int ctiles = (m * h + 31) / 32;
+  const dim3 grid((unsigned)((nrows + 31) / 32), (ctiles + UN_WAVES - 1) / UN_WAVES);
+  if (rng) hipLaunchKernelGGL(icm_unary_kernel<true>, grid, dim3(UN_WAVES * 64), 0, stream, U, X, C, sa, nrows, d, m, h, HS, rng);
+  else hipLaunchKernelGGL(icm_unary_kernel<false>, grid, dim3(UN_WAVES * 64), 0, stream, U, X, C, sa, nrows, d, m, h, HS, rng);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
 }
 
 namespace {

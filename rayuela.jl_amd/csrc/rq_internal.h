@@ -54,7 +54,7 @@ int aux_streams(hipStream_t *compute, hipStream_t *transfer);
 // counters of the big-base scan: 8 XCDs x SCAN_PACE_SLOTS x {chunks done, members}
 constexpr int SCAN_PACE_SLOTS = 64;
 constexpr size_t WS_COUNTER_BYTES = 256 + 8 * SCAN_PACE_SLOTS * 8;
-enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_SLOTS = 16 };
+enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_CHAIN = 16, WS_SLOTS = 17 };
 
 // Per-device launch lock (recursive): held while a call looks up scratch, resets the work counter and
 // launches, so two host threads cannot interleave those sequences on one device.
@@ -201,4 +201,11 @@ int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out,
                    int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
                    int64_t t0, int nsplits, hipStream_t stream, double *unary_ms);
 
+int icm_sqnorm_launch(float *sa, const float *C, int m, int h, int d, hipStream_t stream);                 // sa[i*h+k] = <c_ik, c_ik>
+int icm_unary_launch(float *U, const float *X, const float *C, const float *sa, int64_t nrows, int d, int m, int h, int HS,
+                     const int *rng, hipStream_t stream);   // U [nrows][m][HS]; rng [m][2]: codebook i is zero outside [lo, hi), or null
+// ---- LSQ codebook update (rq_lsq.hip): A [mh][mh], b [mh][d] f64; A <- its Cholesky factor, Y [mh][d] <- A^-1 Y ------------
+int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
+                         double rho, hipStream_t stream);
+int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t stream);
 }  // namespace rq

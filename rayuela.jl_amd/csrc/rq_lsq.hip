@@ -486,6 +486,15 @@ void lsq_clock_reset() {
 
 }  // namespace
 
+// The normal equations and the SPD solve for the chain codebook update (rq_chain.hip); no phase clock.
+int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
+                         double rho, hipStream_t s) {
+  PhaseClock clk(s, false);
+  return normal_eq_dev(A, b, X, codes, n, d, m, h, rho, s, clk);
+}
+
+int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t s) { return spd_solve_dev(A, Y, mh, d, s); }
+
 }  // namespace rq
 
 using namespace rq;

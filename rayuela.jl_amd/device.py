@@ -292,6 +292,42 @@ def update_codebooks_lsq(X, codes, h, rho=1e-4, out=None):
     return out
 
 
+def quantize_chainq(X, C, nsplits=1, out=None):
+    """quantize_chainq (src/ChainQ.jl:305-348) on resident tensors: X (n, d), C (m, h, d) -> codes (n, m) uint8 zero-based."""
+    from .ChainQ import _check_encode
+    n, d, m, h = _check_encode(X, C, nsplits)
+    out = torch.empty((n, m), dtype=torch.uint8, device=X.device) if out is None else out
+    if out.numel() != n * m:
+        raise ValueError("out must hold n * m = %d codes" % (n * m))
+    _lib.check(_lib.lib().rq_dev_quantize_chainq(_chk(out, torch.uint8, "codes"), _chk(X, torch.float32, "X"),
+                                                 _chk(C, torch.float32, "C"), n, d, m, h, int(nsplits), _stream()))
+    return out
+
+
+def update_codebooks_chain(X, codes, h, rho=1e-4, out=None):
+    """update_codebooks_chain_bin (src/codebook_update.jl:367-412) on the device: C [m][h][d] float32."""
+    from .codebook_update import _check_chain_update
+    n, d = X.shape
+    m = codes.shape[1] if codes.dim() == 2 else -1
+    rho = _check_chain_update(n, d, tuple(codes.shape), m, h, rho)
+    out = torch.empty((m, h, d), dtype=torch.float32, device=X.device) if out is None else out
+    if out.numel() != m * h * d:
+        raise ValueError("out must hold m * h * d = %d floats" % (m * h * d))
+    _lib.check(_lib.lib().rq_dev_update_codebooks_chain(_chk(out, torch.float32, "C"), _chk(X, torch.float32, "X"),
+                                                        _chk(codes, torch.uint8, "codes"), n, d, m, h, rho, _stream()))
+    return out
+
+
+def reconstruct_aq(codes, C, out=None):
+    """CB (n, d) = sum_i C_i[codes[:, i]] for full-dimensional codebooks C (m, h, d): f32 adds in codebook order."""
+    n, m = codes.shape
+    _, h, d = C.shape
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device) if out is None else out
+    _lib.check(_lib.lib().rq_dev_reconstruct_aq(_chk(out, torch.float32, "CB"), _chk(codes, torch.uint8, "codes"),
+                                                _chk(C, torch.float32, "C"), n, d, m, h, _stream()))
+    return out
+
+
 def gram(X, CB):
     """G = X' CB, [d][d] with G[a][b] = sum_j X[j][a] CB[j][b]."""
     n, d = X.shape
