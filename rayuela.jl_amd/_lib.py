@@ -22,7 +22,8 @@ def lib_path():
 
 _vp, _i32, _i64, _u32, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64
 
-# name -> (restype, argtypes); kept in sync with include/rayuela_hip.h (tests/test_cabi.py checks it)
+# name -> (restype, argtypes); kept in sync with include/rayuela_hip.h: tests/test_cabi.py parses the header's prototypes and
+# compares names, arity and the size, signedness and kind of every argument and return type
 SIGNATURES = {
     "rq_version": (C.c_char_p, []),
     "rq_last_scan_kernel": (C.c_char_p, []),

@@ -142,3 +142,273 @@ def test_order_plan_host_logic():
     assert p[8] == 11 and p[0] + p[1] == 11 and p[2:8] == [0] * 6
     out = (C.c_int * 12)()
     assert L.rq_order_plan(1000, 65, C.cast(out, C.c_void_p), 12) != 0          # m > 64
+
+
+# ---- typed parity of the three bindings: include/rayuela_hip.h, _lib.SIGNATURES (ctypes), julia/RayuelaHIP.jl (ccall) ----------
+# The checkers are pure functions of text / tables, so the negatives below can feed them doctored strings.
+
+_C_SCALARS = {"int": ("int", 4, True), "int64_t": ("int", 8, True), "uint32_t": ("int", 4, False),
+              "unsigned": ("int", 4, False), "unsigned int": ("int", 4, False), "uint64_t": ("int", 8, False),
+              "size_t": ("int", ctypes.sizeof(ctypes.c_size_t), False), "double": ("float", 8, True)}
+
+
+def _parse_prototypes(src):
+    """{name: (return type, [(type, parameter name), ...])} of every function a C header declares.  Types are normalised:
+    no `const`, single blanks, every `*` glued to the type ("uint8_t **")."""
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    src = re.sub(r"^[ \t]*#[^\n]*(\\\n[^\n]*)*", " ", src, flags=re.M)
+    src = re.sub(r'extern\s+"C"\s*\{', " ", src)
+
+    def norm(t):
+        t = re.sub(r"\bconst\b", " ", t)
+        stars = t.count("*")
+        return " ".join(t.replace("*", " ").split()) + (" " + "*" * stars if stars else "")
+
+    protos = {}
+    for stmt in src.split(";"):
+        stmt = " ".join(stmt.replace("}", " ").split())
+        mo = re.match(r"^(.*?)([A-Za-z_]\w*)\s*\((.*)\)$", stmt)
+        if not mo or stmt.startswith("typedef"):
+            continue
+        ret, name, plist = mo.group(1), mo.group(2), mo.group(3).strip()
+        params = []
+        if plist != "void":
+            for p in plist.split(","):
+                pm = re.match(r"^(.*?)([A-Za-z_]\w*)$", p.strip())
+                assert pm and pm.group(1).strip(), "unnamed parameter in %s: %r" % (name, p)
+                params.append((norm(pm.group(1)), pm.group(2)))
+        assert name not in protos, "declared twice: " + name
+        protos[name] = (norm(ret), params)
+    return protos
+
+
+def _header_prototypes():
+    return _parse_prototypes(open(os.path.join(ROOT, "include", "rayuela_hip.h")).read())
+
+
+def _ctype_class(cls):
+    """(kind, size, signed) of a ctypes class, so that aliases (c_int / c_int32, c_uint64 / c_size_t on LP64) compare equal."""
+    if cls is None:
+        return ("void", 0, False)
+    if cls in (ctypes.c_void_p, ctypes.c_char_p):
+        return ("pointer", ctypes.sizeof(cls), False)
+    if cls in (ctypes.c_double, ctypes.c_float):
+        return ("float", ctypes.sizeof(cls), True)
+    return ("int", ctypes.sizeof(cls), cls(-1).value < 0)
+
+
+def _python_mismatches(protos, signatures):
+    """Every disagreement between C prototypes and a ctypes (restype, argtypes) table, as readable strings."""
+    bad = []
+
+    def want(ctype):
+        if ctype == "void":
+            return ("void", 0, False)
+        if ctype.endswith("*"):
+            return ("pointer", ctypes.sizeof(ctypes.c_void_p), False)
+        assert ctype in _C_SCALARS, "header type the checker does not know: " + ctype
+        return _C_SCALARS[ctype]
+
+    for name, (ret, params) in sorted(protos.items()):
+        if name not in signatures:
+            bad.append("%s: not bound" % name)
+            continue
+        res, args = signatures[name]
+        if _ctype_class(res) != want(ret):
+            bad.append("%s: returns %s, bound as %s" % (name, ret, res))
+        if res is ctypes.c_char_p and ret != "char *":
+            bad.append("%s: c_char_p for a %s" % (name, ret))
+        if len(args) != len(params):
+            bad.append("%s: %d parameters, %d bound" % (name, len(params), len(args)))
+            continue
+        for i, ((ctype, pname), cls) in enumerate(zip(params, args)):
+            if _ctype_class(cls) != want(ctype):
+                bad.append("%s: parameter %d (%s %s) bound as %s" % (name, i, ctype, pname, cls.__name__))
+            elif cls is ctypes.c_char_p and ctype != "char *":
+                bad.append("%s: parameter %d (%s %s) bound as c_char_p" % (name, i, ctype, pname))
+    return bad
+
+
+def _split_top(s):
+    """Split at the commas outside every bracket and string."""
+    out, depth, cur, i = [], 0, [], 0
+    while i < len(s):
+        c = s[i]
+        if c == '"':
+            j = s.index('"', i + 1)
+            cur.append(s[i:j + 1])
+            i = j + 1
+            continue
+        if c in "([{":
+            depth += 1
+        elif c in ")]}":
+            depth -= 1
+        if c == "," and depth == 0:
+            out.append("".join(cur).strip())
+            cur = []
+        else:
+            cur.append(c)
+        i += 1
+    tail = "".join(cur).strip()
+    if tail:
+        out.append(tail)
+    return out
+
+
+def _parse_ccalls(jl):
+    """[(symbol, return type, [argument types], [argument expressions])] of every ccall((:sym, lib), Ret, (T...), a...)."""
+    jl = "\n".join(line for line in jl.split("\n") if not line.lstrip().startswith("#"))
+    calls = []
+    for mo in re.finditer(r"\bccall\(", jl):
+        i, depth = mo.end(), 1
+        while depth:
+            c = jl[i]
+            if c == '"':
+                i = jl.index('"', i + 1)
+            elif c in "([{":
+                depth += 1
+            elif c in ")]}":
+                depth -= 1
+            i += 1
+        parts = _split_top(jl[mo.end():i - 1])
+        assert len(parts) >= 3, "ccall the checker cannot read: " + jl[mo.start():i]
+        sym = re.match(r"^\(\s*:(\w+)\s*,\s*\w+\s*\)$", parts[0])
+        assert sym and parts[2].startswith("(") and parts[2].endswith(")"), "ccall the checker cannot read: " + jl[mo.start():i]
+        calls.append((sym.group(1), parts[1], _split_top(parts[2][1:-1]), parts[3:]))
+    return calls
+
+
+_JL_SCALARS = {"Cint": "int", "Int32": "int", "Int64": "int64_t", "Clonglong": "int64_t", "UInt32": "uint32_t",
+               "Cuint": "uint32_t", "UInt64": "uint64_t", "Culonglong": "uint64_t", "Cdouble": "double",
+               "Float64": "double", "Csize_t": "size_t"}
+_JL_ELEMS = {"Cfloat": "float", "Float32": "float", "Cdouble": "double", "Float64": "double", "UInt8": "uint8_t",
+             "Cuchar": "uint8_t", "Int16": "int16_t", "Cshort": "int16_t", "Cuint": "uint32_t", "UInt32": "uint32_t",
+             "Cint": "int", "Int32": "int", "Int64": "int64_t", "UInt64": "uint64_t", "Cvoid": "void"}
+_C_ALIASES = {"unsigned": "uint32_t", "unsigned int": "uint32_t", "unsigned char": "uint8_t",
+              "unsigned long long": "uint64_t"}
+_C_ELEMS = {"float", "double", "uint8_t", "int16_t", "uint32_t", "int", "int64_t", "uint64_t"}
+
+
+def _julia_type_matches(jtype, ctype, is_return=False):
+    ctype = _C_ALIASES.get(ctype, ctype)
+    if ctype == "void":
+        return jtype == "Cvoid"
+    if not ctype.endswith("*"):
+        return _JL_SCALARS.get(jtype) == ctype
+    if ctype == "char *":
+        return jtype in ("Cstring", "Ptr{UInt8}", "Ptr{Cchar}")
+    pm = re.match(r"^(Ptr|Ref)\{(\w+)\}$", jtype)
+    if not pm or (is_return and pm.group(1) != "Ptr"):
+        return False
+    base = ctype[:-1].strip()
+    base = _C_ALIASES.get(base, base)
+    if base in _C_ELEMS:
+        return _JL_ELEMS.get(pm.group(2)) == base
+    return pm.group(2) == "Cvoid"          # void *, an opaque handle struct, a pointer to a pointer
+
+
+# (symbol, position) pairs excused from the argument-order rule, each with its reason; keep under 5 entries
+_ORDER_EXCEPTIONS = {}
+
+
+def _julia_mismatches(protos, calls, exceptions=_ORDER_EXCEPTIONS):
+    """(disagreements between ccalls and C prototypes, number of scalar positions whose argument names the header's parameter)"""
+    bad, named = [], 0
+    for sym, ret, types, args in calls:
+        if sym not in protos:
+            bad.append("%s: not declared in the header" % sym)
+            continue
+        cret, params = protos[sym]
+        if not _julia_type_matches(ret, cret, is_return=True):
+            bad.append("%s: returns %s, ccall says %s" % (sym, cret, ret))
+        if len(types) != len(params) or len(args) != len(params):
+            bad.append("%s: %d parameters, %d types and %d arguments in the ccall" % (sym, len(params), len(types), len(args)))
+            continue
+        scalars = {pname for ctype, pname in params if not ctype.endswith("*")}
+        for i, ((ctype, pname), jtype, arg) in enumerate(zip(params, types, args)):
+            if not _julia_type_matches(jtype, ctype):
+                bad.append("%s: parameter %d (%s %s) passed as %s" % (sym, i, ctype, pname, jtype))
+            if ctype.endswith("*"):
+                continue
+            idents = set(re.findall(r"[A-Za-z_]\w*", re.sub(r'"[^"]*"', " ", arg))) & scalars
+            if idents == {pname}:
+                named += 1
+            elif idents and (sym, i) not in exceptions:
+                bad.append("%s: parameter %d is `%s` but the argument `%s` names %s" % (sym, i, pname, arg, sorted(idents)))
+    return bad, named
+
+
+def _julia_source():
+    return open(os.path.join(ROOT, "julia", "RayuelaHIP.jl")).read()
+
+
+def test_prototype_parser_reads_the_whole_header():
+    protos = _header_prototypes()
+    assert sorted(protos) == _declared_symbols()
+    assert protos["rq_dev_rotate_T"] == ("int", [("float *", "RX"), ("float *", "R"), ("float *", "X"), ("int", "d"),
+                                                 ("int64_t", "n"), ("void *", "stream")])
+    assert protos["rq_version"] == ("char *", []) and protos["rq_host_alloc"] == ("void *", [("size_t", "bytes")])
+    assert protos["rq_dev_order_rows"][1][1] == ("uint8_t **", "codes_out")
+    assert protos["linscan_aqd_query"][1][6] == ("unsigned int", "NQ") and protos["rq_lsq_release"][0] == "void"
+
+
+def test_python_binding_types_equal_the_header():
+    from rayuela_jl_amd import _lib
+    protos = _header_prototypes()
+    assert len(protos) >= 88
+    assert _python_mismatches(protos, _lib.SIGNATURES) == []
+
+
+def test_julia_ccalls_equal_the_header():
+    protos = _header_prototypes()
+    calls = _parse_ccalls(_julia_source())
+    assert len(calls) >= 36, len(calls)
+    bad, named = _julia_mismatches(protos, calls)
+    assert bad == []
+    assert named >= 110, named          # the argument-order rule must stay a positive one
+    assert len(_ORDER_EXCEPTIONS) < 5
+
+
+def test_binding_checkers_report_doctored_input():
+    """Negatives for the checkers themselves (strings only; no file is touched)."""
+    C = ctypes
+    protos = _parse_prototypes("int f(float *X, int64_t n, int m, int h, void *stream);\nconst char *g(void);\n"
+                               "int s(double *acc, size_t bytes, double rho);")
+    good = {"f": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]), "g": (C.c_char_p, []),
+            "s": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_double])}
+    assert _python_mismatches(protos, good) == []
+
+    def py(**patch):
+        return _python_mismatches(protos, dict(good, **patch))
+
+    assert any("parameter 1 (int64_t n)" in b for b in py(f=(C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p])))
+    assert any("parameter 2 (int m)" in b for b in py(f=(C.c_int, [C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_void_p])))
+    assert any("5 parameters, 4 bound" in b for b in py(f=(C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p])))
+    assert any("returns" in b for b in py(f=(None, good["f"][1])))
+    assert any("returns" in b for b in py(g=(C.c_int, [])))
+    assert any("parameter 2 (double rho)" in b for b in py(s=(C.c_int, [C.c_void_p, C.c_size_t, C.c_int64])))
+    assert any("c_char_p" in b for b in py(f=(C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.c_int, C.c_void_p])))
+    assert any("not bound" in b for b in _python_mismatches(protos, {"f": good["f"], "g": good["g"]}))
+
+    call = ("_check(ccall((:f, librayuela_hip), Cint, (Ptr{Cfloat}, Int64, Cint, Cint, Ptr{Cvoid}),\n"
+            "  X, Int64(n), Cint(m), Cint(h), C_NULL))")
+    bad, named = _julia_mismatches(protos, _parse_ccalls(call))
+    assert bad == [] and named == 3
+
+    def jl(old, new):
+        assert old in call
+        return _julia_mismatches(protos, _parse_ccalls(call.replace(old, new)))[0]
+
+    assert any("parameter 2 is `m`" in b for b in jl("Cint(m), Cint(h)", "Cint(h), Cint(m)"))
+    assert any("5 parameters, 5 types and 4 arguments" in b for b in jl("Cint(m), Cint(h)", "Cint(m)"))
+    assert any("5 parameters, 4 types and 5 arguments" in b for b in jl("Int64, Cint, Cint", "Int64, Cint"))
+    assert any("parameter 1 (int64_t n) passed as Cint" in b for b in jl("Int64, Cint", "Cint, Cint"))
+    assert any("parameter 0 (float * X) passed as Ptr{Cdouble}" in b for b in jl("Ptr{Cfloat}", "Ptr{Cdouble}"))
+    assert any("returns int" in b for b in jl("Cint, (Ptr", "Cvoid, (Ptr"))
+    assert any("not declared" in b for b in jl(":f,", ":f2,"))
+    dbl = _julia_mismatches(protos, _parse_ccalls("ccall((:s, lib), Cint, (Ptr{Cfloat}, Csize_t, Cdouble), acc, bytes, rho)"))[0]
+    assert any("parameter 0 (double * acc) passed as Ptr{Cfloat}" in b for b in dbl)
+    # an expression that names no parameter passes; one that names the wrong one among others does not
+    assert jl("Cint(h), C_NULL", "Cint(size(C, 2)), C_NULL") == []
+    assert any("parameter 3 is `h`" in b for b in jl("Cint(h), C_NULL", "Cint(h * m), C_NULL"))
