@@ -296,7 +296,13 @@ int rq_dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *c
  * The scan's table gathers are LDS-bank-conflict bound; rows sorted by the top 3 bits of their leading code bytes make
  * the 32 lanes of a gather hit 32 distinct bank columns (SIFT1M shape: 2.45 -> 2.1 ms at k = 1000, more on larger bases).
  *   rq_dev_linscan           orders a scratch copy itself when that pays (tuning SCAN_ORDER = 1: from ORDER_MIN_NQ = 2048
- *                            queries and ORDER_MIN_ROWS = 65536 rows on; ~40 us per 1e6 rows, inside the call's time)
+ *                            queries and ORDER_MIN_ROWS = 65536 rows on; ~40 us per 1e6 rows, inside the call's time) and
+ *                            KEEPS the copy per device and stream: every later call compares its codes, on the device and
+ *                            byte for byte, with a snapshot kept next to the copy and orders again only when they differ, so
+ *                            codes rewritten in place or re-allocated at the same address are safe; a kept copy is balanced
+ *                            on its second use.  Hidden scratch: n * (2 * w + 8) bytes, w = rq_scan_row_width(m), until
+ *                            rq_release_workspaces; over ORDER_MAX_SCRATCH_MB without the snapshot's n * w the call orders
+ *                            uncached, as before (rq_order_cache_stats counts what happened)
  *   rq_index_set_codes[_synth]  order every shard once, at load time (tuning INDEX_ORDER = 1)
  *   rq_dev_order_rows        the same for callers that keep device-resident codes: `ordered` (rq_order_bytes(n, m) bytes,
  *                            16-byte aligned) receives the permuted rows, padded to rq_scan_row_width(m) bytes each, and
@@ -473,6 +479,13 @@ int rq_scan_stats(unsigned long long *out16);
  * the tie look (bf_tie_twins) sent to select + sort before any bucket work, [2] items that took select + sort in the end
  * ([2] - [1] gave up after their histogram); [3..7] reserved (0).  Counts, not clocks: what tests assert on. */
 int rq_scan_finish_stats(unsigned long long *out8);
+/* Diagnostics: the kept in-call row order (csrc/rq_order.hip) of the current device, summed over its streams, since the last
+ * rq_release_workspaces.  A raw-pointer scan that orders a scratch copy of its base keeps that copy and proves on every call, on
+ * the device, that it still is the order of the codes it was handed.  [0] calls that consulted the kept copy, [1] hits (the copy
+ * was reused as it was), [2] builds of a plain (sorted) copy, [3] builds of a balanced copy, [4] calls that ordered uncached (the
+ * snapshot did not fit under ORDER_MAX_SCRATCH_MB), [5] of [3]: upgrades of a plain copy on its first hit, [6..7] reserved (0).
+ * [0] = [1] + [2] + [3].  Waits for the device.  Counts, not clocks: what tests assert on. */
+int rq_order_cache_stats(unsigned long long *out8);
 
 /* Diagnostics (pure host code, no device needed): the scan planner's decision for a shard of n rows, nq queries,
  * m sub-quantizers, dimension d, k neighbours on a device with num_cu compute units.  out[0] queries per group,

@@ -545,4 +545,12 @@ function train_chainq(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Floa
   return _split_codebooks(Cc, m, h), convert(Matrix{Int16}, codes) .+ Int16(1), Rn, convert(Vector{Float32}, obj)
 end
 
+# Diagnostics: the kept in-call row order of raw-pointer scans on the current device since the last release
+# (include/rayuela_hip.h, rq_order_cache_stats): consulted, hits, plain builds, balanced builds, uncached, upgrades.
+function order_cache_stats()
+  out8 = zeros(UInt64, 8)
+  _check(ccall((:rq_order_cache_stats, librayuela_hip), Cint, (Ptr{UInt64},), out8))
+  return (consulted=out8[1], hits=out8[2], plain_builds=out8[3], balanced_builds=out8[4], uncached=out8[5], upgrades=out8[6])
+end
+
 end # module

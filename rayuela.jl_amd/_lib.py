@@ -112,6 +112,7 @@ SIGNATURES = {
     "rq_scan_stats": (_i32, [_vp]),
     "rq_scan_orders_in_call": (_i32, [_i64, _i64, _i32]),
     "rq_scan_finish_stats": (_i32, [_vp]),
+    "rq_order_cache_stats": (_i32, [_vp]),
     "rq_scan_plan": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "rq_last_timing": (_i32, [_vp, _vp, _vp, _vp]),
 }
@@ -171,6 +172,13 @@ def scan_plan(n, nq, m, d, k, num_cu=256):
     p = dict(zip(keys, [int(x) for x in out]))
     p["bigk"], p["xcd"], p["bulk"] = p["flags"] & 1, (p["flags"] >> 1) & 1, (p["flags"] >> 2) & 1
     return p
+
+
+def order_cache_stats():
+    """The kept in-call row order of raw-pointer scans on the current device since the last release (rq_order_cache_stats)."""
+    out = (C.c_uint64 * 8)()
+    check(lib().rq_order_cache_stats(C.cast(out, C.c_void_p)))
+    return dict(zip(["consulted", "hits", "plain_builds", "balanced_builds", "uncached", "upgrades"], [int(x) for x in out[:6]]))
 
 
 def scan_stats():

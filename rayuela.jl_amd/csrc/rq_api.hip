@@ -72,6 +72,8 @@ struct StreamWs {
   bool used = false;
   void *ws[WS_SLOTS] = {nullptr};
   size_t ws_bytes[WS_SLOTS] = {0};
+  uint64_t ws_gen[WS_SLOTS] = {0};     // allocations of the slot so far (the kept order must notice a new buffer)
+  OrderCacheHost oc;                   // the kept order of dev_linscan (WS_ORDER / WS_ORDER_STATE)
 };
 struct DevCtx {
   bool inited = false;
@@ -129,6 +131,8 @@ DeviceLock::DeviceLock() {
 }
 DeviceLock::~DeviceLock() { static_cast<std::recursive_mutex *>(mu_)->unlock(); }
 
+static uint64_t g_ws_gen = 0;      // (g_mu) numbers the allocations of all workspaces: a freed and re-used StreamWs never repeats one
+
 int workspace(int slot, size_t bytes, void **ptr, hipStream_t stream) {
   int dev = 0;
   RQ_HIP(hipGetDevice(&dev));
@@ -153,9 +157,26 @@ int workspace(int slot, size_t bytes, void **ptr, hipStream_t stream) {
     want = (want + 255) & ~(size_t)255;
     RQ_HIP(hipMalloc(&w->ws[slot], want));
     w->ws_bytes[slot] = want;
+    w->ws_gen[slot] = ++g_ws_gen;
   }
   *ptr = w->ws[slot];
   return RQ_OK;
+}
+
+// The (device, stream) workspace's order cache and the allocation numbers of its two buffers (after workspace() made them).
+static int order_cache_of(hipStream_t stream, OrderCacheHost **h, uint64_t *order_gen, uint64_t *state_gen) {
+  int dev = 0;
+  RQ_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(g_mu);
+  DevCtx &c = g_dev[dev];
+  for (int i = 0; i < MAX_STREAM_WS; ++i)
+    if (c.sw[i].used && c.sw[i].stream == stream) {
+      *h = &c.sw[i].oc;
+      *order_gen = c.sw[i].ws_gen[WS_ORDER];
+      *state_gen = c.sw[i].ws_gen[WS_ORDER_STATE];
+      return RQ_OK;
+    }
+  return fail(RQ_EINVAL, "order cache: the stream has no workspace");
 }
 
 // Free the scratch of one stream of the current device (called before the stream is destroyed).
@@ -172,6 +193,7 @@ int release_stream_workspace(hipStream_t stream) {
       c.sw[i].ws[s] = nullptr;
       c.sw[i].ws_bytes[s] = 0;
     }
+    c.sw[i].oc = OrderCacheHost();
     c.sw[i].used = false;
     c.sw[i].stream = nullptr;
   }
@@ -192,6 +214,7 @@ int release_workspaces() {
       c.sw[i].ws[s] = nullptr;
       c.sw[i].ws_bytes[s] = 0;
     }
+    c.sw[i].oc = OrderCacheHost();
     c.sw[i].used = false;
     c.sw[i].stream = nullptr;
   }
@@ -383,6 +406,85 @@ int order_base(const uint8_t **out_codes, const uint32_t **out_perm, void *dst, 
   return RQ_OK;
 }
 
+// The uncached in-call order: a scratch copy ordered by every call.  It writes the buffer of the kept order, so that one is
+// declared unbuilt first (in stream order).
+static int order_in_call(const uint8_t **ocodes, const uint32_t **operm, const uint8_t *codes, int64_t n, int mp, int64_t nq,
+                         hipStream_t stream) {
+  void *ord = nullptr;
+  RQ_TRY(workspace(WS_ORDER, order_base_bytes(n, mp), &ord, stream));
+  OrderCacheHost *h = nullptr;
+  uint64_t og = 0, sg = 0;
+  RQ_TRY(order_cache_of(stream, &h, &og, &sg));
+  if (sg != 0) {
+    void *state = nullptr;
+    RQ_TRY(workspace(WS_ORDER_STATE, order_cache_state_bytes(), &state, stream));
+    RQ_HIP(hipMemsetAsync(state, 0, 8 * sizeof(uint32_t), stream));     // (the counters behind stay)
+  }
+  h->key_id = 0;
+  ++h->uncached;
+  order_set_call_queries(nq);      // (the greedy balance of the order costs more than the sort: only for batches it pays for)
+  const int orc = order_base(ocodes, operm, ord, codes, n, mp, stream);
+  order_set_call_queries(0);
+  return orc;
+}
+
+// The kept order.  WS_ORDER: [copy | perm] (order_base_bytes) | snapshot at snap_off; WS_ORDER_STATE: the device words.  A new
+// allocation of either starts from zeroed words and a new key id.  *kept = false: no memory for the larger buffer, nothing was
+// launched -- the caller orders in the call.
+static int order_kept(bool *kept, const uint8_t **ocodes, const uint32_t **operm, const uint8_t *codes, int64_t n, int m, int mp,
+                      int64_t nq, size_t snap_off, hipStream_t stream) {
+  *kept = true;
+  OrderTiling ot;
+  scan_order_tiling(mp, &ot);
+  const int bits = order_cached_key_bits(n, mp, ot);
+  if (bits <= 0) return RQ_OK;          // tiny base: stays as it is
+  void *ord = nullptr, *state = nullptr, *tmp = nullptr;
+  int rc = workspace(WS_ORDER, snap_off + (size_t)n * mp, &ord, stream);
+  if (is_oom(rc)) { forgive_oom(); *kept = false; return RQ_OK; }
+  RQ_TRY(rc);
+  RQ_TRY(workspace(WS_ORDER_STATE, order_cache_state_bytes(), &state, stream));
+  RQ_TRY(workspace(WS_ORDER_TMP, order_scratch_bytes(n, bits), &tmp, stream));
+  OrderCacheHost *h = nullptr;
+  uint64_t og = 0, sg = 0;
+  RQ_TRY(order_cache_of(stream, &h, &og, &sg));
+  if (h->state_gen != sg) {
+    RQ_HIP(hipMemsetAsync(state, 0, order_cache_state_bytes(), stream));
+    h->state_gen = sg; h->order_gen = og; h->key_id = 0;
+  } else if (h->order_gen != og) {
+    RQ_HIP(hipMemsetAsync(state, 0, 8 * sizeof(uint32_t), stream));
+    h->order_gen = og; h->key_id = 0;
+  }
+  ++h->consulted;
+  uint8_t *dst = (uint8_t *)ord;
+  uint32_t *pm = reinterpret_cast<uint32_t *>(dst + (order_base_bytes(n, mp) - (size_t)n * 4));
+  RQ_TRY(order_rows_cached(dst, pm, dst + snap_off, codes, n, m, mp, tmp, ot, nq, (uint32_t *)state, h, stream));
+  *ocodes = dst;
+  *operm = pm;
+  return RQ_OK;
+}
+
+// rq_order_cache_stats: the kept order's counters of the current device since the last release, summed over its streams.
+int order_cache_stats(unsigned long long *out8) {
+  if (!out8) return fail(RQ_EINVAL, "rq_order_cache_stats: null output");
+  int dev = 0;
+  RQ_HIP(hipGetDevice(&dev));
+  DeviceLock launch_lock;
+  RQ_HIP(hipDeviceSynchronize());
+  std::lock_guard<std::mutex> lk(g_mu);
+  DevCtx &c = g_dev[dev];
+  for (int i = 0; i < 8; ++i) out8[i] = 0;
+  for (int i = 0; i < MAX_STREAM_WS; ++i) {
+    if (!c.sw[i].used) continue;
+    out8[0] += c.sw[i].oc.consulted;
+    out8[4] += c.sw[i].oc.uncached;
+    if (!c.sw[i].ws[WS_ORDER_STATE] || c.sw[i].oc.state_gen != c.sw[i].ws_gen[WS_ORDER_STATE]) continue;
+    uint32_t w[16];
+    RQ_HIP(hipMemcpy(w, c.sw[i].ws[WS_ORDER_STATE], sizeof(w), hipMemcpyDeviceToHost));
+    out8[1] += w[8]; out8[2] += w[9]; out8[3] += w[10]; out8[5] += w[11];
+  }
+  return RQ_OK;
+}
+
 // ---- shared implementation of the scan on device pointers --------------------------------------------
 int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *codes, const float *centers,
                 const float *queries, int64_t n, int64_t nq, int m, int d, int k, uint32_t id_offset,
@@ -423,20 +525,26 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
   // (order_base: index handles, rq_dev_order_rows, the host-pointer calls).  Otherwise the call orders a copy itself when
   // that pays: the four small kernels cost ~40 us at 1e6 rows, a scan of nq queries gains ~15 % of its time -- from
   // ORDER_MIN_NQ (2048) queries on.  LSQ scans index row_bias / norm bytes by position and keep the arrival order.
-  // The in-call order is an optimisation on hidden scratch (n * (mp + 8) bytes per device and stream, kept until
+  // The in-call order is an optimisation on hidden scratch (n * (2 * mp + 8) bytes per device and stream -- the copy, its perm, the
+  // key scratch and the snapshot of the kept order below; n * (mp + 8) where the snapshot does not fit the cap --, kept until
   // rq_release_workspaces): it is skipped above ORDER_MAX_SCRATCH_MB (default 2048 MiB = a 1.25e8-row m = 8 shard; bigger
   // bases belong in an index handle or rq_dev_order_rows, which order ONCE), and a scratch allocation that fails (out of memory)
   // means "scan in arrival order" -- the round-3 path, which needs no extra memory -- never a failed search; any other error of
   // the ordering kernels is returned.
-  if (!perm && !row_bias && order_pays(n, nq, k) &&
-      order_base_bytes(n, mp) + (size_t)n * 4 <= (size_t)std::max(0, tuning("ORDER_MAX_SCRATCH_MB", 2048)) * 1048576ull) {
-    void *ord = nullptr;
+  // The copy is KEPT (rq_order.hip, "the kept order"): callers scan the same base batch after batch, so every call checks on the
+  // device, byte for byte against an arrival-order snapshot, that the copy still is the order of the codes it was handed, and the
+  // ordering kernels return at once when it is; a kept order is also balanced on its second use, whatever the batch size.  The
+  // snapshot counts towards ORDER_MAX_SCRATCH_MB: where copy + perm + snapshot exceed it but copy + perm do not, the call orders
+  // uncached as it always did.
+  const size_t order_cap = (size_t)std::max(0, tuning("ORDER_MAX_SCRATCH_MB", 2048)) * 1048576ull;
+  if (!perm && !row_bias && order_pays(n, nq, k) && order_base_bytes(n, mp) + (size_t)n * 4 <= order_cap) {
     const uint8_t *ocodes = codes;
     const uint32_t *operm = nullptr;
-    int orc = workspace(WS_ORDER, order_base_bytes(n, mp), &ord, stream);
-    order_set_call_queries(nq);      // (the greedy balance of the order costs more than the sort: only for batches it pays for)
-    if (orc == RQ_OK) orc = order_base(&ocodes, &operm, ord, codes, n, mp, stream);
-    order_set_call_queries(0);
+    const size_t snap_off = (order_base_bytes(n, mp) + 255) & ~(size_t)255, snap_bytes = (size_t)n * mp;
+    bool kept = false;              // the snapshot fits the cap and the memory: the kept order; else today's order in the call
+    int orc = RQ_OK;
+    if (snap_off + snap_bytes + (size_t)n * 4 <= order_cap) orc = order_kept(&kept, &ocodes, &operm, codes, n, m, mp, nq, snap_off, stream);
+    if (orc == RQ_OK && !kept) orc = order_in_call(&ocodes, &operm, codes, n, mp, nq, stream);
     if (orc == RQ_OK) {
       codes = ocodes;
       perm = operm;
@@ -912,6 +1020,8 @@ int rq_scan_finish_stats(unsigned long long *out8) {
   RQ_HIP(hipMemcpy(out8, (char *)counter + 64 + 128, 64, hipMemcpyDeviceToHost));
   return RQ_OK;
 }
+
+int rq_order_cache_stats(unsigned long long *out8) { return order_cache_stats(out8); }
 
 int rq_release_workspaces(void) {
   rq::sharded_cache_release();

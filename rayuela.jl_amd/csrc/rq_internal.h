@@ -54,7 +54,7 @@ int aux_streams(hipStream_t *compute, hipStream_t *transfer);
 // counters of the big-base scan: 8 XCDs x SCAN_PACE_SLOTS x {chunks done, members}
 constexpr int SCAN_PACE_SLOTS = 64;
 constexpr size_t WS_COUNTER_BYTES = 256 + 8 * SCAN_PACE_SLOTS * 8;
-enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_CHAIN = 16, WS_SLOTS = 17 };
+enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_CHAIN = 16, WS_ORDER_STATE = 17, WS_SLOTS = 18 };
 
 // Per-device launch lock (recursive): held while a call looks up scratch, resets the work counter and
 // launches, so two host threads cannot interleave those sequences on one device.
@@ -119,7 +119,7 @@ int order_base(const uint8_t **out_codes, const uint32_t **out_perm, void *dst, 
 // ---- bank-aware row order (rq_order.hip) ---------------------------------------------------------
 struct OrderTiling { int rpt, gran, group, cbits, blk; };                    // see scan_order_tiling (rq_scan.hip)
 void scan_order_tiling(int mp, OrderTiling *t);
-void order_set_call_queries(int64_t nq);   // > 0: the ordering that follows serves ONE scan of nq queries (greedy balance only if it pays)
+void order_set_call_queries(int64_t nq);   // > 0: the ordering that follows serves ONE scan of nq queries (greedy balance only if it pays); < 0: never balanced
 bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4]);
 bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4]);  // the launch's balance predicate
 int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]);  // key layout; returns the total bits (0: no ordering)
@@ -129,6 +129,21 @@ uint32_t order_sample_rows(int64_t n, int blk, uint32_t *sgroups);   // arrival-
 int gather_f32_launch(float *dst, const float *src, const uint32_t *perm, int64_t n, hipStream_t stream);
 int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t n, int mp, void *scratch,
                       const OrderTiling &t, hipStream_t stream);
+// The kept order of dev_linscan (rq_order.hip, "the kept order"): the host half of one (device, stream) workspace's cache.  The
+// device half -- which key the copy was built for, the verdict of the call's check, the counters -- is WS_ORDER_STATE.
+struct OrderCacheHost {
+  unsigned char key[768];            // what defines the order (OrderCacheKey); the codes pointer is not part of it
+  uint32_t key_id = 0;               // 0: no key yet; the device word must equal it for a hit
+  uint32_t epoch = 0;                // number of the call, never 0
+  uint64_t order_gen = 0, state_gen = 0;     // allocations of WS_ORDER / WS_ORDER_STATE the cache was set up in
+  unsigned long long consulted = 0, uncached = 0;   // rq_order_cache_stats
+};
+size_t order_cache_state_bytes();
+int order_cached_key_bits(int64_t n, int mp, const OrderTiling &t);
+// order `src` into dst / perm unless the copy there is proven (on the device, in stream order) to be the order of these bytes
+int order_rows_cached(uint8_t *dst, uint32_t *perm, uint8_t *snap, const uint8_t *src, int64_t n, int m, int mp, void *scratch,
+                      const OrderTiling &t, int64_t nq, uint32_t *state, OrderCacheHost *h, hipStream_t stream);
+int order_cache_stats(unsigned long long *out8);
 // [P][nq][k] -> [nq][P][k] (lists gathered shard-major, merged query-major)
 int interleave_keys_launch(uint64_t *dst, const uint64_t *src, int64_t nq, int P, int k, size_t pstride, hipStream_t stream);
 int scan_padded_m(int m);   // smallest tiled row width >= m (2,4,8,16,32,64) or -1

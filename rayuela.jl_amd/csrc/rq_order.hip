@@ -27,6 +27,8 @@
 #include "rq_internal.h"
 
 #include <cmath>
+#include <cstring>
+#include <mutex>
 
 namespace rq {
 
@@ -103,16 +105,104 @@ __device__ __forceinline__ uint32_t order_key_of(const OrderParams &p, uint32_t 
   return key;
 }
 
+// ---- the kept order of dev_linscan (order_rows_cached below) -----------------------------------------------------------------
+// A raw-pointer scan orders a scratch copy of its base; callers scan the same base batch after batch, so the copy is KEPT and
+// every call only proves, on the device and in stream order, that it still is the order of the bytes it was handed: the state
+// words below, an arrival-order snapshot of the codes next to the copy, and order_check_kernel.  The ordering kernels are
+// launched on every call (the host cannot know the outcome without waiting) and return at once unless the verdict opens them.
+// Only kernels write these words, so a launch that failed or a captured stream that was never replayed reads as "not built".
+enum { OC_BUILT = 0,       // id of the host key the copy was last built for (0: none); zeroed by the first kernel of a rebuild
+       OC_BALANCED = 1,    // that build ran the greedy balance
+       OC_MISS = 2,        // epoch of the last call whose codes differed from the snapshot
+       OC_VERDICT = 3, OC_VEPOCH = 4,   // this call's verdict and the epoch it belongs to (a stale verdict opens nothing)
+       OC_CNT = 8,         // diagnostics (rq_order_cache_stats): hits, plain builds, balanced builds, of those upgrades on a hit
+       OC_WORDS = 16 };
+enum { OCV_REBUILD = 1, OCV_HIT = 2, OCV_UPGRADE = 3 };
+
+struct OrderGate {
+  uint32_t *state;        // [OC_WORDS]; nullptr: an ordinary ordering, nothing gated
+  uint8_t *snap;          // [n * mp] arrival-order snapshot, written by the first kernel of a rebuild
+  uint32_t key, epoch;
+  uint32_t role;          // 1: the rebuild on a miss, 2: the balanced rebuild on "hit, not balanced"
+  uint32_t can_upgrade;   // role 2 follows
+  uint32_t balanced;      // this set runs the greedy balance
+};
+
+// First kernel of a set.  Role 1 derives the verdict from the state words -- the same in every thread: the only word written
+// meanwhile is OC_BUILT = 0, by block 0 and only on a verdict that a zero confirms -- and block 0 publishes it.
+__device__ __forceinline__ bool order_gate_first(const OrderGate &g) {
+  if (!g.state) return true;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+  if (g.role == 2) {
+    const bool open = g.state[OC_VEPOCH] == g.epoch && g.state[OC_VERDICT] == OCV_UPGRADE;
+    if (open && lead) { g.state[OC_BUILT] = 0; g.state[OC_CNT + 2] += 1; g.state[OC_CNT + 3] += 1; }
+    return open;
+  }
+  const bool hit = g.state[OC_BUILT] == g.key && g.state[OC_MISS] != g.epoch;
+  const uint32_t v = !hit ? OCV_REBUILD : (g.can_upgrade && !g.state[OC_BALANCED]) ? OCV_UPGRADE : OCV_HIT;
+  if (lead) {
+    g.state[OC_VERDICT] = v; g.state[OC_VEPOCH] = g.epoch;
+    if (v == OCV_REBUILD) { g.state[OC_BUILT] = 0; g.state[OC_CNT + (g.balanced ? 2 : 1)] += 1; }
+    else if (v == OCV_HIT) g.state[OC_CNT] += 1;
+  }
+  return v == OCV_REBUILD;
+}
+__device__ __forceinline__ bool order_gate_open(const OrderGate &g) {
+  return !g.state || (g.state[OC_VEPOCH] == g.epoch && g.state[OC_VERDICT] == (g.role == 2 ? OCV_UPGRADE : OCV_REBUILD));
+}
+// Last kernel of a set: the copy is this key's once the kernel has run (nothing reads the word before the next kernel).
+__device__ __forceinline__ bool order_gate_last(const OrderGate &g) {
+  if (!order_gate_open(g)) return false;
+  if (g.state && blockIdx.x == 0 && threadIdx.x == 0) { g.state[OC_BALANCED] = g.balanced; g.state[OC_BUILT] = g.key; }
+  return true;
+}
+// the snapshot of a rebuild: a coalesced copy of the n * mp code bytes by the whole grid (codes are 16-byte aligned)
+__device__ __forceinline__ void order_snapshot(const OrderGate &g, const uint8_t *src, size_t bytes) {
+  if (!g.state || !g.snap || g.role != 1) return;
+  const size_t nv = bytes / 16, nth = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = t0; i < nv; i += nth) reinterpret_cast<uint4 *>(g.snap)[i] = reinterpret_cast<const uint4 *>(src)[i];
+  if (t0 == 0) for (size_t b = nv * 16; b < bytes; ++b) g.snap[b] = src[b];
+}
+
+// Is the kept copy still the order of `codes`?  Exact: every byte against the snapshot, 16 bytes per lane.  A difference is
+// recorded as OC_MISS = epoch (a plain store of the call's own number: nothing to clear between calls, no atomics).  The built
+// word is tested before the snapshot is touched.  The grid also zeroes the two-level counters of the rebuild that may follow.
+__global__ __launch_bounds__(256) void order_check_kernel(const uint8_t *codes, const uint8_t *snap, size_t bytes, uint32_t *state,
+                                                          uint32_t key, uint32_t epoch, uint32_t *zero, uint32_t nzero) {
+  const size_t nth = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = t0; i < nzero; i += nth) zero[i] = 0u;
+  if (state[OC_BUILT] != key) return;
+  const size_t nv = bytes / 16;
+  bool bad = false;
+  for (size_t i = t0; i < nv; i += nth) {
+    const uint4 a = reinterpret_cast<const uint4 *>(codes)[i], b = reinterpret_cast<const uint4 *>(snap)[i];
+    bad |= ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u;
+  }
+  if (t0 == 0) for (size_t b = nv * 16; b < bytes; ++b) bad |= codes[b] != snap[b];
+  if (bad) state[OC_MISS] = epoch;
+}
+
+// pass 0 of a GATED one-level ordering: the histogram is zeroed (and the snapshot written) only when the verdict asks for a
+// rebuild -- a memset would cost every hit (nbins + ntiles) * 4 bytes, 2-64 MB for keys of 19-24 bits
+__global__ __launch_bounds__(256) void order_zero_kernel(OrderParams p, uint32_t count, OrderGate g) {
+  if (!order_gate_first(g)) return;
+  order_snapshot(g, p.src, (size_t)p.n * p.mp);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) p.hist[i] = 0u;
+}
+
 // pass 1: bucket sizes, and every row's arrival rank inside its bucket (any order will do: the result of the scan does not
 // depend on the permutation)
-__global__ __launch_bounds__(256) void order_rank_kernel(OrderParams p) {
+// (gated, order_rows_cached: order_zero_kernel is the set's first kernel and has published the verdict)
+__global__ __launch_bounds__(256) void order_rank_kernel(OrderParams p, OrderGate g) {
+  if (!order_gate_open(g)) return;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += gridDim.x * blockDim.x)
     if (!order_in_prefix(p, i)) p.rank[i] = atomicAdd(&p.hist[order_key_of(p, i)], 1u);
 }
 
 // pass 2a: exclusive scan inside tiles of ORDER_SCAN_TILE bins, tile totals to hist[nbins + tile]
-__global__ __launch_bounds__(1024) void order_scan_tiles_kernel(uint32_t *hist, uint32_t nbins) {
+__global__ __launch_bounds__(1024) void order_scan_tiles_kernel(uint32_t *hist, uint32_t nbins, OrderGate g) {
   __shared__ uint32_t wsum[16];
+  if (!order_gate_open(g)) return;
   const uint32_t t0 = blockIdx.x * ORDER_SCAN_TILE + threadIdx.x * 16;
   uint32_t v[16], s = 0;
 #pragma unroll
@@ -135,8 +225,9 @@ __global__ __launch_bounds__(1024) void order_scan_tiles_kernel(uint32_t *hist, 
 }
 
 // pass 2b: exclusive scan of the (<= 1024) tile totals, one workgroup
-__global__ __launch_bounds__(1024) void order_scan_top_kernel(uint32_t *tot, uint32_t ntiles) {
+__global__ __launch_bounds__(1024) void order_scan_top_kernel(uint32_t *tot, uint32_t ntiles, OrderGate g) {
   __shared__ uint32_t wsum[16];
+  if (!order_gate_open(g)) return;
   const uint32_t s = threadIdx.x < ntiles ? tot[threadIdx.x] : 0u;
   uint32_t x = s;
 #pragma unroll
@@ -172,7 +263,8 @@ __device__ __forceinline__ uint32_t order_deal(const OrderParams &p, uint32_t s)
 }
 
 // pass 3: every row to its position, perm[position] = row
-__global__ __launch_bounds__(256) void order_scatter_kernel(OrderParams p) {
+__global__ __launch_bounds__(256) void order_scatter_kernel(OrderParams p, OrderGate g) {
+  if (!order_gate_last(g)) return;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += gridDim.x * blockDim.x) {
     if (order_in_prefix(p, i)) { order_copy_row(p, i, order_sample_pos(p, i / p.stride)); continue; }
     const uint32_t key = order_key_of(p, i);
@@ -224,9 +316,11 @@ __device__ __forceinline__ void coarse_starts(uint32_t *starts /*LDS [257]*/, co
   __syncthreads();
 }
 
-__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_coarse_count_kernel(OrderParams p, OrderSmall q) {
+__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_coarse_count_kernel(OrderParams p, OrderSmall q, OrderGate g) {
   __shared__ uint32_t h[ORDER_COARSE];
   const uint32_t tid = threadIdx.x;
+  if (!order_gate_first(g)) return;
+  order_snapshot(g, p.src, (size_t)p.n * p.mp);
   if (tid < ORDER_COARSE) h[tid] = 0;
   __syncthreads();
   const uint32_t r0 = blockIdx.x * q.rows_per_wg, r1 = min(p.n, r0 + q.rows_per_wg);
@@ -236,9 +330,10 @@ __global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_coarse_count_kernel
   if (tid < ORDER_COARSE && h[tid]) atomicAdd(&q.ctot[tid], h[tid]);
 }
 
-__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_coarse_scatter_kernel(OrderParams p, OrderSmall q) {
+__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_coarse_scatter_kernel(OrderParams p, OrderSmall q, OrderGate g) {
   __shared__ uint32_t h[ORDER_COARSE], base[ORDER_COARSE], starts[ORDER_COARSE + 1];
   const uint32_t tid = threadIdx.x;
+  if (!order_gate_open(g)) return;
   if (tid < ORDER_COARSE) h[tid] = 0;
   coarse_starts(starts, q.ctot);
   const uint32_t r0 = blockIdx.x * q.rows_per_wg, r1 = min(p.n, r0 + q.rows_per_wg);
@@ -264,9 +359,10 @@ __global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_coarse_scatter_kern
   }
 }
 
-__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_fine_kernel(OrderParams p, OrderSmall q) {
+__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_fine_kernel(OrderParams p, OrderSmall q, OrderGate g) {
   __shared__ uint32_t f[ORDER_FINE_MAX], starts[ORDER_COARSE + 1], wsum[16];
   const uint32_t tid = threadIdx.x, nfine = 1u << q.fine_bits, fmask = nfine - 1u;
+  if (!order_gate_last(g)) return;
   for (uint32_t i = tid; i < nfine; i += ORDER_SMALL_THREADS) f[i] = 0;
   coarse_starts(starts, q.ctot);
   const uint32_t b0 = starts[blockIdx.x], b1 = starts[blockIdx.x + 1];
@@ -401,10 +497,11 @@ __device__ __forceinline__ void greedy_chunk(const OrderParams &p, const uint32_
   }
 }
 
-__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_fine_greedy_kernel(OrderParams p, OrderSmall q) {
+__global__ __launch_bounds__(ORDER_SMALL_THREADS) void order_fine_greedy_kernel(OrderParams p, OrderSmall q, OrderGate g) {
   __shared__ uint32_t f[ORDER_FINE_MAX], fst[ORDER_FINE_MAX + 1], starts[ORDER_COARSE + 1], wsum[16];
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];         // [glist] row list | [gwaves] balance state
   const uint32_t tid = threadIdx.x, nfine = 1u << q.fine_bits, fmask = nfine - 1u;
+  if (!order_gate_last(g)) return;
   for (uint32_t i = tid; i < nfine; i += ORDER_SMALL_THREADS) f[i] = 0;
   coarse_starts(starts, q.ctot);
   const uint32_t b0 = starts[blockIdx.x], b1 = starts[blockIdx.x + 1];
@@ -496,6 +593,7 @@ static thread_local int64_t g_order_call_nq = 0;
 void order_set_call_queries(int64_t nq) { g_order_call_nq = nq; }
 
 bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4]) {
+  if (g_order_call_nq < 0) return false;          // (order_rows_cached: the plain set)
   if (!tuning("ORDER_GREEDY", 1) || !tuning("ORDER_TWO_LEVEL", 1) || tuning("ORDER_CBITS", 0) > 0) return false;
   if (g_order_call_nq > 0 && g_order_call_nq < tuning("ORDER_GREEDY_MIN_NQ", 16384)) return false;
   if (mp != 8 && mp != 16) return false;
@@ -550,23 +648,30 @@ size_t order_scratch_bytes(int64_t n, int total_bits) {
   return (size_t)n * 4 + (nbins + ntiles + 16) * 4;
 }
 
-// codes [n][mp] -> dst [n][mp] + perm [n]; scratch of order_scratch_bytes().  t: the scan tiling (scan_order_tiling).
-int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t n, int mp, void *scratch,
-                      const OrderTiling &t, hipStream_t stream) {
+// One ordering as the host plans it: the kernels' parameters (pointers left out: order_bind) and which path runs them.
+struct OrderSet {
   OrderParams p;
+  OrderSmall q;
+  bool two_level, greedy;
+  int total;
+  uint32_t lds;           // dynamic LDS of order_fine_greedy_kernel
+};
+
+// Plan the ordering of n rows of mp bytes under the switches as they stand (and order_set_call_queries).  Every byte of the
+// set is defined -- it is part of order_rows_cached's key.
+static int order_plan_set(OrderSet &s, int64_t n, int mp, const OrderTiling &t) {
+  memset(&s, 0, sizeof(s));
+  OrderParams &p = s.p;
   const int rpt = t.rpt, gran = t.gran;
   const int total = order_key_bits(n, mp, t, p.nb);
   if (total <= 0 || total > 24) return fail(RQ_EINVAL, "order_rows: nothing to order (n=%lld)", (long long)n);
-  p.gfree = 0; p.gwaves = 0; p.glist = 0;
+  s.total = total;
   uint32_t gp[4];
   const bool greedy_on = order_greedy_runs(n, mp, t, total, gp);
-  p.src = src; p.dst = dst; p.perm = perm;
   p.n = (uint32_t)n; p.mp = mp;
   p.ncoord = 0;
   for (int c = 0; c < 8; ++c) if (p.nb[c]) p.ncoord = c + 1;
   p.nbins = 1u << total;
-  p.rank = reinterpret_cast<uint32_t *>(scratch);
-  p.hist = p.rank + n;
   p.rpt = (uint32_t)rpt;
   p.group = (uint32_t)t.group;
   p.tile = 64u * (uint32_t)rpt;
@@ -582,38 +687,149 @@ int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t 
     while (gcd_u32(a, p.ngran) != 1u) a += 2u;
     p.weyl = a % p.ngran;
   }
-  if (total >= 9 && total <= 18 && tuning("ORDER_TWO_LEVEL", 1)) {
+  s.two_level = total >= 9 && total <= 18 && tuning("ORDER_TWO_LEVEL", 1);
+  if (s.two_level) {
     // two levels: 256 coarse buckets, <= 1024 fine ones inside each (scratch: [n] row numbers | 512 counters)
-    OrderSmall q;
-    q.idx = reinterpret_cast<uint32_t *>(scratch);
-    q.ctot = q.idx + n;
-    q.fine_bits = total - 8;
-    q.rows_per_wg = 4 * ORDER_SMALL_THREADS;       // (order_coarse_scatter_kernel: PER)
-    const uint32_t nwg = (uint32_t)((n + q.rows_per_wg - 1) / q.rows_per_wg);
-    RQ_HIP(hipMemsetAsync(q.ctot, 0, 2 * ORDER_COARSE * 4, stream));
-    hipLaunchKernelGGL(order_coarse_count_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q);
-    hipLaunchKernelGGL(order_coarse_scatter_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q);
+    s.q.fine_bits = total - 8;
+    s.q.rows_per_wg = 4 * ORDER_SMALL_THREADS;       // (order_coarse_scatter_kernel: PER)
     if (greedy_on) {
       // the free tables: the last gfree bytes of the row (the key covers the leading ones; a partly covered byte is balanced too)
+      s.greedy = true;
       p.gfree = (int)gp[0];
       p.gwaves = gp[1]; p.glist = gp[2];
+      s.lds = gp[3];
+    }
+  }
+  return RQ_OK;
+}
+
+static void order_bind(OrderSet &s, uint8_t *dst, uint32_t *perm, const uint8_t *src, void *scratch) {
+  s.p.src = src; s.p.dst = dst; s.p.perm = perm;
+  s.p.rank = reinterpret_cast<uint32_t *>(scratch);
+  s.p.hist = s.p.rank + s.p.n;
+  s.q.idx = reinterpret_cast<uint32_t *>(scratch);
+  s.q.ctot = s.q.idx + s.p.n;
+}
+
+// Launch a bound set.  g.state == nullptr: an ordinary ordering.  Gated (order_rows_cached): the launch stops at the first
+// kernel that could not be queued, so the kernel that marks the copy as built never runs behind a hole.
+static int order_run_set(const OrderSet &s, const OrderGate &g, bool zero_counters, hipStream_t stream) {
+  const OrderParams &p = s.p;
+  const int64_t n = p.n;
+  if (s.two_level) {
+    const OrderSmall &q = s.q;
+    const uint32_t nwg = (uint32_t)((n + q.rows_per_wg - 1) / q.rows_per_wg);
+    if (zero_counters) RQ_HIP(hipMemsetAsync(q.ctot, 0, 2 * ORDER_COARSE * 4, stream));
+    hipLaunchKernelGGL(order_coarse_count_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q, g);
+    RQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(order_coarse_scatter_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q, g);
+    RQ_HIP(hipGetLastError());
+    if (s.greedy) {
       RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(order_fine_greedy_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp[3]));
-      hipLaunchKernelGGL(order_fine_greedy_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), gp[3], stream, p, q);
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+      hipLaunchKernelGGL(order_fine_greedy_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), s.lds, stream, p, q, g);
     } else {
-      hipLaunchKernelGGL(order_fine_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), 0, stream, p, q);
+      hipLaunchKernelGGL(order_fine_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), 0, stream, p, q, g);
     }
     RQ_HIP(hipGetLastError());
     return RQ_OK;
   }
   const uint32_t ntiles = (p.nbins + ORDER_SCAN_TILE - 1) / ORDER_SCAN_TILE;
-  RQ_HIP(hipMemsetAsync(p.hist, 0, (size_t)(p.nbins + ntiles) * 4, stream));
   const uint32_t grid = (uint32_t)std::min<int64_t>((n + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(order_rank_kernel, dim3(grid), dim3(256), 0, stream, p);
-  hipLaunchKernelGGL(order_scan_tiles_kernel, dim3(ntiles), dim3(1024), 0, stream, p.hist, p.nbins);
-  hipLaunchKernelGGL(order_scan_top_kernel, dim3(1), dim3(1024), 0, stream, p.hist + p.nbins, ntiles);
-  hipLaunchKernelGGL(order_scatter_kernel, dim3(grid), dim3(256), 0, stream, p);
+  if (g.state) {
+    hipLaunchKernelGGL(order_zero_kernel, dim3(grid), dim3(256), 0, stream, p, p.nbins + ntiles, g);
+    RQ_HIP(hipGetLastError());
+  } else if (zero_counters) {
+    RQ_HIP(hipMemsetAsync(p.hist, 0, (size_t)(p.nbins + ntiles) * 4, stream));
+  }
+  hipLaunchKernelGGL(order_rank_kernel, dim3(grid), dim3(256), 0, stream, p, g);
   RQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(order_scan_tiles_kernel, dim3(ntiles), dim3(1024), 0, stream, p.hist, p.nbins, g);
+  RQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(order_scan_top_kernel, dim3(1), dim3(1024), 0, stream, p.hist + p.nbins, ntiles, g);
+  RQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(order_scatter_kernel, dim3(grid), dim3(256), 0, stream, p, g);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
+// codes [n][mp] -> dst [n][mp] + perm [n]; scratch of order_scratch_bytes().  t: the scan tiling (scan_order_tiling).
+int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t n, int mp, void *scratch,
+                      const OrderTiling &t, hipStream_t stream) {
+  OrderSet s;
+  RQ_TRY(order_plan_set(s, n, mp, t));
+  order_bind(s, dst, perm, src, scratch);
+  OrderGate g;
+  memset(&g, 0, sizeof(g));
+  return order_run_set(s, g, true, stream);
+}
+
+// ---- the kept order: host side ---------------------------------------------------------------------------------------------------
+// The key is everything that defines the order except the bytes themselves: n, m, mp and the non-pointer content of the plain
+// set and of the balanced set a once-ordered base of this shape would get (none: ORDER_GREEDY = 0, shapes without a balance).
+// It does not depend on the batch size: ORDER_GREEDY_MIN_NQ only picks which of the two a MISS builds.  A new key gets a new id,
+// and the device word OC_BUILT says which id the copy holds -- the host never vouches for kernels that may not have run.
+struct OrderCacheKey {
+  int64_t n;
+  int m, mp, has_b;
+  OrderSet plain, bal;
+};
+static_assert(sizeof(OrderCacheKey) <= sizeof(OrderCacheHost::key), "OrderCacheHost::key too small");
+
+size_t order_cache_state_bytes() { return OC_WORDS * sizeof(uint32_t); }
+
+int order_cached_key_bits(int64_t n, int mp, const OrderTiling &t) {       // the longer key of the two sets: sizes the scratch
+  int nb[8];
+  order_set_call_queries(-1);
+  const int bits = order_key_bits(n, mp, t, nb);
+  order_set_call_queries(0);
+  return bits;
+}
+
+int order_rows_cached(uint8_t *dst, uint32_t *perm, uint8_t *snap, const uint8_t *src, int64_t n, int m, int mp, void *scratch,
+                      const OrderTiling &t, int64_t nq, uint32_t *state, OrderCacheHost *h, hipStream_t stream) {
+  static uint32_t next_id = 0;          // callers hold the device lock of their own device only
+  static std::mutex id_mu;
+  OrderCacheKey key;
+  memset(&key, 0, sizeof(key));
+  key.n = n; key.m = m; key.mp = mp;
+  order_set_call_queries(-1);           // never balanced
+  int rc = order_plan_set(key.plain, n, mp, t);
+  order_set_call_queries(0);            // as a base that is ordered once
+  if (rc == RQ_OK) rc = order_plan_set(key.bal, n, mp, t);
+  if (rc != RQ_OK) return rc;
+  key.has_b = key.bal.greedy ? 1 : 0;
+  if (!key.has_b) memset(&key.bal, 0, sizeof(key.bal));
+  if (h->key_id == 0 || memcmp(h->key, &key, sizeof(key)) != 0) {
+    std::lock_guard<std::mutex> lk(id_mu);
+    if (++next_id == 0) ++next_id;
+    h->key_id = next_id;
+    memcpy(h->key, &key, sizeof(key));
+  }
+  if (++h->epoch == 0) ++h->epoch;
+  // today's rule for the build on a miss: balanced only for batches that pay for it in one call
+  const bool first_bal = key.has_b && !(nq > 0 && nq < tuning("ORDER_GREEDY_MIN_NQ", 16384));
+  OrderSet first = first_bal ? key.bal : key.plain;
+  order_bind(first, dst, perm, src, scratch);
+  OrderGate g;
+  memset(&g, 0, sizeof(g));
+  g.state = state; g.snap = snap; g.key = h->key_id; g.epoch = h->epoch;
+  // The upgrade set follows whichever set a miss would build: a plain copy left by a short first batch must not be scanned
+  // unbalanced for good by the large batches that come after it.
+  g.role = 1; g.can_upgrade = key.has_b; g.balanced = first_bal;
+  const size_t bytes = (size_t)n * mp;
+  const uint32_t cgrid = (uint32_t)std::max<size_t>(1, std::min<size_t>((bytes / 16 + 511) / 512, 2048));
+  const bool zero2 = first.two_level || g.can_upgrade;      // both sets keep their 512 counters behind the n scratch words
+  hipLaunchKernelGGL(order_check_kernel, dim3(cgrid), dim3(256), 0, stream, src, (const uint8_t *)snap, bytes, state, g.key, g.epoch,
+                     reinterpret_cast<uint32_t *>(scratch) + n, zero2 ? 2u * ORDER_COARSE : 0u);
+  RQ_HIP(hipGetLastError());
+  RQ_TRY(order_run_set(first, g, false, stream));
+  if (g.can_upgrade) {
+    OrderSet up = key.bal;
+    order_bind(up, dst, perm, src, scratch);
+    g.role = 2; g.can_upgrade = 0; g.balanced = 1;
+    RQ_TRY(order_run_set(up, g, false, stream));
+  }
   return RQ_OK;
 }
 
