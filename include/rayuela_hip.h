@@ -159,6 +159,44 @@ int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *X, const fl
  * back, the obj means), encodes (training)}; cap entries written */
 int rq_last_lsq_timing(double *ms, int cap);
 
+/* ---- LSQ++: stochastic relaxations of LSQ (src/SR.jl, src/SR_perturbations.jl).  Contract in DESIGN.md section 2
+ * ("SR noise").  The reference draws from Julia's global randn; here the noise is a counter-based standard normal
+ * variate z(seed, kind, call, element index) that tests/sr_oracle.py restates bit for bit, so results depend on
+ * neither nsplits, the chunking nor the run. */
+#define RQ_SR_C 0           /* noise on the data (SR_C_perturb) */
+#define RQ_SR_D 1           /* noise on the codebooks (SR_D_perturb) */
+/* Statistics.std(X, dims=2) (src/SR_perturbations.jl:38, :62): sigma [d] = the sample standard deviation (divisor n - 1)
+ * of every column of X [n][d]; a two-pass f64 reduction in a fixed order, rounded to f32, bitwise reproducible.  n >= 2
+ * (the reference gives NaN below that), d >= 1. */
+int rq_sr_std(float *sigma, const float *X, int64_t n, int d);
+/* The noise of SR_C_perturb (src/SR_perturbations.jl:67-70) and SR_D_perturb (:41-46):
+ * Y[r][j] = (float)((double)X[r][j] + z * ((double)sigma[j] * scale)), z = z(seed, kind, call, (row0 + r) * d + j).
+ * X, Y [n][d] (Y may alias X), sigma [d]; kind RQ_SR_C or RQ_SR_D; call >= 0 numbers the perturbation call of a training
+ * run; row0 >= 0 is the first row's index in that call's whole array, so a slice gives the same rows; scale finite. */
+int rq_sr_perturb(float *Y, const float *X, const float *sigma, double scale, int64_t n, int d, int kind, uint64_t seed,
+                  int64_t call, int64_t row0);
+/* apply_schedule (src/SR_perturbations.jl:4-25), the factor alone, f64 on the host (no device is touched):
+ * schedule 1: (1 - iter/niter)^p, 2: 1/(1 + iter)^p (the reference divides stdev by the power: at most one f64 rounding
+ * apart), 3: p^(iter/2); any other schedule is an error.  niter >= 1, iter >= 0 (<= niter for schedule 1), p finite and
+ * >= 0; a scale that does not come out finite is an error. */
+int rq_sr_schedule(double *scale, int schedule, int64_t iter, int64_t niter, double p);
+/* train_sr_cuda (src/SR.jl:88-176; clean_update = 1) / train_sr (:4-84; clean_update = 0, schedule 1), device-resident:
+ * RX = R'X; step(0); for it = 1..niter { obj[it-1] = qerror(RX, codes, C); step(it); if clean_update: C = update(RX,
+ * codes) }; obj[niter] = qerror; C_i <- R C_i.  step(call) is, for method RQ_SR_C, C = update(perturb(RX)), and for
+ * RQ_SR_D, C = perturb(update(RX)) with sigma = rq_sr_std of C as [m h][d], / m in f32; then codes = encode(RX, codes, C)
+ * with ILS iterations call * ilsiter .. of one `seed` stream (rq_encode_icm).  The perturbation of call `call` has the
+ * scale of schedule iteration `call`, except that RQ_SR_D's call 0 has that of iteration 1 (:127).  update is
+ * rq_update_codebooks_lsq with rho = 1e-4; qerror is the mean of a fresh veccost pass against the current C.
+ * C [m][h][d] out; codes [n][m] in: start codes, out: final codes; obj [niter + 1] f64 out; R [d][d] memory image of
+ * Julia's R, NULL = identity.  Limits of rq_train_lsq, and niter >= 1, n >= 2 for RQ_SR_C.  Every argument is checked
+ * before any device work. */
+int rq_train_sr(float *C, uint8_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h,
+                int niter, int ilsiter, int icmiter, int npert, int randord, int method, int schedule, double p,
+                int clean_update, uint64_t seed, int nsplits);
+/* milliseconds of this thread's last rq_train_sr by phase (hipEvents), summed over the call: {standard deviations,
+ * perturbations, codebook updates, encodes, obj passes, other (the uploads, R'X, the rotation back)}; cap entries written */
+int rq_last_sr_timing(double *ms, int cap);
+
 /* ---- Chain quantization (src/ChainQ.jl).  Contract in DESIGN.md section 2 ("Chain quantization").
  * Layouts as for LSQ: X [n][d], C [m][h][d] (m full-dimensional codebooks, one codeword per row; a trained chain quantizer
  * is zero outside rq_chain_dims, but any C is accepted), codes [n][m] uint8 zero-based.  1 <= m <= 16, 2 <= h <= 256, d >= 1.

@@ -18,6 +18,7 @@ import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
+export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
 export HipIndex, set_codes!, set_codes_synth!, search, HipDataset, quantize
 
@@ -492,6 +493,91 @@ function train_lsq_cuda(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Fl
                         C::Vector{Matrix{Float32}}, niter::Integer, ilsiter::Integer, icmiter::Integer, randord::Bool,
                         npert::Integer, nsplits::Integer=1, V::Bool=false; seed::Integer=0)
   Cn, Bn, obj = _train_lsq(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits)
+  V && for (it, o) in enumerate(obj); println("$it $o"); end
+  return Cn, Bn, obj
+end
+
+# ---- LSQ++ (src/SR.jl:4-84, :88-176; src/SR_perturbations.jl:4-73): the noise (a counter-based standard normal variate,
+# DESIGN.md section 2 "SR noise") and the training loop run on the device.  These shims follow the LSQ ones above and,
+# like them, have not been run (no Julia was available).
+function _sr_kind(method::AbstractString)
+  method in ["SR_C", "SR_D"] || error("SR method unknown")
+  return method == "SR_C" ? 0 : 1
+end
+
+function _sr_scale(iter::Integer, niter::Integer, schedule::Integer, p::AbstractFloat)
+  scale = Ref{Cdouble}(0.0)
+  _check(ccall((:rq_sr_schedule, librayuela_hip), Cint, (Ref{Cdouble}, Cint, Int64, Int64, Cdouble),
+    scale, Cint(schedule), Int64(iter), Int64(niter), Float64(p)))
+  return scale[]
+end
+
+function _sr_std(X::Matrix{Float32})
+  d, n  = size(X)
+  sigma = Vector{Float32}(undef, d)
+  _check(ccall((:rq_sr_std, librayuela_hip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint), sigma, X, Int64(n), Cint(d)))
+  return sigma
+end
+
+function _sr_perturb(X::Matrix{Float32}, sigma::Vector{Float32}, scale::Float64, kind::Integer, seed::Integer,
+                     call::Integer, row0::Integer=0)
+  d, n = size(X)
+  Y    = Matrix{Float32}(undef, d, n)
+  _check(ccall((:rq_sr_perturb, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Cdouble, Int64, Cint, Cint, UInt64, Int64, Int64),
+    Y, X, sigma, Float64(scale), Int64(n), Cint(d), Cint(kind), UInt64(seed), Int64(call), Int64(row0)))
+  return Y
+end
+
+function SR_C_perturb(X::Matrix{Float32}, iter::Integer, niter::Integer, schedule::Integer=1, p::AbstractFloat=0.5;
+                      seed::Integer=0, call::Integer=iter)
+  return _sr_perturb(X, _sr_std(X), _sr_scale(iter, niter, schedule, p), 0, seed, call)
+end
+
+function SR_D_perturb(C::Vector{Matrix{Float32}}, iter::Integer, niter::Integer, schedule::Integer=1,
+                      p::AbstractFloat=0.5; seed::Integer=0, call::Integer=iter)
+  m     = length(C)
+  h     = size(C[1], 2)
+  Cc    = cat(C..., dims=2)
+  sigma = _sr_std(Cc) ./ Float32(m)
+  Y     = _sr_perturb(Cc, sigma, _sr_scale(iter, niter, schedule, p), 1, seed, call)
+  for i = 1:m; C[i] .= Y[:, (i - 1) * h + 1:i * h]; end
+  return C
+end
+
+function _train_sr(X::Matrix{Float32}, m, h, R::Matrix{Float32}, B::Matrix{Int16}, niter, ilsiter, icmiter, randord,
+                   npert, method, schedule, p, clean_update, seed, nsplits)
+  d, n  = size(X)
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  obj   = zeros(Float64, niter + 1)
+  _check(ccall((:rq_train_sr, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Cint,
+     Cint, Cint, Cint, Cdouble, Cint, UInt64, Cint),
+    Cc, codes, obj, X, R, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), Cint(ilsiter), Cint(icmiter), Cint(npert),
+    Cint(randord ? 1 : 0), Cint(_sr_kind(method)), Cint(schedule), Float64(p), Cint(clean_update ? 1 : 0), UInt64(seed),
+    Cint(nsplits)))
+  return _split_codebooks(Cc, m, h), convert(Matrix{Int16}, codes) .+ Int16(1), convert(Vector{Float32}, obj)
+end
+
+# As committed the reference passes p where the schedule is expected (src/SR.jl:35, :66); its evident intent, schedule 1
+# with power p, runs here.  No codebook update follows an iteration's encode.
+function train_sr(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Float32}, B::Matrix{Int16},
+                  C::Vector{Matrix{Float32}}, niter::Integer, ilsiter::Integer, icmiter::Integer, randord::Bool,
+                  npert::Integer, method::AbstractString, p::Float32, cpp::Bool=true, V::Bool=false; seed::Integer=0)
+  cpp && h != 256 && throw(ArgumentError("train_sr with cpp=true requires h = 256 codewords; got h=$h"))
+  Cn, Bn, obj = _train_sr(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, method, 1, p, false, seed, 1)
+  copyto!(B, Bn)          # the final codes land in B, as encoding_icm's do
+  V && for (it, o) in enumerate(obj); println("$it $o"); end
+  return Cn, Bn, obj
+end
+
+function train_sr_cuda(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Float32}, B::Matrix{Int16},
+                       C::Vector{Matrix{Float32}}, niter::Integer, ilsiter::Integer, icmiter::Integer, randord::Bool,
+                       npert::Integer, method::AbstractString, schedule::Integer, p::AbstractFloat=0.5,
+                       nsplits::Integer=1, V::Bool=false; seed::Integer=0)
+  Cn, Bn, obj = _train_sr(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, method, schedule, p, true, seed,
+                          nsplits)
   V && for (it, o) in enumerate(obj); println("$it $o"); end
   return Cn, Bn, obj
 end

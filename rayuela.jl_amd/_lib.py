@@ -58,6 +58,12 @@ SIGNATURES = {
     "rq_dev_lsq_normal_eq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _vp]),
     "rq_train_lsq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i32]),
     "rq_last_lsq_timing": (_i32, [_vp, _i32]),
+    "rq_sr_std": (_i32, [_vp, _vp, _i64, _i32]),
+    "rq_sr_perturb": (_i32, [_vp, _vp, _vp, C.c_double, _i64, _i32, _i32, _u64, _i64, _i64]),
+    "rq_sr_schedule": (_i32, [_vp, _i32, _i64, _i64, C.c_double]),
+    "rq_train_sr": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                           C.c_double, _i32, _u64, _i32]),
+    "rq_last_sr_timing": (_i32, [_vp, _i32]),
     "rq_quantize_chainq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
     "rq_dev_quantize_chainq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "rq_chain_dims": (_i32, [_i32, _i32, _vp, _vp]),

@@ -347,11 +347,15 @@ int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out,
   RQ_TRY(workspace(WS_ICM_BIN, bin_bytes + sa_bytes, &wbin, stream));
   RQ_TRY(workspace(WS_ICM_U, (size_t)chunk * row_bytes, &wu, stream));
   float *binT = (float *)wbin, *sa = binT + bin_bytes / 4, *U = (float *)wu;
-  RQ_HIP(hipMemsetAsync(binT, 0, bin_bytes, stream));
-  hipLaunchKernelGGL(icm_pair_kernel, dim3(m * m * h), dim3(256), 0, stream, binT, C, m, h, d, HS);
-  RQ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(icm_sqnorm_kernel, dim3((m * h + 255) / 256), dim3(256), 0, stream, sa, C, m * h, d);
-  RQ_HIP(hipGetLastError());
+  // a zero-iteration encode is a veccost pass: the ILS kernel then uses neither the tables nor the unaries it loads
+  const bool tables = ilsiter > 0;
+  if (tables) {
+    RQ_HIP(hipMemsetAsync(binT, 0, bin_bytes, stream));
+    hipLaunchKernelGGL(icm_pair_kernel, dim3(m * m * h), dim3(256), 0, stream, binT, C, m, h, d, HS);
+    RQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(icm_sqnorm_kernel, dim3((m * h + 255) / 256), dim3(256), 0, stream, sa, C, m * h, d);
+    RQ_HIP(hipGetLastError());
+  }
   hipEvent_t ev[2] = {nullptr, nullptr};
   if (unary_ms) {
     *unary_ms = 0;
@@ -363,9 +367,11 @@ int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out,
     const int64_t nr = std::min(chunk, n - r0);
     const int ctiles = (m * h + 31) / 32;
     if (unary_ms) (void)hipEventRecord(ev[0], stream);
-    hipLaunchKernelGGL(icm_unary_kernel<false>, dim3((unsigned)((nr + 31) / 32), (ctiles + UN_WAVES - 1) / UN_WAVES),
-                       dim3(UN_WAVES * 64), 0, stream, U, X + (size_t)r0 * d, C, sa, nr, d, m, h, HS, (const int *)nullptr);
-    if (hipGetLastError() != hipSuccess) { rc = fail(RQ_EINVAL, "encode_icm: unary launch failed"); break; }
+    if (tables) {
+      hipLaunchKernelGGL(icm_unary_kernel<false>, dim3((unsigned)((nr + 31) / 32), (ctiles + UN_WAVES - 1) / UN_WAVES),
+                         dim3(UN_WAVES * 64), 0, stream, U, X + (size_t)r0 * d, C, sa, nr, d, m, h, HS, (const int *)nullptr);
+      if (hipGetLastError() != hipSuccess) { rc = fail(RQ_EINVAL, "encode_icm: unary launch failed"); break; }
+    }
     if (unary_ms) {
       (void)hipEventRecord(ev[1], stream);
       (void)hipEventSynchronize(ev[1]);

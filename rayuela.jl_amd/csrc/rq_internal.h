@@ -223,4 +223,8 @@ int icm_unary_launch(float *U, const float *X, const float *C, const float *sa, 
 int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
                          double rho, hipStream_t stream);
 int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t stream);
+// C [m][h][d] f32 <- the fastbin update of (X, codes); *out <- the f64 mean of cost [n] (rq_train_lsq's obj); device pointers
+int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
+                      hipStream_t stream);
+int lsq_mean_launch(double *out, const float *cost, int64_t n, hipStream_t stream);
 }  // namespace rq

@@ -495,6 +495,18 @@ int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *co
 
 int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t s) { return spd_solve_dev(A, Y, mh, d, s); }
 
+// The fastbin update and the obj mean for the SR training loop (rq_sr.hip), which keeps a phase clock of its own.
+int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
+                      hipStream_t s) {
+  PhaseClock clk(s, false);
+  return update_dev(C, X, codes, n, d, m, h, rho, s, clk);
+}
+
+int lsq_mean_launch(double *out, const float *cost, int64_t n, hipStream_t s) {
+  LSQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, out, cost, n);
+  return RQ_OK;
+}
+
 }  // namespace rq
 
 using namespace rq;

@@ -1,5 +1,6 @@
 """Host mirror of the end-to-end drivers: experiment_pq (src/PQ.jl:104-132), experiment_pq_query_base
-(:137-159), experiment_opq (src/OPQ.jl:142-171), experiment_opq_query_base (:174-197).
+(:137-159), experiment_opq (src/OPQ.jl:142-171), experiment_opq_query_base (:174-197), experiment_rvq
+(src/RVQ.jl:130-175), experiment_sr_cuda (src/SR.jl:247-306, :348-373), experiment_sr_cuda_query_base (:308-344, :376-402).
 train -> encode the base -> ADC search -> recall, every O(n) step on the device."""
 import numpy as np
 
@@ -103,3 +104,70 @@ def experiment_rvq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
+
+
+def _sr_init(Xt, m, h, niter_init, chain, V, seed):
+    """The initialisation of the LSQ++ drivers: train_opq "natural" (src/SR.jl:365, :391), then train_chainq (:397) where
+    the reference runs it.  Returns C, B, R, opq_error."""
+    from .ChainQ import train_chainq
+    C, B, R, opq_error = train_opq(Xt, m, h, niter_init, "natural", V, seed=seed)
+    if chain:
+        C, B, R, _ = train_chainq(Xt, m, h, R, B, C, niter_init, V)
+    return C, B, R, opq_error
+
+
+def experiment_sr_cuda_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, nsplits_train=1, sr_method="SR_D", V=False,
+                                  seed=0, B=None, C=None, R=None, ilsiter=8, icmiter=4, randord=True, npert=4,
+                                  schedule=1, p=0.5, niter_init=25):
+    """experiment_sr_cuda_query_base (src/SR.jl:308-344, :376-402): train_sr_cuda -> norms codebook -> linscan_lsq over
+    the training codes -> eval_recall.  Without B, C, R the start is train_opq "natural" then train_chainq (niter_init
+    iterations each, the reference's 25) and the result is ((C, B, R, train_error, recall), opq_error) like the
+    reference's six-argument method; with them it is (C, B, R, train_error, recall) like the full method."""
+    from .Linscan import linscan_lsq
+    from .SR import train_sr_cuda
+    d = Xt.shape[1]
+    opq_error = None
+    given = B is not None
+    if not given:
+        C, B, R, opq_error = _sr_init(Xt, m, h, niter_init, True, V, seed)
+    if V:
+        print("Running CUDA %s training... " % sr_method)
+    C, B, train_error = train_sr_cuda(Xt, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, sr_method, schedule, p,
+                                      nsplits_train, V, seed=seed)
+    norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
+    db_norms = norms_C[norms_B - 1].astype(np.float32)
+    dists, idx = linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    recall = eval_recall(gt, idx, knn, verbose=V)
+    res = (C, B, R, train_error, recall)
+    return res if given else (res, opq_error)
+
+
+def experiment_sr_cuda(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, nsplits_train=1, nsplits_base=1, sr_method="SR_D",
+                       V=False, seed=0, B=None, C=None, R=None, ilsiter=8, icmiter=4, randord=True, npert=4, schedule=1,
+                       p=0.5, niter_init=25):
+    """experiment_sr_cuda (src/SR.jl:247-306, :348-373): train_sr_cuda -> norms codebook -> the base encoded by
+    encode_icm_cuda with 4 ilsiter iterations from seeded random codes -> quantised database norms -> linscan_lsq ->
+    eval_recall.  Without B, C, R the start is train_opq "natural" (the reference leaves train_chainq out here, :369).
+    Returns C, B, R, train_error, B_base, recall."""
+    from .Linscan import linscan_lsq
+    from .LSQ import encode_icm_cuda
+    from .SR import train_sr_cuda
+    d = Xt.shape[1]
+    if B is None:
+        C, B, R, _ = _sr_init(Xt, m, h, niter_init, False, V, seed)
+    if V:
+        print("Running LSQ++ (%s) with %d codebooks, %d perturbations, %d icm iterations and random order = %s"
+              % (sr_method, m, npert, icmiter, bool(randord)))
+    C, B, train_error = train_sr_cuda(Xt, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, sr_method, schedule, p,
+                                      nsplits_train, V, seed=seed)
+    _, norms_C = _norms_codebook(B, C, h, seed=seed)
+    B_base = np.random.default_rng(seed).integers(1, h + 1, size=(Xb.shape[0], m)).astype(np.int16)
+    Bs_base, objs = encode_icm_cuda(Xb, B_base, C, [ilsiter * 4], icmiter, npert, randord, nsplits_base, V, seed=seed)
+    B_base = Bs_base[-1]
+    if V:
+        print("Error in base is %e" % objs[-1])
+    B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
+    db_norms = norms_C[B_base_norms - 1].astype(np.float32)
+    dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    recall = eval_recall(gt, idx, knn, verbose=V)
+    return C, B, R, train_error, B_base, recall
