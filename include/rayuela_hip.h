@@ -121,7 +121,9 @@ int rq_dev_encode_rvq(uint8_t *codes, float *Xr, const float *codebooks, int64_t
  * ilsiter, icmiter, t0 >= 0, nsplits >= 1 (the minimum number of row chunks).  ILS iterations t0 .. t0+ilsiter-1 run, so a
  * checkpointed run continues the same random stream; results depend on neither nsplits nor the chunking.  codes_out may
  * alias codes_in; cost_out [n] (may be NULL) receives each row's final veccost.  Arguments (codes < h included) are checked
- * before any encode work; errors through rq_last_error.  Non-finite inputs give unspecified but in-range codes. */
+ * before any encode work; errors through rq_last_error.  Non-finite inputs give unspecified but in-range codes FOR THEIR OWN
+ * ROWS: rows are encoded independently, so every other row keeps its codes and its cost (tests/test_gpu_nonfinite_aq.py; the
+ * same holds for rq_quantize_chainq and rq_encode_rvq). */
 int rq_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,
                   int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
                   int64_t t0, int nsplits);
@@ -250,7 +252,8 @@ int rq_last_chainq_timing(double *ms, int cap);
  * 5e5 rows x 4096 queries) -- same answers, not tuned. */
 int rq_linscan_pq(float *dists, uint32_t *ids, const uint8_t *codes, const float *centers,
                   const float *queries, int64_t n, int64_t nq, int m, int d, int k, int id_base);
-/* Non-finite inputs (every scan entry point; tests/test_gpu_nonfinite.py).  The reference builds its table and its distances in
+/* Non-finite inputs (every scan entry point; tests/test_gpu_nonfinite.py, tests/test_gpu_nonfinite_aq.py; the contract in plain
+ * numpy: tests/nonfinite_ref.py, pinned to the oracle by tests/test_nonfinite_ref.py).  The reference builds its table and its distances in
  * plain f32 (deps/src/linscan_aqd.cpp:66-87) and hands the pairs to std::partial_sort (:91-97): +Inf is an ordinary value there
  * (ties part by id), while a NaN breaks the pair comparison's strict weak order -- the reference's answer for such a query is
  * unspecified.  Here:
@@ -261,7 +264,15 @@ int rq_linscan_pq(float *dists, uint32_t *ids, const uint8_t *codes, const float
  *     rows with comparable distances are returned exactly, in (dist, id) order; a list that runs out of them ends in the padding
  *     pair (dist = NaN, id = 0xFFFFFFFF + id_base, i.e. 0 on the one-based Julia side: "no row");
  *   - the other queries of the same 8-query group and of the same launch are unaffected, bit for bit (a group that holds a
- *     NaN query takes the exact, un-sampled path: slower, same answer).  No status is raised: the poisoned rows are data. */
+ *     NaN query takes the exact, un-sampled path: slower, same answer).  No status is raised: the poisoned rows are data.
+ * A NaN is a NaN whatever its sign bit (0x7FC00000 as well as the 0xFFC00000 that x86 gives for Inf - Inf) and whatever produced
+ * it (a NaN input, Inf - Inf, 0 x Inf inside a table); the padding distance is the bit pattern 0x7FFFFFFF, a packed key KEY_MAX.
+ * dbnorms (rq_linscan_lsq, the *_extra_byte symbols, rq_dev_linscan_aq, rq_lsq_prepare) are row data like the codes: a NaN entry
+ * takes its row out of every query's answer, a +Inf / -Inf entry gives the row that distance (unless the row's table sum is the
+ * opposite infinity: NaN again), exactly as `acc + dbnorms[row]` does in the reference.  The LSQ pre-filter's preparation pass
+ * leaves NaN residual norms out of the range it quantises and is switched off by an infinite one; neither changes an answer.
+ * Intermediates that overflow (2 * q of the LSQ table at |q| > 1.7e38) are infinities like any other, denormal tables and
+ * norms keep their bits (nothing is flushed to zero). */
 /* linscan_opq (src/Linscan.jl:93-103): queries are rotated by R' on the device first. */
 int rq_linscan_opq(float *dists, uint32_t *ids, const uint8_t *codes, const float *centers,
                    const float *queries, const float *R, int64_t n, int64_t nq, int m, int d,

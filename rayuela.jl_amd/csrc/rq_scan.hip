@@ -1122,10 +1122,16 @@ __global__ void norm_residual_kernel(const float *__restrict__ nrm, const uint8_
   }
 }
 
+// Range of the COMPARABLE residual norms.  A NaN rho (a NaN norm of either sign, Inf - Inf, a NaN codebook entry) is left out:
+// f2ord is an order for NaN-free inputs only -- a NaN with the sign bit clear would sort above +Inf, one with the sign bit set
+// below -Inf.  Such a row's distance is NaN (never a neighbour, whatever the filter says) unless the NaN came from Inf - Inf
+// against an infinite |c|^2, which switches the filter off (build_qtab).
 __global__ void norm_minmax_kernel(const float *__restrict__ nrm, uint32_t n, uint32_t *info) {
   uint32_t lo = 0xffffffffu, hi = 0u;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint32_t o = f2ord(nrm[i] + 0.0f);
+    const float v = nrm[i];
+    if (v != v) continue;
+    const uint32_t o = f2ord(v + 0.0f);
     lo = min(lo, o);
     hi = max(hi, o);
   }
@@ -1137,9 +1143,13 @@ __global__ void norm_minmax_kernel(const float *__restrict__ nrm, uint32_t n, ui
   if ((threadIdx.x & 63) == 0) { atomicMin(&info[0], lo); atomicMax(&info[1], hi); }
 }
 
+// {nmin, nstep, max |rho|} over the rows norm_minmax_kernel counted.  What build_qtab relies on: nmin <= rho(row) and
+// max |rho| >= |rho(row)| for every row with a comparable rho.  An infinite rho makes max |rho| infinite, which switches the
+// filter off for every query (build_qtab: A < +Inf); no comparable rho at all (info still holds the start values) gives zeros.
 __global__ void norm_info_kernel(uint32_t *info) {
   float *f = reinterpret_cast<float *>(info);
-  const float nmin = ord2f(info[0]), nmax = ord2f(info[1]);
+  const bool none = info[0] > info[1];
+  const float nmin = none ? 0.0f : ord2f(info[0]), nmax = none ? 0.0f : ord2f(info[1]);
   float nstep = (nmax - nmin) / 255.0f;
   if (!(nstep > 0.0f) || !(nstep < __uint_as_float(0x7f800000u))) nstep = 0.0f;   // constant norms (or not finite): one cell
   f[4] = nmin;
@@ -1152,7 +1162,7 @@ __global__ void norm_quant_kernel(const float *__restrict__ nrm, uint32_t n, con
   const float nmin = f[4], nstep = f[5];
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const float v = nrm[i];
-    uint32_t b = 0;
+    uint32_t b = 0;                 // (a NaN rho stays in cell 0: every comparison below is false)
     if (nstep > 0.0f) {
       const float t = (v - nmin) / nstep;
       b = t >= 255.0f ? 255u : t > 0.0f ? (uint32_t)t : 0u;

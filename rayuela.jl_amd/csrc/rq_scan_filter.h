@@ -207,7 +207,10 @@ __device__ __forceinline__ void build_qtab(ScanCtrl<ScanCfg<M>::QG> *ctrl, const
     // LSQ tables are signed (-2 <q, c>) and every row adds its norm.  Shifted by their minima the entries are >= 0 again;
     // the norm enters as one more table, indexed by the row's norm BYTE, whose entry is the cell's lower edge -- a lower
     // bound of it.  Rounding is accounted for ABSOLUTELY: with A >= sum_k max|T_k| + max|norm| (original magnitudes,
-    // bounded through the folded ones: fmax = max|T'| + 2 max|c|^2), the sequential f32
+    // bounded through the folded ones: fmax = max|T'| + 2 max|c|^2; the maxima run over the COMPARABLE values -- fmaxf and
+    // norm_minmax_kernel leave NaN entries and NaN residual norms out: a row that uses one either has a NaN distance, so it
+    // is no neighbour whatever the filter says, or got it from Inf - Inf against an infinite |c|^2, and any infinite term
+    // makes A infinite, which switches the filter off for the query), the sequential f32
     // distance of a row (M + 1 <= 17 terms) is within 17u A < 2^-19.9 A of the real sum, so is the f32 sum of the minima,
     // and (tau - base) itself rounds by 2^-24 |tau - base|.  The margin 2^-16 A + 2^-18 |tau - base| covers the three
     // seven times over; A is a few ranges, so it costs < 1e-3 of a filter step.
