@@ -115,6 +115,40 @@ int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n
 int rq_dev_encode_rvq(uint8_t *codes, float *Xr, const float *codebooks, int64_t n, int d, int m, int h,
                       uint32_t *counts, void *stream);
 
+/* ---- Enhanced RVQ / Stacked Quantizers: train_ervq (src/ERVQ.jl:51-135, arXiv 1411.2173).  Contract in DESIGN.md
+ * section 2 ("ERVQ").  quantize_ervq IS quantize_rvq (src/ERVQ.jl:19-26): use rq_encode_rvq.  Layouts as for RVQ: X [n][d],
+ * C [m][h][d] (m full-dimensional codebooks back to back, one entry per row).  1 <= m <= 64, 2 <= h <= 256, any d >= 1.
+ * Every argument (each code's range included) is checked before any work; errors through rq_last_error.  Non-finite input
+ * gives unspecified results, as for rq_train_rvq.
+ *
+ * The codebook update of one step alone (src/ERVQ.jl:85-90, Clustering.update_centers! unweighted): every entry k of block
+ * j (zero-based, 0 <= j < m) that has rows becomes the mean of X - sum_{i != j} C_i[b_i] over the rows with b_j = k, computed
+ * as C_j[k] + the mean of the full residual X - sum_i C_i[b_i] over those rows (the same value; in f32 closer to an f64
+ * evaluation than the literal sum), in a fixed summation order without float atomics: bitwise reproducible.  C in/out: only
+ * block j is written, an entry without rows keeps its bits, nothing is refilled.  codes [n][m] uint8 zero-based; counts [h]
+ * out = the rows per entry of column j.  n >= 0. */
+int rq_ervq_update_codebook(float *C, uint32_t *counts, const float *X, const uint8_t *codes, int64_t n, int d, int m,
+                            int h, int j);
+/* train_ervq(X, B, C, m, h, niter) (src/ERVQ.jl:51-135), device-resident.  C in: start codebooks, out: trained; B1 [n][m]
+ * Int16 one-based in: start codes, out: final codes (== quantize_rvq(X, C) after every complete iteration).  For it = 0 ..
+ * niter-1 and j = 0 .. m-1: the update above on codebook j; entries of j without rows are refilled; stages j .. m-1 are
+ * encoded again (quantize_rvq on the residual entering stage j); the error is recorded.  obj (may be NULL) has niter*m + 1
+ * doubles: obj[0] = qerror of the inputs, obj[1 + it*m + j] = qerror(X, B, C) after step j of iteration it; *error = the
+ * last obj entry.  The trace need not fall from step to step: the greedy re-encode may lose what the update won.  niter = 0
+ * leaves C and B1 untouched and reports their error.  n >= 1.
+ * Entries without rows, for every j: Clustering.repick_unused_centers' rule on the residual entering stage j -- a row drawn
+ * with probability proportional to its cost under the entry values the codes were assigned with, costs lowered after each
+ * draw -- so a refilled entry is a row of that residual (of X for j = 0) bit for bit.  j = 0 follows the same rule as
+ * j >= 1: the reference's own branch for its first codebook (src/ERVQ.jl:93-100) goes through a Julia-0.6 `sum(A, 1)` and
+ * does not run on Julia >= 0.7.  The draws come from the library's stream seeded by `seed`, not from Julia's RNG, so
+ * refilled entries differ from the reference's; without empty entries the result does not depend on `seed`. */
+int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, const float *X, int64_t n, int d, int m, int h,
+                  int niter, uint64_t seed);
+/* milliseconds of this thread's last rq_train_ervq by phase (hipEvents), summed over the call: {initial residual,
+ * increments, refills (with the read-back of the counts), stage encodes, epilogues, error passes, other (the uploads,
+ * the code conversions)}; cap entries written */
+int rq_last_ervq_timing(double *ms, int cap);
+
 /* ---- LSQ encoding: encoding_icm (src/LSQ.jl:272-302) / encode_icm_cuda (src/LSQ_GPU.jl:218-264) -------------------
  * Iterated local search around ICM, contract in DESIGN.md section 2.  X [n][d], C [m][h][d] (m full-dimensional codebooks,
  * one codeword per row), codes [n][m] uint8 zero-based.  1 <= m <= 16, 2 <= h <= 256, d >= 1, 0 <= npert <= m,

@@ -6,6 +6,7 @@
 #   linscan_pq    src/Linscan.jl:5-37    linscan_opq   src/Linscan.jl:93-115
 #   linscan_lsq   src/Linscan.jl:118-157 linscan_cq    src/Linscan.jl:160-193   (SURVEY 8f rank 2)
 #   quantize_rvq  src/RVQ.jl:18-66                                              (SURVEY 8f rank 3)
+#   quantize_ervq src/ERVQ.jl:19-26      train_ervq    src/ERVQ.jl:51-148
 # Julia's column-major arrays are passed as they are: a d-by-n Matrix{Float32} is the C array
 # [n][d] the library expects, an m-by-n Matrix{UInt8} is [n][m], k-by-nq outputs are [nq][k].
 #
@@ -17,6 +18,7 @@ module RayuelaHIP
 import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
+export quantize_ervq, train_ervq
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
@@ -141,6 +143,54 @@ function train_rvq(X::Matrix{Float32}, m::Integer, h::Integer, niter::Integer=25
     Ccat, B, err, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed)))
   C = [Ccat[:, :, i] for i = 1:m]
   return C, B, Float32(err[])
+end
+
+"""
+    quantize_ervq(X, C, V=false) -> B, singletons     (src/ERVQ.jl:19-26): identical to quantize_rvq
+"""
+quantize_ervq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, V::Bool=false) = quantize_rvq(X, C, V)
+
+"""
+    train_ervq(X, B, C, m, h, niter=25, V=false; seed=0) -> C, B, error     (src/ERVQ.jl:51-135)
+Enhanced RVQ / Stacked Quantizers, device-resident (rq_train_ervq): per iteration and codebook j, the codebook update,
+the refill of entries without rows, the re-encode of stages j..m and the error.  `B` is any integer m-by-n matrix of
+one-based codes; the result is `Matrix{Int16}` and equals `quantize_ervq(X, C)[1]`.  The reference prints `Qerror is ...`
+after every step; here `V=true` prints those lines from the recorded trace.  Entries without rows are re-drawn by
+Clustering's rule from the library's stream seeded by `seed` (the reference: Julia's RNG), for the first codebook too.
+"""
+function train_ervq(X::Matrix{Float32}, B::Matrix{T2}, C::Vector{Matrix{Float32}}, m::Integer, h::Integer,
+                    niter::Integer=25, V::Bool=false; seed::Integer=0) where T2 <: Integer
+  d, n = size(X)
+  @assert size(B) == (m, n) && length(C) == m && all(size(Ci) == (d, h) for Ci in C)
+  Ccat = Array{Float32}(undef, d, h, m)            # C view [m][h][d]
+  for i = 1:m
+    Ccat[:, :, i] = C[i]
+  end
+  B1  = convert(Matrix{Int16}, B)
+  B1 === B && (B1 = copy(B))
+  err = Ref{Cdouble}(0.0)
+  obj = Vector{Cdouble}(undef, niter * m + 1)
+  _check(ccall((:rq_train_ervq, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64),
+    Ccat, B1, err, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed)))
+  if V
+    print("Error after init is $(obj[1]) \n")
+    for i = 1:niter
+      print("=== Iteration $i / $niter ===\n")
+      for j = 1:m
+        print("Updating codebook $j... done.\nUpdating codes... done. Qerror is $(obj[1 + (i - 1) * m + j]).\n")
+      end
+    end
+  end
+  return [Ccat[:, :, i] for i = 1:m], B1, Float32(err[])
+end
+
+"""
+    train_ervq(X, m, h, niter=25, V=false; seed=0) -> C, B, error     (src/ERVQ.jl:138-148): initialised by train_rvq
+"""
+function train_ervq(X::Matrix{Float32}, m::Integer, h::Integer, niter::Integer=25, V::Bool=false; seed::Integer=0)
+  C, B, _ = train_rvq(X, m, h, niter, V; seed=seed)
+  train_ervq(X, B, C, m, h, niter, V; seed=seed)
 end
 
 """

@@ -16,6 +16,7 @@ from .RVQ import quantize_rvq, quantize_rvq_u8  # noqa: F401
 from .PQ import train_pq, kmpp_seeds  # noqa: F401,E402
 from .OPQ import train_opq  # noqa: F401,E402
 from .RVQ import train_rvq  # noqa: F401,E402
+from .ERVQ import quantize_ervq, train_ervq, ervq_update_codebook, last_ervq_timing  # noqa: F401,E402
 from .LSQ import encoding_icm, encode_icm_cuda, veccost, qerror, train_lsq, train_lsq_cuda  # noqa: F401,E402
 from .SR import apply_schedule, SR_C_perturb, SR_D_perturb, train_sr, train_sr_cuda  # noqa: F401,E402
 from .codebook_update import (update_codebooks, update_codebooks_fast_bin, update_codebooks_chain_bin,  # noqa: F401,E402
@@ -32,4 +33,5 @@ __all__ = ["quantize_pq", "quantize_opq", "linscan_pq", "linscan_opq", "linscan_
            "encoding_icm", "encode_icm_cuda", "train_lsq", "train_lsq_cuda", "train_sr", "train_sr_cuda",
            "apply_schedule", "SR_C_perturb", "SR_D_perturb", "update_codebooks",
            "update_codebooks_fast_bin", "quantize_chainq", "train_chainq", "update_codebooks_chain_bin", "get_cbdims_chain",
+           "quantize_ervq", "train_ervq", "ervq_update_codebook", "last_ervq_timing",
            "eval_recall", "splitarray"]

@@ -49,6 +49,9 @@ SIGNATURES = {
     "rq_encode_rvq_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_train_rvq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_uint64]),
     "rq_dev_encode_rvq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "rq_ervq_update_codebook": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_train_ervq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _u64]),
+    "rq_last_ervq_timing": (_i32, [_vp, _i32]),
     "rq_encode_icm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i64, _i32]),
     "rq_dev_encode_icm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i64,
                                  _i32, _vp]),

@@ -1,0 +1,332 @@
+// rq_ervq.hip -- Enhanced RVQ / Stacked Quantizers (src/ERVQ.jl, arXiv 1411.2173): train_ervq, device-resident.
+//
+// The reference (src/ERVQ.jl:51-135) refines m full-dimensional codebooks that train_rvq initialised: for every iteration and
+// every codebook j, in this order,
+//   1. C_j[k] <- mean over the rows with b_j = k of Xd = X - sum_{i != j} C_i[b_i]      (Clustering.update_centers!, :85-90)
+//   2. entries without rows are refilled                                                  (:93-109)
+//   3. B[j:end] = quantize_rvq(X - sum_{i < j} C_i[b_i], C[j:end])                         (:113-118)
+//   4. qerror(X, B, C) is reported                                                        (:120)
+// What runs here is the same loop in another form.  Let E = X - sum_i C_i[b_i], the full residual that step 3 of the previous
+// step leaves as the final residual of its quantize_rvq.  Then Xd = E + C_j[b_j], and the mean of Xd over the rows of entry k is
+//   C_j[k] + mean_{b_j = k}(E):
+// the update is an INCREMENT by the mean residual.  It gathers from no other codebook, and in f32 it lands about ten times closer
+// to an f64 evaluation of the reference's formula than the literal form (sums of small residuals instead of sums of data-sized
+// values; tests/test_ervq_oracle.py measures both).  The segment sum is update_centers' (rq_train.hip: ervq_increment_launch),
+// the stage encode is encode_launch with one sub-quantizer of width d, the error pass qerror_launch on E.
+//
+// Buffers: X (= P_1, the residual entering stage 1), two prefix buffers that alternate as P_j / P_{j+1}, one working buffer that
+// ends every step as E.  Step j encodes stage j on P_j and writes P_{j+1} = P_j - C_j[b_j] OUT OF PLACE into the other prefix
+// buffer, stage j + 1 goes from there into the working buffer, the later stages run in place: no n x d copy per step.
+//
+// Entries without rows, for EVERY j: Clustering.repick_unused_centers' rule (what repick_unused of rq_train_host.hip does for
+// train_pq / train_rvq; same costs, same draws) on P_j, the residual entering stage j -- a row drawn with probability
+// proportional to |P_j[row] - C_j[b_j]|^2 under the entry values the codes were assigned with, costs lowered after each
+// draw, from the library's seeded stream.  The O(n d) parts (the costs, their lowering) run on the device and only the n
+// costs come to the host for the draw: an ERVQ step at h = 256 empties entries routinely, and the host form, which
+// downloads P_j and loops over n d values per draw, took 7 s of a 35 ms iteration at 1e6 x 128.  The reference takes the
+// refill for j >= 2 from quantize_rvq's `singletons` (the same rule with Julia's RNG: other draws) and for j = 1 calls
+// repick_unused_centers through a Julia-0.6 `sum(..., 1)` that does not run on Julia >= 0.7; here j = 1 follows the rule of j >= 2.
+#include <string.h>
+
+#include <utility>
+#include <vector>
+
+#include "rq_internal.h"
+
+namespace rq {
+
+namespace {
+
+// Stage epilogue, out of place: dst[row][:] = src[row][:] - Cj[code][:] with code = codes_in[row * in_stride]; the code goes to
+// codes_out[row * m + stage] (codes_out may be NULL) and counts[code] (may be NULL) is incremented.  dst may be src: every
+// element is read and written by its own thread.  One thread per W floats (W = 4: d % 4 == 0 and 16-byte aligned pointers).
+template <int W>
+__global__ __launch_bounds__(256) void ervq_residual_kernel(float *dst, const float *src, const float *__restrict__ Cj,
+                                                            const uint8_t *codes_in, int in_stride, uint8_t *codes_out,
+                                                            unsigned int *counts, int64_t n, int d, int m, int stage) {
+  const int dw = d / W;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n * dw) return;
+  const int64_t row = e / dw;
+  const int c = (int)(e - row * dw);
+  const int code = codes_in[row * in_stride];
+  if constexpr (W == 4) {
+    float4 x = reinterpret_cast<const float4 *>(src)[e];
+    const float4 v = reinterpret_cast<const float4 *>(Cj)[(size_t)code * dw + c];
+    x.x = x.x - v.x; x.y = x.y - v.y; x.z = x.z - v.z; x.w = x.w - v.w;
+    reinterpret_cast<float4 *>(dst)[e] = x;
+  } else {
+    dst[e] = src[e] - Cj[(size_t)code * d + c];
+  }
+  if (c == 0) {
+    if (codes_out) codes_out[row * m + stage] = (uint8_t)code;
+    if (counts) atomicAdd(&counts[code], 1u);
+  }
+}
+
+int ervq_residual_launch(float *dst, const float *src, const float *Cj, const uint8_t *codes_in, int in_stride,
+                         uint8_t *codes_out, unsigned int *counts, int64_t n, int d, int m, int stage, hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  const bool vec = (d & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)Cj) & 15) == 0;
+  const int64_t blocks = (n * (vec ? d >> 2 : d) + 255) / 256;
+  if (blocks > 0x7fffffffll) return fail(RQ_EUNSUPPORTED, "ervq: n=%lld d=%d is too large", (long long)n, d);
+  if (vec)
+    hipLaunchKernelGGL(ervq_residual_kernel<4>, dim3((uint32_t)blocks), dim3(256), 0, stream, dst, src, Cj, codes_in, in_stride,
+                       codes_out, counts, n, d, m, stage);
+  else
+    hipLaunchKernelGGL(ervq_residual_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, stream, dst, src, Cj, codes_in, in_stride,
+                       codes_out, counts, n, d, m, stage);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
+// one-based Int16 codes -> zero-based bytes (the inverse of widen_codes_launch; the range was checked on the host)
+__global__ __launch_bounds__(256) void ervq_narrow_kernel(uint8_t *codes, const int16_t *B1, size_t nelem) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < nelem) codes[e] = (uint8_t)(B1[e] - 1);
+}
+
+// Costs of the refill, f64, one thread per row, the d terms in ascending order (the host loop of repick_unused bit for bit):
+// BY_CODE: tc[row] = |P[row] - Cref[code(row)]|^2 (Cref [h][d]); else tc[row] = min(tc[row], |P[row] - Cref|^2) (Cref [d]).
+template <bool BY_CODE>
+__global__ __launch_bounds__(256) void ervq_cost_kernel(double *tc, const float *__restrict__ P, const float *__restrict__ Cref,
+                                                        const uint8_t *__restrict__ codes, int cstride, int col, int64_t n, int d) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  const float *x = P + row * d;
+  const float *c = BY_CODE ? Cref + (size_t)codes[row * cstride + col] * d : Cref;
+  double a = 0;
+  for (int t = 0; t < d; ++t) {
+    const double e = (double)x[t] - (double)c[t];
+    a += e * e;
+  }
+  if (BY_CODE) tc[row] = a;
+  else if (a < tc[row]) tc[row] = a;
+}
+
+// Clustering.repick_unused_centers for the `unused` entries of Cj [h][d]: rows of P drawn with probability proportional to
+// their cost under Cold (the entries the codes were assigned with); the drawn row's cost drops to zero and every cost is
+// lowered to the distance to the new entry before the next draw.  dtc: n doubles of device scratch.
+int ervq_refill(float *Cj, const float *Cold, const float *P, const uint8_t *codes, int cstride, int col, int64_t n, int d,
+                const std::vector<int> &unused, Rng &rng, double *dtc, std::vector<double> &tc, hipStream_t stream) {
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  hipLaunchKernelGGL(ervq_cost_kernel<true>, grid, dim3(256), 0, stream, dtc, P, Cold, codes, cstride, col, n, d);
+  RQ_HIP(hipGetLastError());
+  tc.resize((size_t)n);
+  for (size_t q = 0; q < unused.size(); ++q) {
+    RQ_HIP(hipMemcpyAsync(tc.data(), dtc, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
+    RQ_HIP(hipStreamSynchronize(stream));
+    double total = 0;
+    for (int64_t r = 0; r < n; ++r) total += tc[r];
+    int64_t pick = (int64_t)(rng.next() % (uint64_t)n);          // all costs zero (fewer distinct rows than entries): uniform
+    if (total > 0) {
+      const double u = rng.uniform() * total;
+      double run = 0;
+      pick = n - 1;
+      for (int64_t r = 0; r < n; ++r) { run += tc[r]; if (run > u) { pick = r; break; } }
+    }
+    float *v = Cj + (size_t)unused[q] * d;
+    RQ_HIP(hipMemcpyAsync(v, P + pick * d, (size_t)d * 4, hipMemcpyDeviceToDevice, stream));
+    if (q + 1 < unused.size()) {
+      hipLaunchKernelGGL(ervq_cost_kernel<false>, grid, dim3(256), 0, stream, dtc, P, v, codes, cstride, col, n, d);
+      RQ_HIP(hipGetLastError());
+    }
+  }
+  return RQ_OK;
+}
+
+// E = X - sum_i C_i[b_i] by m in-place epilogues in codebook order (the order quantize_rvq subtracts in)
+int ervq_full_residual(float *E, const float *C, const uint8_t *codes, int64_t n, int d, int m, int h, hipStream_t stream) {
+  for (int i = 0; i < m; ++i)
+    RQ_TRY(ervq_residual_launch(E, E, C + (size_t)i * h * d, codes + i, m, nullptr, nullptr, n, d, m, i, stream));
+  return RQ_OK;
+}
+
+int ervq_check_shape(const char *who, int64_t n, int d, int m, int h) {
+  if (m < 1 || m > 64) return fail(RQ_EINVAL, "%s: m=%d outside 1..64", who, m);
+  if (h < 2 || h > 256) return fail(RQ_EINVAL, "%s: h=%d outside 2..256", who, h);
+  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
+  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
+  return RQ_OK;
+}
+
+// Phase clock of rq_train_ervq: hipEvents between the phases of the calling thread's last call, read at its end.
+enum { EV_INIT, EV_INCREMENT, EV_REFILL, EV_ENCODE, EV_EPILOGUE, EV_ERROR, EV_OTHER, EV_N };
+thread_local double g_ervq_ms[EV_N] = {0};
+
+struct ErvqClock {
+  hipStream_t s;
+  bool on = false;
+  std::vector<std::pair<int, hipEvent_t>> marks;   // (phase ending here, event)
+  hipEvent_t first = nullptr;
+  explicit ErvqClock(hipStream_t st) : s(st) {
+    if (hipEventCreate(&first) == hipSuccess) on = hipEventRecord(first, s) == hipSuccess;
+  }
+  void mark(int phase) {
+    if (!on) return;
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return;
+    (void)hipEventRecord(e, s);
+    marks.push_back({phase, e});
+  }
+  void collect() {
+    if (!on) return;
+    (void)hipStreamSynchronize(s);
+    hipEvent_t prev = first;
+    for (auto &pe : marks) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) g_ervq_ms[pe.first] += ms;
+      prev = pe.second;
+    }
+  }
+  ~ErvqClock() {
+    for (auto &pe : marks) (void)hipEventDestroy(pe.second);
+    if (first) (void)hipEventDestroy(first);
+  }
+};
+
+}  // namespace
+
+}  // namespace rq
+
+using namespace rq;
+
+extern "C" int rq_ervq_update_codebook(float *C, uint32_t *counts, const float *X, const uint8_t *codes, int64_t n, int d, int m,
+                                       int h, int j) {
+  RQ_TRY(ervq_check_shape("ervq_update_codebook", n, d, m, h));
+  if (j < 0 || j >= m) return fail(RQ_EINVAL, "ervq_update_codebook: j=%d outside 0..%d", j, m - 1);
+  if (!C || !counts || (n > 0 && (!X || !codes))) return fail(RQ_EINVAL, "ervq_update_codebook: null pointer");
+  for (int64_t e = 0; e < n * m; ++e)
+    if (codes[e] >= h)
+      return fail(RQ_EINVAL, "ervq_update_codebook: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
+                  (long long)(e % m), h);
+  if (n == 0) {
+    memset(counts, 0, (size_t)h * sizeof(uint32_t));
+    return RQ_OK;
+  }
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  const size_t xb = (size_t)n * d * 4, cb = (size_t)m * h * d * 4, jb = (size_t)h * d * 4;
+  DevMem dE, dC, dcodes, dcnt;
+  RQ_TRY(dE.alloc(xb)); RQ_TRY(dC.alloc(cb)); RQ_TRY(dcodes.alloc((size_t)n * m)); RQ_TRY(dcnt.alloc((size_t)h * 4));
+  RQ_HIP(hipMemcpy(dE.p, X, xb, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(dC.p, C, cb, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
+  RQ_TRY(ervq_full_residual(dE.as<float>(), dC.as<float>(), dcodes.as<uint8_t>(), n, d, m, h, nullptr));
+  float *Cj = dC.as<float>() + (size_t)j * h * d;
+  RQ_TRY(ervq_increment_launch(Cj, dcnt.as<unsigned int>(), dE.as<float>(), dcodes.as<uint8_t>(), n, d, m, j, h, di.num_cu,
+                               nullptr));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(C + (size_t)j * h * d, Cj, jb, hipMemcpyDeviceToHost));   // the other blocks are not written
+  RQ_HIP(hipMemcpy(counts, dcnt.p, (size_t)h * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+extern "C" int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, const float *X, int64_t n, int d, int m, int h,
+                             int niter, uint64_t seed) {
+  RQ_TRY(ervq_check_shape("train_ervq", n, d, m, h));
+  if (n < 1) return fail(RQ_EINVAL, "train_ervq: n=%lld < 1", (long long)n);
+  if (niter < 0 || (int64_t)niter * m + 1 > INT32_MAX) return fail(RQ_EINVAL, "train_ervq: niter=%d", niter);
+  if (!C || !B1 || !X) return fail(RQ_EINVAL, "train_ervq: null pointer");
+  for (int64_t e = 0; e < n * m; ++e)
+    if (B1[e] < 1 || B1[e] > h)
+      return fail(RQ_EINVAL, "train_ervq: code %d at [%lld][%lld] is outside 1..h=%d", (int)B1[e], (long long)(e / m),
+                  (long long)(e % m), h);
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  const size_t xb = (size_t)n * d * 4, jb = (size_t)h * d * 4, cb = (size_t)m * jb;
+  const int nobj = niter * m + 1;
+  Rng rng{seed * 0x9E3779B97F4A7C15ull + 4};
+  DevMem dX, dP[2], dW, dC, dCold, dcodes, dstage, dcnt, dobj, d16;
+  RQ_TRY(dX.alloc(xb)); RQ_TRY(dW.alloc(xb)); RQ_TRY(dC.alloc(cb)); RQ_TRY(dCold.alloc(jb));
+  RQ_TRY(dcodes.alloc((size_t)n * m)); RQ_TRY(dstage.alloc((size_t)n)); RQ_TRY(dcnt.alloc((size_t)h * 4));
+  RQ_TRY(dobj.alloc((size_t)nobj * 8)); RQ_TRY(d16.alloc((size_t)n * m * 2));
+  if (niter > 0 && m > 1) { RQ_TRY(dP[0].alloc(xb)); RQ_TRY(dP[1].alloc(xb)); }
+  const hipStream_t s = nullptr;
+  for (int q = 0; q < EV_N; ++q) g_ervq_ms[q] = 0;
+  ErvqClock clk(s);
+  RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(dC.p, C, cb, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(d16.p, B1, (size_t)n * m * 2, hipMemcpyHostToDevice));
+  float *Xd = dX.as<float>(), *W = dW.as<float>(), *Cd = dC.as<float>();
+  uint8_t *codes = dcodes.as<uint8_t>(), *stage = dstage.as<uint8_t>();
+  double *objd = dobj.as<double>();
+  hipLaunchKernelGGL(ervq_narrow_kernel, dim3((uint32_t)(((size_t)n * m + 255) / 256)), dim3(256), 0, s, codes,
+                     d16.as<int16_t>(), (size_t)n * m);
+  RQ_HIP(hipGetLastError());
+  clk.mark(EV_OTHER);
+  // E of the caller's codes and codebooks, and its error
+  RQ_HIP(hipMemcpyAsync(W, Xd, xb, hipMemcpyDeviceToDevice, s));
+  RQ_TRY(ervq_full_residual(W, Cd, codes, n, d, m, h, s));
+  clk.mark(EV_INIT);
+  RQ_TRY(qerror_launch(objd, W, nullptr, n, d, di.num_cu, s));
+  clk.mark(EV_ERROR);
+  std::vector<unsigned int> counts((size_t)h);
+  std::vector<int> unused;
+  DevMem dtc;                 // the refill's costs: allocated when the first entry without rows turns up
+  std::vector<double> tc;
+  for (int it = 0; it < niter; ++it) {
+    const float *P = Xd;          // P_j: the residual entering stage j under the current codes and codebooks
+    for (int j = 0; j < m; ++j) {
+      float *Cj = Cd + (size_t)j * h * d;
+      // 1. the increment (dCold keeps the entries the codes were assigned with: the refill draws with THOSE costs)
+      RQ_HIP(hipMemcpyAsync(dCold.p, Cj, jb, hipMemcpyDeviceToDevice, s));
+      RQ_TRY(ervq_increment_launch(Cj, dcnt.as<unsigned int>(), W, codes, n, d, m, j, h, di.num_cu, s));
+      clk.mark(EV_INCREMENT);
+      // 2. entries without rows
+      RQ_HIP(hipMemcpy(counts.data(), dcnt.p, (size_t)h * 4, hipMemcpyDeviceToHost));
+      unused.clear();
+      for (int k = 0; k < h; ++k)
+        if (counts[k] == 0) unused.push_back(k);
+      if (!unused.empty()) {
+        if (!dtc.p) RQ_TRY(dtc.alloc((size_t)n * 8));
+        RQ_TRY(ervq_refill(Cj, dCold.as<float>(), P, codes, m, j, n, d, unused, rng, dtc.as<double>(), tc, s));
+      }
+      clk.mark(EV_REFILL);
+      // 3. stages j..m-1 again: P_j -> P_{j+1} (kept for the next step) -> the working buffer, then in place
+      float *Pnext = dP[j & 1].as<float>();
+      const float *src = P;
+      for (int i = j; i < m; ++i) {
+        const float *Ci = Cd + (size_t)i * h * d;
+        RQ_TRY(encode_launch(stage, src, Ci, n, d, 1, h, di.num_cu, s));
+        clk.mark(EV_ENCODE);
+        if (i == j && j + 1 < m) {
+          RQ_TRY(ervq_residual_launch(Pnext, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
+          src = Pnext;
+        } else if (src != W) {
+          RQ_TRY(ervq_residual_launch(W, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
+          src = W;
+        } else {
+          RQ_TRY(rvq_residual_launch(W, Ci, stage, codes, nullptr, n, d, m, i, s));
+        }
+        clk.mark(EV_EPILOGUE);
+      }
+      if (j + 1 < m) P = Pnext;
+      // 4. the error of this step
+      RQ_TRY(qerror_launch(objd + 1 + (size_t)it * m + j, W, nullptr, n, d, di.num_cu, s));
+      clk.mark(EV_ERROR);
+    }
+  }
+  RQ_TRY(widen_codes_launch(d16.as<int16_t>(), codes, n * m, s));
+  clk.mark(EV_OTHER);
+  clk.collect();
+  RQ_HIP(hipDeviceSynchronize());
+  std::vector<double> acc((size_t)nobj);
+  RQ_HIP(hipMemcpy(acc.data(), objd, (size_t)nobj * 8, hipMemcpyDeviceToHost));
+  for (double &a : acc) a /= (double)n;
+  if (obj) memcpy(obj, acc.data(), (size_t)nobj * 8);
+  if (error) *error = acc[(size_t)nobj - 1];
+  if (niter > 0) {      // niter = 0 returns the inputs as they are
+    RQ_HIP(hipMemcpy(C, Cd, cb, hipMemcpyDeviceToHost));
+    RQ_HIP(hipMemcpy(B1, d16.p, (size_t)n * m * 2, hipMemcpyDeviceToHost));
+  }
+  return RQ_OK;
+}
+
+extern "C" int rq_last_ervq_timing(double *ms, int cap) {
+  if (!ms) return fail(RQ_EINVAL, "rq_last_ervq_timing: null pointer");
+  for (int q = 0; q < cap && q < EV_N; ++q) ms[q] = g_ervq_ms[q];
+  return RQ_OK;
+}

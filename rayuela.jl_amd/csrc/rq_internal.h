@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <math.h>
+
 #include <algorithm>
 
 #include "../../include/rayuela_hip.h"
@@ -207,6 +209,33 @@ size_t polar_ns_scratch_bytes(int d, int num_cu);
 int polar_ns_launch(float *Rimg, const float *G, int d, int *status, void *scratch, int num_cu, hipStream_t stream);
 int codes_changed_launch(unsigned long long *out, const uint8_t *a, const uint8_t *b, size_t nbytes, hipStream_t stream);
 int gram_launch(float *G, const float *X, const float *CB, int64_t n, int d, int num_cu, hipStream_t stream);
+
+// ---- training loops on host pointers (rq_train_host.hip, rq_ervq.hip) --------------------------------------------------------
+// the library's seeded stream (splitmix64): every draw of a training call comes from one of these
+struct Rng {
+  uint64_t s;
+  uint64_t next() {
+    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+  }
+  double uniform() { return (double)(next() >> 11) / 9007199254740992.0; }
+  double normal() {  // Box-Muller
+    double u1 = uniform(), u2 = uniform();
+    if (u1 < 1e-300) u1 = 1e-300;
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+  }
+};
+struct DevMem {
+  void *p = nullptr;
+  ~DevMem() { if (p) (void)hipFree(p); }
+  int alloc(size_t bytes) { RQ_HIP(hipMalloc(&p, bytes ? bytes : 16)); return RQ_OK; }
+  template <class T> T *as() { return reinterpret_cast<T *>(p); }
+};
+// ---- ERVQ (rq_train.hip: the increment shares update_centers' segment sum; rq_ervq.hip: epilogue and loop) -------------------
+int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
+                          int col, int h, int num_cu, hipStream_t stream);
 
 // ---- LSQ encoding (rq_icm.hip): argument checks, and the device body of rq_dev_encode_icm (codes already in range) -----
 int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t stream, const char *who);   // codes [n][m] < h

@@ -29,6 +29,7 @@ struct TrainParams {
   unsigned int *counts;  // [m][h] out
   int64_t n;
   int d, m, h;
+  int cs, ccol;          // centers_mfma_kernel: sub-quantizer q's code of a row is codes[row * cs + ccol + q]
   int off[33];
 };
 
@@ -146,9 +147,9 @@ __global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nu
   // 408 VALU instructions of a step, and the kernel is bound by VALU + MFMA issue)
   const int64_t nrows = r1 > r0 ? r1 - r0 : 0;
   const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.X + r0 * p.d), 0, (int)(nrows * p.d * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.codes + r0 * p.m), 0, (int)(nrows * p.m), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.codes + r0 * p.cs), 0, (int)(nrows * p.cs), 0x00020000);
   const int xoff = ((8 * kg) * p.d + col0 + (colok ? i : 0)) * 4;
-  const int coff = (8 * kg) * p.m + q;
+  const int coff = (8 * kg) * p.cs + p.ccol + q;
   const uint32_t ones = i == 0 ? 0x3F803F80u : 0u;
   const cm_bf16x8 Bc = __builtin_bit_cast(cm_bf16x8, make_uint4(ones, ones, ones, ones));
   // raw operands of ONE pair of 32-row steps; a step re-loads its half for the next pair as soon as it has turned the values
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nu
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int L = L0 + u;                                         // wave-uniform
-      cr[s][u] = __builtin_amdgcn_raw_buffer_load_b8(rC, coff, L * p.m, 0);
+      cr[s][u] = __builtin_amdgcn_raw_buffer_load_b8(rC, coff, L * p.cs, 0);
       xr[s][u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX, xoff, L * p.d * 4, 0));
     }
   };
@@ -291,6 +292,19 @@ __global__ void centers_finish_kernel(TrainParams p, int nparts) {
   const int sub = p.off[q + 1] - p.off[q];
   if (c > 0) p.C[(size_t)p.h * p.off[q] + (size_t)code * sub + (dim - p.off[q])] = s * (1.0f / (float)c);
   if (dim == p.off[q]) p.counts[q * p.h + code] = c;
+}
+
+// ERVQ (src/ERVQ.jl:85-90): the finishing pass of the codebook INCREMENT.  `red` is one reduced slice of a single full-dimensional
+// sub-quantizer, [h][d] sums of the residual E then [h] counts; entry k moves by the mean residual of its rows,
+// C[k] += sum / count, entries without rows keep their bits, counts [h] is written out.
+__global__ void ervq_increment_finish_kernel(float *__restrict__ C, unsigned int *__restrict__ counts, const float *__restrict__ red,
+                                             int h, int d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= h * d) return;
+  const int code = i / d;
+  const unsigned int c = reinterpret_cast<const unsigned int *>(red + (size_t)h * d)[code];
+  if (c > 0) C[i] = C[i] + red[i] / (float)c;
+  if (i == code * d) counts[code] = c;
 }
 
 // ---- reconstruction ----------------------------------------------------------------------------------
@@ -851,7 +865,7 @@ int update_centers_launch(float *C, unsigned int *counts, const float *X, const 
   if (m < 1 || m > 32 || d < m || h < 1 || h > 256)
     return fail(RQ_EUNSUPPORTED, "update_centers covers m <= 32, h <= 256 (got m=%d d=%d h=%d)", m, d, h);
   TrainParams p{};
-  p.X = X; p.codes = codes; p.C = C; p.counts = counts; p.n = n; p.d = d; p.m = m; p.h = h;
+  p.X = X; p.codes = codes; p.C = C; p.counts = counts; p.n = n; p.d = d; p.m = m; p.h = h; p.cs = m; p.ccol = 0;
   fill_offsets(p.off, d, m);
   const int grid = (int)std::min<int64_t>(num_cu, (n + 1023) / 1024);
   void *part = nullptr;
@@ -880,6 +894,43 @@ int update_centers_launch(float *C, unsigned int *counts, const float *X, const 
     RQ_HIP(hipGetLastError());
   }
   return centers_finish(p, grid, stream);
+}
+
+// Codebook increment of ERVQ: Cj [h][d] += the per-entry mean of E [n][d] over the rows with codes[row * cstride + col] == entry
+// (rq_ervq.hip says why this equals the reference's update); counts [h] out.  The segment sum is the one-hot bf16 x 3 product of
+// update_centers with ONE sub-quantizer of width d, read at a code stride and column of its own: same fixed order, no float
+// atomics.  Any d >= 1, 1 <= h <= 256, any n: the row slices are sized to the kernel's 32-bit offsets and f32 counters.
+int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
+                          int col, int h, int num_cu, hipStream_t stream) {
+  if (d < 1 || h < 1 || h > 256 || cstride < 1 || col < 0 || col >= cstride)
+    return fail(RQ_EINVAL, "ervq increment: d=%d h=%d stride=%d column=%d", d, h, cstride, col);
+  if (n <= 0) {
+    RQ_HIP(hipMemsetAsync(counts, 0, (size_t)h * sizeof(unsigned int), stream));
+    return RQ_OK;
+  }
+  const int64_t cap = std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4));   // rows of one slice
+  if (cap < 64) return fail(RQ_EUNSUPPORTED, "ervq increment: d=%d", d);
+  TrainParams p{};
+  p.X = E; p.codes = codes; p.n = n; p.d = d; p.m = 1; p.h = h; p.cs = cstride; p.ccol = col;
+  p.off[0] = 0; p.off[1] = d;
+  const int grid = (int)std::max<int64_t>(std::min<int64_t>(num_cu, (n + 1023) / 1024), (n + cap - 1) / cap);
+  const size_t stride = (size_t)h * d + (size_t)h;
+  void *part = nullptr;
+  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * stride * sizeof(float), &part, stream));
+  p.partial = (float *)part;
+  const int nunits = (d + 15) / 16;
+  const dim3 g3(grid, (nunits + 7) / 8);
+  if (h <= 64) hipLaunchKernelGGL(centers_mfma_kernel<4>, g3, dim3(512), 0, stream, p, nunits);
+  else if (h <= 128) hipLaunchKernelGGL(centers_mfma_kernel<8>, g3, dim3(512), 0, stream, p, nunits);
+  else hipLaunchKernelGGL(centers_mfma_kernel<16>, g3, dim3(512), 0, stream, p, nunits);
+  RQ_HIP(hipGetLastError());
+  float *red = p.partial + (size_t)grid * stride;
+  RQ_TRY(partials_reduce<float>(red, p.partial, stride, grid, h * d, stream));
+  RQ_TRY(partials_reduce<unsigned int>(reinterpret_cast<unsigned int *>(red + (size_t)h * d),
+                                       reinterpret_cast<const unsigned int *>(p.partial + (size_t)h * d), stride, grid, h, stream));
+  hipLaunchKernelGGL(ervq_increment_finish_kernel, dim3((h * d + 255) / 256), dim3(256), 0, stream, Cj, counts, red, h, d);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
 }
 
 int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h,

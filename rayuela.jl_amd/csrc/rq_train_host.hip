@@ -18,22 +18,6 @@
 
 namespace rq {
 
-struct Rng {
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  }
-  double uniform() { return (double)(next() >> 11) / 9007199254740992.0; }
-  double normal() {  // Box-Muller
-    double u1 = uniform(), u2 = uniform();
-    if (u1 < 1e-300) u1 = 1e-300;
-    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-  }
-};
-
 // h distinct indices out of n (sample(1:n, h, replace=false), src/OPQ.jl:82): partial Fisher-Yates on a
 // sparse map when n is large
 static void sample_distinct(Rng &rng, int64_t n, int h, std::vector<int64_t> &out) {
@@ -169,13 +153,6 @@ struct TrainProf {
   void loop_end(int iters) { (void)hipDeviceSynchronize(); g_train_prof[TP_LOOP] = since(tl); g_train_prof[TP_ITERS] = iters; }
 };
 #define RQ_PH(slot, stmt) do { prof.start(); stmt; prof.stop(slot); } while (0)
-
-struct DevMem {
-  void *p = nullptr;
-  ~DevMem() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { RQ_HIP(hipMalloc(&p, bytes ? bytes : 16)); return RQ_OK; }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
 
 // the device's persistent non-blocking compute stream (the caller holds the DeviceLock) with the two events that order it
 // against the default stream

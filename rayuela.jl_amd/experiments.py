@@ -1,6 +1,7 @@
 """Host mirror of the end-to-end drivers: experiment_pq (src/PQ.jl:104-132), experiment_pq_query_base
 (:137-159), experiment_opq (src/OPQ.jl:142-171), experiment_opq_query_base (:174-197), experiment_rvq
-(src/RVQ.jl:130-175), experiment_sr_cuda (src/SR.jl:247-306, :348-373), experiment_sr_cuda_query_base (:308-344, :376-402).
+(src/RVQ.jl:130-175), experiment_rvq_query_base (:163-188), experiment_ervq and experiment_ervq_query_base
+(src/ERVQ.jl:151-242), experiment_sr_cuda (src/SR.jl:247-306, :348-373), experiment_sr_cuda_query_base (:308-344, :376-402).
 train -> encode the base -> ADC search -> recall, every O(n) step on the device."""
 import numpy as np
 
@@ -90,6 +91,14 @@ def _quantize_norms(B, C, norms_C):
     return order[np.where(left, pos - 1, pos)] + 1, dbnorms
 
 
+def _qerror_aq(X, B, C):
+    """qerror (src/qerrors.jl) of full-dimensional codebooks: mean squared error of the summed reconstruction."""
+    recon = np.zeros(X.shape, dtype=np.float64)
+    for i in range(len(C)):
+        recon += np.asarray(C[i], dtype=np.float64)[B[:, i].astype(np.int64) - 1]
+    return float(((X.astype(np.float64) - recon) ** 2).sum() / X.shape[0])
+
+
 def experiment_rvq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     """experiment_rvq (src/RVQ.jl:130-175): train_rvq -> norms codebook -> quantize_rvq of the base ->
     quantised database norms -> linscan_lsq -> eval_recall."""
@@ -104,6 +113,91 @@ def experiment_rvq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
+
+
+def experiment_rvq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
+    """experiment_rvq_query_base (src/RVQ.jl:163-188): train_rvq -> norms codebook -> linscan_lsq over the training codes
+    -> eval_recall."""
+    from .RVQ import train_rvq
+    from .Linscan import linscan_lsq
+    d = Xt.shape[1]
+    C, B, train_error = train_rvq(Xt, m, h, niter, V, seed=seed)
+    norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
+    db_norms = norms_C[norms_B - 1].astype(np.float32)
+    dists, idx = linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    recall = eval_recall(gt, idx, knn, verbose=V)
+    return C, B, train_error, recall
+
+
+def experiment_ervq(Xt, *args, V=False, seed=0):
+    """experiment_ervq(Xt, B, C, Xb, Xq, gt, m, h, niter=25, knn=1000, V=false)         (src/ERVQ.jl:151-184)
+    experiment_ervq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=false)                (src/ERVQ.jl:214-227)
+
+    train_ervq -> norms codebook -> quantize_ervq of the base -> quantised database norms -> linscan_lsq -> eval_recall.
+    The second method starts from train_rvq(Xt, m, h, niter, V).  Returns C, B, train_error, B_base, recall."""
+    from .ERVQ import train_ervq, quantize_ervq
+    from .RVQ import train_rvq
+    from .Linscan import linscan_lsq
+    if len(args) >= 7 and np.ndim(args[5]) == 0 and np.ndim(args[6]) == 0 and np.ndim(args[3]) > 0:
+        B, C, Xb, Xq, gt, m, h = args[:7]
+        rest = list(args[7:])
+    elif len(args) >= 5:
+        Xb, Xq, gt, m, h = args[:5]
+        rest = list(args[5:])
+        B = None
+    else:
+        raise TypeError("experiment_ervq(Xt, [B, C,] Xb, Xq, gt, m, h, niter=25, knn=1000, V=false)")
+    niter = int(rest.pop(0)) if rest else 25
+    knn = int(rest.pop(0)) if rest else 1000
+    V = bool(rest.pop(0)) if rest else V
+    if rest:
+        raise TypeError("experiment_ervq: too many arguments")
+    if B is None:
+        C, B, _ = train_rvq(Xt, m, h, niter, V, seed=seed)
+    d = Xt.shape[1]
+    C, B, train_error = train_ervq(Xt, B, C, m, h, niter, V, seed=seed)
+    _, norms_C = _norms_codebook(B, C, h, seed=seed)
+    B_base, _ = quantize_ervq(Xb, C, V)
+    if V:
+        print("Error in base is %e" % _qerror_aq(Xb, B_base, C))
+    B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
+    db_norms = norms_C[B_base_norms - 1].astype(np.float32)
+    dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    recall = eval_recall(gt, idx, knn, verbose=V)
+    return C, B, train_error, B_base, recall
+
+
+def experiment_ervq_query_base(Xt, *args, V=False, seed=0):
+    """experiment_ervq_query_base(Xt, B, C, Xq, gt, m, h, niter=25, knn=1000, V=false)  (src/ERVQ.jl:187-211)
+    experiment_ervq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=false)         (src/ERVQ.jl:230-242)
+
+    train_ervq -> norms codebook -> linscan_lsq over the training codes -> eval_recall.  Returns C, B, train_error, recall."""
+    from .ERVQ import train_ervq
+    from .RVQ import train_rvq
+    from .Linscan import linscan_lsq
+    if len(args) >= 6 and np.ndim(args[4]) == 0 and np.ndim(args[5]) == 0 and np.ndim(args[2]) > 0:
+        B, C, Xq, gt, m, h = args[:6]
+        rest = list(args[6:])
+    elif len(args) >= 4:
+        Xq, gt, m, h = args[:4]
+        rest = list(args[4:])
+        B = None
+    else:
+        raise TypeError("experiment_ervq_query_base(Xt, [B, C,] Xq, gt, m, h, niter=25, knn=1000, V=false)")
+    niter = int(rest.pop(0)) if rest else 25
+    knn = int(rest.pop(0)) if rest else 1000
+    V = bool(rest.pop(0)) if rest else V
+    if rest:
+        raise TypeError("experiment_ervq_query_base: too many arguments")
+    if B is None:
+        C, B, _ = train_rvq(Xt, m, h, niter, V, seed=seed)
+    d = Xt.shape[1]
+    C, B, train_error = train_ervq(Xt, B, C, m, h, niter, V, seed=seed)
+    norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
+    db_norms = norms_C[norms_B - 1].astype(np.float32)
+    dists, idx = linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    recall = eval_recall(gt, idx, knn, verbose=V)
+    return C, B, train_error, recall
 
 
 def _sr_init(Xt, m, h, niter_init, chain, V, seed):

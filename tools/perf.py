@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Quick kernel timings on resident synthetic data (development aid; bench.py is the contract).
-usage: python tools/perf.py [scan] [encode] [rotate] [--n 1000000] [--nq 10000] [--m 8] [--ks 1,100,1000]"""
+usage: python tools/perf.py [scan] [aq] [encode] [rotate] [train] [ervq] [--n 1000000] [--nq 10000] [--m 8] [--ks 1,100,1000]"""
 import argparse
 import os
 import sys
@@ -34,6 +34,8 @@ ap.add_argument("--m", type=int, default=8)
 ap.add_argument("--d", type=int, default=128)
 ap.add_argument("--ks", default="1,100,1000")
 ap.add_argument("--iters", type=int, default=5)
+ap.add_argument("--rvq-niter", type=int, default=3, help="ervq: k-means iterations per stage of the train_rvq start")
+ap.add_argument("--composed", action="store_true", help="ervq: also time two steps composed from the host-pointer calls")
 a = ap.parse_args()
 dev = "cuda"
 g = torch.Generator(device=dev).manual_seed(1)
@@ -94,3 +96,53 @@ if "train" in a.what:
     t0 = time.perf_counter()
     U, S, Vt = np.linalg.svd(rqd.gram(X, CB).cpu().numpy().astype(np.float64))
     print("train  host SVD %dx%d      %8.3f ms" % (d, d, (time.perf_counter() - t0) * 1e3))
+
+if "ervq" in a.what:   # one train_ervq iteration at (n, d, m), h = 256: the phases, and the same loop from the host-pointer calls
+    import time
+    import numpy as np
+    from rayuela_jl_amd import synth
+    from rayuela_jl_amd.ERVQ import train_ervq_i16, last_ervq_timing
+    h = 256
+    X = synth.sift_like(n, d, seed=1)
+    C0, B0, _ = rq.train_rvq(X, m, h, a.rvq_niter, seed=2)
+    C0 = np.stack(C0)
+    empty0 = sum(int((np.bincount(B0[:, i] - 1, minlength=h) == 0).sum()) for i in range(m))
+    train_ervq_i16(X, B0, C0, m, h, 1)                                   # warm-up: scratch, code objects
+    t0 = time.perf_counter()
+    Cn, Bn, err, obj = train_ervq_i16(X, B0, C0, m, h, 1)
+    wall = (time.perf_counter() - t0) * 1e3
+    ph = last_ervq_timing()
+    dev_ms = sum(v for k, v in ph.items() if k not in ("other_ms", "init_ms"))
+    print("ervq   n=%d d=%d m=%d h=%d: one iteration %8.3f ms on the device (%d stage encodes), call %8.1f ms with transfers"
+          % (n, d, m, h, dev_ms, m * (m + 1) // 2, wall))
+    print("       " + "  ".join("%s=%.3f" % (k, v) for k, v in ph.items()))
+    print("       increment alone %8.3f ms (of %d);  error %.4f -> %.4f;  entries without rows in the start codes: %d"
+          % (ph["increment_ms"] / m, m, obj[0], obj[-1], empty0))
+    Xd = torch.from_numpy(X).cuda()
+    pq_codes = rqd.synth_codes(n, m, seed=3)
+    Cpq = torch.zeros(h * d, device=dev)
+    print("       update_centers (PQ, m=%d) at the same n x d %8.3f ms" % (m, bench(lambda: rqd.update_centers(Cpq, Xd, pq_codes, m, h), a.iters)))
+    del Xd
+    # the loop of the parent commit: class means on the host, rq_encode_rvq on host pointers per step (two steps are timed)
+    codes, C = (B0 - 1).astype(np.uint8), C0.copy()
+    P = X.copy()
+    enc_ms, upd_ms, steps = 0.0, 0.0, min(m, 2) if a.composed else 0
+    for j in range(steps):
+        t0 = time.perf_counter()
+        E = X.copy()
+        for i in range(m):
+            if i != j:
+                E -= C[i][codes[:, i]]
+        order = np.argsort(codes[:, j], kind="stable")
+        cnt = np.bincount(codes[:, j], minlength=h)
+        used = np.flatnonzero(cnt)
+        starts = np.concatenate(([0], np.cumsum(cnt)))[used]
+        C[j][used] = np.add.reduceat(E[order], starts, axis=0) / cnt[used, None]
+        upd_ms += (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        codes[:, j:] = rq.quantize_rvq_u8(P, [C[i] for i in range(j, m)])
+        enc_ms += (time.perf_counter() - t0) * 1e3
+        P -= C[j][codes[:, j]]
+    if steps:
+        print("       composed from host-pointer calls, steps 0..%d: host update %8.1f ms + rq_encode_rvq %8.1f ms per step"
+              % (steps - 1, upd_ms / steps, enc_ms / steps))
