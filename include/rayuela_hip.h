@@ -88,11 +88,48 @@ rq_lsq_index *rq_lsq_prepare(const uint8_t *codes, const float *codebooks, const
 int rq_lsq_search(rq_lsq_index *ix, float *dists, uint32_t *ids, const float *queries, const float *R, int64_t nq,
                   int k, int id_base);
 void rq_lsq_release(rq_lsq_index *ix);
+/* The same handle from a norms codebook instead of per-row norms (the search leg of src/LSQ_GPU.jl:357-362, src/RVQ.jl:150-158:
+ * quantize_norms, then db_norms = norms_C[B_base_norms]): dbnorms[i] = cbnorms[quantize(|sum_k C_k[b_ik]|^2)] is computed on the
+ * device from the uploaded codes and codebooks, with the arithmetic of rq_aq_norms and rq_dev_quantize_norms below, so a base is
+ * searched from codes, codebooks and a table of hn <= 256 floats alone.  Equals rq_lsq_prepare given those dbnorms, bit for bit;
+ * rq_lsq_search and rq_lsq_release are unchanged.  NULL (message in rq_last_error) on a bad argument. */
+rq_lsq_index *rq_lsq_prepare_cbnorms(const uint8_t *codes, const float *codebooks, const float *cbnorms, int hn, int64_t n,
+                                     int m, int h, int d);
 /* device-pointer form; lut_mode 1 = LSQ (dbnorms required), 2 = CQ */
 int rq_dev_linscan_aq(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *codes,
                       const float *codebooks, const float *queries, const float *dbnorms, int64_t n,
                       int64_t nq, int m, int d, int k, int lut_mode, uint32_t id_offset, int id_base,
                       void *stream);
+
+/* ---- database norms of additive-quantizer search: get_norms_codebook (src/utils.jl:4-26) and quantize_norms (:29-59).  Contract
+ * in DESIGN.md section 4.14.  codes [n][m] uint8 zero-based, C [m][h][d] (m full-dimensional codebooks back to back), 1 <= m <= 64,
+ * 2 <= h <= 256, d >= 1, 1 <= hn <= 256; n >= 0, and n >= hn for rq_get_norms_codebook.  Every argument (each code being below
+ * h included) is checked before any work, errors go through rq_last_error and leave the outputs untouched.  Non-finite
+ * codebook entries, norms or cbnorms give unspecified results, as for rq_train_rvq.
+ *
+ * rq_aq_norms (src/utils.jl:15-16, :34-48: reconstruct, then sum(CB.^2)): norms[i] = |sum_k C_k[b_ik]|^2 without the n x d
+ * reconstruction, in veccost's order of f32 sums: CB[t] by adds from +0 in codebook order, 64 partial sums of CB[t]^2 over
+ * t = l, l + 64, ... (multiply and add unfused), added by the xor butterfly 32, 16, 8, 4, 2, 1 -- the veccost of an all-zero X
+ * (rq_encode_icm with no iterations), bit for bit. */
+int rq_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h);
+int rq_dev_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream);
+/* quantize_norms (src/utils.jl:29-59): norm_codes[i] = the FIRST index j (zero-based) that minimises fl(fl(norm - cbnorms[j])^2)
+ * in f32 -- one subtract, one multiply, strict < like findmin (:50-55); cbnorms [hn] need not be sorted.  norms_out [n] (may be
+ * NULL) = the norms themselves, equal to rq_aq_norms (the reference's second return value). */
+int rq_quantize_norms(uint8_t *norm_codes, float *norms_out, const uint8_t *codes, const float *C, const float *cbnorms,
+                      int64_t n, int d, int m, int h, int hn);
+/* device-pointer form on norms already computed; dbnorms_out [n] (may be NULL) = cbnorms[norm_codes[i]], what linscan_lsq takes */
+int rq_dev_quantize_norms(uint8_t *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n, int hn,
+                          void *stream);
+/* get_norms_codebook (src/utils.jl:4-26): Clustering.kmeans(dbnorms, hn) as the Lloyd loop of rq_train_pq with d = m = 1 on
+ * the norms of rq_aq_norms, which stay on the device: cbnorms [hn] and the final assignments equal rq_train_pq(d = 1, m = 1,
+ * h = hn) on those norms with the same niter and seed, bit for bit (and the call overwrites rq_train_profile likewise).
+ * norm_codes [n] zero-based = the k-means' final assignments, like the reference's dbnormsq.assignments.  They come from the
+ * encoder's distance form (|c|^2 - 2 c x, first index on ties), so for a norm near the edge of two cells they can differ from
+ * rq_quantize_norms' (norm - c)^2 on the same codebook; a base searched with quantised norms should take rq_quantize_norms'.
+ * norms_out [n] may be NULL. */
+int rq_get_norms_codebook(uint8_t *norm_codes, float *cbnorms, float *norms_out, const uint8_t *codes, const float *C,
+                          int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed);
 
 /* ---- quantize_rvq (src/RVQ.jl:18-66) -----------------------------------------
  * m full-dimensional stages on the running residual: stage i = pairwise SqEuclidean + first-index

@@ -19,6 +19,7 @@ import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
 export quantize_ervq, train_ervq
+export get_norms_codebook, quantize_norms
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
@@ -294,6 +295,45 @@ function search(ix::HipLsqIndex, X::Matrix{Cfloat}, R::Matrix{Cfloat}, k::Int=10
     ix.handle, dists, res, X, R, Int64(nq), Cint(k), Cint(1)))
   return dists, res
 end
+
+"""
+    get_norms_codebook(B, C; niter=100, seed=0) -> norms_codes, norms_codebook     (src/utils.jl:4-26)
+The norms of the reconstructions, computed on the device and clustered there by a 1-D k-means with h centres
+(rq_get_norms_codebook); `norms_codes` are the k-means' final assignments, one-based.  `niter` = 100 is Clustering's default
+`maxiter` as recalled; `seed` feeds the library's stream where the reference draws from Julia's global RNG.
+"""
+function get_norms_codebook(B::Matrix{UInt8}, C::Vector{Matrix{Cfloat}}; niter::Integer=100, seed::Integer=0)
+  m, n = size(B)
+  d, h = size(C[1])
+  hn = h
+  norm_codes = Vector{UInt8}(undef, n)
+  cbnorms    = Vector{Cfloat}(undef, hn)
+  _check(ccall((:rq_get_norms_codebook, librayuela_hip), Cint,
+    (Ptr{Cuchar}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cuchar}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, UInt64),
+    norm_codes, cbnorms, C_NULL, B, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(hn), Cint(niter), UInt64(seed)))
+  return convert(Vector{Int}, norm_codes) .+ 1, cbnorms
+end
+get_norms_codebook(B::Matrix{T}, C::Vector{Matrix{Cfloat}}; niter::Integer=100, seed::Integer=0) where T <: Integer =
+  get_norms_codebook(convert(Matrix{UInt8}, B .- 1), C; niter=niter, seed=seed)
+
+"""
+    quantize_norms(B, C, cbnorms) -> dbnormsB, dbnormsX     (src/utils.jl:29-59)
+For every column of B the first entry of `cbnorms` nearest to the norm of its reconstruction ((norm - c)^2 in Float32,
+findmin's tie rule), one-based, and the norms themselves (rq_quantize_norms).
+"""
+function quantize_norms(B::Matrix{UInt8}, C::Vector{Matrix{Cfloat}}, cbnorms::Vector{Cfloat})
+  m, n = size(B)
+  d, h = size(C[1])
+  hn = length(cbnorms)
+  norm_codes = Vector{UInt8}(undef, n)
+  dbnormsX   = Vector{Cfloat}(undef, n)
+  _check(ccall((:rq_quantize_norms, librayuela_hip), Cint,
+    (Ptr{Cuchar}, Ptr{Cfloat}, Ptr{Cuchar}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+    norm_codes, dbnormsX, B, hcat(C...), cbnorms, Int64(n), Cint(d), Cint(m), Cint(h), Cint(hn)))
+  return convert(Vector{Int16}, norm_codes) .+ Int16(1), dbnormsX
+end
+quantize_norms(B::Matrix{T}, C::Vector{Matrix{Cfloat}}, cbnorms::Vector{Cfloat}) where T <: Integer =
+  quantize_norms(convert(Matrix{UInt8}, B .- 1), C, cbnorms)
 
 """
     linscan_cq(B, X, C, k=10000) -> dists, idx     (src/Linscan.jl:160-193)

@@ -115,6 +115,23 @@ class LsqIndex:
         if not self._h:
             raise _lib.RayuelaHipError("rq_lsq_prepare: " + _lib.lib().rq_last_error().decode("utf-8", "replace"))
 
+    @classmethod
+    def from_cbnorms(cls, B, C, cbnorms):
+        """The same handle from a norms codebook (rq_lsq_prepare_cbnorms): dbnorms = cbnorms[quantize_norms(B, C, cbnorms)] is
+        computed on the device, so no per-row array is built on the host or uploaded.  search() returns exactly what
+        LsqIndex(B, C, cbnorms[quantize_norms(B, C, cbnorms)[0] - 1]) returns."""
+        Bu = _codes_u8(B)
+        n, m = Bu.shape
+        d = np.asarray(C[0]).shape[1]
+        cb = _hcat(C, m, d)
+        cbn = np.ascontiguousarray(_as_f32(cbnorms, "cbnorms").reshape(-1))
+        self = cls.__new__(cls)
+        self.n, self.m, self.d = n, m, d
+        self._h = _lib.lib().rq_lsq_prepare_cbnorms(Bu.ctypes.data, cb.ctypes.data, cbn.ctypes.data, cbn.shape[0], n, m, 256, d)
+        if not self._h:
+            raise _lib.RayuelaHipError("rq_lsq_prepare_cbnorms: " + _lib.lib().rq_last_error().decode("utf-8", "replace"))
+        return self
+
     def search(self, X, R=None, k=10000):
         X = _as_f32(X, "X")
         nq, d = X.shape
@@ -139,6 +156,13 @@ class LsqIndex:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def linscan_lsq_cbnorms(B, X, C, cbnorms, R, k=10000):
+    """linscan_lsq with the database norms given as a norms codebook: the search leg of the experiment_* drivers
+    (quantize_norms, db_norms = norms_C[B_base_norms], linscan_lsq; src/LSQ_GPU.jl:357-362) with the norms leg on the device."""
+    with LsqIndex.from_cbnorms(B, C, cbnorms) as ix:
+        return ix.search(X, R, k)
 
 
 def linscan_cq(B, X, C, k=10000):

@@ -6,7 +6,7 @@ the C ABI of librayuela_hip.so (include/rayuela_hip.h).  The Julia drop-in files
 ABI with `ccall` live in julia/.  No CPU fallback exists: without the HIP library every call raises.
 """
 from ._lib import RayuelaHipError, lib, lib_path, set_tuning, reset_tuning, last_timing  # noqa: F401
-from .utils import splitarray, cat_codebooks  # noqa: F401
+from .utils import splitarray, cat_codebooks, get_norms_codebook, quantize_norms, aq_norms  # noqa: F401
 from .xvecs import fvecs_read, ivecs_read, bvecs_read, fvecs_write, ivecs_write  # noqa: F401
 from .PQ import quantize_pq, quantize_pq_u8  # noqa: F401
 from .OPQ import quantize_opq, rotate  # noqa: F401
@@ -23,7 +23,7 @@ from .codebook_update import (update_codebooks, update_codebooks_fast_bin, updat
                               get_cbdims_chain)
 from .ChainQ import quantize_chainq, train_chainq  # noqa: F401,E402
 from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_aqd_query, LsqIndex,  # noqa: F401
-                      linscan_aqd_query_extra_byte, eval_recall)
+                      linscan_aqd_query_extra_byte, eval_recall, linscan_lsq_cbnorms)
 
 from .index import Index, Dataset  # noqa: F401,E402
 from . import h5results  # noqa: F401,E402  (libhdf5 is looked up lazily, on first use)
@@ -34,4 +34,4 @@ __all__ = ["quantize_pq", "quantize_opq", "linscan_pq", "linscan_opq", "linscan_
            "apply_schedule", "SR_C_perturb", "SR_D_perturb", "update_codebooks",
            "update_codebooks_fast_bin", "quantize_chainq", "train_chainq", "update_codebooks_chain_bin", "get_cbdims_chain",
            "quantize_ervq", "train_ervq", "ervq_update_codebook", "last_ervq_timing",
-           "eval_recall", "splitarray"]
+           "eval_recall", "splitarray", "get_norms_codebook", "quantize_norms"]

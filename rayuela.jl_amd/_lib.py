@@ -38,6 +38,12 @@ SIGNATURES = {
     "rq_lsq_prepare": (_vp, [_vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_lsq_search": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32]),
     "rq_lsq_release": (None, [_vp]),
+    "rq_lsq_prepare_cbnorms": (_vp, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32]),
+    "rq_aq_norms": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_dev_aq_norms": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_quantize_norms": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_dev_quantize_norms": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "rq_get_norms_codebook": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _u64]),
     "rq_dev_linscan_aq": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _u32, _i32, _vp]),
     "rq_linscan_pq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32]),
     "rq_linscan_opq": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32]),

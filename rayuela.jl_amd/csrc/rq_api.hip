@@ -1105,9 +1105,10 @@ static void lsq_free(rq_lsq_index_impl *ix) {
   delete ix;
 }
 
-rq_lsq_index *rq_lsq_prepare(const uint8_t *codes, const float *codebooks, const float *dbnorms, int64_t n, int m, int h,
-                             int d) {
-  if (!codes || !codebooks || !dbnorms) { fail(RQ_EINVAL, "rq_lsq_prepare: NULL argument"); return nullptr; }
+// dbnorms given (rq_lsq_prepare), or cbnorms [hn]: dbnorms = cbnorms[quantize_norms(|sum_k C_k[b_k]|^2)] computed on the device
+// from the uploaded codes and codebooks (rq_lsq_prepare_cbnorms; arguments checked by the caller)
+static rq_lsq_index *lsq_prepare(const uint8_t *codes, const float *codebooks, const float *dbnorms, const float *cbnorms, int hn,
+                                 int64_t n, int m, int h, int d) {
   if (h != 256) { fail(RQ_EUNSUPPORTED, "the scan kernels cover h = 256 (uint8 codes); got h=%d", h); return nullptr; }
   if (n < 1 || n >= (1LL << 31) || m < 1 || d < 1) { fail(RQ_EINVAL, "rq_lsq_prepare: bad shape n=%lld m=%d d=%d", (long long)n, m, d); return nullptr; }
   const int mp = scan_padded_m(m);
@@ -1128,15 +1129,26 @@ rq_lsq_index *rq_lsq_prepare(const uint8_t *codes, const float *codebooks, const
     RQ_HIP(hipMalloc((void **)&ix->cb, (size_t)m * 256 * d * 4));
     RQ_HIP(hipMalloc((void **)&ix->norms, (size_t)n * 4));
     RQ_HIP(hipMemcpy(ix->cb, codebooks, (size_t)m * 256 * d * 4, hipMemcpyHostToDevice));
-    RQ_HIP(hipMemcpy(ix->norms, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (mp == m) {
-      RQ_HIP(hipMemcpy(ix->codes, codes, (size_t)n * m, hipMemcpyHostToDevice));
-    } else {
+    if (dbnorms) RQ_HIP(hipMemcpy(ix->norms, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
+    {
       DevBuf raw;
-      RQ_TRY(raw.alloc((size_t)n * m));
-      RQ_HIP(hipMemcpy(raw.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
-      RQ_TRY(pad_codes_launch(ix->codes, raw.as<uint8_t>(), n, m, mp, nullptr));
-      RQ_HIP(hipDeviceSynchronize());
+      const uint8_t *rawc = ix->codes;      // the [n][m] rows as uploaded
+      if (mp == m) {
+        RQ_HIP(hipMemcpy(ix->codes, codes, (size_t)n * m, hipMemcpyHostToDevice));
+      } else {
+        RQ_TRY(raw.alloc((size_t)n * m));
+        RQ_HIP(hipMemcpy(raw.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
+        RQ_TRY(pad_codes_launch(ix->codes, raw.as<uint8_t>(), n, m, mp, nullptr));
+        rawc = raw.as<uint8_t>();
+      }
+      if (!dbnorms) {
+        DevBuf dcbn, dsq;
+        RQ_TRY(dcbn.alloc((size_t)hn * 4)); RQ_TRY(dsq.alloc((size_t)n * 4));
+        RQ_HIP(hipMemcpy(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
+        RQ_TRY(aq_norms_launch(dsq.as<float>(), rawc, ix->cb, n, d, m, 256, nullptr));
+        RQ_TRY(quantize_norms_launch(nullptr, ix->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, nullptr));
+      }
+      RQ_HIP(hipDeviceSynchronize());       // before the scratch of this block goes back
     }
     // the base is resident: bank-aware row order once (rq_order.hip), norms permuted alike -- row_bias and the filter's
     // norm bytes are indexed by POSITION in the kernel, ids come from perm
@@ -1173,6 +1185,19 @@ rq_lsq_index *rq_lsq_prepare(const uint8_t *codes, const float *codebooks, const
   };
   if (body() != RQ_OK) { lsq_free(ix); return nullptr; }
   return reinterpret_cast<rq_lsq_index *>(ix);
+}
+
+rq_lsq_index *rq_lsq_prepare(const uint8_t *codes, const float *codebooks, const float *dbnorms, int64_t n, int m, int h,
+                             int d) {
+  if (!codes || !codebooks || !dbnorms) { fail(RQ_EINVAL, "rq_lsq_prepare: NULL argument"); return nullptr; }
+  return lsq_prepare(codes, codebooks, dbnorms, nullptr, 0, n, m, h, d);
+}
+
+rq_lsq_index *rq_lsq_prepare_cbnorms(const uint8_t *codes, const float *codebooks, const float *cbnorms, int hn, int64_t n,
+                                     int m, int h, int d) {
+  if (!codes || !codebooks || !cbnorms) { fail(RQ_EINVAL, "rq_lsq_prepare_cbnorms: NULL argument"); return nullptr; }
+  if (hn < 1 || hn > 256) { fail(RQ_EINVAL, "rq_lsq_prepare_cbnorms: hn=%d outside 1..256", hn); return nullptr; }
+  return lsq_prepare(codes, codebooks, nullptr, cbnorms, hn, n, m, h, d);
 }
 
 void rq_lsq_release(rq_lsq_index *handle) { lsq_free(reinterpret_cast<rq_lsq_index_impl *>(handle)); }

@@ -233,6 +233,14 @@ struct DevMem {
   int alloc(size_t bytes) { RQ_HIP(hipMalloc(&p, bytes ? bytes : 16)); return RQ_OK; }
   template <class T> T *as() { return reinterpret_cast<T *>(p); }
 };
+// the Lloyd loop of rq_train_pq on a device-resident X [n][d] (rq_train_host.hip): dC [h * d] and dcodes [n][m] (device) out;
+// the caller holds the DeviceLock.  Overwrites the calling thread's rq_train_profile like rq_train_pq.
+int train_pq_resident(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed);
+// ---- database norms of additive-quantizer search (rq_norms.hip) -------------------------------------
+int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
+// norm_codes [n] u8 and / or dbnorms [n] = cbnorms[code] (either may be null); cbnorms [hn <= 256], unsorted
+int quantize_norms_launch(uint8_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
+                          hipStream_t stream);
 // ---- ERVQ (rq_train.hip: the increment shares update_centers' segment sum; rq_ervq.hip: epilogue and loop) -------------------
 int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
                           int col, int h, int num_cu, hipStream_t stream);

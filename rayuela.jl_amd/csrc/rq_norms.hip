@@ -1,0 +1,232 @@
+// rq_norms.hip -- the database norms of additive-quantizer search (src/utils.jl:4-26 get_norms_codebook, :29-59
+// quantize_norms) on gfx950; contract in DESIGN.md section 4.14.
+//
+//   aq_norms_kernel       norms[i] = |sum_k C_k[b_ik]|^2 straight from codes and codebooks: one wavefront per row, NR rows in
+//                         flight per wavefront, the n x d reconstruction is never written.  The order of the f32 sums is
+//                         veccost's (rq_icm.hip icm_cost): CB[t] by adds from +0 in codebook order, lane l sums CB[t]^2 over
+//                         t = l, l + 64, ... from +0 (multiply and add unfused: -ffp-contract=off), the xor butterfly
+//                         32, 16, 8, 4, 2, 1 adds the 64 partial sums.  So norms == veccost of an all-zero X, bit for bit.
+//   quantize_norms_kernel first index j minimising fl(fl(norm - cb[j])^2) (strict <: findmin, src/utils.jl:50-55), the
+//                         unsorted codebook of hn <= 256 entries in LDS; optionally the dequantised cb[j] beside the code.
+// The 1-D k-means of get_norms_codebook is train_pq_resident (rq_train_host.hip) with d = m = 1 on the resident norms.
+#include "rq_internal.h"
+
+#include <vector>
+
+namespace rq {
+
+namespace {
+
+constexpr int NR = 4, NI = 4;   // rows per wavefront and codebooks per step: NR * NI independent gathers hide the L2 latency
+
+__global__ __launch_bounds__(256) void aq_norms_kernel(float *norms, const uint8_t *codes, const float *C, int64_t n, int d,
+                                                       int m, int h) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
+  if (row0 >= n) return;
+  // lane i holds the codebook row (i * h + b_i < m * h <= 2^14) of each of the wavefront's rows (m <= 64), lanes past m row 0;
+  // a row past n repeats row n - 1 and is not stored
+  int ent[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    const int64_t row = std::min<int64_t>(row0 + r, n - 1);
+    const int b = (int)codes[row * m + std::min(lane, m - 1)];
+    ent[r] = lane < m ? lane * h + b : 0;
+  }
+  float acc[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) acc[r] = 0.0f;
+  for (int t0 = 0; t0 < d; t0 += 64) {            // uniform trip count: the readlanes below are wavefront-uniform
+    const int t = t0 + lane, tc = std::min(t, d - 1);      // every gather reads inside the table; `in` selects
+    const bool in = t < d;
+    float cb[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) cb[r] = 0.0f;
+    for (int i0 = 0; i0 < m; i0 += NI) {          // NI * NR gathers issued before the first add needs one
+      float v[NI][NR];
+#pragma unroll
+      for (int u = 0; u < NI; ++u) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const float *p = C + (size_t)__builtin_amdgcn_readlane(ent[r], (i0 + u) & 63) * d;
+          const float g = p[tc];
+          v[u][r] = in ? g : 0.0f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < NI; ++u) {
+        if (i0 + u < m) {
+#pragma unroll
+          for (int r = 0; r < NR; ++r) cb[r] = cb[r] + v[u][r];
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = acc[r] + cb[r] * cb[r];
+  }
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc[r] = acc[r] + __shfl_xor(acc[r], o, 64);
+  }
+#pragma unroll
+  for (int r = 0; r < NR; ++r)
+    if (lane == r && row0 + r < n) norms[row0 + r] = acc[r];
+}
+
+__global__ __launch_bounds__(256) void quantize_norms_kernel(uint8_t *norm_codes, float *dbnorms, const float *norms,
+                                                             const float *cbnorms, int64_t n, int hn) {
+  __shared__ float cb[256];
+  if ((int)threadIdx.x < hn) cb[threadIdx.x] = cbnorms[threadIdx.x];
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float v = norms[i];
+    float df = v - cb[0];
+    float best = df * df;
+    int bj = 0;
+    for (int j = 1; j < hn; ++j) {
+      df = v - cb[j];
+      const float e = df * df;
+      if (e < best) { best = e; bj = j; }
+    }
+    if (norm_codes) norm_codes[i] = (uint8_t)bj;
+    if (dbnorms) dbnorms[i] = cb[bj];
+  }
+}
+
+int norms_check_shape(const char *who, int64_t n, int d, int m, int h) {
+  if (m < 1 || m > 64) return fail(RQ_EINVAL, "%s: m=%d outside 1..64", who, m);
+  if (h < 2 || h > 256) return fail(RQ_EINVAL, "%s: h=%d outside 2..256", who, h);
+  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
+  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
+  return RQ_OK;
+}
+
+int norms_check_hn(const char *who, int hn) {
+  if (hn < 1 || hn > 256) return fail(RQ_EINVAL, "%s: hn=%d outside 1..256", who, hn);
+  return RQ_OK;
+}
+
+int norms_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *who) {
+  if (h >= 256) return RQ_OK;
+  for (int64_t i = 0; i < n * m; ++i)
+    if (codes[i] >= h)
+      return fail(RQ_EINVAL, "%s: code %d at [%lld][%lld] is >= h=%d", who, codes[i], (long long)(i / m), (long long)(i % m), h);
+  return RQ_OK;
+}
+
+}  // namespace
+
+int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  const int64_t waves = (n + NR - 1) / NR;
+  hipLaunchKernelGGL(aq_norms_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, norms, codes, C, n, d, m, h);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
+int quantize_norms_launch(uint8_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
+                          hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(quantize_norms_kernel, dim3(grid), dim3(256), 0, stream, norm_codes, dbnorms, norms, cbnorms, n, hn);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
+// codes and codebooks of a host-pointer call on the device, and the norms computed from them
+struct NormsOnDevice {
+  DevMem codes, C, norms;
+  int run(const uint8_t *hcodes, const float *hC, int64_t n, int d, int m, int h) {
+    RQ_TRY(codes.alloc((size_t)n * m)); RQ_TRY(C.alloc((size_t)m * h * d * 4)); RQ_TRY(norms.alloc((size_t)n * 4));
+    RQ_HIP(hipMemcpy(codes.p, hcodes, (size_t)n * m, hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(C.p, hC, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
+    return aq_norms_launch(norms.as<float>(), codes.as<uint8_t>(), C.as<float>(), n, d, m, h, nullptr);
+  }
+};
+
+}  // namespace rq
+
+using namespace rq;
+
+extern "C" {
+
+int rq_dev_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
+  RQ_TRY(norms_check_shape("rq_dev_aq_norms", n, d, m, h));
+  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "rq_dev_aq_norms: null pointer");
+  if (n == 0) return RQ_OK;
+  hipStream_t s = (hipStream_t)stream;
+  RQ_TRY(dev_code_range(codes, n, m, h, s, "rq_dev_aq_norms"));
+  return aq_norms_launch(norms, codes, C, n, d, m, h, s);
+}
+
+int rq_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h) {
+  RQ_TRY(norms_check_shape("rq_aq_norms", n, d, m, h));
+  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "rq_aq_norms: null pointer");
+  RQ_TRY(norms_code_range(codes, n, m, h, "rq_aq_norms"));
+  if (n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDevice dv;
+  RQ_TRY(dv.run(codes, C, n, d, m, h));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(norms, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+int rq_dev_quantize_norms(uint8_t *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n,
+                          int hn, void *stream) {
+  RQ_TRY(norms_check_hn("rq_dev_quantize_norms", hn));
+  if (n < 0) return fail(RQ_EINVAL, "rq_dev_quantize_norms: n=%lld < 0", (long long)n);
+  if (!cbnorms || (n > 0 && (!norm_codes || !norms))) return fail(RQ_EINVAL, "rq_dev_quantize_norms: null pointer");
+  return quantize_norms_launch(norm_codes, dbnorms_out, norms, cbnorms, n, hn, (hipStream_t)stream);
+}
+
+int rq_quantize_norms(uint8_t *norm_codes, float *norms_out, const uint8_t *codes, const float *C, const float *cbnorms,
+                      int64_t n, int d, int m, int h, int hn) {
+  RQ_TRY(norms_check_shape("rq_quantize_norms", n, d, m, h));
+  RQ_TRY(norms_check_hn("rq_quantize_norms", hn));
+  if (!cbnorms || (n > 0 && (!norm_codes || !codes || !C))) return fail(RQ_EINVAL, "rq_quantize_norms: null pointer");
+  RQ_TRY(norms_code_range(codes, n, m, h, "rq_quantize_norms"));
+  if (n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDevice dv;
+  DevMem dcb, dnc;
+  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n));
+  RQ_HIP(hipMemcpy(dcb.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
+  RQ_TRY(dv.run(codes, C, n, d, m, h));
+  RQ_TRY(quantize_norms_launch(dnc.as<uint8_t>(), nullptr, dv.norms.as<float>(), dcb.as<float>(), n, hn, nullptr));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n, hipMemcpyDeviceToHost));
+  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+int rq_get_norms_codebook(uint8_t *norm_codes, float *cbnorms, float *norms_out, const uint8_t *codes, const float *C,
+                          int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed) {
+  RQ_TRY(norms_check_shape("rq_get_norms_codebook", n, d, m, h));
+  RQ_TRY(norms_check_hn("rq_get_norms_codebook", hn));
+  if (niter < 0) return fail(RQ_EINVAL, "rq_get_norms_codebook: niter=%d < 0", niter);
+  if (n < hn) return fail(RQ_EINVAL, "rq_get_norms_codebook: fewer rows (%lld) than norm codebook entries (%d)", (long long)n, hn);
+  if (!norm_codes || !cbnorms || !codes || !C) return fail(RQ_EINVAL, "rq_get_norms_codebook: null pointer");
+  RQ_TRY(norms_code_range(codes, n, m, h, "rq_get_norms_codebook"));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDevice dv;
+  DevMem dcb, dnc;
+  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n));
+  RQ_TRY(dv.run(codes, C, n, d, m, h));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_TRY(train_pq_resident(dcb.as<float>(), dnc.as<uint8_t>(), dv.norms.as<float>(), n, 1, 1, hn, niter, seed));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(cbnorms, dcb.p, (size_t)hn * 4, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n, hipMemcpyDeviceToHost));
+  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+}  // extern "C"

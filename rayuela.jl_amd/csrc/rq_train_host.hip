@@ -264,6 +264,77 @@ static int repick_unused(float *dCsub, const float *dCassigned, const float *dX,
   return RQ_OK;
 }
 
+// The Lloyd loop of train_pq (src/PQ.jl:68-99) on a device-resident X [n][d]: kmeans++ seeding, niter iterations, then the
+// assignments of the final centres.  dC [h * d] and dcodes [n][m] (device) receive them.  rq_train_pq is this loop between an
+// upload and a download; rq_get_norms_codebook runs it with d = m = 1 on norms that never leave the device.
+static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed,
+                         const DeviceInfo &di, TrainProf &prof) {
+  int off[33];
+  offsets(off, d, m);
+  Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
+  DevMem dprev;
+  RQ_TRY(dprev.alloc((size_t)n * m));
+  RQ_PH(TP_INIT, RQ_TRY(seed_centers(dC, dX, n, d, m, h, off, rng)));
+  std::vector<unsigned int> counts((size_t)m * h);
+  // Convergence.  Clustering.kmeans (v0.12.2 `_kmeans!`) stops when |objv - prev_objv| < tol, tol = 1e-6 ABSOLUTE on
+  // objv = sum(costs), a Float32 sum: for any data whose objective exceeds ~10 (float32 resolution 1e-6) that is "the rounded
+  // objective did not move", which an iteration without a changed assignment produces exactly (same assignments -> same centres
+  // -> same costs) and one WITH changed assignments practically never does.  So the loop stops on "no assignment changed" --
+  // the same stopping point on the bench shapes (tests/test_gpu_train.py compares the final error with the oracle loop that
+  // applies Clustering's own rule) -- and does not pay a pass over X per iteration for the objective.  The codes of two consecutive
+  // iterations are compared ON THE DEVICE (a D2H of n*m bytes + a host compare per iteration cost more than the encode)
+  // The change counter sits right behind the cluster counts: ONE small read-back per iteration serves the convergence test
+  // and the empty-cluster check (the centres are recomputed before the test is known; with unchanged assignments that
+  // reproduces them bit for bit).  The two code buffers swap roles instead of being copied.
+  DevMem dCold;        // the centres the current codes were assigned with (repick_unused draws with THOSE costs)
+  RQ_TRY(dCold.alloc((size_t)h * d * 4));
+  DevMem dcc;
+  const size_t cnt_bytes = (size_t)m * h * 4;
+  RQ_TRY(dcc.alloc(cnt_bytes + 8));
+  unsigned int *dcnt_p = dcc.as<unsigned int>();
+  unsigned long long *dchg_p = reinterpret_cast<unsigned long long *>(dcc.as<unsigned char>() + cnt_bytes);
+  std::vector<unsigned char> back(cnt_bytes + 8);
+  uint8_t *cur = dcodes, *prev = dprev.as<uint8_t>();
+  int iters_done = 0;
+  prof.loop_begin();
+  for (int it = 0; it < niter; ++it) {
+    RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(cur, dX, dC, n, d, m, h, di.num_cu, nullptr)));
+    prof.start();
+    if (it > 0) RQ_TRY(codes_changed_launch(dchg_p, cur, prev, (size_t)n * m, nullptr));
+    prof.stop(TP_CONVERGE);
+    RQ_HIP(hipMemcpyAsync(dCold.p, dC, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
+    RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch(dC, dcnt_p, dX, cur, n, d, m, h, di.num_cu, nullptr)));
+    prof.start();
+    RQ_HIP(hipMemcpy(back.data(), dcc.p, cnt_bytes + 8, hipMemcpyDeviceToHost));
+    unsigned long long changed = 1;
+    if (it > 0) memcpy(&changed, back.data() + cnt_bytes, 8);
+    prof.stop(TP_CONVERGE);
+    if (!changed) break;   // assignments stable: Lloyd has converged
+    ++iters_done;
+    memcpy(counts.data(), back.data(), cnt_bytes);
+    for (int i = 0; i < m; ++i) {             // centres that lost all their points: re-drawn like Clustering.kmeans does
+      std::vector<int> unused;
+      for (int k = 0; k < h; ++k)
+        if (counts[(size_t)i * h + k] == 0) unused.push_back(k);
+      if (!unused.empty())
+        RQ_TRY(repick_unused(dC + (size_t)h * off[i], dCold.as<float>() + (size_t)h * off[i], dX, n, d,
+                             off[i], off[i + 1] - off[i], cur, m, i, h, unused, rng));
+    }
+    std::swap(cur, prev);
+  }
+  prof.loop_end(iters_done);      // the final encode overwrites every code: which of the two buffers the loop ended on is moot
+  RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(dcodes, dX, dC, n, d, m, h, di.num_cu, nullptr)));
+  return RQ_OK;
+}
+
+int train_pq_resident(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed) {
+  RQ_TRY(check_train(n, d, m, h, niter));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  TrainProf prof;
+  return train_pq_loop(dC, dcodes, dX, n, d, m, h, niter, seed, di, prof);
+}
+
 }  // namespace rq
 
 using namespace rq;
@@ -295,66 +366,12 @@ int rq_train_pq(float *C, int16_t *B1, double *error, const float *X, int64_t n,
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  int off[33];
-  offsets(off, d, m);
-  Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
-  DevMem dX, dC, dcodes, dprev, dcnt, dCB, dacc, d16;
+  DevMem dX, dC, dcodes, dCB, dacc, d16;
   RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dC.alloc((size_t)h * d * 4)); RQ_TRY(dcodes.alloc((size_t)n * m));
-  RQ_TRY(dprev.alloc((size_t)n * m)); RQ_TRY(dcnt.alloc((size_t)m * h * 4));
   RQ_TRY(dacc.alloc(8)); RQ_TRY(d16.alloc((size_t)n * m * 2));
   TrainProf prof;
   RQ_PH(TP_H2D, RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice)));
-  RQ_PH(TP_INIT, RQ_TRY(seed_centers(dC.as<float>(), dX.as<float>(), n, d, m, h, off, rng)));
-  std::vector<unsigned int> counts((size_t)m * h);
-  // Convergence.  Clustering.kmeans (v0.12.2 `_kmeans!`) stops when |objv - prev_objv| < tol, tol = 1e-6 ABSOLUTE on
-  // objv = sum(costs), a Float32 sum: for any data whose objective exceeds ~10 (float32 resolution 1e-6) that is "the rounded
-  // objective did not move", which an iteration without a changed assignment produces exactly (same assignments -> same centres
-  // -> same costs) and one WITH changed assignments practically never does.  So the loop stops on "no assignment changed" --
-  // the same stopping point on the bench shapes (tests/test_gpu_train.py compares the final error with the oracle loop that
-  // applies Clustering's own rule) -- and does not pay a pass over X per iteration for the objective.  The codes of two consecutive
-  // iterations are compared ON THE DEVICE (a D2H of n*m bytes + a host compare per iteration cost more than the encode)
-  // The change counter sits right behind the cluster counts: ONE small read-back per iteration serves the convergence test
-  // and the empty-cluster check (the centres are recomputed before the test is known; with unchanged assignments that
-  // reproduces them bit for bit).  The two code buffers swap roles instead of being copied.
-  DevMem dCold;        // the centres the current codes were assigned with (repick_unused draws with THOSE costs)
-  RQ_TRY(dCold.alloc((size_t)h * d * 4));
-  DevMem dcc;
-  const size_t cnt_bytes = (size_t)m * h * 4;
-  RQ_TRY(dcc.alloc(cnt_bytes + 8));
-  unsigned int *dcnt_p = dcc.as<unsigned int>();
-  unsigned long long *dchg_p = reinterpret_cast<unsigned long long *>(dcc.as<unsigned char>() + cnt_bytes);
-  std::vector<unsigned char> back(cnt_bytes + 8);
-  uint8_t *cur = dcodes.as<uint8_t>(), *prev = dprev.as<uint8_t>();
-  int iters_done = 0;
-  prof.loop_begin();
-  for (int it = 0; it < niter; ++it) {
-    RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(cur, dX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
-    prof.start();
-    if (it > 0) RQ_TRY(codes_changed_launch(dchg_p, cur, prev, (size_t)n * m, nullptr));
-    prof.stop(TP_CONVERGE);
-    RQ_HIP(hipMemcpyAsync(dCold.p, dC.p, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
-    RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch(dC.as<float>(), dcnt_p, dX.as<float>(), cur, n, d, m, h, di.num_cu, nullptr)));
-    prof.start();
-    RQ_HIP(hipMemcpy(back.data(), dcc.p, cnt_bytes + 8, hipMemcpyDeviceToHost));
-    unsigned long long changed = 1;
-    if (it > 0) memcpy(&changed, back.data() + cnt_bytes, 8);
-    prof.stop(TP_CONVERGE);
-    if (!changed) break;   // assignments stable: Lloyd has converged
-    ++iters_done;
-    memcpy(counts.data(), back.data(), cnt_bytes);
-    for (int i = 0; i < m; ++i) {             // centres that lost all their points: re-drawn like Clustering.kmeans does
-      std::vector<int> unused;
-      for (int k = 0; k < h; ++k)
-        if (counts[(size_t)i * h + k] == 0) unused.push_back(k);
-      if (!unused.empty())
-        RQ_TRY(repick_unused(dC.as<float>() + (size_t)h * off[i], dCold.as<float>() + (size_t)h * off[i], dX.as<float>(), n, d,
-                             off[i], off[i + 1] - off[i], cur, m, i, h, unused, rng));
-    }
-    std::swap(cur, prev);
-  }
-  if (cur != dcodes.as<uint8_t>()) std::swap(dcodes.p, dprev.p);      // the final encode below writes (and the download reads) dcodes
-  prof.loop_end(iters_done);
-  RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(dcodes.as<uint8_t>(), dX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
+  RQ_TRY(train_pq_loop(dC.as<float>(), dcodes.as<uint8_t>(), dX.as<float>(), n, d, m, h, niter, seed, di, prof));
   if (codes_forms_ok(d, m, h, false)) {
     RQ_PH(TP_QERROR, RQ_TRY(qerror_codes_launch(dacc.as<double>(), dX.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
   } else {

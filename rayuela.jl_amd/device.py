@@ -328,6 +328,29 @@ def reconstruct_aq(codes, C, out=None):
     return out
 
 
+def aq_norms(codes, C, out=None):
+    """norms (n,) = |sum_i C_i[codes[:, i]]|^2 for full-dimensional codebooks C (m, h, d), without the reconstruction
+    (rq_dev_aq_norms; the order of the f32 sums is veccost's)."""
+    n, m = codes.shape
+    _, h, d = C.shape
+    out = torch.empty((n,), dtype=torch.float32, device=codes.device) if out is None else out
+    _lib.check(_lib.lib().rq_dev_aq_norms(_chk(out, torch.float32, "norms"), _chk(codes, torch.uint8, "codes"),
+                                          _chk(C, torch.float32, "C"), n, d, m, h, _stream()))
+    return out
+
+
+def quantize_norms(norms, cbnorms, out=None, dbnorms=None):
+    """(norm codes (n,) uint8 zero-based, dbnorms (n,) = cbnorms[code]) of resident norms: the first entry of the unsorted
+    cbnorms (hn <= 256) nearest in f32, findmin's tie rule (rq_dev_quantize_norms)."""
+    n = norms.shape[0]
+    out = torch.empty((n,), dtype=torch.uint8, device=norms.device) if out is None else out
+    dbnorms = torch.empty((n,), dtype=torch.float32, device=norms.device) if dbnorms is None else dbnorms
+    _lib.check(_lib.lib().rq_dev_quantize_norms(_chk(out, torch.uint8, "norm_codes"), _chk(dbnorms, torch.float32, "dbnorms"),
+                                                _chk(norms, torch.float32, "norms"), _chk(cbnorms, torch.float32, "cbnorms"),
+                                                n, cbnorms.shape[0], _stream()))
+    return out, dbnorms
+
+
 def gram(X, CB):
     """G = X' CB, [d][d] with G[a][b] = sum_j X[j][a] CB[j][b]."""
     n, d = X.shape

@@ -1,8 +1,11 @@
 """Host mirror of the end-to-end drivers: experiment_pq (src/PQ.jl:104-132), experiment_pq_query_base
 (:137-159), experiment_opq (src/OPQ.jl:142-171), experiment_opq_query_base (:174-197), experiment_rvq
 (src/RVQ.jl:130-175), experiment_rvq_query_base (:163-188), experiment_ervq and experiment_ervq_query_base
-(src/ERVQ.jl:151-242), experiment_sr_cuda (src/SR.jl:247-306, :348-373), experiment_sr_cuda_query_base (:308-344, :376-402).
-train -> encode the base -> ADC search -> recall, every O(n) step on the device."""
+(src/ERVQ.jl:151-242), experiment_sr_cuda (src/SR.jl:247-306, :348-373), experiment_sr_cuda_query_base (:308-344, :376-402),
+experiment_lsq_cuda and experiment_lsq_cuda_query_base (src/LSQ_GPU.jl:322-467).
+train -> encode the base -> ADC search -> recall, every O(n) step on the device.  The norms leg of the additive quantizers
+(get_norms_codebook, quantize_norms) runs on the device in the LSQ drivers and, with norms="device", in the RVQ, ERVQ and SR
+drivers; their default norms="host" keeps the two numpy helpers below."""
 import numpy as np
 
 from .Linscan import eval_recall, linscan_opq, linscan_pq
@@ -91,6 +94,41 @@ def _quantize_norms(B, C, norms_C):
     return order[np.where(left, pos - 1, pos)] + 1, dbnorms
 
 
+def _check_norms_arg(norms):
+    if norms not in ("host", "device"):
+        raise ValueError('norms must be "host" or "device"; got %r' % (norms,))
+
+
+def _search_base(B, C, h, seed, B_base, Xq, knn, norms, norms_niter=25):
+    """The search leg over an encoded base: norms codebook of the training codes -> quantised norms of the base -> linscan_lsq.
+    norms_niter: the k-means iterations of the device path; 25 is what the host helper runs, so that the two paths of the RVQ,
+    ERVQ and SR drivers differ in the rounding of the norms alone."""
+    from .Linscan import linscan_lsq, linscan_lsq_cbnorms
+    from .utils import get_norms_codebook
+    d = Xq.shape[1]
+    R = np.eye(d, dtype=np.float32)
+    if norms == "device":
+        _, norms_C = get_norms_codebook(B, C, norms_niter, seed=seed)
+        return linscan_lsq_cbnorms(B_base, Xq, C, norms_C, R, knn)
+    _, norms_C = _norms_codebook(B, C, h, seed=seed)
+    B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
+    db_norms = norms_C[B_base_norms - 1].astype(np.float32)
+    return linscan_lsq(B_base, Xq, C, db_norms, R, knn)
+
+
+def _search_train(B, C, h, seed, Xq, knn, norms, norms_niter=25):
+    """The search leg of the query-base drivers: the k-means' own assignments of the training codes are their quantised norms."""
+    from .Linscan import linscan_lsq
+    from .utils import get_norms_codebook
+    d = Xq.shape[1]
+    if norms == "device":
+        norms_B, norms_C = get_norms_codebook(B, C, norms_niter, seed=seed)
+    else:
+        norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
+    db_norms = norms_C[norms_B - 1].astype(np.float32)
+    return linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+
+
 def _qerror_aq(X, B, C):
     """qerror (src/qerrors.jl) of full-dimensional codebooks: mean squared error of the summed reconstruction."""
     recon = np.zeros(X.shape, dtype=np.float64)
@@ -99,45 +137,40 @@ def _qerror_aq(X, B, C):
     return float(((X.astype(np.float64) - recon) ** 2).sum() / X.shape[0])
 
 
-def experiment_rvq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
+def experiment_rvq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0, norms="host"):
     """experiment_rvq (src/RVQ.jl:130-175): train_rvq -> norms codebook -> quantize_rvq of the base ->
-    quantised database norms -> linscan_lsq -> eval_recall."""
+    quantised database norms -> linscan_lsq -> eval_recall.  norms="device": the norms leg on the device (get_norms_codebook,
+    LsqIndex.from_cbnorms) instead of the numpy helpers."""
     from .RVQ import train_rvq, quantize_rvq
-    from .Linscan import linscan_lsq
-    d = Xt.shape[1]
+    _check_norms_arg(norms)
     C, B, train_error = train_rvq(Xt, m, h, niter, V, seed=seed)
-    _, norms_C = _norms_codebook(B, C, h, seed=seed)
     B_base, _ = quantize_rvq(Xb, C, V)
-    B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
-    db_norms = norms_C[B_base_norms - 1].astype(np.float32)
-    dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    dists, idx = _search_base(B, C, h, seed, B_base, Xq, knn, norms)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
 
 
-def experiment_rvq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
+def experiment_rvq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0, norms="host"):
     """experiment_rvq_query_base (src/RVQ.jl:163-188): train_rvq -> norms codebook -> linscan_lsq over the training codes
-    -> eval_recall."""
+    -> eval_recall.  norms as for experiment_rvq."""
     from .RVQ import train_rvq
-    from .Linscan import linscan_lsq
-    d = Xt.shape[1]
+    _check_norms_arg(norms)
     C, B, train_error = train_rvq(Xt, m, h, niter, V, seed=seed)
-    norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
-    db_norms = norms_C[norms_B - 1].astype(np.float32)
-    dists, idx = linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    dists, idx = _search_train(B, C, h, seed, Xq, knn, norms)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, recall
 
 
-def experiment_ervq(Xt, *args, V=False, seed=0):
+def experiment_ervq(Xt, *args, V=False, seed=0, norms="host"):
     """experiment_ervq(Xt, B, C, Xb, Xq, gt, m, h, niter=25, knn=1000, V=false)         (src/ERVQ.jl:151-184)
     experiment_ervq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=false)                (src/ERVQ.jl:214-227)
 
     train_ervq -> norms codebook -> quantize_ervq of the base -> quantised database norms -> linscan_lsq -> eval_recall.
-    The second method starts from train_rvq(Xt, m, h, niter, V).  Returns C, B, train_error, B_base, recall."""
+    The second method starts from train_rvq(Xt, m, h, niter, V).  Returns C, B, train_error, B_base, recall.
+    norms as for experiment_rvq."""
     from .ERVQ import train_ervq, quantize_ervq
     from .RVQ import train_rvq
-    from .Linscan import linscan_lsq
+    _check_norms_arg(norms)
     if len(args) >= 7 and np.ndim(args[5]) == 0 and np.ndim(args[6]) == 0 and np.ndim(args[3]) > 0:
         B, C, Xb, Xq, gt, m, h = args[:7]
         rest = list(args[7:])
@@ -154,27 +187,24 @@ def experiment_ervq(Xt, *args, V=False, seed=0):
         raise TypeError("experiment_ervq: too many arguments")
     if B is None:
         C, B, _ = train_rvq(Xt, m, h, niter, V, seed=seed)
-    d = Xt.shape[1]
     C, B, train_error = train_ervq(Xt, B, C, m, h, niter, V, seed=seed)
-    _, norms_C = _norms_codebook(B, C, h, seed=seed)
     B_base, _ = quantize_ervq(Xb, C, V)
     if V:
         print("Error in base is %e" % _qerror_aq(Xb, B_base, C))
-    B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
-    db_norms = norms_C[B_base_norms - 1].astype(np.float32)
-    dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    dists, idx = _search_base(B, C, h, seed, B_base, Xq, knn, norms)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
 
 
-def experiment_ervq_query_base(Xt, *args, V=False, seed=0):
+def experiment_ervq_query_base(Xt, *args, V=False, seed=0, norms="host"):
     """experiment_ervq_query_base(Xt, B, C, Xq, gt, m, h, niter=25, knn=1000, V=false)  (src/ERVQ.jl:187-211)
     experiment_ervq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=false)         (src/ERVQ.jl:230-242)
 
-    train_ervq -> norms codebook -> linscan_lsq over the training codes -> eval_recall.  Returns C, B, train_error, recall."""
+    train_ervq -> norms codebook -> linscan_lsq over the training codes -> eval_recall.  Returns C, B, train_error, recall.
+    norms as for experiment_rvq."""
     from .ERVQ import train_ervq
     from .RVQ import train_rvq
-    from .Linscan import linscan_lsq
+    _check_norms_arg(norms)
     if len(args) >= 6 and np.ndim(args[4]) == 0 and np.ndim(args[5]) == 0 and np.ndim(args[2]) > 0:
         B, C, Xq, gt, m, h = args[:6]
         rest = list(args[6:])
@@ -191,11 +221,8 @@ def experiment_ervq_query_base(Xt, *args, V=False, seed=0):
         raise TypeError("experiment_ervq_query_base: too many arguments")
     if B is None:
         C, B, _ = train_rvq(Xt, m, h, niter, V, seed=seed)
-    d = Xt.shape[1]
     C, B, train_error = train_ervq(Xt, B, C, m, h, niter, V, seed=seed)
-    norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
-    db_norms = norms_C[norms_B - 1].astype(np.float32)
-    dists, idx = linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    dists, idx = _search_train(B, C, h, seed, Xq, knn, norms)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, recall
 
@@ -212,14 +239,14 @@ def _sr_init(Xt, m, h, niter_init, chain, V, seed):
 
 def experiment_sr_cuda_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, nsplits_train=1, sr_method="SR_D", V=False,
                                   seed=0, B=None, C=None, R=None, ilsiter=8, icmiter=4, randord=True, npert=4,
-                                  schedule=1, p=0.5, niter_init=25):
+                                  schedule=1, p=0.5, niter_init=25, norms="host"):
     """experiment_sr_cuda_query_base (src/SR.jl:308-344, :376-402): train_sr_cuda -> norms codebook -> linscan_lsq over
     the training codes -> eval_recall.  Without B, C, R the start is train_opq "natural" then train_chainq (niter_init
     iterations each, the reference's 25) and the result is ((C, B, R, train_error, recall), opq_error) like the
-    reference's six-argument method; with them it is (C, B, R, train_error, recall) like the full method."""
-    from .Linscan import linscan_lsq
+    reference's six-argument method; with them it is (C, B, R, train_error, recall) like the full method.
+    norms as for experiment_rvq."""
     from .SR import train_sr_cuda
-    d = Xt.shape[1]
+    _check_norms_arg(norms)
     opq_error = None
     given = B is not None
     if not given:
@@ -228,9 +255,7 @@ def experiment_sr_cuda_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, nsplits_
         print("Running CUDA %s training... " % sr_method)
     C, B, train_error = train_sr_cuda(Xt, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, sr_method, schedule, p,
                                       nsplits_train, V, seed=seed)
-    norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
-    db_norms = norms_C[norms_B - 1].astype(np.float32)
-    dists, idx = linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    dists, idx = _search_train(B, C, h, seed, Xq, knn, norms)
     recall = eval_recall(gt, idx, knn, verbose=V)
     res = (C, B, R, train_error, recall)
     return res if given else (res, opq_error)
@@ -238,15 +263,14 @@ def experiment_sr_cuda_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, nsplits_
 
 def experiment_sr_cuda(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, nsplits_train=1, nsplits_base=1, sr_method="SR_D",
                        V=False, seed=0, B=None, C=None, R=None, ilsiter=8, icmiter=4, randord=True, npert=4, schedule=1,
-                       p=0.5, niter_init=25):
+                       p=0.5, niter_init=25, norms="host"):
     """experiment_sr_cuda (src/SR.jl:247-306, :348-373): train_sr_cuda -> norms codebook -> the base encoded by
     encode_icm_cuda with 4 ilsiter iterations from seeded random codes -> quantised database norms -> linscan_lsq ->
     eval_recall.  Without B, C, R the start is train_opq "natural" (the reference leaves train_chainq out here, :369).
-    Returns C, B, R, train_error, B_base, recall."""
-    from .Linscan import linscan_lsq
+    Returns C, B, R, train_error, B_base, recall.  norms as for experiment_rvq."""
     from .LSQ import encode_icm_cuda
     from .SR import train_sr_cuda
-    d = Xt.shape[1]
+    _check_norms_arg(norms)
     if B is None:
         C, B, R, _ = _sr_init(Xt, m, h, niter_init, False, V, seed)
     if V:
@@ -254,14 +278,99 @@ def experiment_sr_cuda(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, nsplits_train=1
               % (sr_method, m, npert, icmiter, bool(randord)))
     C, B, train_error = train_sr_cuda(Xt, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, sr_method, schedule, p,
                                       nsplits_train, V, seed=seed)
-    _, norms_C = _norms_codebook(B, C, h, seed=seed)
     B_base = np.random.default_rng(seed).integers(1, h + 1, size=(Xb.shape[0], m)).astype(np.int16)
     Bs_base, objs = encode_icm_cuda(Xb, B_base, C, [ilsiter * 4], icmiter, npert, randord, nsplits_base, V, seed=seed)
     B_base = Bs_base[-1]
     if V:
         print("Error in base is %e" % objs[-1])
-    B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
-    db_norms = norms_C[B_base_norms - 1].astype(np.float32)
-    dists, idx = linscan_lsq(B_base, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    dists, idx = _search_base(B, C, h, seed, B_base, Xq, knn, norms)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, R, train_error, B_base, recall
+
+
+def experiment_lsq_cuda(Xt, *args, V=False, seed=0, niter_init=25):
+    """experiment_lsq_cuda(Xt, B, C, R, Xb, Xq, gt, m, h, niter=25, ilsiter=8, icmiter=4, randord=true, npert=4, knn=1000,
+                        nsplits_train=1, nsplits_base=1, V=false)                                  (src/LSQ_GPU.jl:322-368)
+    experiment_lsq_cuda(Xt, Xb, Xq, gt, m, h, niter=25, ...the same...)                               (src/LSQ_GPU.jl:407-436)
+
+    train_lsq_cuda -> norms codebook -> the base encoded by encode_icm_cuda with 4 ilsiter iterations from seeded random
+    codes -> quantised database norms -> linscan_lsq -> eval_recall; the norms leg runs on the device (get_norms_codebook,
+    LsqIndex.from_cbnorms).  The second method starts from train_opq "natural" (niter_init iterations; the reference passes
+    niter, :426 -- niter_init defaults to its 25).  Returns C, B, R, train_error, B_base, recall."""
+    from .LSQ import encode_icm_cuda, train_lsq_cuda
+    if len(args) >= 8 and np.ndim(args[6]) == 0 and np.ndim(args[7]) == 0 and np.ndim(args[3]) > 0:
+        B, C, R, Xb, Xq, gt, m, h = args[:8]
+        rest = list(args[8:])
+    elif len(args) >= 5:
+        Xb, Xq, gt, m, h = args[:5]
+        rest = list(args[5:])
+        B = None
+    else:
+        raise TypeError("experiment_lsq_cuda(Xt, [B, C, R,] Xb, Xq, gt, m, h, niter=25, ilsiter=8, icmiter=4, randord=true, "
+                        "npert=4, knn=1000, nsplits_train=1, nsplits_base=1, V=false)")
+    names = ("niter", "ilsiter", "icmiter", "randord", "npert", "knn", "nsplits_train", "nsplits_base", "V")
+    if len(rest) > len(names):
+        raise TypeError("experiment_lsq_cuda: too many arguments")
+    o = dict(niter=25, ilsiter=8, icmiter=4, randord=True, npert=4, knn=1000, nsplits_train=1, nsplits_base=1, V=V)
+    o.update(zip(names, rest))
+    V = bool(o["V"])
+    if B is None:
+        C, B, R, _ = train_opq(Xt, m, h, niter_init, "natural", V, seed=seed)
+    if V:
+        print("Running CUDA LSQ training... ")
+    C, B, train_error = train_lsq_cuda(Xt, m, h, R, B, C, o["niter"], o["ilsiter"], o["icmiter"], o["randord"], o["npert"],
+                                       o["nsplits_train"], V, seed=seed)
+    B_base = np.random.default_rng(seed).integers(1, h + 1, size=(Xb.shape[0], m)).astype(np.int16)
+    Bs_base, objs = encode_icm_cuda(Xb, B_base, C, [o["ilsiter"] * 4], o["icmiter"], o["npert"], o["randord"],
+                                    o["nsplits_base"], V, seed=seed)
+    B_base = Bs_base[-1]
+    if V:
+        print("Error in base is %e" % objs[-1])
+    dists, idx = _search_base(B, C, h, seed, B_base, Xq, int(o["knn"]), "device", 100)
+    recall = eval_recall(gt, idx, int(o["knn"]), verbose=V)
+    return C, B, R, train_error, B_base, recall
+
+
+def experiment_lsq_cuda_query_base(Xt, *args, V=False, seed=0):
+    """experiment_lsq_cuda_query_base(Xt, B, C, R, Xq, gt, m, h, niter=25, ilsiter=8, icmiter=4, randord=true, npert=4,
+                                   knn=1000, nsplits_train=1, V=false)                             (src/LSQ_GPU.jl:370-403)
+    experiment_lsq_cuda_query_base(Xt, Xq, gt, m, h, niter=25, ilsiter=8, icmiter=4, randord=true, npert=4, init="natural",
+                                   niter_opq=25, niter_chainq=25, knn=1000, nsplits_train=1, V=false)  (src/LSQ_GPU.jl:438-468)
+
+    train_lsq_cuda -> norms codebook on the device -> linscan_lsq over the training codes with the k-means' assignments ->
+    eval_recall.  The first method returns (C, B, R, train_error, recall).  The second starts from train_opq(init) then
+    train_chainq and returns ((C, B, R, train_error, recall), opq_error).  Deviation: the reference's second method hands
+    `niter, knn, nsplits_train, V` positionally to the first (:467), where they land in the slots niter, ilsiter, icmiter,
+    randord; here every argument is passed by meaning (ilsiter, icmiter, randord, npert included)."""
+    from .ChainQ import train_chainq
+    from .LSQ import train_lsq_cuda
+    full = len(args) >= 7 and np.ndim(args[5]) == 0 and np.ndim(args[6]) == 0 and np.ndim(args[2]) > 0
+    if full:
+        B, C, R, Xq, gt, m, h = args[:7]
+        rest = list(args[7:])
+        names = ("niter", "ilsiter", "icmiter", "randord", "npert", "knn", "nsplits_train", "V")
+    elif len(args) >= 4:
+        Xq, gt, m, h = args[:4]
+        rest = list(args[4:])
+        names = ("niter", "ilsiter", "icmiter", "randord", "npert", "init", "niter_opq", "niter_chainq", "knn",
+                 "nsplits_train", "V")
+    else:
+        raise TypeError("experiment_lsq_cuda_query_base(Xt, [B, C, R,] Xq, gt, m, h, niter=25, ...)")
+    if len(rest) > len(names):
+        raise TypeError("experiment_lsq_cuda_query_base: too many arguments")
+    o = dict(niter=25, ilsiter=8, icmiter=4, randord=True, npert=4, init="natural", niter_opq=25, niter_chainq=25, knn=1000,
+             nsplits_train=1, V=V)
+    o.update(zip(names, rest))
+    V = bool(o["V"])
+    opq_error = None
+    if not full:
+        C, B, R, opq_error = train_opq(Xt, m, h, o["niter_opq"], o["init"], V, seed=seed)
+        C, B, R, _ = train_chainq(Xt, m, h, R, B, C, o["niter_chainq"], V)
+    if V:
+        print("Running CUDA LSQ training... ")
+    C, B, train_error = train_lsq_cuda(Xt, m, h, R, B, C, o["niter"], o["ilsiter"], o["icmiter"], o["randord"], o["npert"],
+                                       o["nsplits_train"], V, seed=seed)
+    dists, idx = _search_train(B, C, h, seed, Xq, int(o["knn"]), "device", 100)
+    recall = eval_recall(gt, idx, int(o["knn"]), verbose=V)
+    res = (C, B, R, train_error, recall)
+    return res if full else (res, opq_error)
