@@ -152,6 +152,29 @@ int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n
 int rq_dev_encode_rvq(uint8_t *codes, float *Xr, const float *codebooks, int64_t n, int d, int m, int h,
                       uint32_t *counts, void *stream);
 
+/* ---- Beam-search residual encoding: CompetitiveQ's `encode` (src/CompetitiveQ.jl:75-135).  Contract in DESIGN.md section 2
+ * ("Beam encoding contract").  Like quantize_rvq, but the H best partial encodings of each vector survive a stage instead of
+ * one: stage i ranks the H_i * h candidates (parent j, codeword k) by (v, j * h + k), v = max(0, fl(fl(sa_k + sb_j) - 2 g_jk))
+ * with k-ordered fmaf chains, and keeps the min(H, H_i * h) smallest; the answer is the rank-0 survivor of the last stage.
+ * X [n][d], codebooks [m][h][d] as for rq_encode_rvq, codes [n][m] uint8 zero-based (Int16 one-based for _i16), cost_out [n]
+ * = the answer's last-stage v and Xr_out [n][d] = its residual (either may be NULL).  1 <= m <= 64, 1 <= h <= 256,
+ * 1 <= H <= 32 and H <= h, d >= 1, n >= 0, nsplits >= 1 (the minimum number of row chunks; results do not depend on it).
+ * Every argument is checked before any work; a violation returns RQ_EINVAL through rq_last_error and writes no output byte.
+ * H = 1 gives rq_encode_rvq's codes and residual bit for bit.  Non-finite inputs: the call returns, codes stay below h, the
+ * values are unspecified.  train_competitiveq (src/CompetitiveQ.jl:138-221) is a per-sample SGD and is not provided. */
+int rq_encode_rvq_beam(uint8_t *codes, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int H,
+                       int nsplits, float *cost_out, float *Xr_out);
+/* src/CompetitiveQ.jl:75-135 with the reference's Int16 one-based codes */
+int rq_encode_rvq_beam_i16(int16_t *codes1, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int H,
+                           int nsplits, float *cost_out, float *Xr_out);
+/* src/CompetitiveQ.jl:75-135 on device pointers, queued on `stream`; X is NOT overwritten, scratch comes from the per-stream
+ * workspace (at most 2 GiB: rows are chunked); Xr_out and cost_out may be NULL and are then not touched */
+int rq_dev_encode_rvq_beam(uint8_t *codes, float *Xr_out, float *cost_out, const float *X, const float *codebooks, int64_t n,
+                           int d, int m, int h, int H, int nsplits, void *stream);
+/* milliseconds of this thread's last beam call (src/CompetitiveQ.jl:75-135) by phase (hipEvents): {stage kernels, expand
+ * kernels, other}; cap entries written.  After a device-pointer call it waits for that call's last event. */
+int rq_last_beam_timing(double *ms, int cap);
+
 /* ---- Enhanced RVQ / Stacked Quantizers: train_ervq (src/ERVQ.jl:51-135, arXiv 1411.2173).  Contract in DESIGN.md
  * section 2 ("ERVQ").  quantize_ervq IS quantize_rvq (src/ERVQ.jl:19-26): use rq_encode_rvq.  Layouts as for RVQ: X [n][d],
  * C [m][h][d] (m full-dimensional codebooks back to back, one entry per row).  1 <= m <= 64, 2 <= h <= 256, any d >= 1.

@@ -19,6 +19,7 @@ import Clustering, Distances
 
 export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan_lsq, linscan_cq, train_pq, train_opq, train_rvq
 export quantize_ervq, train_ervq
+export quantize_competitiveq
 export get_norms_codebook, quantize_norms
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
@@ -126,6 +127,45 @@ function quantize_rvq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, V::Bool=fa
     end
   end
   return B, singletons
+end
+
+"""
+    quantize_competitiveq(X, C, H; nsplits=1) -> B     (src/CompetitiveQ.jl:75-135 for every column of X)
+Beam-search residual encoding: the `H` best partial encodings of each vector survive a stage (1 <= H <= min(32, h)); H = 1 is
+`quantize_rvq`.  `B::Matrix{Int16}` m-by-n one-based, in `quantize_rvq`'s layout.  `train_competitiveq`
+(src/CompetitiveQ.jl:138-221) is a per-sample SGD and is not provided: train with `train_rvq` / `train_ervq`.
+"""
+function quantize_competitiveq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, H::Integer; nsplits::Integer=1)
+  d, n = size(X)
+  m    = length(C)
+  h    = size(C[1], 2)
+  B    = Matrix{Int16}(undef, m, n)
+  _check(ccall((:rq_encode_rvq_beam_i16, librayuela_hip), Cint,
+    (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
+    B, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(H), Cint(nsplits), C_NULL, C_NULL))
+  return B
+end
+
+"""
+    encode(x, C, new_res, m, h, d, H) -> codes, residual     (src/CompetitiveQ.jl:75-135)
+The reference's signature for one vector; `new_res` (its residual buffer) is accepted and ignored.  Not exported: call it
+as `RayuelaHIP.encode`.
+"""
+function encode(x::Vector{Float32}, C::Vector{Matrix{Float32}}, new_res, m::Integer, h::Integer, d::Integer, H::Integer)
+  codes = Vector{UInt8}(undef, m)
+  xr    = Vector{Float32}(undef, d)
+  _check(ccall((:rq_encode_rvq_beam, librayuela_hip), Cint,
+    (Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
+    codes, x, hcat(C...), Int64(1), Cint(d), Cint(m), Cint(h), Cint(H), Cint(1), C_NULL, xr))
+  return Int16.(codes) .+ Int16(1), xr
+end
+
+"""milliseconds of this thread's last beam call: (stage kernels, expand kernels, other)"""
+function last_beam_timing()
+  ms  = zeros(Cdouble, 3)
+  cap = 3
+  _check(ccall((:rq_last_beam_timing, librayuela_hip), Cint, (Ptr{Cdouble}, Cint), ms, Cint(cap)))
+  return (stage=ms[1], expand=ms[2], other=ms[3])
 end
 
 """
