@@ -10,6 +10,8 @@
  *   src/Linscan.jl:93-115  linscan_opq                                    -> rq_linscan_opq
  *   src/PQ.jl:18-48        quantize_pq                                    -> rq_encode_pq[_i16]
  *   src/OPQ.jl:19-27       quantize_opq  (R'X then quantize_pq)           -> rq_encode_opq[_i16], rq_rotate_T
+ *   src/xvecs_read.jl:14-52 + src/read_datasets.jl:148-167  bvecs (UInt8) data, widened before it is encoded
+ *                                                                         -> rq_encode_pq_bytes[_i16], rq_encode_opq_bytes[_i16]
  *
  * Array layouts are the C views of the Julia (column-major) arrays, so Julia passes its
  * arrays as they are (zero-copy on the host side):
@@ -381,6 +383,28 @@ int rq_encode_pq_i16(int16_t *codes1, const float *X, const float *C, int64_t n,
                      int h);
 int rq_encode_opq_i16(int16_t *codes1, const float *X, const float *R, const float *C, int64_t n,
                       int d, int m, int h);
+/* ---- byte rows: quantize_pq / quantize_opq of UInt8 data without widening it on the host.
+ * bvecs files (SIFT1B: bigann_base / learn / query) hold UInt8 vectors -- bvecs_read returns Matrix{UInt8},
+ * src/xvecs_read.jl:14-52 -- and the reference converts them to Float32 on the host before it encodes them
+ * (src/read_datasets.jl:148-167: convert(Matrix{Float32}, X)).  These take X [n][d] uint8 as it lies in the file and
+ * return, for every input, byte for byte the codes of the f32 entry point on the widened matrix (u8 -> f32 is exact);
+ * a quarter of the bytes cross PCIe (chunks of max(32768, 2^25 / d) rows, as the f32 calls use, double buffered; tuning
+ * HOST_OVERLAP = 0: one buffer, no overlap).  Every (d, m, h) the f32 entry points accept is accepted: even sub-space
+ * widths <= 16 run the filter + exact pass with byte loaders (rq_last_encode_kernel: "encode_pq_filter_bytes_kernel"),
+ * rotations of d in {32, 64, 96, 128} a byte-loading rotation; every other shape is widened on the device into a bounded
+ * scratch and takes the f32 kernels (rq_last_encode_kernel then names the f32 kernel).  Statuses, rq_last_timing and
+ * rq_last_encode_stats as the f32 entry points; a NULL pointer is RQ_EINVAL. */
+/* quantize_pq on UInt8 data (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167; src/PQ.jl:18-48). */
+int rq_encode_pq_bytes(uint8_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h);
+/* quantize_opq on UInt8 data (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167; src/OPQ.jl:19-27). */
+int rq_encode_opq_bytes(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n,
+                        int d, int m, int h);
+/* The same with Julia's return type: Int16, ONE-based, m x n (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167;
+ * src/PQ.jl:45-47). */
+int rq_encode_pq_bytes_i16(int16_t *codes1, const uint8_t *X, const float *C, int64_t n, int d, int m,
+                           int h);
+int rq_encode_opq_bytes_i16(int16_t *codes1, const uint8_t *X, const float *R, const float *C, int64_t n,
+                            int d, int m, int h);
 /* A base set kept on the device: upload X [n][d] once (to the calling thread's current device), encode it as often
  * as needed -- quantize_pq and quantize_opq of the same Xb with different codebooks / rotations pay PCIe once
  * (from host memory quantize_pq is upload-bound: ~9 ms of PCIe against 0.7 ms of kernel per 1e6 x 128).
@@ -388,6 +412,10 @@ int rq_encode_opq_i16(int16_t *codes1, const float *X, const float *R, const flo
  * [n][m] uint8 zero-based and/or codes1 m x n Int16 one-based (either may be NULL). */
 typedef struct rq_dataset rq_dataset;
 rq_dataset *rq_dataset_upload(const float *X, int64_t n, int d);
+/* The same for UInt8 rows (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167): the base stays n d BYTES on the device
+ * (1e9 x 128: 128 GB, which fits one MI355X; as f32 it would not).  rq_dataset_encode / rq_dataset_free work on either
+ * kind; R'X of a byte base lives chunk-wise in scratch. */
+rq_dataset *rq_dataset_upload_bytes(const uint8_t *X, int64_t n, int d);
 int rq_dataset_encode(rq_dataset *ds, uint8_t *codes, int16_t *codes1, const float *R, const float *C, int m, int h);
 void rq_dataset_free(rq_dataset *ds);
 /* RX = R' * X (src/OPQ.jl:26, src/Linscan.jl:102). */
@@ -418,6 +446,15 @@ int rq_dev_encode_pq_filter_w(uint8_t *codes, float *W, const float *X, const fl
 /* Fused rotate+encode is an implementation detail; tmp may be NULL (library workspace). */
 int rq_dev_encode_opq(uint8_t *codes, const float *X, const float *R, const float *C, int64_t n,
                       int d, int m, int h, void *stream);
+/* Device-pointer forms of the byte entry points (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167): X uint8 [n][d]
+ * at ANY byte alignment (the kernels pick the widest load X, d and the sub-space width allow, down to single bytes);
+ * every other pointer 16-byte aligned.  Codes / R'X are bit for bit those of rq_dev_encode_pq / rq_dev_encode_opq /
+ * rq_dev_rotate_T on the widened rows.  Scratch: the stream's workspace, bounded by max(32768, 2^25 / d) rows of f32. */
+int rq_dev_encode_pq_bytes(uint8_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m,
+                           int h, void *stream);
+int rq_dev_encode_opq_bytes(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n,
+                            int d, int m, int h, void *stream);
+int rq_dev_rotate_T_bytes(float *RX, const float *R, const uint8_t *X, int d, int64_t n, void *stream);
 /* Per-query ADC look-up tables lut [nq][m][256] (deps/src/linscan_aqd.cpp:66-74); test aid. */
 int rq_dev_adc_lut(float *lut, const float *centers, const float *queries, int64_t nq, int m,
                    int subdim, void *stream);

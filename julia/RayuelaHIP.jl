@@ -95,6 +95,37 @@ function quantize_opq(X::Matrix{Float32}, R::Matrix{Float32}, C::Vector{Matrix{F
 end
 
 """
+    quantize_pq(X::Matrix{UInt8}, C, V=false) -> B
+    quantize_opq(X::Matrix{UInt8}, R, C, V=false) -> B
+Byte data as `bvecs_read` returns it (src/xvecs_read.jl:14-52), encoded without the host-side
+`convert(Matrix{Float32}, X)` of src/read_datasets.jl:148-167: `B == quantize_pq(convert(Matrix{Float32}, X), C)`,
+from a quarter of the bytes over PCIe.
+"""
+function quantize_pq(X::Matrix{UInt8}, C::Vector{Matrix{Float32}}, V::Bool=false)
+  d, n = size(X)
+  m    = length(C)
+  h    = size(C[1], 2)
+  B    = _result(Int16, m, n)
+  if V print("Encoding on $m codebooks with librayuela_hip... ") end
+  _check(ccall((:rq_encode_pq_bytes_i16, librayuela_hip), Cint,
+    (Ptr{Int16}, Ptr{UInt8}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
+    B, X, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
+  if V println("done") end
+  return B
+end
+
+function quantize_opq(X::Matrix{UInt8}, R::Matrix{Float32}, C::Vector{Matrix{Float32}}, V::Bool=false)
+  d, n = size(X)
+  m    = length(C)
+  h    = size(C[1], 2)
+  B    = _result(Int16, m, n)
+  _check(ccall((:rq_encode_opq_bytes_i16, librayuela_hip), Cint,
+    (Ptr{Int16}, Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
+    B, X, R, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
+  return B
+end
+
+"""
     quantize_rvq(X, C, V=false) -> B, singletons     (src/RVQ.jl:18-66)
 `B::Matrix{Int16}` m-by-n one-based; `singletons[i]` holds re-picked entries for the unused centres of
 codebook i.  The m encode stages and residual updates run on the device; the library returns the

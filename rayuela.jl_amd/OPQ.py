@@ -2,16 +2,17 @@
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32, cat_codebooks
+from .utils import _as_f32, _as_f32_or_u8, cat_codebooks
 
 
 def quantize_opq(X, R, C, V=False):
     """quantize_opq(X, R, C, V=false) -> B      (src/OPQ.jl:19-27) == quantize_pq(R' * X, C, V)
 
     R : (d, d) float32, the memory image of Julia's d-by-d rotation (so R_numpy[i, k] == R_julia[k, i]).
+    X : (n, d) float32, or (n, d) uint8 (bvecs data): the codes of X.astype(float32), rotated and encoded from the bytes.
     Returns (n, m) int16 ONE-based codes.
     """
-    X = _as_f32(X, "X")
+    X = _as_f32_or_u8(X, "X")
     R = _as_f32(R, "R")
     n, d = X.shape
     if R.shape != (d, d):
@@ -20,8 +21,9 @@ def quantize_opq(X, R, C, V=False):
     h = np.asarray(C[0]).shape[0]
     Cc = cat_codebooks(C)
     B = _lib.result_empty((n, m), np.int16)
-    _lib.check(_lib.lib().rq_encode_opq_i16(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data,
-                                            n, d, m, h))
+    L = _lib.lib()
+    encode = L.rq_encode_opq_bytes_i16 if X.dtype == np.uint8 else L.rq_encode_opq_i16
+    _lib.check(encode(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data, n, d, m, h))
     return B
 
 

@@ -2,17 +2,18 @@
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32, cat_codebooks
+from .utils import _as_f32, _as_f32_or_u8, cat_codebooks
 
 
 def quantize_pq(X, C, V=False):
     """quantize_pq(X, C, V=false) -> B          (src/PQ.jl:18-48)
 
-    X : (n, d) float32 -- the memory image of Julia's d-by-n matrix
+    X : (n, d) float32 -- the memory image of Julia's d-by-n matrix -- or (n, d) uint8 (bvecs data, src/xvecs_read.jl:14-52):
+        the codes of X.astype(float32), encoded from the bytes (rq_encode_pq_bytes_i16)
     C : list of m arrays (h, sub_i) float32 -- memory images of the sub_i-by-h codebooks
     Returns B : (n, m) int16, ONE-based codes (memory image of Julia's m-by-n Matrix{Int16}).
     """
-    X = _as_f32(X, "X")
+    X = _as_f32_or_u8(X, "X")
     n, d = X.shape
     m = len(C)
     h = np.asarray(C[0]).shape[0]
@@ -22,7 +23,9 @@ def quantize_pq(X, C, V=False):
     if V:
         print("Encoding on %d codebooks with librayuela_hip... " % m, end="")
     B = _lib.result_empty((n, m), np.int16)
-    _lib.check(_lib.lib().rq_encode_pq_i16(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
+    L = _lib.lib()
+    encode = L.rq_encode_pq_bytes_i16 if X.dtype == np.uint8 else L.rq_encode_pq_i16
+    _lib.check(encode(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
     if V:
         print("done")
     return B
@@ -31,13 +34,15 @@ def quantize_pq(X, C, V=False):
 def quantize_pq_u8(X, C):
     """Same encode, returning the zero-based uint8 wire format the scan consumes
     (convert(Matrix{UInt8}, B .- 1), src/Linscan.jl:35)."""
-    X = _as_f32(X, "X")
+    X = _as_f32_or_u8(X, "X")
     n, d = X.shape
     m = len(C)
     h = np.asarray(C[0]).shape[0]
     Cc = cat_codebooks(C)
     B = _lib.result_empty((n, m), np.uint8)
-    _lib.check(_lib.lib().rq_encode_pq(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
+    L = _lib.lib()
+    encode = L.rq_encode_pq_bytes if X.dtype == np.uint8 else L.rq_encode_pq
+    _lib.check(encode(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
     return B
 
 

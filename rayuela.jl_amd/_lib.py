@@ -51,6 +51,10 @@ SIGNATURES = {
     "rq_encode_opq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_encode_pq_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_encode_opq_i16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_encode_pq_bytes": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_encode_opq_bytes": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_encode_pq_bytes_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_encode_opq_bytes_i16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_encode_rvq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_encode_rvq_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_train_rvq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_uint64]),
@@ -86,6 +90,7 @@ SIGNATURES = {
     "rq_train_chainq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
     "rq_last_chainq_timing": (_i32, [_vp, _i32]),
     "rq_dataset_upload": (_vp, [_vp, _i64, _i32]),
+    "rq_dataset_upload_bytes": (_vp, [_vp, _i64, _i32]),
     "rq_dataset_encode": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),
     "rq_dataset_free": (None, [_vp]),
     "rq_rotate_T": (_i32, [_vp, _vp, _vp, _i32, _i64]),
@@ -95,6 +100,9 @@ SIGNATURES = {
     "rq_last_encode_stats": (C.c_int, [C.c_void_p]),
     "rq_dev_rotate_T": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
     "rq_dev_encode_opq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_dev_encode_pq_bytes": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_dev_encode_opq_bytes": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_dev_rotate_T_bytes": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
     "rq_dev_adc_lut": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "rq_dev_linscan": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _u32, _i32, _vp]),
     "rq_scan_row_width": (_i32, [_i32]),

@@ -828,7 +828,10 @@ static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, co
 // (two device buffers; the codes stay on the device and come back in ONE copy at the end -- a pageable D2H per
 // chunk would make the host wait for each kernel and serialise the pipeline).  PCIe is the bound of this call
 // (57 GB/s from pageable memory): the kernels now hide behind the uploads instead of adding to them.
-static int encode_host_rows(uint8_t *codes, int16_t *codes1, const float *X, const float *R, const float *C,
+// esz = 4: X is f32 [n][d].  esz = 1: X is uint8 [n][d] (bvecs: src/xvecs_read.jl:14-52; the reference widens on the host,
+// src/read_datasets.jl:148-167) -- the SAME rows per chunk, so an upload is 32 MiB where f32 moves 128 MiB, and the chunk
+// is rotated / encoded from bytes (encode_bytes_launch; its f32 scratch is bounded by the chunk).
+static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int esz, const float *R, const float *C,
                             int64_t n, int d, int m, int h, double *t_h2d, double *t_tail) {
   DeviceInfo di;
   RQ_TRY(device_info(&di));
@@ -836,15 +839,15 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const float *X, con
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, std::max<int64_t>(32768, (1LL << 27) / ((int64_t)d * 4))));
   const bool piped = tuning("HOST_OVERLAP", 1) && n > chunk;
   DevBuf dX[2], dRX, dR, dC, dcodes, d16;
-  RQ_TRY(dX[0].alloc((size_t)chunk * d * 4));
-  if (piped) RQ_TRY(dX[1].alloc((size_t)chunk * d * 4));
+  RQ_TRY(dX[0].alloc((size_t)chunk * d * esz));
+  if (piped) RQ_TRY(dX[1].alloc((size_t)chunk * d * esz));
   RQ_TRY(dC.alloc((size_t)h * d * 4));
   RQ_TRY(dcodes.alloc((size_t)n * m));
   if (codes1) RQ_TRY(d16.alloc((size_t)n * m * 2));
   RQ_HIP(hipMemcpy(dC.p, C, (size_t)h * d * 4, hipMemcpyHostToDevice));
   if (R) {
     RQ_TRY(dR.alloc((size_t)d * d * 4));
-    RQ_TRY(dRX.alloc((size_t)chunk * d * 4));
+    if (esz == 4) RQ_TRY(dRX.alloc((size_t)chunk * d * 4));
     RQ_HIP(hipMemcpy(dR.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
   }
   hipStream_t cs = nullptr, xs = nullptr;
@@ -864,16 +867,22 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const float *X, con
     const int b = piped ? (k & 1) : 0;
     if (k >= (piped ? 2 : 1)) RQ_HIP(hipEventSynchronize(ev.done[b]));   // the kernels that read this buffer are done
     Timer t1;
-    RQ_HIP(hipMemcpyAsync(dX[b].p, X + (size_t)r0 * d, (size_t)nr * d * 4, hipMemcpyHostToDevice, xs));
+    RQ_HIP(hipMemcpyAsync(dX[b].p, static_cast<const unsigned char *>(X) + (size_t)r0 * d * esz, (size_t)nr * d * esz,
+                          hipMemcpyHostToDevice, xs));
     RQ_HIP(hipEventRecord(ev.up[b], xs));
     *t_h2d += t1.ms();
     RQ_HIP(hipStreamWaitEvent(cs, ev.up[b], 0));
-    const float *src = dX[b].as<float>();
-    if (R) {
-      RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX[b].as<float>(), d, nr, di.num_cu, cs));
-      src = dRX.as<float>();
+    if (esz == 1) {
+      RQ_TRY(encode_bytes_launch(dcodes.as<uint8_t>() + (size_t)r0 * m, dX[b].as<uint8_t>(), R ? dR.as<float>() : nullptr,
+                                 dC.as<float>(), nr, d, m, h, di.num_cu, cs));
+    } else {
+      const float *src = dX[b].as<float>();
+      if (R) {
+        RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX[b].as<float>(), d, nr, di.num_cu, cs));
+        src = dRX.as<float>();
+      }
+      RQ_TRY(encode_launch(dcodes.as<uint8_t>() + (size_t)r0 * m, src, dC.as<float>(), nr, d, m, h, di.num_cu, cs));
     }
-    RQ_TRY(encode_launch(dcodes.as<uint8_t>() + (size_t)r0 * m, src, dC.as<float>(), nr, d, m, h, di.num_cu, cs));
     RQ_HIP(hipEventRecord(ev.done[b], cs));
   }
   Timer t2;
@@ -885,8 +894,8 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const float *X, con
   return RQ_OK;
 }
 
-static int host_encode(uint8_t *codes, int16_t *codes1, const float *X, const float *R, const float *C,
-                       int64_t n, int d, int m, int h) {
+static int host_encode(uint8_t *codes, int16_t *codes1, const void *X, const float *R, const float *C,
+                       int64_t n, int d, int m, int h, int esz = 4) {
   Timer tt;
   g_t_h2d = g_t_kernel = g_t_d2h = 0;
   if (n <= 0) return RQ_OK;
@@ -909,7 +918,8 @@ static int host_encode(uint8_t *codes, int16_t *codes1, const float *X, const fl
       th.emplace_back([&, i, r0, cnt]() {
         if (hipSetDevice(devs[i]) != hipSuccess) { rc[i] = RQ_ENODEVICE; msg[i] = "hipSetDevice failed"; return; }
         rc[i] = encode_host_rows(codes ? codes + (size_t)r0 * m : nullptr, codes1 ? codes1 + (size_t)r0 * m : nullptr,
-                                 X + (size_t)r0 * d, R, C, cnt, d, m, h, &h2d[i], &tail[i]);
+                                 static_cast<const unsigned char *>(X) + (size_t)r0 * d * esz, esz, R, C, cnt, d, m, h, &h2d[i],
+                                 &tail[i]);
         if (rc[i] != RQ_OK) msg[i] = g_err;
       });
     }
@@ -925,7 +935,7 @@ static int host_encode(uint8_t *codes, int16_t *codes1, const float *X, const fl
   SavedDevice saved;
   if (nd == 1) RQ_HIP(hipSetDevice(devs[0]));
   double h2d = 0, tail = 0;
-  RQ_TRY(encode_host_rows(codes, codes1, X, R, C, n, d, m, h, &h2d, &tail));
+  RQ_TRY(encode_host_rows(codes, codes1, X, esz, R, C, n, d, m, h, &h2d, &tail));
   g_t_h2d = h2d;
   g_t_d2h = tail;          // what is left after the last upload: last chunk's kernels + the one copy back
   g_t_total = tt.ms();
@@ -1301,21 +1311,47 @@ int rq_encode_opq_i16(int16_t *codes1, const float *X, const float *R, const flo
   return host_encode(nullptr, codes1, X, R, C, n, d, m, h);
 }
 
+// Byte rows (bvecs_read returns Matrix{UInt8}, src/xvecs_read.jl:14-52; the reference converts to Float32 on the host before it
+// encodes, src/read_datasets.jl:148-167): the codes of the widened matrix, from a quarter of the upload.
+static int host_encode_bytes(uint8_t *codes, int16_t *codes1, const uint8_t *X, const float *R, const float *C, int64_t n,
+                             int d, int m, int h) {
+  if (n <= 0) return RQ_OK;
+  if (!X || !C || (!codes && !codes1)) return fail(RQ_EINVAL, "byte encode: NULL argument");
+  return host_encode(codes, codes1, X, R, C, n, d, m, h, 1);
+}
+int rq_encode_pq_bytes(uint8_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h) {
+  return host_encode_bytes(codes, nullptr, X, nullptr, C, n, d, m, h);
+}
+int rq_encode_opq_bytes(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h) {
+  if (!R) return fail(RQ_EINVAL, "R is NULL");
+  return host_encode_bytes(codes, nullptr, X, R, C, n, d, m, h);
+}
+int rq_encode_pq_bytes_i16(int16_t *codes1, const uint8_t *X, const float *C, int64_t n, int d, int m, int h) {
+  return host_encode_bytes(nullptr, codes1, X, nullptr, C, n, d, m, h);
+}
+int rq_encode_opq_bytes_i16(int16_t *codes1, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m,
+                            int h) {
+  if (!R) return fail(RQ_EINVAL, "R is NULL");
+  return host_encode_bytes(nullptr, codes1, X, R, C, n, d, m, h);
+}
+
 // ---- resident dataset: X uploaded once, encoded as often as needed ------------------------------------------
 struct rq_dataset_impl {
   int device, d;
   int64_t n;
-  float *X, *RX;
+  float *X, *RX;      // bytes: X holds uint8 [n][d], RX stays null (R'X lives chunk-wise in scratch)
+  int esz;            // 4: f32 rows, 1: byte rows (rq_dataset_upload_bytes)
 };
 
-rq_dataset *rq_dataset_upload(const float *X, int64_t n, int d) {
+static rq_dataset *dataset_upload(const void *X, int64_t n, int d, int esz) {
   if (!X || n < 1 || d < 1) { fail(RQ_EINVAL, "rq_dataset_upload: bad arguments"); return nullptr; }
   DeviceInfo di;
   if (device_info(&di) != RQ_OK) return nullptr;
-  rq_dataset_impl *ds = new rq_dataset_impl{di.device, d, n, nullptr, nullptr};
-  if (hipMalloc((void **)&ds->X, (size_t)n * d * 4) != hipSuccess ||
-      hipMemcpy(ds->X, X, (size_t)n * d * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    fail(RQ_ENODEVICE, "rq_dataset_upload: cannot place %lld x %d floats on device %d", (long long)n, d, di.device);
+  rq_dataset_impl *ds = new rq_dataset_impl{di.device, d, n, nullptr, nullptr, esz};
+  if (hipMalloc((void **)&ds->X, (size_t)n * d * esz) != hipSuccess ||
+      hipMemcpy(ds->X, X, (size_t)n * d * esz, hipMemcpyHostToDevice) != hipSuccess) {
+    fail(RQ_ENODEVICE, "rq_dataset_upload: cannot place %lld x %d %s on device %d", (long long)n, d, esz == 1 ? "bytes" : "floats",
+         di.device);
     (void)hipGetLastError();
     if (ds->X) (void)hipFree(ds->X);
     delete ds;
@@ -1323,6 +1359,10 @@ rq_dataset *rq_dataset_upload(const float *X, int64_t n, int d) {
   }
   return reinterpret_cast<rq_dataset *>(ds);
 }
+rq_dataset *rq_dataset_upload(const float *X, int64_t n, int d) { return dataset_upload(X, n, d, 4); }
+// a byte base stays bytes on the device: 1e9 x 128 is 128 GB, which one MI355X holds; as f32 it is 512 GB
+// (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167)
+rq_dataset *rq_dataset_upload_bytes(const uint8_t *X, int64_t n, int d) { return dataset_upload(X, n, d, 1); }
 
 int rq_dataset_encode(rq_dataset *handle, uint8_t *codes, int16_t *codes1, const float *R, const float *C, int m, int h) {
   rq_dataset_impl *ds = reinterpret_cast<rq_dataset_impl *>(handle);
@@ -1345,11 +1385,18 @@ int rq_dataset_encode(rq_dataset *handle, uint8_t *codes, int16_t *codes1, const
   if (R) {
     RQ_TRY(dR.alloc((size_t)d * d * 4));
     RQ_HIP(hipMemcpy(dR.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-    if (!ds->RX) RQ_HIP(hipMalloc((void **)&ds->RX, (size_t)n * d * 4));
-    RQ_TRY(rotate_launch(ds->RX, dR.as<float>(), ds->X, d, n, di.num_cu, nullptr));
-    src = ds->RX;
   }
-  RQ_TRY(encode_launch(dcodes.as<uint8_t>(), src, dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  if (ds->esz == 1) {
+    RQ_TRY(encode_bytes_launch(dcodes.as<uint8_t>(), reinterpret_cast<const uint8_t *>(ds->X), R ? dR.as<float>() : nullptr,
+                               dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  } else {
+    if (R) {
+      if (!ds->RX) RQ_HIP(hipMalloc((void **)&ds->RX, (size_t)n * d * 4));
+      RQ_TRY(rotate_launch(ds->RX, dR.as<float>(), ds->X, d, n, di.num_cu, nullptr));
+      src = ds->RX;
+    }
+    RQ_TRY(encode_launch(dcodes.as<uint8_t>(), src, dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  }
   if (codes1) {
     RQ_TRY(d16.alloc((size_t)n * m * 2));
     RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), n * m, nullptr));
@@ -1429,6 +1476,33 @@ int rq_dev_encode_opq(uint8_t *codes, const float *X, const float *R, const floa
   RQ_TRY(workspace(WS_TMP, (size_t)n * d * 4, &tmp, (hipStream_t)stream));
   RQ_TRY(rotate_launch((float *)tmp, R, X, d, n, di.num_cu, (hipStream_t)stream));
   return encode_launch(codes, (const float *)tmp, C, n, d, m, h, di.num_cu, (hipStream_t)stream);
+}
+
+// ---- byte rows on the device (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167): X uint8 [n][d] at ANY alignment --------
+int rq_dev_encode_pq_bytes(uint8_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, void *stream) {
+  if (n <= 0) return RQ_OK;
+  if (!codes || !X || !C) return fail(RQ_EINVAL, "rq_dev_encode_pq_bytes: NULL argument");
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  return encode_bytes_launch(codes, X, nullptr, C, n, d, m, h, di.num_cu, (hipStream_t)stream);
+}
+
+int rq_dev_encode_opq_bytes(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m,
+                            int h, void *stream) {
+  if (!R) return fail(RQ_EINVAL, "R is NULL");
+  if (n <= 0) return RQ_OK;
+  if (!codes || !X || !C) return fail(RQ_EINVAL, "rq_dev_encode_opq_bytes: NULL argument");
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  return encode_bytes_launch(codes, X, R, C, n, d, m, h, di.num_cu, (hipStream_t)stream);
+}
+
+int rq_dev_rotate_T_bytes(float *RX, const float *R, const uint8_t *X, int d, int64_t n, void *stream) {
+  if (n <= 0) return RQ_OK;
+  if (!RX || !R || !X || d < 1) return fail(RQ_EINVAL, "rq_dev_rotate_T_bytes: bad arguments");
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  return rotate_bytes_launch(RX, R, X, d, n, di.num_cu, (hipStream_t)stream);
 }
 
 int rq_dev_encode_rvq(uint8_t *codes, float *Xr, const float *codebooks, int64_t n, int d, int m, int h,

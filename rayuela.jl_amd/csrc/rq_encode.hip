@@ -1273,6 +1273,7 @@ const char *last_encode_kernel_name() {
     case 3: return "encode_pq_kernel";
     case 4: return "encode_wide_kernel";
     case 5: return "encode_pq_filter_kernel";
+    case 6: return "encode_pq_filter_bytes_kernel";
     default: return "";
   }
 }
@@ -1373,6 +1374,26 @@ int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int
   if (nt <= 2) return launch_encode_wide<2>(p, num_cu, stream);
   if (nt <= 4) return launch_encode_wide<4>(p, num_cu, stream);
   return launch_encode_wide<8>(p, num_cu, stream);
+}
+
+// Byte rows (rq_encode_bytes.hip): the filter + exact pass with byte loaders covers what the f32 dispatch above gives to
+// encode_filter_launch -- ENC_SPLIT = 1, even sub-space widths <= 16 -- at ANY alignment of X; every other shape (and
+// ENC_SPLIT = 0 / 2) is widened into scratch and takes encode_launch.
+bool encode_filter_bytes_covers(int d, int m) {
+  return tuning("ENC_SPLIT", 1) == 1 && m >= 1 && (d % m == 0) && (d / m) % 2 == 0 && d / m <= 16;
+}
+
+int encode_filter_bytes(uint8_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                        hipStream_t stream) {
+  EncParams p;
+  p.X = reinterpret_cast<const float *>(X);      // the byte kernels read it as uint8 [n][d]
+  p.C = C; p.codes = codes; p.n = n; p.d = d; p.m = m; p.h = h;
+  p.NT = (h + 31) / 32;
+  p.delta_rel = (float)tuning("ENC_SPLIT_DELTA_MILLI", 3000) * 1e-3f * 6.103515625e-05f;
+  p.dbg_w = nullptr;
+  for (int i = 0; i <= m; ++i) p.off[i] = i * (d / m);
+  g_last_encode_kernel = 6;
+  return encode_filter_bytes_launch(p, d / m, (h + 31) / 32, tuning("ENC_SPLIT_WAVES", 0), num_cu, stream);
 }
 
 int rotate_launch(float *RX, const float *R, const float *X, int d, int64_t n, int num_cu,

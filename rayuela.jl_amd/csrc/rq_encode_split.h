@@ -164,7 +164,62 @@ __device__ __forceinline__ int argmin_finish(const ArgminState &st, int hi) {
   return st.best_t * 32 + 4 * hi + 8 * (rf >> 2) + (rf & 3);
 }
 
+// ---- byte rows (bvecs are UInt8, src/xvecs_read.jl:14-52; the reference widens them on the host, src/read_datasets.jl:148-167)
+// The byte kernels read X as uint8 and widen in registers: u8 -> f32 is exact, so every value the f32 kernels load from the
+// widened matrix is reproduced bit for bit, and everything after the loaders is the same code.
+// byte_align: the widest power of two (<= 8) that divides the address of EVERY piece a kernel loads, X + row d + i SUB
+// (+ 8 hi): the lowest set bit of X | d | SUB | 8.  Uniform over the launch.
+__device__ __forceinline__ int byte_align(const void *X, int d, int sub) {
+  const uint32_t mix = (uint32_t)(uintptr_t)X | (uint32_t)d | (uint32_t)sub | 8u;
+  return (int)(mix & (0u - mix));
+}
+// w <- the first nb bytes at src (nb <= NB; a multiple of `al`), zero above them, with the widest loads `al` allows;
+// nothing outside [src, src + nb) is read
+template <int NB>
+__device__ __forceinline__ void load_bytes(const uint8_t *src, int al, int nb, uint32_t (&w)[(NB + 3) / 4]) {
+#pragma unroll
+  for (int q = 0; q < (NB + 3) / 4; ++q) w[q] = 0u;
+  if (NB % 8 == 0 && al >= 8) {
+#pragma unroll
+    for (int q = 0; q < NB / 8; ++q)
+      if (8 * q < nb) { const uint2 v = *reinterpret_cast<const uint2 *>(src + 8 * q); w[2 * q] = v.x; w[2 * q + 1] = v.y; }
+  } else if (NB % 4 == 0 && al >= 4) {
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q)
+      if (4 * q < nb) w[q] = *reinterpret_cast<const uint32_t *>(src + 4 * q);
+  } else if (NB % 2 == 0 && al >= 2) {
+#pragma unroll
+    for (int q = 0; q < NB / 2; ++q)
+      if (2 * q < nb) w[q >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t *>(src + 2 * q) << (16 * (q & 1));
+  } else {
+#pragma unroll
+    for (int q = 0; q < NB; ++q)
+      if (q < nb) w[q >> 2] |= (uint32_t)src[q] << (8 * (q & 3));
+  }
+}
+// byte S of the packed words as f32: the hardware's v_cvt_f32_ubyte0..3, no integer arithmetic on the way
+template <int S>
+__device__ __forceinline__ float byte_f32(const uint32_t *w) {
+  float r;
+  if constexpr ((S & 3) == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(r) : "v"(w[S >> 2]));
+  else if constexpr ((S & 3) == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(r) : "v"(w[S >> 2]));
+  else if constexpr ((S & 3) == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(r) : "v"(w[S >> 2]));
+  else asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(r) : "v"(w[S >> 2]));
+  return r;
+}
+template <int N, int S = 0>
+__device__ __forceinline__ void bytes_f32(const uint32_t *w, float *x) {
+  if constexpr (S < N) { x[S] = byte_f32<S>(w); bytes_f32<N, S + 1>(w, x); }
+}
+
 // rq_encode_filter.hip: filter launch + exact pass per group of sub-quantizers that fits LDS (even widths <= 16)
 int encode_filter_launch(const EncParams &p, int sub, int nt, int waves, int num_cu, hipStream_t stream);
+// the same on byte rows: p.X reinterpreted as uint8 [n][d], any alignment (encode_pq_filter_bytes_kernel)
+int encode_filter_bytes_launch(const EncParams &p, int sub, int nt, int waves, int num_cu, hipStream_t stream);
+// rq_encode.hip: whether the byte filter covers (d, m) under the current ENC_SPLIT, and its launch (encode_launch's
+// set-up; records "encode_pq_filter_bytes_kernel" for rq_last_encode_kernel)
+bool encode_filter_bytes_covers(int d, int m);
+int encode_filter_bytes(uint8_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                        hipStream_t stream);
 
 }  // namespace rq

@@ -187,6 +187,13 @@ int rvq_encode_launch(uint8_t *codes, float *Xr, uint8_t *stage_codes, unsigned 
 int rotate_launch(float *RX, const float *R, const float *X, int d, int64_t n, int num_cu,
                   hipStream_t stream);
 int widen_codes_launch(int16_t *out1, const uint8_t *codes, int64_t nelem, hipStream_t stream);
+// ---- byte rows (rq_encode_bytes.hip): X uint8 [n][d] on the device, any alignment ------------------------------------------
+int64_t bytes_chunk_rows(int d);      // rows per upload chunk / per piece of f32 scratch: max(32768, 2^25 / d)
+int widen_bytes_launch(float *out, const uint8_t *in, size_t nelem, hipStream_t stream);
+// codes of the widened rows (R == null: quantize_pq, else quantize_opq with R [d][d] on the device), as encode_launch gives them
+int encode_bytes_launch(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                        int num_cu, hipStream_t stream);
+int rotate_bytes_launch(float *RX, const float *R, const uint8_t *X, int d, int64_t n, int num_cu, hipStream_t stream);
 
 // ---- training reductions (rq_train.hip) --------------------------------------------------------
 int update_centers_launch(float *C, unsigned int *counts, const float *X, const uint8_t *codes, int64_t n, int d,

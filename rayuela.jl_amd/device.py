@@ -18,8 +18,13 @@ def _chk(t, dtype, name):
 
 
 def encode_pq(X, Ccat, m, h, out=None):
+    """X float32, or uint8 rows (any byte alignment): the codes of X.float(), encoded from the bytes."""
     n, d = X.shape
     out = torch.empty((n, m), dtype=torch.uint8, device=X.device) if out is None else out
+    if X.dtype == torch.uint8:
+        _lib.check(_lib.lib().rq_dev_encode_pq_bytes(_chk(out, torch.uint8, "codes"), _chk(X, torch.uint8, "X"),
+                                                     _chk(Ccat, torch.float32, "C"), n, d, m, h, _stream()))
+        return out
     _lib.check(_lib.lib().rq_dev_encode_pq(_chk(out, torch.uint8, "codes"), _chk(X, torch.float32, "X"),
                                            _chk(Ccat, torch.float32, "C"), n, d, m, h, _stream()))
     return out
@@ -49,7 +54,13 @@ def polar_factor(G, method=0):
 
 
 def rotate_T(R, X, out=None):
+    """R' X of X float32, or of uint8 rows (any byte alignment): bit for bit rotate_T(R, X.float())."""
     n, d = X.shape
+    if X.dtype == torch.uint8:
+        out = torch.empty((n, d), dtype=torch.float32, device=X.device) if out is None else out
+        _lib.check(_lib.lib().rq_dev_rotate_T_bytes(_chk(out, torch.float32, "RX"), _chk(R, torch.float32, "R"),
+                                                    _chk(X, torch.uint8, "X"), d, n, _stream()))
+        return out
     out = torch.empty_like(X) if out is None else out
     _lib.check(_lib.lib().rq_dev_rotate_T(_chk(out, torch.float32, "RX"), _chk(R, torch.float32, "R"),
                                           _chk(X, torch.float32, "X"), d, n, _stream()))
@@ -57,8 +68,14 @@ def rotate_T(R, X, out=None):
 
 
 def encode_opq(X, R, Ccat, m, h, out=None):
+    """X float32, or uint8 rows (any byte alignment): the codes of X.float(), rotated and encoded from the bytes."""
     n, d = X.shape
     out = torch.empty((n, m), dtype=torch.uint8, device=X.device) if out is None else out
+    if X.dtype == torch.uint8:
+        _lib.check(_lib.lib().rq_dev_encode_opq_bytes(_chk(out, torch.uint8, "codes"), _chk(X, torch.uint8, "X"),
+                                                      _chk(R, torch.float32, "R"), _chk(Ccat, torch.float32, "C"),
+                                                      n, d, m, h, _stream()))
+        return out
     _lib.check(_lib.lib().rq_dev_encode_opq(_chk(out, torch.uint8, "codes"), _chk(X, torch.float32, "X"),
                                             _chk(R, torch.float32, "R"), _chk(Ccat, torch.float32, "C"),
                                             n, d, m, h, _stream()))

@@ -83,12 +83,15 @@ class Index:
 
 
 class Dataset:
-    """A base set resident on the device (rq_dataset_*): uploaded once, encoded as often as needed."""
+    """A base set resident on the device (rq_dataset_*): uploaded once, encoded as often as needed.  X float32, or uint8
+    (bvecs data), which stays n * d bytes on the device and encodes to the codes of X.astype(float32)."""
 
     def __init__(self, X):
-        X = _as_f32(X, "X")
+        from .utils import _as_f32_or_u8
+        X = _as_f32_or_u8(X, "X")
         self.n, self.d = X.shape
-        self._h = _lib.lib().rq_dataset_upload(X.ctypes.data, self.n, self.d)
+        upload = _lib.lib().rq_dataset_upload_bytes if X.dtype == np.uint8 else _lib.lib().rq_dataset_upload
+        self._h = upload(X.ctypes.data, self.n, self.d)
         if not self._h:
             raise _lib.RayuelaHipError("rq_dataset_upload: " + _lib.lib().rq_last_error().decode("utf-8", "replace"))
 

@@ -27,6 +27,20 @@ def _as_f32(a, name):
     return np.ascontiguousarray(a)
 
 
+def _as_f32_or_u8(a, name):
+    """Data the encoders take: float32, or uint8 rows as bvecs files hold them (src/xvecs_read.jl:14-52), which the byte
+    entry points encode without widening them on the host (the reference widens: src/read_datasets.jl:148-167)."""
+    a = np.asarray(a)
+    if a.dtype == np.uint8:
+        return np.ascontiguousarray(a)
+    return _as_f32(a, name)
+
+
+def encode_chunk_rows(d):
+    """Rows per upload chunk of the host-pointer encodes, f32 and bytes alike: max(32768, 2^25 / d)."""
+    return max(32768, (1 << 25) // int(d))
+
+
 def cat_codebooks(C):
     """Vector{Matrix} -> one flat buffer: concatenation of the m [h][sub_i] blocks
     (== cat(C..., dims=3) of src/Linscan.jl:22 when all sub_i are equal)."""

@@ -63,3 +63,62 @@ def fvecs_write(X, filename):
 def ivecs_write(X, filename):
     """ivecs_write(X, filename)    (src/xvecs_write.jl:19-25); X (n, d) int32."""
     _write(X, filename, "<i4")
+
+
+def bvecs_write(X, filename):
+    """bvecs_write(X, filename); X (n, d) uint8.  The reference reads .bvecs (src/xvecs_read.jl:14-52) and has no writer for
+    them; this is the inverse of bvecs_read: per vector int32 d (little endian), then d bytes."""
+    X = np.asarray(X)
+    if X.dtype != np.uint8 or X.ndim != 2:
+        raise TypeError("X must be a (n, d) uint8 array")
+    n, d = X.shape
+    rec = np.empty((n, 4 + d), dtype=np.uint8)
+    rec[:, :4] = np.array([d], dtype="<i4").view(np.uint8)
+    rec[:, 4:] = X
+    rec.tofile(filename)
+
+
+def quantize_bvecs(filename, C, R=None, bounds=None, rows_per_read=1 << 20, one_based=False):
+    """Codes of the vectors of a .bvecs file (bigann_base.bvecs -> Index.set_codes): the file is read piecewise with
+    bvecs_read(bounds, filename), rows_per_read vectors at a time, and every piece is encoded from its bytes -- the reference
+    reads the bytes and widens them to Float32 first (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167); the codes are
+    the same.  R is None: quantize_pq, else quantize_opq.  bounds: None (all), n (first n) or (a, b) one-based inclusive.
+    Returns (n, m) uint8 zero-based codes (the scan's wire format), or int16 one-based with one_based=True."""
+    from . import _lib
+    from .utils import _as_f32, cat_codebooks
+    if rows_per_read < 1:
+        raise ValueError("rows_per_read must be positive")
+    with open(filename, "rb") as f:
+        d = int(np.fromfile(f, dtype="<i4", count=1)[0])
+        f.seek(0, 2)
+        vecnum = f.tell() // (4 + d)
+    if bounds is None:
+        a, b = 1, vecnum
+    elif isinstance(bounds, (int, np.integer)):
+        a, b = 1, int(bounds)
+    else:
+        a, b = int(bounds[0]), int(bounds[1])
+    if a < 1 or b > vecnum or b < a:
+        raise ValueError("%s holds %d vectors, asked for %d..%d" % (filename, vecnum, a, b))
+    m = len(C)
+    h = np.asarray(C[0]).shape[0]
+    Cc = cat_codebooks(C)
+    if Cc.size != h * d:
+        raise ValueError("codebooks do not tile the %d dimensions of %s" % (d, filename))
+    Rc = None if R is None else _as_f32(R, "R")
+    if Rc is not None and Rc.shape != (d, d):
+        raise ValueError("R must be %d x %d" % (d, d))
+    n = b - a + 1
+    out = np.empty((n, m), dtype=np.int16 if one_based else np.uint8)
+    L = _lib.lib()
+    for r0 in range(0, n, rows_per_read):
+        nr = min(rows_per_read, n - r0)
+        X = bvecs_read((a + r0, a + r0 + nr - 1), filename)
+        dst = out[r0:r0 + nr]                       # (a contiguous block of rows of `out`)
+        if Rc is None:
+            encode = L.rq_encode_pq_bytes_i16 if one_based else L.rq_encode_pq_bytes
+            _lib.check(encode(dst.ctypes.data, X.ctypes.data, Cc.ctypes.data, nr, d, m, h))
+        else:
+            encode = L.rq_encode_opq_bytes_i16 if one_based else L.rq_encode_opq_bytes
+            _lib.check(encode(dst.ctypes.data, X.ctypes.data, Rc.ctypes.data, Cc.ctypes.data, nr, d, m, h))
+    return out
