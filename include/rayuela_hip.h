@@ -147,7 +147,8 @@ int rq_encode_rvq_i16(int16_t *codes1, const float *X, const float *codebooks, i
 /* train_rvq (src/RVQ.jl:86-127): one k-means of niter Lloyd iterations per stage on the running residual.
  * C [m][h][d] out; B1 [n][m] Int16 one-based out (== quantize_rvq(X, C)); *error = qerror(X, B, C).
  * Seeding: kmeans++ on the running residual like the reference (rq_kmpp_seeds), from the library's seeded
- * stream instead of Julia's global RNG, so results agree in objective, not bit for bit. */
+ * stream instead of Julia's global RNG, so results agree in objective, not bit for bit.  One stream serves the
+ * whole call: every stage draws its h uniforms where the stage before (its repicks included) left off. */
 int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
                  uint64_t seed);
 /* device-pointer form: Xr [n][d] holds X on entry and the final residual on return */

@@ -70,7 +70,8 @@ def train_rvq(X, m, h, niter=25, V=False, seed=0):
 
     One k-means per stage on the running residual, all on the device (rq_train_rvq).  C: m-long list of
     (h, d) codebooks; B: (n, m) int16 one-based, equal to quantize_rvq(X, C)[0]; error = qerror(X, B, C).
-    Seeding comes from the library's seeded stream (the reference: kmeans++ with Julia's RNG)."""
+    Seeding is kmeans++ on the running residual like the reference, drawn from the library's seeded stream
+    (the reference: Julia's RNG)."""
     import ctypes
     X = _as_f32(X, "X")
     n, d = X.shape

@@ -391,7 +391,8 @@ int rq_train_pq(float *C, int16_t *B1, double *error, const float *X, int64_t n,
 }
 
 // train_rvq (src/RVQ.jl:86-127): one k-means per stage on the running residual (Clustering.kmeans with
-// kmeans++ seeding and Julia's RNG there; h sampled residual rows from the library's seeded stream here),
+// kmeans++ seeding and Julia's RNG there; kmeans++ on the residual rows here too -- seed_centers, h uniforms of the
+// library's seeded stream per stage, one stream for all stages and their repicks),
 // then Xr .-= C[i][:, B[:, i]] (:112).  C [m][h][d]; B1 [n][m] Int16 one-based; error = qerror(X, B, C) (:124).
 int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
                  uint64_t seed) {
