@@ -48,6 +48,7 @@ extern "C" {
 #define RQ_EUNSUPPORTED (-2) /* shape outside what the kernels cover (h>256, LUT > LDS, ...) */
 #define RQ_ENODEVICE (-3)   /* no gfx950 device visible */
 
+#define RQ_MAX_H16 32767   /* most codewords per codebook of the *_wide encodes: the largest value a one-based Int16 names */
 #define RQ_MAX_K 65536      /* largest k served by the candidate-buffer scan; larger k take the bulk path */
 
 const char *rq_version(void);              /* "rayuela-hip <ver> (gfx950) build <sha1 of the kernel sources, 12 hex digits>" */
@@ -384,6 +385,25 @@ int rq_encode_pq_i16(int16_t *codes1, const float *X, const float *C, int64_t n,
                      int h);
 int rq_encode_opq_i16(int16_t *codes1, const float *X, const float *R, const float *C, int64_t n,
                       int d, int m, int h);
+/* ---- more than 256 codewords per codebook: 16-bit codes.  The reference returns Matrix{Int16} from
+ * quantize_pq, quantize_opq and quantize_rvq so that a codebook may hold more than 256 entries (src/PQ.jl:45-47,
+ * src/RVQ.jl:60-62).  Every entry point above keeps refusing h > 256 (their codes are bytes); these accept 1 <= h <= RQ_MAX_H16.
+ * Same arithmetic, wider index: code = first index of the minimum over ALL k in [0, h) of v_k = (u_k > 0 ? u_k : 0),
+ * u_k = fl(fl(sa_k + sb) - 2 g_k), strict '<'; a NaN u_k becomes 0 through the clamp, a row of +Inf values gets index 0, a code
+ * is always < h.  h <= 256 returns exactly the codes of the u8 entry points (it runs their kernels and widens);
+ * rq_last_encode_kernel names "encode_h16_kernel" after a call that ran the streaming kernel.  Layouts of the u8 entry points:
+ * codes [n][m] int16, C the m [h][sub_i] blocks back to back, codebooks [m][h][d], counts [m][h] or NULL.  code_base: 0
+ * (zero-based) or 1 (Julia's one-based Matrix{Int16}), like id_base of the scans.  n <= 0: RQ_OK.  A NULL pointer, a bad
+ * code_base or d < m: RQ_EINVAL; h > RQ_MAX_H16 or m out of range (PQ / OPQ: 1..32, RVQ: 1..64): RQ_EUNSUPPORTED; on any error
+ * no output byte is written.  Wide codes are encoded, not scanned: the scan stays at h = 256 (deps/src/linscan_aqd.cpp:58,67). */
+/* quantize_pq with up to RQ_MAX_H16 codewords per sub-codebook (src/PQ.jl:18-48). */
+int rq_encode_pq_wide(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int code_base);
+/* quantize_opq with up to RQ_MAX_H16 codewords per sub-codebook (src/OPQ.jl:19-27). */
+int rq_encode_opq_wide(int16_t *codes, const float *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                       int code_base);
+/* quantize_rvq with up to RQ_MAX_H16 codewords per stage (src/RVQ.jl:18-66); counts and Xr_out as for rq_encode_rvq. */
+int rq_encode_rvq_wide(int16_t *codes, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int code_base,
+                       uint32_t *counts, float *Xr_out);
 /* ---- byte rows: quantize_pq / quantize_opq of UInt8 data without widening it on the host.
  * bvecs files (SIFT1B: bigann_base / learn / query) hold UInt8 vectors -- bvecs_read returns Matrix{UInt8},
  * src/xvecs_read.jl:14-52 -- and the reference converts them to Float32 on the host before it encodes them
@@ -456,6 +476,15 @@ int rq_dev_encode_pq_bytes(uint8_t *codes, const uint8_t *X, const float *C, int
 int rq_dev_encode_opq_bytes(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n,
                             int d, int m, int h, void *stream);
 int rq_dev_rotate_T_bytes(float *RX, const float *R, const uint8_t *X, int d, int64_t n, void *stream);
+/* Device-pointer forms of the *_wide entry points: zero-based int16 codes [n][m], everything on `stream` (norms pass, kernels,
+ * memsets and the stream's workspace).  quantize_pq (src/PQ.jl:18-48): */
+int rq_dev_encode_pq_wide(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, void *stream);
+/* quantize_opq (src/OPQ.jl:19-27): R'X into the stream's workspace, then the wide encode. */
+int rq_dev_encode_opq_wide(int16_t *codes, const float *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                           void *stream);
+/* quantize_rvq (src/RVQ.jl:18-66): Xr [n][d] holds X on entry and the final residual on return. */
+int rq_dev_encode_rvq_wide(int16_t *codes, float *Xr, const float *codebooks, int64_t n, int d, int m, int h,
+                           uint32_t *counts, void *stream);
 /* Per-query ADC look-up tables lut [nq][m][256] (deps/src/linscan_aqd.cpp:66-74); test aid. */
 int rq_dev_adc_lut(float *lut, const float *centers, const float *queries, int64_t nq, int m,
                    int subdim, void *stream);

@@ -73,6 +73,14 @@ function quantize_pq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, V::Bool=fal
   h    = size(C[1], 2)
   B    = _result(Int16, m, n)
   if V print("Encoding on $m codebooks with librayuela_hip... ") end
+  if h > 256      # more than 256 codewords per codebook: 16-bit codes all the way (src/PQ.jl:45-47), rq_encode_pq_wide
+    code_base = 1
+    _check(ccall((:rq_encode_pq_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+      B, X, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h), Cint(code_base)))
+    if V println("done") end
+    return B
+  end
   _check(ccall((:rq_encode_pq_i16, librayuela_hip), Cint,
     (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
     B, X, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
@@ -88,6 +96,13 @@ function quantize_opq(X::Matrix{Float32}, R::Matrix{Float32}, C::Vector{Matrix{F
   m    = length(C)
   h    = size(C[1], 2)
   B    = _result(Int16, m, n)
+  if h > 256      # rq_encode_opq_wide: up to 32767 codewords per codebook
+    code_base = 1
+    _check(ccall((:rq_encode_opq_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+      B, X, R, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h), Cint(code_base)))
+    return B
+  end
   _check(ccall((:rq_encode_opq_i16, librayuela_hip), Cint,
     (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
     B, X, R, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
@@ -139,9 +154,16 @@ function quantize_rvq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, V::Bool=fa
   h    = size(C[1], 2)
   B      = Matrix{Int16}(undef, m, n)
   counts = Matrix{UInt32}(undef, h, m)          # C view [m][h]
+  if h > 256      # rq_encode_rvq_wide: up to 32767 codewords per stage (src/RVQ.jl:60-62)
+    code_base = 1
+    _check(ccall((:rq_encode_rvq_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Ptr{UInt32}, Ptr{Cfloat}),
+      B, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(code_base), counts, C_NULL))
+  else
   _check(ccall((:rq_encode_rvq_i16, librayuela_hip), Cint,
     (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Ptr{UInt32}, Ptr{Cfloat}),
     B, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), counts, C_NULL))
+  end
   singletons = Vector{Matrix{Float32}}(undef, m)
   if any(counts .== 0)
     Xr = copy(X)

@@ -2,7 +2,7 @@
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32, _as_f32_or_u8, cat_codebooks
+from .utils import _as_f32, _as_f32_or_u8, cat_codebooks, check_wide_h
 
 
 def quantize_opq(X, R, C, V=False):
@@ -10,7 +10,7 @@ def quantize_opq(X, R, C, V=False):
 
     R : (d, d) float32, the memory image of Julia's d-by-d rotation (so R_numpy[i, k] == R_julia[k, i]).
     X : (n, d) float32, or (n, d) uint8 (bvecs data): the codes of X.astype(float32), rotated and encoded from the bytes.
-    Returns (n, m) int16 ONE-based codes.
+    Returns (n, m) int16 ONE-based codes.  256 < h <= 32767 (float32 X only) takes rq_encode_opq_wide.
     """
     X = _as_f32_or_u8(X, "X")
     R = _as_f32(R, "R")
@@ -19,12 +19,32 @@ def quantize_opq(X, R, C, V=False):
         raise ValueError("R must be %d x %d" % (d, d))
     m = len(C)
     h = np.asarray(C[0]).shape[0]
+    wide = check_wide_h(h, X)
     Cc = cat_codebooks(C)
     B = _lib.result_empty((n, m), np.int16)
     L = _lib.lib()
+    if wide:
+        _lib.check(L.rq_encode_opq_wide(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data, n, d, m, h, 1))
+        return B
     encode = L.rq_encode_opq_bytes_i16 if X.dtype == np.uint8 else L.rq_encode_opq_i16
     _lib.check(encode(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data, n, d, m, h))
     return B
+
+
+def quantize_opq_u16(X, R, C):
+    """Same encode for any 1 <= h <= 32767, returning zero-based codes viewed as uint16 (rq_encode_opq_wide, code_base 0)."""
+    X = _as_f32(X, "X")
+    R = _as_f32(R, "R")
+    n, d = X.shape
+    if R.shape != (d, d):
+        raise ValueError("R must be %d x %d" % (d, d))
+    m = len(C)
+    h = np.asarray(C[0]).shape[0]
+    check_wide_h(h)
+    Cc = cat_codebooks(C)
+    B = _lib.result_empty((n, m), np.int16)
+    _lib.check(_lib.lib().rq_encode_opq_wide(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data, n, d, m, h, 0))
+    return B.view(np.uint16)
 
 
 def rotate(R, X):

@@ -2,7 +2,7 @@
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32, _as_f32_or_u8, cat_codebooks
+from .utils import _as_f32, _as_f32_or_u8, cat_codebooks, check_wide_h
 
 
 def quantize_pq(X, C, V=False):
@@ -12,11 +12,13 @@ def quantize_pq(X, C, V=False):
         the codes of X.astype(float32), encoded from the bytes (rq_encode_pq_bytes_i16)
     C : list of m arrays (h, sub_i) float32 -- memory images of the sub_i-by-h codebooks
     Returns B : (n, m) int16, ONE-based codes (memory image of Julia's m-by-n Matrix{Int16}).
+    256 < h <= 32767 codewords per codebook (float32 X only) take rq_encode_pq_wide; the return type is the same.
     """
     X = _as_f32_or_u8(X, "X")
     n, d = X.shape
     m = len(C)
     h = np.asarray(C[0]).shape[0]
+    wide = check_wide_h(h, X)
     Cc = cat_codebooks(C)
     if Cc.size != h * d:
         raise ValueError("codebooks do not tile the %d dimensions of X" % d)
@@ -24,8 +26,11 @@ def quantize_pq(X, C, V=False):
         print("Encoding on %d codebooks with librayuela_hip... " % m, end="")
     B = _lib.result_empty((n, m), np.int16)
     L = _lib.lib()
-    encode = L.rq_encode_pq_bytes_i16 if X.dtype == np.uint8 else L.rq_encode_pq_i16
-    _lib.check(encode(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
+    if wide:
+        _lib.check(L.rq_encode_pq_wide(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h, 1))
+    else:
+        encode = L.rq_encode_pq_bytes_i16 if X.dtype == np.uint8 else L.rq_encode_pq_i16
+        _lib.check(encode(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
     if V:
         print("done")
     return B
@@ -44,6 +49,21 @@ def quantize_pq_u8(X, C):
     encode = L.rq_encode_pq_bytes if X.dtype == np.uint8 else L.rq_encode_pq
     _lib.check(encode(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h))
     return B
+
+
+def quantize_pq_u16(X, C):
+    """Same encode for any 1 <= h <= 32767, returning zero-based codes viewed as uint16 (rq_encode_pq_wide, code_base 0)."""
+    X = _as_f32(X, "X")
+    n, d = X.shape
+    m = len(C)
+    h = np.asarray(C[0]).shape[0]
+    check_wide_h(h)
+    Cc = cat_codebooks(C)
+    if Cc.size != h * d:
+        raise ValueError("codebooks do not tile the %d dimensions of X" % d)
+    B = _lib.result_empty((n, m), np.int16)
+    _lib.check(_lib.lib().rq_encode_pq_wide(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h, 0))
+    return B.view(np.uint16)
 
 
 def train_pq(X, m, h, niter=25, V=False, seed=0):

@@ -2,7 +2,7 @@
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32
+from .utils import _as_f32, check_wide_h
 
 
 def _stack_codebooks(C):
@@ -22,17 +22,25 @@ def quantize_rvq(X, C, V=False, rng=None):
     re-picks them with Clustering.repick_unused_centers driven by Julia's global RNG (:50-53), so those
     VALUES are RNG-specific there as well; here they are drawn with `rng` (numpy Generator) by the same
     rule (a data point sampled with probability proportional to its cost).
+    256 < h <= 32767 codewords per stage take rq_encode_rvq_wide; the return types are the same.
     """
+    if np.asarray(X).dtype == np.uint8:
+        check_wide_h(np.asarray(C[0]).shape[0], np.asarray(X))
     X = _as_f32(X, "X")
     n, d = X.shape
+    wide = check_wide_h(np.asarray(C[0]).shape[0])
     Cs = _stack_codebooks(C)
     m, h, d2 = Cs.shape
     if d2 != d:
         raise ValueError("codebooks are %d-dimensional, data is %d-dimensional" % (d2, d))
     B = np.empty((n, m), dtype=np.int16)
     counts = np.zeros((m, h), dtype=np.uint32)
-    _lib.check(_lib.lib().rq_encode_rvq_i16(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h,
-                                            counts.ctypes.data, None))
+    if wide:
+        _lib.check(_lib.lib().rq_encode_rvq_wide(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h, 1,
+                                                 counts.ctypes.data, None))
+    else:
+        _lib.check(_lib.lib().rq_encode_rvq_i16(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h,
+                                                counts.ctypes.data, None))
     singletons = [None] * m
     if (counts == 0).any():
         rng = np.random.default_rng(0) if rng is None else rng
@@ -62,6 +70,23 @@ def quantize_rvq_u8(X, C, with_extras=False):
     Xr = np.empty((n, d), dtype=np.float32) if with_extras else None
     _lib.check(_lib.lib().rq_encode_rvq(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h,
                                         counts.ctypes.data, None if Xr is None else Xr.ctypes.data))
+    return (B, counts, Xr) if with_extras else B
+
+
+def quantize_rvq_u16(X, C, with_extras=False):
+    """Zero-based codes viewed as uint16 for any 1 <= h <= 32767 (rq_encode_rvq_wide, code_base 0); with_extras ->
+    (codes, counts, final residual)."""
+    X = _as_f32(X, "X")
+    n, d = X.shape
+    check_wide_h(np.asarray(C[0]).shape[0])
+    Cs = _stack_codebooks(C)
+    m, h, _ = Cs.shape
+    B = np.empty((n, m), dtype=np.int16)
+    counts = np.zeros((m, h), dtype=np.uint32)
+    Xr = np.empty((n, d), dtype=np.float32) if with_extras else None
+    _lib.check(_lib.lib().rq_encode_rvq_wide(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h, 0,
+                                             counts.ctypes.data, None if Xr is None else Xr.ctypes.data))
+    B = B.view(np.uint16)
     return (B, counts, Xr) if with_extras else B
 
 

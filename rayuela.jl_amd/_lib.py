@@ -55,6 +55,12 @@ SIGNATURES = {
     "rq_encode_opq_bytes": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_encode_pq_bytes_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_encode_opq_bytes_i16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_encode_pq_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_encode_opq_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_encode_rvq_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "rq_dev_encode_pq_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_dev_encode_opq_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_dev_encode_rvq_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_encode_rvq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_encode_rvq_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "rq_train_rvq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_uint64]),

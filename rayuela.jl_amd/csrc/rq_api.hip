@@ -831,8 +831,11 @@ static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, co
 // esz = 4: X is f32 [n][d].  esz = 1: X is uint8 [n][d] (bvecs: src/xvecs_read.jl:14-52; the reference widens on the host,
 // src/read_datasets.jl:148-167) -- the SAME rows per chunk, so an upload is 32 MiB where f32 moves 128 MiB, and the chunk
 // is rotated / encoded from bytes (encode_bytes_launch; its f32 scratch is bounded by the chunk).
+// wide_base >= 0 (f32 rows only): the *_wide entry points -- the same pipeline with 16-bit codes on the device
+// (encode_h16_launch per chunk), codes1 = zero-based codes + wide_base, the addition on the device.
 static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int esz, const float *R, const float *C,
-                            int64_t n, int d, int m, int h, double *t_h2d, double *t_tail) {
+                            int64_t n, int d, int m, int h, double *t_h2d, double *t_tail, int wide_base = -1) {
+  const bool wide = wide_base >= 0;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;   // host-pointer calls on one device run one at a time (shared scratch + streams)
@@ -842,7 +845,7 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int 
   RQ_TRY(dX[0].alloc((size_t)chunk * d * esz));
   if (piped) RQ_TRY(dX[1].alloc((size_t)chunk * d * esz));
   RQ_TRY(dC.alloc((size_t)h * d * 4));
-  RQ_TRY(dcodes.alloc((size_t)n * m));
+  if (!wide) RQ_TRY(dcodes.alloc((size_t)n * m));
   if (codes1) RQ_TRY(d16.alloc((size_t)n * m * 2));
   RQ_HIP(hipMemcpy(dC.p, C, (size_t)h * d * 4, hipMemcpyHostToDevice));
   if (R) {
@@ -881,12 +884,14 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int 
         RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX[b].as<float>(), d, nr, di.num_cu, cs));
         src = dRX.as<float>();
       }
-      RQ_TRY(encode_launch(dcodes.as<uint8_t>() + (size_t)r0 * m, src, dC.as<float>(), nr, d, m, h, di.num_cu, cs));
+      if (wide) RQ_TRY(encode_h16_launch(d16.as<int16_t>() + (size_t)r0 * m, src, dC.as<float>(), nr, d, m, h, di.num_cu, cs));
+      else RQ_TRY(encode_launch(dcodes.as<uint8_t>() + (size_t)r0 * m, src, dC.as<float>(), nr, d, m, h, di.num_cu, cs));
     }
     RQ_HIP(hipEventRecord(ev.done[b], cs));
   }
   Timer t2;
-  if (codes1) RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), n * m, cs));
+  if (wide) RQ_TRY(add_base_codes_launch(d16.as<int16_t>(), n * m, wide_base, cs));
+  else if (codes1) RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), n * m, cs));
   RQ_HIP(hipStreamSynchronize(cs));
   if (codes1) RQ_HIP(hipMemcpy(codes1, d16.p, (size_t)n * m * 2, hipMemcpyDeviceToHost));
   else RQ_HIP(hipMemcpy(codes, dcodes.p, (size_t)n * m, hipMemcpyDeviceToHost));
@@ -895,7 +900,7 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int 
 }
 
 static int host_encode(uint8_t *codes, int16_t *codes1, const void *X, const float *R, const float *C,
-                       int64_t n, int d, int m, int h, int esz = 4) {
+                       int64_t n, int d, int m, int h, int esz = 4, int wide_base = -1) {
   Timer tt;
   g_t_h2d = g_t_kernel = g_t_d2h = 0;
   if (n <= 0) return RQ_OK;
@@ -919,7 +924,7 @@ static int host_encode(uint8_t *codes, int16_t *codes1, const void *X, const flo
         if (hipSetDevice(devs[i]) != hipSuccess) { rc[i] = RQ_ENODEVICE; msg[i] = "hipSetDevice failed"; return; }
         rc[i] = encode_host_rows(codes ? codes + (size_t)r0 * m : nullptr, codes1 ? codes1 + (size_t)r0 * m : nullptr,
                                  static_cast<const unsigned char *>(X) + (size_t)r0 * d * esz, esz, R, C, cnt, d, m, h, &h2d[i],
-                                 &tail[i]);
+                                 &tail[i], wide_base);
         if (rc[i] != RQ_OK) msg[i] = g_err;
       });
     }
@@ -935,7 +940,7 @@ static int host_encode(uint8_t *codes, int16_t *codes1, const void *X, const flo
   SavedDevice saved;
   if (nd == 1) RQ_HIP(hipSetDevice(devs[0]));
   double h2d = 0, tail = 0;
-  RQ_TRY(encode_host_rows(codes, codes1, X, esz, R, C, n, d, m, h, &h2d, &tail));
+  RQ_TRY(encode_host_rows(codes, codes1, X, esz, R, C, n, d, m, h, &h2d, &tail, wide_base));
   g_t_h2d = h2d;
   g_t_d2h = tail;          // what is left after the last upload: last chunk's kernels + the one copy back
   g_t_total = tt.ms();
@@ -1516,13 +1521,16 @@ int rq_dev_encode_rvq(uint8_t *codes, float *Xr, const float *codebooks, int64_t
   return rvq_encode_launch(codes, Xr, (uint8_t *)tmp, counts, codebooks, n, d, m, h, di.num_cu, (hipStream_t)stream);
 }
 
+// wide_base >= 0: rq_encode_rvq_wide (its arguments are checked by the caller) -- 16-bit codes on the device, codes1 = zero-based
+// codes + wide_base
 static int host_encode_rvq(uint8_t *codes, int16_t *codes1, const float *X, const float *C, int64_t n, int d, int m,
-                           int h, uint32_t *counts, float *Xr_out) {
+                           int h, uint32_t *counts, float *Xr_out, int wide_base = -1) {
   Timer tt;
+  const bool wide = wide_base >= 0;
   g_t_h2d = g_t_kernel = g_t_d2h = 0;
   if (counts) memset(counts, 0, (size_t)m * h * sizeof(uint32_t));
   if (n <= 0) return RQ_OK;
-  if (d < 1 || m < 1 || h < 1 || h > 256) return fail(RQ_EINVAL, "rvq: bad shape d=%d m=%d h=%d", d, m, h);
+  if (d < 1 || m < 1 || h < 1 || (!wide && h > 256)) return fail(RQ_EINVAL, "rvq: bad shape d=%d m=%d h=%d", d, m, h);
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;   // host-pointer calls on one device run one at a time (shared scratch + streams)
@@ -1530,8 +1538,8 @@ static int host_encode_rvq(uint8_t *codes, int16_t *codes1, const float *X, cons
   DevBuf dX, dC, dcodes, dstage, d16, dcnt;
   RQ_TRY(dX.alloc((size_t)chunk * d * 4));
   RQ_TRY(dC.alloc((size_t)m * h * d * 4));
-  RQ_TRY(dcodes.alloc((size_t)chunk * m));
-  RQ_TRY(dstage.alloc((size_t)chunk));
+  if (!wide) RQ_TRY(dcodes.alloc((size_t)chunk * m));
+  RQ_TRY(dstage.alloc((size_t)chunk * (wide ? 2 : 1)));
   RQ_TRY(dcnt.alloc((size_t)m * h * 4));
   if (codes1) RQ_TRY(d16.alloc((size_t)chunk * m * 2));
   RQ_HIP(hipMemcpy(dC.p, C, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
@@ -1542,10 +1550,16 @@ static int host_encode_rvq(uint8_t *codes, int16_t *codes1, const float *X, cons
     RQ_HIP(hipMemcpy(dX.p, X + (size_t)r0 * d, (size_t)nr * d * 4, hipMemcpyHostToDevice));
     g_t_h2d += t1.ms();
     Timer t2;
-    RQ_TRY(rvq_encode_launch(dcodes.as<uint8_t>(), dX.as<float>(), dstage.as<uint8_t>(),
-                             counts ? dcnt.as<unsigned int>() : nullptr, dC.as<float>(), nr, d, m, h, di.num_cu,
-                             nullptr));
-    if (codes1) RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), nr * m, nullptr));
+    if (wide) {
+      RQ_TRY(rvq_h16_encode_launch(d16.as<int16_t>(), dX.as<float>(), dstage.as<int16_t>(),
+                                   counts ? dcnt.as<unsigned int>() : nullptr, dC.as<float>(), nr, d, m, h, di.num_cu, nullptr));
+      RQ_TRY(add_base_codes_launch(d16.as<int16_t>(), nr * m, wide_base, nullptr));
+    } else {
+      RQ_TRY(rvq_encode_launch(dcodes.as<uint8_t>(), dX.as<float>(), dstage.as<uint8_t>(),
+                               counts ? dcnt.as<unsigned int>() : nullptr, dC.as<float>(), nr, d, m, h, di.num_cu,
+                               nullptr));
+      if (codes1) RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), nr * m, nullptr));
+    }
     RQ_HIP(hipDeviceSynchronize());
     g_t_kernel += t2.ms();
     Timer t3;
@@ -1571,6 +1585,63 @@ int rq_encode_rvq(uint8_t *codes, const float *X, const float *codebooks, int64_
 int rq_encode_rvq_i16(int16_t *codes1, const float *X, const float *codebooks, int64_t n, int d, int m, int h,
                       uint32_t *counts, float *Xr_out) {
   return host_encode_rvq(nullptr, codes1, X, codebooks, n, d, m, h, counts, Xr_out);
+}
+
+// ---- more than 256 codewords per codebook: 16-bit codes (rq_encode_h16.hip).  Every argument is checked before any work. ------
+static int wide_check(const char *who, bool null_arg, int64_t n, int d, int m, int h, int mmax, bool pq, int code_base) {
+  (void)n;
+  if (null_arg) return fail(RQ_EINVAL, "%s: NULL argument", who);
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  if (m < 1 || m > mmax) return fail(RQ_EUNSUPPORTED, "%s covers 1 <= m <= %d; got m=%d", who, mmax, m);
+  if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "%s emits Int16 codes: 1 <= h <= %d; got h=%d", who, RQ_MAX_H16, h);
+  if (d < 1 || (pq && d < m)) return fail(RQ_EINVAL, "%s: d=%d < m=%d", who, d, m);
+  return RQ_OK;
+}
+
+int rq_encode_pq_wide(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int code_base) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_encode_pq_wide", !codes || !X || !C, n, d, m, h, 32, true, code_base));
+  return host_encode(nullptr, codes, X, nullptr, C, n, d, m, h, 4, code_base);
+}
+int rq_encode_opq_wide(int16_t *codes, const float *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                       int code_base) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_encode_opq_wide", !codes || !X || !R || !C, n, d, m, h, 32, true, code_base));
+  return host_encode(nullptr, codes, X, R, C, n, d, m, h, 4, code_base);
+}
+int rq_encode_rvq_wide(int16_t *codes, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int code_base,
+                       uint32_t *counts, float *Xr_out) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_encode_rvq_wide", !codes || !X || !codebooks, n, d, m, h, 64, false, code_base));
+  return host_encode_rvq(nullptr, codes, X, codebooks, n, d, m, h, counts, Xr_out, code_base);
+}
+int rq_dev_encode_pq_wide(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, void *stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_dev_encode_pq_wide", !codes || !X || !C, n, d, m, h, 32, true, 0));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  return encode_h16_launch(codes, X, C, n, d, m, h, di.num_cu, (hipStream_t)stream);
+}
+int rq_dev_encode_opq_wide(int16_t *codes, const float *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                           void *stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_dev_encode_opq_wide", !codes || !X || !R || !C, n, d, m, h, 32, true, 0));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  void *tmp = nullptr;
+  RQ_TRY(workspace(WS_TMP, (size_t)n * d * 4, &tmp, (hipStream_t)stream));
+  RQ_TRY(rotate_launch((float *)tmp, R, X, d, n, di.num_cu, (hipStream_t)stream));
+  return encode_h16_launch(codes, (const float *)tmp, C, n, d, m, h, di.num_cu, (hipStream_t)stream);
+}
+int rq_dev_encode_rvq_wide(int16_t *codes, float *Xr, const float *codebooks, int64_t n, int d, int m, int h,
+                           uint32_t *counts, void *stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_dev_encode_rvq_wide", !codes || !Xr || !codebooks, n, d, m, h, 64, false, 0));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  void *tmp = nullptr;
+  RQ_TRY(workspace(WS_TMP, (size_t)n * 2, &tmp, (hipStream_t)stream));
+  return rvq_h16_encode_launch(codes, Xr, (int16_t *)tmp, counts, codebooks, n, d, m, h, di.num_cu, (hipStream_t)stream);
 }
 
 int rq_dev_adc_lut(float *lut, const float *centers, const float *queries, int64_t nq, int m, int subdim,

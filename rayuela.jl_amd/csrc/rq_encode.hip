@@ -1274,9 +1274,12 @@ const char *last_encode_kernel_name() {
     case 4: return "encode_wide_kernel";
     case 5: return "encode_pq_filter_kernel";
     case 6: return "encode_pq_filter_bytes_kernel";
+    case 7: return "encode_h16_kernel";
     default: return "";
   }
 }
+
+void note_encode_h16_kernel() { g_last_encode_kernel = 7; }   // rq_encode_h16.hip ran its kernel for the calling thread
 
 int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h,
                   int num_cu, hipStream_t stream, float *dbg_w) {

@@ -56,7 +56,7 @@ int aux_streams(hipStream_t *compute, hipStream_t *transfer);
 // counters of the big-base scan: 8 XCDs x SCAN_PACE_SLOTS x {chunks done, members}
 constexpr int SCAN_PACE_SLOTS = 64;
 constexpr size_t WS_COUNTER_BYTES = 256 + 8 * SCAN_PACE_SLOTS * 8;
-enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_CHAIN = 16, WS_ORDER_STATE = 17, WS_SLOTS = 18 };
+enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_CHAIN = 16, WS_ORDER_STATE = 17, WS_H16_SA = 18, WS_H16_CODES = 19, WS_SLOTS = 20 };
 
 // Per-device launch lock (recursive): held while a call looks up scratch, resets the work counter and
 // launches, so two host threads cannot interleave those sequences on one device.
@@ -187,6 +187,14 @@ int rvq_encode_launch(uint8_t *codes, float *Xr, uint8_t *stage_codes, unsigned 
 int rotate_launch(float *RX, const float *R, const float *X, int d, int64_t n, int num_cu,
                   hipStream_t stream);
 int widen_codes_launch(int16_t *out1, const uint8_t *codes, int64_t nelem, hipStream_t stream);
+// ---- more than 256 codewords per codebook, 16-bit codes (rq_encode_h16.hip) --------------------------
+// codes [n][m] int16 ZERO-based, 1 <= h <= RQ_MAX_H16; h <= 256 runs encode_launch and widens.  Scratch: WS_H16_SA, WS_H16_CODES.
+int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                      hipStream_t stream);
+int rvq_h16_encode_launch(int16_t *codes, float *Xr, int16_t *stage_codes, unsigned int *counts, const float *C, int64_t n,
+                          int d, int m, int h, int num_cu, hipStream_t stream);
+int add_base_codes_launch(int16_t *codes, int64_t nelem, int base, hipStream_t stream);   // codes += base, in place
+void note_encode_h16_kernel();          // rq_last_encode_kernel: "encode_h16_kernel"
 // ---- byte rows (rq_encode_bytes.hip): X uint8 [n][d] on the device, any alignment ------------------------------------------
 int64_t bytes_chunk_rows(int d);      // rows per upload chunk / per piece of f32 scratch: max(32768, 2^25 / d)
 int widen_bytes_launch(float *out, const uint8_t *in, size_t nelem, hipStream_t stream);

@@ -95,6 +95,39 @@ def encode_rvq(Xr, C, out=None, want_counts=False):
     return (out, counts) if want_counts else out
 
 
+def encode_pq_wide(X, Ccat, m, h, out=None):
+    """quantize_pq with 1 <= h <= 32767 codewords per sub-codebook on resident tensors (rq_dev_encode_pq_wide).
+    Returns codes (n, m) int16, zero-based."""
+    n, d = X.shape
+    out = torch.empty((n, m), dtype=torch.int16, device=X.device) if out is None else out
+    _lib.check(_lib.lib().rq_dev_encode_pq_wide(_chk(out, torch.int16, "codes"), _chk(X, torch.float32, "X"),
+                                                _chk(Ccat, torch.float32, "C"), n, d, m, h, _stream()))
+    return out
+
+
+def encode_opq_wide(X, R, Ccat, m, h, out=None):
+    """quantize_opq with 1 <= h <= 32767 codewords per sub-codebook (rq_dev_encode_opq_wide): codes (n, m) int16, zero-based."""
+    n, d = X.shape
+    out = torch.empty((n, m), dtype=torch.int16, device=X.device) if out is None else out
+    _lib.check(_lib.lib().rq_dev_encode_opq_wide(_chk(out, torch.int16, "codes"), _chk(X, torch.float32, "X"),
+                                                 _chk(R, torch.float32, "R"), _chk(Ccat, torch.float32, "C"),
+                                                 n, d, m, h, _stream()))
+    return out
+
+
+def encode_rvq_wide(Xr, C, out=None, want_counts=False):
+    """quantize_rvq with 1 <= h <= 32767 codewords per stage (rq_dev_encode_rvq_wide).  Xr (n, d) holds X and is OVERWRITTEN
+    with the final residual; C (m, h, d).  Returns codes (n, m) int16 zero-based [, counts (m, h) int32]."""
+    n, d = Xr.shape
+    m, h, _ = C.shape
+    out = torch.empty((n, m), dtype=torch.int16, device=Xr.device) if out is None else out
+    counts = torch.zeros((m, h), dtype=torch.int32, device=Xr.device) if want_counts else None
+    _lib.check(_lib.lib().rq_dev_encode_rvq_wide(_chk(out, torch.int16, "codes"), _chk(Xr, torch.float32, "Xr"),
+                                                 _chk(C, torch.float32, "C"), n, d, m, h,
+                                                 None if counts is None else counts.data_ptr(), _stream()))
+    return (out, counts) if want_counts else out
+
+
 def encode_rvq_beam(X, C, H, nsplits=1, out=None, want_extras=False):
     """Beam-search residual encoding (src/CompetitiveQ.jl:75-135 `encode`) on resident tensors: X (n, d) is only read, C (m, h, d),
     1 <= H <= min(32, h).  Returns codes (n, m) uint8 zero-based [, cost (n,), final residual (n, d)]."""

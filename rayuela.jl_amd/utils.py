@@ -41,6 +41,20 @@ def encode_chunk_rows(d):
     return max(32768, (1 << 25) // int(d))
 
 
+MAX_H16 = 32767          # RQ_MAX_H16: the largest value a one-based Int16 can name
+
+
+def check_wide_h(h, X=None):
+    """True when h codewords per codebook take the *_wide (16-bit) entry points.  Raises ValueError -- before the library
+    is touched -- for an h no Int16 code can name, and for byte rows with h > 256 (the byte kernels cover h <= 256)."""
+    h = int(h)
+    if h > MAX_H16:
+        raise ValueError("h = %d codewords per codebook: Int16 codes name at most %d (the Int16 limit)" % (h, MAX_H16))
+    if h > 256 and X is not None and X.dtype == np.uint8:
+        raise ValueError("byte rows (uint8 X) cover h <= 256; got h = %d -- pass X.astype(float32)" % h)
+    return h > 256
+
+
 def cat_codebooks(C):
     """Vector{Matrix} -> one flat buffer: concatenation of the m [h][sub_i] blocks
     (== cat(C..., dims=3) of src/Linscan.jl:22 when all sub_i are equal)."""
