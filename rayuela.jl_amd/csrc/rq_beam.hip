@@ -390,6 +390,7 @@ int beam_encode_dev(uint8_t *codes, float *Xr_out, float *cost_out, const float 
                 H, d, m, per_v, BEAM_SCRATCH_BYTES);
   int64_t chunk = (n + nsplits - 1) / nsplits;
   chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t)(BEAM_SCRATCH_BYTES / per_v)));
+  chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, LAUNCH_MAX_THREADS / 64 / H));   // beam_expand_kernel: a wavefront per beam row
   void *wsa = nullptr, *wb = nullptr;
   RQ_TRY(workspace(WS_ICM_BIN, (size_t)m * h * 4, &wsa, s));
   RQ_TRY(workspace(WS_ICM_U, (size_t)chunk * per_v + 64, &wb, s));

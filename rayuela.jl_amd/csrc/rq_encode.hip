@@ -1491,16 +1491,21 @@ __global__ __launch_bounds__(256) void rvq_residual_scalar_kernel(float *Xr, con
 int rvq_residual_launch(float *Xr, const float *Ci, const uint8_t *stage_codes, uint8_t *codes, unsigned int *cnt,
                         int64_t n, int d, int m, int stage, hipStream_t stream) {
   if (n <= 0) return RQ_OK;
-  if ((d & 3) == 0 && (((uintptr_t)Xr | (uintptr_t)Ci) & 15) == 0) {
-    const int64_t total = n * (d >> 2);
-    hipLaunchKernelGGL(rvq_residual_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, Xr, Ci,
-                       stage_codes, codes, cnt, n, d, m, stage);
-  } else {
-    const int64_t total = n * d;
-    hipLaunchKernelGGL(rvq_residual_scalar_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, Xr,
-                       Ci, stage_codes, codes, cnt, n, d, m, stage);
+  // one thread per float4 (or float) of Xr, in row slices of at most LAUNCH_MAX_THREADS threads
+  const bool vec = (d & 3) == 0 && (((uintptr_t)Xr | (uintptr_t)Ci) & 15) == 0;
+  const int per_row = vec ? d >> 2 : d;
+  const int64_t rows = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per_row);
+  for (int64_t r0 = 0; r0 < n; r0 += rows) {
+    const int64_t nr = std::min(rows, n - r0);
+    const dim3 grid((uint32_t)((nr * per_row + 255) / 256));
+    if (vec)
+      hipLaunchKernelGGL(rvq_residual_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
+                         codes + (size_t)r0 * m, cnt, nr, d, m, stage);
+    else
+      hipLaunchKernelGGL(rvq_residual_scalar_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
+                         codes + (size_t)r0 * m, cnt, nr, d, m, stage);
+    RQ_HIP(hipGetLastError());
   }
-  RQ_HIP(hipGetLastError());
   return RQ_OK;
 }
 
@@ -1518,9 +1523,12 @@ int rvq_encode_launch(uint8_t *codes, float *Xr, uint8_t *stage_codes, unsigned 
 
 int widen_codes_launch(int16_t *out1, const uint8_t *codes, int64_t nelem, hipStream_t stream) {
   if (nelem <= 0) return RQ_OK;
-  hipLaunchKernelGGL(widen_codes_kernel, dim3((uint32_t)((nelem + 255) / 256)), dim3(256), 0, stream, out1,
-                     codes, (size_t)nelem);
-  RQ_HIP(hipGetLastError());
+  for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
+    const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
+    hipLaunchKernelGGL(widen_codes_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, out1 + e0,
+                       codes + e0, (size_t)ne);
+    RQ_HIP(hipGetLastError());
+  }
   return RQ_OK;
 }
 

@@ -247,9 +247,12 @@ __global__ void add_base_codes_kernel(int16_t *codes, size_t nelem, int base) {
 
 int add_base_codes_launch(int16_t *codes, int64_t nelem, int base, hipStream_t stream) {
   if (nelem <= 0 || base == 0) return RQ_OK;
-  hipLaunchKernelGGL(add_base_codes_kernel, dim3((uint32_t)((nelem + 255) / 256)), dim3(256), 0, stream, codes, (size_t)nelem,
-                     base);
-  RQ_HIP(hipGetLastError());
+  for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
+    const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
+    hipLaunchKernelGGL(add_base_codes_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, codes + e0, (size_t)ne,
+                       base);
+    RQ_HIP(hipGetLastError());
+  }
   return RQ_OK;
 }
 
@@ -265,9 +268,13 @@ int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n,
     void *tmp = nullptr;
     RQ_TRY(workspace(WS_H16_CODES, (size_t)n * m, &tmp, stream));
     RQ_TRY(encode_launch((uint8_t *)tmp, X, C, n, d, m, h, num_cu, stream));
-    hipLaunchKernelGGL(widen0_codes_kernel, dim3((uint32_t)(((size_t)n * m + 255) / 256)), dim3(256), 0, stream, codes,
-                       (const uint8_t *)tmp, (size_t)n * m);
-    RQ_HIP(hipGetLastError());
+    const int64_t nelem = n * m;
+    for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
+      const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
+      hipLaunchKernelGGL(widen0_codes_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, codes + e0,
+                         (const uint8_t *)tmp + e0, (size_t)ne);
+      RQ_HIP(hipGetLastError());
+    }
     return RQ_OK;
   }
   H16Params p;
@@ -336,16 +343,21 @@ int rvq_h16_encode_launch(int16_t *codes, float *Xr, int16_t *stage_codes, unsig
     const float *Ci = C + (size_t)i * h * d;
     unsigned int *cnt = counts ? counts + (size_t)i * h : nullptr;
     RQ_TRY(encode_h16_launch(stage_codes, Xr, Ci, n, d, 1, h, num_cu, stream));
-    if ((d & 3) == 0 && (((uintptr_t)Xr | (uintptr_t)Ci) & 15) == 0) {
-      const int64_t total = n * (d >> 2);
-      hipLaunchKernelGGL(rvq16_residual_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, Xr, Ci,
-                         stage_codes, codes, cnt, n, d, m, i);
-    } else {
-      const int64_t total = n * d;
-      hipLaunchKernelGGL(rvq16_residual_scalar_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, Xr, Ci,
-                         stage_codes, codes, cnt, n, d, m, i);
+    // one thread per float4 (or float) of Xr, in row slices of at most LAUNCH_MAX_THREADS threads (rvq_residual_launch)
+    const bool vec = (d & 3) == 0 && (((uintptr_t)Xr | (uintptr_t)Ci) & 15) == 0;
+    const int per_row = vec ? d >> 2 : d;
+    const int64_t rows = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per_row);
+    for (int64_t r0 = 0; r0 < n; r0 += rows) {
+      const int64_t nr = std::min(rows, n - r0);
+      const dim3 grid((uint32_t)((nr * per_row + 255) / 256));
+      if (vec)
+        hipLaunchKernelGGL(rvq16_residual_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
+                           codes + (size_t)r0 * m, cnt, nr, d, m, i);
+      else
+        hipLaunchKernelGGL(rvq16_residual_scalar_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
+                           codes + (size_t)r0 * m, cnt, nr, d, m, i);
+      RQ_HIP(hipGetLastError());
     }
-    RQ_HIP(hipGetLastError());
   }
   return RQ_OK;
 }

@@ -68,15 +68,22 @@ int ervq_residual_launch(float *dst, const float *src, const float *Cj, const ui
                          uint8_t *codes_out, unsigned int *counts, int64_t n, int d, int m, int stage, hipStream_t stream) {
   if (n <= 0) return RQ_OK;
   const bool vec = (d & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)Cj) & 15) == 0;
-  const int64_t blocks = (n * (vec ? d >> 2 : d) + 255) / 256;
-  if (blocks > 0x7fffffffll) return fail(RQ_EUNSUPPORTED, "ervq: n=%lld d=%d is too large", (long long)n, d);
-  if (vec)
-    hipLaunchKernelGGL(ervq_residual_kernel<4>, dim3((uint32_t)blocks), dim3(256), 0, stream, dst, src, Cj, codes_in, in_stride,
-                       codes_out, counts, n, d, m, stage);
-  else
-    hipLaunchKernelGGL(ervq_residual_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, stream, dst, src, Cj, codes_in, in_stride,
-                       codes_out, counts, n, d, m, stage);
-  RQ_HIP(hipGetLastError());
+  // one thread per float4 (or float), in row slices of at most LAUNCH_MAX_THREADS threads: any n
+  const int per_row = vec ? d >> 2 : d;
+  const int64_t rows = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per_row);
+  for (int64_t r0 = 0; r0 < n; r0 += rows) {
+    const int64_t nr = std::min(rows, n - r0);
+    const dim3 grid((uint32_t)((nr * per_row + 255) / 256));
+    float *ds = dst + (size_t)r0 * d;
+    const float *ss = src + (size_t)r0 * d;
+    const uint8_t *ci = codes_in + (size_t)r0 * in_stride;
+    uint8_t *co = codes_out ? codes_out + (size_t)r0 * m : nullptr;
+    if (vec)
+      hipLaunchKernelGGL(ervq_residual_kernel<4>, grid, dim3(256), 0, stream, ds, ss, Cj, ci, in_stride, co, counts, nr, d, m, stage);
+    else
+      hipLaunchKernelGGL(ervq_residual_kernel<1>, grid, dim3(256), 0, stream, ds, ss, Cj, ci, in_stride, co, counts, nr, d, m, stage);
+    RQ_HIP(hipGetLastError());
+  }
   return RQ_OK;
 }
 
@@ -253,9 +260,12 @@ extern "C" int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, 
   float *Xd = dX.as<float>(), *W = dW.as<float>(), *Cd = dC.as<float>();
   uint8_t *codes = dcodes.as<uint8_t>(), *stage = dstage.as<uint8_t>();
   double *objd = dobj.as<double>();
-  hipLaunchKernelGGL(ervq_narrow_kernel, dim3((uint32_t)(((size_t)n * m + 255) / 256)), dim3(256), 0, s, codes,
-                     d16.as<int16_t>(), (size_t)n * m);
-  RQ_HIP(hipGetLastError());
+  for (int64_t e0 = 0; e0 < n * m; e0 += LAUNCH_MAX_THREADS) {
+    const int64_t ne = std::min(LAUNCH_MAX_THREADS, n * m - e0);
+    hipLaunchKernelGGL(ervq_narrow_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, s, codes + e0,
+                       d16.as<int16_t>() + e0, (size_t)ne);
+    RQ_HIP(hipGetLastError());
+  }
   clk.mark(EV_OTHER);
   // E of the caller's codes and codebooks, and its error
   RQ_HIP(hipMemcpyAsync(W, Xd, xb, hipMemcpyDeviceToDevice, s));

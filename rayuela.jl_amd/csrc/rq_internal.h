@@ -44,6 +44,10 @@ int device_info(DeviceInfo *out);
 
 // Grow-only scratch owned by the library, keyed by (current device, stream): launches on different
 // streams never share a buffer.  At most 8 distinct streams per device (release_workspaces() resets).
+// A dispatch carries fewer than 2^32 work-items per grid dimension (a 32-bit field of the dispatch packet): a launch of more
+// does not fail, it wraps and runs the remainder only.  Launches of one thread or one wavefront per element of an n-sized
+// array therefore go in slices of at most LAUNCH_MAX_THREADS work-items (tests/test_gpu_large_offsets.py runs them past it).
+constexpr int64_t LAUNCH_MAX_THREADS = 1ll << 31;
 int workspace(int slot, size_t bytes, void **ptr, hipStream_t stream);
 int release_workspaces();
 int release_stream_workspace(hipStream_t stream);

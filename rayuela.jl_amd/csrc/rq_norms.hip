@@ -119,9 +119,15 @@ int norms_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *
 
 int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
   if (n <= 0) return RQ_OK;
-  const int64_t waves = (n + NR - 1) / NR;
-  hipLaunchKernelGGL(aq_norms_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, norms, codes, C, n, d, m, h);
-  RQ_HIP(hipGetLastError());
+  // one wavefront per NR rows, in row slices of at most LAUNCH_MAX_THREADS threads (2^27 rows)
+  const int64_t rows = LAUNCH_MAX_THREADS / 64 * NR;
+  for (int64_t r0 = 0; r0 < n; r0 += rows) {
+    const int64_t nr = std::min(rows, n - r0);
+    const int64_t waves = (nr + NR - 1) / NR;
+    hipLaunchKernelGGL(aq_norms_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, norms + r0,
+                       codes + (size_t)r0 * m, C, nr, d, m, h);
+    RQ_HIP(hipGetLastError());
+  }
   return RQ_OK;
 }
 
