@@ -395,7 +395,8 @@ int rq_encode_opq_i16(int16_t *codes1, const float *X, const float *R, const flo
  * codes [n][m] int16, C the m [h][sub_i] blocks back to back, codebooks [m][h][d], counts [m][h] or NULL.  code_base: 0
  * (zero-based) or 1 (Julia's one-based Matrix{Int16}), like id_base of the scans.  n <= 0: RQ_OK.  A NULL pointer, a bad
  * code_base or d < m: RQ_EINVAL; h > RQ_MAX_H16 or m out of range (PQ / OPQ: 1..32, RVQ: 1..64): RQ_EUNSUPPORTED; on any error
- * no output byte is written.  Wide codes are encoded, not scanned: the scan stays at h = 256 (deps/src/linscan_aqd.cpp:58,67). */
+ * no output byte is written.  Wide codes are scanned by the *_wide scans below (rq_linscan_pq_wide, rq_dev_linscan_wide); the byte
+ * scans stay at h = 256 (deps/src/linscan_aqd.cpp:58,67). */
 /* quantize_pq with up to RQ_MAX_H16 codewords per sub-codebook (src/PQ.jl:18-48). */
 int rq_encode_pq_wide(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int code_base);
 /* quantize_opq with up to RQ_MAX_H16 codewords per sub-codebook (src/OPQ.jl:19-27). */
@@ -404,6 +405,28 @@ int rq_encode_opq_wide(int16_t *codes, const float *X, const float *R, const flo
 /* quantize_rvq with up to RQ_MAX_H16 codewords per stage (src/RVQ.jl:18-66); counts and Xr_out as for rq_encode_rvq. */
 int rq_encode_rvq_wide(int16_t *codes, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int code_base,
                        uint32_t *counts, float *Xr_out);
+/* ---- the ADC scan over 16-bit codes: linscan_pq / linscan_opq for 1 <= h <= RQ_MAX_H16.  The reference has no
+ * such scan (deps/src/linscan_aqd.cpp:58,67 hard-wire 256 entries per table); this is its arithmetic with `256` replaced by h:
+ * T[k][r] = sum_s (c[(k h + r) sub + s] - q[k sub + s])^2 in sequential f32 (deps/src/linscan_aqd.cpp:66-74), row distance
+ * ((T[0][b0] + T[1][b1]) + ...) + T[m-1][b_{m-1}] (:78-87), answer: the k smallest (dist, id) pairs in lexicographic order (:91-97),
+ * exact for every 1 <= k <= n -- at h = 256 bit for bit the answer of the byte scans.  One path for every k: a packed key per row
+ * and query, then the select / sort chain of the bulk top-k (rq_dev_linscan), in query batches inside the same 2 GiB of scratch
+ * per device and stream (8 n + 16 k bytes per query, plus the tables); a single query that needs more fails with the
+ * out-of-memory error (above about 2.1e8 rows).  The non-finite contract above holds unchanged.  codes [n][m] int16, centers
+ * [m][h][d/m], 1 <= m <= 32, d % m == 0, 1 <= k <= n < 2^31.  code_base: 0 (zero-based) or 1 (Julia's Matrix{Int16}), as in the
+ * wide encodes.  A code outside [0, h) (after code_base): the host entries validate the codes on the device before any output is
+ * written and return RQ_EINVAL naming the first bad row (the reference's InexactError of convert(Matrix{UInt8}, B .- 1),
+ * src/Linscan.jl:35); the device entry never makes such a row a neighbour (its key is KEY_MAX for every query, the table index is
+ * clamped).  nq <= 0: RQ_OK.  A NULL pointer, a bad code_base or id_base, d % m != 0, k outside [1, n], n >= 2^31: RQ_EINVAL; h
+ * outside [1, RQ_MAX_H16] or m outside [1, 32]: RQ_EUNSUPPORTED; on any error no output byte is written.  With several devices in
+ * RAYUELA_HIP_DEVICES the host entries use the first.  rq_last_scan_kernel names the distance kernel:
+ * "adc_keys_h16_kernel<4, true>" (queries per gather, table in LDS). */
+/* linscan_pq over 16-bit codes (src/Linscan.jl:5-37; deps/src/linscan_aqd.cpp:66-97 with h entries per table). */
+int rq_linscan_pq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *centers, const float *queries,
+                       int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base);
+/* linscan_opq over 16-bit codes (src/Linscan.jl:93-115): queries are rotated by R' on the device first. */
+int rq_linscan_opq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *centers, const float *queries,
+                        const float *R, int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base);
 /* ---- byte rows: quantize_pq / quantize_opq of UInt8 data without widening it on the host.
  * bvecs files (SIFT1B: bigann_base / learn / query) hold UInt8 vectors -- bvecs_read returns Matrix{UInt8},
  * src/xvecs_read.jl:14-52 -- and the reference converts them to Float32 on the host before it encodes them
@@ -500,6 +523,22 @@ int rq_dev_adc_lut(float *lut, const float *centers, const float *queries, int64
 int rq_dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *codes,
                    const float *centers, const float *queries, int64_t n, int64_t nq, int m,
                    int d, int k, uint32_t id_offset, int id_base, void *stream);
+/* The ADC scan + exact top-k over one resident shard of n rows of ZERO-based int16 codes (deps/src/linscan_aqd.cpp:66-97 with h
+ * entries per table; see rq_linscan_pq_wide).  dists / ids / keys, id_offset and id_base exactly as for rq_dev_linscan, so shards
+ * merge through rq_dev_merge_topk unchanged.  codes 2-byte aligned (rows are loaded with the widest load the row pitch 2 m and
+ * the pointer allow), centers and queries 4-byte aligned (16 for vector loads of the codebook rows).  Everything runs on
+ * `stream`. */
+int rq_dev_linscan_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *centers,
+                        const float *queries, int64_t n, int64_t nq, int m, int h, int d, int k,
+                        uint32_t id_offset, int id_base, void *stream);
+/* Per-query ADC look-up tables lut [nq][m][h] of centers [m][h][subdim] (deps/src/linscan_aqd.cpp:66-74 with h entries per
+ * table); test aid: the table's bits can be pinned apart from the scan. */
+int rq_dev_adc_lut_wide(float *lut, const float *centers, const float *queries, int64_t nq, int m, int h, int subdim,
+                        void *stream);
+/* Host-only: where rq_dev_linscan_wide keeps the table of m * h entries (no reference counterpart; the reference's table is a
+ * heap array, deps/src/linscan_aqd.cpp:58).  out[0] queries per gather (4, 2 or 1), out[1] 1: the table of a query group is in
+ * LDS, 0: gathered from global memory, out[2] queries per group, out[3] LDS bytes.  cap >= 4. */
+int rq_scan_wide_plan(int m, int h, int *out, int cap);
 /* Bank-aware row order of a resident base (round 4, csrc/rq_order.hip).  No reference counterpart: the reference scans
  * rows in arrival order (deps/src/linscan_aqd.cpp:78-89); the result of the scan -- the k smallest (dist, id) pairs, :91-97
  * -- does not depend on the order rows are visited in, so this is a data-layout choice in HBM, invisible in the answer.

@@ -305,6 +305,21 @@ function linscan_pq(B::Matrix{UInt8}, X::Matrix{Cfloat}, C::Vector{Matrix{Cfloat
 end
 
 function linscan_pq(B::Matrix{T}, X::Matrix{Cfloat}, C::Vector{Matrix{Cfloat}}, b::Int, k::Int=10000) where T <: Integer
+  h = size(C[1], 2)
+  if h > 256      # 16-bit codes (quantize_pq at h > 256): rq_linscan_pq_wide; `b` is accepted and not interpreted
+    m, n  = size(B)
+    d, nq = size(X)
+    B16   = convert(Matrix{Int16}, B)            # one-based, as quantize_pq returns them: code_base = 1
+    dists = _result(Cfloat, k, nq)
+    res   = _result(Cuint,  k, nq)
+    code_base = 1
+    id_base   = 1
+    _check(ccall((:rq_linscan_pq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Cuint}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int64, Cint, Cint, Cint, Cint, Cint, Cint),
+      dists, res, B16, cat(C..., dims=3), X, Int64(n), Int64(nq), Cint(m), Cint(h), Cint(d), Cint(k), Cint(code_base),
+      Cint(id_base)))
+    return dists, res
+  end
   B_uint8 = convert(Matrix{UInt8}, B .- 1)      # src/Linscan.jl:35
   return linscan_pq(B_uint8, X, C, b, k)
 end
@@ -326,6 +341,22 @@ end
 
 function linscan_opq(B::Matrix{T}, X::Matrix{Cfloat}, C::Vector{Matrix{Cfloat}}, b::Int,
                      R::Matrix{Cfloat}, k::Int=10000) where T <: Integer
+  h = size(C[1], 2)
+  if h > 256      # 16-bit codes (quantize_opq at h > 256): rq_linscan_opq_wide; `b` is accepted and not interpreted
+    m, n  = size(B)
+    d, nq = size(X)
+    B16   = convert(Matrix{Int16}, B)
+    dists = _result(Cfloat, k, nq)
+    res   = _result(Cuint,  k, nq)
+    code_base = 1
+    id_base   = 1
+    _check(ccall((:rq_linscan_opq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Cuint}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int64, Cint, Cint, Cint, Cint, Cint,
+       Cint),
+      dists, res, B16, cat(C..., dims=3), X, R, Int64(n), Int64(nq), Cint(m), Cint(h), Cint(d), Cint(k), Cint(code_base),
+      Cint(id_base)))
+    return dists, res
+  end
   B_uint8 = convert(Matrix{UInt8}, B .- 1)
   return linscan_opq(B_uint8, X, C, b, R, k)
 end

@@ -67,6 +67,75 @@ def linscan_opq(B, X, C, b, R, k=10000):
     return dists, idx
 
 
+def _codes_i16(B, h):
+    """(codes (n, m) int16, code_base): uint16 / int16 arrays hold zero-based codes (what quantize_*_u16 return), any other
+    integer dtype one-based codes (src/Linscan.jl:35 B .- 1)."""
+    B = np.asarray(B)
+    if B.ndim != 2:
+        raise ValueError("B must be an (n, m) matrix of codes")
+    if not np.issubdtype(B.dtype, np.integer):
+        raise TypeError("B must be an integer array")
+    base = 0 if B.dtype in (np.uint16, np.int16) else 1
+    wide = B.astype(np.int64)
+    if wide.min(initial=base) < base or wide.max(initial=base) > h - 1 + base:
+        raise OverflowError("InexactError: a %s-based code outside %d..%d" % ("zero" if base == 0 else "one", base, h - 1 + base))
+    return np.ascontiguousarray(wide.astype(np.int16)), base
+
+
+def _centers_wide(C, m, d):
+    from .utils import check_wide_h
+    arr = np.stack([_as_f32(c, "C[i]") for c in C])
+    if arr.ndim != 3 or arr.shape[0] != m or arr.shape[2] != d // m:
+        raise ValueError("linscan needs m codebooks of shape (h, d/m); got %s" % (arr.shape,))
+    check_wide_h(arr.shape[1])
+    return np.ascontiguousarray(arr)
+
+
+def _linscan_u16(B, X, C, R, k):
+    X = _as_f32(X, "X")
+    nq, d = X.shape
+    m = len(C)
+    if m < 1 or m > 32:
+        raise ValueError("the scan over 16-bit codes covers 1 <= m <= 32 codebooks; got %d" % m)
+    if d % m:
+        raise ValueError("InexactError: Cint(d/m) with d=%d m=%d (src/Linscan.jl:23)" % (d, m))
+    cen = _centers_wide(C, m, d)
+    h = cen.shape[1]
+    Bi, base = _codes_i16(B, h)
+    n = Bi.shape[0]
+    if Bi.shape[1] != m:
+        raise ValueError("B has %d columns for %d codebooks" % (Bi.shape[1], m))
+    if k < 1 or k > n:
+        raise ValueError("k=%d must be in [1, n=%d]" % (k, n))
+    dists = _lib.result_empty((nq, k), np.float32)     # every element is written by the library
+    idx = _lib.result_empty((nq, k), np.uint32)
+    if R is None:
+        _lib.check(_lib.lib().rq_linscan_pq_wide(dists.ctypes.data, idx.ctypes.data, Bi.ctypes.data, cen.ctypes.data,
+                                                 X.ctypes.data, n, nq, m, h, d, k, base, 1))
+    else:
+        R = _as_f32(R, "R")
+        if R.shape != (d, d):
+            raise ValueError("R must be (d, d)")
+        _lib.check(_lib.lib().rq_linscan_opq_wide(dists.ctypes.data, idx.ctypes.data, Bi.ctypes.data, cen.ctypes.data,
+                                                  X.ctypes.data, R.ctypes.data, n, nq, m, h, d, k, base, 1))
+    return dists, idx
+
+
+def linscan_pq_u16(B, X, C, k=10000):
+    """linscan_pq over 16-bit codes: any 1 <= h <= 32767 codewords per codebook (rq_linscan_pq_wide) -> dists, idx
+
+    B : (n, m) uint16 / int16 zero-based codes (what quantize_pq_u16 returns), or any other integer dtype holding ONE-based codes
+    X : (nq, d) float32 queries;  C : list of m (h, d/m) codebooks
+    Returns dists (nq, k) float32 ascending and idx (nq, k) uint32, ONE-based like linscan_pq: the k smallest (dist, id) pairs
+    of the reference's arithmetic (src/Linscan.jl:5-37, deps/src/linscan_aqd.cpp:66-97) with h entries per table."""
+    return _linscan_u16(B, X, C, None, k)
+
+
+def linscan_opq_u16(B, X, C, R, k=10000):
+    """linscan_opq over 16-bit codes (src/Linscan.jl:93-115; rq_linscan_opq_wide) == linscan_pq_u16(B, R'X, C, k)."""
+    return _linscan_u16(B, X, C, R, k)
+
+
 def _hcat(C, m, d):
     arr = np.concatenate([_as_f32(c, "C[i]") for c in C], axis=0)   # hcat(C...) == [m*h][d] in memory
     if arr.shape != (m * 256, d):

@@ -111,6 +111,11 @@ SIGNATURES = {
     "rq_dev_rotate_T_bytes": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
     "rq_dev_adc_lut": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "rq_dev_linscan": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _u32, _i32, _vp]),
+    "rq_linscan_pq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "rq_linscan_opq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "rq_dev_linscan_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _u32, _i32, _vp]),
+    "rq_dev_adc_lut_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_scan_wide_plan": (_i32, [_i32, _i32, _vp, _i32]),
     "rq_scan_row_width": (_i32, [_i32]),
     "rq_order_bytes": (_i64, [_i64, _i32]),
     "rq_order_plan": (_i32, [_i64, _i32, _vp, _i32]),
@@ -205,6 +210,15 @@ def scan_plan(n, nq, m, d, k, num_cu=256):
     p = dict(zip(keys, [int(x) for x in out]))
     p["bigk"], p["xcd"], p["bulk"] = p["flags"] & 1, (p["flags"] >> 1) & 1, (p["flags"] >> 2) & 1
     return p
+
+
+def scan_wide_plan(m, h):
+    """Where the scan over 16-bit codes keeps its table of m * h entries (host code only, rq_scan_wide_plan): dict of qpg (queries
+    per gather: 4, 2 or 1), in_lds (1: the table of a query group is in LDS, 0: gathered from global memory), qg (queries per
+    group) and lds_bytes."""
+    out = (C.c_int * 4)()
+    check(lib().rq_scan_wide_plan(m, h, C.cast(out, C.c_void_p), 4))
+    return dict(zip(("qpg", "in_lds", "qg", "lds_bytes"), [int(x) for x in out]))
 
 
 def order_cache_stats():

@@ -758,6 +758,57 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
   return RQ_OK;
 }
 
+// linscan_pq / linscan_opq over 16-bit codes on host pointers (rq_scan_h16.hip): the shape of host_linscan's bulk branch -- upload,
+// then bulk_fetch in query chunks.  The codes are validated (and made zero-based) on the device before any output is written.
+static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const int16_t *codes, const float *centers,
+                             const float *queries, const float *R, bool need_R, int64_t n, int64_t nq, int m, int h, int d,
+                             int k, int code_base, int id_base) {
+  Timer tt;
+  g_t_h2d = g_t_kernel = g_t_d2h = 0;
+  if (nq <= 0) return RQ_OK;
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  RQ_TRY(linscan_wide_check(who, !dists || !ids || !codes || !centers || !queries || (need_R && !R), n, m, h, d, k, 0, id_base));
+  SavedDevice saved;
+  {
+    int devs[64];
+    const int nd = env_devices(devs, 64);      // wide bases are not sharded: the first listed device scans
+    if (nd >= 1) RQ_HIP(hipSetDevice(devs[0]));
+  }
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  DevBuf dcodes, dcent, dq, dr, drq, dbad;
+  const size_t cb = (size_t)n * m * 2, ce = (size_t)m * h * (d / m) * 4, qb = (size_t)nq * d * 4;
+  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce)); RQ_TRY(dq.alloc(qb)); RQ_TRY(dbad.alloc(8));
+  Timer t1;
+  RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(dcent.p, centers, ce, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
+  if (R) {
+    RQ_TRY(dr.alloc((size_t)d * d * 4)); RQ_TRY(drq.alloc(qb));
+    RQ_HIP(hipMemcpy(dr.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
+  }
+  g_t_h2d = t1.ms();
+  RQ_TRY(prepare_codes_h16_launch(dcodes.as<int16_t>(), dbad.as<unsigned long long>(), n, m, h, code_base, nullptr));
+  unsigned long long first_bad = 0;
+  RQ_HIP(hipMemcpy(&first_bad, dbad.p, 8, hipMemcpyDeviceToHost));
+  if (first_bad != ~0ull)
+    return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d] (InexactError of src/Linscan.jl:35 convert(Matrix{UInt8}, B .- 1))",
+                who, first_bad, code_base, h - 1 + code_base);
+  const float *qdev = dq.as<float>();
+  if (R) {
+    RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, di.num_cu, nullptr));
+    qdev = drq.as<float>();
+  }
+  const int16_t *cdev = dcodes.as<int16_t>();
+  const float *cen = dcent.as<float>();
+  RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
+    return dev_linscan_wide(bd, bi, nullptr, cdev, cen, qdev + (size_t)q0 * d, n, nqc, m, h, d, k, 0, id_base, nullptr);
+  }));
+  g_t_total = tt.ms();
+  return RQ_OK;
+}
+
 // linscan_lsq / linscan_cq on host pointers (src/Linscan.jl:118-193): codebooks [m*h][d], h = 256
 static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, const float *queries,
                            const float *codebooks, const float *dbnorms, const float *R, int64_t n, int64_t nq,
@@ -1655,6 +1706,39 @@ int rq_dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *c
                    int id_base, void *stream) {
   return dev_linscan(dists, ids, keys, codes, centers, queries, n, nq, m, d, k, id_offset, id_base,
                      (hipStream_t)stream);
+}
+
+// ---- the ADC scan over 16-bit codes (rq_scan_h16.hip) ---------------------------------------------------------------------------
+int rq_linscan_pq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *centers, const float *queries,
+                       int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base) {
+  return host_linscan_wide("rq_linscan_pq_wide", dists, ids, codes, centers, queries, nullptr, false, n, nq, m, h, d, k, code_base,
+                           id_base);
+}
+int rq_linscan_opq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *centers, const float *queries,
+                        const float *R, int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base) {
+  return host_linscan_wide("rq_linscan_opq_wide", dists, ids, codes, centers, queries, R, true, n, nq, m, h, d, k, code_base,
+                           id_base);
+}
+int rq_dev_linscan_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *centers,
+                        const float *queries, int64_t n, int64_t nq, int m, int h, int d, int k, uint32_t id_offset,
+                        int id_base, void *stream) {
+  return dev_linscan_wide(dists, ids, keys, codes, centers, queries, n, nq, m, h, d, k, id_offset, id_base, (hipStream_t)stream);
+}
+int rq_dev_adc_lut_wide(float *lut, const float *centers, const float *queries, int64_t nq, int m, int h, int subdim,
+                        void *stream) {
+  if (nq <= 0) return RQ_OK;
+  if (!lut || !centers || !queries) return fail(RQ_EINVAL, "rq_dev_adc_lut_wide: NULL argument");
+  if (m < 1 || m > 32) return fail(RQ_EUNSUPPORTED, "rq_dev_adc_lut_wide covers 1 <= m <= 32; got m=%d", m);
+  if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "rq_dev_adc_lut_wide: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
+  if (subdim < 1) return fail(RQ_EINVAL, "rq_dev_adc_lut_wide: subdim=%d < 1", subdim);
+  return lut_h16_launch(lut, centers, queries, nq, m, h, subdim, (hipStream_t)stream);
+}
+int rq_scan_wide_plan(int m, int h, int *out, int cap) {
+  if (!out || cap < 4) return fail(RQ_EINVAL, "rq_scan_wide_plan: out needs 4 ints");
+  if (m < 1 || m > 32) return fail(RQ_EUNSUPPORTED, "rq_scan_wide_plan covers 1 <= m <= 32; got m=%d", m);
+  if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "rq_scan_wide_plan: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
+  scan_h16_plan(m, h, out);
+  return RQ_OK;
 }
 
 int rq_scan_row_width(int m) { return scan_padded_m(m); }

@@ -26,7 +26,6 @@ constexpr int BK_T = 256;                          // threads of the select / co
 constexpr uint32_t BK_ITEMS = 16;                  // keys per thread of a sort tile
 constexpr uint32_t BK_TILE = BK_T * BK_ITEMS;      // keys per sort tile
 constexpr uint32_t BK_SPAN = BK_T * 8;             // select / compact: keys per block step (8 loads in flight per thread)
-constexpr int64_t BK_MAX_NB = 16384;               // queries per batch (grid.y)
 constexpr int BK_WINDOWS = 8;                      // 8-bit windows of a 64-bit key
 
 struct BulkQ {
@@ -37,25 +36,6 @@ struct BulkQ {
   uint32_t cnt;                  // kept keys (<= k)
   uint32_t nwin;                 // sort windows; the sorted keys end in buf[nwin & 1]
   uint32_t shift[BK_WINDOWS];
-};
-
-struct BulkSel {
-  const uint64_t *src;   // keys of query q: src[q * ld + i], i < cnt
-  size_t ld;
-  uint32_t cnt, k;
-  uint32_t span;         // keys per select / compact block
-  uint32_t tiles;        // sort tiles per query: ceil(k / BK_TILE)
-  BulkQ *st;             // [nb]
-  uint32_t *hist;        // [nb][256]
-  uint32_t *th;          // [nb][256][tiles] tile histograms, then scatter offsets
-  uint64_t *buf0, *buf1; // [nb][k] sort ping-pong
-};
-
-struct BulkOut {
-  float *dists;          // [nb][k] (already offset to the batch) or nullptr
-  uint32_t *ids;
-  uint64_t *keys;
-  uint32_t id_base;
 };
 
 __global__ __launch_bounds__(BK_T) void bulk_init_kernel(BulkSel s) {
@@ -381,13 +361,13 @@ __global__ __launch_bounds__(BULK_KEY_THREADS) void adc_bulk_keys_kernel(BulkKey
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // per-query scratch of the select + sort (the keys themselves excluded)
-static size_t sel_bytes_per_query(uint32_t k) {
+size_t sel_bytes_per_query(uint32_t k) {
   const size_t tiles = (k + BK_TILE - 1) / BK_TILE;
   return 2 * (size_t)k * 8 + tiles * 256 * 4 + 256 * 4 + sizeof(BulkQ) + 4 * 256;   // (+ alignment slack)
 }
 
 // lays the select + sort scratch of nb queries out from `at` (bytes advanced)
-static void sel_layout(BulkSel &s, unsigned char *&at, int64_t nb, uint32_t k) {
+void sel_layout(BulkSel &s, unsigned char *&at, int64_t nb, uint32_t k) {
   s.k = k;
   s.tiles = (k + BK_TILE - 1) / BK_TILE;
   s.buf0 = (uint64_t *)at; at += align256((size_t)nb * k * 8);
@@ -398,7 +378,7 @@ static void sel_layout(BulkSel &s, unsigned char *&at, int64_t nb, uint32_t k) {
 }
 
 // blocks per query of the select / compact passes: ~4 per CU over the batch
-static void sel_grid(BulkSel &s, uint32_t cnt, int64_t nb, int num_cu, uint32_t *hx) {
+void sel_grid(BulkSel &s, uint32_t cnt, int64_t nb, int num_cu, uint32_t *hx) {
   s.cnt = cnt;
   const uint64_t want = std::max<uint64_t>(1, (uint64_t)(4 * num_cu + nb - 1) / (uint64_t)nb);
   const uint64_t steps = ((uint64_t)cnt + BK_SPAN - 1) / BK_SPAN;
@@ -408,7 +388,7 @@ static void sel_grid(BulkSel &s, uint32_t cnt, int64_t nb, int num_cu, uint32_t 
 }
 
 // steps 2-5 for nb queries whose keys are ready in s.src
-static int sel_run(const BulkSel &s, uint32_t hx, int64_t nb, const BulkOut &o, hipStream_t stream) {
+int sel_run(const BulkSel &s, uint32_t hx, int64_t nb, const BulkOut &o, hipStream_t stream) {
   const uint32_t ub = (uint32_t)nb;
   hipLaunchKernelGGL(bulk_init_kernel, dim3(ub), dim3(BK_T), 0, stream, s);
   for (int pass = 0; pass < 8; ++pass) {
@@ -428,7 +408,7 @@ static int sel_run(const BulkSel &s, uint32_t hx, int64_t nb, const BulkOut &o, 
 }
 
 // the usable part of the budget: workspace() allocates 1.25x the request
-static size_t bulk_usable() { return BULK_SCRATCH_BYTES / 5 * 4; }
+size_t bulk_usable() { return BULK_SCRATCH_BYTES / 5 * 4; }
 
 template <int M>
 static void bulk_key_grid(int64_t nb, int64_t n, int num_cu, uint32_t *gx, uint32_t *gy) {

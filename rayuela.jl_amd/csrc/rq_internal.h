@@ -167,8 +167,46 @@ int bulk_merge(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *
                int id_base, hipStream_t stream);
 // rq_scan_plan's view of a bulk call: queries per group, groups, grid of the distance kernel, queries per batch
 void bulk_plan(int64_t n, int64_t nq, int m, int k, int num_cu, int64_t *qg, int64_t *groups, int64_t *grid, int64_t *batch);
+// The select -> compact -> sort -> unpack chain of rq_bulk.hip (its steps 2-5) on keys that are ready in device memory: shared
+// with the scan over 16-bit codes (rq_scan_h16.hip), which writes its own keys and then runs exactly this chain.
+constexpr int64_t BK_MAX_NB = 16384;   // queries per batch (grid.y)
+struct BulkQ;                          // per-query select / sort state (rq_bulk.hip)
+struct BulkSel {
+  const uint64_t *src;   // keys of query q: src[q * ld + i], i < cnt
+  size_t ld;
+  uint32_t cnt, k;
+  uint32_t span;         // keys per select / compact block
+  uint32_t tiles;        // sort tiles per query: ceil(k / BK_TILE)
+  BulkQ *st;             // [nb]
+  uint32_t *hist;        // [nb][256]
+  uint32_t *th;          // [nb][256][tiles] tile histograms, then scatter offsets
+  uint64_t *buf0, *buf1; // [nb][k] sort ping-pong
+};
+struct BulkOut {
+  float *dists;          // [nb][k] (already offset to the batch) or nullptr
+  uint32_t *ids;
+  uint64_t *keys;
+  uint32_t id_base;
+};
+size_t bulk_usable();                          // the usable part of BULK_SCRATCH_BYTES (workspace() allocates 1.25x the request)
+size_t sel_bytes_per_query(uint32_t k);        // scratch of the chain per query, the keys themselves excluded
+void sel_layout(BulkSel &s, unsigned char *&at, int64_t nb, uint32_t k);             // lays that scratch out from `at`
+void sel_grid(BulkSel &s, uint32_t cnt, int64_t nb, int num_cu, uint32_t *hx);       // blocks per query of select / compact
+int sel_run(const BulkSel &s, uint32_t hx, int64_t nb, const BulkOut &o, hipStream_t stream);
 int merge_launch(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *keys_in, int64_t nq,
                  int P, int K, int id_base, hipStream_t stream);
+// ---- ADC scan over 16-bit codes (rq_scan_h16.hip): codes [n][m] int16 zero-based, centers [m][h][d/m] ----
+// every argument check of rq_dev_linscan_wide / rq_linscan_*_wide (`who` names the entry point); no device work
+int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, int d, int k, uint32_t id_offset, int id_base);
+int dev_linscan_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *centers,
+                     const float *queries, int64_t n, int64_t nq, int m, int h, int d, int k, uint32_t id_offset, int id_base,
+                     hipStream_t stream);
+int lut_h16_launch(float *lut, const float *centers, const float *queries, int64_t nq, int m, int h, int sub,
+                   hipStream_t stream);                   // plain [nq][m][h]
+// host entries: codes -= code_base in place; *first_bad (device) <- the first row with a code outside [0, h), else ~0
+int prepare_codes_h16_launch(int16_t *codes, unsigned long long *first_bad, int64_t n, int m, int h, int code_base,
+                             hipStream_t stream);
+void scan_h16_plan(int m, int h, int out[4]);             // rq_scan_wide_plan
 int lut_launch(float *lut, const float *centers, const float *queries, int64_t nq, int m, int sub,
                hipStream_t stream);
 int synth_codes_launch(uint8_t *codes, int64_t n, int m, uint64_t seed, int64_t row0, hipStream_t stream);

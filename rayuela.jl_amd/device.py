@@ -155,6 +155,16 @@ def adc_lut(centers, queries):
     return lut
 
 
+def adc_lut_wide(centers, queries):
+    """Per-query tables lut (nq, m, h) of centers (m, h, sub) with any 1 <= h <= 32767 (rq_dev_adc_lut_wide); test aid."""
+    m, h, sub = centers.shape
+    nq = queries.shape[0]
+    lut = torch.empty((nq, m, h), dtype=torch.float32, device=queries.device)
+    _lib.check(_lib.lib().rq_dev_adc_lut_wide(lut.data_ptr(), _chk(centers, torch.float32, "centers"),
+                                              _chk(queries, torch.float32, "queries"), nq, m, h, sub, _stream()))
+    return lut
+
+
 class OrderedBase:
     """A resident code matrix in bank-aware row order (rq_dev_order_rows): `codes` [n][row_width] uint8 and `perm` [n]
     int32 (position -> original row; None for a base too small to order) are views into ONE device buffer."""
@@ -231,6 +241,30 @@ def linscan(codes, centers, queries, k, id_offset=0, id_base=0, want_keys=False,
                                          _chk(queries, torch.float32, "queries"), n, nq, m, d, k,
                                          id_offset, id_base, _stream()))
     return dists, ids
+
+
+def linscan_wide(codes, centers, queries, k, id_offset=0, id_base=0, want_keys=False, out=None):
+    """Scan one resident shard of 16-bit codes (rq_dev_linscan_wide): codes (n, m) int16 zero-based, centers (m, h, d/m) with
+    1 <= h <= 32767.  Returns (dists, ids), or the packed sorted keys (nq, k) (int64 view of the uint64 keys) when want_keys."""
+    n, m = codes.shape
+    h = centers.shape[1]
+    nq, d = queries.shape
+    dev = queries.device
+    if want_keys:
+        dists = ids = None
+        keys = torch.empty((nq, k), dtype=torch.int64, device=dev) if out is None else out
+    elif out is None:
+        keys = None
+        dists = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    else:
+        keys = None
+        dists, ids = out
+    _lib.check(_lib.lib().rq_dev_linscan_wide(
+        None if dists is None else dists.data_ptr(), None if ids is None else ids.data_ptr(),
+        None if keys is None else keys.data_ptr(), _chk(codes, torch.int16, "codes"), _chk(centers, torch.float32, "centers"),
+        _chk(queries, torch.float32, "queries"), n, nq, m, h, d, k, id_offset, id_base, _stream()))
+    return keys if want_keys else (dists, ids)
 
 
 def linscan_aq(codes, codebooks, queries, k, dbnorms=None, id_offset=0, id_base=0, want_keys=False, out=None):
