@@ -4,7 +4,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -179,6 +178,18 @@ static int order_cache_of(hipStream_t stream, OrderCacheHost **h, uint64_t *orde
   return fail(RQ_EINVAL, "order cache: the stream has no workspace");
 }
 
+// Free every slot of one stream's scratch and hand the entry back (g_mu held; the stream's work is done).
+static void free_stream_ws(StreamWs &w) {
+  for (int s = 0; s < WS_SLOTS; ++s) {
+    if (w.ws[s]) (void)hipFree(w.ws[s]);
+    w.ws[s] = nullptr;
+    w.ws_bytes[s] = 0;
+  }
+  w.oc = OrderCacheHost();
+  w.used = false;
+  w.stream = nullptr;
+}
+
 // Free the scratch of one stream of the current device (called before the stream is destroyed).
 int release_stream_workspace(hipStream_t stream) {
   int dev = 0;
@@ -188,14 +199,7 @@ int release_stream_workspace(hipStream_t stream) {
   for (int i = 0; i < MAX_STREAM_WS; ++i) {
     if (!c.sw[i].used || c.sw[i].stream != stream) continue;
     RQ_HIP(hipStreamSynchronize(stream));
-    for (int s = 0; s < WS_SLOTS; ++s) {
-      if (c.sw[i].ws[s]) (void)hipFree(c.sw[i].ws[s]);
-      c.sw[i].ws[s] = nullptr;
-      c.sw[i].ws_bytes[s] = 0;
-    }
-    c.sw[i].oc = OrderCacheHost();
-    c.sw[i].used = false;
-    c.sw[i].stream = nullptr;
+    free_stream_ws(c.sw[i]);
   }
   return RQ_OK;
 }
@@ -208,16 +212,7 @@ int release_workspaces() {
   RQ_HIP(hipDeviceSynchronize());
   std::lock_guard<std::mutex> lk(g_mu);
   DevCtx &c = g_dev[dev];
-  for (int i = 0; i < MAX_STREAM_WS; ++i) {
-    for (int s = 0; s < WS_SLOTS; ++s) {
-      if (c.sw[i].ws[s]) (void)hipFree(c.sw[i].ws[s]);
-      c.sw[i].ws[s] = nullptr;
-      c.sw[i].ws_bytes[s] = 0;
-    }
-    c.sw[i].oc = OrderCacheHost();
-    c.sw[i].used = false;
-    c.sw[i].stream = nullptr;
-  }
+  for (int i = 0; i < MAX_STREAM_WS; ++i) free_stream_ws(c.sw[i]);
   for (auto &b : c.pool) (void)hipFree(b.p);
   c.pool.clear();
   c.pool_bytes = 0;
@@ -234,8 +229,8 @@ int release_workspaces() {
 // milliseconds).  Limits: HOST_PIN_MAX_MB (4096) handed out at any time -- beyond it rq_host_alloc returns NULL and
 // the shim uses an ordinary array -- and HOST_PIN_POOL_MB (1024) kept idle.
 struct HostPool {
-  struct Buf { void *p; size_t bytes; };
-  std::vector<Buf> idle, live;
+  struct Block { void *p; size_t bytes; };
+  std::vector<Block> idle, live;
   size_t idle_bytes = 0, live_bytes = 0;
 };
 static HostPool g_hp;
@@ -252,7 +247,7 @@ void *host_pool_alloc(size_t bytes) {
   for (size_t i = 0; i < g_hp.idle.size(); ++i)
     if (g_hp.idle[i].bytes >= want && g_hp.idle[i].bytes <= 2 * want &&
         (best < 0 || g_hp.idle[i].bytes < g_hp.idle[best].bytes)) best = (int)i;
-  HostPool::Buf b{nullptr, 0};
+  HostPool::Block b{nullptr, 0};
   if (best >= 0) {
     b = g_hp.idle[best];
     g_hp.idle_bytes -= b.bytes;
@@ -271,7 +266,7 @@ void host_pool_free(void *p) {
   int keep_mb = tuning("HOST_PIN_POOL_MB", 0);
   if (keep_mb <= 0) keep_mb = 1024;
   const size_t keep = (size_t)keep_mb << 20;
-  HostPool::Buf b{nullptr, 0};
+  HostPool::Block b{nullptr, 0};
   {
     std::lock_guard<std::mutex> lk(g_mu);
     for (size_t i = 0; i < g_hp.live.size(); ++i)
@@ -296,7 +291,7 @@ bool host_pool_owns(const void *p, size_t bytes) {
 }
 
 void host_pool_trim() {
-  std::vector<HostPool::Buf> drop;
+  std::vector<HostPool::Block> drop;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     drop.swap(g_hp.idle);
@@ -364,13 +359,6 @@ struct DevBuf {
     return RQ_OK;
   }
   template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-
-struct Timer {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  double ms() const {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
 };
 
 // ---- bank-aware row order of a resident base (rq_order.hip) ---------------------------------------------
@@ -585,7 +573,7 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
 // Scan `nq` resident queries and bring the [nq][k] results to host memory.  Large batches are scanned in
 // chunks of 4096 queries (one full round of work items) on a compute stream while a second stream copies
 // the previous chunk's results: 80 MB of results at k = 1000 cost 4.6-6 ms over PCIe into pageable memory,
-// against 7 ms of kernel.  scan(q0, nqc, stream) launches the scan of queries [q0, q0+nqc) into dd/di.
+// against 7 ms of kernel.  scan(d, i, q0, nqc, stream) launches the scan of queries [q0, q0+nqc) into d/i [nqc][k].
 template <class ScanFn>
 static int scan_and_fetch(float *dists, uint32_t *ids, float *dd, uint32_t *di, int64_t nq, int k, ScanFn scan) {
   const int64_t hc = std::max(256, tuning("HOST_CHUNK", 4096));
@@ -595,14 +583,14 @@ static int scan_and_fetch(float *dists, uint32_t *ids, float *dd, uint32_t *di, 
     // the caller's result arrays are page-locked buffers of the library (rq_host_alloc): the scan writes its answer
     // straight into them over PCIe -- one launch over all queries, no copy back
     Timer t2;
-    RQ_TRY(scan(0, nq, nullptr));
+    RQ_TRY(scan(dists, ids, 0, nq, nullptr));
     RQ_HIP(hipDeviceSynchronize());
     g_t_kernel = t2.ms();
     return RQ_OK;
   }
   if (chunk >= nq) {
     Timer t2;
-    RQ_TRY(scan(0, nq, nullptr));
+    RQ_TRY(scan(dd, di, 0, nq, nullptr));
     RQ_HIP(hipDeviceSynchronize());
     g_t_kernel = t2.ms();
     Timer t3;
@@ -634,7 +622,7 @@ static int scan_and_fetch(float *dists, uint32_t *ids, float *dd, uint32_t *di, 
   };
   for (int64_t q0 = 0; q0 < nq; q0 += chunk, ++c) {
     const int64_t nqc = std::min(chunk, nq - q0);
-    RQ_TRY(scan(q0, nqc, st.cs));
+    RQ_TRY(scan(dd + (size_t)q0 * k, di + (size_t)q0 * k, q0, nqc, st.cs));
     RQ_HIP(hipEventRecord(st.ev[c & 1], st.cs));
     if (prev_q0 >= 0) RQ_TRY(fetch(prev_q0, prev_n, st.ev[(c - 1) & 1]));   // overlaps with the scan just queued
     prev_q0 = q0; prev_n = nqc;
@@ -660,7 +648,7 @@ static bool use_direct_results(const float *dists, const uint32_t *ids, int64_t 
 }
 
 // k > RQ_MAX_K on host pointers (bulk path): the results travel through a device buffer of at most BULK_HOST_RESULT_BYTES,
-// one query chunk at a time, never nq * k * 8 bytes at once.  scan(dd, di, q0, nqc) scans queries [q0, q0 + nqc) into dd/di.
+// one query chunk at a time, never nq * k * 8 bytes at once.  scan(dd, di, q0, nqc, stream) scans queries [q0, q0 + nqc) into dd/di.
 template <class ScanFn>
 static int bulk_fetch(float *dists, uint32_t *ids, int64_t nq, int k, ScanFn scan) {
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(BULK_HOST_RESULT_BYTES / ((size_t)k * 8))));
@@ -671,7 +659,7 @@ static int bulk_fetch(float *dists, uint32_t *ids, int64_t nq, int k, ScanFn sca
   double d2h = 0;
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int64_t nqc = std::min(chunk, nq - q0);
-    RQ_TRY(scan(dd.as<float>(), di.as<uint32_t>(), q0, nqc));
+    RQ_TRY(scan(dd.as<float>(), di.as<uint32_t>(), q0, nqc, nullptr));
     RQ_HIP(hipDeviceSynchronize());
     Timer t3;
     RQ_HIP(hipMemcpy(dists + (size_t)q0 * k, dd.p, (size_t)nqc * k * 4, hipMemcpyDeviceToHost));
@@ -682,6 +670,41 @@ static int bulk_fetch(float *dists, uint32_t *ids, int64_t nq, int k, ScanFn sca
   g_t_d2h = d2h;
   return RQ_OK;
 }
+
+// The [nq][k] results of a host-pointer scan, by the path that suits them: the bulk path in query chunks (k > RQ_MAX_K, and
+// the scan over 16-bit codes at every k: `bulk`), one launch into the caller's page-locked arrays, or staged device buffers.
+// scan(d, i, q0, nqc, stream) scans queries [q0, q0 + nqc) into d/i [nqc][k] on `stream`.
+template <class ScanFn>
+static int deliver(float *dists, uint32_t *ids, int64_t nq, int k, ScanFn scan, bool bulk = false) {
+  if (bulk || k > RQ_MAX_K) return bulk_fetch(dists, ids, nq, k, scan);
+  // direct: the kernel's own stores land in the caller's arrays
+  if (use_direct_results(dists, ids, nq, k)) return scan_and_fetch(dists, ids, nullptr, nullptr, nq, k, scan);
+  DevBuf dd, di;
+  RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di.alloc((size_t)nq * k * 4));
+  return scan_and_fetch(dists, ids, dd.as<float>(), di.as<uint32_t>(), nq, k, scan);
+}
+
+// The queries of a host-pointer scan on the current device: uploaded, and rotated by R [d][d] when one is given.  The two
+// copies are added to the call's h2d bracket; the allocations and the rotation are not part of it.
+struct RQ_LOCAL DevQueries {
+  DevBuf dq, dr, drq;
+  const float *p = nullptr;      // [nq][d], what the scan reads
+  int stage(const float *queries, const float *R, int64_t nq, int d, int num_cu) {
+    const size_t qb = (size_t)nq * d * 4, rb = (size_t)d * d * 4;
+    RQ_TRY(dq.alloc(qb));
+    if (R) { RQ_TRY(dr.alloc(rb)); RQ_TRY(drq.alloc(qb)); }
+    Timer t1;
+    RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
+    if (R) RQ_HIP(hipMemcpy(dr.p, R, rb, hipMemcpyHostToDevice));
+    g_t_h2d += t1.ms();
+    p = dq.as<float>();
+    if (R) {
+      RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, num_cu, nullptr));
+      p = drq.as<float>();
+    }
+    return RQ_OK;
+  }
+};
 
 static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const float *centers,
                         const float *queries, const float *R, int64_t n, int64_t nq, int m, int d, int k,
@@ -708,28 +731,15 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;   // host-pointer calls on one device run one at a time (shared scratch + streams)
-  DevBuf dcodes, dcent, dq, dr, drq, dd, di_;
-  const size_t cb = (size_t)n * m, ce = (size_t)m * 256 * (d / m) * 4, qb = (size_t)nq * d * 4;
-  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce)); RQ_TRY(dq.alloc(qb));
-  const bool bulk = k > RQ_MAX_K;
-  const bool direct = !bulk && use_direct_results(dists, ids, nq, k);
-  if (!direct && !bulk) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
+  DevBuf dcodes, dcent;
+  DevQueries q;
+  const size_t cb = (size_t)n * m, ce = (size_t)m * 256 * (d / m) * 4;
+  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce));
   Timer t1;
   RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dcent.p, centers, ce, hipMemcpyHostToDevice));
-  RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
-  const float *qdev = dq.as<float>();
-  if (R) {
-    RQ_TRY(dr.alloc((size_t)d * d * 4)); RQ_TRY(drq.alloc(qb));
-    RQ_HIP(hipMemcpy(dr.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-  }
   g_t_h2d = t1.ms();
-  if (R) {
-    RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, di.num_cu, nullptr));
-    qdev = drq.as<float>();
-  }
-  float *ddp = direct ? dists : dd.as<float>();       // direct: the kernel's own stores land in the caller's arrays
-  uint32_t *dip = direct ? ids : di_.as<uint32_t>();
+  RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
   const uint8_t *cdev = dcodes.as<uint8_t>();
   const float *cen = dcent.as<float>();
   // the query chunks below scan the same base: order it once for the whole call (rows of a tiled width only -- other
@@ -742,24 +752,17 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
   }
   ScanBase sbase;
   sbase.perm = perm;
-  if (bulk) {
-    RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
-      return dev_linscan(bd, bi, nullptr, cdev, cen, qdev + (size_t)q0 * d, n, nqc, m, d, k, 0, id_base, nullptr, LUT_PQ, nullptr,
-                         &sbase);
-    }));
-    g_t_total = tt.ms();
-    return RQ_OK;
-  }
-  RQ_TRY(scan_and_fetch(dists, ids, direct ? nullptr : ddp, dip, nq, k, [&](int64_t q0, int64_t nqc, hipStream_t stream) {
-    return dev_linscan(ddp + (size_t)q0 * k, dip + (size_t)q0 * k, nullptr, cdev, cen, qdev + (size_t)q0 * d, n, nqc, m,
-                       d, k, 0, id_base, stream, LUT_PQ, nullptr, &sbase);
+  RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
+    return dev_linscan(dd, di_, nullptr, cdev, cen, q.p + (size_t)q0 * d, n, nqc, m, d, k, 0, id_base, stream, LUT_PQ, nullptr,
+                       &sbase);
   }));
   g_t_total = tt.ms();
   return RQ_OK;
 }
 
 // linscan_pq / linscan_opq over 16-bit codes on host pointers (rq_scan_h16.hip): the shape of host_linscan's bulk branch -- upload,
-// then bulk_fetch in query chunks.  The codes are validated (and made zero-based) on the device before any output is written.
+// then the bulk branch of deliver (query chunks) at every k.  The codes are validated (and made zero-based) on the device before
+// any output is written.
 static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const int16_t *codes, const float *centers,
                              const float *queries, const float *R, bool need_R, int64_t n, int64_t nq, int m, int h, int d,
                              int k, int code_base, int id_base) {
@@ -777,17 +780,13 @@ static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  DevBuf dcodes, dcent, dq, dr, drq, dbad;
-  const size_t cb = (size_t)n * m * 2, ce = (size_t)m * h * (d / m) * 4, qb = (size_t)nq * d * 4;
-  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce)); RQ_TRY(dq.alloc(qb)); RQ_TRY(dbad.alloc(8));
+  DevBuf dcodes, dcent, dbad;
+  DevQueries q;
+  const size_t cb = (size_t)n * m * 2, ce = (size_t)m * h * (d / m) * 4;
+  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce)); RQ_TRY(dbad.alloc(8));
   Timer t1;
   RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dcent.p, centers, ce, hipMemcpyHostToDevice));
-  RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
-  if (R) {
-    RQ_TRY(dr.alloc((size_t)d * d * 4)); RQ_TRY(drq.alloc(qb));
-    RQ_HIP(hipMemcpy(dr.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-  }
   g_t_h2d = t1.ms();
   RQ_TRY(prepare_codes_h16_launch(dcodes.as<int16_t>(), dbad.as<unsigned long long>(), n, m, h, code_base, nullptr));
   unsigned long long first_bad = 0;
@@ -795,16 +794,12 @@ static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const
   if (first_bad != ~0ull)
     return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d] (InexactError of src/Linscan.jl:35 convert(Matrix{UInt8}, B .- 1))",
                 who, first_bad, code_base, h - 1 + code_base);
-  const float *qdev = dq.as<float>();
-  if (R) {
-    RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, di.num_cu, nullptr));
-    qdev = drq.as<float>();
-  }
+  RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
   const int16_t *cdev = dcodes.as<int16_t>();
   const float *cen = dcent.as<float>();
-  RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
-    return dev_linscan_wide(bd, bi, nullptr, cdev, cen, qdev + (size_t)q0 * d, n, nqc, m, h, d, k, 0, id_base, nullptr);
-  }));
+  RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
+    return dev_linscan_wide(dd, di_, nullptr, cdev, cen, q.p + (size_t)q0 * d, n, nqc, m, h, d, k, 0, id_base, stream);
+  }, true));
   g_t_total = tt.ms();
   return RQ_OK;
 }
@@ -830,45 +825,22 @@ static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, co
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;   // host-pointer calls on one device run one at a time (shared scratch + streams)
-  DevBuf dcodes, dcb, dq, dn, dr, drq, dd, di_;
-  const size_t cb = (size_t)n * m, ce = (size_t)m * 256 * d * 4, qb = (size_t)nq * d * 4;
-  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcb.alloc(ce)); RQ_TRY(dq.alloc(qb));
-  const bool bulk = k > RQ_MAX_K;
-  const bool direct = !bulk && use_direct_results(dists, ids, nq, k);
-  if (!direct && !bulk) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
+  DevBuf dcodes, dcb, dn;
+  DevQueries q;
+  const size_t cb = (size_t)n * m, ce = (size_t)m * 256 * d * 4;
+  RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcb.alloc(ce));
+  if (dbnorms) RQ_TRY(dn.alloc((size_t)n * 4));
   Timer t1;
   RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dcb.p, codebooks, ce, hipMemcpyHostToDevice));
-  RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
-  if (dbnorms) {
-    RQ_TRY(dn.alloc((size_t)n * 4));
-    RQ_HIP(hipMemcpy(dn.p, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
-  }
-  const float *qdev = dq.as<float>();
-  if (R) {
-    RQ_TRY(dr.alloc((size_t)d * d * 4)); RQ_TRY(drq.alloc(qb));
-    RQ_HIP(hipMemcpy(dr.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-  }
+  if (dbnorms) RQ_HIP(hipMemcpy(dn.p, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
   g_t_h2d = t1.ms();
-  if (R) {
-    RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, di.num_cu, nullptr));
-    qdev = drq.as<float>();
-  }
-  float *ddp = direct ? dists : dd.as<float>();
-  uint32_t *dip = direct ? ids : di_.as<uint32_t>();
+  RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
   const uint8_t *cdev = dcodes.as<uint8_t>();
   const float *cbk = dcb.as<float>();
   const float *nrm = dbnorms ? dn.as<float>() : nullptr;
-  if (bulk) {
-    RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
-      return dev_linscan(bd, bi, nullptr, cdev, cbk, qdev + (size_t)q0 * d, n, nqc, m, d, k, 0, id_base, nullptr, lut_mode, nrm);
-    }));
-    g_t_total = tt.ms();
-    return RQ_OK;
-  }
-  RQ_TRY(scan_and_fetch(dists, ids, direct ? nullptr : ddp, dip, nq, k, [&](int64_t q0, int64_t nqc, hipStream_t stream) {
-    return dev_linscan(ddp + (size_t)q0 * k, dip + (size_t)q0 * k, nullptr, cdev, cbk, qdev + (size_t)q0 * d, n, nqc, m,
-                       d, k, 0, id_base, stream, lut_mode, nrm);
+  RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
+    return dev_linscan(dd, di_, nullptr, cdev, cbk, q.p + (size_t)q0 * d, n, nqc, m, d, k, 0, id_base, stream, lut_mode, nrm);
   }));
   g_t_total = tt.ms();
   return RQ_OK;
@@ -1283,44 +1255,15 @@ int rq_lsq_search(rq_lsq_index *handle, float *dists, uint32_t *ids, const float
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   const int d = ix->d;
-  DevBuf dq, dr, drq, dd, di_;
-  const size_t qb = (size_t)nq * d * 4;
-  RQ_TRY(dq.alloc(qb));
-  const bool bulk = k > RQ_MAX_K;
-  const bool direct = !bulk && use_direct_results(dists, ids, nq, k);
-  if (!direct && !bulk) { RQ_TRY(dd.alloc((size_t)nq * k * 4)); RQ_TRY(di_.alloc((size_t)nq * k * 4)); }
-  Timer t1;
-  RQ_HIP(hipMemcpy(dq.p, queries, qb, hipMemcpyHostToDevice));
-  const float *qdev = dq.as<float>();
-  if (R) {
-    RQ_TRY(dr.alloc((size_t)d * d * 4)); RQ_TRY(drq.alloc(qb));
-    RQ_HIP(hipMemcpy(dr.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-  }
-  g_t_h2d = t1.ms();
-  if (R) {
-    RQ_TRY(rotate_launch(drq.as<float>(), dr.as<float>(), dq.as<float>(), d, nq, di.num_cu, nullptr));
-    qdev = drq.as<float>();
-  }
-  if (bulk) {
-    ScanBase sb;
-    sb.padded = true;
-    sb.perm = ix->perm;
-    RQ_TRY(bulk_fetch(dists, ids, nq, k, [&](float *bd, uint32_t *bi, int64_t q0, int64_t nqc) {
-      return dev_linscan(bd, bi, nullptr, ix->perm ? ix->ocodes : ix->codes, ix->cb, qdev + (size_t)q0 * d, ix->n, nqc, ix->m, d,
-                         k, 0, id_base, nullptr, LUT_LSQ, ix->norms, &sb);
-    }));
-    g_t_total = tt.ms();
-    return RQ_OK;
-  }
-  float *ddp = direct ? dists : dd.as<float>();
-  uint32_t *dip = direct ? ids : di_.as<uint32_t>();
-  RQ_TRY(scan_and_fetch(dists, ids, direct ? nullptr : ddp, dip, nq, k, [&](int64_t q0, int64_t nqc, hipStream_t stream) {
-    ScanBase sb;
-    sb.padded = true;
-    sb.norm_prepared = ix->normb;
-    sb.perm = ix->perm;
-    return dev_linscan(ddp + (size_t)q0 * k, dip + (size_t)q0 * k, nullptr, ix->perm ? ix->ocodes : ix->codes, ix->cb, qdev + (size_t)q0 * d, ix->n, nqc,
-                       ix->m, d, k, 0, id_base, stream, LUT_LSQ, ix->norms, &sb);
+  DevQueries q;
+  RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
+  ScanBase sb;      // (the bulk path of dev_linscan branches off before it reads the norm buffer)
+  sb.padded = true;
+  sb.norm_prepared = ix->normb;
+  sb.perm = ix->perm;
+  RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
+    return dev_linscan(dd, di_, nullptr, ix->perm ? ix->ocodes : ix->codes, ix->cb, q.p + (size_t)q0 * d, ix->n, nqc, ix->m, d, k,
+                       0, id_base, stream, LUT_LSQ, ix->norms, &sb);
   }));
   g_t_total = tt.ms();
   return RQ_OK;
@@ -1425,9 +1368,7 @@ int rq_dataset_encode(rq_dataset *handle, uint8_t *codes, int16_t *codes1, const
   if (!ds || !C || (!codes && !codes1)) return fail(RQ_EINVAL, "rq_dataset_encode: bad arguments");
   if (m < 1 || h < 1 || ds->d < m) return fail(RQ_EINVAL, "bad shape d=%d m=%d h=%d", ds->d, m, h);
   Timer tt;
-  int cur = 0;
-  RQ_HIP(hipGetDevice(&cur));
-  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{cur};
+  SavedDevice saved;
   RQ_HIP(hipSetDevice(ds->device));
   DeviceInfo di;
   RQ_TRY(device_info(&di));

@@ -20,7 +20,6 @@
 
 #include <math.h>
 
-#include <chrono>
 #include <vector>
 
 namespace rq {
@@ -243,51 +242,9 @@ void chain_split(int d, int parts, int i, int *lo, int *hi) {
   *hi = *lo + per + (i < xtra ? 1 : 0);
 }
 
-#define CH_LAUNCH(...)                \
-  do {                                \
-    hipLaunchKernelGGL(__VA_ARGS__);  \
-    RQ_HIP(hipGetLastError());        \
-  } while (0)
-
 // phase clock of the host-pointer entries: milliseconds of the calling thread's last call
 enum { CP_UNARY, CP_TABLES, CP_VITERBI, CP_UPDATE, CP_ROTATION, CP_N };
 thread_local double g_chain_ms[CP_N] = {0};
-
-struct ChainClock {
-  bool on = false;
-  hipStream_t s;
-  hipEvent_t prev = nullptr;
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;
-  ChainClock(hipStream_t st, bool want) : s(st) {
-    if (want && hipEventCreate(&prev) == hipSuccess) {
-      (void)hipEventRecord(prev, s);
-      on = true;
-    }
-  }
-  // the work queued since the previous mark belongs to `phase`
-  void mark(int phase) {
-    if (!on) return;
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, s);
-    spans.push_back({phase, {prev, e}});
-    prev = e;
-  }
-  void collect() {
-    if (!on) return;
-    (void)hipStreamSynchronize(s);
-    for (auto &sp : spans) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, sp.second.first, sp.second.second) == hipSuccess) g_chain_ms[sp.first] += ms;
-    }
-  }
-  ~ChainClock() {
-    if (!on) return;
-    if (spans.empty()) (void)hipEventDestroy(prev);
-    else (void)hipEventDestroy(spans.front().second.first);
-    for (auto &sp : spans) (void)hipEventDestroy(sp.second.second);
-  }
-};
 
 void chain_clock_reset() {
   for (int q = 0; q < CP_N; ++q) g_chain_ms[q] = 0;
@@ -317,16 +274,9 @@ int chain_check_update(const void *C, const void *X, const void *codes, int64_t 
   return RQ_OK;
 }
 
-int host_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *who) {
-  for (int64_t e = 0; e < n * m; ++e)
-    if (codes[e] >= h)
-      return fail(RQ_EINVAL, "%s: code %d at [%lld][%lld] is >= h=%d", who, codes[e], (long long)(e / m), (long long)(e % m), h);
-  return RQ_OK;
-}
-
 // The device body of the encoder: arguments already checked.
 int chain_encode_dev(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int nsplits,
-                     hipStream_t s, ChainClock &clk) {
+                     hipStream_t s, PhaseClock &clk) {
   if (n <= 0) return RQ_OK;
   const int E = (h + 63) / 64, HS = 64 * E;
   const size_t tab_bytes = (size_t)(m - 1) * h * VT_B * 4, tba_bytes = (size_t)(m - 1) * h * HS * 4;
@@ -341,24 +291,24 @@ int chain_encode_dev(uint8_t *codes, const float *X, const float *C, int64_t n, 
   int *rng = (int *)(sa + sa_bytes / 4);
   if (m > 1) {
     RQ_HIP(hipMemsetAsync(Tab, 0, tab_bytes + tba_bytes, s));
-    CH_LAUNCH(chain_pair_kernel, dim3((m - 1) * h), dim3(256), 0, s, Tab, Tba, C, m, h, d, HS);
+    RQ_LAUNCH(chain_pair_kernel, dim3((m - 1) * h), dim3(256), 0, s, Tab, Tba, C, m, h, d, HS);
   }
   RQ_TRY(icm_sqnorm_launch(sa, C, m, h, d, s));
-  CH_LAUNCH(chain_range_kernel, dim3(m), dim3(256), 0, s, rng, C, h, d);
+  RQ_LAUNCH(chain_range_kernel, dim3(m), dim3(256), 0, s, rng, C, h, d);
   clk.mark(CP_TABLES);
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t nr = std::min(chunk, n - r0);
     RQ_TRY(icm_unary_launch(U, X + (size_t)r0 * d, C, sa, nr, d, m, h, HS, rng, s));
     clk.mark(CP_UNARY);
     if (m > 1)
-      CH_LAUNCH(chain_forward_kernel, dim3((unsigned)((nr + VT_ROWS - 1) / VT_ROWS)), dim3(256), 0, s, U,
+      RQ_LAUNCH(chain_forward_kernel, dim3((unsigned)((nr + VT_ROWS - 1) / VT_ROWS)), dim3(256), 0, s, U,
                 (const float *)Tab, nr, m, h, HS);
     const dim3 grid((unsigned)((nr + 3) / 4));
     uint8_t *out = codes + (size_t)r0 * m;
-    if (E == 1) CH_LAUNCH((chain_backtrace_kernel<1>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
-    else if (E == 2) CH_LAUNCH((chain_backtrace_kernel<2>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
-    else if (E == 3) CH_LAUNCH((chain_backtrace_kernel<3>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
-    else CH_LAUNCH((chain_backtrace_kernel<4>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
+    if (E == 1) RQ_LAUNCH((chain_backtrace_kernel<1>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
+    else if (E == 2) RQ_LAUNCH((chain_backtrace_kernel<2>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
+    else if (E == 3) RQ_LAUNCH((chain_backtrace_kernel<3>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
+    else RQ_LAUNCH((chain_backtrace_kernel<4>), grid, dim3(256), 0, s, out, (const float *)U, (const float *)Tba, nr, m, h, HS);
     clk.mark(CP_VITERBI);
   }
   return RQ_OK;
@@ -367,7 +317,7 @@ int chain_encode_dev(uint8_t *codes, const float *X, const float *C, int64_t n, 
 // C [m][h][d] f32 <- the chain update of (X, codes): arguments checked, codes in range.  The m-1 blocks are solved one
 // after the other (each through the blocked Cholesky of rq_lsq.hip on its own copy: adjacent blocks share a diagonal part).
 int chain_update_dev(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
-                     hipStream_t s, ChainClock &clk) {
+                     hipStream_t s, PhaseClock &clk) {
   const int mh = m * h, h2 = 2 * h;
   void *wa = nullptr, *wb = nullptr, *wc = nullptr;
   RQ_TRY(workspace(WS_LSQ_A, (size_t)mh * mh * 8, &wa, s));
@@ -388,10 +338,10 @@ int chain_update_dev(float *C, const float *X, const uint8_t *codes, int64_t n, 
     const int len = hi - lo;
     if (len <= 0) continue;
     const int64_t cnt = (int64_t)h2 * h2 + (int64_t)h2 * len;
-    CH_LAUNCH(chain_block_gather_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 4096)), dim3(256), 0, s, Ab, Yb,
+    RQ_LAUNCH(chain_block_gather_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 4096)), dim3(256), 0, s, Ab, Yb,
               (const double *)A, (const double *)b, mh, d, h, i, lo, len);
     RQ_TRY(lsq_spd_solve_launch(Ab, Yb, h2, len, s));
-    CH_LAUNCH(chain_block_scatter_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)h2 * len + 255) / 256, 4096)), dim3(256),
+    RQ_LAUNCH(chain_block_scatter_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)h2 * len + 255) / 256, 4096)), dim3(256),
               0, s, C, (const double *)Yb, d, h, i, lo, len);
   }
   clk.mark(CP_UPDATE);
@@ -400,19 +350,10 @@ int chain_update_dev(float *C, const float *X, const uint8_t *codes, int64_t n, 
 
 int chain_reconstruct_dev(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t s) {
   if (n <= 0) return RQ_OK;
-  CH_LAUNCH(chain_reconstruct_kernel, dim3((unsigned)std::min<int64_t>((n * d + 255) / 256, 8192)), dim3(256), 0, s, CB,
+  RQ_LAUNCH(chain_reconstruct_kernel, dim3((unsigned)std::min<int64_t>((n * d + 255) / 256, 8192)), dim3(256), 0, s, CB,
             codes, C, n, d, m, h);
   return RQ_OK;
 }
-
-struct ChainBuf {
-  void *p = nullptr;
-  ~ChainBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    RQ_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return RQ_OK;
-  }
-};
 
 }  // namespace
 
@@ -442,7 +383,7 @@ extern "C" int rq_dev_quantize_chainq(uint8_t *codes, const float *X, const floa
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   chain_clock_reset();
-  ChainClock clk((hipStream_t)stream, false);
+  PhaseClock clk((hipStream_t)stream, g_chain_ms, false);
   return chain_encode_dev(codes, X, C, n, d, m, h, nsplits, (hipStream_t)stream, clk);
 }
 
@@ -454,14 +395,14 @@ extern "C" int rq_quantize_chainq(uint8_t *codes, const float *X, const float *C
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  ChainBuf dX, dC, dcodes;
+  DevMem dX, dC, dcodes;
   RQ_TRY(dX.alloc((size_t)n * d * 4));
   RQ_TRY(dC.alloc((size_t)m * h * d * 4));
   RQ_TRY(dcodes.alloc((size_t)n * m));
   RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dC.p, C, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
   {
-    ChainClock clk(nullptr, true);
+    PhaseClock clk(nullptr, g_chain_ms);
     RQ_TRY(chain_encode_dev((uint8_t *)dcodes.p, (const float *)dX.p, (const float *)dC.p, n, d, m, h, nsplits, nullptr, clk));
     clk.collect();
   }
@@ -479,7 +420,7 @@ extern "C" int rq_dev_update_codebooks_chain(float *C, const float *X, const uin
   DeviceLock call_lock;
   RQ_TRY(dev_code_range(codes, n, m, h, s, "update_codebooks_chain"));
   chain_clock_reset();
-  ChainClock clk(s, false);
+  PhaseClock clk(s, g_chain_ms, false);
   return chain_update_dev(C, X, codes, n, d, m, h, rho, s, clk);
 }
 
@@ -491,7 +432,7 @@ extern "C" int rq_update_codebooks_chain(float *C, const float *X, const uint8_t
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  ChainBuf dX, dcodes, dC;
+  DevMem dX, dcodes, dC;
   RQ_TRY(dX.alloc((size_t)n * d * 4));
   RQ_TRY(dcodes.alloc((size_t)n * m));
   RQ_TRY(dC.alloc((size_t)m * h * d * 4));
@@ -500,7 +441,7 @@ extern "C" int rq_update_codebooks_chain(float *C, const float *X, const uint8_t
     RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
   }
   {
-    ChainClock clk(nullptr, true);
+    PhaseClock clk(nullptr, g_chain_ms);
     RQ_TRY(chain_update_dev((float *)dC.p, (const float *)dX.p, (const uint8_t *)dcodes.p, n, d, m, h, rho, nullptr, clk));
     clk.collect();
   }
@@ -531,7 +472,7 @@ extern "C" int rq_train_chainq(float *C, uint8_t *codes, float *R, double *obj, 
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   const size_t xb = (size_t)n * d * 4, cb = (size_t)m * h * d * 4;
-  ChainBuf dX, dRX, dCB, dR, dC, dcodes, dG, dobj, dstat, dns;
+  DevMem dX, dRX, dCB, dR, dC, dcodes, dG, dobj, dstat, dns;
   RQ_TRY(dX.alloc(xb)); RQ_TRY(dRX.alloc(xb)); RQ_TRY(dCB.alloc(xb));
   RQ_TRY(dR.alloc((size_t)d * d * 4)); RQ_TRY(dG.alloc((size_t)d * d * 4));
   RQ_TRY(dC.alloc(cb)); RQ_TRY(dcodes.alloc((size_t)n * m));
@@ -546,7 +487,7 @@ extern "C" int rq_train_chainq(float *C, uint8_t *codes, float *R, double *obj, 
   double *objd = (double *)dobj.p;
   const hipStream_t s = nullptr;
   {
-    ChainClock clk(s, true);
+    PhaseClock clk(s, g_chain_ms);
     // RX = R'X; C = update(RX, B); B = viterbi(RX, C)   (src/ChainQ.jl:393-401)
     RQ_TRY(rotate_launch(RX, Rd, Xd, d, n, di.num_cu, s));
     clk.mark(CP_ROTATION);

@@ -161,37 +161,6 @@ int ervq_check_shape(const char *who, int64_t n, int d, int m, int h) {
 enum { EV_INIT, EV_INCREMENT, EV_REFILL, EV_ENCODE, EV_EPILOGUE, EV_ERROR, EV_OTHER, EV_N };
 thread_local double g_ervq_ms[EV_N] = {0};
 
-struct ErvqClock {
-  hipStream_t s;
-  bool on = false;
-  std::vector<std::pair<int, hipEvent_t>> marks;   // (phase ending here, event)
-  hipEvent_t first = nullptr;
-  explicit ErvqClock(hipStream_t st) : s(st) {
-    if (hipEventCreate(&first) == hipSuccess) on = hipEventRecord(first, s) == hipSuccess;
-  }
-  void mark(int phase) {
-    if (!on) return;
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, s);
-    marks.push_back({phase, e});
-  }
-  void collect() {
-    if (!on) return;
-    (void)hipStreamSynchronize(s);
-    hipEvent_t prev = first;
-    for (auto &pe : marks) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) g_ervq_ms[pe.first] += ms;
-      prev = pe.second;
-    }
-  }
-  ~ErvqClock() {
-    for (auto &pe : marks) (void)hipEventDestroy(pe.second);
-    if (first) (void)hipEventDestroy(first);
-  }
-};
-
 }  // namespace
 
 }  // namespace rq
@@ -203,10 +172,7 @@ extern "C" int rq_ervq_update_codebook(float *C, uint32_t *counts, const float *
   RQ_TRY(ervq_check_shape("ervq_update_codebook", n, d, m, h));
   if (j < 0 || j >= m) return fail(RQ_EINVAL, "ervq_update_codebook: j=%d outside 0..%d", j, m - 1);
   if (!C || !counts || (n > 0 && (!X || !codes))) return fail(RQ_EINVAL, "ervq_update_codebook: null pointer");
-  for (int64_t e = 0; e < n * m; ++e)
-    if (codes[e] >= h)
-      return fail(RQ_EINVAL, "ervq_update_codebook: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
-                  (long long)(e % m), h);
+  RQ_TRY(host_code_range(codes, n, m, h, "ervq_update_codebook"));
   if (n == 0) {
     memset(counts, 0, (size_t)h * sizeof(uint32_t));
     return RQ_OK;
@@ -253,7 +219,7 @@ extern "C" int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, 
   if (niter > 0 && m > 1) { RQ_TRY(dP[0].alloc(xb)); RQ_TRY(dP[1].alloc(xb)); }
   const hipStream_t s = nullptr;
   for (int q = 0; q < EV_N; ++q) g_ervq_ms[q] = 0;
-  ErvqClock clk(s);
+  PhaseClock clk(s, g_ervq_ms);
   RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dC.p, C, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(d16.p, B1, (size_t)n * m * 2, hipMemcpyHostToDevice));

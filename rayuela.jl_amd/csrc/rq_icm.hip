@@ -13,7 +13,6 @@
 // restatement tests/icm_oracle.py bit for bit.
 #include "rq_internal.h"
 
-#include <chrono>
 #include <vector>
 
 namespace rq {
@@ -316,6 +315,14 @@ int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t s,
   return RQ_OK;
 }
 
+int host_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *who) {
+  if (h >= 256) return RQ_OK;
+  for (int64_t e = 0; e < n * m; ++e)
+    if (codes[e] >= h)
+      return fail(RQ_EINVAL, "%s: code %d at [%lld][%lld] is >= h=%d", who, codes[e], (long long)(e / m), (long long)(e % m), h);
+  return RQ_OK;
+}
+
 int icm_check_args(const void *codes_out, const void *codes_in, const void *X, const void *C, int64_t n, int d, int m,
                    int h, int ilsiter, int icmiter, int npert, int64_t t0, int nsplits) {
   if (m < 1 || m > ICM_MAX_M) return fail(RQ_EINVAL, "encode_icm: m=%d outside 1..%d", m, ICM_MAX_M);
@@ -420,15 +427,6 @@ int icm_unary_launch(float *U, const float *X, const float *C, const float *sa, 
 
 namespace {
 
-struct IcmBuf {
-  void *p = nullptr;
-  ~IcmBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    RQ_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return RQ_OK;
-  }
-};
-
 thread_local double g_icm_unary_ms = 0, g_icm_total_ms = 0;
 
 }  // namespace
@@ -452,16 +450,14 @@ extern "C" int rq_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float 
                              const float *C, int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert,
                              int randord, uint64_t seed, int64_t t0, int nsplits) {
   RQ_TRY(icm_check_args(codes_out, codes_in, X, C, n, d, m, h, ilsiter, icmiter, npert, t0, nsplits));
-  for (int64_t i = 0; i < n * m; ++i)
-    if (codes_in[i] >= h) return fail(RQ_EINVAL, "encode_icm: code %d at [%lld][%lld] is >= h=%d", codes_in[i],
-                                      (long long)(i / m), (long long)(i % m), h);
+  RQ_TRY(host_code_range(codes_in, n, m, h, "encode_icm"));
   g_icm_unary_ms = g_icm_total_ms = 0;
   if (n == 0) return RQ_OK;
-  const auto t_start = std::chrono::steady_clock::now();
+  Timer tt;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  IcmBuf dX, dC, dcodes, dcost;
+  DevMem dX, dC, dcodes, dcost;
   RQ_TRY(dX.alloc((size_t)n * d * 4));
   RQ_TRY(dC.alloc((size_t)m * h * d * 4));
   RQ_TRY(dcodes.alloc((size_t)n * m));
@@ -477,7 +473,7 @@ extern "C" int rq_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float 
   RQ_HIP(hipMemcpy(codes_out, dcodes.p, (size_t)n * m, hipMemcpyDeviceToHost));
   if (cost_out) RQ_HIP(hipMemcpy(cost_out, dcost.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   g_icm_unary_ms = un_ms;
-  g_icm_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  g_icm_total_ms = tt.ms();
   return RQ_OK;
 }
 

@@ -27,7 +27,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <mutex>
 #include <vector>
 
@@ -143,11 +142,6 @@ static int grow(void **p, size_t *cap, size_t bytes) {
   *cap = want;
   return RQ_OK;
 }
-
-struct Clock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
 
 }  // namespace rq
 
@@ -365,7 +359,7 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
     const int64_t per_q = (int64_t)k * 8 * (2 * (int64_t)ix->shards.size() + 1);
     const int64_t chunk = std::max<int64_t>(1, (int64_t)BULK_HOST_RESULT_BYTES / per_q);
     if (k > RQ_MAX_K && nq > chunk) {
-      Clock tc;
+      Timer tc;
       for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
         const int64_t nqc = std::min(chunk, nq - q0);
         RQ_TRY(index_search(ix, dists + (size_t)q0 * k, ids + (size_t)q0 * k, queries_host + (size_t)q0 * ix->d, R_host, nqc,
@@ -377,14 +371,14 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
   }
   std::lock_guard<std::mutex> lk(ix->mu);
   SavedDevice saved;
-  Clock tt;
+  Timer tt;
   const int m = ix->m, d = ix->d;
   const int P = (int)ix->shards.size();
   const size_t qb = (size_t)nq * d * 4, cnt = (size_t)nq * k, ob = cnt * 4;
   IxDev &root = ix->devs[0];
 
   // ---- queries to every device (and R'q there: linscan_opq rotates the queries first, src/Linscan.jl:102) ----
-  Clock t1;
+  Timer t1;
   for (auto &dv : ix->devs) {
     RQ_HIP(hipSetDevice(dv.device));
     if (dv.q_cap < qb) {
@@ -405,7 +399,7 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
     }
   }
   const double h2d_ms = t1.ms();
-  Clock t2;
+  Timer t2;
 
   RQ_HIP(hipSetDevice(root.device));
   RQ_TRY(grow((void **)&ix->dd, &ix->dd_cap, ob));
@@ -524,7 +518,7 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
     if (dv.mstream) RQ_HIP(hipStreamSynchronize(dv.mstream));
   }
   const double kernel_ms = t2.ms();
-  Clock t3;
+  Timer t3;
   RQ_HIP(hipSetDevice(root.device));
   RQ_HIP(hipMemcpy(dists, ix->dd, ob, hipMemcpyDeviceToHost));
   RQ_HIP(hipMemcpy(ids, ix->di, ob, hipMemcpyDeviceToHost));

@@ -7,6 +7,9 @@
 #include <math.h>
 
 #include <algorithm>
+#include <chrono>
+#include <utility>
+#include <vector>
 
 #include "../../include/rayuela_hip.h"
 
@@ -31,6 +34,17 @@ void forgive_oom();
   do {                          \
     int _r = (expr);            \
     if (_r != RQ_OK) return _r; \
+  } while (0)
+
+// Host tools that other translation units share but the library does not export: the dynamic symbol table holds the C ABI
+// and what it held before them.
+#define RQ_LOCAL __attribute__((visibility("hidden")))
+
+// launch a kernel and return the launch error, if any
+#define RQ_LAUNCH(...)                \
+  do {                                \
+    hipLaunchKernelGGL(__VA_ARGS__);  \
+    RQ_HIP(hipGetLastError());        \
   } while (0)
 
 int tuning(const char *key, int dflt);  // env RQ_<KEY> or rq_set_tuning override
@@ -81,6 +95,52 @@ struct SavedDevice {
   ~SavedDevice() { if (dev >= 0) (void)hipSetDevice(dev); }
   SavedDevice(const SavedDevice &) = delete;
   SavedDevice &operator=(const SavedDevice &) = delete;
+};
+
+// Wall clock of the host-pointer calls: milliseconds since it was made.
+struct Timer {
+  using clock = std::chrono::steady_clock;
+  clock::time_point t0 = clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); }
+};
+
+// Phase clock of the host-pointer entries (which synchronise anyway): hipEvents between the phases of one call, read at its
+// end into the caller's per-phase milliseconds `acc`.  want == false (the device-pointer entries, which may run under stream
+// capture) creates and records no event and leaves `acc` alone; so does a clock whose first event cannot be made.
+struct RQ_LOCAL PhaseClock {
+  bool on = false;
+  hipStream_t s;
+  double *acc;
+  std::vector<std::pair<int, hipEvent_t>> marks;   // (phase ending here, event)
+  hipEvent_t first = nullptr;
+  PhaseClock(hipStream_t st, double *acc_ms, bool want = true) : s(st), acc(acc_ms) {
+    if (want && hipEventCreate(&first) == hipSuccess) on = hipEventRecord(first, s) == hipSuccess;
+  }
+  PhaseClock(const PhaseClock &) = delete;
+  PhaseClock &operator=(const PhaseClock &) = delete;
+  // the work queued since the previous mark belongs to `phase`
+  void mark(int phase) {
+    if (!on) return;
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return;
+    (void)hipEventRecord(e, s);
+    marks.push_back({phase, e});
+  }
+  // accumulate the intervals into acc (interval = previous mark .. this mark)
+  void collect() {
+    if (!on) return;
+    (void)hipStreamSynchronize(s);
+    hipEvent_t prev = first;
+    for (auto &pe : marks) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) acc[pe.first] += ms;
+      prev = pe.second;
+    }
+  }
+  ~PhaseClock() {
+    for (auto &pe : marks) (void)hipEventDestroy(pe.second);
+    if (first) (void)hipEventDestroy(first);
+  }
 };
 
 // Milliseconds reported by rq_last_timing() for the calling thread.
@@ -304,6 +364,7 @@ int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const
 
 // ---- LSQ encoding (rq_icm.hip): argument checks, and the device body of rq_dev_encode_icm (codes already in range) -----
 int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t stream, const char *who);   // codes [n][m] < h
+RQ_LOCAL int host_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *who);   // on host codes; names the first one >= h
 int icm_check_args(const void *codes_out, const void *codes_in, const void *X, const void *C, int64_t n, int d, int m,
                    int h, int ilsiter, int icmiter, int npert, int64_t t0, int nsplits);
 int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,
@@ -321,4 +382,6 @@ int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t stream
 int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
                       hipStream_t stream);
 int lsq_mean_launch(double *out, const float *cost, int64_t n, hipStream_t stream);
+// the rotation of a training call (rq_train_lsq, rq_train_sr): dR <- R | R' ([d][d] each; R on the host), dRX [n][d] <- R'X
+RQ_LOCAL int upload_rotation(DevMem &dR, DevMem &dRX, const float *R, const float *X, int64_t n, int d, int num_cu, hipStream_t stream);
 }  // namespace rq

@@ -342,39 +342,6 @@ int lsq_check(const void *out0, const void *out1, const void *X, const void *cod
 enum { PH_COUNT, PH_SORT, PH_B, PH_ASSEMBLE, PH_SOLVE, PH_OTHER, PH_ENCODE, PH_N };
 thread_local double g_lsq_ms[PH_N] = {0};
 
-struct PhaseClock {
-  bool on;
-  hipStream_t s;
-  std::vector<std::pair<int, hipEvent_t>> marks;   // (phase ending here, event)
-  hipEvent_t first = nullptr;
-  PhaseClock(hipStream_t st, bool want) : on(want), s(st) {
-    if (on && hipEventCreate(&first) == hipSuccess) (void)hipEventRecord(first, s);
-    else on = false;
-  }
-  void mark(int phase) {
-    if (!on) return;
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, s);
-    marks.push_back({phase, e});
-  }
-  // accumulate the intervals into g_lsq_ms (interval = previous mark .. this mark)
-  void collect() {
-    if (!on) return;
-    (void)hipStreamSynchronize(s);
-    hipEvent_t prev = first;
-    for (auto &pe : marks) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) g_lsq_ms[pe.first] += ms;
-      prev = pe.second;
-    }
-  }
-  ~PhaseClock() {
-    for (auto &pe : marks) (void)hipEventDestroy(pe.second);
-    if (first) (void)hipEventDestroy(first);
-  }
-};
-
 // A [mh][mh], b [mh][d] f64 (device pointers; arguments checked, codes in range)
 int normal_eq_dev(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
                   hipStream_t s, PhaseClock &clk) {
@@ -415,41 +382,35 @@ int normal_eq_dev(double *A, double *b, const float *X, const uint8_t *codes, in
   return RQ_OK;
 }
 
-#define LSQ_LAUNCH(...)                 \
-  do {                                  \
-    hipLaunchKernelGGL(__VA_ARGS__);    \
-    RQ_HIP(hipGetLastError());          \
-  } while (0)
-
 // A <- its Cholesky factor (lower), Y [mh][d] <- A^-1 Y
 int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
   for (int k = 0; k < mh; k += NB) {
     const int nb = std::min(NB, mh - k), rest = mh - k - nb;
-    LSQ_LAUNCH(lsq_chol_diag_kernel, dim3(1), dim3(256), 0, s, A, mh, k, nb);
+    RQ_LAUNCH(lsq_chol_diag_kernel, dim3(1), dim3(256), 0, s, A, mh, k, nb);
     if (rest > 0) {
-      LSQ_LAUNCH(lsq_chol_panel_kernel, dim3((rest + 63) / 64), dim3(64), 0, s, A, mh, k, nb);
+      RQ_LAUNCH(lsq_chol_panel_kernel, dim3((rest + 63) / 64), dim3(64), 0, s, A, mh, k, nb);
       double *pan = A + (size_t)(k + nb) * mh + k;
       const unsigned tiles = (unsigned)((rest + GT - 1) / GT);
-      LSQ_LAUNCH(lsq_gemm_sub_kernel, dim3(tiles, tiles), dim3(256), 0, s, pan + nb, (int64_t)mh, rest, rest,
-                 (const double *)pan, (int64_t)mh, (int64_t)1, (const double *)pan, (int64_t)mh, (int64_t)1, nb, 1);
+      RQ_LAUNCH(lsq_gemm_sub_kernel, dim3(tiles, tiles), dim3(256), 0, s, pan + nb, (int64_t)mh, rest, rest,
+                (const double *)pan, (int64_t)mh, (int64_t)1, (const double *)pan, (int64_t)mh, (int64_t)1, nb, 1);
     }
   }
   const unsigned cgrid = (unsigned)((d + 63) / 64), ntile = (unsigned)((d + GT - 1) / GT);
   for (int k = 0; k < mh; k += NB) {   // L y = b
     const int nb = std::min(NB, mh - k), rest = mh - k - nb;
-    LSQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 1);
+    RQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 1);
     if (rest > 0)
-      LSQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((rest + GT - 1) / GT)), dim3(256), 0, s,
-                 Y + (size_t)(k + nb) * d, (int64_t)d, rest, d, (const double *)(A + (size_t)(k + nb) * mh + k),
-                 (int64_t)mh, (int64_t)1, (const double *)(Y + (size_t)k * d), (int64_t)1, (int64_t)d, nb, 0);
+      RQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((rest + GT - 1) / GT)), dim3(256), 0, s,
+                Y + (size_t)(k + nb) * d, (int64_t)d, rest, d, (const double *)(A + (size_t)(k + nb) * mh + k),
+                (int64_t)mh, (int64_t)1, (const double *)(Y + (size_t)k * d), (int64_t)1, (int64_t)d, nb, 0);
   }
   for (int k = ((mh - 1) / NB) * NB; k >= 0; k -= NB) {   // L' x = y
     const int nb = std::min(NB, mh - k);
-    LSQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 0);
+    RQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 0);
     if (k > 0)
-      LSQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((k + GT - 1) / GT)), dim3(256), 0, s, Y, (int64_t)d, k, d,
-                 (const double *)(A + (size_t)k * mh), (int64_t)1, (int64_t)mh, (const double *)(Y + (size_t)k * d),
-                 (int64_t)1, (int64_t)d, nb, 0);
+      RQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((k + GT - 1) / GT)), dim3(256), 0, s, Y, (int64_t)d, k, d,
+                (const double *)(A + (size_t)k * mh), (int64_t)1, (int64_t)mh, (const double *)(Y + (size_t)k * d),
+                (int64_t)1, (int64_t)d, nb, 0);
   }
   return RQ_OK;
 }
@@ -465,20 +426,11 @@ int update_dev(float *C, const float *X, const uint8_t *codes, int64_t n, int d,
   RQ_TRY(normal_eq_dev(A, b, X, codes, n, d, m, h, rho, s, clk));
   RQ_TRY(spd_solve_dev(A, b, mh, d, s));
   const int64_t cnt = (int64_t)mh * d;
-  LSQ_LAUNCH(lsq_to_f32_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, s, C,
-             (const double *)b, cnt);
+  RQ_LAUNCH(lsq_to_f32_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, s, C,
+            (const double *)b, cnt);
   clk.mark(PH_SOLVE);
   return RQ_OK;
 }
-
-struct LsqBuf {
-  void *p = nullptr;
-  ~LsqBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    RQ_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return RQ_OK;
-  }
-};
 
 void lsq_clock_reset() {
   for (int q = 0; q < PH_N; ++q) g_lsq_ms[q] = 0;
@@ -489,7 +441,7 @@ void lsq_clock_reset() {
 // The normal equations and the SPD solve for the chain codebook update (rq_chain.hip); no phase clock.
 int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
                          double rho, hipStream_t s) {
-  PhaseClock clk(s, false);
+  PhaseClock clk(s, g_lsq_ms, false);
   return normal_eq_dev(A, b, X, codes, n, d, m, h, rho, s, clk);
 }
 
@@ -498,12 +450,24 @@ int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t s) { r
 // The fastbin update and the obj mean for the SR training loop (rq_sr.hip), which keeps a phase clock of its own.
 int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
                       hipStream_t s) {
-  PhaseClock clk(s, false);
+  PhaseClock clk(s, g_lsq_ms, false);
   return update_dev(C, X, codes, n, d, m, h, rho, s, clk);
 }
 
+int upload_rotation(DevMem &dR, DevMem &dRX, const float *R, const float *X, int64_t n, int d, int num_cu, hipStream_t s) {
+  const size_t rb = (size_t)d * d * 4;
+  std::vector<float> Rt((size_t)d * d);
+  for (int i = 0; i < d; ++i)
+    for (int k = 0; k < d; ++k) Rt[(size_t)i * d + k] = R[(size_t)k * d + i];
+  RQ_TRY(dRX.alloc((size_t)n * d * 4));
+  RQ_TRY(dR.alloc(rb * 2));
+  RQ_HIP(hipMemcpy(dR.p, R, rb, hipMemcpyHostToDevice));
+  RQ_HIP(hipMemcpy(dR.as<float>() + (size_t)d * d, Rt.data(), rb, hipMemcpyHostToDevice));
+  return rotate_launch(dRX.as<float>(), dR.as<float>(), X, d, n, num_cu, s);
+}
+
 int lsq_mean_launch(double *out, const float *cost, int64_t n, hipStream_t s) {
-  LSQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, out, cost, n);
+  RQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, out, cost, n);
   return RQ_OK;
 }
 
@@ -520,7 +484,7 @@ extern "C" int rq_dev_lsq_normal_eq(double *A, double *b, const float *X, const 
   DeviceLock call_lock;
   RQ_TRY(dev_code_range(codes, n, m, h, s, "lsq_normal_eq"));
   lsq_clock_reset();
-  PhaseClock clk(s, false);
+  PhaseClock clk(s, g_lsq_ms, false);
   RQ_TRY(normal_eq_dev(A, b, X, codes, n, d, m, h, rho, s, clk));
   return RQ_OK;
 }
@@ -534,7 +498,7 @@ extern "C" int rq_dev_update_codebooks_lsq(float *C, const float *X, const uint8
   DeviceLock call_lock;
   RQ_TRY(dev_code_range(codes, n, m, h, s, "update_codebooks_lsq"));
   lsq_clock_reset();
-  PhaseClock clk(s, false);
+  PhaseClock clk(s, g_lsq_ms, false);
   RQ_TRY(update_dev(C, X, codes, n, d, m, h, rho, s, clk));
   return RQ_OK;
 }
@@ -542,14 +506,11 @@ extern "C" int rq_dev_update_codebooks_lsq(float *C, const float *X, const uint8
 extern "C" int rq_update_codebooks_lsq(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
                                        double rho) {
   RQ_TRY(lsq_check(C, C, X, codes, n, d, m, h, rho, "update_codebooks_lsq"));
-  for (int64_t e = 0; e < n * m; ++e)
-    if (codes[e] >= h)
-      return fail(RQ_EINVAL, "update_codebooks_lsq: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
-                  (long long)(e % m), h);
+  RQ_TRY(host_code_range(codes, n, m, h, "update_codebooks_lsq"));
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  LsqBuf dX, dcodes, dC;
+  DevMem dX, dcodes, dC;
   RQ_TRY(dX.alloc((size_t)n * d * 4));
   RQ_TRY(dcodes.alloc((size_t)n * m));
   RQ_TRY(dC.alloc((size_t)m * h * d * 4));
@@ -558,7 +519,7 @@ extern "C" int rq_update_codebooks_lsq(float *C, const float *X, const uint8_t *
     RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
   }
   lsq_clock_reset();
-  PhaseClock clk(nullptr, true);
+  PhaseClock clk(nullptr, g_lsq_ms);
   RQ_TRY(update_dev((float *)dC.p, (const float *)dX.p, (const uint8_t *)dcodes.p, n, d, m, h, rho, nullptr, clk));
   clk.collect();
   RQ_HIP(hipDeviceSynchronize());
@@ -576,16 +537,13 @@ extern "C" int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *
   if ((int64_t)ilsiter * ((int64_t)niter + 1) > INT32_MAX)
     return fail(RQ_EINVAL, "train_lsq: ilsiter * (niter + 1) overflows the ILS iteration counter");
   RQ_TRY(icm_check_args(codes, codes, X, C, n, d, m, h, ilsiter, icmiter, npert, 0, nsplits));
-  for (int64_t e = 0; e < n * m; ++e)
-    if (codes[e] >= h)
-      return fail(RQ_EINVAL, "train_lsq: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
-                  (long long)(e % m), h);
+  RQ_TRY(host_code_range(codes, n, m, h, "train_lsq"));
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   const int mh = m * h;
   const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4;
-  LsqBuf dX, dRX, dR, dC, dC2, dcodes, dcost, dobj;
+  DevMem dX, dRX, dR, dC, dC2, dcodes, dcost, dobj;
   RQ_TRY(dX.alloc(xb));
   RQ_TRY(dcodes.alloc((size_t)n * m));
   RQ_TRY(dC.alloc(cb));
@@ -601,19 +559,12 @@ extern "C" int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *
   double *objd = (double *)dobj.p;
   const hipStream_t s = nullptr;
   lsq_clock_reset();
-  PhaseClock clk(s, true);
+  PhaseClock clk(s, g_lsq_ms);
   // C = update(R'X, B); C_i <- R C_i   (src/LSQ.jl:345-350)
   if (R) {
-    std::vector<float> Rt((size_t)d * d);
-    for (int i = 0; i < d; ++i)
-      for (int k = 0; k < d; ++k) Rt[(size_t)i * d + k] = R[(size_t)k * d + i];
-    RQ_TRY(dRX.alloc(xb));
-    RQ_TRY(dR.alloc((size_t)d * d * 4 * 2));
+    RQ_TRY(upload_rotation(dR, dRX, R, Xd, n, d, di.num_cu, s));
     RQ_TRY(dC2.alloc(cb));
-    float *Rd = (float *)dR.p, *Rtd = Rd + (size_t)d * d;
-    RQ_HIP(hipMemcpy(Rd, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-    RQ_HIP(hipMemcpy(Rtd, Rt.data(), (size_t)d * d * 4, hipMemcpyHostToDevice));
-    RQ_TRY(rotate_launch((float *)dRX.p, Rd, Xd, d, n, di.num_cu, s));
+    const float *Rtd = dR.as<float>() + (size_t)d * d;
     clk.mark(PH_OTHER);
     RQ_TRY(update_dev((float *)dC2.p, (const float *)dRX.p, B, n, d, m, h, 1e-4, s, clk));
     RQ_TRY(rotate_launch(Cd, Rtd, (const float *)dC2.p, d, mh, di.num_cu, s));
@@ -626,7 +577,7 @@ extern "C" int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *
   clk.mark(PH_ENCODE);
   for (int it = 1; it <= niter; ++it) {
     // obj[iter] = qerror(X, B, C): the mean of the previous encode's per-row costs (NaN when n = 0: a mean of no rows)
-    LSQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, objd + (it - 1), (const float *)cost, n);
+    RQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, objd + (it - 1), (const float *)cost, n);
     clk.mark(PH_OTHER);
     RQ_TRY(update_dev(Cd, Xd, B, n, d, m, h, 1e-4, s, clk));
     RQ_TRY(icm_encode_dev(B, B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed,

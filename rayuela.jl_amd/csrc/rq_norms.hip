@@ -107,14 +107,6 @@ int norms_check_hn(const char *who, int hn) {
   return RQ_OK;
 }
 
-int norms_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *who) {
-  if (h >= 256) return RQ_OK;
-  for (int64_t i = 0; i < n * m; ++i)
-    if (codes[i] >= h)
-      return fail(RQ_EINVAL, "%s: code %d at [%lld][%lld] is >= h=%d", who, codes[i], (long long)(i / m), (long long)(i % m), h);
-  return RQ_OK;
-}
-
 }  // namespace
 
 int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
@@ -169,7 +161,7 @@ int rq_dev_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t 
 int rq_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h) {
   RQ_TRY(norms_check_shape("rq_aq_norms", n, d, m, h));
   if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "rq_aq_norms: null pointer");
-  RQ_TRY(norms_code_range(codes, n, m, h, "rq_aq_norms"));
+  RQ_TRY(host_code_range(codes, n, m, h, "rq_aq_norms"));
   if (n == 0) return RQ_OK;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
@@ -194,7 +186,7 @@ int rq_quantize_norms(uint8_t *norm_codes, float *norms_out, const uint8_t *code
   RQ_TRY(norms_check_shape("rq_quantize_norms", n, d, m, h));
   RQ_TRY(norms_check_hn("rq_quantize_norms", hn));
   if (!cbnorms || (n > 0 && (!norm_codes || !codes || !C))) return fail(RQ_EINVAL, "rq_quantize_norms: null pointer");
-  RQ_TRY(norms_code_range(codes, n, m, h, "rq_quantize_norms"));
+  RQ_TRY(host_code_range(codes, n, m, h, "rq_quantize_norms"));
   if (n == 0) return RQ_OK;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
@@ -218,7 +210,7 @@ int rq_get_norms_codebook(uint8_t *norm_codes, float *cbnorms, float *norms_out,
   if (niter < 0) return fail(RQ_EINVAL, "rq_get_norms_codebook: niter=%d < 0", niter);
   if (n < hn) return fail(RQ_EINVAL, "rq_get_norms_codebook: fewer rows (%lld) than norm codebook entries (%d)", (long long)n, hn);
   if (!norm_codes || !cbnorms || !codes || !C) return fail(RQ_EINVAL, "rq_get_norms_codebook: null pointer");
-  RQ_TRY(norms_code_range(codes, n, m, h, "rq_get_norms_codebook"));
+  RQ_TRY(host_code_range(codes, n, m, h, "rq_get_norms_codebook"));
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;

@@ -235,49 +235,9 @@ int sr_perturb_check(const void *Y, const void *X, const void *sigma, double sca
   return RQ_OK;
 }
 
-struct SrBuf {
-  void *p = nullptr;
-  ~SrBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) {
-    RQ_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return RQ_OK;
-  }
-};
-
 // Phase clock of rq_train_sr: hipEvents between the phases of the calling thread's last call, read at its end.
 enum { SR_STD, SR_PERTURB, SR_UPDATE, SR_ENCODE, SR_OBJ, SR_OTHER, SR_N };
 thread_local double g_sr_ms[SR_N] = {0};
-
-struct SrClock {
-  hipStream_t s;
-  bool on = false;
-  std::vector<std::pair<int, hipEvent_t>> marks;   // (phase ending here, event)
-  hipEvent_t first = nullptr;
-  explicit SrClock(hipStream_t st) : s(st) {
-    if (hipEventCreate(&first) == hipSuccess) on = hipEventRecord(first, s) == hipSuccess;
-  }
-  void mark(int phase) {
-    if (!on) return;
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, s);
-    marks.push_back({phase, e});
-  }
-  void collect() {
-    if (!on) return;
-    (void)hipStreamSynchronize(s);
-    hipEvent_t prev = first;
-    for (auto &pe : marks) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) g_sr_ms[pe.first] += ms;
-      prev = pe.second;
-    }
-  }
-  ~SrClock() {
-    for (auto &pe : marks) (void)hipEventDestroy(pe.second);
-    if (first) (void)hipEventDestroy(first);
-  }
-};
 
 }  // namespace
 
@@ -297,7 +257,7 @@ extern "C" int rq_sr_std(float *sigma, const float *X, int64_t n, int d) {
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  SrBuf dX, dsig, dscr;
+  DevMem dX, dsig, dscr;
   RQ_TRY(dX.alloc((size_t)n * d * 4));
   RQ_TRY(dsig.alloc((size_t)d * 4));
   RQ_TRY(dscr.alloc(sr_std_scratch_bytes(n, d)));
@@ -315,7 +275,7 @@ extern "C" int rq_sr_perturb(float *Y, const float *X, const float *sigma, doubl
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  SrBuf dX, dsig;
+  DevMem dX, dsig;
   const size_t xb = (size_t)n * d * 4;
   RQ_TRY(dX.alloc(xb));
   RQ_TRY(dsig.alloc((size_t)d * 4));
@@ -348,16 +308,13 @@ extern "C" int rq_train_sr(float *C, uint8_t *codes, double *obj, const float *X
   std::vector<double> scale((size_t)niter + 1);
   for (int it = 0; it <= niter; ++it)
     RQ_TRY(sr_schedule(&scale[it], schedule, it == 0 && method == RQ_SR_D ? 1 : it, niter, p));
-  for (int64_t e = 0; e < n * m; ++e)
-    if (codes[e] >= h)
-      return fail(RQ_EINVAL, "train_sr: code %d at [%lld][%lld] is >= h=%d", codes[e], (long long)(e / m),
-                  (long long)(e % m), h);
+  RQ_TRY(host_code_range(codes, n, m, h, "train_sr"));
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   const int mh = m * h;
   const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4;
-  SrBuf dX, dRX, dR, dC, dC2, dnoisy, dcodes, dcost, dobj, dsig, dscr;
+  DevMem dX, dRX, dR, dC, dC2, dnoisy, dcodes, dcost, dobj, dsig, dscr;
   RQ_TRY(dX.alloc(xb));
   RQ_TRY(dcodes.alloc((size_t)n * m));
   RQ_TRY(dC.alloc(cb));
@@ -368,7 +325,7 @@ extern "C" int rq_train_sr(float *C, uint8_t *codes, double *obj, const float *X
   if (method == RQ_SR_C) RQ_TRY(dnoisy.alloc(xb));
   const hipStream_t s = nullptr;
   for (int q = 0; q < SR_N; ++q) g_sr_ms[q] = 0;
-  SrClock clk(s);   // SR_OTHER: the uploads, R'X and the rotation back
+  PhaseClock clk(s, g_sr_ms);   // SR_OTHER: the uploads, R'X and the rotation back
   if (n > 0) {
     RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
     RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
@@ -379,17 +336,9 @@ extern "C" int rq_train_sr(float *C, uint8_t *codes, double *obj, const float *X
   double *objd = (double *)dobj.p, *scr = (double *)dscr.p;
   const float *Rtd = nullptr;
   if (R) {   // RX = R'X   (src/SR.jl:115)
-    std::vector<float> Rt((size_t)d * d);
-    for (int i = 0; i < d; ++i)
-      for (int k = 0; k < d; ++k) Rt[(size_t)i * d + k] = R[(size_t)k * d + i];
-    RQ_TRY(dRX.alloc(xb));
-    RQ_TRY(dR.alloc((size_t)d * d * 4 * 2));
+    RQ_TRY(upload_rotation(dR, dRX, R, (const float *)dX.p, n, d, di.num_cu, s));
     RQ_TRY(dC2.alloc(cb));
-    float *Rd = (float *)dR.p;
-    RQ_HIP(hipMemcpy(Rd, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
-    RQ_HIP(hipMemcpy(Rd + (size_t)d * d, Rt.data(), (size_t)d * d * 4, hipMemcpyHostToDevice));
-    Rtd = Rd + (size_t)d * d;
-    RQ_TRY(rotate_launch((float *)dRX.p, Rd, (const float *)dX.p, d, n, di.num_cu, s));
+    Rtd = dR.as<float>() + (size_t)d * d;
     RX = (const float *)dRX.p;
   }
   clk.mark(SR_OTHER);

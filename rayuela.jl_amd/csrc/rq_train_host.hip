@@ -11,7 +11,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <chrono>
 #include <vector>
 
 #include "rq_internal.h"
@@ -142,15 +141,12 @@ enum { TP_H2D = 0, TP_INIT, TP_QERROR, TP_GRAM, TP_SVD, TP_ROTATE, TP_CENTERS, T
 static thread_local double g_train_prof[TP_SLOTS];
 struct TrainProf {
   bool fine;
-  std::chrono::steady_clock::time_point t0, tl;
-  TrainProf() : fine(tuning("TRAIN_PROFILE", 0) != 0) { for (double &x : g_train_prof) x = 0.0; }
-  static double since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-  }
-  void start() { if (fine) { (void)hipDeviceSynchronize(); t0 = std::chrono::steady_clock::now(); } }
-  void stop(int slot) { if (fine) { (void)hipDeviceSynchronize(); g_train_prof[slot] += since(t0); } }
-  void loop_begin() { (void)hipDeviceSynchronize(); tl = std::chrono::steady_clock::now(); }
-  void loop_end(int iters) { (void)hipDeviceSynchronize(); g_train_prof[TP_LOOP] = since(tl); g_train_prof[TP_ITERS] = iters; }
+  Timer t0, tl;
+  RQ_LOCAL TrainProf() : fine(tuning("TRAIN_PROFILE", 0) != 0) { for (double &x : g_train_prof) x = 0.0; }
+  void start() { if (fine) { (void)hipDeviceSynchronize(); t0 = Timer(); } }
+  void stop(int slot) { if (fine) { (void)hipDeviceSynchronize(); g_train_prof[slot] += t0.ms(); } }
+  void loop_begin() { (void)hipDeviceSynchronize(); tl = Timer(); }
+  void loop_end(int iters) { (void)hipDeviceSynchronize(); g_train_prof[TP_LOOP] = tl.ms(); g_train_prof[TP_ITERS] = iters; }
 };
 #define RQ_PH(slot, stmt) do { prof.start(); stmt; prof.stop(slot); } while (0)
 

@@ -58,12 +58,14 @@ def test_aq_vs_oracle_random(rq, oracle, n, m, d, nq, K):
     assert np.array_equal(i0, i1) and _eq_bits(d0, d1)
 
 
-@pytest.mark.parametrize("n,m,d,nq,K", [(300_000, 8, 64, 24, 1000), (100_003, 16, 48, 9, 100), (50_000, 5, 40, 7, 50), (5_000, 4, 32, 3, 5000)])
+@pytest.mark.parametrize("n,m,d,nq,K", [(300_000, 8, 64, 24, 1000), (100_003, 16, 48, 9, 100), (50_000, 5, 40, 7, 50), (5_000, 4, 32, 3, 5000),
+                                        (66_000, 4, 16, 2, 65_537)])
 def test_prepared_lsq_index_equals_linscan_lsq(rq, oracle, n, m, d, nq, K):
     """rq_lsq_prepare / rq_lsq_search / rq_lsq_release (ADVICE r2): the pre-filter's O(n) preprocessing is paid once per base;
     every search returns what linscan_lsq returns (= the compiled reference's deps/src/linscan_aqd_pairwise_byte.cpp:14-94
     semantics, one-based ids), with and without a rotation, on clustered codes where the filter is active (m = 8, 16), on a
-    padded width (m = 5) and on a width without the filter (m = 4)."""
+    padded width (m = 5) and on a width without the filter (m = 4).  K = 65537 is the bulk path (k > RQ_MAX_K) of rq_lsq_search;
+    with n >= 65536 the prepared base is in bank-aware order, so the ids travel through its perm there too."""
     import rayuela_jl_amd.synth as synth
     rng = np.random.default_rng(n + m)
     C = [rng.standard_normal((256, d)).astype(np.float32) for _ in range(m)]

@@ -2,6 +2,7 @@
 against the numpy restatements of tests/ervq_oracle.py, the loop's contract (B == quantize_rvq(X, C), the obj trace,
 reproducibility, the refill of entries without rows, argument checks) and experiment_ervq end to end."""
 import ctypes
+import time
 
 import numpy as np
 import pytest
@@ -101,9 +102,19 @@ def test_train_ervq_follows_the_restatement(rq, fix):
     `literal` (f64 means) and `incremental` (f32): trace 5.342e-10 relative, worst codebook entry 7.629e-06, 0 differing
     codes -- so 5.4e-9 on every obj entry and no differing code (the caps, 3e-4 and 2e-2 of
     test_train_opq_follows_the_oracle_loop, are far above).  Measured on the MI355X: trace 9.855e-10, no differing code,
-    worst codebook entry 7.629e-06 (EXPERIMENTS.md section 13)."""
+    worst codebook entry 7.629e-06 (EXPERIMENTS.md section 13).
+    The call's phase clock (rq_last_ervq_timing): every slot finite and >= 0, the phases this shape runs > 0 (the refill and
+    the in-place epilogue may have no work of their own), and no more in total than the wall time of the call."""
+    from rayuela_jl_amd.ERVQ import last_ervq_timing
     X, codes, C, ref = fix
+    t0 = time.perf_counter()
     Cg, Bg, err, obj = _train(X, codes, C, eo.FIX_NITER)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    ph = last_ervq_timing()
+    print("phases:", "  ".join("%s=%.3f" % kv for kv in ph.items()), " wall %.3f ms" % wall_ms)
+    assert all(np.isfinite(v) and v >= 0 for v in ph.values()), ph
+    assert all(ph[k] > 0 for k in ("init_ms", "increment_ms", "encode_ms", "error_ms")), ph
+    assert sum(ph.values()) <= wall_ms, (ph, wall_ms)
     Cr, Br, objr, _ = ref
     trace = np.abs(obj - objr) / objr
     diff = float(np.mean((Bg - 1) != Br))

@@ -56,8 +56,12 @@ def test_iteration_knobs_bit_exact(rq, oracle, icmiter, npert, randord):
 
 
 def test_odd_shapes_bit_exact(rq, oracle):
+    from rayuela_jl_amd.LSQ import last_timing
     X, C, B0 = _data(77, 37, 5, 100, seed=4)
-    _assert_same(_gpu(X, C, B0, 3, 2, 3, True, seed=2), io.ils(oracle, X, C, B0, 3, 2, 3, True, seed=2))
+    got = _gpu(X, C, B0, 3, 2, 3, True, seed=2)
+    t = last_timing()                                  # the host entry's clocks (rq_last_icm_timing): the unaries within the call
+    assert 0 <= t["unary_ms"] <= t["total_ms"] and t["total_ms"] > 0, t
+    _assert_same(got, io.ils(oracle, X, C, B0, 3, 2, 3, True, seed=2))
 
 
 def test_nsplits_do_not_change_results(rq):
