@@ -461,7 +461,6 @@ static int bulk_scan_m(float *dists, uint32_t *ids, uint64_t *keys, const uint8_
   void (*kern)(BulkKeyParams) = row_bias ? adc_bulk_keys_kernel<M, true> : adc_bulk_keys_kernel<M, false>;
   const size_t lds = (size_t)Cfg::LUT_LDS_BYTES + (size_t)Cfg::QG * d * 4;
   if (lds > 160 * 1024) return fail(RQ_EUNSUPPORTED, "bulk top-k: d=%d does not fit the LDS table plan", d);
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (int64_t q0 = 0; q0 < nq; q0 += nbmax) {
     const int64_t nb = std::min(nbmax, nq - q0);
     uint32_t gx, gy;
@@ -477,8 +476,7 @@ static int bulk_scan_m(float *dists, uint32_t *ids, uint64_t *keys, const uint8_
     p.rows_per_wg = (uint32_t)((n + gx - 1) / gx);
     p.keys = (uint64_t *)at; at += align256((size_t)nb * n * 8);
     p.gtab = (float4 *)at; at += align256((size_t)gx * gy * (Cfg::GTAB_F4 > 0 ? Cfg::GTAB_F4 : 1) * sizeof(float4));
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(BULK_KEY_THREADS), lds, stream, p);
-    RQ_HIP(hipGetLastError());
+    RQ_LAUNCH_LDS(kern, dim3(gx, gy), dim3(BULK_KEY_THREADS), lds, stream, p);
     BulkSel s;
     s.src = p.keys;
     s.ld = (size_t)n;

@@ -37,7 +37,7 @@ constexpr int XS_STRIDE = 33;
 template <int KS, int NT, int NWAVES>
 __global__ __launch_bounds__(NWAVES * 64) void encode_pq_kernel(EncParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int m = p.m, h = p.h, d = p.d;
+  const int m = p.m, d = p.d;
   const int i0 = p.i0, mg = p.i1 - p.i0;                        // this launch's group of sub-quantizers
   float *cbA = reinterpret_cast<float *>(smem);                 // mg*NT*KS*64
   float *saL = cbA + (size_t)mg * NT * KS * 64;                 // mg*NT*32
@@ -47,36 +47,8 @@ __global__ __launch_bounds__(NWAVES * 64) void encode_pq_kernel(EncParams p) {
   float *xs = xs_all + (size_t)wave * (2 * KS * XS_STRIDE);
 
   // ---- prologue: codebooks -> A-fragment order, norms -> C/D-fragment order -------------------
-  for (int idx = tid; idx < mg * NT * KS * 64; idx += NWAVES * 64) {
-    const int l = idx & 63;
-    int rest = idx >> 6;
-    const int kk = rest % KS; rest /= KS;
-    const int t = rest % NT;
-    const int i = i0 + rest / NT;
-    const int sub = p.off[i + 1] - p.off[i];
-    const int cen = t * 32 + (l & 31);
-    const int s = 2 * kk + (l >> 5);
-    float v = 0.0f;
-    if (cen < h && s < sub) v = p.C[(size_t)h * p.off[i] + (size_t)cen * sub + s];
-    cbA[idx] = v;
-  }
-  for (int idx = tid; idx < mg * NT * 32; idx += NWAVES * 64) {
-    const int c32 = idx & 31;
-    const int t = (idx >> 5) % NT;
-    const int il = (idx >> 5) / NT;
-    const int i = i0 + il;
-    const int sub = p.off[i + 1] - p.off[i];
-    const int cen = t * 32 + c32;
-    float sa = __uint_as_float(0x7f800000u);
-    if (cen < h) {
-      const float *c = p.C + (size_t)h * p.off[i] + (size_t)cen * sub;
-      sa = 0.0f;
-      for (int s = 0; s < sub; ++s) sa = __builtin_fmaf(c[s], c[s], sa);
-    }
-    const int hh = (c32 >> 2) & 1;
-    const int r = (c32 & 3) + 4 * (c32 >> 3);
-    saL[((size_t)(il * NT + t) * 2 + hh) * 16 + r] = sa;
-  }
+  stage_codebooks_A<KS, NT, 0, NWAVES * 64>(cbA, p, i0, mg, tid);
+  stage_norms_cd<NT, 0, NWAVES * 64>(saL, p, i0, mg, tid);
   __syncthreads();
 
   const int64_t ntiles = (p.n + 31) / 32;
@@ -181,16 +153,7 @@ __global__ __launch_bounds__(NWAVES * 64) void encode_pq_kernel(EncParams p) {
       for (int w = 0; w < 4; ++w)
         if ((i >> 3) == w) cw[w] |= (uint64_t)(uint32_t)best_i << (8 * (i & 7));
     }
-    if (hi == 0 && row0 + j < p.n) {
-      uint8_t *o = p.codes + (size_t)(row0 + j) * m;
-      if ((m & 7) == 0 && mg == m) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-          if (w * 8 < m) reinterpret_cast<uint64_t *>(o)[w] = cw[w];
-      } else {
-        for (int i = i0; i < p.i1; ++i) o[i] = (uint8_t)(cw[i >> 3] >> (8 * (i & 7)));
-      }
-    }
+    if (hi == 0 && row0 + j < p.n) codewords_store(cw, p.codes + (size_t)(row0 + j) * m, m, i0, p.i1, (m & 7) == 0 && mg == m);
   }
 }
 
@@ -205,38 +168,14 @@ template <int KS, int NT, int NWAVES>
 __global__ __launch_bounds__(NWAVES * 64) void encode_pq_direct_kernel(EncParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int SUB = 2 * KS;
-  const int m = p.m, h = p.h, d = p.d;
+  const int m = p.m, d = p.d;
   const int i0 = p.i0, mg = p.i1 - p.i0;
   float *cbA = reinterpret_cast<float *>(smem);                 // mg*NT*KS*64
   float *saL = cbA + (size_t)mg * NT * KS * 64;                 // mg*NT*32
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, hi = lane >> 5;
-  for (int idx = tid; idx < mg * NT * KS * 64; idx += NWAVES * 64) {
-    const int l = idx & 63;
-    int rest = idx >> 6;
-    const int kk = rest % KS; rest /= KS;
-    const int t = rest % NT;
-    const int i = i0 + rest / NT;
-    const int cen = t * 32 + (l & 31);
-    const int sx = 2 * kk + (l >> 5);
-    cbA[idx] = cen < h ? p.C[(size_t)h * SUB * i + (size_t)cen * SUB + sx] : 0.0f;
-  }
-  for (int idx = tid; idx < mg * NT * 32; idx += NWAVES * 64) {
-    const int c32 = idx & 31;
-    const int t = (idx >> 5) % NT;
-    const int il = (idx >> 5) / NT;
-    const int cen = t * 32 + c32;
-    float sa = __uint_as_float(0x7f800000u);
-    if (cen < h) {
-      const float *c = p.C + (size_t)h * SUB * (i0 + il) + (size_t)cen * SUB;
-      sa = 0.0f;
-#pragma unroll
-      for (int sx = 0; sx < SUB; ++sx) sa = __builtin_fmaf(c[sx], c[sx], sa);
-    }
-    const int hh = (c32 >> 2) & 1;
-    const int r = (c32 & 3) + 4 * (c32 >> 3);
-    saL[((size_t)(il * NT + t) * 2 + hh) * 16 + r] = sa;
-  }
+  stage_codebooks_A<KS, NT, SUB, NWAVES * 64>(cbA, p, i0, mg, tid);
+  stage_norms_cd<NT, SUB, NWAVES * 64>(saL, p, i0, mg, tid);
   __syncthreads();
 
   const int64_t ntiles = (p.n + 31) / 32;
@@ -299,16 +238,7 @@ __global__ __launch_bounds__(NWAVES * 64) void encode_pq_direct_kernel(EncParams
       for (int w = 0; w < 4; ++w)
         if ((i >> 3) == w) cw[w] |= (uint64_t)(uint32_t)best_i << (8 * (i & 7));
     }
-    if (hi == 0 && row0 + j < p.n) {
-      uint8_t *o = p.codes + (size_t)(row0 + j) * m;
-      if ((m & 7) == 0 && mg == m) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-          if (w * 8 < m) reinterpret_cast<uint64_t *>(o)[w] = cw[w];
-      } else {
-        for (int i = i0; i < p.i1; ++i) o[i] = (uint8_t)(cw[i >> 3] >> (8 * (i & 7)));
-      }
-    }
+    if (hi == 0 && row0 + j < p.n) codewords_store(cw, p.codes + (size_t)(row0 + j) * m, m, i0, p.i1, (m & 7) == 0 && mg == m);
   }
 }
 
@@ -745,22 +675,7 @@ __global__ __launch_bounds__(NWAVES * 64) void encode_wide_kernel(EncParams p) {
   const int j = lane & 31, hi = lane >> 5;
   float *xs = xs_all + wave * 32 * XSTR;
 
-  for (int idx = tid; idx < m * NT * 32; idx += NWAVES * 64) {
-    const int c32 = idx & 31;
-    const int t = (idx >> 5) % NT;
-    const int i = (idx >> 5) / NT;
-    const int sub = p.off[i + 1] - p.off[i];
-    const int cen = t * 32 + c32;
-    float sa = __uint_as_float(0x7f800000u);
-    if (cen < h) {
-      const float *c = p.C + (size_t)h * p.off[i] + (size_t)cen * sub;
-      sa = 0.0f;
-      for (int s = 0; s < sub; ++s) sa = __builtin_fmaf(c[s], c[s], sa);
-    }
-    const int hh = (c32 >> 2) & 1;
-    const int r = (c32 & 3) + 4 * (c32 >> 3);
-    saL[((size_t)(i * NT + t) * 2 + hh) * 16 + r] = sa;
-  }
+  stage_norms_cd<NT, 0, NWAVES * 64>(saL, p, 0, m, tid);
 
   // element `e` of a staged chunk -> (tile t, k-step kk, lane l): centroid t*32 + (l & 31), dimension 2kk + (l >> 5)
   auto cb_load = [&](int i, int c, int e) -> float {
@@ -875,13 +790,9 @@ static int launch_encode_wide(EncParams p, int num_cu, hipStream_t stream) {
                      (size_t)p.m * NT * 32 * sizeof(float);
   if (lds > 160 * 1024)
     return fail(RQ_EUNSUPPORTED, "wide encode: m=%d sub-quantizers of h=%d need %zu B of LDS", p.m, p.h, lds);
-  auto kern = encode_wide_kernel<NT, NW>;
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)lds));
   const int64_t ngroups = ((p.n + 31) / 32 + NW - 1) / NW;
   const int grid = (int)std::min<int64_t>(num_cu, ngroups);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, stream, p);
-  RQ_HIP(hipGetLastError());
+  RQ_LAUNCH_LDS((encode_wide_kernel<NT, NW>), dim3(grid), dim3(NW * 64), lds, stream, p);
   return RQ_OK;
 }
 
@@ -907,12 +818,7 @@ __global__ __launch_bounds__(NWAVES * 64) void rotate_kernel(RotParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, hi = lane >> 5;
   float *xs = xs_all + (size_t)wave * (2 * KK * XS_STRIDE);
-  for (int idx = tid; idx < NT * KK * 64; idx += NWAVES * 64) {
-    const int l = idx & 63;
-    const int kk = (idx >> 6) % KK, t = (idx >> 6) / KK;
-    const int i = t * 32 + (l & 31), k = 2 * kk + (l >> 5);
-    RA[idx] = (i < d && k < d) ? p.R[(size_t)i * d + k] : 0.0f;
-  }
+  stage_rotation_A<true>(RA, p.R, d, NT, KK, tid, NWAVES * 64);
   __syncthreads();
   const int64_t ntiles = (p.n + 31) / 32;
   const int64_t total_waves = (int64_t)gridDim.x * NWAVES;
@@ -944,13 +850,7 @@ __global__ __launch_bounds__(NWAVES * 64) void rotate_kernel(RotParams p) {
         float *o = p.RX + (size_t)(row0 + j) * d;
         const int ibase = t * 32 + 4 * hi;
         if ((d & 3) == 0) {
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const int i0 = ibase + 8 * g4;
-            if (i0 < d)
-              *reinterpret_cast<float4 *>(o + i0) =
-                  make_float4(acc[g4 * 4 + 0], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]);
-          }
+          store_rotated_tile(o, acc, ibase, d);
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -1108,48 +1008,34 @@ __global__ __launch_bounds__(NWAVES * 64) void rotate_wide2_kernel(RotParams p) 
       if (row0 + j < p.n) {
         float *o = p.RX + (size_t)(row0 + j) * d;
 #pragma unroll
-        for (int t = 0; t < TG; ++t) {
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const int i0 = (g0 + t) * 32 + 4 * hi + 8 * g4;
-            if (i0 < d)
-              *reinterpret_cast<float4 *>(o + i0) = make_float4(acc[t][g4 * 4 + 0], acc[t][g4 * 4 + 1], acc[t][g4 * 4 + 2], acc[t][g4 * 4 + 3]);
-          }
-        }
+        for (int t = 0; t < TG; ++t) store_rotated_tile(o, acc[t], (g0 + t) * 32 + 4 * hi, d);
       }
     }
   }
 }
 
 // Rotation, fast path for d % 8 == 0 (KK = d/2 compile time): the 32 x d tile of X never touches
-// LDS.  Lane (j, hi) loads the 16-byte pieces X[j][8q + 4hi .. +3]; two v_permlane32_swap per piece
-// pair turn them into the B fragments of k-steps 4q..4q+3 (lanes 0-31 the even, 32-63 the odd
-// dimension of each step).  R stays in LDS in A-fragment order, so LDS holds only d*d*4 bytes and a
+// LDS.  Lane (j, hi) loads the pieces X[j][8q + 4hi .. +3] (Rows: 16 bytes of f32 rows, or 4 bytes of byte rows widened in
+// registers); two v_permlane32_swap per piece turn them into the B fragments of k-steps 4q..4q+3 (lanes 0-31 the even, 32-63
+// the odd dimension of each step).  R stays in LDS in A-fragment order, so LDS holds only d*d*4 bytes and a
 // workgroup can run 8-16 wavefronts; loads of the next tile are issued before the MFMA chains.
-template <int KK, int NWAVES>
+template <int KK, int NWAVES, class Rows>
 __global__ __launch_bounds__(NWAVES * 64) void rotate_kernel_v2(RotParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int D = 2 * KK, NT = (D + 31) / 32, NP = D / 8;   // NP 16-byte pieces per lane
+  constexpr int D = 2 * KK, NT = (D + 31) / 32, NP = D / 8;   // NP pieces per lane
   float *RA = reinterpret_cast<float *>(smem);                 // NT*KK*64
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, hi = lane >> 5;
-  for (int idx = tid; idx < NT * KK * 64; idx += NWAVES * 64) {
-    const int l = idx & 63;
-    const int kk = (idx >> 6) % KK, t = (idx >> 6) / KK;
-    const int i = t * 32 + (l & 31), k = 2 * kk + (l >> 5);
-    RA[idx] = (i < D) ? p.R[(size_t)i * D + k] : 0.0f;
-  }
+  stage_rotation_A<false>(RA, p.R, D, NT, KK, tid, NWAVES * 64);
   __syncthreads();
   const int64_t ntiles = (p.n + 31) / 32;
   const int64_t total_waves = (int64_t)gridDim.x * NWAVES;
   const int64_t tile0 = (int64_t)blockIdx.x * NWAVES + wave;
-  float4 nx[NP];
+  Rows rows(p.X);
   auto gload = [&](int64_t tile) {
     int64_t gr = tile * 32 + j;
     if (gr >= p.n) gr = p.n - 1;
-    const float4 *src = reinterpret_cast<const float4 *>(p.X + gr * D + 4 * hi);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) nx[q] = src[2 * q];
+    rows.issue(gr, hi);
   };
   if (tile0 < ntiles) gload(tile0);
   for (int64_t tile = tile0; tile < ntiles; tile += total_waves) {
@@ -1157,14 +1043,15 @@ __global__ __launch_bounds__(NWAVES * 64) void rotate_kernel_v2(RotParams p) {
     float b[KK];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      float x = nx[q].x, y = nx[q].y, z = nx[q].z, w = nx[q].w;
+      const float4 v = rows.piece(q);
+      float x = v.x, y = v.y, z = v.z, w = v.w;
       swap32(x, y);   // x: dims (8q, 8q+1) = k-step 4q      y: dims (8q+4, 8q+5) = k-step 4q+2
       swap32(z, w);   // z: dims (8q+2, 8q+3) = k-step 4q+1  w: dims (8q+6, 8q+7) = k-step 4q+3
       b[4 * q + 0] = x; b[4 * q + 1] = z; b[4 * q + 2] = y; b[4 * q + 3] = w;
     }
 #pragma unroll 1      // (unrolled, so that a tile's stores overlap the next chain: spills, 0.31 -> 0.61 ms)
     for (int t = 0; t < NT; ++t) {
-      // next tile's loads go out under the last chain of this one (keeps nx's live range short)
+      // next tile's loads go out under the last chain of this one (keeps the pieces' live range short)
       if (t == NT - 1 && tile + total_waves < ntiles) gload(tile + total_waves);
       f32x16 acc;
 #pragma unroll
@@ -1172,17 +1059,7 @@ __global__ __launch_bounds__(NWAVES * 64) void rotate_kernel_v2(RotParams p) {
       const float *ra = RA + (size_t)t * KK * 64 + lane;
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[kk * 64], b[kk], acc, 0, 0, 0);
-      if (row0 + j < p.n) {
-        float *o = p.RX + (size_t)(row0 + j) * D;
-        const int ibase = t * 32 + 4 * hi;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int i0 = ibase + 8 * g4;
-          if (i0 < D)
-            *reinterpret_cast<float4 *>(o + i0) =
-                make_float4(acc[g4 * 4 + 0], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]);
-        }
-      }
+      if (row0 + j < p.n) store_rotated_tile(p.RX + (size_t)(row0 + j) * D, acc, t * 32 + 4 * hi, D);
     }
   }
 }
@@ -1191,23 +1068,29 @@ __global__ __launch_bounds__(NWAVES * 64) void rotate_kernel_v2(RotParams p) {
 #define RQ_ROT_NW 8
 #endif
 template <int KK>
-static int launch_rotate_v2(const RotParams &p, int num_cu, hipStream_t stream) {
+static int launch_rotate_v2(const RotParams &p, bool bytes, int num_cu, hipStream_t stream) {
   constexpr int NW = RQ_ROT_NW;
   constexpr int NT = (2 * KK + 31) / 32;
   const size_t lds = (size_t)NT * KK * 64 * sizeof(float);
-  auto kern = rotate_kernel_v2<KK, NW>;
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const auto kern = bytes ? rotate_kernel_v2<KK, NW, RowsU8<2 * KK>> : rotate_kernel_v2<KK, NW, RowsF32<2 * KK>>;
   const int64_t ntiles = (p.n + 31) / 32;
   const int grid = (int)std::min<int64_t>(num_cu, (ntiles + NW - 1) / NW);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, stream, p);
-  RQ_HIP(hipGetLastError());
+  RQ_LAUNCH_LDS(kern, dim3(grid), dim3(NW * 64), lds, stream, p);
   return RQ_OK;
 }
 
-__global__ void widen_codes_kernel(int16_t *out1, const uint8_t *codes, size_t nelem) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nelem) out1[i] = (int16_t)((int)codes[i] + 1);  // src/PQ.jl:45-47: Int16, one-based
+int rotate_v2_launch(float *RX, const float *R, const void *X, bool bytes, int d, int64_t n, int num_cu, hipStream_t stream) {
+  RotParams p;
+  p.R = R; p.X = reinterpret_cast<const float *>(X); p.RX = RX; p.n = n; p.d = d;   // (the byte loader reads X as uint8 [n][d])
+  p.NT = (d + 31) / 32;
+  p.KK = d / 2;
+  switch (d) {
+    case 32: return launch_rotate_v2<16>(p, bytes, num_cu, stream);
+    case 64: return launch_rotate_v2<32>(p, bytes, num_cu, stream);
+    case 96: return launch_rotate_v2<48>(p, bytes, num_cu, stream);
+    case 128: return launch_rotate_v2<64>(p, bytes, num_cu, stream);
+    default: return fail(RQ_EUNSUPPORTED, "rotate_kernel_v2 covers d in {32, 64, 96, 128}; got d=%d", d);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1235,10 +1118,7 @@ static int launch_encode(EncParams p, int num_cu, hipStream_t stream) {
     p.i0 = i0;
     p.i1 = std::min(p.m, i0 + gmax);
     const size_t lds = per_sub * (size_t)(p.i1 - p.i0) + fixed;
-    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWAVES * 64), lds, stream, p);
-    RQ_HIP(hipGetLastError());
+    RQ_LAUNCH_LDS(kern, dim3(grid), dim3(NWAVES * 64), lds, stream, p);
   }
   return RQ_OK;
 }
@@ -1258,11 +1138,18 @@ static int launch_encode_split(EncParams p, int num_cu, hipStream_t stream) {
     p.i0 = i0;
     p.i1 = std::min(p.m, i0 + gmax);
     const size_t lds = per_sub * (size_t)(p.i1 - p.i0) + 64;
-    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWAVES * 64), lds, stream, p);
-    RQ_HIP(hipGetLastError());
+    RQ_LAUNCH_LDS(kern, dim3(grid), dim3(NWAVES * 64), lds, stream, p);
   }
   return RQ_OK;
+}
+
+// fn(NT) with the compile-time NT in {1, 2, 4, 8} that holds nt <= 8 tiles of 32 centroids
+template <class F>
+static int by_nt(int nt, F fn) {
+  if (nt <= 1) return fn(std::integral_constant<int, 1>{});
+  if (nt <= 2) return fn(std::integral_constant<int, 2>{});
+  if (nt <= 4) return fn(std::integral_constant<int, 4>{});
+  return fn(std::integral_constant<int, 8>{});
 }
 
 static thread_local int g_last_encode_kernel = 0;      // 1 split, 2 f32-MFMA direct (X in registers), 3 f32-MFMA LDS-staged, 4 wide
@@ -1294,16 +1181,7 @@ int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int
   // find where codes first change -- the measured safety factor of the filter (tests/test_gpu_encode_margin.py)
   p.delta_rel = (float)tuning("ENC_SPLIT_DELTA_MILLI", 3000) * 1e-3f * 6.103515625e-05f;
   p.dbg_w = dbg_w;
-  const int per = d / m, extra = d % m;
-  int pos = 0, maxsub = 0;
-  for (int i = 0; i < m; ++i) {
-    p.off[i] = pos;
-    const int s = per + (i < extra ? 1 : 0);
-    pos += s;
-    maxsub = std::max(maxsub, s);
-  }
-  p.off[m] = pos;
-  const int ks = (maxsub + 1) / 2;
+  const int ks = (split_offsets(p.off, d, m) + 1) / 2;
   const int nw = tuning("ENC_WAVES", 16);
   const int nt = (h + 31) / 32;
   // even sub-space widths up to 16 (BASELINE's 16 and 6): bf16 matrix-core filter + exact re-evaluation of the candidates
@@ -1317,10 +1195,7 @@ int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int
 #define RQ_SPLIT_NT(SUBV, NW)                                                        \
   do {                                                                               \
     g_last_encode_kernel = 1;                                                        \
-    if (nt <= 1) return launch_encode_split<SUBV, 1, NW>(p, num_cu, stream);           \
-    if (nt <= 2) return launch_encode_split<SUBV, 2, NW>(p, num_cu, stream);           \
-    if (nt <= 4) return launch_encode_split<SUBV, 4, NW>(p, num_cu, stream);           \
-    return launch_encode_split<SUBV, 8, NW>(p, num_cu, stream);                        \
+    return by_nt(nt, [&](auto NT) { return launch_encode_split<SUBV, decltype(NT)::value, NW>(p, num_cu, stream); }); \
   } while (0)
 #define RQ_SPLIT_CASE(SUBV)                                                          \
   if (d / m == SUBV) {                                                               \
@@ -1337,10 +1212,7 @@ int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int
 #define RQ_ENC_NT(KSV, NW, DIR)                                             \
   do {                                                                     \
     g_last_encode_kernel = DIR ? 2 : 3;                                    \
-    if (nt <= 1) return launch_encode<KSV, 1, NW, DIR>(p, num_cu, stream);  \
-    if (nt <= 2) return launch_encode<KSV, 2, NW, DIR>(p, num_cu, stream);  \
-    if (nt <= 4) return launch_encode<KSV, 4, NW, DIR>(p, num_cu, stream);  \
-    return launch_encode<KSV, 8, NW, DIR>(p, num_cu, stream);               \
+    return by_nt(nt, [&](auto NT) { return launch_encode<KSV, decltype(NT)::value, NW, DIR>(p, num_cu, stream); }); \
   } while (0)
   // fast path: every sub-quantizer exactly 2*KS wide and rows 8-byte aligned -> X straight to registers,
   // 8 or 16 wavefronts per workgroup; otherwise the LDS-staged kernel (8 wavefronts)
@@ -1373,10 +1245,7 @@ int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int
 #undef RQ_ENC_CASE
   // any other width: chunked kernel, codebook streamed through LDS
   g_last_encode_kernel = 4;
-  if (nt <= 1) return launch_encode_wide<1>(p, num_cu, stream);
-  if (nt <= 2) return launch_encode_wide<2>(p, num_cu, stream);
-  if (nt <= 4) return launch_encode_wide<4>(p, num_cu, stream);
-  return launch_encode_wide<8>(p, num_cu, stream);
+  return by_nt(nt, [&](auto NT) { return launch_encode_wide<decltype(NT)::value>(p, num_cu, stream); });
 }
 
 // Byte rows (rq_encode_bytes.hip): the filter + exact pass with byte loaders covers what the f32 dispatch above gives to
@@ -1406,15 +1275,9 @@ int rotate_launch(float *RX, const float *R, const float *X, int d, int64_t n, i
   p.R = R; p.X = X; p.RX = RX; p.n = n; p.d = d;
   p.NT = (d + 31) / 32;
   p.KK = (d + 1) / 2;
-  if (tuning("ROT_V2", 1) && ((uintptr_t)X & 15) == 0) {
-    switch (d) {
-      case 32: return launch_rotate_v2<16>(p, num_cu, stream);
-      case 64: return launch_rotate_v2<32>(p, num_cu, stream);
-      case 96: return launch_rotate_v2<48>(p, num_cu, stream);
-      case 128: return launch_rotate_v2<64>(p, num_cu, stream);
-      default: break;   // other d: generic LDS-staged kernel below
-    }
-  }
+  // other d (and unaligned rows): the generic LDS-staged kernels below
+  if (tuning("ROT_V2", 1) && ((uintptr_t)X & 15) == 0 && (d == 32 || d == 64 || d == 96 || d == 128))
+    return rotate_v2_launch(RX, R, X, false, d, n, num_cu, stream);
   constexpr int NW = 4;
   const size_t lds = ((size_t)p.NT * p.KK * 64 + (size_t)NW * 2 * p.KK * XS_STRIDE) * sizeof(float);
   if (lds > 160 * 1024) {
@@ -1422,93 +1285,78 @@ int rotate_launch(float *RX, const float *R, const float *X, int d, int64_t n, i
     constexpr int TG = 8, KC = 32;
     if (tuning("ROT_WIDE2", 1) && (d & 3) == 0 && (((uintptr_t)X | (uintptr_t)R | (uintptr_t)RX) & 15) == 0) {
       const size_t lds2 = ((size_t)TG * (KC / 2) * RW_RA_STRIDE + (size_t)NW * KC * XS_STRIDE) * sizeof(float);
-      auto wk2 = rotate_wide2_kernel<NW, TG>;
-      RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wk2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
       const int64_t nb2 = ((n + 31) / 32 + NW - 1) / NW;
-      hipLaunchKernelGGL(wk2, dim3((int)std::min<int64_t>(2 * (int64_t)num_cu, nb2)), dim3(NW * 64), lds2, stream, p);
-      RQ_HIP(hipGetLastError());
+      RQ_LAUNCH_LDS((rotate_wide2_kernel<NW, TG>), dim3((int)std::min<int64_t>(2 * (int64_t)num_cu, nb2)), dim3(NW * 64), lds2,
+                    stream, p);
       return RQ_OK;
     }
     const size_t wlds = ((size_t)TG * (KC / 2) * 64 + (size_t)NW * KC * XS_STRIDE) * sizeof(float);
-    auto wk = rotate_wide_kernel<NW, TG, KC>;
-    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds));
     const int64_t nb = ((n + 31) / 32 + NW - 1) / NW;
-    hipLaunchKernelGGL(wk, dim3((int)std::min<int64_t>(2 * (int64_t)num_cu, nb)), dim3(NW * 64), wlds, stream, p);
-    RQ_HIP(hipGetLastError());
+    RQ_LAUNCH_LDS((rotate_wide_kernel<NW, TG, KC>), dim3((int)std::min<int64_t>(2 * (int64_t)num_cu, nb)), dim3(NW * 64), wlds,
+                  stream, p);
     return RQ_OK;
   }
-  auto kern = rotate_kernel<NW>;
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t ntiles = (n + 31) / 32;
   const int grid = (int)std::min<int64_t>(num_cu, (ntiles + NW - 1) / NW);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, stream, p);
-  RQ_HIP(hipGetLastError());
+  RQ_LAUNCH_LDS(rotate_kernel<NW>, dim3(grid), dim3(NW * 64), lds, stream, p);
   return RQ_OK;
 }
 
-// RVQ stage epilogue (src/RVQ.jl:56  Xr .-= C[i][:, B[i]]): Xr[j][:] -= C_i[code_j][:], the stage's
-// codes go to column `stage` of the [n][m] code matrix, and the per-centre counts of the stage
-// (update_assignments!'s `counts`, src/RVQ.jl:43-47) are accumulated.  One thread per float4 of Xr.
-__global__ __launch_bounds__(256) void rvq_residual_kernel(float *Xr, const float *Ci, const uint8_t *stage_codes,
-                                                           uint8_t *codes, unsigned int *counts, int64_t n, int d,
-                                                           int m, int stage) {
-  const int d4 = d >> 2;   // d % 4 == 0 on this path
+// RVQ / ERVQ stage epilogue (src/RVQ.jl:56  Xr .-= C[i][:, B[i]]): dst[row][:] = src[row][:] - Cj[code][:] with code =
+// codes_in[row * in_stride]; the code goes to column `stage` of the [n][m] matrix codes_out (may be NULL) and the per-centre
+// counts of the stage (update_assignments!'s `counts`, src/RVQ.jl:43-47; may be NULL) are accumulated.  dst may be src: every
+// element is read and written by its own thread.  One thread per W floats (W = 4: d % 4 == 0 and 16-byte aligned pointers).
+template <int W, class Code>
+__global__ __launch_bounds__(256) void residual_kernel(float *dst, const float *src, const float *__restrict__ Cj,
+                                                       const Code *codes_in, int in_stride, Code *codes_out,
+                                                       unsigned int *counts, int64_t n, int d, int m, int stage) {
+  using UCode = typename std::make_unsigned<Code>::type;
+  const int dw = d / W;
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * d4) return;
-  const int64_t j = e / d4;
-  const int c4 = (int)(e - j * d4);
-  const int code = stage_codes[j];
-  float4 x = reinterpret_cast<float4 *>(Xr)[e];
-  const float4 c = reinterpret_cast<const float4 *>(Ci)[(size_t)code * d4 + c4];
-  x.x = x.x - c.x; x.y = x.y - c.y; x.z = x.z - c.z; x.w = x.w - c.w;
-  reinterpret_cast<float4 *>(Xr)[e] = x;
-  if (c4 == 0) {
-    codes[j * m + stage] = (uint8_t)code;
+  if (e >= n * dw) return;
+  const int64_t row = e / dw;
+  const int c = (int)(e - row * dw);
+  const int code = (int)(UCode)codes_in[row * in_stride];
+  if constexpr (W == 4) {
+    float4 x = reinterpret_cast<const float4 *>(src)[e];
+    const float4 v = reinterpret_cast<const float4 *>(Cj)[(size_t)code * dw + c];
+    x.x = x.x - v.x; x.y = x.y - v.y; x.z = x.z - v.z; x.w = x.w - v.w;
+    reinterpret_cast<float4 *>(dst)[e] = x;
+  } else {
+    dst[e] = src[e] - Cj[(size_t)code * d + c];
+  }
+  if (c == 0) {
+    if (codes_out) codes_out[row * m + stage] = (Code)code;
     if (counts) atomicAdd(&counts[code], 1u);
   }
 }
 
-__global__ __launch_bounds__(256) void rvq_residual_scalar_kernel(float *Xr, const float *Ci, const uint8_t *stage_codes,
-                                                                  uint8_t *codes, unsigned int *counts, int64_t n,
-                                                                  int d, int m, int stage) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * d) return;
-  const int64_t j = e / d;
-  const int c = (int)(e - j * d);
-  const int code = stage_codes[j];
-  Xr[e] = Xr[e] - Ci[(size_t)code * d + c];
-  if (c == 0) {
-    codes[j * m + stage] = (uint8_t)code;
-    if (counts) atomicAdd(&counts[code], 1u);
-  }
+template <class Code>
+int residual_launch(float *dst, const float *src, const float *Cj, const Code *codes_in, int in_stride, Code *codes_out,
+                    unsigned int *counts, int64_t n, int d, int m, int stage, hipStream_t stream) {
+  const bool vec = (d & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)Cj) & 15) == 0;
+  const int per_row = vec ? d >> 2 : d;     // one thread per float4 (or float)
+  return for_slices(n, [&](int64_t r0, int64_t nr) {
+    const auto kern = vec ? residual_kernel<4, Code> : residual_kernel<1, Code>;
+    RQ_LAUNCH(kern, dim3((uint32_t)((nr * per_row + 255) / 256)), dim3(256), 0, stream, dst + (size_t)r0 * d,
+              src + (size_t)r0 * d, Cj, codes_in + (size_t)r0 * in_stride, in_stride, codes_out ? codes_out + (size_t)r0 * m : nullptr,
+              counts, nr, d, m, stage);
+    return RQ_OK;
+  }, per_row);
+}
+template int residual_launch(float *, const float *, const float *, const uint8_t *, int, uint8_t *, unsigned int *, int64_t, int,
+                             int, int, hipStream_t);
+template int residual_launch(float *, const float *, const float *, const int16_t *, int, int16_t *, unsigned int *, int64_t, int,
+                             int, int, hipStream_t);
+
+int rvq_residual_launch(float *Xr, const float *Ci, const uint8_t *stage_codes, uint8_t *codes, unsigned int *cnt,
+                        int64_t n, int d, int m, int stage, hipStream_t stream) {
+  return residual_launch(Xr, Xr, Ci, stage_codes, 1, codes, cnt, n, d, m, stage, stream);
 }
 
 // quantize_rvq (src/RVQ.jl:18-66) on resident data: m full-dimensional stages, each the encode kernel
 // with one sub-quantizer of width d on the running residual.  Xr [n][d] is overwritten (in: X or a copy
 // of it, out: the final residual); stage_codes is n bytes of scratch; counts is [m][h] or NULL.
-// one stage's epilogue: Xr -= Ci[stage_codes], codes[:, stage] = stage_codes, cnt[code] += 1 (cnt may be NULL)
-int rvq_residual_launch(float *Xr, const float *Ci, const uint8_t *stage_codes, uint8_t *codes, unsigned int *cnt,
-                        int64_t n, int d, int m, int stage, hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
-  // one thread per float4 (or float) of Xr, in row slices of at most LAUNCH_MAX_THREADS threads
-  const bool vec = (d & 3) == 0 && (((uintptr_t)Xr | (uintptr_t)Ci) & 15) == 0;
-  const int per_row = vec ? d >> 2 : d;
-  const int64_t rows = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per_row);
-  for (int64_t r0 = 0; r0 < n; r0 += rows) {
-    const int64_t nr = std::min(rows, n - r0);
-    const dim3 grid((uint32_t)((nr * per_row + 255) / 256));
-    if (vec)
-      hipLaunchKernelGGL(rvq_residual_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
-                         codes + (size_t)r0 * m, cnt, nr, d, m, stage);
-    else
-      hipLaunchKernelGGL(rvq_residual_scalar_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
-                         codes + (size_t)r0 * m, cnt, nr, d, m, stage);
-    RQ_HIP(hipGetLastError());
-  }
-  return RQ_OK;
-}
-
 int rvq_encode_launch(uint8_t *codes, float *Xr, uint8_t *stage_codes, unsigned int *counts, const float *C,
                       int64_t n, int d, int m, int h, int num_cu, hipStream_t stream) {
   if (n <= 0) return RQ_OK;
@@ -1521,15 +1369,32 @@ int rvq_encode_launch(uint8_t *codes, float *Xr, uint8_t *stage_codes, unsigned 
   return RQ_OK;
 }
 
+// Element-wise code conversion out[i] = in[i] + add: zero-based bytes <-> Julia's one-based Matrix{Int16} (src/PQ.jl:45-47),
+// bytes -> zero-based Int16, Int16 += base in place.  out may be in when the types agree.
+template <class Out, class In>
+__global__ __launch_bounds__(256) void convert_codes_kernel(Out *out, const In *in, size_t nelem, int add) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nelem) out[i] = (Out)((int)in[i] + add);
+}
+
+template <class Out, class In>
+int convert_codes_launch(Out *out, const In *in, int64_t nelem, int add, hipStream_t stream) {
+  if (add == 0 && (const void *)out == (const void *)in) return RQ_OK;
+  return for_slices(nelem, [&](int64_t e0, int64_t ne) {
+    RQ_LAUNCH((convert_codes_kernel<Out, In>), dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, out + e0, in + e0,
+              (size_t)ne, add);
+    return RQ_OK;
+  });
+}
+template int convert_codes_launch(int16_t *, const uint8_t *, int64_t, int, hipStream_t);
+template int convert_codes_launch(int16_t *, const int16_t *, int64_t, int, hipStream_t);
+template int convert_codes_launch(uint8_t *, const int16_t *, int64_t, int, hipStream_t);
+
 int widen_codes_launch(int16_t *out1, const uint8_t *codes, int64_t nelem, hipStream_t stream) {
-  if (nelem <= 0) return RQ_OK;
-  for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
-    const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
-    hipLaunchKernelGGL(widen_codes_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, out1 + e0,
-                       codes + e0, (size_t)ne);
-    RQ_HIP(hipGetLastError());
-  }
-  return RQ_OK;
+  return convert_codes_launch(out1, codes, nelem, 1, stream);
+}
+int add_base_codes_launch(int16_t *codes, int64_t nelem, int base, hipStream_t stream) {
+  return convert_codes_launch(codes, (const int16_t *)codes, nelem, base, stream);
 }
 
 }  // namespace rq

@@ -234,28 +234,6 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
   }
 }
 
-__global__ void widen0_codes_kernel(int16_t *out, const uint8_t *codes, size_t nelem) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nelem) out[i] = (int16_t)codes[i];
-}
-
-// the 16-bit sibling of widen_codes_kernel: zero-based codes -> Julia's one-based Matrix{Int16} (src/PQ.jl:45-47), in place
-__global__ void add_base_codes_kernel(int16_t *codes, size_t nelem, int base) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nelem) codes[i] = (int16_t)(codes[i] + base);
-}
-
-int add_base_codes_launch(int16_t *codes, int64_t nelem, int base, hipStream_t stream) {
-  if (nelem <= 0 || base == 0) return RQ_OK;
-  for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
-    const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
-    hipLaunchKernelGGL(add_base_codes_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, codes + e0, (size_t)ne,
-                       base);
-    RQ_HIP(hipGetLastError());
-  }
-  return RQ_OK;
-}
-
 // codes [n][m] int16 zero-based.  h <= 256: the kernels of rq_encode.hip into scratch, widened (the u8 entry points' codes by
 // construction); above: the norms pass and encode_h16_kernel.  Everything on `stream`.
 int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
@@ -268,24 +246,11 @@ int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n,
     void *tmp = nullptr;
     RQ_TRY(workspace(WS_H16_CODES, (size_t)n * m, &tmp, stream));
     RQ_TRY(encode_launch((uint8_t *)tmp, X, C, n, d, m, h, num_cu, stream));
-    const int64_t nelem = n * m;
-    for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
-      const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
-      hipLaunchKernelGGL(widen0_codes_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, codes + e0,
-                         (const uint8_t *)tmp + e0, (size_t)ne);
-      RQ_HIP(hipGetLastError());
-    }
-    return RQ_OK;
+    return convert_codes_launch(codes, (const uint8_t *)tmp, n * m, 0, stream);
   }
   H16Params p;
   p.X = X; p.C = C; p.codes = codes; p.n = n; p.d = d; p.m = m; p.h = h;
-  const int per = d / m, extra = d % m;
-  int pos = 0;
-  for (int i = 0; i < m; ++i) {
-    p.off[i] = pos;
-    pos += per + (i < extra ? 1 : 0);
-  }
-  p.off[m] = pos;
+  split_offsets(p.off, d, m);
   void *sa = nullptr;
   RQ_TRY(workspace(WS_H16_SA, (size_t)m * h * sizeof(float), &sa, stream));
   p.sa = (const float *)sa;
@@ -299,41 +264,6 @@ int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n,
   return RQ_OK;
 }
 
-// ---- RVQ stage epilogue on 16-bit codes (rvq_residual_kernel / rvq_residual_scalar_kernel of rq_encode.hip) ------------------
-__global__ __launch_bounds__(256) void rvq16_residual_kernel(float *Xr, const float *Ci, const int16_t *stage_codes,
-                                                             int16_t *codes, unsigned int *counts, int64_t n, int d, int m,
-                                                             int stage) {
-  const int d4 = d >> 2;   // d % 4 == 0 on this path
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * d4) return;
-  const int64_t j = e / d4;
-  const int c4 = (int)(e - j * d4);
-  const int code = (int)(uint16_t)stage_codes[j];
-  float4 x = reinterpret_cast<float4 *>(Xr)[e];
-  const float4 c = reinterpret_cast<const float4 *>(Ci)[(size_t)code * d4 + c4];
-  x.x = x.x - c.x; x.y = x.y - c.y; x.z = x.z - c.z; x.w = x.w - c.w;
-  reinterpret_cast<float4 *>(Xr)[e] = x;
-  if (c4 == 0) {
-    codes[j * m + stage] = (int16_t)code;
-    if (counts) atomicAdd(&counts[code], 1u);
-  }
-}
-
-__global__ __launch_bounds__(256) void rvq16_residual_scalar_kernel(float *Xr, const float *Ci, const int16_t *stage_codes,
-                                                                    int16_t *codes, unsigned int *counts, int64_t n, int d,
-                                                                    int m, int stage) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * d) return;
-  const int64_t j = e / d;
-  const int c = (int)(e - j * d);
-  const int code = (int)(uint16_t)stage_codes[j];
-  Xr[e] = Xr[e] - Ci[(size_t)code * d + c];
-  if (c == 0) {
-    codes[j * m + stage] = (int16_t)code;
-    if (counts) atomicAdd(&counts[code], 1u);
-  }
-}
-
 // quantize_rvq (src/RVQ.jl:18-66) with 16-bit codes on resident data: stage_codes is n int16 of scratch, counts [m][h] or NULL
 int rvq_h16_encode_launch(int16_t *codes, float *Xr, int16_t *stage_codes, unsigned int *counts, const float *C, int64_t n,
                           int d, int m, int h, int num_cu, hipStream_t stream) {
@@ -343,21 +273,7 @@ int rvq_h16_encode_launch(int16_t *codes, float *Xr, int16_t *stage_codes, unsig
     const float *Ci = C + (size_t)i * h * d;
     unsigned int *cnt = counts ? counts + (size_t)i * h : nullptr;
     RQ_TRY(encode_h16_launch(stage_codes, Xr, Ci, n, d, 1, h, num_cu, stream));
-    // one thread per float4 (or float) of Xr, in row slices of at most LAUNCH_MAX_THREADS threads (rvq_residual_launch)
-    const bool vec = (d & 3) == 0 && (((uintptr_t)Xr | (uintptr_t)Ci) & 15) == 0;
-    const int per_row = vec ? d >> 2 : d;
-    const int64_t rows = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per_row);
-    for (int64_t r0 = 0; r0 < n; r0 += rows) {
-      const int64_t nr = std::min(rows, n - r0);
-      const dim3 grid((uint32_t)((nr * per_row + 255) / 256));
-      if (vec)
-        hipLaunchKernelGGL(rvq16_residual_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
-                           codes + (size_t)r0 * m, cnt, nr, d, m, i);
-      else
-        hipLaunchKernelGGL(rvq16_residual_scalar_kernel, grid, dim3(256), 0, stream, Xr + (size_t)r0 * d, Ci, stage_codes + r0,
-                           codes + (size_t)r0 * m, cnt, nr, d, m, i);
-      RQ_HIP(hipGetLastError());
-    }
+    RQ_TRY(residual_launch(Xr, Xr, Ci, stage_codes, 1, codes, cnt, n, d, m, i, stream));
   }
   return RQ_OK;
 }

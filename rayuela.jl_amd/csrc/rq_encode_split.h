@@ -164,6 +164,97 @@ __device__ __forceinline__ int argmin_finish(const ArgminState &st, int hi) {
   return st.best_t * 32 + 4 * hi + 8 * (rf >> 2) + (rf & 3);
 }
 
+// Prologue: the codebooks of sub-quantizers [i0, i0 + mg) -> LDS in A-fragment order, cbA [mg][NT][KS][64]: lane l of k-step
+// kk holds C_i[t*32 + (l & 31)][2kk + (l >> 5)], zero past h and past the sub-space.  SUB > 0: every sub-space is SUB = 2 KS
+// wide (constant strides); SUB == 0: the widths of p.off.
+template <int KS, int NT, int SUB, int NTHREADS>
+__device__ __forceinline__ void stage_codebooks_A(float *cbA, const EncParams &p, int i0, int mg, int tid) {
+  const int h = p.h;
+  for (int idx = tid; idx < mg * NT * KS * 64; idx += NTHREADS) {
+    const int l = idx & 63;
+    int rest = idx >> 6;
+    const int kk = rest % KS; rest /= KS;
+    const int t = rest % NT;
+    const int i = i0 + rest / NT;
+    const int cen = t * 32 + (l & 31);
+    const int s = 2 * kk + (l >> 5);
+    if constexpr (SUB > 0) {
+      cbA[idx] = cen < h ? p.C[(size_t)h * SUB * i + (size_t)cen * SUB + s] : 0.0f;
+    } else {
+      const int sub = p.off[i + 1] - p.off[i];
+      float v = 0.0f;
+      if (cen < h && s < sub) v = p.C[(size_t)h * p.off[i] + (size_t)cen * sub + s];
+      cbA[idx] = v;
+    }
+  }
+}
+
+// Prologue: |c_k|^2 (the canonical chain s = 0..sub-1 from +0) of the same sub-quantizers -> LDS in C/D-fragment order,
+// saL [mg][NT][2][16], +Inf for the padded centroids k >= h.  SUB as above (the chain unrolls).
+template <int NT, int SUB, int NTHREADS>
+__device__ __forceinline__ void stage_norms_cd(float *saL, const EncParams &p, int i0, int mg, int tid) {
+  const int h = p.h;
+  for (int idx = tid; idx < mg * NT * 32; idx += NTHREADS) {
+    const int c32 = idx & 31;
+    const int t = (idx >> 5) % NT;
+    const int il = (idx >> 5) / NT;
+    const int i = i0 + il;
+    const int cen = t * 32 + c32;
+    float sa = __uint_as_float(0x7f800000u);
+    if (cen < h) {
+      sa = 0.0f;
+      if constexpr (SUB > 0) {
+        const float *c = p.C + (size_t)h * SUB * i + (size_t)cen * SUB;
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) sa = __builtin_fmaf(c[s], c[s], sa);
+      } else {
+        const int sub = p.off[i + 1] - p.off[i];
+        const float *c = p.C + (size_t)h * p.off[i] + (size_t)cen * sub;
+        for (int s = 0; s < sub; ++s) sa = __builtin_fmaf(c[s], c[s], sa);
+      }
+    }
+    const int hh = (c32 >> 2) & 1;
+    const int r = (c32 & 3) + 4 * (c32 >> 3);
+    saL[((size_t)(il * NT + t) * 2 + hh) * 16 + r] = sa;
+  }
+}
+
+// The code bytes of one vector (m <= 32) are gathered in uint64_t cw[4] over the sub-quantizers of a launch and written once
+// per tile.  (The gathering stays in the kernels: as a helper, in either of two forms, it moved cw into scratch or changed the
+// tile loop's instructions.)
+// o: the vector's m code bytes.  whole (m % 8 == 0 and the launch covers all m): 8-byte stores; else the bytes [i0, i1)
+__device__ __forceinline__ void codewords_store(const uint64_t (&cw)[4], uint8_t *o, int m, int i0, int i1, bool whole) {
+  if (whole) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+      if (w * 8 < m) reinterpret_cast<uint64_t *>(o)[w] = cw[w];
+  } else {
+    for (int i = i0; i < i1; ++i) o[i] = (uint8_t)(cw[i >> 3] >> (8 * (i & 7)));
+  }
+}
+
+// ---- building blocks of the rotation kernels (rq_encode.hip) -------------------------------------------------------------
+// R [d][d] -> LDS in A-fragment order, RA [NT][KK][64]: lane l of k-step kk holds R[t*32 + (l & 31)][2kk + (l >> 5)], zero
+// outside R (PAD_K: the last k-step reaches one dimension past an odd d)
+template <bool PAD_K>
+__device__ __forceinline__ void stage_rotation_A(float *RA, const float *R, int d, int NT, int KK, int tid, int nthreads) {
+  for (int idx = tid; idx < NT * KK * 64; idx += nthreads) {
+    const int l = idx & 63;
+    const int kk = (idx >> 6) % KK, t = (idx >> 6) / KK;
+    const int i = t * 32 + (l & 31), k = 2 * kk + (l >> 5);
+    RA[idx] = (i < d && (!PAD_K || k < d)) ? R[(size_t)i * d + k] : 0.0f;
+  }
+}
+// one lane's 16 outputs of a 32 x 32 tile -> o[ibase + 8 g4 .. + 3], g4 = 0..3, as float4 (d % 4 == 0, o 16-byte aligned)
+__device__ __forceinline__ void store_rotated_tile(float *o, const f32x16 &acc, int ibase, int d) {
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    const int i0 = ibase + 8 * g4;
+    if (i0 < d)
+      *reinterpret_cast<float4 *>(o + i0) = make_float4(acc[g4 * 4 + 0], acc[g4 * 4 + 1], acc[g4 * 4 + 2], acc[g4 * 4 + 3]);
+  }
+}
+
 // ---- byte rows (bvecs are UInt8, src/xvecs_read.jl:14-52; the reference widens them on the host, src/read_datasets.jl:148-167)
 // The byte kernels read X as uint8 and widen in registers: u8 -> f32 is exact, so every value the f32 kernels load from the
 // widened matrix is reproduced bit for bit, and everything after the loaders is the same code.
@@ -212,6 +303,48 @@ __device__ __forceinline__ void bytes_f32(const uint32_t *w, float *x) {
   if constexpr (S < N) { x[S] = byte_f32<S>(w); bytes_f32<N, S + 1>(w, x); }
 }
 
+// Row loaders of rotate_kernel_v2 (rq_encode.hip): lane (j, hi) keeps the NP = D / 8 pieces X[row][8q + 4hi .. +3] of its row
+// in flight.  issue() sends the loads of a row out, piece(q) is piece q as four floats.
+template <int D>
+struct RowsF32 {                 // 16-byte loads; X 16-byte aligned
+  static constexpr int NP = D / 8;
+  const float *X;
+  float4 nx[NP];
+  __device__ __forceinline__ explicit RowsF32(const float *x) : X(x) {}
+  __device__ __forceinline__ void issue(int64_t row, int hi) {
+    const float4 *src = reinterpret_cast<const float4 *>(X + row * D + 4 * hi);
+#pragma unroll
+    for (int q = 0; q < NP; ++q) nx[q] = src[2 * q];
+  }
+  __device__ __forceinline__ float4 piece(int q) const { return nx[q]; }
+};
+// Byte rows: one register per piece in flight instead of four, widened when the tile's turn comes (u8 -> f32 is exact, so R'X
+// is bit for bit that of the widened rows).  The pieces sit at X + row D + 8q + 4hi with D % 8 == 0: 4-byte loads when X is
+// 4-byte aligned, else 2-byte or single-byte loads.
+template <int D>
+struct RowsU8 {
+  static constexpr int NP = D / 8;
+  const uint8_t *X;
+  const int al;
+  uint32_t nx[NP];
+  __device__ __forceinline__ explicit RowsU8(const float *x) : X(reinterpret_cast<const uint8_t *>(x)), al(byte_align(x, D, 4)) {}
+  __device__ __forceinline__ void issue(int64_t row, int hi) {
+    const uint8_t *src = X + (size_t)row * D + 4 * hi;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      uint32_t w[1];
+      load_bytes<4>(src + 8 * q, al, 4, w);
+      nx[q] = w[0];
+    }
+  }
+  __device__ __forceinline__ float4 piece(int q) const {
+    return make_float4(byte_f32<0>(&nx[q]), byte_f32<1>(&nx[q]), byte_f32<2>(&nx[q]), byte_f32<3>(&nx[q]));
+  }
+};
+
+// rq_encode.hip: RX [n][d] <- R' x_j by rotate_kernel_v2, d in {32, 64, 96, 128}; X is f32 rows (16-byte aligned) or, with
+// `bytes`, uint8 rows of any alignment
+RQ_LOCAL int rotate_v2_launch(float *RX, const float *R, const void *X, bool bytes, int d, int64_t n, int num_cu, hipStream_t stream);
 // rq_encode_filter.hip: filter launch + exact pass per group of sub-quantizers that fits LDS (even widths <= 16)
 int encode_filter_launch(const EncParams &p, int sub, int nt, int waves, int num_cu, hipStream_t stream);
 // the same on byte rows: p.X reinterpreted as uint8 [n][d], any alignment (encode_pq_filter_bytes_kernel)

@@ -37,62 +37,6 @@ namespace rq {
 
 namespace {
 
-// Stage epilogue, out of place: dst[row][:] = src[row][:] - Cj[code][:] with code = codes_in[row * in_stride]; the code goes to
-// codes_out[row * m + stage] (codes_out may be NULL) and counts[code] (may be NULL) is incremented.  dst may be src: every
-// element is read and written by its own thread.  One thread per W floats (W = 4: d % 4 == 0 and 16-byte aligned pointers).
-template <int W>
-__global__ __launch_bounds__(256) void ervq_residual_kernel(float *dst, const float *src, const float *__restrict__ Cj,
-                                                            const uint8_t *codes_in, int in_stride, uint8_t *codes_out,
-                                                            unsigned int *counts, int64_t n, int d, int m, int stage) {
-  const int dw = d / W;
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * dw) return;
-  const int64_t row = e / dw;
-  const int c = (int)(e - row * dw);
-  const int code = codes_in[row * in_stride];
-  if constexpr (W == 4) {
-    float4 x = reinterpret_cast<const float4 *>(src)[e];
-    const float4 v = reinterpret_cast<const float4 *>(Cj)[(size_t)code * dw + c];
-    x.x = x.x - v.x; x.y = x.y - v.y; x.z = x.z - v.z; x.w = x.w - v.w;
-    reinterpret_cast<float4 *>(dst)[e] = x;
-  } else {
-    dst[e] = src[e] - Cj[(size_t)code * d + c];
-  }
-  if (c == 0) {
-    if (codes_out) codes_out[row * m + stage] = (uint8_t)code;
-    if (counts) atomicAdd(&counts[code], 1u);
-  }
-}
-
-int ervq_residual_launch(float *dst, const float *src, const float *Cj, const uint8_t *codes_in, int in_stride,
-                         uint8_t *codes_out, unsigned int *counts, int64_t n, int d, int m, int stage, hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
-  const bool vec = (d & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)Cj) & 15) == 0;
-  // one thread per float4 (or float), in row slices of at most LAUNCH_MAX_THREADS threads: any n
-  const int per_row = vec ? d >> 2 : d;
-  const int64_t rows = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per_row);
-  for (int64_t r0 = 0; r0 < n; r0 += rows) {
-    const int64_t nr = std::min(rows, n - r0);
-    const dim3 grid((uint32_t)((nr * per_row + 255) / 256));
-    float *ds = dst + (size_t)r0 * d;
-    const float *ss = src + (size_t)r0 * d;
-    const uint8_t *ci = codes_in + (size_t)r0 * in_stride;
-    uint8_t *co = codes_out ? codes_out + (size_t)r0 * m : nullptr;
-    if (vec)
-      hipLaunchKernelGGL(ervq_residual_kernel<4>, grid, dim3(256), 0, stream, ds, ss, Cj, ci, in_stride, co, counts, nr, d, m, stage);
-    else
-      hipLaunchKernelGGL(ervq_residual_kernel<1>, grid, dim3(256), 0, stream, ds, ss, Cj, ci, in_stride, co, counts, nr, d, m, stage);
-    RQ_HIP(hipGetLastError());
-  }
-  return RQ_OK;
-}
-
-// one-based Int16 codes -> zero-based bytes (the inverse of widen_codes_launch; the range was checked on the host)
-__global__ __launch_bounds__(256) void ervq_narrow_kernel(uint8_t *codes, const int16_t *B1, size_t nelem) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < nelem) codes[e] = (uint8_t)(B1[e] - 1);
-}
-
 // Costs of the refill, f64, one thread per row, the d terms in ascending order (the host loop of repick_unused bit for bit):
 // BY_CODE: tc[row] = |P[row] - Cref[code(row)]|^2 (Cref [h][d]); else tc[row] = min(tc[row], |P[row] - Cref|^2) (Cref [d]).
 template <bool BY_CODE>
@@ -145,7 +89,7 @@ int ervq_refill(float *Cj, const float *Cold, const float *P, const uint8_t *cod
 // E = X - sum_i C_i[b_i] by m in-place epilogues in codebook order (the order quantize_rvq subtracts in)
 int ervq_full_residual(float *E, const float *C, const uint8_t *codes, int64_t n, int d, int m, int h, hipStream_t stream) {
   for (int i = 0; i < m; ++i)
-    RQ_TRY(ervq_residual_launch(E, E, C + (size_t)i * h * d, codes + i, m, nullptr, nullptr, n, d, m, i, stream));
+    RQ_TRY(residual_launch<uint8_t>(E, E, C + (size_t)i * h * d, codes + i, m, nullptr, nullptr, n, d, m, i, stream));
   return RQ_OK;
 }
 
@@ -226,12 +170,8 @@ extern "C" int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, 
   float *Xd = dX.as<float>(), *W = dW.as<float>(), *Cd = dC.as<float>();
   uint8_t *codes = dcodes.as<uint8_t>(), *stage = dstage.as<uint8_t>();
   double *objd = dobj.as<double>();
-  for (int64_t e0 = 0; e0 < n * m; e0 += LAUNCH_MAX_THREADS) {
-    const int64_t ne = std::min(LAUNCH_MAX_THREADS, n * m - e0);
-    hipLaunchKernelGGL(ervq_narrow_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, s, codes + e0,
-                       d16.as<int16_t>() + e0, (size_t)ne);
-    RQ_HIP(hipGetLastError());
-  }
+  // one-based Int16 codes -> zero-based bytes (the range was checked on the host)
+  RQ_TRY(convert_codes_launch(codes, (const int16_t *)d16.as<int16_t>(), n * m, -1, s));
   clk.mark(EV_OTHER);
   // E of the caller's codes and codebooks, and its error
   RQ_HIP(hipMemcpyAsync(W, Xd, xb, hipMemcpyDeviceToDevice, s));
@@ -269,13 +209,13 @@ extern "C" int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, 
         RQ_TRY(encode_launch(stage, src, Ci, n, d, 1, h, di.num_cu, s));
         clk.mark(EV_ENCODE);
         if (i == j && j + 1 < m) {
-          RQ_TRY(ervq_residual_launch(Pnext, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
+          RQ_TRY(residual_launch(Pnext, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
           src = Pnext;
         } else if (src != W) {
-          RQ_TRY(ervq_residual_launch(W, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
+          RQ_TRY(residual_launch(W, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
           src = W;
         } else {
-          RQ_TRY(rvq_residual_launch(W, Ci, stage, codes, nullptr, n, d, m, i, s));
+          RQ_TRY(residual_launch(W, W, Ci, stage, 1, codes, nullptr, n, d, m, i, s));
         }
         clk.mark(EV_EPILOGUE);
       }

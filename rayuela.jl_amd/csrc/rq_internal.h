@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -47,7 +48,26 @@ void forgive_oom();
     RQ_HIP(hipGetLastError());        \
   } while (0)
 
+// the same for a kernel that needs dynamic LDS: the limit is set on every launch (it is per device and may have been set
+// for another LDS size by the previous call)
+#define RQ_LAUNCH_LDS(kern, grid, block, lds, stream, ...)                                               \
+  do {                                                                                                    \
+    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                               (int)(lds)));                                                              \
+    RQ_LAUNCH(kern, grid, block, lds, stream, __VA_ARGS__);                                               \
+  } while (0)
+
 int tuning(const char *key, int dflt);  // env RQ_<KEY> or rq_set_tuning override
+
+// splitarray offsets (src/utils.jl:179-203): sub-space i of m spans dimensions [off[i], off[i + 1]) of d, the first d % m
+// one wider than the rest.  Fills off[0..m]; returns the widest sub-space.
+inline int split_offsets(int *off, int d, int m) {
+  const int per = d / m, extra = d % m;
+  int pos = 0;
+  for (int i = 0; i < m; ++i) { off[i] = pos; pos += per + (i < extra ? 1 : 0); }
+  off[m] = pos;
+  return per + (extra ? 1 : 0);
+}
 
 struct DeviceInfo {
   int device;
@@ -62,6 +82,14 @@ int device_info(DeviceInfo *out);
 // does not fail, it wraps and runs the remainder only.  Launches of one thread or one wavefront per element of an n-sized
 // array therefore go in slices of at most LAUNCH_MAX_THREADS work-items (tests/test_gpu_large_offsets.py runs them past it).
 constexpr int64_t LAUNCH_MAX_THREADS = 1ll << 31;
+// fn(e0, ne) over [0, total) in pieces of at most LAUNCH_MAX_THREADS / per elements (`per` work-items each); stops at the
+// first error
+template <class F>
+inline int for_slices(int64_t total, F fn, int64_t per = 1) {
+  const int64_t piece = std::max<int64_t>(1, LAUNCH_MAX_THREADS / per);
+  for (int64_t e0 = 0; e0 < total; e0 += piece) RQ_TRY(fn(e0, std::min(piece, total - e0)));
+  return RQ_OK;
+}
 int workspace(int slot, size_t bytes, void **ptr, hipStream_t stream);
 int release_workspaces();
 int release_stream_workspace(hipStream_t stream);
@@ -282,12 +310,23 @@ int encode_launch(uint8_t *codes, const float *X, const float *C, int64_t n, int
                   int num_cu, hipStream_t stream, float *dbg_w = nullptr);
 const char *last_encode_kernel_name();   // which kernel the calling thread's last encode_launch chose
 void last_encode_stats(unsigned long long out[2]);   // tuning ENC_STATS = 1: {pairs, pairs that took the exact pass} of that encode
+// Stage epilogue of RVQ / ERVQ (src/RVQ.jl:56  Xr .-= C[i][:, B[i]]): dst[row][:] = src[row][:] - Cj[code][:] with code =
+// codes_in[row * in_stride]; codes_out[row * m + stage] = code and counts[code] += 1 (either may be NULL).  dst may be src.
+// Code: uint8_t or int16_t (zero-based, read zero-extended).
+template <class Code>
+RQ_LOCAL int residual_launch(float *dst, const float *src, const float *Cj, const Code *codes_in, int in_stride, Code *codes_out,
+                             unsigned int *counts, int64_t n, int d, int m, int stage, hipStream_t stream);
+// the in-place stage of quantize_rvq: Xr -= Ci[stage_codes], codes[:, stage] = stage_codes, cnt[code] += 1 (cnt may be NULL)
 int rvq_residual_launch(float *Xr, const float *Ci, const uint8_t *stage_codes, uint8_t *codes, unsigned int *cnt,
                         int64_t n, int d, int m, int stage, hipStream_t stream);
 int rvq_encode_launch(uint8_t *codes, float *Xr, uint8_t *stage_codes, unsigned int *counts, const float *C,
                       int64_t n, int d, int m, int h, int num_cu, hipStream_t stream);
 int rotate_launch(float *RX, const float *R, const float *X, int d, int64_t n, int num_cu,
                   hipStream_t stream);
+// out[i] = in[i] + add (uint8_t / int16_t in either place; in place when out == in, then add == 0 launches nothing)
+template <class Out, class In>
+RQ_LOCAL int convert_codes_launch(Out *out, const In *in, int64_t nelem, int add, hipStream_t stream);
+// zero-based bytes -> Julia's one-based Matrix{Int16} (src/PQ.jl:45-47)
 int widen_codes_launch(int16_t *out1, const uint8_t *codes, int64_t nelem, hipStream_t stream);
 // ---- more than 256 codewords per codebook, 16-bit codes (rq_encode_h16.hip) --------------------------
 // codes [n][m] int16 ZERO-based, 1 <= h <= RQ_MAX_H16; h <= 256 runs encode_launch and widens.  Scratch: WS_H16_SA, WS_H16_CODES.

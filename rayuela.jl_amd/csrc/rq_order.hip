@@ -725,13 +725,10 @@ static int order_run_set(const OrderSet &s, const OrderGate &g, bool zero_counte
     hipLaunchKernelGGL(order_coarse_scatter_kernel, dim3(nwg), dim3(ORDER_SMALL_THREADS), 0, stream, p, q, g);
     RQ_HIP(hipGetLastError());
     if (s.greedy) {
-      RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(order_fine_greedy_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
-      hipLaunchKernelGGL(order_fine_greedy_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), s.lds, stream, p, q, g);
+      RQ_LAUNCH_LDS(order_fine_greedy_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), s.lds, stream, p, q, g);
     } else {
-      hipLaunchKernelGGL(order_fine_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), 0, stream, p, q, g);
+      RQ_LAUNCH(order_fine_kernel, dim3(ORDER_COARSE), dim3(ORDER_SMALL_THREADS), 0, stream, p, q, g);
     }
-    RQ_HIP(hipGetLastError());
     return RQ_OK;
   }
   const uint32_t ntiles = (p.nbins + ORDER_SCAN_TILE - 1) / ORDER_SCAN_TILE;

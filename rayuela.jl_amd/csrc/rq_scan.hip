@@ -972,10 +972,7 @@ static int launch_scan(ScanParams &p, const ScanPlan &plan, hipStream_t stream) 
   }
   snprintf(g_last_scan_kernel, sizeof(g_last_scan_kernel), "adc_scan_kernel<%d, %s, %s, %s>", M, t_bias ? "true" : "false",
            t_filt ? "true" : "false", t_fine ? "true" : "false");
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(Cfg::THREADS), lds, stream, p);
-  RQ_HIP(hipGetLastError());
+  RQ_LAUNCH_LDS(kern, dim3(plan.grid), dim3(Cfg::THREADS), lds, stream, p);
   return RQ_OK;
 }
 
@@ -1103,15 +1100,6 @@ int scan_plan(ScanPlan &pl, int64_t n, int64_t nq, int m, int d, int K, int num_
 
 // ---- LSQ pre-filter: the rows' norms as one byte each (the "code" of the row-norm table, see build_qtab) -----------
 // info (uint32 view): [0] ordered(min), [1] ordered(max); (float view) [4] nmin, [5] nstep, [6] max |norm|
-// |c_k[r]|^2 of the full-dimensional codebooks [m * 256][d] (any rounding will do: the residual below uses these values)
-__global__ void cnorm_kernel(const float *__restrict__ cb, int entries, int d, float *cn) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= entries) return;
-  float s = 0.0f;
-  for (int i = 0; i < d; ++i) s = __builtin_fmaf(cb[(size_t)e * d + i], cb[(size_t)e * d + i], s);
-  cn[e] = s;
-}
-
 // rho(row) = norm(row) - sum_k cn[k][b_k], in float64 (exact for f32 inputs up to m = 16) and rounded DOWN to f32
 __global__ void norm_residual_kernel(const float *__restrict__ nrm, const uint8_t *__restrict__ codes, uint32_t n, int mrow,
                                      int mreal, const float *__restrict__ cn, float *rho) {
@@ -1187,7 +1175,8 @@ int lsq_norm_prepare(uint8_t *norm_buf, const uint8_t *codes, const float *cente
   RQ_HIP(hipMemsetAsync(info + 1, 0, 4, stream));
   RQ_HIP(hipMemsetAsync(cn, 0, 16 * 256 * 4, stream));       // padding tables (m_real < m): |c|^2 = 0
   const uint32_t grid = (uint32_t)std::min<int64_t>(2048, (n + 255) / 256);
-  hipLaunchKernelGGL(cnorm_kernel, dim3((m_real * 256 + 255) / 256), dim3(256), 0, stream, centers, m_real * 256, d, cn);
+  // |c_k[r]|^2 of the full-dimensional codebooks [m_real][256][d] (any rounding will do: the residual below uses these values)
+  RQ_TRY(icm_sqnorm_launch(cn, centers, m_real, 256, d, stream));
   hipLaunchKernelGGL(norm_residual_kernel, dim3(grid), dim3(256), 0, stream, row_bias, codes, (uint32_t)n, mp, m_real, cn, rho);
   hipLaunchKernelGGL(norm_minmax_kernel, dim3(grid), dim3(256), 0, stream, (const float *)rho, (uint32_t)n, info);
   hipLaunchKernelGGL(norm_info_kernel, dim3(1), dim3(1), 0, stream, info);
@@ -1307,18 +1296,12 @@ int merge_launch(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t
     RQ_TRY(workspace(WS_MERGE, (size_t)grid * per_wg * (sizeof(uint64_t) + sizeof(uint16_t)) + 16, &ws, stream));
     uint64_t *scratch = (uint64_t *)ws;
     uint16_t *bkt = (uint16_t *)(scratch + (size_t)grid * per_wg);
-    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(merge_topk_big_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SS_LDS_BYTES));
-    hipLaunchKernelGGL(merge_topk_big_kernel, dim3(grid), dim3(SCAN_THREADS), SS_LDS_BYTES, stream, p, scratch, bkt);
-    RQ_HIP(hipGetLastError());
+    RQ_LAUNCH_LDS(merge_topk_big_kernel, dim3(grid), dim3(SCAN_THREADS), SS_LDS_BYTES, stream, p, scratch, bkt);
     return RQ_OK;
   }
   constexpr int CTRL_BYTES = (sizeof(MergeCtrl) + 15) & ~15;
   size_t lds = CTRL_BYTES + (size_t)p.p2 * 8;
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(merge_topk_kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(merge_topk_kernel, dim3((uint32_t)nq), dim3(MERGE_THREADS), lds, stream, p);
-  RQ_HIP(hipGetLastError());
+  RQ_LAUNCH_LDS(merge_topk_kernel, dim3((uint32_t)nq), dim3(MERGE_THREADS), lds, stream, p);
   return RQ_OK;
 }
 

@@ -241,13 +241,11 @@ int prepare_codes_h16_launch(int16_t *codes, unsigned long long *first_bad, int6
                              hipStream_t stream) {
   RQ_HIP(hipMemsetAsync(first_bad, 0xFF, 8, stream));
   const int64_t nelem = n * m;
-  for (int64_t e0 = 0; e0 < nelem; e0 += LAUNCH_MAX_THREADS) {
-    const int64_t ne = std::min(LAUNCH_MAX_THREADS, nelem - e0);
-    hipLaunchKernelGGL(prepare_codes_h16_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, codes, first_bad,
-                       (size_t)e0, (size_t)nelem, m, h, code_base);
-    RQ_HIP(hipGetLastError());
-  }
-  return RQ_OK;
+  return for_slices(nelem, [&](int64_t e0, int64_t ne) {
+    RQ_LAUNCH(prepare_codes_h16_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, stream, codes, first_bad, (size_t)e0,
+              (size_t)nelem, m, h, code_base);
+    return RQ_OK;
+  });
 }
 
 // ---- the scan -------------------------------------------------------------------------------------------------------------

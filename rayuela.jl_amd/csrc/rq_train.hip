@@ -812,12 +812,7 @@ int kmpp_init_launch(float *C, long long *seeds, float *mincost, double *partial
   p.nblk = (int)std::min<int64_t>(KMPP_THREADS, (n + KMPP_THREADS - 1) / KMPP_THREADS);
   p.rows_per_blk = (n + p.nblk - 1) / p.nblk;
   p.nblk = (int)((n + p.rows_per_blk - 1) / p.rows_per_blk);
-  {
-    const int per = d / m, extra = d % m;
-    int pos = 0;
-    for (int i = 0; i < m; ++i) { p.off[i] = pos; pos += per + (i < extra ? 1 : 0); }
-    p.off[m] = pos;
-  }
+  split_offsets(p.off, d, m);
   const int upd_threads = m * (256 / m);           // a multiple of m: every thread keeps one sub-space
   const size_t upd_lds = (size_t)((d + 3) & ~3) * sizeof(float) + (size_t)upd_threads * sizeof(double);
   hipLaunchKernelGGL(kmpp_first_kernel, dim3(m), dim3(64), 0, stream, p);
@@ -832,13 +827,6 @@ int kmpp_init_launch(float *C, long long *seeds, float *mincost, double *partial
 int kmpp_partial_count(int64_t n) { return KMPP_THREADS; }
 
 // ------------------------------------------------------------------------------------------------------
-static void fill_offsets(int *off, int d, int m) {
-  const int per = d / m, extra = d % m;
-  int pos = 0;
-  for (int i = 0; i < m; ++i) { off[i] = pos; pos += per + (i < extra ? 1 : 0); }
-  off[m] = pos;
-}
-
 template <class T>
 static int partials_reduce(T *dst, const T *src, size_t stride, int nparts, int count, hipStream_t stream) {
   hipLaunchKernelGGL(partials_reduce_kernel<T>, dim3((count + 63) / 64), dim3(1024), 0, stream, dst, src, stride, nparts, count);
@@ -866,7 +854,7 @@ int update_centers_launch(float *C, unsigned int *counts, const float *X, const 
     return fail(RQ_EUNSUPPORTED, "update_centers covers m <= 32, h <= 256 (got m=%d d=%d h=%d)", m, d, h);
   TrainParams p{};
   p.X = X; p.codes = codes; p.C = C; p.counts = counts; p.n = n; p.d = d; p.m = m; p.h = h; p.cs = m; p.ccol = 0;
-  fill_offsets(p.off, d, m);
+  split_offsets(p.off, d, m);
   const int grid = (int)std::min<int64_t>(num_cu, (n + 1023) / 1024);
   void *part = nullptr;
   RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * ((size_t)h * d + (size_t)m * h) * sizeof(float), &part, stream));
@@ -888,10 +876,7 @@ int update_centers_launch(float *C, unsigned int *counts, const float *X, const 
   for (int dc0 = 0; dc0 < d; dc0 += 128) {
     const int dcw = std::min(128, d - dc0);
     const size_t lds = ((size_t)h * dcw + (size_t)m * h) * sizeof(float);
-    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(centers_partial_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(centers_partial_kernel, dim3(grid), dim3(1024), lds, stream, p, dc0, dcw);
-    RQ_HIP(hipGetLastError());
+    RQ_LAUNCH_LDS(centers_partial_kernel, dim3(grid), dim3(1024), lds, stream, p, dc0, dcw);
   }
   return centers_finish(p, grid, stream);
 }
@@ -939,7 +924,7 @@ int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t 
   if (m < 1 || m > 32 || d < m) return fail(RQ_EINVAL, "reconstruct: m=%d d=%d", m, d);
   TrainParams p{};
   p.codes = codes; p.C = const_cast<float *>(C); p.CB = CB; p.n = n; p.d = d; p.m = m; p.h = h;
-  fill_offsets(p.off, d, m);
+  split_offsets(p.off, d, m);
   const int64_t total = n * d;
   if (d > 8192) return fail(RQ_EUNSUPPORTED, "reconstruct: d=%d", d);
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
@@ -973,7 +958,7 @@ int codes_forms_width(int d, int m, int h, bool for_gram) {
   if (m < 1 || m > 32 || d < m || (d & 1) || h < 1 || h > 256) return 0;
   if (d > 1024) return 0;
   int off[33];
-  fill_offsets(off, d, m);
+  split_offsets(off, d, m);
   int w = 4;
   for (int q = 0; q <= m; ++q) {
     if (off[q] & 1) return 0;
@@ -985,16 +970,13 @@ bool codes_forms_ok(int d, int m, int h, bool for_gram) { return codes_forms_wid
 
 static void fill_codes_params(CodesParams &p, const float *X, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h) {
   p.X = X; p.codes = codes; p.C = C; p.partial = nullptr; p.dpartial = nullptr; p.n = n; p.d = d; p.m = m; p.h = h; p.NT = (d + 31) / 32;
-  fill_offsets(p.off, d, m);
+  split_offsets(p.off, d, m);
 }
 
 template <int NTT, int W>
 static int gram_codes_run(CodesParams &p, int grid, size_t lds, hipStream_t stream) {
-  auto kern = gram_codes_kernel<NTT, W>;
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int nblk = (p.d + 32 * NTT - 1) / (32 * NTT);
-  hipLaunchKernelGGL(kern, dim3(grid, nblk * nblk), dim3(NTT * 64), lds, stream, p);
-  RQ_HIP(hipGetLastError());
+  RQ_LAUNCH_LDS((gram_codes_kernel<NTT, W>), dim3(grid, nblk * nblk), dim3(NTT * 64), lds, stream, p);
   return RQ_OK;
 }
 
@@ -1259,8 +1241,7 @@ int polar_factor_launch(float *Rimg, const float *G, double *Vw, int warm, int d
   double *AU = scratch, *sv = scratch + (size_t)d * d;
   const int nb = (d * d + 255) / 256;
   hipLaunchKernelGGL(polar_prep_kernel, dim3(nb), dim3(256), 0, stream, AU, G, (const double *)Vw, warm, d);
-  RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(polar_jacobi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(polar_jacobi_kernel, dim3(1), dim3(POLAR_THREADS), lds, stream, AU, sv, d, status);
+  RQ_LAUNCH_LDS(polar_jacobi_kernel, dim3(1), dim3(POLAR_THREADS), lds, stream, AU, sv, d, status);
   hipLaunchKernelGGL(polar_vt_kernel, dim3(nb), dim3(256), 0, stream, Vw, (const double *)AU, G, (const double *)sv, d, (const int *)status);
   hipLaunchKernelGGL(polar_r_kernel, dim3(nb), dim3(256), 0, stream, Rimg, (const double *)AU, (const double *)Vw, d, (const int *)status);
   RQ_HIP(hipGetLastError());

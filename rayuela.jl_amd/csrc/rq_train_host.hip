@@ -169,13 +169,6 @@ struct SideStream {
   }
 };
 
-static void offsets(int *off, int d, int m) {
-  const int per = d / m, extra = d % m;
-  int pos = 0;
-  for (int i = 0; i < m; ++i) { off[i] = pos; pos += per + (i < extra ? 1 : 0); }
-  off[m] = pos;
-}
-
 // initial centres: C_i = h sampled rows of (rotated) X restricted to subspace i
 static int init_centers(float *dC, const float *dX, int64_t n, int d, int m, int h, const int *off, Rng &rng) {
   std::vector<int64_t> idx;
@@ -266,7 +259,7 @@ static int repick_unused(float *dCsub, const float *dCassigned, const float *dX,
 static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed,
                          const DeviceInfo &di, TrainProf &prof) {
   int off[33];
-  offsets(off, d, m);
+  split_offsets(off, d, m);
   Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
   DevMem dprev;
   RQ_TRY(dprev.alloc((size_t)n * m));
@@ -344,7 +337,7 @@ int rq_kmpp_seeds(int64_t *seeds, float *C, const float *X, int64_t n, int d, in
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   int off[33];
-  offsets(off, d, m);
+  split_offsets(off, d, m);
   Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
   DevMem dX, dC;
   RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dC.alloc((size_t)h * d * 4));
@@ -449,7 +442,7 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   int off[33];
-  offsets(off, d, m);
+  split_offsets(off, d, m);
   Rng rng{seed * 0x9E3779B97F4A7C15ull + 2};
   std::vector<float> Rh((size_t)d * d, 0.0f);   // memory image of Julia's R: Rh[i*d+k] = R[k, i]
   std::vector<double> G((size_t)d * d), P((size_t)d * d);

@@ -238,7 +238,7 @@ def test_device_entries_at_every_byte_offset(rq, oracle, side, shape):
         assert np.array_equal(tX.cpu().numpy(), X) and int(buf[:off].sum()) == 0                         # the input is only read
 
 
-@pytest.mark.parametrize("d", [32, 96, 128, 512])
+@pytest.mark.parametrize("d", [32, 64, 96, 128, 512])
 def test_rotation_of_bytes_is_bit_equal(rq, oracle, d):
     """rq_dev_rotate_T_bytes against the oracle's rotation of the widened rows; d = 512 takes the widen fallback"""
     import torch

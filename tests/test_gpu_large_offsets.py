@@ -17,7 +17,7 @@ rq_dev_aq_norms (m <= 64) and rq_dev_encode_pq (d = m = 32) do pass it and are r
 
 What the file found: no 32-bit index, but launches of more than 2^32 work-items.  A dispatch that large does not fail, it
 wraps and runs the remainder: rq_dev_encode_rvq at d = 30 (one thread per float, n * d = 2^32 + 123 360) returned RQ_OK with
-the first 4114 of 143 169 689 rows encoded and the rest untouched.  rvq_residual_launch, its 16-bit sibling, the ERVQ epilogue,
+the first 4114 of 143 169 689 rows encoded and the rest untouched.  residual_launch (the RVQ, 16-bit RVQ and ERVQ epilogue),
 aq_norms_launch (16 work-items per row: 2^28 rows) and the code-widening kernels now cut their rows into launches of at most
 2^31 work-items; test_encode_rvq_scalar_epilogue_all_rows and test_norms_past_the_work_items_of_one_launch pin it.
 
@@ -301,7 +301,7 @@ def test_encode_rvq_all_rows(rq, oracle, bases):
 @pytest.mark.parametrize("h", [64, 300])
 def test_encode_rvq_scalar_epilogue_all_rows(rq, oracle, bases, h):
     """d = 30 is no multiple of 4: the stage epilogue runs one thread per float, n * d = 2^32 + 123 360 of them -- more work-items
-    than one launch takes (rq_encode.hip: rvq_residual_launch; h = 300: rq_encode_h16.hip).  m = 2."""
+    than one launch takes (rq_encode.hip: residual_launch; h = 300: its int16 instantiation).  m = 2."""
     import torch
     import wide_oracle as wo
     d, m = 30, 2
@@ -697,8 +697,8 @@ def test_host_encode_pq_all_rows(rq, oracle, bases, kind):
 # The launchers that state a row limit check it ahead of every access to their arrays (read in rq_lsq.hip: lsq_check is the
 # first statement of rq_dev_lsq_normal_eq / rq_dev_update_codebooks_lsq; rq_chain.hip: chain_check_update of
 # rq_dev_update_codebooks_chain; rq_sr.hip: rq_train_sr and rq_sr_std test n before anything else), so a call at limit + 1 is
-# safe on small sentinel-filled arrays.  rq_ervq.hip's ervq_residual_launch no longer states a limit: it cuts its rows into
-# launches like rvq_residual_launch (a limit inside the launch sequence, behind the host form's upload, could not be pinned).
+# safe on small sentinel-filled arrays.  residual_launch (rq_encode.hip) states no limit: it cuts its rows into
+# launches for every caller (a limit inside the launch sequence, behind the host form's upload, could not be pinned).
 def test_row_limits_are_refused_before_any_access(rq):
     import torch
     L = _L()
