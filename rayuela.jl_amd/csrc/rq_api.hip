@@ -379,16 +379,16 @@ size_t order_base_bytes(int64_t n, int mp) { return (((size_t)n * mp + 255) & ~(
 // codes [n][mp] (already padded to a tiled width) -> *out_codes [n][mp] in bank-aware order + *out_perm [n], both inside
 // `dst` (order_base_bytes).  The key scratch comes from the (device, stream) workspace.
 int order_base(const uint8_t **out_codes, const uint32_t **out_perm, void *dst, const uint8_t *codes, int64_t n, int mp,
-               hipStream_t stream) {
+               int64_t batch, hipStream_t stream) {
   int nb[8];
   OrderTiling ot;
   scan_order_tiling(mp, &ot);
-  const int bits = order_key_bits(n, mp, ot, nb);
+  const int bits = order_key_bits(n, mp, ot, nb, batch);
   if (bits <= 0) return RQ_OK;          // tiny base: stays as it is (*out_perm untouched = nullptr)
   void *tmp = nullptr;
   RQ_TRY(workspace(WS_ORDER_TMP, order_scratch_bytes(n, bits), &tmp, stream));
   uint32_t *pm = reinterpret_cast<uint32_t *>((uint8_t *)dst + (order_base_bytes(n, mp) - (size_t)n * 4));
-  RQ_TRY(order_rows_launch((uint8_t *)dst, pm, codes, n, mp, tmp, ot, stream));
+  RQ_TRY(order_rows_launch((uint8_t *)dst, pm, codes, n, mp, tmp, ot, batch, stream));
   *out_codes = (const uint8_t *)dst;
   *out_perm = pm;
   return RQ_OK;
@@ -410,10 +410,8 @@ static int order_in_call(const uint8_t **ocodes, const uint32_t **operm, const u
   }
   h->key_id = 0;
   ++h->uncached;
-  order_set_call_queries(nq);      // (the greedy balance of the order costs more than the sort: only for batches it pays for)
-  const int orc = order_base(ocodes, operm, ord, codes, n, mp, stream);
-  order_set_call_queries(0);
-  return orc;
+  // (batch = nq: the greedy balance of the order costs more than the sort -- only for batches it pays for)
+  return order_base(ocodes, operm, ord, codes, n, mp, nq, stream);
 }
 
 // The kept order.  WS_ORDER: [copy | perm] (order_base_bytes) | snapshot at snap_off; WS_ORDER_STATE: the device words.  A new
@@ -557,9 +555,16 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
   void *normb = norm_prepared;     // LSQ pre-filter: one byte per row, 32 bytes of min / step, |c|^2 tables, f32 residual norms
   if (lut_mode == LUT_LSQ && row_bias && !normb)
     RQ_TRY(workspace(WS_NORMB, lsq_norm_bytes(n), &normb, stream));
-  RQ_TRY(scan_launch(pl, both ? nullptr : dists, both ? nullptr : ids, keys, (uint64_t *)part, codes, centers, queries,
-                     n, nq, m, d, k, id_offset, id_base, (uint32_t *)counter, (uint64_t *)cand, stream, lut_mode,
-                     row_bias, (uint8_t *)normb, perm, norm_prepared != nullptr));
+  ScanCall call;
+  call.dists = both ? nullptr : dists; call.ids = both ? nullptr : ids; call.keys = keys; call.part = (uint64_t *)part;
+  call.codes = codes; call.centers = centers; call.queries = queries;
+  call.n = n; call.nq = nq; call.m = m; call.d = d; call.K = k;
+  call.id_offset = id_offset; call.id_base = id_base;
+  call.work_counter = (uint32_t *)counter; call.cand = (uint64_t *)cand;
+  call.lut_mode = lut_mode; call.row_bias = row_bias;
+  call.norm_buf = (uint8_t *)normb; call.norm_ready = norm_prepared != nullptr;
+  call.perm = perm;
+  RQ_TRY(scan_launch(pl, call, stream));
   if (sliced) {
     const size_t off = (size_t)q_tail * k;
     RQ_TRY(merge_launch(both || !dists ? nullptr : dists + off, both || !ids ? nullptr : ids + off,
@@ -748,7 +753,8 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
   DevBuf dord;
   if (scan_padded_m(m) == m && order_pays(n, nq, k)) {
     RQ_TRY(dord.alloc(order_base_bytes(n, m)));
-    RQ_TRY(order_base(&cdev, &perm, dord.p, cdev, n, m, nullptr));
+    // (ORDER_ONCE: this call always balances, whatever nq -- a behaviour question of its own, kept as it is)
+    RQ_TRY(order_base(&cdev, &perm, dord.p, cdev, n, m, ORDER_ONCE, nullptr));
   }
   ScanBase sbase;
   sbase.perm = perm;
@@ -1196,7 +1202,7 @@ static rq_lsq_index *lsq_prepare(const uint8_t *codes, const float *codebooks, c
       ix->ordered = nullptr;
     }
     if (ix->ordered) {
-      const int orc = order_base(&ix->ocodes, &ix->perm, ix->ordered, ix->codes, n, mp, nullptr);
+      const int orc = order_base(&ix->ocodes, &ix->perm, ix->ordered, ix->codes, n, mp, ORDER_ONCE, nullptr);
       if (is_oom(orc)) { forgive_oom(); ix->perm = nullptr; }      // (the key scratch)
       else if (orc != RQ_OK) return orc;                           // launch errors surface
       if (ix->perm) {
@@ -1693,12 +1699,12 @@ int rq_order_plan(int64_t n, int m, int *out, int cap) {
   OrderTiling ot;
   scan_order_tiling(mp, &ot);
   int nb[8];
-  const int total = order_key_bits(n, mp, ot, nb);
+  const int total = order_key_bits(n, mp, ot, nb, ORDER_ONCE);
   for (int c = 0; c < 8; ++c) out[c] = nb[c];
   out[8] = total; out[9] = ot.group; out[10] = ot.gran; out[11] = mp;
   if (cap >= 14) {          // [12] tables the greedy balance deals over (0: plain sort), [13] wavefronts per workgroup that balance
     uint32_t gp[4];
-    const bool on = order_greedy_runs(n, mp, ot, total, gp);     // (order_rows_launch asks the same)
+    const bool on = order_greedy_runs(n, mp, ot, total, gp, ORDER_ONCE);     // (order_rows_launch asks the same)
     out[12] = on ? (int)gp[0] : 0;
     out[13] = on ? (int)gp[1] : 0;
   }
@@ -1727,7 +1733,7 @@ int rq_dev_order_rows(void *ordered, const uint8_t **codes_out, const uint32_t *
     src = (const uint8_t *)padded;
   }
   *codes_out = nullptr; *perm_out = nullptr;
-  RQ_TRY(order_base(codes_out, perm_out, ordered, src, n, mp, st));
+  RQ_TRY(order_base(codes_out, perm_out, ordered, src, n, mp, ORDER_ONCE, st));
   if (!*perm_out) {       // tiny base: nothing to order -- identity copy so that the pair is always usable
     RQ_HIP(hipMemcpyAsync(ordered, src, (size_t)n * mp, hipMemcpyDeviceToDevice, st));
     *codes_out = (const uint8_t *)ordered;

@@ -320,7 +320,7 @@ static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
       const uint32_t *op = nullptr;
       int rc = RQ_OK;
       if (hipMalloc(&ord, order_base_bytes(s.n, ix->m)) != hipSuccess) { (void)hipGetLastError(); rc = (int)hipErrorOutOfMemory; ord = nullptr; }
-      if (rc == RQ_OK) rc = order_base(&oc, &op, ord, s.codes, s.n, ix->m, dv.stream);
+      if (rc == RQ_OK) rc = order_base(&oc, &op, ord, s.codes, s.n, ix->m, ORDER_ONCE, dv.stream);
       if (rc == RQ_OK) { hipError_t e = hipStreamSynchronize(dv.stream); if (e != hipSuccess) rc = fail_hip(e, "order sync", __FILE__, __LINE__); }
       if (rc == RQ_OK && op) {
         RQ_HIP(hipFree(s.codes));

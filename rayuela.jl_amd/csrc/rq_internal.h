@@ -98,10 +98,9 @@ void host_pool_free(void *p);
 void host_pool_trim();
 void sharded_cache_release();
 int aux_streams(hipStream_t *compute, hipStream_t *transfer);
-// WS_COUNTER: [0..63] work tickets / finished items per XCD, [64..255] diagnostics (rq_scan_stats), [256..] chunk-pacing
-// counters of the big-base scan: 8 XCDs x SCAN_PACE_SLOTS x {chunks done, members}
-constexpr int SCAN_PACE_SLOTS = 64;
-constexpr size_t WS_COUNTER_BYTES = 256 + 8 * SCAN_PACE_SLOTS * 8;
+// WS_COUNTER, in bytes: [0, 64) work tickets / finished items per XCD, [64, 256) diagnostics (rq_scan_stats; the encode
+// filter's two counters at byte 128)
+constexpr size_t WS_COUNTER_BYTES = 256;
 enum { WS_CAND = 0, WS_COUNTER = 1, WS_KEYS = 2, WS_TMP = 3, WS_PAD = 4, WS_MERGE = 5, WS_NORMB = 6, WS_ORDER = 7, WS_ORDER_TMP = 8, WS_ENCFLAG = 9, WS_BULK = 10, WS_ICM_BIN = 11, WS_ICM_U = 12, WS_LSQ_A = 13, WS_LSQ_B = 14, WS_LSQ_S = 15, WS_CHAIN = 16, WS_ORDER_STATE = 17, WS_H16_SA = 18, WS_H16_CODES = 19, WS_SLOTS = 20 };
 
 // Per-device launch lock (recursive): held while a call looks up scratch, resets the work counter and
@@ -184,17 +183,33 @@ struct ScanPlan {
   bool xcd;        // big base: short row windows handed out per XCD (see plan_for)
 };
 int scan_plan(ScanPlan &pl, int64_t n, int64_t nq, int m, int d, int K, int num_cu, int force_slices);
-int scan_launch(const ScanPlan &pl, float *dists, uint32_t *ids, uint64_t *keys, uint64_t *part, const uint8_t *codes,
-                const float *centers, const float *queries, int64_t n, int64_t nq, int m, int d, int K,
-                uint32_t id_offset, int id_base, uint32_t *work_counter, uint64_t *cand,
-                hipStream_t stream, int lut_mode = 0, const float *row_bias = nullptr, uint8_t *norm_buf = nullptr,
-                const uint32_t *perm = nullptr, bool norm_ready = false);
+enum { LUT_PQ = 0, LUT_LSQ = 1, LUT_CQ = 2 };
+// one planned scan of a resident shard: outputs, inputs, shape and scratch (rq_scan_plan.hip)
+struct ScanCall {
+  float *dists = nullptr;             // whole items: [nq][K] dists / ids, or packed keys [nq][K] when keys != nullptr
+  uint32_t *ids = nullptr;
+  uint64_t *keys = nullptr;
+  uint64_t *part = nullptr;           // sliced items: per-slice key lists for merge_launch
+  const uint8_t *codes = nullptr;     // [n][scan_padded_m(m)]
+  const float *centers = nullptr, *queries = nullptr;
+  int64_t n = 0, nq = 0;
+  int m = 0, d = 0, K = 0;
+  uint32_t id_offset = 0;
+  int id_base = 0;
+  uint32_t *work_counter = nullptr;   // WS_COUNTER
+  uint64_t *cand = nullptr;           // WS_CAND, pl.cand_bytes
+  int lut_mode = LUT_PQ;
+  const float *row_bias = nullptr;
+  uint8_t *norm_buf = nullptr;        // LSQ pre-filter: lsq_norm_bytes(n), prepared by the call unless norm_ready
+  bool norm_ready = false;
+  const uint32_t *perm = nullptr;     // ordered base (rq_order.hip)
+};
+RQ_LOCAL int scan_launch(const ScanPlan &pl, const ScanCall &c, hipStream_t stream);
 const char *last_scan_kernel_name();      // which instantiation the calling thread's last scan_launch chose
 void set_last_scan_kernel(const char *name);
 size_t lsq_norm_bytes(int64_t n);      // LSQ pre-filter: bytes of a base's prepared norm buffer
 int lsq_norm_prepare(uint8_t *norm_buf, const uint8_t *codes, const float *centers, const float *row_bias, int64_t n,
                      int mp, int m_real, int d, hipStream_t stream);
-enum { LUT_PQ = 0, LUT_LSQ = 1, LUT_CQ = 2 };
 // what a caller may know about a resident base beyond its code bytes
 struct ScanBase {
   const uint32_t *perm = nullptr;     // rows are in bank-aware order (rq_order.hip): perm[position] = row; implies `padded`
@@ -208,21 +223,24 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
                 const ScanBase *base = nullptr);
 bool order_pays(int64_t n, int64_t nq, int k);                          // SCAN_ORDER / ORDER_MIN_ROWS / ORDER_MIN_NQ / ORDER_MAX_K
 size_t order_base_bytes(int64_t n, int mp);
-int order_base(const uint8_t **out_codes, const uint32_t **out_perm, void *dst, const uint8_t *codes, int64_t n, int mp,
-               hipStream_t stream);
+// `batch` of the order planner: the number of queries of the ONE scan the ordering serves (the greedy balance runs only where
+// it pays within that call, ORDER_GREEDY_MIN_NQ), or one of
+constexpr int64_t ORDER_ONCE = 0;      // a base that is ordered once and scanned many times: always balanced
+constexpr int64_t ORDER_PLAIN = -1;    // the plain set: never balanced
+RQ_LOCAL int order_base(const uint8_t **out_codes, const uint32_t **out_perm, void *dst, const uint8_t *codes, int64_t n, int mp,
+                        int64_t batch, hipStream_t stream);
 // ---- bank-aware row order (rq_order.hip) ---------------------------------------------------------
-struct OrderTiling { int rpt, gran, group, cbits, blk; };                    // see scan_order_tiling (rq_scan.hip)
+struct OrderTiling { int rpt, gran, group, cbits, blk; };                    // see scan_order_tiling (rq_scan_plan.hip)
 void scan_order_tiling(int mp, OrderTiling *t);
-void order_set_call_queries(int64_t nq);   // > 0: the ordering that follows serves ONE scan of nq queries (greedy balance only if it pays); < 0: never balanced
-bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4]);
-bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4]);  // the launch's balance predicate
-int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]);  // key layout; returns the total bits (0: no ordering)
+RQ_LOCAL bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4], int64_t batch);
+RQ_LOCAL bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4], int64_t batch);  // the launch's balance predicate
+RQ_LOCAL int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8], int64_t batch);  // key layout; returns the total bits (0: no ordering)
 size_t order_scratch_bytes(int64_t n, int total_bits);
 int order_sample_stride();                                               // ORDER_SAMPLE_STRIDE (16; < 2: no sample blocks)
 uint32_t order_sample_rows(int64_t n, int blk, uint32_t *sgroups);   // arrival-order sample blocks of an ordered base
 int gather_f32_launch(float *dst, const float *src, const uint32_t *perm, int64_t n, hipStream_t stream);
-int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t n, int mp, void *scratch,
-                      const OrderTiling &t, hipStream_t stream);
+RQ_LOCAL int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t n, int mp, void *scratch,
+                               const OrderTiling &t, int64_t batch, hipStream_t stream);
 // The kept order of dev_linscan (rq_order.hip, "the kept order"): the host half of one (device, stream) workspace's cache.  The
 // device half -- which key the copy was built for, the verdict of the call's check, the counters -- is WS_ORDER_STATE.
 struct OrderCacheHost {

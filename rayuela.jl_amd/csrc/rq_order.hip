@@ -582,20 +582,17 @@ uint32_t order_sample_rows(int64_t n, int blk, uint32_t *sgroups) {
   return g * (uint32_t)blk;
 }
 
-// Does the greedy balance run for a base of n (sorted) rows of mp bytes whose full key would have `budget` bits?  Rows of 4, 8 or
+// Does the greedy balance run for a base of n (sorted) rows of mp bytes whose full key would have `budget` bits?  Rows of 8 or
 // 16 bytes, the two-level path with at least 4 fine bits left after the key gives up 3, and coarse buckets (n / 256 rows) that fit
 // the LDS list with room for skew.  out: {free tables, balancing wavefronts, list capacity (rows), dynamic LDS bytes}.
 // A raw-pointer scan that orders its own scratch copy pays for the balance on EVERY call (0.11 ms per 1e6 rows of 8 bytes, 0.31 ms
 // of 16 bytes, against 0.06 for the plain sort) and gains ~4-6 % of its scan: it pays from ORDER_GREEDY_MIN_NQ queries on (16384;
-// measured at 1e4 queries: m = 8 +0.4 ... +2 %, m = 16 -0.7 ... +0.1 %).  dev_linscan announces its batch here; bases that are
-// ordered ONCE (index handles, rq_dev_order_rows, ShardedIndex) leave it at 0 and always balance.
-static thread_local int64_t g_order_call_nq = 0;
-void order_set_call_queries(int64_t nq) { g_order_call_nq = nq; }
-
-bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4]) {
-  if (g_order_call_nq < 0) return false;          // (order_rows_cached: the plain set)
+// measured at 1e4 queries: m = 8 +0.4 ... +2 %, m = 16 -0.7 ... +0.1 %).  dev_linscan passes its batch size as `batch`; bases that
+// are ordered ONCE (index handles, rq_dev_order_rows, ShardedIndex) pass ORDER_ONCE and always balance.
+bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4], int64_t batch) {
+  if (batch == ORDER_PLAIN) return false;         // (order_rows_cached: the plain set)
   if (!tuning("ORDER_GREEDY", 1) || !tuning("ORDER_TWO_LEVEL", 1) || tuning("ORDER_CBITS", 0) > 0) return false;
-  if (g_order_call_nq > 0 && g_order_call_nq < tuning("ORDER_GREEDY_MIN_NQ", 16384)) return false;
+  if (batch > 0 && batch < tuning("ORDER_GREEDY_MIN_NQ", 16384)) return false;
   if (mp != 8 && mp != 16) return false;
   const int total = budget - 3;
   if (total < 12 || total > 18) return false;      // (>= 4 tables under the key: the free tables are the row's last 4 / 12 bytes)
@@ -609,7 +606,7 @@ bool order_greedy_plan(int64_t n, int mp, int budget, uint32_t out[4]) {
   return true;
 }
 
-int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]) {
+int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8], int64_t batch) {
   for (int c = 0; c < 8; ++c) nb[c] = 0;
   if (n < 1024) return 0;
   n -= order_sample_rows(n, t.blk, nullptr);
@@ -621,7 +618,7 @@ int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]) {
   if (cb <= 0) cb = t.cbits;
   // round 6: where the greedy balance runs (order_greedy_plan) the key gives up one table's bits -- the buckets it leaves hold
   // ~8 lane groups of rows, and balancing those over ALL uncovered tables beats one more conflict-free table (15.5 -> 12.7 passes)
-  if (order_greedy_plan(n, mp, budget, nullptr)) budget -= cb;
+  if (order_greedy_plan(n, mp, budget, nullptr, batch)) budget -= cb;
   int total = 0;
   for (int c = 0; c < nc && total < budget; ++c) { nb[c] = std::min(cb, budget - total); total += nb[c]; }
   // narrow rows (m <= 4): more bits per byte once every byte has its window
@@ -632,14 +629,14 @@ int order_key_bits(int64_t n, int mp, const OrderTiling &t, int nb[8]) {
 // Does order_rows_launch balance (order_fine_greedy_kernel) a base of n rows whose key order_key_bits made `total` bits long?  Only
 // where order_key_bits gave up a table's bits for it -- the full budget of the sorted rows, not `total`, decides.  The one
 // predicate of the launch and of rq_order_plan.  gp: order_greedy_plan's out.
-bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4]) {
+bool order_greedy_runs(int64_t n, int mp, const OrderTiling &t, int total, uint32_t gp[4], int64_t batch) {
   gp[0] = gp[1] = gp[2] = gp[3] = 0;
   if (total <= 0) return false;
   const int64_t ns = n - order_sample_rows(n, t.blk, nullptr);
   int budget = tuning("ORDER_BITS", 0);
   if (budget <= 0) budget = (int)std::floor(std::log2((double)ns / (double)t.group) + 0.5);
   budget = std::min(budget, 24);
-  return total == budget - 3 && order_greedy_plan(ns, mp, budget, gp);
+  return total == budget - 3 && order_greedy_plan(ns, mp, budget, gp, batch);
 }
 
 size_t order_scratch_bytes(int64_t n, int total_bits) {
@@ -657,17 +654,17 @@ struct OrderSet {
   uint32_t lds;           // dynamic LDS of order_fine_greedy_kernel
 };
 
-// Plan the ordering of n rows of mp bytes under the switches as they stand (and order_set_call_queries).  Every byte of the
-// set is defined -- it is part of order_rows_cached's key.
-static int order_plan_set(OrderSet &s, int64_t n, int mp, const OrderTiling &t) {
+// Plan the ordering of n rows of mp bytes under the switches as they stand, for `batch` (a scan's queries, ORDER_ONCE or
+// ORDER_PLAIN).  Every byte of the set is defined -- it is part of order_rows_cached's key.
+static int order_plan_set(OrderSet &s, int64_t n, int mp, const OrderTiling &t, int64_t batch) {
   memset(&s, 0, sizeof(s));
   OrderParams &p = s.p;
   const int rpt = t.rpt, gran = t.gran;
-  const int total = order_key_bits(n, mp, t, p.nb);
+  const int total = order_key_bits(n, mp, t, p.nb, batch);
   if (total <= 0 || total > 24) return fail(RQ_EINVAL, "order_rows: nothing to order (n=%lld)", (long long)n);
   s.total = total;
   uint32_t gp[4];
-  const bool greedy_on = order_greedy_runs(n, mp, t, total, gp);
+  const bool greedy_on = order_greedy_runs(n, mp, t, total, gp, batch);
   p.n = (uint32_t)n; p.mp = mp;
   p.ncoord = 0;
   for (int c = 0; c < 8; ++c) if (p.nb[c]) p.ncoord = c + 1;
@@ -752,9 +749,9 @@ static int order_run_set(const OrderSet &s, const OrderGate &g, bool zero_counte
 
 // codes [n][mp] -> dst [n][mp] + perm [n]; scratch of order_scratch_bytes().  t: the scan tiling (scan_order_tiling).
 int order_rows_launch(uint8_t *dst, uint32_t *perm, const uint8_t *src, int64_t n, int mp, void *scratch,
-                      const OrderTiling &t, hipStream_t stream) {
+                      const OrderTiling &t, int64_t batch, hipStream_t stream) {
   OrderSet s;
-  RQ_TRY(order_plan_set(s, n, mp, t));
+  RQ_TRY(order_plan_set(s, n, mp, t, batch));
   order_bind(s, dst, perm, src, scratch);
   OrderGate g;
   memset(&g, 0, sizeof(g));
@@ -777,10 +774,7 @@ size_t order_cache_state_bytes() { return OC_WORDS * sizeof(uint32_t); }
 
 int order_cached_key_bits(int64_t n, int mp, const OrderTiling &t) {       // the longer key of the two sets: sizes the scratch
   int nb[8];
-  order_set_call_queries(-1);
-  const int bits = order_key_bits(n, mp, t, nb);
-  order_set_call_queries(0);
-  return bits;
+  return order_key_bits(n, mp, t, nb, ORDER_PLAIN);
 }
 
 int order_rows_cached(uint8_t *dst, uint32_t *perm, uint8_t *snap, const uint8_t *src, int64_t n, int m, int mp, void *scratch,
@@ -790,10 +784,8 @@ int order_rows_cached(uint8_t *dst, uint32_t *perm, uint8_t *snap, const uint8_t
   OrderCacheKey key;
   memset(&key, 0, sizeof(key));
   key.n = n; key.m = m; key.mp = mp;
-  order_set_call_queries(-1);           // never balanced
-  int rc = order_plan_set(key.plain, n, mp, t);
-  order_set_call_queries(0);            // as a base that is ordered once
-  if (rc == RQ_OK) rc = order_plan_set(key.bal, n, mp, t);
+  int rc = order_plan_set(key.plain, n, mp, t, ORDER_PLAIN);
+  if (rc == RQ_OK) rc = order_plan_set(key.bal, n, mp, t, ORDER_ONCE);
   if (rc != RQ_OK) return rc;
   key.has_b = key.bal.greedy ? 1 : 0;
   if (!key.has_b) memset(&key.bal, 0, sizeof(key.bal));

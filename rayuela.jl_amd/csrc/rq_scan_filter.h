@@ -88,12 +88,6 @@ template <> __device__ __forceinline__ uint2 lds_abs_load<uint2>(uint32_t addr) 
   const unsigned long long v = *(lds_u64_t *)(uintptr_t)addr;
   return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
 }
-template <> __device__ __forceinline__ uint4 lds_abs_load<uint4>(uint32_t addr) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  typedef const u32x4 __attribute__((address_space(3))) lds_u128_t;
-  const u32x4 v = *(lds_u128_t *)(uintptr_t)addr;
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
 template <> __device__ __forceinline__ uint32_t lds_abs_load<uint32_t>(uint32_t addr) {
   typedef const uint32_t __attribute__((address_space(3))) lds_u32_t;
   return *(lds_u32_t *)(uintptr_t)addr;
@@ -101,14 +95,9 @@ template <> __device__ __forceinline__ uint32_t lds_abs_load<uint32_t>(uint32_t 
 
 // dword j of a byte-table entry (4 queries per dword)
 __device__ __forceinline__ uint32_t fv_word(const uint2 &v, int j) { return j == 0 ? v.x : v.y; }
-__device__ __forceinline__ uint32_t fv_word(const uint4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 
 template <int M> struct FiltVec;               // table entry: one byte per query of the group
-#if RQ_QG16
-template <> struct FiltVec<8> { using type = uint4; };    // experiment: 16 queries per ds_read_b128
-#else
 template <> struct FiltVec<8> { using type = uint2; };    // 8 queries per ds_read_b64
-#endif
 template <> struct FiltVec<16> { using type = uint2; };
 template <> struct FiltVec<4> { using type = uint2; };
 
@@ -119,13 +108,6 @@ constexpr uint32_t filt_clamp() {
   return LSQ ? (M <= 8 ? 51u : 28u)
              : (M == 4 ? (filt_off8(false) ? (255u - filt_off8(false)) / 4u : 63u)      // m = 4: ONE set of 4 entries (round 6)
                 : M == 8 ? filt_clamp8(FINE) : (M == 16 && filt_off16() ? (255u - filt_off16()) / 8u : FILT_CLAMP));
-}
-
-// row norm -> its quantisation cell's LOWER edge, with exactly these two rounded operations (the quantiser checks its
-// choice against the same expression, so EDGE(byte of a row) <= the row's norm holds in exact arithmetic)
-__device__ __forceinline__ float norm_edge(float nmin, float nstep, uint32_t b) {
-  const float t = (float)b * nstep;
-  return nmin + t;
 }
 
 template <int M, bool FINE, bool LSQ = false>
@@ -454,6 +436,5 @@ __device__ __forceinline__ void refine_queue(ScanCtrl<ScanCfg<M>::QG> *ctrl, uin
     refine_pairs<M, BIAS, FINE>(ctrl, cand_wg, codes, row_bias, id_offset, cap, lut4, gtab, qtab, queue, count, norm_bytes, perm);
 }
 #define RQ_REFINE(c, cw, cd, rb, io, cp, l4, gt, qu, n) refine_queue<M, BIAS, FILT, FINE>(c, cw, cd, rb, io, cp, l4, gt, qtab, qu, n, p.norm_bytes, p.perm)
-
 
 }  // namespace rq

@@ -1,22 +1,12 @@
-// rq_scan_tables.h -- tiling constants (ScanCfg), per-item state, f32 look-up tables and the exact row evaluation
-// Part of the ADC scan (rq_scan.hip); device code only, included by that file alone.
+// rq_scan_tables.h -- f32 look-up tables, the exact row evaluation and the survivors' append of the ADC scan kernel
+// Device code only, part of the kernel: included by rq_scan.hip alone (through rq_scan_filter.h and rq_scan_select.h too).
+// The tiling constants and the kernel's parameter block are in rq_scan_cfg.h.
 #pragma once
 #include "rq_internal.h"
 #include "rq_topk.h"
-
-#ifndef RQ_SCAN_PACE_BUILD
-#define RQ_SCAN_PACE_BUILD 0
-#endif
-// EXPERIMENT build (EXPERIMENTS.md 9.3): m = 8 scans with 16 queries per group -- byte tables of 16 queries read by ds_read_b128,
-// one 1024-thread workgroup per CU, half of the f32 tables through L1.  tools/build_variant.sh qg16 rq_scan.hip "-DRQ_QG16=1"
-#ifndef RQ_QG16
-#define RQ_QG16 0
-#endif
+#include "rq_scan_cfg.h"
 
 namespace rq {
-
-
-constexpr int SCAN_THREADS = 512;       // two workgroups per CU (ScanCfg<M>::THREADS is 1024 where one group needs more than half of the LDS)
 
 // v_writelane_b32 (no clang builtin in ROCm 7.2): lane `L` of `old` <- wave-uniform `val`
 template <class T>
@@ -38,120 +28,7 @@ template <> struct LutVec<2> {
   static __device__ __forceinline__ float get(const type &v, int i) { return i == 0 ? v.x : v.y; }
 };
 
-// Experiments that did not ship (history: git log): 16 queries per 16-byte gather at m = 8 (one
-// 1024-thread workgroup per CU; correct and slower: k = 1 2.25 vs 2.01 ms, k = 1000 3.28 vs 2.46 -- a 16-byte entry costs
-// four adds, the wider accumulators spill), exact re-evaluation of whole rows instead of (row, query) pairs, all tables in
-// LDS (no L1-gathered part), other block / vote periods.
 constexpr uint32_t FILT_MAX_SHARE_PCT = 60;   // first block: share of rows the pre-filter may let through before it is switched off
-template <int M>
-struct ScanCfg {
-  // queries per LDS gather: a float4 entry (ds_read_b128) up to m = 32; m = 64 only fits the 160 KiB of
-  // LDS with float2 entries (ds_read_b64, 2 queries per gather)
-  static constexpr int QPG = (M <= 32) ? 4 : 2;
-  static constexpr int QG = (RQ_QG16 && M == 8) ? 16 : (M <= 16) ? 8 : (M <= 32) ? 4 : 2;   // queries per group
-  static constexpr int NQUAD = QG / QPG;                         // gathers per code byte
-  // rows per thread per sub-step: ~32 gathers' worth, and a whole number of 16-byte code loads
-  static constexpr int RPT = (32 / (M * NQUAD)) > (M < 16 ? 16 / M : 1) ? 32 / (M * NQUAD) : (M < 16 ? 16 / M : 1);
-  // threads per workgroup: two 512-thread workgroups per CU, or ONE of 1024 where a group's tables take more than half of
-  // the LDS (m = 16: 96 KiB of f32 tables + 32 KiB of byte tables; m = 32, 64: 112 KiB of f32 tables) -- the same 16
-  // wavefronts per CU either way (m = 32 exact scan 27.1 -> 24.6 ms against one 512-thread workgroup per CU)
-  static constexpr int THREADS = (M * QG >= 128) ? 1024 : SCAN_THREADS;
-  static constexpr int SUB = THREADS * RPT;    // rows per sub-step (one 16/32-byte load per lane)
-  static constexpr int U = (M <= 8) ? 8 : (M <= 16) ? 4 : (M <= 32) ? 2 : 1;  // sub-steps per block: loads of a block fly together
-  static constexpr int BLK = SUB * U;               // rows per workgroup block
-  // blocks between two capacity votes (the only barrier of the streaming loop): one vote per ~32768 rows.  Measured at
-  // SIFT1M shape, votes every 1 / 2 / 4 / 8 blocks: k = 1 2.13 / 2.05 / 2.00 / 1.99 ms, k = 1000 2.62 / 2.62 / 2.46 / 2.44;
-  // the candidate buffers grow by 2 * VP * BLK keys (a slow wavefront may still be appending the previous period's rows)
-  static constexpr int VP = (32768 / BLK) < 1 ? 1 : (32768 / BLK) > 8 ? 8 : (32768 / BLK);
-  static constexpr int LUT_BYTES = M * QG * 1024;   // full table; the LDS part is LUT_LDS_BYTES below
-  // The LDS gather pipe is the kernel's bound (~11-12 cycles per 64-lane ds_read_b128 with random
-  // slots).  The vector-memory path can gather the same 16 bytes from an L1-resident table in ~29
-  // cycles per wavefront (tools/micro/gather_l1.hip) and runs beside the LDS, so the LAST KG
-  // sub-quantizers (~25 % of the gathers, <= 16 KiB of table) are looked up through L1 instead.
-  static constexpr int KG = (M == 8) ? (RQ_QG16 ? 4 : 2) : (M == 16) ? 4 : (M == 32) ? 4 : (M == 4) ? 1 : 0;   // M = 64: all in LDS
-  static constexpr int KL = M - KG;                 // sub-quantizers [0, KL) gather from LDS
-  static constexpr int GTAB_F4 = KG * NQUAD * 256;  // entries (float4 for QPG = 4) of the global (L1) table
-  static constexpr int LUT_LDS_BYTES = KL * QG * 1024;
-  // integer pre-filter (see build_qtab): one byte per (sub-quantizer, code, query); tiled for M = 8 and 16
-  static constexpr bool HAS_FILT = (M == 4 || M == 8 || M == 16) && SCAN_THREADS == 512;     // (the default build; m = 4 since round 6: PQ / CQ tables only)
-  // byte accumulator sets: 8 sub-quantizers each; m = 8 in FINE mode: two sets of 4 with 6-bit entries (half the step)
-  static constexpr int NACC = HAS_FILT ? (M == 8 ? 2 : M >= 8 ? M / 8 : 1) : 1;
-  static constexpr int kpa(bool fine) { return (M == 8 && fine) ? 4 : 8; }   // sub-quantizers per accumulator set
-  static constexpr int QTAB_BYTES = HAS_FILT ? (M + 1) * 256 * QG : 0;   // + 1: the row-norm table of LSQ scans
-  // scratch behind the staged queries: the threshold sample's [QG][THREADS] minima, later the filter table
-  static constexpr int AUX_BYTES = (QG * THREADS * 4 > QTAB_BYTES) ? QG * THREADS * 4 : QTAB_BYTES;
-  static_assert(RPT >= 1, "M too large for this tiling");
-};
-
-template <int QG>
-struct ScanCtrl {
-  float tau[QG];
-  uint32_t cnt[QG];
-  uint32_t sel[QG];     // which half of the candidate ping-pong buffer is current
-  uint32_t item;
-  uint32_t selmask;     // bit q == sel[q] (one LDS word the hot loop reads per block)
-  uint32_t pad[2];
-  // integer pre-filter (FILT kernels): per-(sub-quantizer, query) table minima and the per-query scale
-  float fmin[16][QG];
-  float fmax[16][QG];   // LSQ scans: per-(sub-quantizer, query) max |entry| (absolute rounding margins)
-  float finv[QG];
-  uint32_t fpush;       // rows the pre-filter let through in the item's first block (it is switched off if too many)
-  SelState<QG> st;      // st.hist doubles as the per-wavefront queues of rows waiting for the exact evaluation
-};
-
-struct ScanParams {
-  const uint8_t *codes;     // [n][M]
-  const float *centers;     // [M][256][sub]
-  const float *queries;     // [nq][d]
-  uint32_t n, nq;
-  int sub, d, K;
-  int m_real;               // sub-quantizers that exist; tables k >= m_real are all-zero padding
-  int lut_mode;             // 0 PQ sub-space (c-q)^2 | 1 LSQ -2<q,c> full-dim | 2 CQ (q-c)^2 full-dim
-  const float *row_bias;    // LSQ: dbnorms[n], added after the table sum; else nullptr
-  const uint8_t *norm_bytes;  // LSQ pre-filter: row norms quantised to 256 lower edges, [n]
-  const float *norm_info;     // ... {nmin, nstep, max |.|} of the quantised quantity: norm[row] - sum_k |c_k[b_k]|^2
-  const float *cnorm;         // ... |c_k[r]|^2, [M][256]: folded into the filter's tables (see build_qtab)
-  const uint32_t *perm;     // bank-aware row order (rq_order.hip): perm[position] = original row, read for survivors only; or nullptr
-  uint32_t samp_end;        // ... below this position one block in every samp_stride is an arrival-order sample of the base
-  uint32_t samp_stride;     //     (order_sample_rows, rq_order.hip); samp_end == 0: none
-  uint32_t id_offset;
-  int id_base;
-  uint32_t nslices, rows_per_slice, ngroups;
-  uint32_t whole;           // query groups [0, whole) are ONE item over all rows (answer written directly);
-                            // groups [whole, ngroups) are cut into nslices row slices (key lists -> merge)
-  uint32_t xcd_mode;        // 1: big base -- row windows are handed out per XCD (work_counter[0..7]), see the item loop
-  uint32_t xcd_slack;       // ... an item may start while at most this many items of the XCD's earlier rounds still run
-  uint32_t xcd_round;       // ... items per pacing round (a window's items, or the XCD's resident workgroups)
-#if RQ_SCAN_PACE_BUILD      // (experiment builds only: even unused kernel arguments moved the streaming loop's register allocation)
-  uint32_t *pace;           // chunk pacing inside a round (round 6): [8][SCAN_PACE_SLOTS][2] {chunks done, members}; nullptr = off
-  uint32_t pace_lag;        // ... a workgroup runs at most this many chunks ahead of its wave's average
-  uint32_t pace_votes;      // ... a chunk = this many capacity votes (VP blocks each)
-#endif
-  uint32_t cap;             // candidate buffer capacity per query (keys)
-  uint32_t trigger;         // compact when cnt > trigger  (cap - 2*VP*BLK >= trigger >= K)
-  uint32_t p2;              // next_pow2(K)
-  uint32_t scratch_keys;    // LDS sort scratch capacity in keys
-  uint32_t sample;          // rows sampled per slice to initialise tau (0 = off)
-  uint32_t sample_rt;       // ... for slices that get the second estimate (a looser first tau only rules 1/8 of the rows)
-  uint32_t srank_mul;       // target survivors per slice = srank_mul * K (3; 0 forces the fallback, tests)
-  int retune_z;             // second threshold estimate after 1/8 of the rows: rank = mean + z sigma (6; 0 = off; < 0: tests)
-  int retune_min_k;         // ... only for K >= this
-  int retune_div;           // ... after rows / retune_div rows (8)
-  uint32_t *work_counter;
-  float4 *gtab;               // [gridDim][GTAB_F4] L1-gathered part of the LUT
-  unsigned long long *stats;  // optional [8]: cycles in lut, sample, stream, cuts, final cut, sort; #cuts; #fallbacks
-  uint64_t *cand;           // [gridDim][QG][2][cap]
-  uint16_t *bkt;            // [gridDim][cap] bucket ids of the large-K sample sort
-  int filter;               // 1: 8-bit lower-bound pre-filter in front of the exact evaluation (FILT kernels)
-  int bigk;                 // K > SCAN_SS_MIN_K: finish with samplesort_topk instead of cut + LDS bitonic (1: map buckets first, 2: sorted splitters only)
-  int bfin;                 // K <= SCAN_SS_MIN_K: cut + sort per query by one wavefront through distance buckets (SCAN_BUCKET_FINISH)
-  // outputs of whole items: dists/ids [nq][K], or packed keys [nq][K] when keys != nullptr;
-  // of sliced items: part [(query - whole*QG)][nslices][K] packed keys
-  float *dists;
-  uint32_t *ids;
-  uint64_t *keys;
-  uint64_t *part;
-};
 
 // ------------------------------------------------------------------------------------------
 // LUT construction, one (k, r) entry at a time for all QG queries of the group; compiled with
@@ -281,7 +158,6 @@ __device__ __forceinline__ void load_row(uint32_t *w, const uint8_t *codes, uint
   }
 }
 
-
 // ------------------------------------------------------------------------------------------
 // Survivors of one wave-row-step: lane `lane` holds the exact distances acc[q] of ONE row (key id `kid`) to the
 // QG queries; rows with acc[q] <= tau[q] are appended to query q's candidate buffer (INCLUSIVE: tau is a sampled
@@ -326,6 +202,5 @@ __device__ __forceinline__ void emit_survivors(const float (&acc)[QG], const flo
     }
   }
 }
-
 
 }  // namespace rq

@@ -112,9 +112,6 @@ SWITCHES = {
     "SCAN_XCD_ROUND": dict(default=0, values=(1, 3), workload="scan_xcd",
                            note="no readout: the pacing round of the XCD plan (the plan is asserted to stay the XCD plan)"),
     "SCAN_STATS": dict(default=0, reason="fills the finish / fallback counters of rq_scan_finish_stats; results untouched"),
-    "SCAN_PACE": dict(default=0, reason="read only in -DRQ_SCAN_PACE_BUILD=1 experiment builds, not in the shipped library"),
-    "SCAN_PACE_LAG": dict(default=2, reason="read only in -DRQ_SCAN_PACE_BUILD=1 experiment builds, not in the shipped library"),
-    "SCAN_PACE_VOTES": dict(default=1, reason="read only in -DRQ_SCAN_PACE_BUILD=1 experiment builds, not in the shipped library"),
     # ---- host-pointer calls (rq_api.hip) ----
     "HOST_DIRECT": dict(default=1, values=(0,), workload="host",
                         note="no readout: how results reach the host arrays; compared with the default call and the oracle"),

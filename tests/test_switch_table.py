@@ -14,7 +14,7 @@ CSRC = os.path.join(ROOT, "rayuela.jl_amd", "csrc")
 
 
 def _code_keys():
-    """key -> set of defaults at its call sites `tuning("KEY", default)`; PACE keys -> only inside RQ_SCAN_PACE_BUILD."""
+    """key -> set of defaults at its call sites `tuning("KEY", default)`."""
     keys = {}
     for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h"))):
         src = open(path).read()
@@ -25,7 +25,7 @@ def _code_keys():
 
 def test_every_key_the_code_reads_is_in_the_table_with_its_default():
     keys = _code_keys()
-    assert len(keys) >= 70, sorted(keys)
+    assert len(keys) == 69, sorted(keys)
     assert sorted(set(keys) - set(SWITCHES)) == [], "switches missing from tests/switch_table.py"
     assert sorted(set(SWITCHES) - set(keys)) == [], "table entries the code no longer reads"
     for k, dflts in keys.items():
@@ -62,18 +62,6 @@ def test_integration_doc_names_only_keys_the_code_reads():
     assert len(named) > 30, named
     keys = _code_keys()
     assert sorted(named - set(keys)) == [], "INTEGRATION.md section 6 names keys the code does not read"
-    # SCAN_PACE* exist in experiment builds only: every call site sits inside #if RQ_SCAN_PACE_BUILD
-    src = open(os.path.join(CSRC, "rq_scan.hip")).read()
-    depth, guarded = [], []
-    for line in src.splitlines():
-        s = line.strip()
-        if s.startswith("#if"):
-            depth.append("RQ_SCAN_PACE_BUILD" in s)
-        elif s.startswith("#endif"):
-            depth.pop()
-        elif re.search(r'tuning\("SCAN_PACE', s):
-            guarded.append(any(depth))
-    assert guarded and all(guarded)
 
 
 def _scan_plan():
@@ -117,7 +105,7 @@ def test_reset_returns_a_switch_to_its_default(monkeypatch):
 
 
 def test_the_table_holds_every_key_at_once():
-    """Setting every switch of the table in one process (72 keys) used to fail with 'too many tuning keys' past 64."""
+    """Setting every switch of the table in one process (69 keys) used to fail with 'too many tuning keys' past 64."""
     with switches(**{k: e["default"] for k, e in SWITCHES.items()}):
         pass
     with pytest.raises(KeyError):
