@@ -108,7 +108,7 @@ int rq_dev_linscan_aq(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t
  * in DESIGN.md section 4.14.  codes [n][m] uint8 zero-based, C [m][h][d] (m full-dimensional codebooks back to back), 1 <= m <= 64,
  * 2 <= h <= 256, d >= 1, 1 <= hn <= 256; n >= 0, and n >= hn for rq_get_norms_codebook.  Every argument (each code being below
  * h included) is checked before any work, errors go through rq_last_error and leave the outputs untouched.  Non-finite
- * codebook entries, norms or cbnorms give unspecified results, as for rq_train_rvq.
+ * codebook entries, norms or cbnorms give unspecified values, as for rq_train_rvq ("Non-finite inputs of the encode" below).
  *
  * rq_aq_norms (src/utils.jl:15-16, :34-48: reconstruct, then sum(CB.^2)): norms[i] = |sum_k C_k[b_ik]|^2 without the n x d
  * reconstruction, in veccost's order of f32 sums: CB[t] by adds from +0 in codebook order, 64 partial sums of CB[t]^2 over
@@ -183,7 +183,8 @@ int rq_last_beam_timing(double *ms, int cap);
  * section 2 ("ERVQ").  quantize_ervq IS quantize_rvq (src/ERVQ.jl:19-26): use rq_encode_rvq.  Layouts as for RVQ: X [n][d],
  * C [m][h][d] (m full-dimensional codebooks back to back, one entry per row).  1 <= m <= 64, 2 <= h <= 256, any d >= 1.
  * Every argument (each code's range included) is checked before any work; errors through rq_last_error.  Non-finite input
- * gives unspecified results, as for rq_train_rvq.
+ * gives unspecified values under the guarantees of "Non-finite inputs of the encode" below (the call returns, codes in range,
+ * the same bits twice), as for rq_train_rvq.
  *
  * The codebook update of one step alone (src/ERVQ.jl:85-90, Clustering.update_centers! unweighted): every entry k of block
  * j (zero-based, 0 <= j < m) that has rows becomes the mean of X - sum_{i != j} C_i[b_i] over the rows with b_j = k, computed
@@ -375,6 +376,25 @@ int rq_linscan_pq(float *dists, uint32_t *ids, const uint8_t *codes, const float
 int rq_linscan_opq(float *dists, uint32_t *ids, const uint8_t *codes, const float *centers,
                    const float *queries, const float *R, int64_t n, int64_t nq, int m, int d,
                    int k, int id_base);
+/* Non-finite inputs of the encode at h <= 256 -- rq_encode_pq / rq_encode_opq, their rq_dev_*, _i16, _bytes and
+ * rq_dataset_encode forms, rq_rotate_T, every kernel the dispatch can choose (tests/test_gpu_nonfinite_encode.py; the oracle
+ * side of it on the same inputs: tests/test_nonfinite_encode_ref.py):
+ *   1. the call returns RQ_OK and every code written is below h (1 .. h in the one-based forms);
+ *   2. rows are encoded independently: a finite row under finite codebooks has the reference arithmetic's codes, bit for
+ *      bit, whatever the other rows of its tile, chunk or launch hold;
+ *   3. sub-quantizers are independent: a non-finite entry of codebook i leaves column j != i of every finite row unchanged;
+ *      column i is in range and otherwise unspecified;
+ *   4. a sub-vector whose every distance is NaN (any NaN coordinate; an Inf coordinate that makes every u_k NaN) gets code 0,
+ *      which is what max(NaN, 0) = 0 with a strict `<` gives in the reference arithmetic.  Other poisoned sub-vectors (mixed
+ *      Inf / NaN distances, |x|^2 overflowing to +Inf) are in range and otherwise unspecified;
+ *   5. rotation: a finite row under a finite R is R'x bit for bit; a poisoned row is NaN exactly where the k-ordered fmaf chain
+ *      is NaN and bit-equal where that is finite or +-Inf.  With a non-finite R the call returns, no further claim;
+ *   6. the OPQ encode is 5 followed by 1 - 4.
+ * Training on a base with non-finite rows (rq_train_pq, rq_train_opq, rq_train_rvq, rq_kmpp_seeds, rq_train_ervq,
+ * rq_ervq_update_codebook with in-range codes): the call returns RQ_OK or a negative status with a message, B1 lies in 1 .. h,
+ * the seeds in [0, n), every row is counted once per stage, and the same call gives the same bits twice.  Codebooks, R and the
+ * objective are unspecified (one non-finite row turns every centre of its sub-space into NaN: the segment sums are matrix
+ * products).  LSQ / chain / SR training are not covered. */
 /* quantize_pq (src/PQ.jl:18-48): codes [n][m] uint8 zero-based.  h <= 256. */
 int rq_encode_pq(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h);
 /* quantize_opq (src/OPQ.jl:19-27). */

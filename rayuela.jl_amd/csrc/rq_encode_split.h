@@ -157,11 +157,24 @@ __device__ __forceinline__ void tile_argmin(const f32x16 &acc, const float4 *sa4
 
 // First index of the clamped minimum inside the winning tile: the first r with u_r <= cm (for
 // cm > 0 that is the first minimum; for cm == 0 the first value the reference's max(.,0) clamps).
+//
+// Non-finite inputs (include/rayuela_hip.h, "Non-finite inputs"; tests/test_gpu_nonfinite_encode.py).  best_v is never NaN
+// (fmaxf(NaN, 0) = 0).  A lane's search finds nothing in exactly one case: the 16 u values of its winning tile are ALL NaN
+// (fminf skips NaN operands, so a tile with one ordered value has its minimum among them; and a lane that never took a tile
+// keeps best_v = +Inf over ub = 0, which finds r = 0).  All NaN means a NaN coordinate, or an Inf one against this lane's
+// centroids: mm = NaN, cm = 0 < +Inf, the tile is taken.  The oracle's fmaxf clamps every such distance to 0 and answers with
+// the first centroid, so the lane answers 0 -- the sub-quantizer's index 0, not a position inside the tile, which at h < 28
+// (27 + 4 hi) or in a tile of zero-padded centroids (k >= h: +Inf norm, 0 * Inf = NaN under an Inf row) lies past h.
+// An index that IS found is below h: a padded centroid's u is +Inf (finite row) or NaN, and neither is <= a best_v below +Inf.
+// The half-wave merge of the callers keeps the smaller (value, index) pair: an unfound lane carries (0, 0), which no pair
+// precedes, and a lane that never took a tile carries (+Inf, 4 hi), which the other half's (<= +Inf, 0 or a found index)
+// precedes or ties with a smaller index -- so the merged index is below h as well.  Once per (row, sub-quantizer): one
+// compare and one select more than the search itself.
 __device__ __forceinline__ int argmin_finish(const ArgminState &st, int hi) {
-  int rf = 15;
+  int rf = 16;
 #pragma unroll
-  for (int r = 14; r >= 0; --r) rf = (((r & 1) ? st.ub[r >> 1].y : st.ub[r >> 1].x) <= st.best_v) ? r : rf;
-  return st.best_t * 32 + 4 * hi + 8 * (rf >> 2) + (rf & 3);
+  for (int r = 15; r >= 0; --r) rf = (((r & 1) ? st.ub[r >> 1].y : st.ub[r >> 1].x) <= st.best_v) ? r : rf;
+  return rf == 16 ? 0 : st.best_t * 32 + 4 * hi + 8 * (rf >> 2) + (rf & 3);
 }
 
 // Prologue: the codebooks of sub-quantizers [i0, i0 + mg) -> LDS in A-fragment order, cbA [mg][NT][KS][64]: lane l of k-step

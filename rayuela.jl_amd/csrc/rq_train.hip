@@ -753,7 +753,12 @@ __global__ __launch_bounds__(KMPP_THREADS) void kmpp_select_kernel(KmppParams p,
     const double before = tid ? scan[tid - 1] : 0.0;
     if (tid < p.nblk && scan[tid] > thr && !(before > thr)) { pick[0] = tid; resid = thr - before; }
     __syncthreads();
-    if (pick[0] < 0) {
+    // No block sum exceeds the threshold when `total` is +Inf (an Inf coordinate, or magnitudes near 1e19, in a row that is
+    // not a seed).  The decision must be the same in all 1024 threads, because a barrier follows inside the branch: every
+    // thread reads pick[0] into a register, and the barrier below keeps thread 0's store behind the last of those reads.
+    const long long first_blk = pick[0];
+    __syncthreads();
+    if (first_blk < 0) {
       if (tid == 0) {
         int b = p.nblk - 1;
         while (b > 0 && !(part[b] > 0.0)) --b;
@@ -791,6 +796,7 @@ __global__ __launch_bounds__(KMPP_THREADS) void kmpp_select_kernel(KmppParams p,
       pick[1] = rr;
     }
     __syncthreads();
+    // (only thread 0 enters, and the barrier after the branch is outside it: uniform whatever pick[1] holds)
     if (pick[1] < 0 && tid == 0) {      // threshold beyond the block's re-summed total: last row with a cost
       for (int64_t r = r1 - 1; r >= r0; --r) if (mcq[r * ms] > 0.0f) { pick[1] = r; break; }
       if (pick[1] < 0) pick[1] = r0;

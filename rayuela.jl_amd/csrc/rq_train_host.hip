@@ -279,10 +279,13 @@ static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n,
   RQ_TRY(dCold.alloc((size_t)h * d * 4));
   DevMem dcc;
   const size_t cnt_bytes = (size_t)m * h * 4;
-  RQ_TRY(dcc.alloc(cnt_bytes + 8));
+  // the 64-bit change counter takes atomic adds: on an 8-byte boundary also when m * h is odd (h = 17, m = 5 put it 4 bytes
+  // off, and the first iteration that changed a code faulted)
+  const size_t chg_at = (cnt_bytes + 7) & ~(size_t)7;
+  RQ_TRY(dcc.alloc(chg_at + 8));
   unsigned int *dcnt_p = dcc.as<unsigned int>();
-  unsigned long long *dchg_p = reinterpret_cast<unsigned long long *>(dcc.as<unsigned char>() + cnt_bytes);
-  std::vector<unsigned char> back(cnt_bytes + 8);
+  unsigned long long *dchg_p = reinterpret_cast<unsigned long long *>(dcc.as<unsigned char>() + chg_at);
+  std::vector<unsigned char> back(chg_at + 8);
   uint8_t *cur = dcodes, *prev = dprev.as<uint8_t>();
   int iters_done = 0;
   prof.loop_begin();
@@ -294,9 +297,9 @@ static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n,
     RQ_HIP(hipMemcpyAsync(dCold.p, dC, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
     RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch(dC, dcnt_p, dX, cur, n, d, m, h, di.num_cu, nullptr)));
     prof.start();
-    RQ_HIP(hipMemcpy(back.data(), dcc.p, cnt_bytes + 8, hipMemcpyDeviceToHost));
+    RQ_HIP(hipMemcpy(back.data(), dcc.p, chg_at + 8, hipMemcpyDeviceToHost));
     unsigned long long changed = 1;
-    if (it > 0) memcpy(&changed, back.data() + cnt_bytes, 8);
+    if (it > 0) memcpy(&changed, back.data() + chg_at, 8);
     prof.stop(TP_CONVERGE);
     if (!changed) break;   // assignments stable: Lloyd has converged
     ++iters_done;

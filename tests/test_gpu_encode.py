@@ -204,9 +204,11 @@ def test_split_encode_hostile_inputs(rq, oracle, case, waves):
     """What the filter's margin has to survive: massive exact ties (small-integer data: several centroids at the very
     same distance, in different 32-centroid tiles -> tiles re-run at the end, first index must win), duplicated
     centroids, vectors that ARE centroids (clamped zeros), magnitudes where the bound is unusable (every centroid is then
-    evaluated exactly), wide dynamic range inside one sub-space.  (Distances that overflow to inf / NaN are outside every
-    contract: Julia's `max(NaN, 0)` is NaN and `update_assignments!` then keeps centre 1 whenever `dmat[1, j]` is NaN, the C
-    oracle's fmaxf returns 0 -- the kernels are only required to agree with the oracle on finite distances.)"""
+    evaluated exactly), wide dynamic range inside one sub-space.  (Distances that overflow to inf / NaN are not this
+    test's: Julia's `max(NaN, 0)` is NaN and `update_assignments!` then keeps centre 1 whenever `dmat[1, j]` is NaN, the C
+    oracle's fmaxf returns 0.  What the kernels promise there -- codes in range, finite rows and finite sub-quantizers
+    untouched, code 0 for an all-NaN sub-vector -- is the contract above rq_encode_pq in include/rayuela_hip.h, held by
+    tests/test_gpu_nonfinite_encode.py.)"""
     rng = np.random.default_rng({"ties": 1, "dups": 2, "exact_hits": 3, "tiny": 4, "huge": 5, "mixed_scale": 6, "negative_w": 7}[case])
     m, sub, h, n = 8, 16, 256, 6_000
     if case == "ties":

@@ -347,5 +347,41 @@ def test_quantize_rvq_non_finite_rows(rq, m):
     assert int(cnt_bad.sum()) == m * ENC_N                 # every row was counted once per stage, the poisoned ones included
     # a smaller codebook: the range is no longer the type's
     C64 = [c[:64] for c in C]
-    bad64 = rq.quantize_rvq_u8(Xbad, C64)
+    bad64, cnt64, _ = rq.quantize_rvq_u8(Xbad, C64, with_extras=True)
     _enc_same(bad64, rq.quantize_rvq_u8(Xzero, C64), clean, 64, ("rvq h=64", m))
+    assert int(cnt64.sum()) == m * ENC_N
+
+
+@pytest.mark.parametrize("h", [16, 17, 27])
+@pytest.mark.parametrize("m", [4, 8])
+def test_quantize_rvq_non_finite_rows_small_h(rq, m, h):
+    """h < 28: where a stage encode whose distances are all NaN used to answer 27 (rq_encode_split.h, argmin_finish) and the
+    stage epilogue then read the codebook and bumped the counts at that index.  The counts and the codebooks sit inside
+    guard-filled device buffers of the test's own, so a stray atomic add or read stays in memory the test owns and shows as
+    a changed guard word or a changed code."""
+    import torch
+    Xbad, Xzero, Cs, _, clean = _enc_data(m, seed=90 + m)
+    Ch = np.ascontiguousarray(Cs[:, :h])
+    G, GUARD_I, GUARD_F = 4096, 0x5A5A5A5A, 12345.0
+    lib = _L().lib()
+
+    def run(X):
+        cbuf = torch.full((2 * G + m * h,), GUARD_I, dtype=torch.int32, device="cuda")
+        bbuf = torch.full((2 * G + Ch.size,), GUARD_F, dtype=torch.float32, device="cuda")
+        bbuf[G:G + Ch.size] = torch.from_numpy(Ch.reshape(-1)).cuda()
+        codes = torch.full((ENC_N, m), 0xEE, dtype=torch.uint8, device="cuda")
+        Xr = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+        _L().check(lib.rq_dev_encode_rvq(codes.data_ptr(), Xr.data_ptr(), bbuf[G:].data_ptr(), ENC_N, ENC_D, m, h,
+                                         cbuf[G:].data_ptr(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        assert bool((cbuf[:G] == GUARD_I).all()) and bool((cbuf[G + m * h:] == GUARD_I).all()), "a count landed outside [m][h]"
+        assert bool((bbuf[:G] == GUARD_F).all()) and bool((bbuf[G + Ch.size:] == GUARD_F).all())
+        return codes.cpu().numpy(), cbuf[G:G + m * h].cpu().numpy().reshape(m, h)
+    bad, cnt_bad = run(Xbad)
+    zero, cnt_zero = run(Xzero)
+    _enc_same(bad, zero, clean, h, ("rvq", m, h))
+    assert int(cnt_bad.sum()) == m * ENC_N and (cnt_bad.sum(axis=1) == ENC_N).all()
+    assert np.array_equal(cnt_bad, np.stack([np.bincount(bad[:, i], minlength=h) for i in range(m)]))
+    assert np.array_equal(cnt_zero, np.stack([np.bincount(zero[:, i], minlength=h) for i in range(m)]))
+    # the first stage of the row that is NaN throughout: every distance NaN, code 0 (the oracle's answer)
+    assert bad[64, 0] == 0
