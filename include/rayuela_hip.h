@@ -647,6 +647,45 @@ int rq_train_pq(float *C, int16_t *B1, double *error, const float *X, int64_t n,
 int rq_kmpp_seeds(int64_t *seeds, float *C, const float *X, int64_t n, int d, int m, int h, uint64_t seed);
 int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, int64_t n, int d, int m,
                  int h, int niter, int init, uint64_t seed, const float *R0, const float *C0);
+/* ---- training with more than 256 codewords per codebook: 16-bit codes.  train_pq (src/PQ.jl:68-99),
+ * train_opq (src/OPQ.jl:49-139) and train_rvq (src/RVQ.jl:86-127) return Matrix{Int16} codes so that a codebook may hold more than
+ * 256 entries; rq_train_pq / rq_train_opq / rq_train_rvq keep refusing h > 256 (their loops run on bytes), these accept
+ * 1 <= h <= RQ_MAX_H16.  The SAME loops, instantiated for 16-bit codes: the assignment step is the wide encode (section 4.17), the
+ * centres come from rq_dev_update_centers_wide's kernel, emptied centres are re-drawn by Clustering.repick_unused_centers' rule
+ * with the costs computed in double on the device (only the n costs come to the host per draw), train_opq reconstructs into an
+ * n x d temporary for X'CB and the objective.  The random stream is that of the byte entry points at any h: salts 1 / 2 / 3, the
+ * same order of draws.  h <= 256 runs the byte loops and widens: C, R, obj, error and the codes are the bits of rq_train_pq /
+ * rq_train_opq / rq_train_rvq for the same arguments.  Layouts are those of the byte entry points; B [n][m] int16 + code_base,
+ * code_base 0 (zero-based) or 1 (Julia's one-based Matrix{Int16}), as in the wide encodes.  rq_train_profile describes the last
+ * wide call with the same slots.  A NULL C, B, X (or R), a bad code_base, d < m, n < h or niter < 0: RQ_EINVAL; h outside
+ * [1, RQ_MAX_H16] or m out of range (PQ / OPQ: 1..32, RVQ: 1..64): RQ_EUNSUPPORTED; on any error no output byte is written.
+ * The non-finite contract pinned for training at h <= 256 is NOT extended to h > 256: non-finite rows give unspecified centres
+ * (no fault). */
+int rq_train_pq_wide(float *C, int16_t *B, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                     uint64_t seed, int code_base);
+int rq_train_opq_wide(float *C, int16_t *B, float *R, float *obj, const float *X, int64_t n, int d, int m, int h, int niter,
+                      int init, uint64_t seed, const float *R0, const float *C0, int code_base);
+int rq_train_rvq_wide(float *C, int16_t *B, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                      uint64_t seed, int code_base);
+/* The two reductions of those loops that read codes, on device pointers, everything on `stream` (kernels, scratch, the reduction
+ * of the partial sums): codes [n][m] int16 ZERO-based, read zero-extended; 1 <= h <= RQ_MAX_H16, 1 <= m <= 32, any d >= m, uneven
+ * splits (src/utils.jl:179-203), any n.
+ *   update_centers  (Clustering.update_centers! as called at src/OPQ.jl:121) C the m [h][sub_i] blocks, counts [m][h]: for each
+ *                   (sub-quantizer q, code k, dimension s) the f32 sum of X[row][off_q + s] over the rows with codes[row][q] == k
+ *                   in a FIXED order (one-hot products on the matrix cores, row slices combined in a fixed tree; no float
+ *                   atomics): two calls on the same input give the same bits.  C = sum * (1.0f / (float)count) for count > 0; a
+ *                   code without rows keeps its bits; counts are exact.  On integer-valued X (coordinates in [0, 255]) with fewer
+ *                   than 65 793 rows per code every partial sum is an exact integer below 2^24 and the result is
+ *                   float32(sum) * (1.0f / float32(count)) bit for bit.  A row whose code lies outside [0, h) (negative ones
+ *                   included) is IGNORED in that sub-space: not summed, not counted, never used as an index.  Non-finite X:
+ *                   unspecified values (a non-finite row may turn every centre of its sub-space into NaN), no fault.
+ *   reconstruct     (src/OPQ.jl:101,128) CB[j][off_i + s] = C_i[codes[j][i]][s], a pure copy.  A code outside [0, h) is not
+ *                   read from C: that sub-space of row j is written as ZEROS.
+ * n <= 0: RQ_OK.  A NULL pointer or d < m: RQ_EINVAL; h or m out of range, or a shape whose partial sums do not fit 2 GiB of
+ * scratch: RQ_EUNSUPPORTED. */
+int rq_dev_update_centers_wide(float *C, uint32_t *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
+                               void *stream);
+int rq_dev_reconstruct_wide(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream);
 /* Phase clock of the calling thread's last rq_train_pq / rq_train_opq call, milliseconds (measurement aid, bench.py
  * --workload train_opq|train_pq): out[0] X upload, [1] initialisation, [2] qerror, [3] gram X'CB, [4] d x d polar factor
  * incl. its two small copies, [5] rotation, [6] update_centers, [7] encode, [8] reconstruct, [9] convergence check,

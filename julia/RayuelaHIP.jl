@@ -232,6 +232,13 @@ function train_rvq(X::Matrix{Float32}, m::Integer, h::Integer, niter::Integer=25
   Ccat = Array{Float32}(undef, d, h, m)            # C view [m][h][d]
   B    = _result(Int16, m, n)
   err  = Ref{Cdouble}(0.0)
+  if h > 256      # more than 256 codewords per stage: the same loop on 16-bit codes, rq_train_rvq_wide
+    code_base = 1
+    _check(ccall((:rq_train_rvq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64, Cint),
+      Ccat, B, err, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed), Cint(code_base)))
+    return [Ccat[:, :, i] for i = 1:m], B, Float32(err[])
+  end
   _check(ccall((:rq_train_rvq, librayuela_hip), Cint,
     (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64),
     Ccat, B, err, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed)))
@@ -500,6 +507,13 @@ function train_pq(X::Matrix{Float32}, m::Integer, h::Integer, niter::Integer=25,
   Ccat = Vector{Float32}(undef, h * d)
   B    = _result(Int16, m, n)
   err  = Ref{Cdouble}(0.0)
+  if h > 256      # more than 256 codewords per codebook: the same loop on 16-bit codes, rq_train_pq_wide
+    code_base = 1
+    _check(ccall((:rq_train_pq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64, Cint),
+      Ccat, B, err, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed), Cint(code_base)))
+    return _split_codebooks(Ccat, d, Int(m), Int(h)), B, Float32(err[])
+  end
   _check(ccall((:rq_train_pq, librayuela_hip), Cint,
     (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64),
     Ccat, B, err, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed)))
@@ -516,6 +530,15 @@ function train_opq(X::Matrix{Float32}, m::Integer, h::Integer, niter::Integer, i
   B    = _result(Int16, m, n)
   R    = Matrix{Float32}(undef, d, d)
   obj  = zeros(Float32, niter + 1)
+  if h > 256      # more than 256 codewords per codebook: the same loop on 16-bit codes, rq_train_opq_wide
+    code_base = 1
+    _check(ccall((:rq_train_opq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, UInt64,
+       Ptr{Cfloat}, Ptr{Cfloat}, Cint),
+      Ccat, B, R, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), Cint(init == "natural" ? 0 : 1),
+      UInt64(seed), C_NULL, C_NULL, Cint(code_base)))
+    return _split_codebooks(Ccat, d, Int(m), Int(h)), B, R, obj
+  end
   _check(ccall((:rq_train_opq, librayuela_hip), Cint,
     (Ptr{Cfloat}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, UInt64,
      Ptr{Cfloat}, Ptr{Cfloat}),

@@ -62,7 +62,8 @@ def train_opq(X, m, h, niter, init, V=False, seed=0, R0=None, C0=None):
 
     init: "natural" (R = I) or "random"; R0 / C0 optionally pin the initial rotation / codebooks.
     Returns C (list of (h, sub_i)), B (n, m) int16 one-based, R (d, d) memory image of Julia's R,
-    obj (niter+1,) float32 -- the objective before every iteration."""
+    obj (niter+1,) float32 -- the objective before every iteration.
+    256 < h <= 32767 codewords per codebook take rq_train_opq_wide; the return types are the same."""
     from .PQ import _split_codebooks
     X = _as_f32(X, "X")
     n, d = X.shape
@@ -74,9 +75,12 @@ def train_opq(X, m, h, niter, init, V=False, seed=0, R0=None, C0=None):
     obj = np.zeros(niter + 1, dtype=np.float32)
     r0 = None if R0 is None else _as_f32(R0, "R0")
     c0 = None if C0 is None else cat_codebooks(C0)
-    _lib.check(_lib.lib().rq_train_opq(Ccat.ctypes.data, B.ctypes.data, R.ctypes.data, obj.ctypes.data, X.ctypes.data,
-                                       n, d, m, h, niter, 0 if init == "natural" else 1, seed,
-                                       None if r0 is None else r0.ctypes.data, None if c0 is None else c0.ctypes.data))
+    args = (Ccat.ctypes.data, B.ctypes.data, R.ctypes.data, obj.ctypes.data, X.ctypes.data, n, d, m, h, niter,
+            0 if init == "natural" else 1, seed, None if r0 is None else r0.ctypes.data, None if c0 is None else c0.ctypes.data)
+    if check_wide_h(h):
+        _lib.check(_lib.lib().rq_train_opq_wide(*args, 1))
+    else:
+        _lib.check(_lib.lib().rq_train_opq(*args))
     if V:
         for it, o in enumerate(obj):
             print("%3d %e" % (it, o))

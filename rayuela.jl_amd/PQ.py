@@ -72,15 +72,20 @@ def train_pq(X, m, h, niter=25, V=False, seed=0):
     Lloyd's k-means in every subspace (all m subspaces per device pass), through rq_train_pq.
     C: list of m (h, sub_i) codebooks; B: (n, m) int16 one-based; error: qerror_pq of the result.
     Initial centres: kmeans++ like the reference (kmeans(..., init=:kmpp)), drawn from the library's seeded
-    stream rather than Julia's RNG (see include/rayuela_hip.h)."""
+    stream rather than Julia's RNG (see include/rayuela_hip.h).
+    256 < h <= 32767 codewords per codebook take rq_train_pq_wide (the same loop on 16-bit codes); the return types are the same."""
     X = _as_f32(X, "X")
     n, d = X.shape
+    wide = check_wide_h(h)
     Ccat = np.empty(h * d, dtype=np.float32)
     B = np.empty((n, m), dtype=np.int16)
     import ctypes
     err = ctypes.c_double(0.0)
-    _lib.check(_lib.lib().rq_train_pq(Ccat.ctypes.data, B.ctypes.data, ctypes.cast(ctypes.byref(err), ctypes.c_void_p),
-                                      X.ctypes.data, n, d, m, h, niter, seed))
+    perr = ctypes.cast(ctypes.byref(err), ctypes.c_void_p)
+    if wide:
+        _lib.check(_lib.lib().rq_train_pq_wide(Ccat.ctypes.data, B.ctypes.data, perr, X.ctypes.data, n, d, m, h, niter, seed, 1))
+    else:
+        _lib.check(_lib.lib().rq_train_pq(Ccat.ctypes.data, B.ctypes.data, perr, X.ctypes.data, n, d, m, h, niter, seed))
     if V:
         print("  Error in training is %e" % err.value)
     return _split_codebooks(Ccat, d, m, h), B, float(err.value)

@@ -96,15 +96,18 @@ def train_rvq(X, m, h, niter=25, V=False, seed=0):
     One k-means per stage on the running residual, all on the device (rq_train_rvq).  C: m-long list of
     (h, d) codebooks; B: (n, m) int16 one-based, equal to quantize_rvq(X, C)[0]; error = qerror(X, B, C).
     Seeding is kmeans++ on the running residual like the reference, drawn from the library's seeded stream
-    (the reference: Julia's RNG)."""
+    (the reference: Julia's RNG).  256 < h <= 32767 codewords per stage take rq_train_rvq_wide; the return types are the same."""
     import ctypes
     X = _as_f32(X, "X")
     n, d = X.shape
     C = np.empty((m, h, d), dtype=np.float32)
     B = np.empty((n, m), dtype=np.int16)
     err = ctypes.c_double(0.0)
-    _lib.check(_lib.lib().rq_train_rvq(C.ctypes.data, B.ctypes.data, ctypes.cast(ctypes.byref(err), ctypes.c_void_p),
-                                       X.ctypes.data, n, d, m, h, niter, seed))
+    perr = ctypes.cast(ctypes.byref(err), ctypes.c_void_p)
+    if check_wide_h(h):
+        _lib.check(_lib.lib().rq_train_rvq_wide(C.ctypes.data, B.ctypes.data, perr, X.ctypes.data, n, d, m, h, niter, seed, 1))
+    else:
+        _lib.check(_lib.lib().rq_train_rvq(C.ctypes.data, B.ctypes.data, perr, X.ctypes.data, n, d, m, h, niter, seed))
     if V:
         print("  Error after codebook %d is %e" % (m, err.value))
     return [C[i] for i in range(m)], B, float(err.value)

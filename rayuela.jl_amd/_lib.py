@@ -132,6 +132,11 @@ SIGNATURES = {
     "rq_kmpp_seeds": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _u64]),
     "rq_train_pq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _u64]),
     "rq_train_opq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _vp]),
+    "rq_train_pq_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _u64, _i32]),
+    "rq_train_opq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _i32]),
+    "rq_train_rvq_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _u64, _i32]),
+    "rq_dev_update_centers_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_dev_reconstruct_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "rq_train_profile": (_i32, [_vp, _i32]),
     "rq_dev_polar_factor": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "rq_index_create": (_vp, [_i32, _i32, _vp]),

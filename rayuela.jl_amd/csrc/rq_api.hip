@@ -1781,6 +1781,22 @@ int rq_dev_reconstruct(float *CB, const uint8_t *codes, const float *C, int64_t 
   return reconstruct_launch(CB, codes, C, n, d, m, h, (hipStream_t)stream);
 }
 
+// the same two over 16-bit codes (rq_train.hip); h <= 256 runs the 16-bit kernels too
+int rq_dev_update_centers_wide(float *C, uint32_t *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
+                               void *stream) {
+  if (n <= 0) return RQ_OK;
+  if (!C || !counts || !X || !codes) return fail(RQ_EINVAL, "rq_dev_update_centers_wide: NULL argument");
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  return update_centers_h16_launch(C, counts, X, codes, n, d, m, h, di.num_cu, (hipStream_t)stream);
+}
+
+int rq_dev_reconstruct_wide(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
+  if (n <= 0) return RQ_OK;
+  if (!CB || !codes || !C) return fail(RQ_EINVAL, "rq_dev_reconstruct_wide: NULL argument");
+  return reconstruct_h16_launch(CB, codes, C, n, d, m, h, (hipStream_t)stream);
+}
+
 int rq_dev_qerror(double *acc, const float *X, const float *CB, int64_t n, int d, void *stream) {
   DeviceInfo di;
   RQ_TRY(device_info(&di));

@@ -37,53 +37,14 @@ namespace rq {
 
 namespace {
 
-// Costs of the refill, f64, one thread per row, the d terms in ascending order (the host loop of repick_unused bit for bit):
-// BY_CODE: tc[row] = |P[row] - Cref[code(row)]|^2 (Cref [h][d]); else tc[row] = min(tc[row], |P[row] - Cref|^2) (Cref [d]).
-template <bool BY_CODE>
-__global__ __launch_bounds__(256) void ervq_cost_kernel(double *tc, const float *__restrict__ P, const float *__restrict__ Cref,
-                                                        const uint8_t *__restrict__ codes, int cstride, int col, int64_t n, int d) {
-  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (row >= n) return;
-  const float *x = P + row * d;
-  const float *c = BY_CODE ? Cref + (size_t)codes[row * cstride + col] * d : Cref;
-  double a = 0;
-  for (int t = 0; t < d; ++t) {
-    const double e = (double)x[t] - (double)c[t];
-    a += e * e;
-  }
-  if (BY_CODE) tc[row] = a;
-  else if (a < tc[row]) tc[row] = a;
-}
-
 // Clustering.repick_unused_centers for the `unused` entries of Cj [h][d]: rows of P drawn with probability proportional to
 // their cost under Cold (the entries the codes were assigned with); the drawn row's cost drops to zero and every cost is
-// lowered to the distance to the new entry before the next draw.  dtc: n doubles of device scratch.
+// lowered to the distance to the new entry before the next draw.  dtc: n doubles of device scratch.  The costs (f64, one thread
+// per row, the d terms in ascending order: the host loop of repick_unused bit for bit) and the draws are refill_unused_launch's
+// (rq_train.hip), here on the whole row: columns [0, d).
 int ervq_refill(float *Cj, const float *Cold, const float *P, const uint8_t *codes, int cstride, int col, int64_t n, int d,
                 const std::vector<int> &unused, Rng &rng, double *dtc, std::vector<double> &tc, hipStream_t stream) {
-  const dim3 grid((uint32_t)((n + 255) / 256));
-  hipLaunchKernelGGL(ervq_cost_kernel<true>, grid, dim3(256), 0, stream, dtc, P, Cold, codes, cstride, col, n, d);
-  RQ_HIP(hipGetLastError());
-  tc.resize((size_t)n);
-  for (size_t q = 0; q < unused.size(); ++q) {
-    RQ_HIP(hipMemcpyAsync(tc.data(), dtc, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
-    RQ_HIP(hipStreamSynchronize(stream));
-    double total = 0;
-    for (int64_t r = 0; r < n; ++r) total += tc[r];
-    int64_t pick = (int64_t)(rng.next() % (uint64_t)n);          // all costs zero (fewer distinct rows than entries): uniform
-    if (total > 0) {
-      const double u = rng.uniform() * total;
-      double run = 0;
-      pick = n - 1;
-      for (int64_t r = 0; r < n; ++r) { run += tc[r]; if (run > u) { pick = r; break; } }
-    }
-    float *v = Cj + (size_t)unused[q] * d;
-    RQ_HIP(hipMemcpyAsync(v, P + pick * d, (size_t)d * 4, hipMemcpyDeviceToDevice, stream));
-    if (q + 1 < unused.size()) {
-      hipLaunchKernelGGL(ervq_cost_kernel<false>, grid, dim3(256), 0, stream, dtc, P, v, codes, cstride, col, n, d);
-      RQ_HIP(hipGetLastError());
-    }
-  }
-  return RQ_OK;
+  return refill_unused_launch<uint8_t>(Cj, Cold, P, codes, cstride, col, n, d, 0, d, unused, rng, dtc, tc, stream);
 }
 
 // E = X - sum_i C_i[b_i] by m in-place epilogues in codebook order (the order quantize_rvq subtracts in)

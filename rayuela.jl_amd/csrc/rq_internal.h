@@ -369,6 +369,21 @@ int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t 
                        hipStream_t stream);
 int qerror_launch(double *acc_dev, const float *X, const float *CB, int64_t n, int d, int num_cu,
                   hipStream_t stream);
+// the same two over 16-bit codes: codes [n][m] int16 zero-based, read zero-extended, 1 <= h <= RQ_MAX_H16.
+// A code outside [0, h): update_centers ignores the row in that sub-space, reconstruct writes zeros for it.
+RQ_LOCAL int update_centers_h16_launch(float *C, unsigned int *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
+                              int num_cu, hipStream_t stream);
+RQ_LOCAL int reconstruct_h16_launch(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
+struct Rng;
+// Clustering.repick_unused_centers on the device: the `unused` entries of Csub [h][sub] re-drawn from the rows of P (stride d,
+// columns [col0, col0 + sub)); costs under Cold (the entries the codes were assigned with) in f64 on the device, only the n costs
+// come to the host per draw (tc); dtc: n doubles of device scratch.  Code: uint8_t or int16_t at codes[row * cstride + col].
+template <class Code>
+RQ_LOCAL int refill_unused_launch(float *Csub, const float *Cold, const float *P, const Code *codes, int cstride, int col, int64_t n,
+                                  int d, int col0, int sub, const std::vector<int> &unused, Rng &rng, double *dtc,
+                                  std::vector<double> &tc, hipStream_t stream);
+// Csub[k][s] = X[rows[k]][col0 + s], rows on the device
+RQ_LOCAL int gather_rows_launch(float *Csub, const float *X, const long long *rows_dev, int h, int d, int col0, int sub, hipStream_t stream);
 // kmeans++ seeding of all m sub-spaces (Clustering.jl init=:kmpp): seeds [m][h] rows, C = their sub-vectors;
 // mincost [n][m] floats and partial [m][1024] doubles are scratch, u [m][h] uniforms in [0,1) (device pointers)
 int kmpp_init_launch(float *C, long long *seeds, float *mincost, double *partial, const double *u, const float *X,

@@ -11,6 +11,8 @@
 //                    same value as |R CB - X|^2 because R is orthonormal)
 //   gram             G = X' CB  (d x d, reduced over the n rows)         (src/OPQ.jl:112, input of the host SVD)
 //                    f32 MFMA, one 32x32 output tile pair per wavefront, split over row slices
+// update_centers and reconstruct also exist over 16-bit codes (more than 256 codewords per codebook): the
+// same kernels, templated on the code type.
 // Summation orders differ from the sequential CPU loops of the reference (which are themselves not
 // pinned by any reference test): parity for these is a float tolerance, stated in tests/.
 #include "rq_internal.h"
@@ -118,11 +120,24 @@ typedef unsigned short cm_u16x2 __attribute__((ext_vector_type(2)));
 using f32x4 = float __attribute__((ext_vector_type(4)));
 using f32x2t = float __attribute__((ext_vector_type(2)));
 
-template <int NT>
-__global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nunits) {
+// 16-BIT CODES (Code = int16_t, read zero-extended): a unit is (sub-quantizer, 16-dimension block, block
+// of 256 codes) -- `nunits` units per code block, blocks blk0 .. blk0 + nblk - 1 along blockIdx.y; a row enters the unit's mask
+// only where (code >> 8) == block, the tiles and the nibble compare are the byte kernel's on the code's low byte, NT is the tile
+// count of the unit's block (the caller launches the ragged last block with its own NT).  A code outside [0, h) matches no
+// block or no tile that is written: its row is neither summed nor counted.  Code = uint8_t compiles to the byte kernel.
+template <int NT, class Code>
+__global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nunits, int blk0, int nblk) {
+  constexpr bool WIDE = sizeof(Code) == 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int unit = blockIdx.y * 8 + wave;
-  if (unit >= nunits) return;                 // (no barriers in this kernel)
+  int unit = blockIdx.y * 8 + wave;
+  uint32_t blk = 0;
+  if constexpr (WIDE) {
+    if (unit >= nunits * nblk) return;
+    blk = (uint32_t)(blk0 + unit / nunits);
+    unit = unit % nunits;
+  } else {
+    if (unit >= nunits) return;               // (no barriers in this kernel)
+  }
   int q = 0, cb = 0;
   {
     int before = 0;
@@ -147,9 +162,10 @@ __global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nu
   // 408 VALU instructions of a step, and the kernel is bound by VALU + MFMA issue)
   const int64_t nrows = r1 > r0 ? r1 - r0 : 0;
   const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.X + r0 * p.d), 0, (int)(nrows * p.d * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.codes + r0 * p.cs), 0, (int)(nrows * p.cs), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.codes + r0 * p.cs * (int)sizeof(Code)), 0,
+                                                                      (int)(nrows * p.cs * (int)sizeof(Code)), 0x00020000);
   const int xoff = ((8 * kg) * p.d + col0 + (colok ? i : 0)) * 4;
-  const int coff = (8 * kg) * p.cs + p.ccol + q;
+  const int coff = ((8 * kg) * p.cs + p.ccol + q) * (int)sizeof(Code);
   const uint32_t ones = i == 0 ? 0x3F803F80u : 0u;
   const cm_bf16x8 Bc = __builtin_bit_cast(cm_bf16x8, make_uint4(ones, ones, ones, ones));
   // raw operands of ONE pair of 32-row steps; a step re-loads its half for the next pair as soon as it has turned the values
@@ -162,7 +178,8 @@ __global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nu
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int L = L0 + u;                                         // wave-uniform
-      cr[s][u] = __builtin_amdgcn_raw_buffer_load_b8(rC, coff, L * p.cs, 0);
+      if constexpr (WIDE) cr[s][u] = __builtin_amdgcn_raw_buffer_load_b16(rC, coff, L * p.cs * 2, 0);
+      else cr[s][u] = __builtin_amdgcn_raw_buffer_load_b8(rC, coff, L * p.cs, 0);
       xr[s][u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rX, xoff, L * p.d * 4, 0));
     }
   };
@@ -179,8 +196,9 @@ __global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nu
         const int u = 2 * pp + e;
         const uint32_t c = cr[s][u];
         bool hit = (c & 15u) == (uint32_t)i;
+        if constexpr (WIDE) hit = hit && (c >> 8) == blk;
         if constexpr (TAIL) hit = hit && r + 32 * s + 8 * kg + u < r1;
-        k2[e] = hit ? (1u << (c >> 4)) : 0u;
+        k2[e] = hit ? (1u << (WIDE ? (c >> 4) & 15u : c >> 4)) : 0u;
       }
       K[pp] = k2[0] | (k2[1] << 16);
     }
@@ -241,7 +259,7 @@ __global__ __launch_bounds__(512) void centers_mfma_kernel(TrainParams p, int nu
   for (int t = 0; t < NT; ++t) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int code = 16 * t + 4 * kg + r;
+      const int code = (int)blk * 256 + 16 * t + 4 * kg + r;
       if (code < p.h) {                      // (the one-hot entries were 2.0: halve, exactly)
         if (colok) out[(size_t)code * p.d + col0 + i] = 0.5f * acc[t][r];
         if (cb == 0 && i == 0) oc[(size_t)q * p.h + code] = (unsigned int)(0.5f * cnt[t][r] + 0.5f);
@@ -310,6 +328,8 @@ __global__ void ervq_increment_finish_kernel(float *__restrict__ C, unsigned int
 // ---- reconstruction ----------------------------------------------------------------------------------
 // a per-dimension table (sub-quantizer | width, gather base) in LDS replaces the walk over the offsets per element; a
 // persistent grid walks the elements with a 32-bit (row, dimension) pair instead of a 64-bit division each
+// Code = int16_t (zero-based, read zero-extended): a code outside [0, h) is not looked up in C, its slice of the row is zeros
+template <class Code>
 __global__ __launch_bounds__(256) void reconstruct_kernel(TrainParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
   int *gbase = reinterpret_cast<int *>(rc_smem);                              // [d]  h * off[q] - off[q] + dim
@@ -330,8 +350,13 @@ __global__ __launch_bounds__(256) void reconstruct_kernel(TrainParams p) {
   int64_t r = e / p.d;
   int dim = (int)(e - r * p.d);
   for (; e < total; e += stride) {
-    const int code = p.codes[r * p.m + gq[dim]];
-    p.CB[e] = p.C[gbase[dim] + code * (int)gsub[dim]];
+    if constexpr (sizeof(Code) == 2) {
+      const int code = reinterpret_cast<const uint16_t *>(p.codes)[r * p.m + gq[dim]];
+      p.CB[e] = code < p.h ? p.C[gbase[dim] + code * (int)gsub[dim]] : 0.0f;
+    } else {
+      const int code = p.codes[r * p.m + gq[dim]];
+      p.CB[e] = p.C[gbase[dim] + code * (int)gsub[dim]];
+    }
     r += srow; dim += sdim;
     if (dim >= p.d) { dim -= p.d; ++r; }
   }
@@ -872,9 +897,9 @@ int update_centers_launch(float *C, unsigned int *counts, const float *X, const 
     for (int q = 0; q < m; ++q) nunits += (p.off[q + 1] - p.off[q] + 15) / 16;
     const int nslice = grid;
     const dim3 g3(nslice, (nunits + 7) / 8);
-    if (h <= 64) hipLaunchKernelGGL(centers_mfma_kernel<4>, g3, dim3(512), 0, stream, p, nunits);
-    else if (h <= 128) hipLaunchKernelGGL(centers_mfma_kernel<8>, g3, dim3(512), 0, stream, p, nunits);
-    else hipLaunchKernelGGL(centers_mfma_kernel<16>, g3, dim3(512), 0, stream, p, nunits);
+    if (h <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
+    else if (h <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
+    else hipLaunchKernelGGL((centers_mfma_kernel<16, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
     RQ_HIP(hipGetLastError());
     return centers_finish(p, grid, stream);
   }
@@ -885,6 +910,131 @@ int update_centers_launch(float *C, unsigned int *counts, const float *X, const 
     RQ_LAUNCH_LDS(centers_partial_kernel, dim3(grid), dim3(1024), lds, stream, p, dc0, dcw);
   }
   return centers_finish(p, grid, stream);
+}
+
+// update_centers over 16-bit codes: codes [n][m] int16 zero-based, read zero-extended; 1 <= h <=
+// RQ_MAX_H16, 1 <= m <= 32, any d >= m, any n.  One kernel, centers_mfma_kernel<NT, int16_t>: ceil(h / 256) code blocks times the
+// byte kernel's units, so the row slices that the byte launch needs to fill the device shrink in proportion:
+//   slices = ceil(num_cu / code blocks), at most one per 1024 rows,
+//            at least what keeps a slice below 2^23 rows (f32 counters) and 2^30 bytes of X (32-bit buffer offsets),
+//            at most what keeps the partials ((slices + 1) x (h d + m h) floats) inside CENTERS_H16_SCRATCH_BYTES;
+// a shape whose single slice does not fit is refused.  The reduction over the slices and the means are the byte path's
+// (partials_reduce_kernel, centers_finish_kernel): the same fixed order, C = s * (1.0f / (float)c), no float atomics.  A row
+// whose code lies outside [0, h) is ignored in that sub-space.
+constexpr size_t CENTERS_H16_SCRATCH_BYTES = (size_t)2 << 30;   // per device and stream, as the other wide paths
+int update_centers_h16_launch(float *C, unsigned int *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
+                              int num_cu, hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  if (m < 1 || m > 32 || h < 1 || h > RQ_MAX_H16)
+    return fail(RQ_EUNSUPPORTED, "update_centers over 16-bit codes covers m <= 32, h <= %d (got m=%d h=%d)", RQ_MAX_H16, m, h);
+  if (d < m) return fail(RQ_EINVAL, "update_centers: d=%d < m=%d", d, m);
+  TrainParams p{};
+  p.X = X; p.codes = reinterpret_cast<const uint8_t *>(codes); p.C = C; p.counts = counts; p.n = n; p.d = d; p.m = m; p.h = h;
+  p.cs = m; p.ccol = 0;
+  split_offsets(p.off, d, m);
+  const int nblocks = (h + 255) / 256;
+  const size_t stride = (size_t)h * d + (size_t)m * h;
+  const int64_t cap = std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4));       // rows of one slice
+  const int64_t most = (int64_t)(CENTERS_H16_SCRATCH_BYTES / 5 * 4 / (stride * sizeof(float))) - 1;   // (workspace() allocates 1.25x)
+  const int64_t least = cap > 0 ? (n + cap - 1) / cap : most + 1;
+  if (least > most || most > INT32_MAX)
+    return fail(RQ_EUNSUPPORTED, "update_centers over 16-bit codes: n=%lld d=%d h=%d needs more than %zu bytes of partial sums",
+                (long long)n, d, h, CENTERS_H16_SCRATCH_BYTES);
+  int64_t want = std::min<int64_t>((num_cu + nblocks - 1) / nblocks, (n + 1023) / 1024);
+  const int grid = (int)std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(want, 1), least), most);
+  void *part = nullptr;
+  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * stride * sizeof(float), &part, stream));
+  p.partial = (float *)part;
+  int nunits = 0;
+  for (int q = 0; q < m; ++q) nunits += (p.off[q + 1] - p.off[q] + 15) / 16;
+  // every (slice, code) pair of the partials is written: block b's units cover its codes below h for every dimension.
+  // The full blocks of 256 codes run with 16 tiles; a ragged last block with the tile count of its own codes.
+  const int last = h - 256 * (nblocks - 1), nfull = last == 256 ? nblocks : nblocks - 1;
+  if ((int64_t)nunits * nblocks > 8 * 65535ll) return fail(RQ_EUNSUPPORTED, "update_centers over 16-bit codes: d=%d h=%d", d, h);
+  if (nfull > 0)
+    hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), dim3(grid, (nunits * nfull + 7) / 8), dim3(512), 0, stream, p, nunits, 0, nfull);
+  if (nfull < nblocks) {
+    const dim3 g3(grid, (nunits + 7) / 8);
+    if (last <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+    else if (last <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+    else hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+  }
+  RQ_HIP(hipGetLastError());
+  return centers_finish(p, grid, stream);
+}
+
+// ---- refill of emptied centres on the device (Clustering.repick_unused_centers; the rule of repick_unused, rq_train_host.hip) ----
+// Costs in f64, one thread per row, the sub-space's terms in ascending order -- the host loop of repick_unused bit for bit.
+// The rows are P[row * d + col0 .. + sub); BY_CODE: tc[row] = |P_row - Cref[code(row)]|^2 (Cref [h][sub], code(row) =
+// codes[row * cstride + col] zero-extended); else tc[row] = min(tc[row], |P_row - Cref|^2) (Cref [sub]).
+template <bool BY_CODE, class Code>
+__global__ __launch_bounds__(256) void refill_cost_kernel(double *tc, const float *__restrict__ P, const float *__restrict__ Cref,
+                                                          const Code *__restrict__ codes, int cstride, int col, int64_t n, int d,
+                                                          int col0, int sub) {
+  using UCode = typename std::make_unsigned<Code>::type;
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  const float *x = P + row * d + col0;
+  const float *c = BY_CODE ? Cref + (size_t)(UCode)codes[row * cstride + col] * sub : Cref;
+  double a = 0;
+  for (int t = 0; t < sub; ++t) {
+    const double e = (double)x[t] - (double)c[t];
+    a += e * e;
+  }
+  if (BY_CODE) tc[row] = a;
+  else if (a < tc[row]) tc[row] = a;
+}
+
+// The `unused` entries of Csub [h][sub] are re-drawn from the rows of P (stride d, columns [col0, col0 + sub)) with probability
+// proportional to their cost under Cold (the entries the codes were assigned with); the drawn row's cost drops to zero and every
+// cost is lowered to the distance to the new entry before the next draw.  Only the n costs come to the host, once per draw.
+// dtc: n doubles of device scratch.  Draw rule and use of the stream are repick_unused's.
+template <class Code>
+int refill_unused_launch(float *Csub, const float *Cold, const float *P, const Code *codes, int cstride, int col, int64_t n, int d,
+                         int col0, int sub, const std::vector<int> &unused, Rng &rng, double *dtc, std::vector<double> &tc,
+                         hipStream_t stream) {
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  hipLaunchKernelGGL((refill_cost_kernel<true, Code>), grid, dim3(256), 0, stream, dtc, P, Cold, codes, cstride, col, n, d, col0, sub);
+  RQ_HIP(hipGetLastError());
+  tc.resize((size_t)n);
+  for (size_t q = 0; q < unused.size(); ++q) {
+    RQ_HIP(hipMemcpyAsync(tc.data(), dtc, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
+    RQ_HIP(hipStreamSynchronize(stream));
+    double total = 0;
+    for (int64_t r = 0; r < n; ++r) total += tc[r];
+    int64_t pick = (int64_t)(rng.next() % (uint64_t)n);          // all costs zero (fewer distinct rows than entries): uniform
+    if (total > 0) {
+      const double u = rng.uniform() * total;
+      double run = 0;
+      pick = n - 1;
+      for (int64_t r = 0; r < n; ++r) { run += tc[r]; if (run > u) { pick = r; break; } }
+    }
+    float *v = Csub + (size_t)unused[q] * sub;
+    RQ_HIP(hipMemcpyAsync(v, P + pick * d + col0, (size_t)sub * 4, hipMemcpyDeviceToDevice, stream));
+    if (q + 1 < unused.size()) {
+      // (the drawn row's own cost becomes |P_pick - v|^2 = 0 here, what the host form sets by hand)
+      hipLaunchKernelGGL((refill_cost_kernel<false, Code>), grid, dim3(256), 0, stream, dtc, P, v, codes, cstride, col, n, d, col0, sub);
+      RQ_HIP(hipGetLastError());
+    }
+  }
+  return RQ_OK;
+}
+template int refill_unused_launch(float *, const float *, const float *, const uint8_t *, int, int, int64_t, int, int, int,
+                                  const std::vector<int> &, Rng &, double *, std::vector<double> &, hipStream_t);
+template int refill_unused_launch(float *, const float *, const float *, const int16_t *, int, int, int64_t, int, int, int,
+                                  const std::vector<int> &, Rng &, double *, std::vector<double> &, hipStream_t);
+
+// rows[k] of X restricted to columns [col0, col0 + sub) -> Csub[k] (init_centers at h > 256: one launch instead of h copies)
+__global__ __launch_bounds__(256) void gather_rows_kernel(float *__restrict__ Csub, const float *__restrict__ X,
+                                                          const long long *__restrict__ rows, int h, int d, int col0, int sub) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= h * sub) return;
+  const int k = e / sub, s = e - k * sub;
+  Csub[e] = X[(size_t)rows[k] * d + col0 + s];
+}
+int gather_rows_launch(float *Csub, const float *X, const long long *rows_dev, int h, int d, int col0, int sub, hipStream_t stream) {
+  RQ_LAUNCH(gather_rows_kernel, dim3((uint32_t)((h * sub + 255) / 256)), dim3(256), 0, stream, Csub, X, rows_dev, h, d, col0, sub);
+  return RQ_OK;
 }
 
 // Codebook increment of ERVQ: Cj [h][d] += the per-entry mean of E [n][d] over the rows with codes[row * cstride + col] == entry
@@ -911,9 +1061,9 @@ int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const
   p.partial = (float *)part;
   const int nunits = (d + 15) / 16;
   const dim3 g3(grid, (nunits + 7) / 8);
-  if (h <= 64) hipLaunchKernelGGL(centers_mfma_kernel<4>, g3, dim3(512), 0, stream, p, nunits);
-  else if (h <= 128) hipLaunchKernelGGL(centers_mfma_kernel<8>, g3, dim3(512), 0, stream, p, nunits);
-  else hipLaunchKernelGGL(centers_mfma_kernel<16>, g3, dim3(512), 0, stream, p, nunits);
+  if (h <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
+  else if (h <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
+  else hipLaunchKernelGGL((centers_mfma_kernel<16, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
   RQ_HIP(hipGetLastError());
   float *red = p.partial + (size_t)grid * stride;
   RQ_TRY(partials_reduce<float>(red, p.partial, stride, grid, h * d, stream));
@@ -934,7 +1084,24 @@ int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t 
   const int64_t total = n * d;
   if (d > 8192) return fail(RQ_EUNSUPPORTED, "reconstruct: d=%d", d);
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(reconstruct_kernel, dim3(grid), dim3(256), (size_t)d * 8, stream, p);
+  hipLaunchKernelGGL(reconstruct_kernel<uint8_t>, dim3(grid), dim3(256), (size_t)d * 8, stream, p);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
+// CB[j][off_i + s] = C_i[codes[j][i]][s] from int16 codes (zero-based, read zero-extended), 1 <= h <= RQ_MAX_H16: a pure copy.
+// A code outside [0, h) is not read from C: that sub-space of the row is written as zeros.
+int reconstruct_h16_launch(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  if (m < 1 || m > 32 || h < 1 || h > RQ_MAX_H16)
+    return fail(RQ_EUNSUPPORTED, "reconstruct over 16-bit codes covers m <= 32, h <= %d (got m=%d h=%d)", RQ_MAX_H16, m, h);
+  if (d < m) return fail(RQ_EINVAL, "reconstruct: d=%d < m=%d", d, m);
+  if (d > 8192 || (int64_t)h * d >= (1ll << 31)) return fail(RQ_EUNSUPPORTED, "reconstruct: d=%d h=%d", d, h);
+  TrainParams p{};
+  p.codes = reinterpret_cast<const uint8_t *>(codes); p.C = const_cast<float *>(C); p.CB = CB; p.n = n; p.d = d; p.m = m; p.h = h;
+  split_offsets(p.off, d, m);
+  const unsigned grid = (unsigned)std::min<int64_t>((n * d + 255) / 256, 256 * 32);
+  hipLaunchKernelGGL(reconstruct_kernel<int16_t>, dim3(grid), dim3(256), (size_t)d * 8, stream, p);
   RQ_HIP(hipGetLastError());
   return RQ_OK;
 }

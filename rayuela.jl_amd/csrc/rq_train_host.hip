@@ -8,9 +8,12 @@
 // reference's kmeans(..., init=:kmpp); train_opq samples h rows like src/OPQ.jl:82.  Randomness (the uniforms of
 // kmeans++, sampled rows, re-seeding of empty clusters, init == random) comes from a splitmix64 stream seeded by
 // the caller -- the reference draws from Julia's global RNG, so runs are comparable statistically, not bit for bit.
+// The loops are templates over the code type: bytes for h <= 256 (rq_train_pq / _opq / _rvq), int16 above (the *_wide entry
+// points).  CodeOps<Code> holds what differs.
 #include <math.h>
 #include <string.h>
 
+#include <unordered_map>
 #include <vector>
 
 #include "rq_internal.h"
@@ -21,15 +24,12 @@ namespace rq {
 // sparse map when n is large
 static void sample_distinct(Rng &rng, int64_t n, int h, std::vector<int64_t> &out) {
   out.clear();
-  std::vector<std::pair<int64_t, int64_t>> swaps;  // position -> value for touched positions
+  std::unordered_map<int64_t, int64_t> swaps;  // position -> value for touched positions (a list searched linearly was O(h^2))
   auto get = [&](int64_t pos) {
-    for (auto &p : swaps) if (p.first == pos) return p.second;
-    return pos;
+    const auto it = swaps.find(pos);
+    return it == swaps.end() ? pos : it->second;
   };
-  auto set = [&](int64_t pos, int64_t val) {
-    for (auto &p : swaps) if (p.first == pos) { p.second = val; return; }
-    swaps.push_back({pos, val});
-  };
+  auto set = [&](int64_t pos, int64_t val) { swaps[pos] = val; };
   for (int i = 0; i < h; ++i) {
     const int64_t j = i + (int64_t)(rng.next() % (uint64_t)(n - i));
     const int64_t vi = get(i), vj = get(j);
@@ -169,12 +169,22 @@ struct SideStream {
   }
 };
 
-// initial centres: C_i = h sampled rows of (rotated) X restricted to subspace i
+// initial centres: C_i = h sampled rows of (rotated) X restricted to subspace i.  h > 256: the row list goes up and one small
+// kernel gathers the sub-space (h * m copies of `sub` floats are 32 768 calls at h = 4096, m = 8).
 static int init_centers(float *dC, const float *dX, int64_t n, int d, int m, int h, const int *off, Rng &rng) {
   std::vector<int64_t> idx;
+  DevMem drows;
+  if (h > 256) RQ_TRY(drows.alloc((size_t)h * 8));
   for (int i = 0; i < m; ++i) {
     sample_distinct(rng, n, h, idx);
     const int sub = off[i + 1] - off[i];
+    if (h > 256) {
+      static_assert(sizeof(long long) == sizeof(int64_t), "row ids are uploaded as they are");
+      RQ_HIP(hipMemcpy(drows.p, idx.data(), (size_t)h * 8, hipMemcpyHostToDevice));
+      RQ_TRY(gather_rows_launch(dC + (size_t)h * off[i], dX, drows.as<long long>(), h, d, off[i], sub, nullptr));
+      RQ_HIP(hipStreamSynchronize(nullptr));      // the next sub-space overwrites the row list
+      continue;
+    }
     for (int k = 0; k < h; ++k)
       RQ_HIP(hipMemcpy(dC + (size_t)h * off[i] + (size_t)k * sub, dX + idx[k] * d + off[i], sizeof(float) * sub,
                        hipMemcpyDeviceToDevice));
@@ -253,16 +263,89 @@ static int repick_unused(float *dCsub, const float *dCassigned, const float *dX,
   return RQ_OK;
 }
 
+// What the training loops below take from the width of a code: the byte kernels at h <= 256, their 16-bit forms above (DESIGN.md
+// section 4.19).  One loop, instantiated twice; the byte instantiation launches what the loops launched before there was a second.
+struct RefillScratch {      // device refill: n doubles on the device and their host copy, made by the first refill of a call
+  DevMem dtc;
+  std::vector<double> tc;
+};
+template <class Code> struct CodeOps;
+template <> struct CodeOps<uint8_t> {
+  static int encode(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu, hipStream_t s) {
+    return encode_launch(codes, X, C, n, d, m, h, num_cu, s);
+  }
+  static int update(float *C, unsigned int *counts, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, int num_cu,
+                    hipStream_t s) {
+    return update_centers_launch(C, counts, X, codes, n, d, m, h, num_cu, s);
+  }
+  static int reconstruct(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t s) {
+    return reconstruct_launch(CB, codes, C, n, d, m, h, s);
+  }
+  // emptied centres are rare at h <= 256: the host form
+  static int refill(float *dCsub, const float *dCassigned, const float *dX, int64_t n, int d, int col0, int sub, const uint8_t *codes,
+                    int cstride, int ci, int h, const std::vector<int> &unused, Rng &rng, RefillScratch &) {
+    return repick_unused(dCsub, dCassigned, dX, n, d, col0, sub, codes, cstride, ci, h, unused, rng);
+  }
+  // the (codes, C) forms of gram / qerror exist for bytes only
+  static bool fused(int d, int m, int h, bool for_gram) { return codes_forms_ok(d, m, h, for_gram); }
+  static int qerror_codes(double *acc, const float *X, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                          hipStream_t s) {
+    return qerror_codes_launch(acc, X, codes, C, n, d, m, h, num_cu, s);
+  }
+  static int gram_codes(float *G, const float *X, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                        hipStream_t s) {
+    return gram_codes_launch(G, X, codes, C, n, d, m, h, num_cu, s);
+  }
+  // the call's codes as int16 + base: widened into d16 (allocated by the caller)
+  static int to_i16(int16_t **out, DevMem &d16, uint8_t *codes, int64_t nelem, int base, hipStream_t s) {
+    *out = d16.as<int16_t>();
+    return convert_codes_launch(*out, (const uint8_t *)codes, nelem, base, s);
+  }
+};
+template <> struct CodeOps<int16_t> {
+  static int encode(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu, hipStream_t s) {
+    return encode_h16_launch(codes, X, C, n, d, m, h, num_cu, s);
+  }
+  static int update(float *C, unsigned int *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, int num_cu,
+                    hipStream_t s) {
+    return update_centers_h16_launch(C, counts, X, codes, n, d, m, h, num_cu, s);
+  }
+  static int reconstruct(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t s) {
+    return reconstruct_h16_launch(CB, codes, C, n, d, m, h, s);
+  }
+  // emptied centres are routine at h in the thousands: costs on the device, the n costs come down per draw (same rule, same draws)
+  static int refill(float *dCsub, const float *dCassigned, const float *dX, int64_t n, int d, int col0, int sub, const int16_t *codes,
+                    int cstride, int ci, int h, const std::vector<int> &unused, Rng &rng, RefillScratch &rs) {
+    if (!rs.dtc.p) RQ_TRY(rs.dtc.alloc((size_t)n * 8));
+    return refill_unused_launch<int16_t>(dCsub, dCassigned, dX, codes, cstride, ci, n, d, col0, sub, unused, rng,
+                                         rs.dtc.as<double>(), rs.tc, nullptr);
+  }
+  static bool fused(int, int, int, bool) { return false; }
+  static int qerror_codes(double *, const float *, const int16_t *, const float *, int64_t, int, int, int, int, hipStream_t) {
+    return fail(RQ_EUNSUPPORTED, "qerror over (codes, C) covers byte codes");
+  }
+  static int gram_codes(float *, const float *, const int16_t *, const float *, int64_t, int, int, int, int, hipStream_t) {
+    return fail(RQ_EUNSUPPORTED, "gram over (codes, C) covers byte codes");
+  }
+  static int to_i16(int16_t **out, DevMem &, int16_t *codes, int64_t nelem, int base, hipStream_t s) {   // in place
+    *out = codes;
+    return add_base_codes_launch(codes, nelem, base, s);
+  }
+};
+
 // The Lloyd loop of train_pq (src/PQ.jl:68-99) on a device-resident X [n][d]: kmeans++ seeding, niter iterations, then the
 // assignments of the final centres.  dC [h * d] and dcodes [n][m] (device) receive them.  rq_train_pq is this loop between an
 // upload and a download; rq_get_norms_codebook runs it with d = m = 1 on norms that never leave the device.
-static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed,
+template <class Code>
+static int train_pq_loop(float *dC, Code *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed,
                          const DeviceInfo &di, TrainProf &prof) {
+  using Ops = CodeOps<Code>;
   int off[33];
   split_offsets(off, d, m);
   Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
+  RefillScratch rs;
   DevMem dprev;
-  RQ_TRY(dprev.alloc((size_t)n * m));
+  RQ_TRY(dprev.alloc((size_t)n * m * sizeof(Code)));
   RQ_PH(TP_INIT, RQ_TRY(seed_centers(dC, dX, n, d, m, h, off, rng)));
   std::vector<unsigned int> counts((size_t)m * h);
   // Convergence.  Clustering.kmeans (v0.12.2 `_kmeans!`) stops when |objv - prev_objv| < tol, tol = 1e-6 ABSOLUTE on
@@ -286,16 +369,18 @@ static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n,
   unsigned int *dcnt_p = dcc.as<unsigned int>();
   unsigned long long *dchg_p = reinterpret_cast<unsigned long long *>(dcc.as<unsigned char>() + chg_at);
   std::vector<unsigned char> back(chg_at + 8);
-  uint8_t *cur = dcodes, *prev = dprev.as<uint8_t>();
+  Code *cur = dcodes, *prev = dprev.as<Code>();
   int iters_done = 0;
   prof.loop_begin();
   for (int it = 0; it < niter; ++it) {
-    RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(cur, dX, dC, n, d, m, h, di.num_cu, nullptr)));
+    RQ_PH(TP_ENCODE, RQ_TRY(Ops::encode(cur, dX, dC, n, d, m, h, di.num_cu, nullptr)));
     prof.start();
-    if (it > 0) RQ_TRY(codes_changed_launch(dchg_p, cur, prev, (size_t)n * m, nullptr));
+    if (it > 0)
+      RQ_TRY(codes_changed_launch(dchg_p, reinterpret_cast<const uint8_t *>(cur), reinterpret_cast<const uint8_t *>(prev),
+                                  (size_t)n * m * sizeof(Code), nullptr));
     prof.stop(TP_CONVERGE);
     RQ_HIP(hipMemcpyAsync(dCold.p, dC, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
-    RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch(dC, dcnt_p, dX, cur, n, d, m, h, di.num_cu, nullptr)));
+    RQ_PH(TP_CENTERS, RQ_TRY(Ops::update(dC, dcnt_p, dX, cur, n, d, m, h, di.num_cu, nullptr)));
     prof.start();
     RQ_HIP(hipMemcpy(back.data(), dcc.p, chg_at + 8, hipMemcpyDeviceToHost));
     unsigned long long changed = 1;
@@ -309,13 +394,13 @@ static int train_pq_loop(float *dC, uint8_t *dcodes, const float *dX, int64_t n,
       for (int k = 0; k < h; ++k)
         if (counts[(size_t)i * h + k] == 0) unused.push_back(k);
       if (!unused.empty())
-        RQ_TRY(repick_unused(dC + (size_t)h * off[i], dCold.as<float>() + (size_t)h * off[i], dX, n, d,
-                             off[i], off[i + 1] - off[i], cur, m, i, h, unused, rng));
+        RQ_TRY(Ops::refill(dC + (size_t)h * off[i], dCold.as<float>() + (size_t)h * off[i], dX, n, d,
+                           off[i], off[i + 1] - off[i], cur, m, i, h, unused, rng, rs));
     }
     std::swap(cur, prev);
   }
   prof.loop_end(iters_done);      // the final encode overwrites every code: which of the two buffers the loop ended on is moot
-  RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(dcodes, dX, dC, n, d, m, h, di.num_cu, nullptr)));
+  RQ_PH(TP_ENCODE, RQ_TRY(Ops::encode(dcodes, dX, dC, n, d, m, h, di.num_cu, nullptr)));
   return RQ_OK;
 }
 
@@ -327,57 +412,37 @@ int train_pq_resident(float *dC, uint8_t *dcodes, const float *dX, int64_t n, in
   return train_pq_loop(dC, dcodes, dX, n, d, m, h, niter, seed, di, prof);
 }
 
-}  // namespace rq
-
-using namespace rq;
-
-extern "C" {
-
-int rq_kmpp_seeds(int64_t *seeds, float *C, const float *X, int64_t n, int d, int m, int h, uint64_t seed) {
-  RQ_TRY(check_train(n, d, m, h, 0));
-  if (!seeds && !C) return fail(RQ_EINVAL, "rq_kmpp_seeds: nothing to return");
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  int off[33];
-  split_offsets(off, d, m);
-  Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
-  DevMem dX, dC;
-  RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dC.alloc((size_t)h * d * 4));
-  RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
-  std::vector<long long> sd((size_t)m * h);
-  RQ_TRY(seed_centers(dC.as<float>(), dX.as<float>(), n, d, m, h, off, rng, sd.data()));
-  if (seeds) for (size_t i = 0; i < sd.size(); ++i) seeds[i] = (int64_t)sd[i];
-  if (C) RQ_HIP(hipMemcpy(C, dC.p, (size_t)h * d * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
-}
-
-int rq_train_pq(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
-                uint64_t seed) {
-  RQ_TRY(check_train(n, d, m, h, niter));
+// train_pq (src/PQ.jl:68-99) on host pointers: upload, the Lloyd loop, qerror_pq of the result, download.  The arguments are
+// checked by the entry points; codes come back as int16 + code_base.
+template <class Code>
+static int train_pq_host(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                         uint64_t seed, int code_base) {
+  using Ops = CodeOps<Code>;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
   DevMem dX, dC, dcodes, dCB, dacc, d16;
-  RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dC.alloc((size_t)h * d * 4)); RQ_TRY(dcodes.alloc((size_t)n * m));
-  RQ_TRY(dacc.alloc(8)); RQ_TRY(d16.alloc((size_t)n * m * 2));
+  RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dC.alloc((size_t)h * d * 4)); RQ_TRY(dcodes.alloc((size_t)n * m * sizeof(Code)));
+  RQ_TRY(dacc.alloc(8));
+  if (sizeof(Code) == 1) RQ_TRY(d16.alloc((size_t)n * m * 2));
   TrainProf prof;
   RQ_PH(TP_H2D, RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice)));
-  RQ_TRY(train_pq_loop(dC.as<float>(), dcodes.as<uint8_t>(), dX.as<float>(), n, d, m, h, niter, seed, di, prof));
-  if (codes_forms_ok(d, m, h, false)) {
-    RQ_PH(TP_QERROR, RQ_TRY(qerror_codes_launch(dacc.as<double>(), dX.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
+  RQ_TRY(train_pq_loop<Code>(dC.as<float>(), dcodes.as<Code>(), dX.as<float>(), n, d, m, h, niter, seed, di, prof));
+  if (Ops::fused(d, m, h, false)) {
+    RQ_PH(TP_QERROR, RQ_TRY(Ops::qerror_codes(dacc.as<double>(), dX.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
   } else {
     RQ_TRY(dCB.alloc((size_t)n * d * 4));
-    RQ_PH(TP_RECONSTRUCT, RQ_TRY(reconstruct_launch(dCB.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, nullptr)));
+    RQ_PH(TP_RECONSTRUCT, RQ_TRY(Ops::reconstruct(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr)));
     RQ_PH(TP_QERROR, RQ_TRY(qerror_launch(dacc.as<double>(), dX.as<float>(), dCB.as<float>(), n, d, di.num_cu, nullptr)));
   }
-  RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), n * m, nullptr));
+  int16_t *out16 = nullptr;
+  RQ_TRY(Ops::to_i16(&out16, d16, dcodes.as<Code>(), n * m, code_base, nullptr));
   double acc = 0;
   RQ_HIP(hipMemcpy(&acc, dacc.p, 8, hipMemcpyDeviceToHost));
   if (error) *error = acc / (double)n;
   prof.start();
   RQ_HIP(hipMemcpy(C, dC.p, (size_t)h * d * 4, hipMemcpyDeviceToHost));
-  RQ_HIP(hipMemcpy(B1, d16.p, (size_t)n * m * 2, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(B1, out16, (size_t)n * m * 2, hipMemcpyDeviceToHost));
   prof.stop(TP_D2H);
   return RQ_OK;
 }
@@ -386,11 +451,11 @@ int rq_train_pq(float *C, int16_t *B1, double *error, const float *X, int64_t n,
 // kmeans++ seeding and Julia's RNG there; kmeans++ on the residual rows here too -- seed_centers, h uniforms of the
 // library's seeded stream per stage, one stream for all stages and their repicks),
 // then Xr .-= C[i][:, B[:, i]] (:112).  C [m][h][d]; B1 [n][m] Int16 one-based; error = qerror(X, B, C) (:124).
-int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
-                 uint64_t seed) {
-  if (n < 1 || d < 1 || m < 1 || m > 64 || h < 1 || h > 256 || niter < 0)
-    return fail(RQ_EINVAL, "train_rvq: n=%lld d=%d m=%d h=%d niter=%d", (long long)n, d, m, h, niter);
-  if (n < h) return fail(RQ_EINVAL, "train_rvq: fewer training vectors (%lld) than codebook entries (%d)", (long long)n, h);
+// The arguments are checked by the entry points; codes come back as int16 + code_base.
+template <class Code>
+static int train_rvq_host(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                          uint64_t seed, int code_base) {
+  using Ops = CodeOps<Code>;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
@@ -398,49 +463,52 @@ int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n
   Rng rng{seed * 0x9E3779B97F4A7C15ull + 3};
   DevMem dXr, dCi, dCold, dstage, dcnt, dcodes, dacc, d16;
   RQ_TRY(dXr.alloc((size_t)n * d * 4)); RQ_TRY(dCi.alloc((size_t)h * d * 4)); RQ_TRY(dCold.alloc((size_t)h * d * 4));
-  RQ_TRY(dstage.alloc((size_t)n));
-  RQ_TRY(dcnt.alloc((size_t)h * 4)); RQ_TRY(dcodes.alloc((size_t)n * m)); RQ_TRY(dacc.alloc(8));
-  RQ_TRY(d16.alloc((size_t)n * m * 2));
+  RQ_TRY(dstage.alloc((size_t)n * sizeof(Code)));
+  RQ_TRY(dcnt.alloc((size_t)h * 4)); RQ_TRY(dcodes.alloc((size_t)n * m * sizeof(Code))); RQ_TRY(dacc.alloc(8));
+  if (sizeof(Code) == 1) RQ_TRY(d16.alloc((size_t)n * m * 2));
   RQ_HIP(hipMemcpy(dXr.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
   std::vector<unsigned int> counts((size_t)h);
-  std::vector<uint8_t> cur((size_t)n), prev;
+  std::vector<Code> cur((size_t)n), prev;
+  RefillScratch rs;
   for (int i = 0; i < m; ++i) {
     RQ_TRY(seed_centers(dCi.as<float>(), dXr.as<float>(), n, d, 1, h, off1, rng));
     prev.clear();
     for (int it = 0; it < niter; ++it) {
-      RQ_TRY(encode_launch(dstage.as<uint8_t>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
-      RQ_HIP(hipMemcpy(cur.data(), dstage.p, (size_t)n, hipMemcpyDeviceToHost));
+      RQ_TRY(Ops::encode(dstage.as<Code>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
+      RQ_HIP(hipMemcpy(cur.data(), dstage.p, (size_t)n * sizeof(Code), hipMemcpyDeviceToHost));
       if (!prev.empty() && prev == cur) break;   // assignments stable: Lloyd has converged
       prev = cur;
       RQ_HIP(hipMemcpyAsync(dCold.p, dCi.p, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
-      RQ_TRY(update_centers_launch(dCi.as<float>(), dcnt.as<unsigned int>(), dXr.as<float>(), dstage.as<uint8_t>(), n,
-                                   d, 1, h, di.num_cu, nullptr));
+      RQ_TRY(Ops::update(dCi.as<float>(), dcnt.as<unsigned int>(), dXr.as<float>(), dstage.as<Code>(), n, d, 1, h, di.num_cu,
+                         nullptr));
       RQ_HIP(hipMemcpy(counts.data(), dcnt.p, (size_t)h * 4, hipMemcpyDeviceToHost));
       std::vector<int> unused;                   // centres that lost all their points: re-drawn like Clustering.kmeans does
       for (int k = 0; k < h; ++k)
         if (counts[k] == 0) unused.push_back(k);
       if (!unused.empty())
-        RQ_TRY(repick_unused(dCi.as<float>(), dCold.as<float>(), dXr.as<float>(), n, d, 0, d, dstage.as<uint8_t>(), 1, 0, h, unused, rng));
+        RQ_TRY(Ops::refill(dCi.as<float>(), dCold.as<float>(), dXr.as<float>(), n, d, 0, d, dstage.as<Code>(), 1, 0, h, unused, rng, rs));
     }
     // the assignments of the final centres (what quantize_rvq would return for this stage), then the residual
-    RQ_TRY(encode_launch(dstage.as<uint8_t>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
-    RQ_TRY(rvq_residual_launch(dXr.as<float>(), dCi.as<float>(), dstage.as<uint8_t>(), dcodes.as<uint8_t>(), nullptr, n,
-                               d, m, i, nullptr));
+    RQ_TRY(Ops::encode(dstage.as<Code>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
+    RQ_TRY(residual_launch<Code>(dXr.as<float>(), dXr.as<float>(), dCi.as<float>(), dstage.as<Code>(), 1, dcodes.as<Code>(), nullptr,
+                                 n, d, m, i, nullptr));
     RQ_HIP(hipMemcpy(C + (size_t)i * h * d, dCi.p, (size_t)h * d * 4, hipMemcpyDeviceToHost));
   }
   RQ_TRY(qerror_launch(dacc.as<double>(), dXr.as<float>(), nullptr, n, d, di.num_cu, nullptr));
-  RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), n * m, nullptr));
+  int16_t *out16 = nullptr;
+  RQ_TRY(Ops::to_i16(&out16, d16, dcodes.as<Code>(), n * m, code_base, nullptr));
   double acc = 0;
   RQ_HIP(hipMemcpy(&acc, dacc.p, 8, hipMemcpyDeviceToHost));
   if (error) *error = acc / (double)n;
-  RQ_HIP(hipMemcpy(B1, d16.p, (size_t)n * m * 2, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(B1, out16, (size_t)n * m * 2, hipMemcpyDeviceToHost));
   return RQ_OK;
 }
 
-int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, int64_t n, int d, int m, int h,
-                 int niter, int init, uint64_t seed, const float *R0, const float *C0) {
-  RQ_TRY(check_train(n, d, m, h, niter));
-  if (init != 0 && init != 1) return fail(RQ_EINVAL, "train_opq: init must be 0 (natural) or 1 (random)");
+// train_opq (src/OPQ.jl:49-139); the arguments are checked by the entry points; codes come back as int16 + code_base.
+template <class Code>
+static int train_opq_host(float *C, int16_t *B1, float *R, float *obj, const float *X, int64_t n, int d, int m, int h,
+                          int niter, int init, uint64_t seed, const float *R0, const float *C0, int code_base) {
+  using Ops = CodeOps<Code>;
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
@@ -461,12 +529,13 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
   }
   DevMem dX, dRX, dR, dC, dcodes, dcnt, dCB, dacc, dG, d16;
   RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dRX.alloc((size_t)n * d * 4)); RQ_TRY(dR.alloc((size_t)d * d * 4));
-  RQ_TRY(dC.alloc((size_t)h * d * 4)); RQ_TRY(dcodes.alloc((size_t)n * m)); RQ_TRY(dcnt.alloc((size_t)m * h * 4));
-  // CB = reconstruct(codes, C) is only materialised for shapes the (codes, C) forms of gram / qerror do not cover
-  const bool fused_cb = codes_forms_ok(d, m, h, true);
+  RQ_TRY(dC.alloc((size_t)h * d * 4)); RQ_TRY(dcodes.alloc((size_t)n * m * sizeof(Code))); RQ_TRY(dcnt.alloc((size_t)m * h * 4));
+  // CB = reconstruct(codes, C) is only materialised for shapes the (codes, C) forms of gram / qerror do not cover (16-bit codes:
+  // every shape)
+  const bool fused_cb = Ops::fused(d, m, h, true);
   if (!fused_cb) RQ_TRY(dCB.alloc((size_t)n * d * 4));
   RQ_TRY(dacc.alloc(8)); RQ_TRY(dG.alloc((size_t)d * d * 4));
-  RQ_TRY(d16.alloc((size_t)n * m * 2));
+  if (sizeof(Code) == 1) RQ_TRY(d16.alloc((size_t)n * m * 2));
   TrainProf prof;
   RQ_PH(TP_H2D, RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice)));
   prof.start();
@@ -474,8 +543,8 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
   RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX.as<float>(), d, n, di.num_cu, nullptr));
   if (C0) RQ_HIP(hipMemcpy(dC.p, C0, (size_t)h * d * 4, hipMemcpyHostToDevice));
   else RQ_TRY(init_centers(dC.as<float>(), dRX.as<float>(), n, d, m, h, off, rng));
-  RQ_TRY(encode_launch(dcodes.as<uint8_t>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
-  if (!fused_cb) RQ_TRY(reconstruct_launch(dCB.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, nullptr));
+  RQ_TRY(Ops::encode(dcodes.as<Code>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  if (!fused_cb) RQ_TRY(Ops::reconstruct(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr));
   prof.stop(TP_INIT);
   std::vector<float> Gf((size_t)d * d);
   std::vector<double> Vwarm;   // empty on the first iteration: cold start
@@ -503,13 +572,13 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
     prof.start();
     RQ_HIP(hipEventRecord(side.ready, nullptr));
     RQ_HIP(hipStreamWaitEvent(side.s, side.ready, 0));
-    if (fused_cb) RQ_TRY(qerror_codes_launch(dobj.as<double>() + it, dRX.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, di.num_cu, side.s));
+    if (fused_cb) RQ_TRY(Ops::qerror_codes(dobj.as<double>() + it, dRX.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, di.num_cu, side.s));
     else RQ_TRY(qerror_launch(dobj.as<double>() + it, dRX.as<float>(), dCB.as<float>(), n, d, di.num_cu, side.s));
     RQ_HIP(hipEventRecord(side.done, side.s));
     prof.stop(TP_QERROR);
     // update R (src/OPQ.jl:112-113): G = X CB' and its polar factor U V' on the device
     prof.start();
-    if (fused_cb) RQ_TRY(gram_codes_launch(dG.as<float>(), dX.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+    if (fused_cb) RQ_TRY(Ops::gram_codes(dG.as<float>(), dX.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
     else RQ_TRY(gram_launch(dG.as<float>(), dX.as<float>(), dCB.as<float>(), n, d, di.num_cu, nullptr));
     prof.stop(TP_GRAM);
     prof.start();
@@ -549,10 +618,10 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
     prof.stop(TP_SVD);
     RQ_HIP(hipStreamWaitEvent(nullptr, side.done, 0));      // the objective has read RX, C (and CB)
     RQ_PH(TP_ROTATE, RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX.as<float>(), d, n, di.num_cu, nullptr)));
-    RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch(dC.as<float>(), dcnt.as<unsigned int>(), dRX.as<float>(), dcodes.as<uint8_t>(), n, d,
+    RQ_PH(TP_CENTERS, RQ_TRY(Ops::update(dC.as<float>(), dcnt.as<unsigned int>(), dRX.as<float>(), dcodes.as<Code>(), n, d,
                                  m, h, di.num_cu, nullptr)));
-    RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(dcodes.as<uint8_t>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
-    if (!fused_cb) RQ_PH(TP_RECONSTRUCT, RQ_TRY(reconstruct_launch(dCB.as<float>(), dcodes.as<uint8_t>(), dC.as<float>(), n, d, m, h, nullptr)));
+    RQ_PH(TP_ENCODE, RQ_TRY(Ops::encode(dcodes.as<Code>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
+    if (!fused_cb) RQ_PH(TP_RECONSTRUCT, RQ_TRY(Ops::reconstruct(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr)));
   }
   prof.loop_end(niter + 1);
   {
@@ -561,16 +630,105 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
     RQ_HIP(hipMemcpy(accs.data(), dobj.p, accs.size() * 8, hipMemcpyDeviceToHost));
     if (obj) for (int it = 0; it <= niter; ++it) obj[it] = (float)(accs[it] / (double)n);
   }
-  RQ_TRY(widen_codes_launch(d16.as<int16_t>(), dcodes.as<uint8_t>(), n * m, nullptr));
+  int16_t *out16 = nullptr;
+  RQ_TRY(Ops::to_i16(&out16, d16, dcodes.as<Code>(), n * m, code_base, nullptr));
   RQ_HIP(hipDeviceSynchronize());
   prof.start();
   RQ_HIP(hipMemcpy(C, dC.p, (size_t)h * d * 4, hipMemcpyDeviceToHost));
-  RQ_HIP(hipMemcpy(B1, d16.p, (size_t)n * m * 2, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(B1, out16, (size_t)n * m * 2, hipMemcpyDeviceToHost));
   RQ_HIP(hipMemcpy(R, dR.p, sizeof(float) * d * d, hipMemcpyDeviceToHost));     // (the device copy is the current R on both paths)
   prof.stop(TP_D2H);
   return RQ_OK;
 }
 
+static int check_train_rvq(int64_t n, int d, int m, int h, int niter) {
+  if (n < 1 || d < 1 || m < 1 || m > 64 || h < 1 || h > 256 || niter < 0)
+    return fail(RQ_EINVAL, "train_rvq: n=%lld d=%d m=%d h=%d niter=%d", (long long)n, d, m, h, niter);
+  if (n < h) return fail(RQ_EINVAL, "train_rvq: fewer training vectors (%lld) than codebook entries (%d)", (long long)n, h);
+  return RQ_OK;
+}
+
+// every argument check of the *_wide training entry points, before any work: NULL pointers, code_base, d < m, n < h, niter < 0:
+// RQ_EINVAL; h outside [1, RQ_MAX_H16] or m outside [1, mmax]: RQ_EUNSUPPORTED
+static int check_train_wide(const char *who, bool null_arg, int64_t n, int d, int m, int h, int niter, int mmax, bool pq, int code_base) {
+  if (null_arg) return fail(RQ_EINVAL, "%s: NULL argument", who);
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  if (m < 1 || m > mmax) return fail(RQ_EUNSUPPORTED, "%s covers 1 <= m <= %d; got m=%d", who, mmax, m);
+  if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "%s emits Int16 codes: 1 <= h <= %d; got h=%d", who, RQ_MAX_H16, h);
+  if (d < 1 || (pq && d < m)) return fail(RQ_EINVAL, "%s: d=%d < m=%d", who, d, m);
+  if (niter < 0) return fail(RQ_EINVAL, "%s: niter=%d", who, niter);
+  if (n < h) return fail(RQ_EINVAL, "%s: fewer training vectors (%lld) than codebook entries (%d)", who, (long long)n, h);
+  return RQ_OK;
+}
+
+}  // namespace rq
+
+using namespace rq;
+
+extern "C" {
+
+int rq_kmpp_seeds(int64_t *seeds, float *C, const float *X, int64_t n, int d, int m, int h, uint64_t seed) {
+  RQ_TRY(check_train(n, d, m, h, 0));
+  if (!seeds && !C) return fail(RQ_EINVAL, "rq_kmpp_seeds: nothing to return");
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  int off[33];
+  split_offsets(off, d, m);
+  Rng rng{seed * 0x9E3779B97F4A7C15ull + 1};
+  DevMem dX, dC;
+  RQ_TRY(dX.alloc((size_t)n * d * 4)); RQ_TRY(dC.alloc((size_t)h * d * 4));
+  RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
+  std::vector<long long> sd((size_t)m * h);
+  RQ_TRY(seed_centers(dC.as<float>(), dX.as<float>(), n, d, m, h, off, rng, sd.data()));
+  if (seeds) for (size_t i = 0; i < sd.size(); ++i) seeds[i] = (int64_t)sd[i];
+  if (C) RQ_HIP(hipMemcpy(C, dC.p, (size_t)h * d * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+int rq_train_pq(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                uint64_t seed) {
+  RQ_TRY(check_train(n, d, m, h, niter));
+  return train_pq_host<uint8_t>(C, B1, error, X, n, d, m, h, niter, seed, 1);
+}
+
+// train_rvq (src/RVQ.jl:86-127): C [m][h][d]; B1 [n][m] Int16 one-based; error = qerror(X, B, C) (:124).
+int rq_train_rvq(float *C, int16_t *B1, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                 uint64_t seed) {
+  RQ_TRY(check_train_rvq(n, d, m, h, niter));
+  return train_rvq_host<uint8_t>(C, B1, error, X, n, d, m, h, niter, seed, 1);
+}
+
+int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, int64_t n, int d, int m, int h,
+                 int niter, int init, uint64_t seed, const float *R0, const float *C0) {
+  RQ_TRY(check_train(n, d, m, h, niter));
+  if (init != 0 && init != 1) return fail(RQ_EINVAL, "train_opq: init must be 0 (natural) or 1 (random)");
+  return train_opq_host<uint8_t>(C, B1, R, obj, X, n, d, m, h, niter, init, seed, R0, C0, 1);
+}
+
+// ---- training with more than 256 codewords per codebook: 16-bit codes.  h <= 256 runs the byte
+// instantiation of the same loops and widens: the bits of rq_train_pq / _opq / _rvq.  Same salts, same order of draws at any h.
+int rq_train_pq_wide(float *C, int16_t *B, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                     uint64_t seed, int code_base) {
+  RQ_TRY(check_train_wide("rq_train_pq_wide", !C || !B || !X, n, d, m, h, niter, 32, true, code_base));
+  if (h <= 256) return train_pq_host<uint8_t>(C, B, error, X, n, d, m, h, niter, seed, code_base);
+  return train_pq_host<int16_t>(C, B, error, X, n, d, m, h, niter, seed, code_base);
+}
+
+int rq_train_opq_wide(float *C, int16_t *B, float *R, float *obj, const float *X, int64_t n, int d, int m, int h, int niter,
+                      int init, uint64_t seed, const float *R0, const float *C0, int code_base) {
+  RQ_TRY(check_train_wide("rq_train_opq_wide", !C || !B || !R || !X, n, d, m, h, niter, 32, true, code_base));
+  if (init != 0 && init != 1) return fail(RQ_EINVAL, "rq_train_opq_wide: init must be 0 (natural) or 1 (random)");
+  if (h <= 256) return train_opq_host<uint8_t>(C, B, R, obj, X, n, d, m, h, niter, init, seed, R0, C0, code_base);
+  return train_opq_host<int16_t>(C, B, R, obj, X, n, d, m, h, niter, init, seed, R0, C0, code_base);
+}
+
+int rq_train_rvq_wide(float *C, int16_t *B, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
+                      uint64_t seed, int code_base) {
+  RQ_TRY(check_train_wide("rq_train_rvq_wide", !C || !B || !X, n, d, m, h, niter, 64, false, code_base));
+  if (h <= 256) return train_rvq_host<uint8_t>(C, B, error, X, n, d, m, h, niter, seed, code_base);
+  return train_rvq_host<int16_t>(C, B, error, X, n, d, m, h, niter, seed, code_base);
+}
 // Rimg[i * d + k] = R[k][i], R = U V' of the d x d matrix G (row-major) -- the rotation update of src/OPQ.jl:112-113 on the
 // device.  method 0: scaled Newton-Schulz (d <= 1024), 1: one-sided Jacobi SVD (even d <= 128).  status[0] = 0 when Rimg was
 // written, 1 when the method gave up (rank-deficient G: rq_train_opq then falls back); status[1] = steps / sweeps.  Synchronous.
@@ -596,7 +754,7 @@ int rq_dev_polar_factor(float *Rimg, const float *G, int d, int method, int *sta
   return RQ_OK;
 }
 
-// Phase clock of the calling thread's last rq_train_pq / rq_train_opq call, milliseconds:
+// Phase clock of the calling thread's last rq_train_pq / rq_train_opq call (or their *_wide forms), milliseconds:
 //   [0] X upload  [1] initialisation (seeding / first rotation + encode)  [2] qerror  [3] gram X'CB  [4] host SVD incl. its
 //   two small copies  [5] rotation  [6] update_centers  [7] encode  [8] reconstruct  [9] convergence check  [10] results D2H
 //   [11] wall time of the iteration loop  [12] iterations run  [13] Jacobi sweeps  [14] Newton-Schulz steps  [15] polar factors

@@ -334,6 +334,26 @@ def reconstruct(codes, Ccat, d, h, out=None):
     return out
 
 
+def update_centers_wide(Ccat, X, codes, m, h):
+    """update_centers over 16-bit codes, 1 <= h <= 32767 (rq_dev_update_centers_wide): codes (n, m) int16 zero-based; a row whose
+    code lies outside [0, h) is ignored in that sub-space.  In place on Ccat; returns counts [m][h]."""
+    n, d = X.shape
+    counts = torch.zeros((m, h), dtype=torch.int32, device=X.device)
+    _lib.check(_lib.lib().rq_dev_update_centers_wide(_chk(Ccat, torch.float32, "C"), counts.data_ptr(),
+                                                     _chk(X, torch.float32, "X"), _chk(codes, torch.int16, "codes"),
+                                                     n, d, m, h, _stream()))
+    return counts
+
+
+def reconstruct_wide(codes, Ccat, d, h, out=None):
+    """CB (n, d) of 16-bit codes (n, m) int16 zero-based (rq_dev_reconstruct_wide); a code outside [0, h) gives zeros."""
+    n, m = codes.shape
+    out = torch.empty((n, d), dtype=torch.float32, device=codes.device) if out is None else out
+    _lib.check(_lib.lib().rq_dev_reconstruct_wide(_chk(out, torch.float32, "CB"), _chk(codes, torch.int16, "codes"),
+                                                  _chk(Ccat, torch.float32, "C"), n, d, m, h, _stream()))
+    return out
+
+
 def qerror(X, CB):
     """mean_j |X_j - CB_j|^2 (python float)."""
     n, d = X.shape

@@ -8,7 +8,7 @@ train -> encode the base -> ADC search -> recall, every O(n) step on the device.
 drivers; their default norms="host" keeps the two numpy helpers below."""
 import numpy as np
 
-from .Linscan import eval_recall, linscan_opq, linscan_pq
+from .Linscan import eval_recall, linscan_opq, linscan_opq_u16, linscan_pq, linscan_pq_u16
 from .OPQ import quantize_opq, train_opq
 from .PQ import quantize_pq, train_pq
 
@@ -21,6 +21,17 @@ def _qerror(X, B, C, R=None):
     return float(((RX.astype(np.float64) - CB) ** 2).sum() / n)
 
 
+def _scan_pq(B, Xq, C, h, m, knn, R=None):
+    """The search leg of the PQ / OPQ drivers: linscan_pq / linscan_opq, and above 256 codewords per codebook the scans over
+    16-bit codes.  Those read an int16 array as ZERO-based, while train_* and quantize_* return int16 ONE-based codes: the codes
+    are converted explicitly."""
+    if h > 256:
+        B0 = (np.asarray(B) - 1).astype(np.uint16)
+        return linscan_pq_u16(B0, Xq, C, knn) if R is None else linscan_opq_u16(B0, Xq, C, R, knn)
+    b = int(np.log2(h) * m)
+    return linscan_pq(B, Xq, C, b, knn) if R is None else linscan_opq(B, Xq, C, b, R, knn)
+
+
 def experiment_pq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     C, B, train_error = train_pq(Xt, m, h, niter, V, seed=seed)
     if V:
@@ -29,16 +40,14 @@ def experiment_pq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     base_error = _qerror(Xb, B_base, C)
     if V:
         print("Error in base is %e" % base_error)
-    b = int(np.log2(h) * m)
-    dists, idx = linscan_pq(B_base, Xq, C, b, knn)
+    dists, idx = _scan_pq(B_base, Xq, C, h, m, knn)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
 
 
 def experiment_pq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     C, B, train_error = train_pq(Xt, m, h, niter, V, seed=seed)
-    b = int(np.log2(h) * m)
-    dists, idx = linscan_pq(B, Xq, C, b, knn)
+    dists, idx = _scan_pq(B, Xq, C, h, m, knn)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, train_error, recall
 
@@ -51,16 +60,14 @@ def experiment_opq(Xt, Xb, Xq, gt, m, h, init, niter=25, knn=1000, V=False, seed
     base_error = _qerror(Xb, B_base, C, R)
     if V:
         print("Error in base is %e" % base_error)
-    b = int(np.log2(h) * m)
-    dists, idx = linscan_opq(B_base, Xq, C, b, R, knn)
+    dists, idx = _scan_pq(B_base, Xq, C, h, m, knn, R)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, R, train_error, B_base, recall
 
 
 def experiment_opq_query_base(Xt, Xq, gt, m, h, init, niter=25, knn=1000, V=False, seed=0):
     C, B, R, train_error = train_opq(Xt, m, h, niter, init, V, seed=seed)
-    b = int(np.log2(h) * m)
-    dists, idx = linscan_opq(B, Xq, C, b, R, knn)
+    dists, idx = _scan_pq(B, Xq, C, h, m, knn, R)
     recall = eval_recall(gt, idx, knn, verbose=V)
     return C, B, R, train_error, recall
 
