@@ -394,7 +394,31 @@ int rq_linscan_opq(float *dists, uint32_t *ids, const uint8_t *codes, const floa
  * rq_ervq_update_codebook with in-range codes): the call returns RQ_OK or a negative status with a message, B1 lies in 1 .. h,
  * the seeds in [0, n), every row is counted once per stage, and the same call gives the same bits twice.  Codebooks, R and the
  * objective are unspecified (one non-finite row turns every centre of its sub-space into NaN: the segment sums are matrix
- * products).  LSQ / chain / SR training are not covered. */
+ * products).
+ * Non-finite inputs of training -- at h > 256 and of LSQ / chain / SR training (tests/test_gpu_nonfinite_train.py; inputs and CPU
+ * restatements in tests/nonfinite_train_cases.py, held to the oracles by tests/test_nonfinite_train_ref.py):
+ *   a. the reductions are column-wise -- a non-finite coordinate (row r, column c) of X reaches column c of the result only.
+ *      rq_dev_update_centers / rq_dev_update_centers_wide: counts exact, row r counted; every column != c has the bits it has
+ *      when column c of X holds zeros; a code without rows keeps its bits in every column; the same bits twice, NaN payloads
+ *      included; column c unspecified (the matrix-core kernel meets 0 x NaN in every code of the column, the owner-thread
+ *      kernel of TRAIN_CENTERS_MFMA = 0 only in the code of row r).  rq_dev_reconstruct_wide copies NaN, Inf and denormal
+ *      entries of C bit for bit.  rq_dev_lsq_normal_eq: A depends on the codes alone; b is NaN exactly where the f64 sums in
+ *      ascending row order are NaN and bit-equal elsewhere (a segmented sum: m cells of column c per poisoned row).
+ *      rq_[dev_]update_codebooks_lsq / _chain: the solve keeps right-hand-side columns apart (one thread per column in the
+ *      triangular solves, one output column per accumulator in the updates; no coupled tiles), so every column != c of C is
+ *      bit-equal to the call on X with column c zeroed and within the finite-data tolerances of the f64 solve; the host entry
+ *      equals the device entry bit for bit; column c unspecified; RQ_OK or a negative status with a message.  rq_sr_std:
+ *      sigma[k], k != c, keeps its bits, sigma[c] is what the f64 two-pass arithmetic gives (NaN for NaN / Inf);
+ *      rq_sr_perturb with a NaN / Inf sigma[c]: column c of Y non-finite, every other column unchanged; a non-finite scale
+ *      is refused;
+ *   b. the training loops -- rq_train_pq_wide, rq_train_opq_wide (with or without R0 / C0), rq_train_rvq_wide, rq_train_lsq,
+ *      rq_train_sr (both methods, with and without the clean update), rq_train_chainq -- on a base with a non-finite or
+ *      overflowing row: RQ_OK or one of the negative codes with a message, never a hipError_t; on RQ_OK every code in range and
+ *      obj of its documented length; the same bits twice on every output; a finite call right afterwards returns its usual bits
+ *      (no device state is left behind).  With the returned codes the reductions of (a) count every row once, and an encode
+ *      with the returned (possibly non-finite) centres is in range.  rq_train_pq_wide at h <= 256 stays the bits of rq_train_pq.
+ *      rq_train_chainq refuses such a base with RQ_EUNSUPPORTED (the polar factor of X CB' does not converge) and writes no
+ *      output; were it to return RQ_OK, R is orthonormal to 1e-5 or holds a NaN.  Centres, R and objective unspecified. */
 /* quantize_pq (src/PQ.jl:18-48): codes [n][m] uint8 zero-based.  h <= 256. */
 int rq_encode_pq(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h);
 /* quantize_opq (src/OPQ.jl:19-27). */
@@ -659,8 +683,9 @@ int rq_train_opq(float *C, int16_t *B1, float *R, float *obj, const float *X, in
  * code_base 0 (zero-based) or 1 (Julia's one-based Matrix{Int16}), as in the wide encodes.  rq_train_profile describes the last
  * wide call with the same slots.  A NULL C, B, X (or R), a bad code_base, d < m, n < h or niter < 0: RQ_EINVAL; h outside
  * [1, RQ_MAX_H16] or m out of range (PQ / OPQ: 1..32, RVQ: 1..64): RQ_EUNSUPPORTED; on any error no output byte is written.
- * The non-finite contract pinned for training at h <= 256 is NOT extended to h > 256: non-finite rows give unspecified centres
- * (no fault). */
+ * Non-finite rows: the contract of "Non-finite inputs of training" above (point b) holds at every h -- status 0 or a negative
+ * code with a message, codes in range, the same bits twice, no device state left behind; centres, R and objective unspecified
+ * (tests/test_gpu_nonfinite_train.py, tests/test_nonfinite_train_ref.py). */
 int rq_train_pq_wide(float *C, int16_t *B, double *error, const float *X, int64_t n, int d, int m, int h, int niter,
                      uint64_t seed, int code_base);
 int rq_train_opq_wide(float *C, int16_t *B, float *R, float *obj, const float *X, int64_t n, int d, int m, int h, int niter,
@@ -678,7 +703,8 @@ int rq_train_rvq_wide(float *C, int16_t *B, double *error, const float *X, int64
  *                   than 65 793 rows per code every partial sum is an exact integer below 2^24 and the result is
  *                   float32(sum) * (1.0f / float32(count)) bit for bit.  A row whose code lies outside [0, h) (negative ones
  *                   included) is IGNORED in that sub-space: not summed, not counted, never used as an index.  Non-finite X:
- *                   unspecified values (a non-finite row may turn every centre of its sub-space into NaN), no fault.
+ *                   a non-finite coordinate (row r, column c) leaves counts and every column != c exactly as they are with
+ *                   column c zeroed; column c is unspecified (0 x NaN reaches every code of it).
  *   reconstruct     (src/OPQ.jl:101,128) CB[j][off_i + s] = C_i[codes[j][i]][s], a pure copy.  A code outside [0, h) is not
  *                   read from C: that sub-space of row j is written as ZEROS.
  * n <= 0: RQ_OK.  A NULL pointer or d < m: RQ_EINVAL; h or m out of range, or a shape whose partial sums do not fit 2 GiB of

@@ -21,8 +21,11 @@ the first 4114 of 143 169 689 rows encoded and the rest untouched.  residual_lau
 aq_norms_launch (16 work-items per row: 2^28 rows) and the code-widening kernels now cut their rows into launches of at most
 2^31 work-items; test_encode_rvq_scalar_epilogue_all_rows and test_norms_past_the_work_items_of_one_launch pin it.
 
+Section 11 takes the slice planner of the wide centre update (update_centers_h16_launch) to its two caps -- 2^23 rows and 2^30
+bytes of X per slice -- and to its refusal; those arrays are 0.5 and 2.1 GB, the limits are the planner's, not an index width.
+
 A GPU test skips only when the device has less free memory than the test needs (never on an MI355X: the file peaks at
-32.4 GiB of tensors; 25 tests, 17 s, the slowest 2.9 s)."""
+32.4 GiB of tensors; 28 tests, 21 s, the slowest 2.9 s)."""
 import ctypes
 
 import numpy as np
@@ -738,3 +741,134 @@ def test_row_limits_are_refused_before_any_access(rq):
     sigma = np.full((d,), -7.0, dtype=np.float32)
     refused(L.rq_sr_std(sigma.ctypes.data, hX.ctypes.data, over, d), "sr_std")
     assert (sigma == -7.0).all() and (hX == -7.0).all()
+
+
+# ---- 11. the slice planner of the wide centre update at its limits ----------------------------------------------------------------------------------
+# update_centers_h16_launch (rq_train.hip) cuts the rows into `grid` slices: want = min(ceil(CUs / code blocks), ceil(n / 1024)),
+# raised to least = ceil(n / cap) with cap = min(2^23 - 1 rows (f32 counters), 2^30 bytes of X (32-bit buffer offsets)), capped by
+# most = the slices whose partial sums ((grid + 1) x (h d + m h) floats, allocated 1.25x) fit 2 GiB; least > most is refused.  The
+# library does not name its grid, so the cases below restate the planner and assert that the cap, not `want`, decides.
+# The refill of emptied centres needs no case here: refill_cost_kernel and gather_rows_kernel (rq_train.hip) index with a 64-bit
+# row throughout (row * d + col0, row * cstride + col and rows[k] * d are int64 / size_t products), so no 32-bit product passes
+# 2^31 at any n the *_wide training entries accept.
+RQ_EUNSUPPORTED = -2
+H16_SCRATCH = 2 << 30
+
+
+def _h16_plan(n, d, m, h):
+    """(want, least, most, grid) of update_centers_h16_launch for the device's CU count."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nblocks = (h + 255) // 256
+    stride = h * d + m * h
+    cap = min((1 << 23) - 1, (1 << 30) // (d * 4))
+    most = (H16_SCRATCH // 5 * 4) // (stride * 4) - 1
+    least = -(-n // cap) if cap > 0 else most + 1
+    want = min(-(-cus // nblocks), -(-n // 1024))
+    return want, least, most, min(max(want, 1, least), most)
+
+
+def _wide_codes(n, m, h):
+    """codes [n][m] int16 on the device: a fixed permutation of (row + 4099 q) % h, so every code has rows (n >= h)."""
+    import torch
+    g = torch.Generator(device="cpu")
+    g.manual_seed(h + m)
+    perm = torch.randperm(h, generator=g).to(torch.int16).cuda()
+    rows = torch.arange(n, device="cuda")
+    return torch.stack([perm[((rows + 4099 * q) % h)] for q in range(m)], dim=1).contiguous()
+
+
+def _int_rows(n, d, seed):
+    """X [n][d] f32 on the device with integer coordinates in [0, 255]."""
+    import torch
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    return torch.randint(0, 256, (n, d), generator=g, device="cuda", dtype=torch.int32).to(torch.float32)
+
+
+def _exact_means_on_device(X, codes, m, h):
+    """(C concatenated f32 (numpy), counts [m][h] int64 (numpy)): counts by bincount, sums by an f64 index_add_ on the device
+    (exact on integers), centres float32(sum) * (1.0f / float32(count)) -- the kernel's finishing formula -- in numpy."""
+    import torch
+    n, d = X.shape
+    sub = d // m
+    assert sub * m == d
+    out, counts = [], np.zeros((m, h), dtype=np.int64)
+    for q in range(m):
+        idx = codes[:, q].long()
+        cnt = torch.bincount(idx, minlength=h).cpu().numpy()
+        sums = torch.zeros((h, sub), dtype=torch.float64, device="cuda").index_add_(0, idx, X[:, q * sub:(q + 1) * sub].double())
+        sums = sums.cpu().numpy()
+        assert cnt.min() > 0 and np.array_equal(sums, np.round(sums))
+        assert 2 * sums.max() < 2 ** 24 and 2 * cnt.max() < 2 ** 24          # the one-hot product carries 2 x the sums in f32
+        out.append((sums.astype(np.float32) * (np.float32(1) / cnt.astype(np.float32))[:, None]).reshape(-1))
+        counts[q] = cnt
+    return np.concatenate(out), counts
+
+
+def _wide_update_exact(n, d, m, h, seed):
+    import torch
+    X, codes = _int_rows(n, d, seed), _wide_codes(n, m, h)
+    want, cnt = _exact_means_on_device(X, codes, m, h)
+    assert cnt.sum() == n * m
+    spare = 64
+    Cd = torch.full((h * d + spare,), 99.5, dtype=torch.float32, device="cuda")
+    counts = torch.full((m * h + spare,), lo.sentinel_of(torch.int32), dtype=torch.int32, device="cuda")
+    _call("rq_dev_update_centers_wide", Cd, counts, X, codes, n, d, m, h, None)
+    assert bool((Cd[h * d:] == 99.5).all()) and bool((counts[m * h:] == lo.sentinel_of(torch.int32)).all())
+    assert np.array_equal(counts[:m * h].cpu().numpy().astype(np.int64).reshape(m, h), cnt)
+    got = Cd[:h * d].cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "%d centre values differ" % int((got != want).sum())
+    return X, codes, Cd
+
+
+def test_update_centers_wide_row_cap_forces_a_third_slice(rq, bases):
+    """n = 2 (2^23 - 1) + 4112 rows of d = 8 (0.54 GB), m = 1, h = 32767: 128 code blocks want 2 slices, the 2^23-row cap of the
+    f32 counters forces 3.  Counts exact, means bit-equal to float32(sum) * (1.0f / float32(count))."""
+    n, d, m, h = 2 * ((1 << 23) - 1) + 4112, 8, 1, 32767
+    want, least, most, grid = _h16_plan(n, d, m, h)
+    assert (want, least, grid) == (2, 3, 3) and most >= 3 and (1 << 30) // (d * 4) > (1 << 23) - 1      # the ROW cap binds
+    bases.drop()
+    _need(n * d * 4 + 2 * n * d * 8 + n * m * 2)
+    _wide_update_exact(n, d, m, h, 5)
+
+
+def test_update_centers_wide_byte_cap_forces_a_third_slice(rq, bases):
+    """d = 2048, m = 8, h = 32767, n = 2 (2^28 / 2048) + 77 rows (2.1 GB of X, 1.1 GB of partial sums): want 2 slices, the
+    2^30-byte rule of the 32-bit buffer offsets forces 3, and 5 would still fit the scratch.  Then rq_dev_reconstruct_wide on the
+    same codes: 5.4e8 output elements gathered from h d = 6.7e7 centre values, bit for bit."""
+    import torch
+    n, d, m, h = 2 * ((1 << 28) // 2048) + 77, 2048, 8, 32767
+    want, least, most, grid = _h16_plan(n, d, m, h)
+    assert (want, least, most, grid) == (2, 3, 5, 3) and (1 << 30) // (d * 4) < (1 << 23) - 1              # the BYTE cap binds
+    bases.drop()
+    _need(3 * n * d * 4 + 2 * n * d * 8 // m + 3 * h * d * 4 + (grid + 1) * (h * d + m * h) * 5)
+    X, codes, Cd = _wide_update_exact(n, d, m, h, 6)
+    del X
+    CB = lo.output(n, (d,), torch.float32)
+    _call("rq_dev_reconstruct_wide", CB, codes, Cd, n, d, m, h, None)
+    sub = d // m
+    for q in range(m):
+        Cq = Cd[h * sub * q:h * sub * (q + 1)].view(h, sub)
+        assert torch.equal(CB[:n, q * sub:(q + 1) * sub].view(torch.int32), Cq[codes[:, q].long()].view(torch.int32)), q
+    lo.assert_sentinel(CB, n)
+
+
+def test_update_centers_wide_refuses_a_slice_that_does_not_fit(rq):
+    """d = 8192, m = 1, h = 32767: ONE slice of partial sums is 1.07 GB and the reduced slice behind it as much again, past the
+    2 GiB of scratch (most = 0 slices): RQ_EUNSUPPORTED naming the shape.  update_centers_h16_launch makes that test before
+    it asks for its workspace or launches anything (read in rq_train.hip), so small sentinel-filled arrays are safe."""
+    import torch
+    n, d, m, h = 100, 8192, 1, 32767
+    want, least, most, grid = _h16_plan(n, d, m, h)
+    assert most == 0 and least == 1
+    X = torch.full((n, d), -7.0, dtype=torch.float32, device="cuda")
+    codes = torch.full((n, m), -3, dtype=torch.int16, device="cuda")
+    Cd = torch.full((4096,), -7.0, dtype=torch.float32, device="cuda")
+    counts = torch.full((4096,), -3, dtype=torch.int32, device="cuda")
+    L = _L()
+    rc = L.rq_dev_update_centers_wide(Cd.data_ptr(), counts.data_ptr(), X.data_ptr(), codes.data_ptr(), n, d, m, h, None)
+    msg = (L.rq_last_error() or b"").decode()
+    torch.cuda.synchronize()
+    assert rc == RQ_EUNSUPPORTED and "n=%d d=%d h=%d" % (n, d, h) in msg and "partial sums" in msg, (rc, msg)
+    assert bool((Cd == -7.0).all()) and bool((counts == -3).all()) and bool((X == -7.0).all()) and bool((codes == -3).all())
