@@ -133,6 +133,21 @@ int rq_dev_quantize_norms(uint8_t *norm_codes, float *dbnorms_out, const float *
  * norms_out [n] may be NULL. */
 int rq_get_norms_codebook(uint8_t *norm_codes, float *cbnorms, float *norms_out, const uint8_t *codes, const float *C,
                           int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed);
+/* The same five over int16 codes, for the codes of rq_train_rvq_wide / rq_encode_rvq_wide: 1 <= m <= 64,
+ * 2 <= h <= RQ_MAX_H16, 1 <= hn <= RQ_MAX_H16, code_base 0 or 1 (the device forms take zero-based codes); norm codes are int16 and
+ * zero-based.  Same kernels instantiated for the wider code, same order of sums: at h, hn <= 256 the bits of the byte entries,
+ * widened.  A code outside [0, h) (after code_base): RQ_EINVAL before any other work, outputs untouched.
+ * rq_aq_norms_wide: src/utils.jl:15-16, :34-48.  rq_quantize_norms_wide: src/utils.jl:29-59, the unsorted table of hn entries in
+ * LDS (128 KiB at most).  rq_get_norms_codebook_wide: src/utils.jl:4-26 as the resident Lloyd loop of rq_train_pq_wide with
+ * d = m = 1, h = hn -- cbnorms and assignments equal that call on the same norms, niter and seed, bit for bit. */
+int rq_aq_norms_wide(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, int code_base);
+int rq_dev_aq_norms_wide(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream);
+int rq_quantize_norms_wide(int16_t *norm_codes, float *norms_out, const int16_t *codes, const float *C, const float *cbnorms,
+                           int64_t n, int d, int m, int h, int hn, int code_base);
+int rq_dev_quantize_norms_wide(int16_t *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n,
+                               int hn, void *stream);
+int rq_get_norms_codebook_wide(int16_t *norm_codes, float *cbnorms, float *norms_out, const int16_t *codes, const float *C,
+                               int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed, int code_base);
 
 /* ---- quantize_rvq (src/RVQ.jl:18-66) -----------------------------------------
  * m full-dimensional stages on the running residual: stage i = pairwise SqEuclidean + first-index
@@ -471,6 +486,33 @@ int rq_linscan_pq_wide(float *dists, uint32_t *ids, const int16_t *codes, const 
 /* linscan_opq over 16-bit codes (src/Linscan.jl:93-115): queries are rotated by R' on the device first. */
 int rq_linscan_opq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *centers, const float *queries,
                         const float *R, int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base);
+/* ---- the additive-quantizer scan over 16-bit codes: linscan_lsq / linscan_cq for 1 <= h <= RQ_MAX_H16,
+ * what searches the Int16 codes of rq_train_rvq_wide / rq_encode_rvq_wide (src/RVQ.jl:139-158).  The contract is
+ * deps/src/linscan_aqd_pairwise_byte.cpp:14-94 (LSQ) and :97-176 (CQ) with `unsigned char *codes` replaced by a zero-based int16
+ * -- its arithmetic already takes h at run time (tentry[h*k + code[k]]).  All f32, every operation rounded on its own:
+ *   LSQ table  T[j] = T[j] - (2 q[k]) * c[j][k], k = 0..d-1 from +0 (:42-49);  CQ table  T[j] = T[j] + (q[k]-c[j][k]) * (q[k]-c[j][k])
+ *   (:124-131);  row distance acc = 0, acc = acc + T[h k + b_k] for k = 0..m-1, then for LSQ acc = acc + dbnorms[row] (:70-74);
+ *   answer: the k smallest (dist, id) pairs in lexicographic order, exact for every 1 <= k <= n (:82-88).
+ * codes [n][m] int16, codebooks [m*h][d] (m full-dimensional codebooks back to back), 1 <= m <= 32, d >= 1 (no d % m rule),
+ * 1 <= k <= n < 2^31, code_base 0 or 1.  "Non-finite inputs" above holds unchanged: a NaN distance -- also one that comes from
+ * dbnorms -- is never a neighbour, -0 becomes +0, a short list ends in the padding pair.  A code outside [0, h), statuses, the
+ * "no output byte written on error" rule, nq <= 0, scratch and the device used: exactly as for rq_linscan_pq_wide.  At h = 256 the
+ * answers are those of rq_linscan_lsq / rq_linscan_cq bit for bit.  rq_last_scan_kernel names the keys kernel:
+ * "adc_keys_h16_kernel<4, true, true>" (queries per gather, table in LDS, row norm added; CQ shares the PQ instantiation and its
+ * name).  The rq_lsq_prepare handle stays byte-only. */
+/* linscan_lsq over 16-bit codes (src/Linscan.jl:118-157; deps/src/linscan_aqd_pairwise_byte.cpp:14-94); R may be NULL */
+int rq_linscan_lsq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *queries, const float *codebooks,
+                        const float *dbnorms, const float *R, int64_t n, int64_t nq, int m, int h, int d, int k,
+                        int code_base, int id_base);
+/* linscan_cq over 16-bit codes (src/Linscan.jl:160-193; deps/src/linscan_aqd_pairwise_byte.cpp:97-176) */
+int rq_linscan_cq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *queries, const float *codebooks,
+                       int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base);
+/* The search leg of src/RVQ.jl:147-155 in one call: dbnorms[i] = cbnorms[quantize(|sum_k C_k[b_ik]|^2)] computed on the device from
+ * the uploaded codes with the arithmetic of rq_quantize_norms_wide (2 <= h, 1 <= hn <= RQ_MAX_H16), then the scan; equals
+ * rq_linscan_lsq_wide given those dbnorms, bit for bit. */
+int rq_linscan_lsq_cbnorms_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *queries,
+                                const float *codebooks, const float *cbnorms, int hn, const float *R, int64_t n, int64_t nq,
+                                int m, int h, int d, int k, int code_base, int id_base);
 /* ---- byte rows: quantize_pq / quantize_opq of UInt8 data without widening it on the host.
  * bvecs files (SIFT1B: bigann_base / learn / query) hold UInt8 vectors -- bvecs_read returns Matrix{UInt8},
  * src/xvecs_read.jl:14-52 -- and the reference converts them to Float32 on the host before it encodes them
@@ -579,6 +621,18 @@ int rq_dev_linscan_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16
  * table); test aid: the table's bits can be pinned apart from the scan. */
 int rq_dev_adc_lut_wide(float *lut, const float *centers, const float *queries, int64_t nq, int m, int h, int subdim,
                         void *stream);
+/* linscan_lsq / linscan_cq over one resident shard of ZERO-based int16 codes (deps/src/linscan_aqd_pairwise_byte.cpp:14-94,
+ * :97-176 with h entries per codebook; see rq_linscan_lsq_wide): codebooks [m*h][d], lut_mode 1 = LSQ (dbnorms [n] required),
+ * 2 = CQ (dbnorms ignored).  dists / ids / keys, id_offset and id_base exactly as for rq_dev_linscan_wide, so shards merge through
+ * rq_dev_merge_topk unchanged; a row with a code outside [0, h) is never returned.  codes 2-byte aligned, the float arrays 4-byte
+ * aligned (16 and d % 4 == 0 for vector loads of the codebook rows).  Everything runs on `stream`. */
+int rq_dev_linscan_aq_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *codebooks,
+                           const float *queries, const float *dbnorms, int64_t n, int64_t nq, int m, int h, int d, int k,
+                           int lut_mode, uint32_t id_offset, int id_base, void *stream);
+/* Per-query tables lut [nq][m][h] of codebooks [m*h][d] (deps/src/linscan_aqd_pairwise_byte.cpp:42-49 for lut_mode 1 = LSQ,
+ * :124-131 for 2 = CQ, with h entries per codebook); test aid: the table's bits can be pinned apart from the scan. */
+int rq_dev_aq_lut_wide(float *lut, const float *codebooks, const float *queries, int64_t nq, int m, int h, int d,
+                       int lut_mode, void *stream);
 /* Host-only: where rq_dev_linscan_wide keeps the table of m * h entries (no reference counterpart; the reference's table is a
  * heap array, deps/src/linscan_aqd.cpp:58).  out[0] queries per gather (4, 2 or 1), out[1] 1: the table of a query group is in
  * LDS, 0: gathered from global memory, out[2] queries per group, out[3] LDS bytes.  cap >= 4. */

@@ -388,6 +388,22 @@ end
 
 function linscan_lsq(B::Matrix{T}, X::Matrix{Cfloat}, C::Vector{Matrix{Cfloat}},
                      dbnorms::Vector{Cfloat}, R::Matrix{Cfloat}, k::Int=10000) where T <: Integer
+  d, h = size(C[1])
+  if h > 256      # 16-bit codes (train_rvq / quantize_rvq at h > 256): rq_linscan_lsq_wide
+    m, n  = size(B)
+    _, nq = size(X)
+    B16   = convert(Matrix{Int16}, B)            # one-based, as quantize_rvq returns them: code_base = 1
+    dists = _result(Cfloat, k, nq)
+    res   = _result(Cuint,  k, nq)
+    code_base = 1
+    id_base   = 1
+    _check(ccall((:rq_linscan_lsq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Cuint}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat},
+       Int64, Int64, Cint, Cint, Cint, Cint, Cint, Cint),
+      dists, res, B16, X, hcat(C...), dbnorms, R, Int64(n), Int64(nq), Cint(m), Cint(h), Cint(d), Cint(k), Cint(code_base),
+      Cint(id_base)))
+    return dists, res
+  end
   return linscan_lsq(convert(Matrix{UInt8}, B .- 1), X, C, dbnorms, R, k)
 end
 
@@ -444,8 +460,23 @@ function get_norms_codebook(B::Matrix{UInt8}, C::Vector{Matrix{Cfloat}}; niter::
     norm_codes, cbnorms, C_NULL, B, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(hn), Cint(niter), UInt64(seed)))
   return convert(Vector{Int}, norm_codes) .+ 1, cbnorms
 end
-get_norms_codebook(B::Matrix{T}, C::Vector{Matrix{Cfloat}}; niter::Integer=100, seed::Integer=0) where T <: Integer =
-  get_norms_codebook(convert(Matrix{UInt8}, B .- 1), C; niter=niter, seed=seed)
+function get_norms_codebook(B::Matrix{T}, C::Vector{Matrix{Cfloat}}; niter::Integer=100, seed::Integer=0) where T <: Integer
+  d, h = size(C[1])
+  if h > 256      # 16-bit codes and a norms codebook of h entries: rq_get_norms_codebook_wide
+    m, n = size(B)
+    hn = h
+    B16 = convert(Matrix{Int16}, B)
+    norm_codes = Vector{Int16}(undef, n)
+    cbnorms    = Vector{Cfloat}(undef, hn)
+    code_base = 1
+    _check(ccall((:rq_get_norms_codebook_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Int16}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, UInt64, Cint),
+      norm_codes, cbnorms, C_NULL, B16, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(hn), Cint(niter), UInt64(seed),
+      Cint(code_base)))
+    return convert(Vector{Int}, norm_codes) .+ 1, cbnorms
+  end
+  return get_norms_codebook(convert(Matrix{UInt8}, B .- 1), C; niter=niter, seed=seed)
+end
 
 """
     quantize_norms(B, C, cbnorms) -> dbnormsB, dbnormsX     (src/utils.jl:29-59)
@@ -463,8 +494,22 @@ function quantize_norms(B::Matrix{UInt8}, C::Vector{Matrix{Cfloat}}, cbnorms::Ve
     norm_codes, dbnormsX, B, hcat(C...), cbnorms, Int64(n), Cint(d), Cint(m), Cint(h), Cint(hn)))
   return convert(Vector{Int16}, norm_codes) .+ Int16(1), dbnormsX
 end
-quantize_norms(B::Matrix{T}, C::Vector{Matrix{Cfloat}}, cbnorms::Vector{Cfloat}) where T <: Integer =
-  quantize_norms(convert(Matrix{UInt8}, B .- 1), C, cbnorms)
+function quantize_norms(B::Matrix{T}, C::Vector{Matrix{Cfloat}}, cbnorms::Vector{Cfloat}) where T <: Integer
+  d, h = size(C[1])
+  if h > 256      # 16-bit codes, cbnorms of up to 32767 entries: rq_quantize_norms_wide
+    m, n = size(B)
+    hn = length(cbnorms)
+    B16 = convert(Matrix{Int16}, B)
+    norm_codes = Vector{Int16}(undef, n)
+    dbnormsX   = Vector{Cfloat}(undef, n)
+    code_base = 1
+    _check(ccall((:rq_quantize_norms_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint),
+      norm_codes, dbnormsX, B16, hcat(C...), cbnorms, Int64(n), Cint(d), Cint(m), Cint(h), Cint(hn), Cint(code_base)))
+    return norm_codes .+ Int16(1), dbnormsX
+  end
+  return quantize_norms(convert(Matrix{UInt8}, B .- 1), C, cbnorms)
+end
 
 """
     linscan_cq(B, X, C, k=10000) -> dists, idx     (src/Linscan.jl:160-193)
@@ -482,6 +527,20 @@ function linscan_cq(B::Matrix{UInt8}, X::Matrix{Cfloat}, C::Vector{Matrix{Cfloat
 end
 
 function linscan_cq(B::Matrix{T}, X::Matrix{Cfloat}, C::Vector{Matrix{Cfloat}}, k::Int=10000) where T <: Integer
+  d, h = size(C[1])
+  if h > 256      # 16-bit codes: rq_linscan_cq_wide
+    m, n  = size(B)
+    _, nq = size(X)
+    B16   = convert(Matrix{Int16}, B)
+    dists = _result(Cfloat, k, nq)
+    res   = _result(Cuint,  k, nq)
+    code_base = 1
+    id_base   = 1
+    _check(ccall((:rq_linscan_cq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Cuint}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int64, Cint, Cint, Cint, Cint, Cint, Cint),
+      dists, res, B16, X, hcat(C...), Int64(n), Int64(nq), Cint(m), Cint(h), Cint(d), Cint(k), Cint(code_base), Cint(id_base)))
+    return dists, res
+  end
   return linscan_cq(convert(Matrix{UInt8}, B .- 1), X, C, k)
 end
 

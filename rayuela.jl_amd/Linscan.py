@@ -136,6 +136,84 @@ def linscan_opq_u16(B, X, C, R, k=10000):
     return _linscan_u16(B, X, C, R, k)
 
 
+def _hcat_wide(C, d):
+    from .utils import check_wide_h
+    arr = np.stack([_as_f32(c, "C[i]") for c in C])
+    if arr.ndim != 3 or arr.shape[2] != d:
+        raise ValueError("linscan_lsq/cq need m codebooks of shape (h, d); got %s" % (arr.shape,))
+    check_wide_h(arr.shape[1])
+    return np.ascontiguousarray(arr)  # hcat(C...) == [m*h][d] in memory
+
+
+def _linscan_aq_u16(B, X, C, k, lsq, dbnorms=None, cbnorms=None, R=None):
+    X = _as_f32(X, "X")
+    nq, d = X.shape
+    m = len(C)
+    if m < 1 or m > 32:
+        raise ValueError("the scan over 16-bit codes covers 1 <= m <= 32 codebooks; got %d" % m)
+    cb = _hcat_wide(C, d)
+    h = cb.shape[1]
+    Bi, base = _codes_i16(B, h)
+    n = Bi.shape[0]
+    if Bi.shape[1] != m:
+        raise ValueError("B has %d columns for %d codebooks" % (Bi.shape[1], m))
+    if k < 1 or k > n:
+        raise ValueError("k=%d must be in [1, n=%d]" % (k, n))
+    Rp = None
+    if R is not None:
+        Rp = _as_f32(R, "R")
+        if Rp.shape != (d, d):
+            raise ValueError("R must be (d, d)")
+    if dbnorms is not None:
+        nrm = np.ascontiguousarray(dbnorms, dtype=np.float32)
+        if nrm.shape != (n,):
+            raise ValueError("dbnorms must have one entry per database row")
+    if cbnorms is not None:
+        cbn = np.ascontiguousarray(_as_f32(cbnorms, "cbnorms").reshape(-1))
+        if cbn.shape[0] < 1 or cbn.shape[0] > 32767:
+            raise ValueError("cbnorms must hold 1..32767 entries; got %d" % cbn.shape[0])
+    dists = _lib.result_empty((nq, k), np.float32)     # every element is written by the library
+    idx = _lib.result_empty((nq, k), np.uint32)
+    L = _lib.lib()
+    Rptr = None if Rp is None else Rp.ctypes.data
+    if not lsq:
+        _lib.check(L.rq_linscan_cq_wide(dists.ctypes.data, idx.ctypes.data, Bi.ctypes.data, X.ctypes.data, cb.ctypes.data,
+                                        n, nq, m, h, d, k, base, 1))
+    elif cbnorms is None:
+        _lib.check(L.rq_linscan_lsq_wide(dists.ctypes.data, idx.ctypes.data, Bi.ctypes.data, X.ctypes.data, cb.ctypes.data,
+                                         nrm.ctypes.data, Rptr, n, nq, m, h, d, k, base, 1))
+    else:
+        _lib.check(L.rq_linscan_lsq_cbnorms_wide(dists.ctypes.data, idx.ctypes.data, Bi.ctypes.data, X.ctypes.data,
+                                                 cb.ctypes.data, cbn.ctypes.data, cbn.shape[0], Rptr, n, nq, m, h, d, k, base, 1))
+    return dists, idx
+
+
+def linscan_lsq_u16(B, X, C, dbnorms, R, k=10000):
+    """linscan_lsq over 16-bit codes: any 1 <= h <= 32767 codewords per codebook (rq_linscan_lsq_wide) -> dists, idx
+
+    B : (n, m) uint16 / int16 zero-based codes, or any other integer dtype holding ONE-based codes (the dtype rule of
+    linscan_pq_u16);  X : (nq, d) float32;  C : list of m (h, d) full-dimensional codebooks;  dbnorms (n,);  R (d, d) or None.
+    idx ONE-based.  The arithmetic of src/Linscan.jl:118-157 / deps/src/linscan_aqd_pairwise_byte.cpp:14-94 with h entries per
+    codebook; at h = 256 the answer of linscan_lsq."""
+    if dbnorms is None:
+        raise ValueError("dbnorms must have one entry per database row")
+    return _linscan_aq_u16(B, X, C, k, True, dbnorms=dbnorms, R=R)
+
+
+def linscan_cq_u16(B, X, C, k=10000):
+    """linscan_cq over 16-bit codes (src/Linscan.jl:160-193; rq_linscan_cq_wide): T = |x - c|^2 per entry, no norms."""
+    return _linscan_aq_u16(B, X, C, k, False)
+
+
+def linscan_lsq_cbnorms_u16(B, X, C, cbnorms, R, k=10000):
+    """linscan_lsq_u16 with the database norms given as a norms codebook of up to 32767 entries: quantize_norms and
+    db_norms = norms_C[B_base_norms] (src/RVQ.jl:150-155) run on the device from the uploaded codes
+    (rq_linscan_lsq_cbnorms_wide)."""
+    if cbnorms is None:
+        raise ValueError("cbnorms is required")
+    return _linscan_aq_u16(B, X, C, k, True, cbnorms=cbnorms, R=R)
+
+
 def _hcat(C, m, d):
     arr = np.concatenate([_as_f32(c, "C[i]") for c in C], axis=0)   # hcat(C...) == [m*h][d] in memory
     if arr.shape != (m * 256, d):

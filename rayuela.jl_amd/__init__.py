@@ -26,7 +26,8 @@ from .ChainQ import quantize_chainq, train_chainq  # noqa: F401,E402
 from .CompetitiveQ import quantize_competitiveq, quantize_competitiveq_u8, last_beam_timing  # noqa: F401,E402
 from . import CompetitiveQ  # noqa: F401,E402  (CompetitiveQ.encode: the reference's one-vector signature)
 from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_aqd_query, LsqIndex,  # noqa: F401
-                      linscan_aqd_query_extra_byte, eval_recall, linscan_lsq_cbnorms, linscan_pq_u16, linscan_opq_u16)
+                      linscan_aqd_query_extra_byte, eval_recall, linscan_lsq_cbnorms, linscan_pq_u16, linscan_opq_u16,
+                      linscan_lsq_u16, linscan_cq_u16, linscan_lsq_cbnorms_u16)
 
 from .index import Index, Dataset  # noqa: F401,E402
 from . import h5results  # noqa: F401,E402  (libhdf5 is looked up lazily, on first use)

@@ -115,6 +115,18 @@ SIGNATURES = {
     "rq_linscan_opq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32]),
     "rq_dev_linscan_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _u32, _i32, _vp]),
     "rq_dev_adc_lut_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_linscan_lsq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "rq_linscan_cq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "rq_linscan_lsq_cbnorms_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32,
+                                           _i32]),
+    "rq_dev_linscan_aq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _u32, _i32,
+                                      _vp]),
+    "rq_dev_aq_lut_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "rq_aq_norms_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_dev_aq_norms_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "rq_quantize_norms_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "rq_dev_quantize_norms_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "rq_get_norms_codebook_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _u64, _i32]),
     "rq_scan_wide_plan": (_i32, [_i32, _i32, _vp, _i32]),
     "rq_scan_row_width": (_i32, [_i32]),
     "rq_order_bytes": (_i64, [_i64, _i32]),

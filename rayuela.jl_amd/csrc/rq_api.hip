@@ -769,14 +769,26 @@ static int host_linscan(float *dists, uint32_t *ids, const uint8_t *codes, const
 // linscan_pq / linscan_opq over 16-bit codes on host pointers (rq_scan_h16.hip): the shape of host_linscan's bulk branch -- upload,
 // then the bulk branch of deliver (query chunks) at every k.  The codes are validated (and made zero-based) on the device before
 // any output is written.
+// `aq` (linscan_lsq / linscan_cq over 16-bit codes): `centers` are codebooks [m * h][d]; LUT_LSQ takes the
+// row norms from dbnorms [n], or computes them on the device as cbnorms[quantize(|sum_k C_k[b_ik]|^2)] from cbnorms [hn].
+struct WideAq {
+  int lut_mode = LUT_PQ;
+  const float *dbnorms = nullptr, *cbnorms = nullptr;
+  int hn = 0;
+};
 static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const int16_t *codes, const float *centers,
                              const float *queries, const float *R, bool need_R, int64_t n, int64_t nq, int m, int h, int d,
-                             int k, int code_base, int id_base) {
+                             int k, int code_base, int id_base, const WideAq &aq = WideAq()) {
   Timer tt;
   g_t_h2d = g_t_kernel = g_t_d2h = 0;
   if (nq <= 0) return RQ_OK;
   if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
-  RQ_TRY(linscan_wide_check(who, !dists || !ids || !codes || !centers || !queries || (need_R && !R), n, m, h, d, k, 0, id_base));
+  const bool full = aq.lut_mode != LUT_PQ, lsq = aq.lut_mode == LUT_LSQ;
+  RQ_TRY(linscan_wide_check(who, !dists || !ids || !codes || !centers || !queries || (need_R && !R) ||
+                                     (lsq && !aq.dbnorms && !aq.cbnorms),
+                            n, m, h, d, k, 0, id_base, full));
+  if (lsq && aq.cbnorms && (aq.hn < 1 || aq.hn > RQ_MAX_H16))
+    return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, aq.hn, RQ_MAX_H16);
   SavedDevice saved;
   {
     int devs[64];
@@ -786,13 +798,17 @@ static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  DevBuf dcodes, dcent, dbad;
+  DevBuf dcodes, dcent, dbad, dn, dcbn;
   DevQueries q;
-  const size_t cb = (size_t)n * m * 2, ce = (size_t)m * h * (d / m) * 4;
+  const size_t cb = (size_t)n * m * 2, ce = (size_t)m * h * (full ? d : d / m) * 4;
   RQ_TRY(dcodes.alloc(cb)); RQ_TRY(dcent.alloc(ce)); RQ_TRY(dbad.alloc(8));
+  if (lsq) RQ_TRY(dn.alloc((size_t)n * 4));
+  if (lsq && !aq.dbnorms) RQ_TRY(dcbn.alloc((size_t)aq.hn * 4));
   Timer t1;
   RQ_HIP(hipMemcpy(dcodes.p, codes, cb, hipMemcpyHostToDevice));
   RQ_HIP(hipMemcpy(dcent.p, centers, ce, hipMemcpyHostToDevice));
+  if (lsq && aq.dbnorms) RQ_HIP(hipMemcpy(dn.p, aq.dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (lsq && !aq.dbnorms) RQ_HIP(hipMemcpy(dcbn.p, aq.cbnorms, (size_t)aq.hn * 4, hipMemcpyHostToDevice));
   g_t_h2d = t1.ms();
   RQ_TRY(prepare_codes_h16_launch(dcodes.as<int16_t>(), dbad.as<unsigned long long>(), n, m, h, code_base, nullptr));
   unsigned long long first_bad = 0;
@@ -803,7 +819,16 @@ static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const
   RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
   const int16_t *cdev = dcodes.as<int16_t>();
   const float *cen = dcent.as<float>();
+  if (lsq && !aq.dbnorms) {      // the norms leg of src/RVQ.jl:150-155 on the device: the arithmetic of rq_quantize_norms_wide
+    if (h < 2 || m > 64) return fail(RQ_EINVAL, "%s: the norms need 2 <= h, m <= 64; got h=%d m=%d", who, h, m);
+    RQ_TRY(aq_norms_h16_launch(dn.as<float>(), cdev, cen, n, d, m, h, nullptr));
+    RQ_TRY(quantize_norms_h16_launch(nullptr, dn.as<float>(), dn.as<float>(), dcbn.as<float>(), n, aq.hn, nullptr));
+  }
+  const float *nrm = lsq ? dn.as<float>() : nullptr;
   RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
+    if (full)
+      return dev_linscan_aq_wide(dd, di_, nullptr, cdev, cen, q.p + (size_t)q0 * d, nrm, n, nqc, m, h, d, k, aq.lut_mode, 0, id_base,
+                                 stream);
     return dev_linscan_wide(dd, di_, nullptr, cdev, cen, q.p + (size_t)q0 * d, n, nqc, m, h, d, k, 0, id_base, stream);
   }, true));
   g_t_total = tt.ms();
@@ -1679,6 +1704,52 @@ int rq_dev_adc_lut_wide(float *lut, const float *centers, const float *queries, 
   if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "rq_dev_adc_lut_wide: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
   if (subdim < 1) return fail(RQ_EINVAL, "rq_dev_adc_lut_wide: subdim=%d < 1", subdim);
   return lut_h16_launch(lut, centers, queries, nq, m, h, subdim, (hipStream_t)stream);
+}
+// ---- linscan_lsq / linscan_cq over 16-bit codes ------------------------------------------------------
+int rq_dev_aq_lut_wide(float *lut, const float *codebooks, const float *queries, int64_t nq, int m, int h, int d, int lut_mode,
+                       void *stream) {
+  if (nq <= 0) return RQ_OK;
+  if (!lut || !codebooks || !queries) return fail(RQ_EINVAL, "rq_dev_aq_lut_wide: NULL argument");
+  if (lut_mode != LUT_LSQ && lut_mode != LUT_CQ) return fail(RQ_EINVAL, "rq_dev_aq_lut_wide: lut_mode must be 1 (LSQ) or 2 (CQ)");
+  if (m < 1 || m > 32) return fail(RQ_EUNSUPPORTED, "rq_dev_aq_lut_wide covers 1 <= m <= 32; got m=%d", m);
+  if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "rq_dev_aq_lut_wide: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
+  if (d < 1) return fail(RQ_EINVAL, "rq_dev_aq_lut_wide: d=%d < 1", d);
+  if (nq >= (1LL << 31)) return fail(RQ_EINVAL, "rq_dev_aq_lut_wide: nq=%lld must be below 2^31", (long long)nq);
+  return aq_lut_h16_launch(lut, codebooks, queries, nq, m, h, d, lut_mode, (hipStream_t)stream);
+}
+int rq_dev_linscan_aq_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *codebooks,
+                           const float *queries, const float *dbnorms, int64_t n, int64_t nq, int m, int h, int d, int k,
+                           int lut_mode, uint32_t id_offset, int id_base, void *stream) {
+  return dev_linscan_aq_wide(dists, ids, keys, codes, codebooks, queries, dbnorms, n, nq, m, h, d, k, lut_mode, id_offset, id_base,
+                             (hipStream_t)stream);
+}
+int rq_linscan_lsq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *queries, const float *codebooks,
+                        const float *dbnorms, const float *R, int64_t n, int64_t nq, int m, int h, int d, int k,
+                        int code_base, int id_base) {
+  if (nq > 0 && !dbnorms) return fail(RQ_EINVAL, "rq_linscan_lsq_wide: NULL argument");
+  WideAq aq;
+  aq.lut_mode = LUT_LSQ;
+  aq.dbnorms = dbnorms;
+  return host_linscan_wide("rq_linscan_lsq_wide", dists, ids, codes, codebooks, queries, R, false, n, nq, m, h, d, k, code_base,
+                           id_base, aq);
+}
+int rq_linscan_cq_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *queries, const float *codebooks,
+                       int64_t n, int64_t nq, int m, int h, int d, int k, int code_base, int id_base) {
+  WideAq aq;
+  aq.lut_mode = LUT_CQ;
+  return host_linscan_wide("rq_linscan_cq_wide", dists, ids, codes, codebooks, queries, nullptr, false, n, nq, m, h, d, k,
+                           code_base, id_base, aq);
+}
+int rq_linscan_lsq_cbnorms_wide(float *dists, uint32_t *ids, const int16_t *codes, const float *queries,
+                                const float *codebooks, const float *cbnorms, int hn, const float *R, int64_t n, int64_t nq,
+                                int m, int h, int d, int k, int code_base, int id_base) {
+  if (nq > 0 && !cbnorms) return fail(RQ_EINVAL, "rq_linscan_lsq_cbnorms_wide: NULL argument");
+  WideAq aq;
+  aq.lut_mode = LUT_LSQ;
+  aq.cbnorms = cbnorms;
+  aq.hn = hn;
+  return host_linscan_wide("rq_linscan_lsq_cbnorms_wide", dists, ids, codes, codebooks, queries, R, false, n, nq, m, h, d, k,
+                           code_base, id_base, aq);
 }
 int rq_scan_wide_plan(int m, int h, int *out, int cap) {
   if (!out || cap < 4) return fail(RQ_EINVAL, "rq_scan_wide_plan: out needs 4 ints");

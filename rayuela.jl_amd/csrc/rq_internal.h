@@ -303,7 +303,9 @@ int merge_launch(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t
                  int P, int K, int id_base, hipStream_t stream);
 // ---- ADC scan over 16-bit codes (rq_scan_h16.hip): codes [n][m] int16 zero-based, centers [m][h][d/m] ----
 // every argument check of rq_dev_linscan_wide / rq_linscan_*_wide (`who` names the entry point); no device work
-int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, int d, int k, uint32_t id_offset, int id_base);
+// full_dim: the additive-quantizer entries (codebooks [m * h][d], section 4.20) -- any d >= 1 instead of d % m == 0
+int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, int d, int k, uint32_t id_offset, int id_base,
+                       bool full_dim = false);
 int dev_linscan_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *centers,
                      const float *queries, int64_t n, int64_t nq, int m, int h, int d, int k, uint32_t id_offset, int id_base,
                      hipStream_t stream);
@@ -313,6 +315,12 @@ int lut_h16_launch(float *lut, const float *centers, const float *queries, int64
 int prepare_codes_h16_launch(int16_t *codes, unsigned long long *first_bad, int64_t n, int m, int h, int code_base,
                              hipStream_t stream);
 void scan_h16_plan(int m, int h, int out[4]);             // rq_scan_wide_plan
+// linscan_lsq / linscan_cq over 16-bit codes: codebooks [m * h][d]; lut_mode LUT_LSQ (dbnorms [n]) or LUT_CQ
+int dev_linscan_aq_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *codebooks,
+                        const float *queries, const float *dbnorms, int64_t n, int64_t nq, int m, int h, int d, int k,
+                        int lut_mode, uint32_t id_offset, int id_base, hipStream_t stream);
+int aq_lut_h16_launch(float *lut, const float *codebooks, const float *queries, int64_t nq, int m, int h, int d, int lut_mode,
+                      hipStream_t stream);                // plain [nq][m][h]
 int lut_launch(float *lut, const float *centers, const float *queries, int64_t nq, int m, int sub,
                hipStream_t stream);
 int synth_codes_launch(uint8_t *codes, int64_t n, int m, uint64_t seed, int64_t row0, hipStream_t stream);
@@ -425,11 +433,17 @@ struct DevMem {
 // the Lloyd loop of rq_train_pq on a device-resident X [n][d] (rq_train_host.hip): dC [h * d] and dcodes [n][m] (device) out;
 // the caller holds the DeviceLock.  Overwrites the calling thread's rq_train_profile like rq_train_pq.
 int train_pq_resident(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed);
+// the same for 1 <= h <= RQ_MAX_H16 and zero-based int16 codes: what rq_train_pq_wide runs between its upload and download
+int train_pq_resident_wide(float *dC, int16_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed);
 // ---- database norms of additive-quantizer search (rq_norms.hip) -------------------------------------
 int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
 // norm_codes [n] u8 and / or dbnorms [n] = cbnorms[code] (either may be null); cbnorms [hn <= 256], unsorted
 int quantize_norms_launch(uint8_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
                           hipStream_t stream);
+// the same over int16 codes: codes zero-based and in range, 2 <= h <= RQ_MAX_H16; hn <= RQ_MAX_H16
+int aq_norms_h16_launch(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
+int quantize_norms_h16_launch(int16_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
+                              hipStream_t stream);
 // ---- ERVQ (rq_train.hip: the increment shares update_centers' segment sum; rq_ervq.hip: epilogue and loop) -------------------
 int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
                           int col, int h, int num_cu, hipStream_t stream);

@@ -9,6 +9,9 @@
 //   quantize_norms_kernel first index j minimising fl(fl(norm - cb[j])^2) (strict <: findmin, src/utils.jl:50-55), the
 //                         unsorted codebook of hn <= 256 entries in LDS; optionally the dequantised cb[j] beside the code.
 // The 1-D k-means of get_norms_codebook is train_pq_resident (rq_train_host.hip) with d = m = 1 on the resident norms.
+// The *_wide entries are the same kernels over int16 codes: aq_norms_kernel<int16_t> for
+// 2 <= h <= RQ_MAX_H16, quantize_norms_wide_kernel with the table of hn <= RQ_MAX_H16 entries in dynamic LDS (128 KiB at most)
+// and int16 norm codes, train_pq_resident_wide for the k-means (the byte loop, widened, at hn <= 256 like rq_train_pq_wide).
 #include "rq_internal.h"
 
 #include <vector>
@@ -19,12 +22,13 @@ namespace {
 
 constexpr int NR = 4, NI = 4;   // rows per wavefront and codebooks per step: NR * NI independent gathers hide the L2 latency
 
-__global__ __launch_bounds__(256) void aq_norms_kernel(float *norms, const uint8_t *codes, const float *C, int64_t n, int d,
+template <class Code>
+__global__ __launch_bounds__(256) void aq_norms_kernel(float *norms, const Code *codes, const float *C, int64_t n, int d,
                                                        int m, int h) {
   const int lane = threadIdx.x & 63;
   const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
   if (row0 >= n) return;
-  // lane i holds the codebook row (i * h + b_i < m * h <= 2^14) of each of the wavefront's rows (m <= 64), lanes past m row 0;
+  // lane i holds the codebook row (i * h + b_i < m * h <= 2^21) of each of the wavefront's rows (m <= 64), lanes past m row 0;
   // a row past n repeats row n - 1 and is not stored
   int ent[NR];
 #pragma unroll
@@ -74,21 +78,39 @@ __global__ __launch_bounds__(256) void aq_norms_kernel(float *norms, const uint8
     if (lane == r && row0 + r < n) norms[row0 + r] = acc[r];
 }
 
+// the search of one norm over cb [hn] in LDS: first index of the smallest fl(fl(v - cb[j])^2), strict <
+__device__ __forceinline__ int nearest_norm(const float *cb, int hn, float v) {
+  float df = v - cb[0];
+  float best = df * df;
+  int bj = 0;
+  for (int j = 1; j < hn; ++j) {
+    df = v - cb[j];
+    const float e = df * df;
+    if (e < best) { best = e; bj = j; }
+  }
+  return bj;
+}
+
+// hn <= RQ_MAX_H16: the table in dynamic LDS (4 hn bytes), int16 codes
+__global__ __launch_bounds__(256) void quantize_norms_wide_kernel(int16_t *norm_codes, float *dbnorms, const float *norms,
+                                                                  const float *cbnorms, int64_t n, int hn) {
+  extern __shared__ __attribute__((aligned(16))) float cbw[];
+  for (int j = threadIdx.x; j < hn; j += 256) cbw[j] = cbnorms[j];
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int bj = nearest_norm(cbw, hn, norms[i]);
+    if (norm_codes) norm_codes[i] = (int16_t)bj;
+    if (dbnorms) dbnorms[i] = cbw[bj];
+  }
+}
+
 __global__ __launch_bounds__(256) void quantize_norms_kernel(uint8_t *norm_codes, float *dbnorms, const float *norms,
                                                              const float *cbnorms, int64_t n, int hn) {
   __shared__ float cb[256];
   if ((int)threadIdx.x < hn) cb[threadIdx.x] = cbnorms[threadIdx.x];
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float v = norms[i];
-    float df = v - cb[0];
-    float best = df * df;
-    int bj = 0;
-    for (int j = 1; j < hn; ++j) {
-      df = v - cb[j];
-      const float e = df * df;
-      if (e < best) { best = e; bj = j; }
-    }
+    const int bj = nearest_norm(cb, hn, norms[i]);
     if (norm_codes) norm_codes[i] = (uint8_t)bj;
     if (dbnorms) dbnorms[i] = cb[bj];
   }
@@ -107,19 +129,51 @@ int norms_check_hn(const char *who, int hn) {
   return RQ_OK;
 }
 
+int norms_check_wide(const char *who, int64_t n, int d, int m, int h, int hn, int code_base) {
+  if (m < 1 || m > 64) return fail(RQ_EINVAL, "%s: m=%d outside 1..64", who, m);
+  if (h < 2 || h > RQ_MAX_H16) return fail(RQ_EINVAL, "%s: h=%d outside 2..%d", who, h, RQ_MAX_H16);
+  if (hn < 1 || hn > RQ_MAX_H16) return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, hn, RQ_MAX_H16);
+  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
+  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  return RQ_OK;
+}
+
 }  // namespace
 
-int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+template <class Code>
+static int aq_norms_run(float *norms, const Code *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
   if (n <= 0) return RQ_OK;
   // one wavefront per NR rows, in row slices of at most LAUNCH_MAX_THREADS threads (2^27 rows)
   const int64_t rows = LAUNCH_MAX_THREADS / 64 * NR;
   for (int64_t r0 = 0; r0 < n; r0 += rows) {
     const int64_t nr = std::min(rows, n - r0);
     const int64_t waves = (nr + NR - 1) / NR;
-    hipLaunchKernelGGL(aq_norms_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, norms + r0,
+    hipLaunchKernelGGL(aq_norms_kernel<Code>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, norms + r0,
                        codes + (size_t)r0 * m, C, nr, d, m, h);
     RQ_HIP(hipGetLastError());
   }
+  return RQ_OK;
+}
+
+int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+  return aq_norms_run(norms, codes, C, n, d, m, h, stream);
+}
+
+int aq_norms_h16_launch(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+  return aq_norms_run(norms, codes, C, n, d, m, h, stream);
+}
+
+int quantize_norms_h16_launch(int16_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
+                              hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  const size_t lds = (size_t)hn * 4;         // hn <= RQ_MAX_H16: 128 KiB at most
+  if (lds > 64 * 1024)
+    RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(quantize_norms_wide_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(quantize_norms_wide_kernel, dim3(grid), dim3(256), lds, stream, norm_codes, dbnorms, norms, cbnorms, n, hn);
+  RQ_HIP(hipGetLastError());
   return RQ_OK;
 }
 
@@ -140,6 +194,23 @@ struct NormsOnDevice {
     RQ_HIP(hipMemcpy(codes.p, hcodes, (size_t)n * m, hipMemcpyHostToDevice));
     RQ_HIP(hipMemcpy(C.p, hC, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
     return aq_norms_launch(norms.as<float>(), codes.as<uint8_t>(), C.as<float>(), n, d, m, h, nullptr);
+  }
+};
+
+// the same for int16 codes: made zero-based and checked against [0, h) on the device before any other work
+struct NormsOnDeviceWide {
+  DevMem codes, C, norms, bad;
+  int run(const char *who, const int16_t *hcodes, const float *hC, int64_t n, int d, int m, int h, int code_base) {
+    RQ_TRY(codes.alloc((size_t)n * m * 2)); RQ_TRY(C.alloc((size_t)m * h * d * 4)); RQ_TRY(norms.alloc((size_t)n * 4));
+    RQ_TRY(bad.alloc(8));
+    RQ_HIP(hipMemcpy(codes.p, hcodes, (size_t)n * m * 2, hipMemcpyHostToDevice));
+    RQ_TRY(prepare_codes_h16_launch(codes.as<int16_t>(), bad.as<unsigned long long>(), n, m, h, code_base, nullptr));
+    unsigned long long first_bad = 0;
+    RQ_HIP(hipMemcpy(&first_bad, bad.p, 8, hipMemcpyDeviceToHost));
+    if (first_bad != ~0ull)
+      return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d]", who, first_bad, code_base, h - 1 + code_base);
+    RQ_HIP(hipMemcpy(C.p, hC, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
+    return aq_norms_h16_launch(norms.as<float>(), codes.as<int16_t>(), C.as<float>(), n, d, m, h, nullptr);
   }
 };
 
@@ -223,6 +294,92 @@ int rq_get_norms_codebook(uint8_t *norm_codes, float *cbnorms, float *norms_out,
   RQ_HIP(hipDeviceSynchronize());
   RQ_HIP(hipMemcpy(cbnorms, dcb.p, (size_t)hn * 4, hipMemcpyDeviceToHost));
   RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n, hipMemcpyDeviceToHost));
+  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+// ---- the same five over int16 codes: 2 <= h <= RQ_MAX_H16, 1 <= hn <= RQ_MAX_H16 ---------------------
+int rq_dev_aq_norms_wide(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
+  const char *who = "rq_dev_aq_norms_wide";
+  RQ_TRY(norms_check_wide(who, n, d, m, h, 1, 0));
+  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "%s: null pointer", who);
+  if (n == 0) return RQ_OK;
+  if (((uintptr_t)codes & 1) != 0) return fail(RQ_EINVAL, "%s: codes must be 2-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  // every code in [0, h): one word, read back before any other work is queued (code_base 0: the codes are only read)
+  void *wf = nullptr;
+  RQ_TRY(workspace(WS_TMP, 256, &wf, s));
+  RQ_TRY(prepare_codes_h16_launch(const_cast<int16_t *>(codes), (unsigned long long *)wf, n, m, h, 0, s));
+  unsigned long long first_bad = 0;
+  RQ_HIP(hipMemcpyAsync(&first_bad, wf, 8, hipMemcpyDeviceToHost, s));
+  RQ_HIP(hipStreamSynchronize(s));
+  if (first_bad != ~0ull) return fail(RQ_EINVAL, "%s: row %llu holds a code outside [0, %d]", who, first_bad, h - 1);
+  return aq_norms_h16_launch(norms, codes, C, n, d, m, h, s);
+}
+
+int rq_aq_norms_wide(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, int code_base) {
+  const char *who = "rq_aq_norms_wide";
+  RQ_TRY(norms_check_wide(who, n, d, m, h, 1, code_base));
+  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "%s: null pointer", who);
+  if (n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDeviceWide dv;
+  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(norms, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+int rq_dev_quantize_norms_wide(int16_t *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n,
+                               int hn, void *stream) {
+  const char *who = "rq_dev_quantize_norms_wide";
+  RQ_TRY(norms_check_wide(who, n, 1, 1, 2, hn, 0));
+  if (!cbnorms || (n > 0 && (!norm_codes || !norms))) return fail(RQ_EINVAL, "%s: null pointer", who);
+  return quantize_norms_h16_launch(norm_codes, dbnorms_out, norms, cbnorms, n, hn, (hipStream_t)stream);
+}
+
+int rq_quantize_norms_wide(int16_t *norm_codes, float *norms_out, const int16_t *codes, const float *C, const float *cbnorms,
+                           int64_t n, int d, int m, int h, int hn, int code_base) {
+  const char *who = "rq_quantize_norms_wide";
+  RQ_TRY(norms_check_wide(who, n, d, m, h, hn, code_base));
+  if (!cbnorms || (n > 0 && (!norm_codes || !codes || !C))) return fail(RQ_EINVAL, "%s: null pointer", who);
+  if (n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDeviceWide dv;
+  DevMem dcb, dnc;
+  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n * 2));
+  RQ_HIP(hipMemcpy(dcb.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
+  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
+  RQ_TRY(quantize_norms_h16_launch(dnc.as<int16_t>(), nullptr, dv.norms.as<float>(), dcb.as<float>(), n, hn, nullptr));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n * 2, hipMemcpyDeviceToHost));
+  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+int rq_get_norms_codebook_wide(int16_t *norm_codes, float *cbnorms, float *norms_out, const int16_t *codes, const float *C,
+                               int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed, int code_base) {
+  const char *who = "rq_get_norms_codebook_wide";
+  RQ_TRY(norms_check_wide(who, n, d, m, h, hn, code_base));
+  if (niter < 0) return fail(RQ_EINVAL, "%s: niter=%d < 0", who, niter);
+  if (n < hn) return fail(RQ_EINVAL, "%s: fewer rows (%lld) than norm codebook entries (%d)", who, (long long)n, hn);
+  if (!norm_codes || !cbnorms || !codes || !C) return fail(RQ_EINVAL, "%s: null pointer", who);
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDeviceWide dv;
+  DevMem dcb, dnc;
+  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n * 2));
+  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_TRY(train_pq_resident_wide(dcb.as<float>(), dnc.as<int16_t>(), dv.norms.as<float>(), n, 1, 1, hn, niter, seed));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(cbnorms, dcb.p, (size_t)hn * 4, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n * 2, hipMemcpyDeviceToHost));
   if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return RQ_OK;
 }

@@ -7,9 +7,13 @@
 //                           of a query group in LDS where it fits 128 KiB, else gathered from the global table through L2;
 //                           a NaN distance and a code outside [0, h) give KEY_MAX (the index is clamped, never used raw)
 //   3. sel_run              the select -> compact -> sort -> unpack chain of rq_bulk.hip on those keys
+// The additive-quantizer scan over 16-bit codes (linscan_lsq / linscan_cq) is the same pipeline with the
+// full-dimensional tables of aq_lut_h16_kernel (rq_aq_lut_h16.h) in step 1 and, for LSQ, the row's norm added last in step 2
+// (adc_keys_h16_kernel<.., HAS_NORM = true>): deps/src/linscan_aqd_pairwise_byte.cpp:14-94, :97-176 with int16 codes.
 // per batch of queries, everything on the caller's stream; the batch is sized so that keys + tables + the chain's scratch fit
 // the BULK_SCRATCH_BYTES budget of WS_BULK.
 #include "rq_internal.h"
+#include "rq_aq_lut_h16.h"
 #include "rq_topk.h"
 
 namespace rq {
@@ -47,23 +51,6 @@ void scan_h16_plan(int m, int h, int out[4]) {
   out[2] = p.qg;
   out[3] = (int)p.lds_bytes;
 }
-
-template <int QPG> struct H16Vec;
-template <> struct H16Vec<4> {
-  using type = float4;
-  static __device__ __forceinline__ type make(const float *a) { return make_float4(a[0], a[1], a[2], a[3]); }
-  static __device__ __forceinline__ float get(const type &v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-};
-template <> struct H16Vec<2> {
-  using type = float2;
-  static __device__ __forceinline__ type make(const float *a) { return make_float2(a[0], a[1]); }
-  static __device__ __forceinline__ float get(const type &v, int i) { return i == 0 ? v.x : v.y; }
-};
-template <> struct H16Vec<1> {
-  using type = float;
-  static __device__ __forceinline__ type make(const float *a) { return a[0]; }
-  static __device__ __forceinline__ float get(const type &v, int) { return v; }
-};
 
 // ---- tables ---------------------------------------------------------------------------------------------------------------
 // One thread per (query group, entry e = k h + r): lut[(g0 + g) * gstride + e * QPG + j] for the QPG queries of group g0 + g (a
@@ -133,10 +120,43 @@ int lut_h16_launch(float *lut, const float *centers, const float *queries, int64
   return lut_h16_groups<1>(lut, centers, queries, nq, m, h, sub, (size_t)m * h, stream);
 }
 
+// the tables of the additive-quantizer scan (rq_aq_lut_h16.h) for queries [0, nq) in groups of QPG: codebooks [m * h][d]
+template <int QPG, int MODE>
+static int aq_lut_h16_mode(float *tab, const float *codebooks, const float *queries, int64_t nq, int m, int h, int d,
+                           size_t gstride, hipStream_t stream) {
+  const int64_t ngroups = (nq + QPG - 1) / QPG;
+  const int64_t E = (int64_t)m * h;
+  const int64_t tiles = (nq + AQ_LUT_TQ - 1) / AQ_LUT_TQ;
+  const int64_t ex = (E + AQ_LUT_THREADS - 1) / AQ_LUT_THREADS;
+  const int vec4 = (d & 3) == 0 && ((uintptr_t)codebooks & 15) == 0;
+  // tiles per launch: fewer than LAUNCH_MAX_THREADS work-items, and a grid.y the hardware takes
+  const int64_t per = std::max<int64_t>(1, std::min<int64_t>(65535, LAUNCH_MAX_THREADS / (ex * AQ_LUT_THREADS)));
+  for (int64_t t0 = 0; t0 < tiles; t0 += per) {
+    const int64_t nt = std::min(per, tiles - t0);
+    hipLaunchKernelGGL((aq_lut_h16_kernel<QPG, MODE>), dim3((uint32_t)ex, (uint32_t)nt), dim3(AQ_LUT_THREADS), 0, stream, tab,
+                       codebooks, queries, (uint32_t)nq, (uint32_t)ngroups, (uint32_t)t0, (uint32_t)E, d, gstride, vec4);
+    RQ_HIP(hipGetLastError());
+  }
+  return RQ_OK;
+}
+
+template <int QPG>
+static int aq_lut_h16_groups(float *tab, const float *codebooks, const float *queries, int64_t nq, int m, int h, int d,
+                             size_t gstride, int lut_mode, hipStream_t stream) {
+  if (lut_mode == LUT_LSQ) return aq_lut_h16_mode<QPG, LUT_LSQ>(tab, codebooks, queries, nq, m, h, d, gstride, stream);
+  return aq_lut_h16_mode<QPG, LUT_CQ>(tab, codebooks, queries, nq, m, h, d, gstride, stream);
+}
+
+int aq_lut_h16_launch(float *lut, const float *codebooks, const float *queries, int64_t nq, int m, int h, int d, int lut_mode,
+                      hipStream_t stream) {
+  return aq_lut_h16_groups<1>(lut, codebooks, queries, nq, m, h, d, (size_t)m * h, lut_mode, stream);
+}
+
 // ---- distances -> keys ----------------------------------------------------------------------------------------------------
 struct H16KeyParams {
   const int16_t *codes;     // [n][m], 2-byte aligned at least
   const float *tab;         // [groups][gstride]: entry e of group g holds QPG queries
+  const float *dbnorms;     // [n], HAS_NORM only: added to the row's sum last (linscan_aqd_pairwise_byte.cpp:74)
   uint64_t *keys;           // [nb][n]
   size_t gstride;
   uint32_t n, nb;
@@ -189,8 +209,9 @@ __device__ __forceinline__ bool h16_row(float *acc, const unsigned char *rp, int
 }
 
 // blockIdx.y: the group of QPG queries, blockIdx.x: a range of rows.  IN_LDS: the group's table is copied to LDS 16 bytes at a
-// time and gathered there with one ds_read of 4 * QPG bytes per code; else the gathers go to the global table.
-template <int QPG, bool IN_LDS>
+// time and gathered there with one ds_read of 4 * QPG bytes per code; else the gathers go to the global table.  HAS_NORM (LSQ):
+// acc = acc + dbnorms[row] after the m entries, one rounding; a NaN norm makes the row no neighbour like any NaN distance.
+template <int QPG, bool IN_LDS, bool HAS_NORM = false>
 __global__ __launch_bounds__(1024) void adc_keys_h16_kernel(H16KeyParams p) {
   using V = H16Vec<QPG>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -220,6 +241,11 @@ __global__ __launch_bounds__(1024) void adc_keys_h16_kernel(H16KeyParams p) {
     else if (p.vec == 8) bad = h16_row<QPG, IN_LDS, 8>(acc, rp, p.m, (uint32_t)p.h, lt, gt);
     else if (p.vec == 4) bad = h16_row<QPG, IN_LDS, 4>(acc, rp, p.m, (uint32_t)p.h, lt, gt);
     else bad = h16_row<QPG, IN_LDS, 2>(acc, rp, p.m, (uint32_t)p.h, lt, gt);
+    if (HAS_NORM) {
+      const float nrm = p.dbnorms[row];
+#pragma unroll
+      for (int q = 0; q < QPG; ++q) acc[q] = acc[q] + nrm;
+    }
     const uint32_t kid = row + p.id_offset;
 #pragma unroll
     for (int q = 0; q < QPG; ++q)
@@ -268,12 +294,14 @@ static int64_t h16_batch(const H16Plan &pl, int64_t nq, int64_t n, int k) {
   return lo;
 }
 
-int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, int d, int k, uint32_t id_offset, int id_base) {
+int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, int d, int k, uint32_t id_offset, int id_base,
+                       bool full_dim) {
   if (null_arg) return fail(RQ_EINVAL, "%s: NULL argument", who);
   if (id_base != 0 && id_base != 1) return fail(RQ_EINVAL, "%s: id_base must be 0 or 1; got %d", who, id_base);
   if (m < 1 || m > 32) return fail(RQ_EUNSUPPORTED, "%s covers 1 <= m <= 32; got m=%d", who, m);
   if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "%s scans Int16 codes: 1 <= h <= %d; got h=%d", who, RQ_MAX_H16, h);
-  if (d < m || d % m != 0)
+  if (full_dim && d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
+  if (!full_dim && (d < m || d % m != 0))
     return fail(RQ_EINVAL, "%s needs d %% m == 0 (src/Linscan.jl:23 Cint(d/m)); got d=%d m=%d", who, d, m);
   if (n < 1 || n >= (1LL << 31)) return fail(RQ_EINVAL, "%s: n=%lld must be in [1, 2^31)", who, (long long)n);
   if (k < 1 || k > n)
@@ -282,10 +310,11 @@ int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, 
   return RQ_OK;
 }
 
-template <int QPG, bool IN_LDS>
+// lut_mode LUT_PQ: centers [m][h][d/m]; LUT_LSQ / LUT_CQ: `centers` are codebooks [m * h][d], dbnorms [n] for LUT_LSQ
+template <int QPG, bool IN_LDS, bool HAS_NORM = false>
 static int h16_scan(const H16Plan &pl, float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *centers,
                     const float *queries, int64_t n, int64_t nq, int m, int h, int d, int k, uint32_t id_offset, int id_base,
-                    int num_cu, hipStream_t stream) {
+                    int num_cu, hipStream_t stream, int lut_mode = LUT_PQ, const float *dbnorms = nullptr) {
   const int64_t nbmax = h16_batch(pl, nq, n, k);
   if (nbmax < 1)
     return fail_hip(hipErrorOutOfMemory, "wide scan: one query needs more than the BULK_SCRATCH_BYTES budget of scratch",
@@ -293,9 +322,9 @@ static int h16_scan(const H16Plan &pl, float *dists, uint32_t *ids, uint64_t *ke
   void *ws = nullptr;
   RQ_TRY(workspace(WS_BULK, h16_scan_bytes(pl, nbmax, n, k), &ws, stream));
   char name[64];
-  snprintf(name, sizeof(name), "adc_keys_h16_kernel<%d, %s>", QPG, IN_LDS ? "true" : "false");
+  snprintf(name, sizeof(name), "adc_keys_h16_kernel<%d, %s%s>", QPG, IN_LDS ? "true" : "false", HAS_NORM ? ", true" : "");
   set_last_scan_kernel(name);
-  void (*kern)(H16KeyParams) = adc_keys_h16_kernel<QPG, IN_LDS>;
+  void (*kern)(H16KeyParams) = adc_keys_h16_kernel<QPG, IN_LDS, HAS_NORM>;
   if (IN_LDS)
     RQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)pl.lds_bytes));
@@ -314,12 +343,14 @@ static int h16_scan(const H16Plan &pl, float *dists, uint32_t *ids, uint64_t *ke
     p.keys = (uint64_t *)at; at += align256((size_t)nb * n * 8);
     float *tab = (float *)at; at += align256((size_t)gy * pl.gstride * 4);
     p.tab = tab;
+    p.dbnorms = dbnorms;
     p.gstride = pl.gstride;
     p.n = (uint32_t)n; p.nb = (uint32_t)nb;
     p.m = m; p.h = h; p.vec = vec;
     p.id_offset = id_offset;
     p.rows_per_wg = (uint32_t)((n + gx - 1) / gx);
-    RQ_TRY(lut_h16_groups<QPG>(tab, centers, queries + (size_t)q0 * d, nb, m, h, d / m, pl.gstride, stream));
+    if (lut_mode == LUT_PQ) RQ_TRY(lut_h16_groups<QPG>(tab, centers, queries + (size_t)q0 * d, nb, m, h, d / m, pl.gstride, stream));
+    else RQ_TRY(aq_lut_h16_groups<QPG>(tab, centers, queries + (size_t)q0 * d, nb, m, h, d, pl.gstride, lut_mode, stream));
     hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(threads), pl.lds_bytes, stream, p);
     RQ_HIP(hipGetLastError());
     BulkSel s;
@@ -351,6 +382,35 @@ int dev_linscan_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t 
   DeviceLock launch_lock;
   const H16Plan pl = h16_plan(m, h);
 #define RQ_H16_ARGS pl, dists, ids, keys, codes, centers, queries, n, nq, m, h, d, k, id_offset, id_base, di.num_cu, stream
+  if (!pl.in_lds) return h16_scan<4, false>(RQ_H16_ARGS);
+  if (pl.qpg == 4) return h16_scan<4, true>(RQ_H16_ARGS);
+  if (pl.qpg == 2) return h16_scan<2, true>(RQ_H16_ARGS);
+  return h16_scan<1, true>(RQ_H16_ARGS);
+#undef RQ_H16_ARGS
+}
+
+// linscan_lsq / linscan_cq over one resident shard of 16-bit codes: codebooks [m * h][d] full-dimensional
+int dev_linscan_aq_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *codebooks,
+                        const float *queries, const float *dbnorms, int64_t n, int64_t nq, int m, int h, int d, int k,
+                        int lut_mode, uint32_t id_offset, int id_base, hipStream_t stream) {
+  const char *who = "rq_dev_linscan_aq_wide";
+  if (nq <= 0) return RQ_OK;
+  if (lut_mode != LUT_LSQ && lut_mode != LUT_CQ) return fail(RQ_EINVAL, "%s: lut_mode must be 1 (LSQ) or 2 (CQ)", who);
+  RQ_TRY(linscan_wide_check(who, !codes || !codebooks || !queries || (!keys && (!dists || !ids)) || (lut_mode == LUT_LSQ && !dbnorms),
+                            n, m, h, d, k, id_offset, id_base, true));
+  if (((uintptr_t)codes & 1) != 0 || ((uintptr_t)codebooks & 3) != 0 || ((uintptr_t)queries & 3) != 0 || ((uintptr_t)dbnorms & 3) != 0)
+    return fail(RQ_EINVAL, "%s: codes must be 2-byte aligned, codebooks, queries and dbnorms 4-byte aligned", who);
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock launch_lock;
+  const H16Plan pl = h16_plan(m, h);
+#define RQ_H16_ARGS pl, dists, ids, keys, codes, codebooks, queries, n, nq, m, h, d, k, id_offset, id_base, di.num_cu, stream, lut_mode
+  if (lut_mode == LUT_LSQ) {
+    if (!pl.in_lds) return h16_scan<4, false, true>(RQ_H16_ARGS, dbnorms);
+    if (pl.qpg == 4) return h16_scan<4, true, true>(RQ_H16_ARGS, dbnorms);
+    if (pl.qpg == 2) return h16_scan<2, true, true>(RQ_H16_ARGS, dbnorms);
+    return h16_scan<1, true, true>(RQ_H16_ARGS, dbnorms);
+  }
   if (!pl.in_lds) return h16_scan<4, false>(RQ_H16_ARGS);
   if (pl.qpg == 4) return h16_scan<4, true>(RQ_H16_ARGS);
   if (pl.qpg == 2) return h16_scan<2, true>(RQ_H16_ARGS);

@@ -412,6 +412,19 @@ int train_pq_resident(float *dC, uint8_t *dcodes, const float *dX, int64_t n, in
   return train_pq_loop(dC, dcodes, dX, n, d, m, h, niter, seed, di, prof);
 }
 
+int train_pq_resident_wide(float *dC, int16_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed) {
+  if (n < 1 || d < m || m < 1 || m > 32 || h < 1 || h > RQ_MAX_H16 || niter < 0 || n < h)
+    return fail(RQ_EINVAL, "train: n=%lld d=%d m=%d h=%d niter=%d", (long long)n, d, m, h, niter);
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  TrainProf prof;
+  if (h > 256) return train_pq_loop(dC, dcodes, dX, n, d, m, h, niter, seed, di, prof);
+  DevMem d8;            // h <= 256: the byte loop, widened -- the bits of train_pq_resident
+  RQ_TRY(d8.alloc((size_t)n * m));
+  RQ_TRY(train_pq_loop(dC, d8.as<uint8_t>(), dX, n, d, m, h, niter, seed, di, prof));
+  return convert_codes_launch(dcodes, d8.as<uint8_t>(), n * m, 0, nullptr);
+}
+
 // train_pq (src/PQ.jl:68-99) on host pointers: upload, the Lloyd loop, qerror_pq of the result, download.  The arguments are
 // checked by the entry points; codes come back as int16 + code_base.
 template <class Code>

@@ -294,6 +294,44 @@ def linscan_aq(codes, codebooks, queries, k, dbnorms=None, id_offset=0, id_base=
     return dists, ids
 
 
+def linscan_aq_wide(codes, codebooks, queries, k, dbnorms=None, id_offset=0, id_base=0, want_keys=False, out=None):
+    """ADC scan for additive quantizers over one resident shard of 16-bit codes (rq_dev_linscan_aq_wide): codes (n, m) int16
+    zero-based, codebooks (m, h, d) or (m*h, d) full-dimensional with 1 <= h <= 32767; dbnorms given -> LSQ tables + per-row norm,
+    else CQ tables.  Returns (dists, ids), or the packed sorted keys (nq, k) (int64 view of the uint64 keys) when want_keys."""
+    n, m = codes.shape
+    nq, d = queries.shape
+    h = codebooks.numel() // (m * d)
+    dev = queries.device
+    mode = 1 if dbnorms is not None else 2
+    nrm = None if dbnorms is None else _chk(dbnorms, torch.float32, "dbnorms")
+    if want_keys:
+        dists = ids = None
+        keys = torch.empty((nq, k), dtype=torch.int64, device=dev) if out is None else out
+    elif out is None:
+        keys = None
+        dists = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    else:
+        keys = None
+        dists, ids = out
+    _lib.check(_lib.lib().rq_dev_linscan_aq_wide(
+        None if dists is None else dists.data_ptr(), None if ids is None else ids.data_ptr(),
+        None if keys is None else keys.data_ptr(), _chk(codes, torch.int16, "codes"), _chk(codebooks, torch.float32, "codebooks"),
+        _chk(queries, torch.float32, "queries"), nrm, n, nq, m, h, d, k, mode, id_offset, id_base, _stream()))
+    return keys if want_keys else (dists, ids)
+
+
+def aq_lut_wide(codebooks, queries, lsq=True):
+    """Per-query tables lut (nq, m, h) of full-dimensional codebooks (m, h, d): -2<q, c> (lsq) or |q - c|^2, any 1 <= h <= 32767
+    (rq_dev_aq_lut_wide); test aid."""
+    m, h, d = codebooks.shape
+    nq = queries.shape[0]
+    lut = torch.empty((nq, m, h), dtype=torch.float32, device=queries.device)
+    _lib.check(_lib.lib().rq_dev_aq_lut_wide(lut.data_ptr(), _chk(codebooks, torch.float32, "codebooks"),
+                                             _chk(queries, torch.float32, "queries"), nq, m, h, d, 1 if lsq else 2, _stream()))
+    return lut
+
+
 def merge_topk(keys_in, k, id_base=0, out=None):
     """keys_in [nq][P][k] int64 (uint64 bit patterns) -> (dists [nq][k], ids [nq][k])."""
     nq, P, kk = keys_in.shape
@@ -470,6 +508,28 @@ def quantize_norms(norms, cbnorms, out=None, dbnorms=None):
     _lib.check(_lib.lib().rq_dev_quantize_norms(_chk(out, torch.uint8, "norm_codes"), _chk(dbnorms, torch.float32, "dbnorms"),
                                                 _chk(norms, torch.float32, "norms"), _chk(cbnorms, torch.float32, "cbnorms"),
                                                 n, cbnorms.shape[0], _stream()))
+    return out, dbnorms
+
+
+def aq_norms_wide(codes, C, out=None):
+    """aq_norms over int16 zero-based codes and codebooks C (m, h, d) with 2 <= h <= 32767 (rq_dev_aq_norms_wide)."""
+    n, m = codes.shape
+    _, h, d = C.shape
+    out = torch.empty((n,), dtype=torch.float32, device=codes.device) if out is None else out
+    _lib.check(_lib.lib().rq_dev_aq_norms_wide(_chk(out, torch.float32, "norms"), _chk(codes, torch.int16, "codes"),
+                                               _chk(C, torch.float32, "C"), n, d, m, h, _stream()))
+    return out
+
+
+def quantize_norms_wide(norms, cbnorms, out=None, dbnorms=None):
+    """quantize_norms with a table of up to 32767 entries: (norm codes (n,) int16 zero-based, dbnorms (n,) = cbnorms[code])
+    (rq_dev_quantize_norms_wide)."""
+    n = norms.shape[0]
+    out = torch.empty((n,), dtype=torch.int16, device=norms.device) if out is None else out
+    dbnorms = torch.empty((n,), dtype=torch.float32, device=norms.device) if dbnorms is None else dbnorms
+    _lib.check(_lib.lib().rq_dev_quantize_norms_wide(_chk(out, torch.int16, "norm_codes"), _chk(dbnorms, torch.float32, "dbnorms"),
+                                                     _chk(norms, torch.float32, "norms"),
+                                                     _chk(cbnorms, torch.float32, "cbnorms"), n, cbnorms.shape[0], _stream()))
     return out, dbnorms
 
 

@@ -109,23 +109,28 @@ def _check_norms_arg(norms):
 def _search_base(B, C, h, seed, B_base, Xq, knn, norms, norms_niter=25):
     """The search leg over an encoded base: norms codebook of the training codes -> quantised norms of the base -> linscan_lsq.
     norms_niter: the k-means iterations of the device path; 25 is what the host helper runs, so that the two paths of the RVQ,
-    ERVQ and SR drivers differ in the rounding of the norms alone."""
-    from .Linscan import linscan_lsq, linscan_lsq_cbnorms
+    ERVQ and SR drivers differ in the rounding of the norms alone.  h > 256 (16-bit codes, the RVQ drivers): the same leg through
+    linscan_lsq_u16 / linscan_lsq_cbnorms_u16 and the *_wide norm entries."""
+    from . import Linscan
     from .utils import get_norms_codebook
     d = Xq.shape[1]
     R = np.eye(d, dtype=np.float32)
+    wide = h > 256      # 16-bit codes: the *_u16 scans; the codes are passed one-based in a dtype those read as one-based
+    B_scan = np.asarray(B_base).astype(np.int32) if wide else B_base
     if norms == "device":
         _, norms_C = get_norms_codebook(B, C, norms_niter, seed=seed)
-        return linscan_lsq_cbnorms(B_base, Xq, C, norms_C, R, knn)
+        scan = Linscan.linscan_lsq_cbnorms_u16 if wide else Linscan.linscan_lsq_cbnorms
+        return scan(B_scan, Xq, C, norms_C, R, knn)
     _, norms_C = _norms_codebook(B, C, h, seed=seed)
     B_base_norms, _ = _quantize_norms(B_base, C, norms_C)
     db_norms = norms_C[B_base_norms - 1].astype(np.float32)
-    return linscan_lsq(B_base, Xq, C, db_norms, R, knn)
+    scan = Linscan.linscan_lsq_u16 if wide else Linscan.linscan_lsq
+    return scan(B_scan, Xq, C, db_norms, R, knn)
 
 
 def _search_train(B, C, h, seed, Xq, knn, norms, norms_niter=25):
     """The search leg of the query-base drivers: the k-means' own assignments of the training codes are their quantised norms."""
-    from .Linscan import linscan_lsq
+    from . import Linscan
     from .utils import get_norms_codebook
     d = Xq.shape[1]
     if norms == "device":
@@ -133,7 +138,9 @@ def _search_train(B, C, h, seed, Xq, knn, norms, norms_niter=25):
     else:
         norms_B, norms_C = _norms_codebook(B, C, h, seed=seed)
     db_norms = norms_C[norms_B - 1].astype(np.float32)
-    return linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    if h > 256:         # 16-bit codes, passed one-based in a dtype linscan_lsq_u16 reads as one-based
+        return Linscan.linscan_lsq_u16(np.asarray(B).astype(np.int32), Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
+    return Linscan.linscan_lsq(B, Xq, C, db_norms, np.eye(d, dtype=np.float32), knn)
 
 
 def _qerror_aq(X, B, C):

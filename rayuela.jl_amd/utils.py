@@ -62,7 +62,8 @@ def cat_codebooks(C):
 
 
 def _aq_args(B, C):
-    """(zero-based uint8 codes (n, m), codebooks (m, h, d)) of one-based integer codes B and an m-long list of (h, d) codebooks."""
+    """(zero-based codes (n, m), codebooks (m, h, d)) of one-based integer codes B and an m-long list of (h, d) codebooks; the
+    codes are uint8, or int16 when h > 256 (check_wide_h: the *_wide entry points)."""
     Cs = np.ascontiguousarray(np.stack([_as_f32(c, "C[i]") for c in C]))
     B = np.asarray(B)
     if not np.issubdtype(B.dtype, np.integer):
@@ -72,7 +73,7 @@ def _aq_args(B, C):
         raise ValueError("B must be (n, m) with m = %d codebooks; got %s" % (m, B.shape))
     if B.size and (B.min() < 1 or B.max() > h):
         raise ValueError("codes must be in 1..%d" % h)
-    return np.ascontiguousarray(B.astype(np.int64) - 1, dtype=np.uint8), Cs
+    return np.ascontiguousarray(B.astype(np.int64) - 1, dtype=np.int16 if check_wide_h(h) else np.uint8), Cs
 
 
 def aq_norms(B, C):
@@ -82,7 +83,10 @@ def aq_norms(B, C):
     n = codes.shape[0]
     m, h, d = Cs.shape
     norms = np.empty(n, dtype=np.float32)
-    _lib.check(_lib.lib().rq_aq_norms(norms.ctypes.data, codes.ctypes.data, Cs.ctypes.data, n, d, m, h))
+    if codes.dtype == np.int16:
+        _lib.check(_lib.lib().rq_aq_norms_wide(norms.ctypes.data, codes.ctypes.data, Cs.ctypes.data, n, d, m, h, 0))
+    else:
+        _lib.check(_lib.lib().rq_aq_norms(norms.ctypes.data, codes.ctypes.data, Cs.ctypes.data, n, d, m, h))
     return norms
 
 
@@ -98,26 +102,35 @@ def get_norms_codebook(B, C, niter=100, seed=0):
     codes, Cs = _aq_args(B, C)
     n = codes.shape[0]
     m, h, d = Cs.shape
-    nc = np.empty(n, dtype=np.uint8)
+    nc = np.empty(n, dtype=codes.dtype)
     cb = np.empty(h, dtype=np.float32)
-    _lib.check(_lib.lib().rq_get_norms_codebook(nc.ctypes.data, cb.ctypes.data, None, codes.ctypes.data, Cs.ctypes.data, n, d,
-                                                m, h, h, int(niter), int(seed) & ((1 << 64) - 1)))
+    if codes.dtype == np.int16:         # h > 256: int16 codes and a norms codebook of h entries (rq_get_norms_codebook_wide)
+        _lib.check(_lib.lib().rq_get_norms_codebook_wide(nc.ctypes.data, cb.ctypes.data, None, codes.ctypes.data, Cs.ctypes.data,
+                                                         n, d, m, h, h, int(niter), int(seed) & ((1 << 64) - 1), 0))
+    else:
+        _lib.check(_lib.lib().rq_get_norms_codebook(nc.ctypes.data, cb.ctypes.data, None, codes.ctypes.data, Cs.ctypes.data, n, d,
+                                                    m, h, h, int(niter), int(seed) & ((1 << 64) - 1)))
     return nc.astype(np.int64) + 1, cb
 
 
 def quantize_norms(B, C, cbnorms):
     """quantize_norms(B, C, cbnorms) -> dbnormsB, dbnormsX                                       (src/utils.jl:29-59)
 
-    For every row the first entry of cbnorms (any length up to 256, unsorted) nearest to the norm of its reconstruction, in
+    For every row the first entry of cbnorms (any length up to 256 -- up to 32767 when h > 256 -- unsorted) nearest to the norm of its reconstruction, in
     f32 with the reference's (norm - c)^2 and findmin's tie rule (rq_quantize_norms).  Returns the codes (n,) one-based in
     B's dtype and the norms (n,) float32."""
     codes, Cs = _aq_args(B, C)
     n = codes.shape[0]
     m, h, d = Cs.shape
     cb = np.ascontiguousarray(_as_f32(cbnorms, "cbnorms").reshape(-1))
-    nc = np.empty(n, dtype=np.uint8)
     norms = np.empty(n, dtype=np.float32)
-    _lib.check(_lib.lib().rq_quantize_norms(nc.ctypes.data, norms.ctypes.data, codes.ctypes.data, Cs.ctypes.data,
-                                            cb.ctypes.data, n, d, m, h, cb.shape[0]))
+    if codes.dtype == np.int16:         # h > 256: int16 codes, cbnorms of up to 32767 entries (rq_quantize_norms_wide)
+        nc = np.empty(n, dtype=np.int16)
+        _lib.check(_lib.lib().rq_quantize_norms_wide(nc.ctypes.data, norms.ctypes.data, codes.ctypes.data, Cs.ctypes.data,
+                                                     cb.ctypes.data, n, d, m, h, cb.shape[0], 0))
+    else:
+        nc = np.empty(n, dtype=np.uint8)
+        _lib.check(_lib.lib().rq_quantize_norms(nc.ctypes.data, norms.ctypes.data, codes.ctypes.data, Cs.ctypes.data,
+                                                cb.ctypes.data, n, d, m, h, cb.shape[0]))
     out_dtype = np.asarray(B).dtype if np.asarray(B).dtype.itemsize >= 2 else np.int16
     return nc.astype(out_dtype) + out_dtype.type(1), norms
