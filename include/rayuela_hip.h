@@ -190,6 +190,17 @@ int rq_encode_rvq_beam_i16(int16_t *codes1, const float *X, const float *codeboo
  * workspace (at most 2 GiB: rows are chunked); Xr_out and cost_out may be NULL and are then not touched */
 int rq_dev_encode_rvq_beam(uint8_t *codes, float *Xr_out, float *cost_out, const float *X, const float *codebooks, int64_t n,
                            int d, int m, int h, int H, int nsplits, void *stream);
+/* src/CompetitiveQ.jl:75-135 with up to RQ_MAX_H16 codewords per stage: the contract above with
+ * 1 <= h <= 256 replaced by 1 <= h <= RQ_MAX_H16 and nothing else changed; codes [n][m] int16 in code_base .. code_base + h - 1
+ * (code_base 0 or 1).  h > RQ_MAX_H16 or m outside 1 .. 64 returns RQ_EUNSUPPORTED, every other violation RQ_EINVAL; no output
+ * byte is written on an error.  H = 1 gives rq_encode_rvq_wide's codes and residual bit for bit; at h <= 256 the codes, costs
+ * and residuals are rq_encode_rvq_beam's. */
+int rq_encode_rvq_beam_wide(int16_t *codes, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int H,
+                            int nsplits, int code_base, float *cost_out, float *Xr_out);
+/* src/CompetitiveQ.jl:75-135 on device pointers with up to RQ_MAX_H16 codewords per stage: rq_dev_encode_rvq_beam with int16
+ * ZERO-based codes; errors as rq_encode_rvq_beam_wide */
+int rq_dev_encode_rvq_beam_wide(int16_t *codes, float *Xr_out, float *cost_out, const float *X, const float *codebooks,
+                                int64_t n, int d, int m, int h, int H, int nsplits, void *stream);
 /* milliseconds of this thread's last beam call (src/CompetitiveQ.jl:75-135) by phase (hipEvents): {stage kernels, expand
  * kernels, other}; cap entries written.  After a device-pointer call it waits for that call's last event. */
 int rq_last_beam_timing(double *ms, int cap);
@@ -224,7 +235,18 @@ int rq_ervq_update_codebook(float *C, uint32_t *counts, const float *X, const ui
  * refilled entries differ from the reference's; without empty entries the result does not depend on `seed`. */
 int rq_train_ervq(float *C, int16_t *B1, double *error, double *obj, const float *X, int64_t n, int d, int m, int h,
                   int niter, uint64_t seed);
-/* milliseconds of this thread's last rq_train_ervq by phase (hipEvents), summed over the call: {initial residual,
+/* The codebook update of one ERVQ step (src/ERVQ.jl:85-90) over Int16 codes, 2 <= h <= RQ_MAX_H16:
+ * rq_ervq_update_codebook with codes [n][m] int16 in code_base .. code_base + h - 1 (code_base 0 or 1).  h > RQ_MAX_H16 or m
+ * outside 1 .. 64 returns RQ_EUNSUPPORTED, every other violation (a code out of range included) RQ_EINVAL, and no output byte is
+ * written.  At h <= 256 the result is rq_ervq_update_codebook's bit for bit. */
+int rq_ervq_update_codebook_wide(float *C, uint32_t *counts, const float *X, const int16_t *codes, int64_t n, int d, int m,
+                                 int h, int j, int code_base);
+/* train_ervq (src/ERVQ.jl:51-135) with 2 <= h <= RQ_MAX_H16 entries per codebook: rq_train_ervq's contract at every h, B [n][m]
+ * int16 in code_base .. code_base + h - 1 in and out.  Errors as rq_ervq_update_codebook_wide.  At h <= 256 C, B, error and
+ * obj are rq_train_ervq's bit for bit (the same draws). */
+int rq_train_ervq_wide(float *C, int16_t *B, double *error, double *obj, const float *X, int64_t n, int d, int m, int h,
+                       int niter, uint64_t seed, int code_base);
+/* milliseconds of this thread's last rq_train_ervq / rq_train_ervq_wide by phase (hipEvents), summed over the call: {initial residual,
  * increments, refills (with the read-back of the counts), stage encodes, epilogues, error passes, other (the uploads,
  * the code conversions)}; cap entries written */
 int rq_last_ervq_timing(double *ms, int cap);

@@ -185,7 +185,7 @@ end
 """
     quantize_competitiveq(X, C, H; nsplits=1) -> B     (src/CompetitiveQ.jl:75-135 for every column of X)
 Beam-search residual encoding: the `H` best partial encodings of each vector survive a stage (1 <= H <= min(32, h)); H = 1 is
-`quantize_rvq`.  `B::Matrix{Int16}` m-by-n one-based, in `quantize_rvq`'s layout.  `train_competitiveq`
+`quantize_rvq`.  `B::Matrix{Int16}` m-by-n one-based, in `quantize_rvq`'s layout; h > 256 takes rq_encode_rvq_beam_wide.  `train_competitiveq`
 (src/CompetitiveQ.jl:138-221) is a per-sample SGD and is not provided: train with `train_rvq` / `train_ervq`.
 """
 function quantize_competitiveq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, H::Integer; nsplits::Integer=1)
@@ -193,6 +193,13 @@ function quantize_competitiveq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, H
   m    = length(C)
   h    = size(C[1], 2)
   B    = Matrix{Int16}(undef, m, n)
+  if h > 256      # rq_encode_rvq_beam_wide: up to 32767 codewords per stage (src/CompetitiveQ.jl:75-135 on Matrix{Int16})
+    code_base = 1
+    _check(ccall((:rq_encode_rvq_beam_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
+      B, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(H), Cint(nsplits), Cint(code_base), C_NULL, C_NULL))
+    return B
+  end
   _check(ccall((:rq_encode_rvq_beam_i16, librayuela_hip), Cint,
     (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
     B, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(H), Cint(nsplits), C_NULL, C_NULL))
@@ -205,8 +212,18 @@ The reference's signature for one vector; `new_res` (its residual buffer) is acc
 as `RayuelaHIP.encode`.
 """
 function encode(x::Vector{Float32}, C::Vector{Matrix{Float32}}, new_res, m::Integer, h::Integer, d::Integer, H::Integer)
-  codes = Vector{UInt8}(undef, m)
   xr    = Vector{Float32}(undef, d)
+  if h > 256      # rq_encode_rvq_beam_wide: Int16 codes, one-based as the reference's
+    codes1    = Vector{Int16}(undef, m)
+    n         = 1
+    nsplits   = 1
+    code_base = 1
+    _check(ccall((:rq_encode_rvq_beam_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
+      codes1, x, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(H), Cint(nsplits), Cint(code_base), C_NULL, xr))
+    return codes1, xr
+  end
+  codes = Vector{UInt8}(undef, m)
   _check(ccall((:rq_encode_rvq_beam, librayuela_hip), Cint,
     (Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
     codes, x, hcat(C...), Int64(1), Cint(d), Cint(m), Cint(h), Cint(H), Cint(1), C_NULL, xr))
@@ -253,7 +270,7 @@ quantize_ervq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, V::Bool=false) = q
 
 """
     train_ervq(X, B, C, m, h, niter=25, V=false; seed=0) -> C, B, error     (src/ERVQ.jl:51-135)
-Enhanced RVQ / Stacked Quantizers, device-resident (rq_train_ervq): per iteration and codebook j, the codebook update,
+Enhanced RVQ / Stacked Quantizers, device-resident (rq_train_ervq; rq_train_ervq_wide when h > 256): per iteration and codebook j, the codebook update,
 the refill of entries without rows, the re-encode of stages j..m and the error.  `B` is any integer m-by-n matrix of
 one-based codes; the result is `Matrix{Int16}` and equals `quantize_ervq(X, C)[1]`.  The reference prints `Qerror is ...`
 after every step; here `V=true` prints those lines from the recorded trace.  Entries without rows are re-drawn by
@@ -271,9 +288,16 @@ function train_ervq(X::Matrix{Float32}, B::Matrix{T2}, C::Vector{Matrix{Float32}
   B1 === B && (B1 = copy(B))
   err = Ref{Cdouble}(0.0)
   obj = Vector{Cdouble}(undef, niter * m + 1)
+  if h > 256      # more than 256 entries per codebook: the same loop on 16-bit codes, rq_train_ervq_wide (src/ERVQ.jl:51-135)
+    code_base = 1
+    _check(ccall((:rq_train_ervq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64, Cint),
+      Ccat, B1, err, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed), Cint(code_base)))
+  else
   _check(ccall((:rq_train_ervq, librayuela_hip), Cint,
     (Ptr{Cfloat}, Ptr{Int16}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, UInt64),
     Ccat, B1, err, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), UInt64(seed)))
+  end
   if V
     print("Error after init is $(obj[1]) \n")
     for i = 1:niter

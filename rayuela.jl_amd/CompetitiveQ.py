@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .RVQ import _stack_codebooks
-from .utils import _as_f32
+from .utils import _as_f32, check_wide_h
 
 BEAM_PHASES = ["stage_ms", "expand_ms", "other_ms"]
 
@@ -19,6 +19,7 @@ def _check(X, C, H, nsplits):
     if X.ndim != 2:
         raise ValueError("X must be (n, d)")
     n, d = X.shape
+    check_wide_h(np.asarray(C[0]).shape[0])
     Cs = _stack_codebooks(C)
     m, h, d2 = Cs.shape
     if d2 != d:
@@ -30,11 +31,16 @@ def quantize_competitiveq(X, C, H, nsplits=1, V=False):
     """`encode` (src/CompetitiveQ.jl:75-135) for every row of X: a beam search of width H over the residual stages.
 
     X (n, d) float32, C m-long list of (h, d) codebooks (quantize_rvq's layout), 1 <= H <= min(32, h).  Returns B (n, m) int16
-    ONE-based, in quantize_rvq's layout; H = 1 gives quantize_rvq's codes.  nsplits: the minimum number of row chunks."""
+    ONE-based, in quantize_rvq's layout; H = 1 gives quantize_rvq's codes.  nsplits: the minimum number of row chunks.
+    256 < h <= 32767 codewords per stage take rq_encode_rvq_beam_wide; the return types are the same."""
     X, Cs, n, d, m, h, H, nsplits = _check(X, C, H, nsplits)
     B = np.empty((n, m), dtype=np.int16)
-    _lib.check(_lib.lib().rq_encode_rvq_beam_i16(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h, H, nsplits,
-                                                 None, None))
+    if check_wide_h(h):
+        _lib.check(_lib.lib().rq_encode_rvq_beam_wide(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h, H, nsplits, 1,
+                                                      None, None))
+    else:
+        _lib.check(_lib.lib().rq_encode_rvq_beam_i16(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h, H, nsplits,
+                                                     None, None))
     if V:
         print("Beam encoding with H = %d on %d codebooks... done" % (H, m))
     return B
@@ -53,6 +59,20 @@ def quantize_competitiveq_u8(X, C, H, nsplits=1, with_extras=False):
     return (B, cost, Xr) if with_extras else B
 
 
+def quantize_competitiveq_u16(X, C, H, nsplits=1, with_extras=False):
+    """Zero-based codes viewed as uint16 for any 1 <= h <= 32767 (rq_encode_rvq_beam_wide, code_base 0); with_extras ->
+    (codes, cost (n,), final residual (n, d)) as quantize_competitiveq_u8."""
+    X, Cs, n, d, m, h, H, nsplits = _check(X, C, H, nsplits)
+    B = np.empty((n, m), dtype=np.int16)
+    cost = np.empty((n,), dtype=np.float32) if with_extras else None
+    Xr = np.empty((n, d), dtype=np.float32) if with_extras else None
+    _lib.check(_lib.lib().rq_encode_rvq_beam_wide(B.ctypes.data, X.ctypes.data, Cs.ctypes.data, n, d, m, h, H, nsplits, 0,
+                                                  None if cost is None else cost.ctypes.data,
+                                                  None if Xr is None else Xr.ctypes.data))
+    B = B.view(np.uint16)
+    return (B, cost, Xr) if with_extras else B
+
+
 def encode(x, C, new_res, m, h, d, H):
     """encode(x, C, new_res, m, h, d, H) -> codes, residual          (src/CompetitiveQ.jl:75-135)
 
@@ -63,7 +83,8 @@ def encode(x, C, new_res, m, h, d, H):
         raise ValueError("x must be a vector of length d = %d" % d)
     if len(C) != m or any(np.shape(c) != (h, d) for c in C):
         raise ValueError("C must hold m = %d codebooks of shape (h, d) = (%d, %d)" % (m, h, d))
-    codes, _, Xr = quantize_competitiveq_u8(x[None, :], C, H, with_extras=True)
+    quantize = quantize_competitiveq_u16 if check_wide_h(h) else quantize_competitiveq_u8
+    codes, _, Xr = quantize(x[None, :], C, H, with_extras=True)
     return codes[0].astype(np.int16) + 1, Xr[0]
 
 

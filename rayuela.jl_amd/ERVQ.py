@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from .RVQ import _stack_codebooks, quantize_rvq, train_rvq
-from .utils import _as_f32
+from .utils import _as_f32, check_wide_h
 
 MAX_M = 64
 _U64 = (1 << 64) - 1
@@ -32,8 +32,9 @@ def _check(X, Cs, codes, m, h, one_based):
         raise ValueError("C holds %d codebooks of %d entries, the call says m=%d, h=%d" % (Cs.shape[0], Cs.shape[1], m, h))
     if not 1 <= int(m) <= MAX_M:
         raise ValueError("ERVQ covers 1 <= m <= %d codebooks; got m=%d" % (MAX_M, m))
-    if not 2 <= int(h) <= 256:
-        raise ValueError("ERVQ covers 2 <= h <= 256 entries; got h=%d" % h)
+    check_wide_h(h)
+    if int(h) < 2:
+        raise ValueError("ERVQ covers 2 <= h <= 32767 entries; got h=%d" % h)
     B = np.asarray(codes)
     if B.dtype.kind not in "iu":
         raise TypeError("codes must be integers; got %s" % B.dtype)
@@ -47,7 +48,8 @@ def _check(X, Cs, codes, m, h, one_based):
 
 def ervq_update_codebook(X, codes, C, j):
     """The codebook update of one ERVQ step alone (src/ERVQ.jl:85-90; rq_ervq_update_codebook): every entry of codebook j
-    (zero-based) that has rows becomes the mean of X - sum_{i != j} C_i[b_i] over its rows.  codes (n, m) uint8 zero-based.
+    (zero-based) that has rows becomes the mean of X - sum_{i != j} C_i[b_i] over its rows.  codes (n, m) uint8 zero-based;
+    int16 / uint16 codes, or more than 256 entries per codebook, take rq_ervq_update_codebook_wide (zero-based as well).
     Returns (C (m, h, d) with block j updated and every other block bit for bit, counts (h,) uint32); an entry without
     rows keeps its value, nothing is refilled."""
     X = np.ascontiguousarray(_as_f32(X, "X"))
@@ -56,15 +58,20 @@ def ervq_update_codebook(X, codes, C, j):
     n, d = _check(X, Cs, codes, m, h, one_based=False)
     if not 0 <= int(j) < m:
         raise ValueError("j must be in 0..m-1 = 0..%d; got %d" % (m - 1, j))
-    codes = np.array(codes, dtype=np.uint8, order="C")
     counts = np.zeros(h, dtype=np.uint32)
+    if check_wide_h(h) or np.asarray(codes).dtype in (np.int16, np.uint16):
+        codes = np.array(codes, dtype=np.int16, order="C")
+        _lib.check(_lib.lib().rq_ervq_update_codebook_wide(Cs.ctypes.data, counts.ctypes.data, X.ctypes.data, codes.ctypes.data,
+                                                           n, d, m, h, int(j), 0))
+        return Cs, counts
+    codes = np.array(codes, dtype=np.uint8, order="C")
     _lib.check(_lib.lib().rq_ervq_update_codebook(Cs.ctypes.data, counts.ctypes.data, X.ctypes.data, codes.ctypes.data, n, d,
                                                   m, h, int(j)))
     return Cs, counts
 
 
 def train_ervq_i16(X, B, C, m, h, niter, seed=0):
-    """The device-resident loop (rq_train_ervq): (C (m, h, d), B (n, m) int16 one-based, error, obj float64 (niter*m + 1,)).
+    """The device-resident loop (rq_train_ervq; rq_train_ervq_wide when h > 256): (C (m, h, d), B (n, m) int16 one-based, error, obj float64 (niter*m + 1,)).
     obj[0] is the error of the inputs, obj[1 + it*m + j] the error after step j of iteration it."""
     X = np.ascontiguousarray(_as_f32(X, "X"))
     Cs = _stack_codebooks(C).copy()
@@ -76,8 +83,13 @@ def train_ervq_i16(X, B, C, m, h, niter, seed=0):
     B1 = np.array(B, dtype=np.int16, order="C")
     obj = np.zeros(int(niter) * int(m) + 1, dtype=np.float64)
     err = ctypes.c_double(0.0)
-    _lib.check(_lib.lib().rq_train_ervq(Cs.ctypes.data, B1.ctypes.data, ctypes.cast(ctypes.byref(err), ctypes.c_void_p),
-                                        obj.ctypes.data, X.ctypes.data, n, d, int(m), int(h), int(niter), int(seed) & _U64))
+    perr = ctypes.cast(ctypes.byref(err), ctypes.c_void_p)
+    if check_wide_h(h):
+        _lib.check(_lib.lib().rq_train_ervq_wide(Cs.ctypes.data, B1.ctypes.data, perr, obj.ctypes.data, X.ctypes.data, n, d,
+                                                 int(m), int(h), int(niter), int(seed) & _U64, 1))
+    else:
+        _lib.check(_lib.lib().rq_train_ervq(Cs.ctypes.data, B1.ctypes.data, perr, obj.ctypes.data, X.ctypes.data, n, d, int(m),
+                                            int(h), int(niter), int(seed) & _U64))
     return Cs, B1, float(err.value), obj
 
 

@@ -23,7 +23,7 @@ from .SR import apply_schedule, SR_C_perturb, SR_D_perturb, train_sr, train_sr_c
 from .codebook_update import (update_codebooks, update_codebooks_fast_bin, update_codebooks_chain_bin,  # noqa: F401,E402
                               get_cbdims_chain)
 from .ChainQ import quantize_chainq, train_chainq  # noqa: F401,E402
-from .CompetitiveQ import quantize_competitiveq, quantize_competitiveq_u8, last_beam_timing  # noqa: F401,E402
+from .CompetitiveQ import quantize_competitiveq, quantize_competitiveq_u8, quantize_competitiveq_u16, last_beam_timing  # noqa: F401,E402
 from . import CompetitiveQ  # noqa: F401,E402  (CompetitiveQ.encode: the reference's one-vector signature)
 from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_aqd_query, LsqIndex,  # noqa: F401
                       linscan_aqd_query_extra_byte, eval_recall, linscan_lsq_cbnorms, linscan_pq_u16, linscan_opq_u16,
@@ -37,6 +37,6 @@ __all__ = ["quantize_pq", "quantize_opq", "linscan_pq", "linscan_opq", "linscan_
            "encoding_icm", "encode_icm_cuda", "train_lsq", "train_lsq_cuda", "train_sr", "train_sr_cuda",
            "apply_schedule", "SR_C_perturb", "SR_D_perturb", "update_codebooks",
            "update_codebooks_fast_bin", "quantize_chainq", "train_chainq", "update_codebooks_chain_bin", "get_cbdims_chain",
-           "quantize_competitiveq", "quantize_competitiveq_u8",
+           "quantize_competitiveq", "quantize_competitiveq_u8", "quantize_competitiveq_u16",
            "quantize_ervq", "train_ervq", "ervq_update_codebook", "last_ervq_timing",
            "eval_recall", "splitarray", "get_norms_codebook", "quantize_norms"]

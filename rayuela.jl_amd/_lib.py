@@ -68,7 +68,11 @@ SIGNATURES = {
     "rq_encode_rvq_beam": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "rq_encode_rvq_beam_i16": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "rq_dev_encode_rvq_beam": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "rq_encode_rvq_beam_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "rq_dev_encode_rvq_beam_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "rq_last_beam_timing": (_i32, [_vp, _i32]),
+    "rq_ervq_update_codebook_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "rq_train_ervq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _u64, _i32]),
     "rq_ervq_update_codebook": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
     "rq_train_ervq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _u64]),
     "rq_last_ervq_timing": (_i32, [_vp, _i32]),

@@ -447,6 +447,9 @@ int quantize_norms_h16_launch(int16_t *norm_codes, float *dbnorms, const float *
 // ---- ERVQ (rq_train.hip: the increment shares update_centers' segment sum; rq_ervq.hip: epilogue and loop) -------------------
 int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
                           int col, int h, int num_cu, hipStream_t stream);
+// the same over int16 codes (zero-based, read zero-extended), 1 <= h <= RQ_MAX_H16
+RQ_LOCAL int ervq_increment_h16_launch(float *Cj, unsigned int *counts, const float *E, const int16_t *codes, int64_t n, int d,
+                                       int cstride, int col, int h, int num_cu, hipStream_t stream);
 
 // ---- LSQ encoding (rq_icm.hip): argument checks, and the device body of rq_dev_encode_icm (codes already in range) -----
 int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t stream, const char *who);   // codes [n][m] < h

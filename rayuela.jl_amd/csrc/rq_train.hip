@@ -1074,6 +1074,57 @@ int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const
   return RQ_OK;
 }
 
+// The same increment over 16-bit codes: codes int16 zero-based, read zero-extended, 1 <= h <= RQ_MAX_H16.
+// The units of update_centers_h16_launch with one sub-quantizer of width d at a code stride and column: (16 dimensions, block of
+// 256 codes), the full blocks with 16 tiles and a ragged last block with its own tile count; the row slices shrink with the
+// number of code blocks and stay inside CENTERS_H16_SCRATCH_BYTES of partials.  Reduction and finish are the byte path's.
+int ervq_increment_h16_launch(float *Cj, unsigned int *counts, const float *E, const int16_t *codes, int64_t n, int d, int cstride,
+                              int col, int h, int num_cu, hipStream_t stream) {
+  if (d < 1 || h < 1 || h > RQ_MAX_H16 || cstride < 1 || col < 0 || col >= cstride)
+    return fail(RQ_EINVAL, "ervq increment: d=%d h=%d stride=%d column=%d", d, h, cstride, col);
+  if (n <= 0) {
+    RQ_HIP(hipMemsetAsync(counts, 0, (size_t)h * sizeof(unsigned int), stream));
+    return RQ_OK;
+  }
+  // rows of one slice: f32 counters, 32-bit buffer offsets into E and into the codes
+  const int64_t cap = std::min<int64_t>(std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4)), (1ll << 30) / ((int64_t)cstride * 2));
+  if (cap < 64 || (int64_t)h * d >= (1ll << 31)) return fail(RQ_EUNSUPPORTED, "ervq increment: d=%d h=%d", d, h);
+  TrainParams p{};
+  p.X = E; p.codes = reinterpret_cast<const uint8_t *>(codes); p.n = n; p.d = d; p.m = 1; p.h = h; p.cs = cstride; p.ccol = col;
+  p.off[0] = 0; p.off[1] = d;
+  const int nblocks = (h + 255) / 256;
+  const size_t stride = (size_t)h * d + (size_t)h;
+  const int64_t most = (int64_t)(CENTERS_H16_SCRATCH_BYTES / 5 * 4 / (stride * sizeof(float))) - 1;   // (workspace() allocates 1.25x)
+  const int64_t least = (n + cap - 1) / cap;
+  if (least > most || most > INT32_MAX)
+    return fail(RQ_EUNSUPPORTED, "ervq increment over 16-bit codes: n=%lld d=%d h=%d needs more than %zu bytes of partial sums",
+                (long long)n, d, h, CENTERS_H16_SCRATCH_BYTES);
+  const int64_t want = std::min<int64_t>((num_cu + nblocks - 1) / nblocks, (n + 1023) / 1024);
+  const int grid = (int)std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(want, 1), least), most);
+  void *part = nullptr;
+  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * stride * sizeof(float), &part, stream));
+  p.partial = (float *)part;
+  const int nunits = (d + 15) / 16;
+  const int last = h - 256 * (nblocks - 1), nfull = last == 256 ? nblocks : nblocks - 1;
+  if ((int64_t)nunits * nblocks > 8 * 65535ll) return fail(RQ_EUNSUPPORTED, "ervq increment over 16-bit codes: d=%d h=%d", d, h);
+  if (nfull > 0)
+    hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), dim3(grid, (nunits * nfull + 7) / 8), dim3(512), 0, stream, p, nunits, 0, nfull);
+  if (nfull < nblocks) {
+    const dim3 g3(grid, (nunits + 7) / 8);
+    if (last <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+    else if (last <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+    else hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+  }
+  RQ_HIP(hipGetLastError());
+  float *red = p.partial + (size_t)grid * stride;
+  RQ_TRY(partials_reduce<float>(red, p.partial, stride, grid, h * d, stream));
+  RQ_TRY(partials_reduce<unsigned int>(reinterpret_cast<unsigned int *>(red + (size_t)h * d),
+                                       reinterpret_cast<const unsigned int *>(p.partial + (size_t)h * d), stride, grid, h, stream));
+  hipLaunchKernelGGL(ervq_increment_finish_kernel, dim3((h * d + 255) / 256), dim3(256), 0, stream, Cj, counts, red, h, d);
+  RQ_HIP(hipGetLastError());
+  return RQ_OK;
+}
+
 int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h,
                        hipStream_t stream) {
   if (n <= 0) return RQ_OK;

@@ -128,6 +128,24 @@ def encode_rvq_wide(Xr, C, out=None, want_counts=False):
     return (out, counts) if want_counts else out
 
 
+def encode_rvq_beam_wide(X, C, H, nsplits=1, out=None, want_extras=False):
+    """encode_rvq_beam with 1 <= h <= 32767 codewords per stage (rq_dev_encode_rvq_beam_wide): codes (n, m) int16 zero-based
+    [, cost (n,), final residual (n, d)]."""
+    if X.dim() != 2 or C.dim() != 3 or C.shape[2] != X.shape[1]:
+        raise ValueError("X must be (n, d) and C (m, h, d)")
+    n, d = X.shape
+    m, h, _ = C.shape
+    out = torch.empty((n, m), dtype=torch.int16, device=X.device) if out is None else out
+    if out.numel() != n * m:
+        raise ValueError("out must hold n * m = %d codes" % (n * m))
+    cost = torch.empty((n,), dtype=torch.float32, device=X.device) if want_extras else None
+    Xr = torch.empty((n, d), dtype=torch.float32, device=X.device) if want_extras else None
+    _lib.check(_lib.lib().rq_dev_encode_rvq_beam_wide(_chk(out, torch.int16, "codes"), None if Xr is None else Xr.data_ptr(),
+                                                      None if cost is None else cost.data_ptr(), _chk(X, torch.float32, "X"),
+                                                      _chk(C, torch.float32, "C"), n, d, m, h, int(H), int(nsplits), _stream()))
+    return (out, cost, Xr) if want_extras else out
+
+
 def encode_rvq_beam(X, C, H, nsplits=1, out=None, want_extras=False):
     """Beam-search residual encoding (src/CompetitiveQ.jl:75-135 `encode`) on resident tensors: X (n, d) is only read, C (m, h, d),
     1 <= H <= min(32, h).  Returns codes (n, m) uint8 zero-based [, cost (n,), final residual (n, d)]."""
