@@ -909,6 +909,25 @@ int rq_scan_plan(int64_t n, int64_t nq, int m, int d, int k, int num_cu, int64_t
  * (hipEvent), D2H -- so the PCIe-inclusive and the resident rates can both be reported. */
 int rq_last_timing(double *total_ms, double *h2d_ms, double *kernel_ms, double *d2h_ms);
 
+/* ---- test hooks: not for callers --------------------------------------------------------------------------------------------
+ * No result of this library depends on what its scratch holds when a call begins; tests/test_gpu_scratch.py pins that with
+ * these two.  Both act on the current device as a whole and wait for it, like rq_release_workspaces.
+ *
+ * rq_test_fill_scratch sets every byte (allocation slack included) of every scratch buffer of every stream, of every idle staging
+ * buffer of the host-pointer calls and of every idle page-locked block (rq_host_alloc) to `value` (0..255).  The kept in-call row
+ * order starts over as after a fresh allocation (its buffers are filled too), and with it the statistics of
+ * rq_order_cache_stats: they read as after rq_release_workspaces.  out7: [0] bytes filled in stream scratch, [1] in
+ * idle staging buffers, [2] in idle page-locked blocks, [3] scratch buffers filled, [4] the number of scratch allocations the
+ * library has made so far (it moves when a call had to grow a buffer, that is, when it ran on fresh memory instead), [5] idle
+ * staging buffers, [6] idle page-locked blocks (either count or its bytes move when a host-pointer call had to take a fresh
+ * buffer instead of a filled one).
+ *
+ * rq_test_scratch_report: for the scratch of stream `of_stream` (NULL: the null stream), per buffer s < 20 (the order of the
+ * WS_* enum of csrc/rq_internal.h): bytes[s] allocated (0: none), differs[s] = 1 if any byte is not the value of the last
+ * fill.  cap: entries of bytes / differs, at least 20. */
+int rq_test_fill_scratch(int value, unsigned long long *out7);
+int rq_test_scratch_report(void *of_stream, int64_t *bytes, int *differs, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,8 @@ SIGNATURES = {
     "rq_order_cache_stats": (_i32, [_vp]),
     "rq_scan_plan": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "rq_last_timing": (_i32, [_vp, _vp, _vp, _vp]),
+    "rq_test_fill_scratch": (_i32, [_i32, _vp]),
+    "rq_test_scratch_report": (_i32, [_vp, _vp, _vp, _i32]),
 }
 
 _LIB = None
@@ -247,6 +249,24 @@ def order_cache_stats():
     out = (C.c_uint64 * 8)()
     check(lib().rq_order_cache_stats(C.cast(out, C.c_void_p)))
     return dict(zip(["consulted", "hits", "plain_builds", "balanced_builds", "uncached", "upgrades"], [int(x) for x in out[:6]]))
+
+
+WS_SLOTS = 20          # csrc/rq_internal.h (tests/test_gpu_scratch.py reads the names from there)
+
+
+def fill_scratch(value):
+    """Test hook, not for callers (rq_test_fill_scratch): every byte of library scratch on the current device becomes `value`."""
+    out = (C.c_uint64 * 7)()
+    check(lib().rq_test_fill_scratch(int(value), C.cast(out, C.c_void_p)))
+    return dict(zip(["slot_bytes", "pool_bytes", "pinned_bytes", "slots", "ws_gen", "pool_buffers", "pinned_blocks"],
+                    [int(x) for x in out]))
+
+
+def scratch_report(stream=0):
+    """Test hook, not for callers (rq_test_scratch_report): (bytes, differs) per scratch slot of `stream` (a handle; 0: null)."""
+    nbytes, differs = (C.c_int64 * WS_SLOTS)(), (C.c_int * WS_SLOTS)()
+    check(lib().rq_test_scratch_report(C.c_void_p(stream or None), C.cast(nbytes, C.c_void_p), C.cast(differs, C.c_void_p), WS_SLOTS))
+    return [int(x) for x in nbytes], [bool(x) for x in differs]
 
 
 def scan_stats():

@@ -300,6 +300,91 @@ void host_pool_trim() {
   for (auto &b : drop) (void)hipHostFree(b.p);
 }
 
+// ---- test hooks (rq_test_fill_scratch / rq_test_scratch_report; tests/test_gpu_scratch.py) ------------------------------------
+// No result may depend on what library scratch holds when a call begins ("what a call may assume about its
+// scratch").  The fill hook makes that content arbitrary: every byte -- the 25 % slack included -- of every slot of every used
+// stream workspace of the current device, of every idle buffer of the device pool and of every idle page-locked block becomes
+// `value`.  The kept order is the one content the library is entitled to keep, so it starts over as after a fresh allocation
+// (free_stream_ws): the buffers are filled and the stream's OrderCacheHost is reset -- with it the `consulted` / `uncached`
+// counts of rq_order_cache_stats.  Like release_workspaces: the whole device,
+// synchronised, under the DeviceLock.
+static int g_fill_value[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // (g_mu) last fill per device
+
+int test_fill_scratch(int value, unsigned long long *out7) {
+  if (!out7) return fail(RQ_EINVAL, "rq_test_fill_scratch: null output");
+  if (value < 0 || value > 255) return fail(RQ_EINVAL, "rq_test_fill_scratch: value=%d is not a byte", value);
+  int dev = 0;
+  RQ_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 16) return fail(RQ_ENODEVICE, "device ordinal %d out of range", dev);
+  DeviceLock launch_lock;
+  RQ_HIP(hipDeviceSynchronize());
+  unsigned long long slot_bytes = 0, pool_bytes = 0, pinned_bytes = 0, slots = 0;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    DevCtx &c = g_dev[dev];
+    for (int i = 0; i < MAX_STREAM_WS; ++i) {
+      StreamWs &w = c.sw[i];
+      if (!w.used) continue;
+      for (int s = 0; s < WS_SLOTS; ++s) {
+        if (!w.ws[s]) continue;
+        RQ_HIP(hipMemset(w.ws[s], value, w.ws_bytes[s]));
+        slot_bytes += w.ws_bytes[s];
+        ++slots;
+      }
+      w.oc = OrderCacheHost();
+    }
+    for (auto &b : c.pool) {
+      RQ_HIP(hipMemset(b.p, value, b.bytes));
+      pool_bytes += b.bytes;
+    }
+    for (auto &b : g_hp.idle) {
+      memset(b.p, value, b.bytes);
+      pinned_bytes += b.bytes;
+    }
+    g_fill_value[dev] = value;
+    out7[4] = g_ws_gen;
+    out7[5] = c.pool.size();
+    out7[6] = g_hp.idle.size();
+  }
+  RQ_HIP(hipDeviceSynchronize());
+  out7[0] = slot_bytes; out7[1] = pool_bytes; out7[2] = pinned_bytes; out7[3] = slots;
+  return RQ_OK;
+}
+
+// Per slot of `stream`'s workspace on the current device: the allocated bytes (0: never taken) and whether any byte differs from
+// the value of the last fill.  A copy to the host and a compare, in pieces of 64 MiB.
+int test_scratch_report(hipStream_t stream, int64_t *bytes, int *differs, int cap) {
+  if (!bytes || !differs || cap < WS_SLOTS)
+    return fail(RQ_EINVAL, "rq_test_scratch_report: needs %d entries of bytes and differs", (int)WS_SLOTS);
+  int dev = 0;
+  RQ_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 16) return fail(RQ_ENODEVICE, "device ordinal %d out of range", dev);
+  DeviceLock launch_lock;
+  RQ_HIP(hipDeviceSynchronize());
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (g_fill_value[dev] < 0) return fail(RQ_EINVAL, "rq_test_scratch_report: no rq_test_fill_scratch on device %d yet", dev);
+  const unsigned char want = (unsigned char)g_fill_value[dev];
+  for (int s = 0; s < cap; ++s) { bytes[s] = 0; differs[s] = 0; }
+  DevCtx &c = g_dev[dev];
+  const size_t piece = (size_t)64 << 20;
+  std::vector<unsigned char> host;
+  for (int i = 0; i < MAX_STREAM_WS; ++i) {
+    const StreamWs &w = c.sw[i];
+    if (!w.used || w.stream != stream) continue;
+    for (int s = 0; s < WS_SLOTS; ++s) {
+      if (!w.ws[s]) continue;
+      bytes[s] = (int64_t)w.ws_bytes[s];
+      for (size_t at = 0; at < w.ws_bytes[s] && !differs[s]; at += piece) {
+        const size_t nb = std::min(piece, w.ws_bytes[s] - at);
+        if (host.size() < nb) host.resize(nb);
+        RQ_HIP(hipMemcpy(host.data(), (const char *)w.ws[s] + at, nb, hipMemcpyDeviceToHost));
+        if (host[0] != want || memcmp(host.data(), host.data() + 1, nb - 1) != 0) differs[s] = 1;
+      }
+    }
+  }
+  return RQ_OK;
+}
+
 // RAII device buffer for the host-pointer entry points.  Buffers up to HOST_CACHE_MAX_MB (256) each go back to a
 // per-device pool of at most HOST_CACHE_MB (2048) instead of hipFree: every host-pointer call synchronises before it
 // returns, so a pooled buffer is idle.
@@ -1096,6 +1181,11 @@ int rq_release_workspaces(void) {
   rq::sharded_cache_release();
   rq::host_pool_trim();
   return release_workspaces();
+}
+
+int rq_test_fill_scratch(int value, unsigned long long *out7) { return test_fill_scratch(value, out7); }
+int rq_test_scratch_report(void *of_stream, int64_t *bytes, int *differs, int cap) {
+  return test_scratch_report((hipStream_t)of_stream, bytes, differs, cap);
 }
 
 void *rq_host_alloc(size_t bytes) { return rq::host_pool_alloc(bytes); }

@@ -221,6 +221,15 @@ def _linscan_bulk():
                 after=_scan_kernel_starts("adc_bulk_keys_kernel<8"))
 
 
+def _linscan_padded():
+    """m = 5 is no tiled row width: the call first pads the rows to 8 bytes in library scratch (WS_PAD)."""
+    from test_gpu_switches import _scan_setup
+    n, m, sub, nq, K = 70_001, 5, 4, 5, 100
+    codes, centers, queries, ref = _scan_setup(n, m, sub, nq, 31, Ks=(K,))
+    return Case("rq_dev_linscan", {"codes": codes, "centers": centers, "queries": queries}, _run_linscan(K),
+                _check_scan(*ref[K]), outputs=_scan_outputs(nq, K), after=_scan_kernel_starts("adc_scan_kernel<8"))
+
+
 def _adc_lut():
     from test_gpu_switches import _scan_setup
     _, centers, queries, _ = _scan_setup(*SCAN_SHAPE)
@@ -590,6 +599,7 @@ CASES = {
     "linscan_k100_orders_in_call": ("rq_dev_linscan", _linscan(100, True)),
     "linscan_k1000_sample_sort": ("rq_dev_linscan", _linscan(1000, False)),
     "linscan_bulk_k65537": ("rq_dev_linscan", _linscan_bulk),
+    "linscan_m5_padded_rows": ("rq_dev_linscan", _linscan_padded),
     "order_rows": ("rq_dev_order_rows", _order_rows),
     "linscan_ordered": ("rq_dev_linscan_ordered", _linscan_ordered),
     "linscan_aq_lsq": ("rq_dev_linscan_aq", _linscan_aq(True)),
@@ -643,11 +653,11 @@ def run_on_side_stream(case, stream, delay_cycles, log=None):
     3. only `stream` is synchronised before the clones are read.
     Work the library puts on another stream without an event dependency runs during the delay.  A misplaced kernel or memset that
     reads a caller's input sees poison, one that writes a caller's output is overwritten or writes after the clone: the clones
-    then differ from the expected output.  What the harness does NOT see: a misplaced reset of library scratch (a memset of work
-    counters, histograms, tables: it runs early and nothing dirties that scratch before the kernels that need it clean), misplaced
-    work that only reads and writes library scratch still holding the same intermediates from an earlier call with these inputs,
-    and -- for the entries that synchronise the stream inside the call (the code range check with h < 256) -- whatever they queue
-    after that point, which is no longer behind the delay."""
+    then differ from the expected output.  What library scratch holds when a call begins -- a reset that is missing or misplaced,
+    a read of an earlier call's intermediates -- is the subject of tests/test_gpu_scratch.py, which runs these cases on scratch
+    filled with four byte values and inside other cases' leftovers.  What the harness does NOT see: for the entries that
+    synchronise the stream inside the call (the code range check with h < 256), whatever they queue after that point, which is
+    no longer behind the delay."""
     import torch
     from switch_table import switches
     torch.cuda.synchronize()

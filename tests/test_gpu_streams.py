@@ -5,7 +5,9 @@ Every other test passes torch's default stream, which on PyTorch-ROCm is the nul
 kernel, memset or scratch reset that the library launched on the wrong stream (a forgotten `stream` argument) gives the right
 answer there and a race for a caller on a side stream.  Here every entry point runs on a side stream behind a delay
 (stream_cases.run_on_side_stream: poison, delay, fill, call, consume, poison) and must give the expected output of its
-family's own tests, compared the same way.  The coverage is derived: test_every_stream_entry_point_has_a_case (no GPU needed)
+family's own tests, compared the same way.  (What library scratch holds when a call begins -- a reset that is missing, or that
+ran early while nothing dirtied the scratch, a read of an earlier call's intermediates -- is tests/test_gpu_scratch.py's
+subject, with these same cases.)  The coverage is derived: test_every_stream_entry_point_has_a_case (no GPU needed)
 parses the header for the prototypes that end in `void *stream`.
 
 The delay is an input of the test, not a threshold of the library.  DELAY_CYCLES = 20 000 000 cycles of torch.cuda._sleep,

@@ -2,7 +2,8 @@
 with the harness of tests/stream_cases.py exactly as tests/bytes_stream_cases.py does -- a plain helper module: no fixtures, no
 pytest hooks.  tests/test_gpu_encode_wide.py and tests/test_wide_oracle.py import it, so the table of
 tests/test_gpu_streams.py is complete whenever the suite is collected as a whole.  h = 512: the streaming kernel, whose norms
-pass, scratch and (RVQ) memset of the counts must sit on the caller's stream as well."""
+pass, scratch and (RVQ) memset of the counts must sit on the caller's stream as well; one h = 256 case: the byte kernels into
+library scratch (WS_H16_CODES), then widened."""
 import numpy as np
 
 import stream_cases as sc
@@ -18,7 +19,7 @@ def _data(n, d, m, h, seed):
     return X, np.concatenate([c.reshape(-1) for c in C])
 
 
-def _encode_pq_wide(n, d, m, h):
+def _encode_pq_wide(n, d, m, h, kernel="encode_h16_kernel"):
     def build():
         X, Ccat = _data(n, d, m, h, 31)
         ref = wo.encode_pq_wide(sc._oracle(), X, Ccat, m, h)
@@ -29,8 +30,12 @@ def _encode_pq_wide(n, d, m, h):
         def check(got):
             assert np.array_equal(got["codes"], ref), "rows differ: %d" % int((got["codes"] != ref).any(axis=1).sum())
 
+        def after():
+            ran = (sc._L().lib().rq_last_encode_kernel() or b"").decode()
+            assert (ran == kernel) if kernel else (ran != "encode_h16_kernel"), (ran, kernel)
+
         return sc.Case("rq_dev_encode_pq_wide", {"X": X, "C": Ccat}, run, check, outputs={"codes": (ref.shape, np.int16)},
-                       after=sc._enc_kernel_is("encode_h16_kernel"))
+                       after=after)
     return build
 
 
@@ -76,6 +81,7 @@ def _encode_rvq_wide(n, d, m, h):
 WIDE_CASES = {
     "encode_pq_wide": ("rq_dev_encode_pq_wide", _encode_pq_wide(4_001, 64, 4, 512)),
     "encode_pq_wide_chunked": ("rq_dev_encode_pq_wide", _encode_pq_wide(3_000, 80, 2, 512)),
+    "encode_pq_wide_h256_byte_kernels": ("rq_dev_encode_pq_wide", _encode_pq_wide(2_001, 64, 4, 256, kernel=None)),
     "encode_opq_wide": ("rq_dev_encode_opq_wide", _encode_opq_wide(4_001, 32, 4, 512)),
     "encode_rvq_wide": ("rq_dev_encode_rvq_wide", _encode_rvq_wide(3_001, 48, 2, 512)),
 }
