@@ -927,6 +927,15 @@ int rq_last_timing(double *total_ms, double *h2d_ms, double *kernel_ms, double *
  * fill.  cap: entries of bytes / differs, at least 20. */
 int rq_test_fill_scratch(int value, unsigned long long *out7);
 int rq_test_scratch_report(void *of_stream, int64_t *bytes, int *differs, int cap);
+/* Host-only, no device: what the segment sum of rq_dev_update_centers[_wide] (cstride == 0) or of the ERVQ codebook increment
+ * (cstride > 0: the code stride, one sub-quantizer of width d, m ignored) would launch for n rows on a device of num_cu compute
+ * units; code_bytes 1 (uint8 codes) or 2 (int16).  The launchers ask the same planner (csrc/rq_train.hip), and the number of row
+ * slices fixes the order of the float reduction, so tests/test_centers_plan.py pins it.  out (cap >= 8 words): [0] the return
+ * code the launcher would give (the rest is 0 unless it is RQ_OK), [1] 1: the matrix-core kernel, 2: the owner-thread kernel
+ * (then [3..6] are 0), [2] row slices, [3] (sub-quantizer, 16-dimension block) units per block of 256 codes, [4] code blocks,
+ * [5] of them launched together with 16 tiles, [6] the tile count (4, 8 or 16) of the ragged last block, 0 if there is none,
+ * [7] bytes asked of the WS_TMP scratch slot. */
+int rq_centers_plan(int64_t n, int d, int m, int h, int num_cu, int code_bytes, int cstride, int64_t *out, int cap);
 
 #ifdef __cplusplus
 }

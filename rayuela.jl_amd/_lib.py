@@ -176,6 +176,7 @@ SIGNATURES = {
     "rq_last_timing": (_i32, [_vp, _vp, _vp, _vp]),
     "rq_test_fill_scratch": (_i32, [_i32, _vp]),
     "rq_test_scratch_report": (_i32, [_vp, _vp, _vp, _i32]),
+    "rq_centers_plan": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
 }
 
 _LIB = None

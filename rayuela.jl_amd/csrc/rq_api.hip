@@ -895,19 +895,15 @@ static int host_linscan_wide(const char *who, float *dists, uint32_t *ids, const
   if (lsq && aq.dbnorms) RQ_HIP(hipMemcpy(dn.p, aq.dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
   if (lsq && !aq.dbnorms) RQ_HIP(hipMemcpy(dcbn.p, aq.cbnorms, (size_t)aq.hn * 4, hipMemcpyHostToDevice));
   g_t_h2d = t1.ms();
-  RQ_TRY(prepare_codes_h16_launch(dcodes.as<int16_t>(), dbad.as<unsigned long long>(), n, m, h, code_base, nullptr));
-  unsigned long long first_bad = 0;
-  RQ_HIP(hipMemcpy(&first_bad, dbad.p, 8, hipMemcpyDeviceToHost));
-  if (first_bad != ~0ull)
-    return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d] (InexactError of src/Linscan.jl:35 convert(Matrix{UInt8}, B .- 1))",
-                who, first_bad, code_base, h - 1 + code_base);
+  RQ_TRY(check_codes_h16(who, dcodes.as<int16_t>(), dbad.as<unsigned long long>(), n, m, h, code_base, nullptr,
+                         " (InexactError of src/Linscan.jl:35 convert(Matrix{UInt8}, B .- 1))"));
   RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
   const int16_t *cdev = dcodes.as<int16_t>();
   const float *cen = dcent.as<float>();
   if (lsq && !aq.dbnorms) {      // the norms leg of src/RVQ.jl:150-155 on the device: the arithmetic of rq_quantize_norms_wide
     if (h < 2 || m > 64) return fail(RQ_EINVAL, "%s: the norms need 2 <= h, m <= 64; got h=%d m=%d", who, h, m);
-    RQ_TRY(aq_norms_h16_launch(dn.as<float>(), cdev, cen, n, d, m, h, nullptr));
-    RQ_TRY(quantize_norms_h16_launch(nullptr, dn.as<float>(), dn.as<float>(), dcbn.as<float>(), n, aq.hn, nullptr));
+    RQ_TRY(aq_norms_launch(dn.as<float>(), cdev, cen, n, d, m, h, nullptr));
+    RQ_TRY(quantize_norms_launch((int16_t *)nullptr, dn.as<float>(), dn.as<float>(), dcbn.as<float>(), n, aq.hn, nullptr));
   }
   const float *nrm = lsq ? dn.as<float>() : nullptr;
   RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
@@ -1305,7 +1301,7 @@ static rq_lsq_index *lsq_prepare(const uint8_t *codes, const float *codebooks, c
         RQ_TRY(dcbn.alloc((size_t)hn * 4)); RQ_TRY(dsq.alloc((size_t)n * 4));
         RQ_HIP(hipMemcpy(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
         RQ_TRY(aq_norms_launch(dsq.as<float>(), rawc, ix->cb, n, d, m, 256, nullptr));
-        RQ_TRY(quantize_norms_launch(nullptr, ix->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, nullptr));
+        RQ_TRY(quantize_norms_launch((uint8_t *)nullptr, ix->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, nullptr));
       }
       RQ_HIP(hipDeviceSynchronize());       // before the scratch of this block goes back
     }
@@ -1849,6 +1845,15 @@ int rq_scan_wide_plan(int m, int h, int *out, int cap) {
   return RQ_OK;
 }
 
+// host-only: what update_centers (cstride == 0) / the ERVQ increment (cstride > 0) would launch for this shape (tests; no device)
+int rq_centers_plan(int64_t n, int d, int m, int h, int num_cu, int code_bytes, int cstride, int64_t *out, int cap) {
+  if (!out || cap < 8) return fail(RQ_EINVAL, "rq_centers_plan: out needs 8 words");
+  if ((code_bytes != 1 && code_bytes != 2) || cstride < 0 || num_cu < 1)
+    return fail(RQ_EINVAL, "rq_centers_plan: code_bytes=%d cstride=%d num_cu=%d", code_bytes, cstride, num_cu);
+  centers_plan_readout(n, d, m, h, num_cu, code_bytes, cstride, out);
+  return RQ_OK;
+}
+
 int rq_scan_row_width(int m) { return scan_padded_m(m); }
 
 // host-only: how a base of n rows x m bytes would be ordered -- out[0..7] key bits per leading code byte, [8] total bits,
@@ -1949,13 +1954,13 @@ int rq_dev_update_centers_wide(float *C, uint32_t *counts, const float *X, const
   if (!C || !counts || !X || !codes) return fail(RQ_EINVAL, "rq_dev_update_centers_wide: NULL argument");
   DeviceInfo di;
   RQ_TRY(device_info(&di));
-  return update_centers_h16_launch(C, counts, X, codes, n, d, m, h, di.num_cu, (hipStream_t)stream);
+  return update_centers_launch(C, counts, X, codes, n, d, m, h, di.num_cu, (hipStream_t)stream);
 }
 
 int rq_dev_reconstruct_wide(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
   if (n <= 0) return RQ_OK;
   if (!CB || !codes || !C) return fail(RQ_EINVAL, "rq_dev_reconstruct_wide: NULL argument");
-  return reconstruct_h16_launch(CB, codes, C, n, d, m, h, (hipStream_t)stream);
+  return reconstruct_launch(CB, codes, C, n, d, m, h, (hipStream_t)stream);
 }
 
 int rq_dev_qerror(double *acc, const float *X, const float *CB, int64_t n, int d, void *stream) {

@@ -35,7 +35,7 @@
 
 // More than 256 codewords per stage: the loop below is ONE template over the code type, as the Lloyd
 // loops of rq_train_host.hip (section 4.19).  Code = uint8_t is the loop as it was -- the same launches, draws and bits; Code =
-// int16_t (zero-based on the device) swaps in ervq_increment_h16_launch and encode_h16_launch and nothing else.
+// int16_t (zero-based on the device) takes ervq_increment_launch<int16_t> and encode_launch's int16 overload and nothing else.
 
 namespace rq {
 
@@ -58,22 +58,6 @@ int ervq_full_residual(float *E, const float *C, const Code *codes, int64_t n, i
   for (int i = 0; i < m; ++i)
     RQ_TRY(residual_launch<Code>(E, E, C + (size_t)i * h * d, codes + i, m, nullptr, nullptr, n, d, m, i, stream));
   return RQ_OK;
-}
-
-// the two pieces that differ between the code types
-int ervq_increment(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride, int col,
-                   int h, int num_cu, hipStream_t stream) {
-  return ervq_increment_launch(Cj, counts, E, codes, n, d, cstride, col, h, num_cu, stream);
-}
-int ervq_increment(float *Cj, unsigned int *counts, const float *E, const int16_t *codes, int64_t n, int d, int cstride, int col,
-                   int h, int num_cu, hipStream_t stream) {
-  return ervq_increment_h16_launch(Cj, counts, E, codes, n, d, cstride, col, h, num_cu, stream);
-}
-int ervq_stage_encode(uint8_t *stage, const float *src, const float *Ci, int64_t n, int d, int h, int num_cu, hipStream_t stream) {
-  return encode_launch(stage, src, Ci, n, d, 1, h, num_cu, stream);
-}
-int ervq_stage_encode(int16_t *stage, const float *src, const float *Ci, int64_t n, int d, int h, int num_cu, hipStream_t stream) {
-  return encode_h16_launch(stage, src, Ci, n, d, 1, h, num_cu, stream);
 }
 
 int ervq_check_shape(const char *who, int64_t n, int d, int m, int h) {
@@ -126,8 +110,7 @@ int ervq_update_host(float *C, uint32_t *counts, const float *X, const Code *cod
   RQ_HIP(hipMemcpy(dcodes.p, codes, kb, hipMemcpyHostToDevice));
   RQ_TRY(ervq_full_residual<Code>(dE.as<float>(), dC.as<float>(), dcodes.as<Code>(), n, d, m, h, nullptr));
   float *Cj = dC.as<float>() + (size_t)j * h * d;
-  RQ_TRY(ervq_increment(Cj, dcnt.as<unsigned int>(), dE.as<float>(), (const Code *)dcodes.as<Code>(), n, d, m, j, h, di.num_cu,
-                        nullptr));
+  RQ_TRY(ervq_increment_launch<Code>(Cj, dcnt.as<unsigned int>(), dE.as<float>(), dcodes.as<Code>(), n, d, m, j, h, di.num_cu, nullptr));
   RQ_HIP(hipDeviceSynchronize());
   RQ_HIP(hipMemcpy(C + (size_t)j * h * d, Cj, jb, hipMemcpyDeviceToHost));   // the other blocks are not written
   RQ_HIP(hipMemcpy(counts, dcnt.p, (size_t)h * 4, hipMemcpyDeviceToHost));
@@ -177,7 +160,7 @@ int train_ervq_host(float *C, int16_t *B, double *error, double *obj, const floa
       float *Cj = Cd + (size_t)j * h * d;
       // 1. the increment (dCold keeps the entries the codes were assigned with: the refill draws with THOSE costs)
       RQ_HIP(hipMemcpyAsync(dCold.p, Cj, jb, hipMemcpyDeviceToDevice, s));
-      RQ_TRY(ervq_increment(Cj, dcnt.as<unsigned int>(), W, (const Code *)codes, n, d, m, j, h, di.num_cu, s));
+      RQ_TRY(ervq_increment_launch<Code>(Cj, dcnt.as<unsigned int>(), W, codes, n, d, m, j, h, di.num_cu, s));
       clk.mark(EV_INCREMENT);
       // 2. entries without rows
       RQ_HIP(hipMemcpy(counts.data(), dcnt.p, (size_t)h * 4, hipMemcpyDeviceToHost));
@@ -194,7 +177,7 @@ int train_ervq_host(float *C, int16_t *B, double *error, double *obj, const floa
       const float *src = P;
       for (int i = j; i < m; ++i) {
         const float *Ci = Cd + (size_t)i * h * d;
-        RQ_TRY(ervq_stage_encode(stage, src, Ci, n, d, h, di.num_cu, s));
+        RQ_TRY(encode_launch(stage, src, Ci, n, d, 1, h, di.num_cu, s));
         clk.mark(EV_ENCODE);
         if (i == j && j + 1 < m) {
           RQ_TRY(residual_launch<Code>(Pnext, src, Ci, stage, 1, codes, nullptr, n, d, m, i, s));

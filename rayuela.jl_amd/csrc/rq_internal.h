@@ -314,6 +314,11 @@ int lut_h16_launch(float *lut, const float *centers, const float *queries, int64
 // host entries: codes -= code_base in place; *first_bad (device) <- the first row with a code outside [0, h), else ~0
 int prepare_codes_h16_launch(int16_t *codes, unsigned long long *first_bad, int64_t n, int m, int h, int code_base,
                              hipStream_t stream);
+// the int16 code check of every entry that takes such codes from a caller: prepare_codes_h16_launch with `flag` (8 device bytes)
+// as its word, the word read back on `stream` before any other work is queued, RQ_EINVAL naming `who`, the first bad row and the
+// accepted range [code_base, h - 1 + code_base], `suffix` appended
+int check_codes_h16(const char *who, int16_t *codes, unsigned long long *flag, int64_t n, int m, int h, int code_base,
+                    hipStream_t stream, const char *suffix = "");
 void scan_h16_plan(int m, int h, int out[4]);             // rq_scan_wide_plan
 // linscan_lsq / linscan_cq over 16-bit codes: codebooks [m * h][d]; lut_mode LUT_LSQ (dbnorms [n]) or LUT_CQ
 int dev_linscan_aq_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *codebooks,
@@ -358,6 +363,11 @@ int widen_codes_launch(int16_t *out1, const uint8_t *codes, int64_t nelem, hipSt
 // codes [n][m] int16 ZERO-based, 1 <= h <= RQ_MAX_H16; h <= 256 runs encode_launch and widens.  Scratch: WS_H16_SA, WS_H16_CODES.
 int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
                       hipStream_t stream);
+// one overload set with the byte encode, for the loops that are templates over the code type
+inline int encode_launch(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                         hipStream_t stream) {
+  return encode_h16_launch(codes, X, C, n, d, m, h, num_cu, stream);
+}
 int rvq_h16_encode_launch(int16_t *codes, float *Xr, int16_t *stage_codes, unsigned int *counts, const float *C, int64_t n,
                           int d, int m, int h, int num_cu, hipStream_t stream);
 int add_base_codes_launch(int16_t *codes, int64_t nelem, int base, hipStream_t stream);   // codes += base, in place
@@ -371,17 +381,17 @@ int encode_bytes_launch(uint8_t *codes, const uint8_t *X, const float *R, const 
 int rotate_bytes_launch(float *RX, const float *R, const uint8_t *X, int d, int64_t n, int num_cu, hipStream_t stream);
 
 // ---- training reductions (rq_train.hip) --------------------------------------------------------
-int update_centers_launch(float *C, unsigned int *counts, const float *X, const uint8_t *codes, int64_t n, int d,
-                          int m, int h, int num_cu, hipStream_t stream);
-int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h,
-                       hipStream_t stream);
+// Code: uint8_t (1 <= h <= 256; reconstruct: any h) or int16_t (zero-based, read zero-extended, 1 <= h <=
+// RQ_MAX_H16; a code outside [0, h): update_centers ignores the row in that sub-space, reconstruct writes zeros for it)
+template <class Code>
+RQ_LOCAL int update_centers_launch(float *C, unsigned int *counts, const float *X, const Code *codes, int64_t n, int d, int m, int h,
+                                   int num_cu, hipStream_t stream);
+template <class Code>
+RQ_LOCAL int reconstruct_launch(float *CB, const Code *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
+// rq_centers_plan: the slice plan of update_centers_launch (cstride == 0) / ervq_increment_launch (cstride > 0), no device work
+void centers_plan_readout(int64_t n, int d, int m, int h, int num_cu, int code_bytes, int cstride, int64_t out[8]);
 int qerror_launch(double *acc_dev, const float *X, const float *CB, int64_t n, int d, int num_cu,
                   hipStream_t stream);
-// the same two over 16-bit codes: codes [n][m] int16 zero-based, read zero-extended, 1 <= h <= RQ_MAX_H16.
-// A code outside [0, h): update_centers ignores the row in that sub-space, reconstruct writes zeros for it.
-RQ_LOCAL int update_centers_h16_launch(float *C, unsigned int *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
-                              int num_cu, hipStream_t stream);
-RQ_LOCAL int reconstruct_h16_launch(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
 struct Rng;
 // Clustering.repick_unused_centers on the device: the `unused` entries of Csub [h][sub] re-drawn from the rows of P (stride d,
 // columns [col0, col0 + sub)); costs under Cold (the entries the codes were assigned with) in f64 on the device, only the n costs
@@ -436,20 +446,20 @@ int train_pq_resident(float *dC, uint8_t *dcodes, const float *dX, int64_t n, in
 // the same for 1 <= h <= RQ_MAX_H16 and zero-based int16 codes: what rq_train_pq_wide runs between its upload and download
 int train_pq_resident_wide(float *dC, int16_t *dcodes, const float *dX, int64_t n, int d, int m, int h, int niter, uint64_t seed);
 // ---- database norms of additive-quantizer search (rq_norms.hip) -------------------------------------
-int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
-// norm_codes [n] u8 and / or dbnorms [n] = cbnorms[code] (either may be null); cbnorms [hn <= 256], unsorted
+// Code: uint8_t (2 <= h <= 256) or int16_t (zero-based and in range, 2 <= h <= RQ_MAX_H16)
+template <class Code>
+RQ_LOCAL int aq_norms_launch(float *norms, const Code *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
+// norm_codes [n] and / or dbnorms [n] = cbnorms[code] (either may be null); cbnorms [hn], unsorted: hn <= 256 for u8 norm codes
+// (the table in static LDS), hn <= RQ_MAX_H16 for int16 ones (dynamic LDS)
 int quantize_norms_launch(uint8_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
                           hipStream_t stream);
-// the same over int16 codes: codes zero-based and in range, 2 <= h <= RQ_MAX_H16; hn <= RQ_MAX_H16
-int aq_norms_h16_launch(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream);
-int quantize_norms_h16_launch(int16_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
-                              hipStream_t stream);
+int quantize_norms_launch(int16_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
+                          hipStream_t stream);
 // ---- ERVQ (rq_train.hip: the increment shares update_centers' segment sum; rq_ervq.hip: epilogue and loop) -------------------
-int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
-                          int col, int h, int num_cu, hipStream_t stream);
-// the same over int16 codes (zero-based, read zero-extended), 1 <= h <= RQ_MAX_H16
-RQ_LOCAL int ervq_increment_h16_launch(float *Cj, unsigned int *counts, const float *E, const int16_t *codes, int64_t n, int d,
-                                       int cstride, int col, int h, int num_cu, hipStream_t stream);
+// Code: uint8_t (1 <= h <= 256) or int16_t (zero-based, read zero-extended, 1 <= h <= RQ_MAX_H16)
+template <class Code>
+RQ_LOCAL int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const Code *codes, int64_t n, int d, int cstride,
+                                   int col, int h, int num_cu, hipStream_t stream);
 
 // ---- LSQ encoding (rq_icm.hip): argument checks, and the device body of rq_dev_encode_icm (codes already in range) -----
 int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t stream, const char *who);   // codes [n][m] < h

@@ -116,33 +116,10 @@ __global__ __launch_bounds__(256) void quantize_norms_kernel(uint8_t *norm_codes
   }
 }
 
-int norms_check_shape(const char *who, int64_t n, int d, int m, int h) {
-  if (m < 1 || m > 64) return fail(RQ_EINVAL, "%s: m=%d outside 1..64", who, m);
-  if (h < 2 || h > 256) return fail(RQ_EINVAL, "%s: h=%d outside 2..256", who, h);
-  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
-  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
-  return RQ_OK;
-}
-
-int norms_check_hn(const char *who, int hn) {
-  if (hn < 1 || hn > 256) return fail(RQ_EINVAL, "%s: hn=%d outside 1..256", who, hn);
-  return RQ_OK;
-}
-
-int norms_check_wide(const char *who, int64_t n, int d, int m, int h, int hn, int code_base) {
-  if (m < 1 || m > 64) return fail(RQ_EINVAL, "%s: m=%d outside 1..64", who, m);
-  if (h < 2 || h > RQ_MAX_H16) return fail(RQ_EINVAL, "%s: h=%d outside 2..%d", who, h, RQ_MAX_H16);
-  if (hn < 1 || hn > RQ_MAX_H16) return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, hn, RQ_MAX_H16);
-  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
-  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
-  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
-  return RQ_OK;
-}
-
 }  // namespace
 
 template <class Code>
-static int aq_norms_run(float *norms, const Code *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+int aq_norms_launch(float *norms, const Code *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
   if (n <= 0) return RQ_OK;
   // one wavefront per NR rows, in row slices of at most LAUNCH_MAX_THREADS threads (2^27 rows)
   const int64_t rows = LAUNCH_MAX_THREADS / 64 * NR;
@@ -155,17 +132,11 @@ static int aq_norms_run(float *norms, const Code *codes, const float *C, int64_t
   }
   return RQ_OK;
 }
+template int aq_norms_launch(float *, const uint8_t *, const float *, int64_t, int, int, int, hipStream_t);
+template int aq_norms_launch(float *, const int16_t *, const float *, int64_t, int, int, int, hipStream_t);
 
-int aq_norms_launch(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
-  return aq_norms_run(norms, codes, C, n, d, m, h, stream);
-}
-
-int aq_norms_h16_launch(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
-  return aq_norms_run(norms, codes, C, n, d, m, h, stream);
-}
-
-int quantize_norms_h16_launch(int16_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
-                              hipStream_t stream) {
+int quantize_norms_launch(int16_t *norm_codes, float *dbnorms, const float *norms, const float *cbnorms, int64_t n, int hn,
+                          hipStream_t stream) {
   if (n <= 0) return RQ_OK;
   const size_t lds = (size_t)hn * 4;         // hn <= RQ_MAX_H16: 128 KiB at most
   if (lds > 64 * 1024)
@@ -186,33 +157,165 @@ int quantize_norms_launch(uint8_t *norm_codes, float *dbnorms, const float *norm
   return RQ_OK;
 }
 
-// codes and codebooks of a host-pointer call on the device, and the norms computed from them
-struct NormsOnDevice {
-  DevMem codes, C, norms;
-  int run(const uint8_t *hcodes, const float *hC, int64_t n, int d, int m, int h) {
-    RQ_TRY(codes.alloc((size_t)n * m)); RQ_TRY(C.alloc((size_t)m * h * d * 4)); RQ_TRY(norms.alloc((size_t)n * 4));
-    RQ_HIP(hipMemcpy(codes.p, hcodes, (size_t)n * m, hipMemcpyHostToDevice));
-    RQ_HIP(hipMemcpy(C.p, hC, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
-    return aq_norms_launch(norms.as<float>(), codes.as<uint8_t>(), C.as<float>(), n, d, m, h, nullptr);
+namespace {
+
+// ---- what the entry points below take from the width of a code -------------------------------------------------------------------
+// Bytes: 2 <= h <= 256, 1 <= hn <= 256, zero-based codes, their range checked where they arrive (on the host for host pointers,
+// by dev_code_range for device pointers).  int16 (the *_wide entries): 2 <= h, 1 <= hn <= RQ_MAX_H16,
+// codes made zero-based and checked against [0, h) on the device before any other work (check_codes_h16).
+template <class Code> struct NormsWidth;
+template <> struct NormsWidth<uint8_t> {
+  static constexpr int MAX_H = 256;
+  static constexpr bool HN_FIRST = false;
+  static int host_range(const char *who, const uint8_t *codes, int64_t n, int m, int h) { return host_code_range(codes, n, m, h, who); }
+  static int uploaded_range(const char *, uint8_t *, int64_t, int, int, int) { return RQ_OK; }
+  static int dev_range(const char *who, const uint8_t *codes, int64_t n, int m, int h, hipStream_t s) {
+    return dev_code_range(codes, n, m, h, s, who);
+  }
+  static int train(float *dC, uint8_t *dcodes, const float *dX, int64_t n, int hn, int niter, uint64_t seed) {
+    return train_pq_resident(dC, dcodes, dX, n, 1, 1, hn, niter, seed);
+  }
+};
+template <> struct NormsWidth<int16_t> {
+  static constexpr int MAX_H = RQ_MAX_H16;
+  static constexpr bool HN_FIRST = true;
+  static int host_range(const char *, const int16_t *, int64_t, int, int) { return RQ_OK; }
+  static int uploaded_range(const char *who, int16_t *dcodes, int64_t n, int m, int h, int code_base) {
+    DevMem bad;
+    RQ_TRY(bad.alloc(8));
+    return check_codes_h16(who, dcodes, bad.as<unsigned long long>(), n, m, h, code_base, nullptr);
+  }
+  // every code in [0, h): one word, read back before any other work is queued (code_base 0: the codes are only read)
+  static int dev_range(const char *who, const int16_t *codes, int64_t n, int m, int h, hipStream_t s) {
+    if (((uintptr_t)codes & 1) != 0) return fail(RQ_EINVAL, "%s: codes must be 2-byte aligned", who);
+    void *wf = nullptr;
+    RQ_TRY(workspace(WS_TMP, 256, &wf, s));
+    return check_codes_h16(who, const_cast<int16_t *>(codes), (unsigned long long *)wf, n, m, h, 0, s);
+  }
+  // the byte loop, widened, at hn <= 256 like rq_train_pq_wide
+  static int train(float *dC, int16_t *dcodes, const float *dX, int64_t n, int hn, int niter, uint64_t seed) {
+    return train_pq_resident_wide(dC, dcodes, dX, n, 1, 1, hn, niter, seed);
   }
 };
 
-// the same for int16 codes: made zero-based and checked against [0, h) on the device before any other work
-struct NormsOnDeviceWide {
-  DevMem codes, C, norms, bad;
-  int run(const char *who, const int16_t *hcodes, const float *hC, int64_t n, int d, int m, int h, int code_base) {
-    RQ_TRY(codes.alloc((size_t)n * m * 2)); RQ_TRY(C.alloc((size_t)m * h * d * 4)); RQ_TRY(norms.alloc((size_t)n * 4));
-    RQ_TRY(bad.alloc(8));
-    RQ_HIP(hipMemcpy(codes.p, hcodes, (size_t)n * m * 2, hipMemcpyHostToDevice));
-    RQ_TRY(prepare_codes_h16_launch(codes.as<int16_t>(), bad.as<unsigned long long>(), n, m, h, code_base, nullptr));
-    unsigned long long first_bad = 0;
-    RQ_HIP(hipMemcpy(&first_bad, bad.p, 8, hipMemcpyDeviceToHost));
-    if (first_bad != ~0ull)
-      return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d]", who, first_bad, code_base, h - 1 + code_base);
+template <class Code>
+int norms_check_hn(const char *who, int hn) {
+  constexpr int MAX_H = NormsWidth<Code>::MAX_H;
+  if (hn < 1 || hn > MAX_H) return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, hn, MAX_H);
+  return RQ_OK;
+}
+
+template <class Code>
+int norms_check(const char *who, int64_t n, int d, int m, int h, int hn, int code_base) {
+  constexpr int MAX_H = NormsWidth<Code>::MAX_H;
+  if (m < 1 || m > 64) return fail(RQ_EINVAL, "%s: m=%d outside 1..64", who, m);
+  if (h < 2 || h > MAX_H) return fail(RQ_EINVAL, "%s: h=%d outside 2..%d", who, h, MAX_H);
+  if (NormsWidth<Code>::HN_FIRST) RQ_TRY(norms_check_hn<Code>(who, hn));   // the int16 entries name a bad hn before a bad d or n,
+  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);               // the byte entries after
+  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
+  RQ_TRY(norms_check_hn<Code>(who, hn));
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  return RQ_OK;
+}
+
+// codes and codebooks of a host-pointer call on the device, and the norms computed from them
+template <class Code>
+struct NormsOnDevice {
+  DevMem codes, C, norms;
+  float *out() { return norms.as<float>(); }
+  int run(const char *who, const Code *hcodes, const float *hC, int64_t n, int d, int m, int h, int code_base) {
+    const size_t cb = (size_t)n * m * sizeof(Code);
+    RQ_TRY(codes.alloc(cb)); RQ_TRY(C.alloc((size_t)m * h * d * 4)); RQ_TRY(norms.alloc((size_t)n * 4));
+    RQ_HIP(hipMemcpy(codes.p, hcodes, cb, hipMemcpyHostToDevice));
+    RQ_TRY(NormsWidth<Code>::uploaded_range(who, codes.as<Code>(), n, m, h, code_base));
     RQ_HIP(hipMemcpy(C.p, hC, (size_t)m * h * d * 4, hipMemcpyHostToDevice));
-    return aq_norms_h16_launch(norms.as<float>(), codes.as<int16_t>(), C.as<float>(), n, d, m, h, nullptr);
+    return aq_norms_launch<Code>(norms.as<float>(), codes.as<Code>(), C.as<float>(), n, d, m, h, nullptr);
   }
 };
+
+// ---- the five entry points, once; `who` names the extern "C" function, the byte ones pass code_base = 0 ----------------------------
+template <class Code>
+int dev_aq_norms(const char *who, float *norms, const Code *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
+  RQ_TRY(norms_check<Code>(who, n, d, m, h, 1, 0));
+  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "%s: null pointer", who);
+  if (n == 0) return RQ_OK;
+  hipStream_t s = (hipStream_t)stream;
+  RQ_TRY(NormsWidth<Code>::dev_range(who, codes, n, m, h, s));
+  return aq_norms_launch<Code>(norms, codes, C, n, d, m, h, s);
+}
+
+template <class Code>
+int host_aq_norms(const char *who, float *norms, const Code *codes, const float *C, int64_t n, int d, int m, int h, int code_base) {
+  RQ_TRY(norms_check<Code>(who, n, d, m, h, 1, code_base));
+  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "%s: null pointer", who);
+  RQ_TRY(NormsWidth<Code>::host_range(who, codes, n, m, h));
+  if (n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDevice<Code> dv;
+  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(norms, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+template <class Code>
+int dev_quantize_norms(const char *who, Code *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n,
+                       int hn, void *stream) {
+  RQ_TRY(norms_check_hn<Code>(who, hn));
+  if (n < 0) return fail(RQ_EINVAL, "%s: n=%lld < 0", who, (long long)n);
+  if (!cbnorms || (n > 0 && (!norm_codes || !norms))) return fail(RQ_EINVAL, "%s: null pointer", who);
+  return quantize_norms_launch(norm_codes, dbnorms_out, norms, cbnorms, n, hn, (hipStream_t)stream);
+}
+
+template <class Code>
+int host_quantize_norms(const char *who, Code *norm_codes, float *norms_out, const Code *codes, const float *C, const float *cbnorms,
+                        int64_t n, int d, int m, int h, int hn, int code_base) {
+  RQ_TRY(norms_check<Code>(who, n, d, m, h, hn, code_base));
+  if (!cbnorms || (n > 0 && (!norm_codes || !codes || !C))) return fail(RQ_EINVAL, "%s: null pointer", who);
+  RQ_TRY(NormsWidth<Code>::host_range(who, codes, n, m, h));
+  if (n == 0) return RQ_OK;
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDevice<Code> dv;
+  DevMem dcb, dnc;
+  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n * sizeof(Code)));
+  RQ_HIP(hipMemcpy(dcb.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
+  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
+  RQ_TRY(quantize_norms_launch(dnc.as<Code>(), nullptr, dv.out(), dcb.as<float>(), n, hn, nullptr));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n * sizeof(Code), hipMemcpyDeviceToHost));
+  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+template <class Code>
+int host_get_norms_codebook(const char *who, Code *norm_codes, float *cbnorms, float *norms_out, const Code *codes, const float *C,
+                            int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed, int code_base) {
+  RQ_TRY(norms_check<Code>(who, n, d, m, h, hn, code_base));
+  if (niter < 0) return fail(RQ_EINVAL, "%s: niter=%d < 0", who, niter);
+  if (n < hn) return fail(RQ_EINVAL, "%s: fewer rows (%lld) than norm codebook entries (%d)", who, (long long)n, hn);
+  if (!norm_codes || !cbnorms || !codes || !C) return fail(RQ_EINVAL, "%s: null pointer", who);
+  RQ_TRY(NormsWidth<Code>::host_range(who, codes, n, m, h));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  NormsOnDevice<Code> dv;
+  DevMem dcb, dnc;
+  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n * sizeof(Code)));
+  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_TRY(NormsWidth<Code>::train(dcb.as<float>(), dnc.as<Code>(), dv.out(), n, hn, niter, seed));
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(cbnorms, dcb.p, (size_t)hn * 4, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n * sizeof(Code), hipMemcpyDeviceToHost));
+  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+}  // namespace
 
 }  // namespace rq
 
@@ -221,167 +324,44 @@ using namespace rq;
 extern "C" {
 
 int rq_dev_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
-  RQ_TRY(norms_check_shape("rq_dev_aq_norms", n, d, m, h));
-  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "rq_dev_aq_norms: null pointer");
-  if (n == 0) return RQ_OK;
-  hipStream_t s = (hipStream_t)stream;
-  RQ_TRY(dev_code_range(codes, n, m, h, s, "rq_dev_aq_norms"));
-  return aq_norms_launch(norms, codes, C, n, d, m, h, s);
+  return dev_aq_norms("rq_dev_aq_norms", norms, codes, C, n, d, m, h, stream);
 }
-
 int rq_aq_norms(float *norms, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h) {
-  RQ_TRY(norms_check_shape("rq_aq_norms", n, d, m, h));
-  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "rq_aq_norms: null pointer");
-  RQ_TRY(host_code_range(codes, n, m, h, "rq_aq_norms"));
-  if (n == 0) return RQ_OK;
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  NormsOnDevice dv;
-  RQ_TRY(dv.run(codes, C, n, d, m, h));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(norms, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
+  return host_aq_norms("rq_aq_norms", norms, codes, C, n, d, m, h, 0);
 }
-
 int rq_dev_quantize_norms(uint8_t *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n,
                           int hn, void *stream) {
-  RQ_TRY(norms_check_hn("rq_dev_quantize_norms", hn));
-  if (n < 0) return fail(RQ_EINVAL, "rq_dev_quantize_norms: n=%lld < 0", (long long)n);
-  if (!cbnorms || (n > 0 && (!norm_codes || !norms))) return fail(RQ_EINVAL, "rq_dev_quantize_norms: null pointer");
-  return quantize_norms_launch(norm_codes, dbnorms_out, norms, cbnorms, n, hn, (hipStream_t)stream);
+  return dev_quantize_norms("rq_dev_quantize_norms", norm_codes, dbnorms_out, norms, cbnorms, n, hn, stream);
 }
-
 int rq_quantize_norms(uint8_t *norm_codes, float *norms_out, const uint8_t *codes, const float *C, const float *cbnorms,
                       int64_t n, int d, int m, int h, int hn) {
-  RQ_TRY(norms_check_shape("rq_quantize_norms", n, d, m, h));
-  RQ_TRY(norms_check_hn("rq_quantize_norms", hn));
-  if (!cbnorms || (n > 0 && (!norm_codes || !codes || !C))) return fail(RQ_EINVAL, "rq_quantize_norms: null pointer");
-  RQ_TRY(host_code_range(codes, n, m, h, "rq_quantize_norms"));
-  if (n == 0) return RQ_OK;
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  NormsOnDevice dv;
-  DevMem dcb, dnc;
-  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n));
-  RQ_HIP(hipMemcpy(dcb.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
-  RQ_TRY(dv.run(codes, C, n, d, m, h));
-  RQ_TRY(quantize_norms_launch(dnc.as<uint8_t>(), nullptr, dv.norms.as<float>(), dcb.as<float>(), n, hn, nullptr));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n, hipMemcpyDeviceToHost));
-  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
+  return host_quantize_norms("rq_quantize_norms", norm_codes, norms_out, codes, C, cbnorms, n, d, m, h, hn, 0);
 }
-
 int rq_get_norms_codebook(uint8_t *norm_codes, float *cbnorms, float *norms_out, const uint8_t *codes, const float *C,
                           int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed) {
-  RQ_TRY(norms_check_shape("rq_get_norms_codebook", n, d, m, h));
-  RQ_TRY(norms_check_hn("rq_get_norms_codebook", hn));
-  if (niter < 0) return fail(RQ_EINVAL, "rq_get_norms_codebook: niter=%d < 0", niter);
-  if (n < hn) return fail(RQ_EINVAL, "rq_get_norms_codebook: fewer rows (%lld) than norm codebook entries (%d)", (long long)n, hn);
-  if (!norm_codes || !cbnorms || !codes || !C) return fail(RQ_EINVAL, "rq_get_norms_codebook: null pointer");
-  RQ_TRY(host_code_range(codes, n, m, h, "rq_get_norms_codebook"));
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  NormsOnDevice dv;
-  DevMem dcb, dnc;
-  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n));
-  RQ_TRY(dv.run(codes, C, n, d, m, h));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_TRY(train_pq_resident(dcb.as<float>(), dnc.as<uint8_t>(), dv.norms.as<float>(), n, 1, 1, hn, niter, seed));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(cbnorms, dcb.p, (size_t)hn * 4, hipMemcpyDeviceToHost));
-  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n, hipMemcpyDeviceToHost));
-  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
+  return host_get_norms_codebook("rq_get_norms_codebook", norm_codes, cbnorms, norms_out, codes, C, n, d, m, h, hn, niter, seed, 0);
 }
 
 // ---- the same five over int16 codes: 2 <= h <= RQ_MAX_H16, 1 <= hn <= RQ_MAX_H16 ---------------------
 int rq_dev_aq_norms_wide(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, void *stream) {
-  const char *who = "rq_dev_aq_norms_wide";
-  RQ_TRY(norms_check_wide(who, n, d, m, h, 1, 0));
-  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "%s: null pointer", who);
-  if (n == 0) return RQ_OK;
-  if (((uintptr_t)codes & 1) != 0) return fail(RQ_EINVAL, "%s: codes must be 2-byte aligned", who);
-  hipStream_t s = (hipStream_t)stream;
-  // every code in [0, h): one word, read back before any other work is queued (code_base 0: the codes are only read)
-  void *wf = nullptr;
-  RQ_TRY(workspace(WS_TMP, 256, &wf, s));
-  RQ_TRY(prepare_codes_h16_launch(const_cast<int16_t *>(codes), (unsigned long long *)wf, n, m, h, 0, s));
-  unsigned long long first_bad = 0;
-  RQ_HIP(hipMemcpyAsync(&first_bad, wf, 8, hipMemcpyDeviceToHost, s));
-  RQ_HIP(hipStreamSynchronize(s));
-  if (first_bad != ~0ull) return fail(RQ_EINVAL, "%s: row %llu holds a code outside [0, %d]", who, first_bad, h - 1);
-  return aq_norms_h16_launch(norms, codes, C, n, d, m, h, s);
+  return dev_aq_norms("rq_dev_aq_norms_wide", norms, codes, C, n, d, m, h, stream);
 }
-
 int rq_aq_norms_wide(float *norms, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, int code_base) {
-  const char *who = "rq_aq_norms_wide";
-  RQ_TRY(norms_check_wide(who, n, d, m, h, 1, code_base));
-  if (n > 0 && (!norms || !codes || !C)) return fail(RQ_EINVAL, "%s: null pointer", who);
-  if (n == 0) return RQ_OK;
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  NormsOnDeviceWide dv;
-  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(norms, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
+  return host_aq_norms("rq_aq_norms_wide", norms, codes, C, n, d, m, h, code_base);
 }
-
 int rq_dev_quantize_norms_wide(int16_t *norm_codes, float *dbnorms_out, const float *norms, const float *cbnorms, int64_t n,
                                int hn, void *stream) {
-  const char *who = "rq_dev_quantize_norms_wide";
-  RQ_TRY(norms_check_wide(who, n, 1, 1, 2, hn, 0));
-  if (!cbnorms || (n > 0 && (!norm_codes || !norms))) return fail(RQ_EINVAL, "%s: null pointer", who);
-  return quantize_norms_h16_launch(norm_codes, dbnorms_out, norms, cbnorms, n, hn, (hipStream_t)stream);
+  return dev_quantize_norms("rq_dev_quantize_norms_wide", norm_codes, dbnorms_out, norms, cbnorms, n, hn, stream);
 }
-
 int rq_quantize_norms_wide(int16_t *norm_codes, float *norms_out, const int16_t *codes, const float *C, const float *cbnorms,
                            int64_t n, int d, int m, int h, int hn, int code_base) {
-  const char *who = "rq_quantize_norms_wide";
-  RQ_TRY(norms_check_wide(who, n, d, m, h, hn, code_base));
-  if (!cbnorms || (n > 0 && (!norm_codes || !codes || !C))) return fail(RQ_EINVAL, "%s: null pointer", who);
-  if (n == 0) return RQ_OK;
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  NormsOnDeviceWide dv;
-  DevMem dcb, dnc;
-  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n * 2));
-  RQ_HIP(hipMemcpy(dcb.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
-  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
-  RQ_TRY(quantize_norms_h16_launch(dnc.as<int16_t>(), nullptr, dv.norms.as<float>(), dcb.as<float>(), n, hn, nullptr));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n * 2, hipMemcpyDeviceToHost));
-  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
+  return host_quantize_norms("rq_quantize_norms_wide", norm_codes, norms_out, codes, C, cbnorms, n, d, m, h, hn, code_base);
 }
-
 int rq_get_norms_codebook_wide(int16_t *norm_codes, float *cbnorms, float *norms_out, const int16_t *codes, const float *C,
                                int64_t n, int d, int m, int h, int hn, int niter, uint64_t seed, int code_base) {
-  const char *who = "rq_get_norms_codebook_wide";
-  RQ_TRY(norms_check_wide(who, n, d, m, h, hn, code_base));
-  if (niter < 0) return fail(RQ_EINVAL, "%s: niter=%d < 0", who, niter);
-  if (n < hn) return fail(RQ_EINVAL, "%s: fewer rows (%lld) than norm codebook entries (%d)", who, (long long)n, hn);
-  if (!norm_codes || !cbnorms || !codes || !C) return fail(RQ_EINVAL, "%s: null pointer", who);
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  NormsOnDeviceWide dv;
-  DevMem dcb, dnc;
-  RQ_TRY(dcb.alloc((size_t)hn * 4)); RQ_TRY(dnc.alloc((size_t)n * 2));
-  RQ_TRY(dv.run(who, codes, C, n, d, m, h, code_base));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_TRY(train_pq_resident_wide(dcb.as<float>(), dnc.as<int16_t>(), dv.norms.as<float>(), n, 1, 1, hn, niter, seed));
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(cbnorms, dcb.p, (size_t)hn * 4, hipMemcpyDeviceToHost));
-  RQ_HIP(hipMemcpy(norm_codes, dnc.p, (size_t)n * 2, hipMemcpyDeviceToHost));
-  if (norms_out) RQ_HIP(hipMemcpy(norms_out, dv.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return RQ_OK;
+  return host_get_norms_codebook("rq_get_norms_codebook_wide", norm_codes, cbnorms, norms_out, codes, C, n, d, m, h, hn, niter, seed,
+                                 code_base);
 }
 
 }  // extern "C"
+

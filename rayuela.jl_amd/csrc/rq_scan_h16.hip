@@ -274,6 +274,19 @@ int prepare_codes_h16_launch(int16_t *codes, unsigned long long *first_bad, int6
   });
 }
 
+// (On the null stream hipMemcpyAsync + hipStreamSynchronize orders exactly as the blocking hipMemcpy the host entries used
+// here: both wait for the kernel above, queued on the same stream, and return with the word on the host.)
+int check_codes_h16(const char *who, int16_t *codes, unsigned long long *flag, int64_t n, int m, int h, int code_base,
+                    hipStream_t stream, const char *suffix) {
+  RQ_TRY(prepare_codes_h16_launch(codes, flag, n, m, h, code_base, stream));
+  unsigned long long first_bad = 0;
+  RQ_HIP(hipMemcpyAsync(&first_bad, flag, 8, hipMemcpyDeviceToHost, stream));
+  RQ_HIP(hipStreamSynchronize(stream));
+  if (first_bad != ~0ull)
+    return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d]%s", who, first_bad, code_base, h - 1 + code_base, suffix);
+  return RQ_OK;
+}
+
 // ---- the scan -------------------------------------------------------------------------------------------------------------
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

@@ -865,103 +865,178 @@ static int partials_reduce(T *dst, const T *src, size_t stride, int nparts, int 
   return RQ_OK;
 }
 
-// slices [grid][h*d + m*h] -> one reduced slice behind them -> means
-static int centers_finish(TrainParams p, int grid, hipStream_t stream) {
-  const size_t hd = (size_t)p.h * p.d, mh = (size_t)p.m * p.h, stride = hd + mh;
-  float *red = p.partial + (size_t)grid * stride;
-  RQ_TRY(partials_reduce<float>(red, p.partial, stride, grid, (int)hd, stream));
-  RQ_TRY(partials_reduce<unsigned int>(reinterpret_cast<unsigned int *>(red + hd), reinterpret_cast<const unsigned int *>(p.partial + hd), stride,
-                                       grid, (int)mh, stream));
-  p.partial = red;
-  hipLaunchKernelGGL(centers_finish_kernel, dim3((p.h * p.d + 255) / 256), dim3(256), 0, stream, p, 1);
-  RQ_HIP(hipGetLastError());
-  return RQ_OK;
-}
-
-int update_centers_launch(float *C, unsigned int *counts, const float *X, const uint8_t *codes, int64_t n, int d,
-                          int m, int h, int num_cu, hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
-  if (m < 1 || m > 32 || d < m || h < 1 || h > 256)
-    return fail(RQ_EUNSUPPORTED, "update_centers covers m <= 32, h <= 256 (got m=%d d=%d h=%d)", m, d, h);
-  TrainParams p{};
-  p.X = X; p.codes = codes; p.C = C; p.counts = counts; p.n = n; p.d = d; p.m = m; p.h = h; p.cs = m; p.ccol = 0;
-  split_offsets(p.off, d, m);
-  const int grid = (int)std::min<int64_t>(num_cu, (n + 1023) / 1024);
-  void *part = nullptr;
-  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * ((size_t)h * d + (size_t)m * h) * sizeof(float), &part, stream));
-  p.partial = (float *)part;
-  if (tuning("TRAIN_CENTERS_MFMA", 1) && n / std::max(1, grid) < (1 << 23) && ((n + grid - 1) / grid) * (int64_t)d * 4 < (1ll << 31)) {
-    // one-hot products on the bf16 matrix cores; a wavefront per (sub-quantizer, 16-dimension block), 8 of them per workgroup.
-    // (counts ride in f32 accumulators: exact below 2^24 rows per slice)
-    int nunits = 0;
-    for (int q = 0; q < m; ++q) nunits += (p.off[q + 1] - p.off[q] + 15) / 16;
-    const int nslice = grid;
-    const dim3 g3(nslice, (nunits + 7) / 8);
-    if (h <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
-    else if (h <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
-    else hipLaunchKernelGGL((centers_mfma_kernel<16, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
-    RQ_HIP(hipGetLastError());
-    return centers_finish(p, grid, stream);
-  }
-  // dimension chunks of <= 128: h * 128 * 4 B of sums (+ m * h counters in the first chunk) always fit the LDS
-  for (int dc0 = 0; dc0 < d; dc0 += 128) {
-    const int dcw = std::min(128, d - dc0);
-    const size_t lds = ((size_t)h * dcw + (size_t)m * h) * sizeof(float);
-    RQ_LAUNCH_LDS(centers_partial_kernel, dim3(grid), dim3(1024), lds, stream, p, dc0, dcw);
-  }
-  return centers_finish(p, grid, stream);
-}
-
-// update_centers over 16-bit codes: codes [n][m] int16 zero-based, read zero-extended; 1 <= h <=
-// RQ_MAX_H16, 1 <= m <= 32, any d >= m, any n.  One kernel, centers_mfma_kernel<NT, int16_t>: ceil(h / 256) code blocks times the
-// byte kernel's units, so the row slices that the byte launch needs to fill the device shrink in proportion:
+// ---- the segment sum of update_centers and of the ERVQ increment: one plan and one launch for both code widths ------------------
+// Bytes (1 <= h <= 256): one block of codes, a wavefront per (sub-quantizer, 16-dimension block), 8 of them per workgroup, the
+// rows cut into one slice per CU, at most one per 1024 rows.  (Counts ride in f32 accumulators: exact below 2^24 rows per slice.)
+// 16-bit codes (int16 zero-based, read zero-extended, 1 <= h <= RQ_MAX_H16): ceil(h / 256) code blocks
+// times the byte kernel's units, so the row slices that the byte launch needs to fill the device shrink in proportion:
 //   slices = ceil(num_cu / code blocks), at most one per 1024 rows,
 //            at least what keeps a slice below 2^23 rows (f32 counters) and 2^30 bytes of X (32-bit buffer offsets),
 //            at most what keeps the partials ((slices + 1) x (h d + m h) floats) inside CENTERS_H16_SCRATCH_BYTES;
-// a shape whose single slice does not fit is refused.  The reduction over the slices and the means are the byte path's
-// (partials_reduce_kernel, centers_finish_kernel): the same fixed order, C = s * (1.0f / (float)c), no float atomics.  A row
-// whose code lies outside [0, h) is ignored in that sub-space.
+// a shape whose single slice does not fit is refused.  A row whose code lies outside [0, h) is ignored in that sub-space.
+// The ERVQ increment is ONE sub-quantizer of width d, read at a code stride and column of its own: its slices also respect the
+// row cap (the byte update_centers falls back to the owner-thread kernel instead), and over 16-bit codes the 2^30 bytes of codes.
+// The slice count fixes the order of the float reduction, so the four rules below decide the output bits: DESIGN.md section 4.19
+// tabulates them, tests/test_centers_plan.py pins them (rq_centers_plan reads this planner out).
 constexpr size_t CENTERS_H16_SCRATCH_BYTES = (size_t)2 << 30;   // per device and stream, as the other wide paths
-int update_centers_h16_launch(float *C, unsigned int *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
-                              int num_cu, hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
+
+struct CentersPlan {
+  int rc = RQ_OK;       // what the launcher returns without launching, if not RQ_OK
+  int path = 0;         // 1: centers_mfma_kernel, 2: centers_partial_kernel (byte update_centers only)
+  int slices = 0;       // row slices = gridDim.x = partial sums to reduce
+  int nunits = 0;       // (sub-quantizer, 16-dimension block) units per block of 256 codes
+  int nblocks = 0;      // blocks of 256 codes
+  int nfull = 0;        // of them launched together with 16 tiles
+  int last_nt = 0;      // tile count of the ragged last block (the byte launch is one such block); 0: there is none
+  size_t ws_bytes = 0;  // WS_TMP: (slices + 1) x (h d + m h) floats
+};
+
+// m = 1 and cstride > 0: the ERVQ increment; cstride == 0: update_centers.  The arguments have passed the caller's checks.
+static CentersPlan centers_plan(int64_t n, int d, int m, int h, int num_cu, bool wide, int cstride) {
+  const bool inc = cstride > 0;
+  const char *who = inc ? "ervq increment" : "update_centers";
+  CentersPlan pl;
+  // rows of one slice: f32 counters, 32-bit buffer offsets into X (and, for the increment over 16-bit codes, into the codes)
+  int64_t cap = std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4));
+  if (inc && wide) cap = std::min<int64_t>(cap, (1ll << 30) / ((int64_t)cstride * 2));
+  if (inc && !wide && cap < 64) { pl.rc = fail(RQ_EUNSUPPORTED, "ervq increment: d=%d", d); return pl; }
+  if (inc && wide && (cap < 64 || (int64_t)h * d >= (1ll << 31))) { pl.rc = fail(RQ_EUNSUPPORTED, "ervq increment: d=%d h=%d", d, h); return pl; }
+  const int nblocks = (h + 255) / 256;
+  const size_t stride = (size_t)h * d + (size_t)m * h;
+  const int64_t want = std::min<int64_t>((num_cu + nblocks - 1) / nblocks, (n + 1023) / 1024);
+  int64_t slices = want;
+  if (wide) {
+    const int64_t most = (int64_t)(CENTERS_H16_SCRATCH_BYTES / 5 * 4 / (stride * sizeof(float))) - 1;   // (workspace() allocates 1.25x)
+    const int64_t least = cap > 0 ? (n + cap - 1) / cap : most + 1;
+    if (least > most || most > INT32_MAX) {
+      pl.rc = fail(RQ_EUNSUPPORTED, "%s over 16-bit codes: n=%lld d=%d h=%d needs more than %zu bytes of partial sums", who,
+                   (long long)n, d, h, CENTERS_H16_SCRATCH_BYTES);
+      return pl;
+    }
+    slices = std::min(std::max(std::max<int64_t>(want, 1), least), most);
+  } else if (inc) {
+    slices = std::max(want, (n + cap - 1) / cap);
+  }
+  int off[33];
+  split_offsets(off, d, m);
+  int nunits = 0;
+  for (int q = 0; q < m; ++q) nunits += (off[q + 1] - off[q] + 15) / 16;
+  if (wide && (int64_t)nunits * nblocks > 8 * 65535ll) {      // gridDim.y
+    pl.rc = fail(RQ_EUNSUPPORTED, "%s over 16-bit codes: d=%d h=%d", who, d, h);
+    return pl;
+  }
+  pl.slices = (int)slices;
+  pl.ws_bytes = (size_t)(pl.slices + 1) * stride * sizeof(float);
+  const int grid = pl.slices;
+  if (!wide && !inc &&
+      !(tuning("TRAIN_CENTERS_MFMA", 1) && n / std::max(1, grid) < (1 << 23) && ((n + grid - 1) / grid) * (int64_t)d * 4 < (1ll << 31))) {
+    pl.path = 2;
+    return pl;
+  }
+  // The full blocks of 256 codes run with 16 tiles; a ragged last block with the tile count of its own codes.  Every (slice, code)
+  // pair of the partials is written: block b's units cover its codes below h for every dimension.
+  const int last = h - 256 * (nblocks - 1);
+  pl.path = 1;
+  pl.nunits = nunits;
+  pl.nblocks = nblocks;
+  pl.nfull = wide && last == 256 ? nblocks : nblocks - 1;
+  pl.last_nt = pl.nfull == nblocks ? 0 : last <= 64 ? 4 : last <= 128 ? 8 : 16;
+  return pl;
+}
+
+// the argument checks of the two launchers, in the order and with the return codes each width always had
+static int update_centers_check(bool wide, int d, int m, int h) {
+  if (!wide) {
+    if (m < 1 || m > 32 || d < m || h < 1 || h > 256)
+      return fail(RQ_EUNSUPPORTED, "update_centers covers m <= 32, h <= 256 (got m=%d d=%d h=%d)", m, d, h);
+    return RQ_OK;
+  }
   if (m < 1 || m > 32 || h < 1 || h > RQ_MAX_H16)
     return fail(RQ_EUNSUPPORTED, "update_centers over 16-bit codes covers m <= 32, h <= %d (got m=%d h=%d)", RQ_MAX_H16, m, h);
   if (d < m) return fail(RQ_EINVAL, "update_centers: d=%d < m=%d", d, m);
+  return RQ_OK;
+}
+
+static int ervq_increment_check(bool wide, int d, int h, int cstride, int col) {
+  if (d < 1 || h < 1 || h > (wide ? RQ_MAX_H16 : 256) || cstride < 1 || col < 0 || col >= cstride)
+    return fail(RQ_EINVAL, "ervq increment: d=%d h=%d stride=%d column=%d", d, h, cstride, col);
+  return RQ_OK;
+}
+
+// rq_centers_plan: what the launchers below would do, without a device
+void centers_plan_readout(int64_t n, int d, int m, int h, int num_cu, int code_bytes, int cstride, int64_t out[8]) {
+  const bool wide = code_bytes == 2;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (cstride == 0 && n <= 0) return;                    // update_centers returns before it looks at the shape
+  out[0] = cstride ? ervq_increment_check(wide, d, h, cstride, 0) : update_centers_check(wide, d, m, h);
+  if (out[0] != RQ_OK || n <= 0) return;
+  const CentersPlan pl = centers_plan(n, d, cstride ? 1 : m, h, num_cu, wide, cstride);
+  out[0] = pl.rc; out[1] = pl.path; out[2] = pl.slices; out[3] = pl.nunits; out[4] = pl.nblocks; out[5] = pl.nfull;
+  out[6] = pl.last_nt; out[7] = (int64_t)pl.ws_bytes;
+}
+
+// slices [grid][h*d + m*h] -> one reduced slice behind them, in partials_reduce_kernel's fixed order; *red <- that slice
+static int centers_reduce(const TrainParams &p, int grid, float **red, hipStream_t stream) {
+  const size_t hd = (size_t)p.h * p.d, mh = (size_t)p.m * p.h, stride = hd + mh;
+  *red = p.partial + (size_t)grid * stride;
+  RQ_TRY(partials_reduce<float>(*red, p.partial, stride, grid, (int)hd, stream));
+  return partials_reduce<unsigned int>(reinterpret_cast<unsigned int *>(*red + hd), reinterpret_cast<const unsigned int *>(p.partial + hd),
+                                       stride, grid, (int)mh, stream);
+}
+
+// The one-hot products of a plan on the bf16 matrix cores, then the reduction over its slices.  p.partial: the plan's WS_TMP bytes.
+template <class Code>
+static int segment_sums_launch(const TrainParams &p, const CentersPlan &pl, float **red, hipStream_t stream) {
+  if (pl.nfull > 0)
+    hipLaunchKernelGGL((centers_mfma_kernel<16, Code>), dim3(pl.slices, (pl.nunits * pl.nfull + 7) / 8), dim3(512), 0, stream, p, pl.nunits, 0,
+                       pl.nfull);
+  if (pl.last_nt) {
+    const dim3 g3(pl.slices, (pl.nunits + 7) / 8);
+    if (pl.last_nt == 4) hipLaunchKernelGGL((centers_mfma_kernel<4, Code>), g3, dim3(512), 0, stream, p, pl.nunits, pl.nfull, 1);
+    else if (pl.last_nt == 8) hipLaunchKernelGGL((centers_mfma_kernel<8, Code>), g3, dim3(512), 0, stream, p, pl.nunits, pl.nfull, 1);
+    else hipLaunchKernelGGL((centers_mfma_kernel<16, Code>), g3, dim3(512), 0, stream, p, pl.nunits, pl.nfull, 1);
+  }
+  RQ_HIP(hipGetLastError());
+  return centers_reduce(p, pl.slices, red, stream);
+}
+
+// update_centers: codes [n][m], 1 <= m <= 32, any d >= m, any n.  The means are C = s * (1.0f / (float)c) in both widths, no
+// float atomics.  The byte form falls back to the owner-thread kernel where a slice would pass the matrix-core kernel's caps
+// (or with TRAIN_CENTERS_MFMA = 0).
+template <class Code>
+int update_centers_launch(float *C, unsigned int *counts, const float *X, const Code *codes, int64_t n, int d, int m, int h,
+                          int num_cu, hipStream_t stream) {
+  constexpr bool WIDE = sizeof(Code) == 2;
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(update_centers_check(WIDE, d, m, h));
+  const CentersPlan pl = centers_plan(n, d, m, h, num_cu, WIDE, 0);
+  RQ_TRY(pl.rc);
   TrainParams p{};
   p.X = X; p.codes = reinterpret_cast<const uint8_t *>(codes); p.C = C; p.counts = counts; p.n = n; p.d = d; p.m = m; p.h = h;
   p.cs = m; p.ccol = 0;
   split_offsets(p.off, d, m);
-  const int nblocks = (h + 255) / 256;
-  const size_t stride = (size_t)h * d + (size_t)m * h;
-  const int64_t cap = std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4));       // rows of one slice
-  const int64_t most = (int64_t)(CENTERS_H16_SCRATCH_BYTES / 5 * 4 / (stride * sizeof(float))) - 1;   // (workspace() allocates 1.25x)
-  const int64_t least = cap > 0 ? (n + cap - 1) / cap : most + 1;
-  if (least > most || most > INT32_MAX)
-    return fail(RQ_EUNSUPPORTED, "update_centers over 16-bit codes: n=%lld d=%d h=%d needs more than %zu bytes of partial sums",
-                (long long)n, d, h, CENTERS_H16_SCRATCH_BYTES);
-  int64_t want = std::min<int64_t>((num_cu + nblocks - 1) / nblocks, (n + 1023) / 1024);
-  const int grid = (int)std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(want, 1), least), most);
   void *part = nullptr;
-  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * stride * sizeof(float), &part, stream));
+  RQ_TRY(workspace(WS_TMP, pl.ws_bytes, &part, stream));
   p.partial = (float *)part;
-  int nunits = 0;
-  for (int q = 0; q < m; ++q) nunits += (p.off[q + 1] - p.off[q] + 15) / 16;
-  // every (slice, code) pair of the partials is written: block b's units cover its codes below h for every dimension.
-  // The full blocks of 256 codes run with 16 tiles; a ragged last block with the tile count of its own codes.
-  const int last = h - 256 * (nblocks - 1), nfull = last == 256 ? nblocks : nblocks - 1;
-  if ((int64_t)nunits * nblocks > 8 * 65535ll) return fail(RQ_EUNSUPPORTED, "update_centers over 16-bit codes: d=%d h=%d", d, h);
-  if (nfull > 0)
-    hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), dim3(grid, (nunits * nfull + 7) / 8), dim3(512), 0, stream, p, nunits, 0, nfull);
-  if (nfull < nblocks) {
-    const dim3 g3(grid, (nunits + 7) / 8);
-    if (last <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
-    else if (last <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
-    else hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
+  float *red = nullptr;
+  if (pl.path == 1) {
+    RQ_TRY(segment_sums_launch<Code>(p, pl, &red, stream));
+  } else {
+    // dimension chunks of <= 128: h * 128 * 4 B of sums (+ m * h counters in the first chunk) always fit the LDS
+    for (int dc0 = 0; dc0 < d; dc0 += 128) {
+      const int dcw = std::min(128, d - dc0);
+      const size_t lds = ((size_t)h * dcw + (size_t)m * h) * sizeof(float);
+      RQ_LAUNCH_LDS(centers_partial_kernel, dim3(pl.slices), dim3(1024), lds, stream, p, dc0, dcw);
+    }
+    RQ_TRY(centers_reduce(p, pl.slices, &red, stream));
   }
+  p.partial = red;      // the means of the one reduced slice
+  hipLaunchKernelGGL(centers_finish_kernel, dim3((p.h * p.d + 255) / 256), dim3(256), 0, stream, p, 1);
   RQ_HIP(hipGetLastError());
-  return centers_finish(p, grid, stream);
+  return RQ_OK;
 }
+template int update_centers_launch(float *, unsigned int *, const float *, const uint8_t *, int64_t, int, int, int, int, hipStream_t);
+template int update_centers_launch(float *, unsigned int *, const float *, const int16_t *, int64_t, int, int, int, int, hipStream_t);
 
 // ---- refill of emptied centres on the device (Clustering.repick_unused_centers; the rule of repick_unused, rq_train_host.hip) ----
 // Costs in f64, one thread per row, the sub-space's terms in ascending order -- the host loop of repick_unused bit for bit.
@@ -1040,122 +1115,63 @@ int gather_rows_launch(float *Csub, const float *X, const long long *rows_dev, i
 // Codebook increment of ERVQ: Cj [h][d] += the per-entry mean of E [n][d] over the rows with codes[row * cstride + col] == entry
 // (rq_ervq.hip says why this equals the reference's update); counts [h] out.  The segment sum is the one-hot bf16 x 3 product of
 // update_centers with ONE sub-quantizer of width d, read at a code stride and column of its own: same fixed order, no float
-// atomics.  Any d >= 1, 1 <= h <= 256, any n: the row slices are sized to the kernel's 32-bit offsets and f32 counters.
-int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const uint8_t *codes, int64_t n, int d, int cstride,
-                          int col, int h, int num_cu, hipStream_t stream) {
-  if (d < 1 || h < 1 || h > 256 || cstride < 1 || col < 0 || col >= cstride)
-    return fail(RQ_EINVAL, "ervq increment: d=%d h=%d stride=%d column=%d", d, h, cstride, col);
+// atomics.  Any d >= 1, any n; 1 <= h <= 256 for bytes, 1 <= h <= RQ_MAX_H16 for int16 codes (zero-based, read zero-extended;
+// DESIGN.md section 4.21): the row slices are sized to the kernel's 32-bit offsets and f32 counters (centers_plan).
+template <class Code>
+int ervq_increment_launch(float *Cj, unsigned int *counts, const float *E, const Code *codes, int64_t n, int d, int cstride, int col,
+                          int h, int num_cu, hipStream_t stream) {
+  constexpr bool WIDE = sizeof(Code) == 2;
+  RQ_TRY(ervq_increment_check(WIDE, d, h, cstride, col));
   if (n <= 0) {
     RQ_HIP(hipMemsetAsync(counts, 0, (size_t)h * sizeof(unsigned int), stream));
     return RQ_OK;
   }
-  const int64_t cap = std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4));   // rows of one slice
-  if (cap < 64) return fail(RQ_EUNSUPPORTED, "ervq increment: d=%d", d);
-  TrainParams p{};
-  p.X = E; p.codes = codes; p.n = n; p.d = d; p.m = 1; p.h = h; p.cs = cstride; p.ccol = col;
-  p.off[0] = 0; p.off[1] = d;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(num_cu, (n + 1023) / 1024), (n + cap - 1) / cap);
-  const size_t stride = (size_t)h * d + (size_t)h;
-  void *part = nullptr;
-  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * stride * sizeof(float), &part, stream));
-  p.partial = (float *)part;
-  const int nunits = (d + 15) / 16;
-  const dim3 g3(grid, (nunits + 7) / 8);
-  if (h <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
-  else if (h <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
-  else hipLaunchKernelGGL((centers_mfma_kernel<16, uint8_t>), g3, dim3(512), 0, stream, p, nunits, 0, 1);
-  RQ_HIP(hipGetLastError());
-  float *red = p.partial + (size_t)grid * stride;
-  RQ_TRY(partials_reduce<float>(red, p.partial, stride, grid, h * d, stream));
-  RQ_TRY(partials_reduce<unsigned int>(reinterpret_cast<unsigned int *>(red + (size_t)h * d),
-                                       reinterpret_cast<const unsigned int *>(p.partial + (size_t)h * d), stride, grid, h, stream));
-  hipLaunchKernelGGL(ervq_increment_finish_kernel, dim3((h * d + 255) / 256), dim3(256), 0, stream, Cj, counts, red, h, d);
-  RQ_HIP(hipGetLastError());
-  return RQ_OK;
-}
-
-// The same increment over 16-bit codes: codes int16 zero-based, read zero-extended, 1 <= h <= RQ_MAX_H16.
-// The units of update_centers_h16_launch with one sub-quantizer of width d at a code stride and column: (16 dimensions, block of
-// 256 codes), the full blocks with 16 tiles and a ragged last block with its own tile count; the row slices shrink with the
-// number of code blocks and stay inside CENTERS_H16_SCRATCH_BYTES of partials.  Reduction and finish are the byte path's.
-int ervq_increment_h16_launch(float *Cj, unsigned int *counts, const float *E, const int16_t *codes, int64_t n, int d, int cstride,
-                              int col, int h, int num_cu, hipStream_t stream) {
-  if (d < 1 || h < 1 || h > RQ_MAX_H16 || cstride < 1 || col < 0 || col >= cstride)
-    return fail(RQ_EINVAL, "ervq increment: d=%d h=%d stride=%d column=%d", d, h, cstride, col);
-  if (n <= 0) {
-    RQ_HIP(hipMemsetAsync(counts, 0, (size_t)h * sizeof(unsigned int), stream));
-    return RQ_OK;
-  }
-  // rows of one slice: f32 counters, 32-bit buffer offsets into E and into the codes
-  const int64_t cap = std::min<int64_t>(std::min<int64_t>((1 << 23) - 1, (1ll << 30) / ((int64_t)d * 4)), (1ll << 30) / ((int64_t)cstride * 2));
-  if (cap < 64 || (int64_t)h * d >= (1ll << 31)) return fail(RQ_EUNSUPPORTED, "ervq increment: d=%d h=%d", d, h);
+  const CentersPlan pl = centers_plan(n, d, 1, h, num_cu, WIDE, cstride);
+  RQ_TRY(pl.rc);
   TrainParams p{};
   p.X = E; p.codes = reinterpret_cast<const uint8_t *>(codes); p.n = n; p.d = d; p.m = 1; p.h = h; p.cs = cstride; p.ccol = col;
   p.off[0] = 0; p.off[1] = d;
-  const int nblocks = (h + 255) / 256;
-  const size_t stride = (size_t)h * d + (size_t)h;
-  const int64_t most = (int64_t)(CENTERS_H16_SCRATCH_BYTES / 5 * 4 / (stride * sizeof(float))) - 1;   // (workspace() allocates 1.25x)
-  const int64_t least = (n + cap - 1) / cap;
-  if (least > most || most > INT32_MAX)
-    return fail(RQ_EUNSUPPORTED, "ervq increment over 16-bit codes: n=%lld d=%d h=%d needs more than %zu bytes of partial sums",
-                (long long)n, d, h, CENTERS_H16_SCRATCH_BYTES);
-  const int64_t want = std::min<int64_t>((num_cu + nblocks - 1) / nblocks, (n + 1023) / 1024);
-  const int grid = (int)std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(want, 1), least), most);
   void *part = nullptr;
-  RQ_TRY(workspace(WS_TMP, (size_t)(grid + 1) * stride * sizeof(float), &part, stream));
+  RQ_TRY(workspace(WS_TMP, pl.ws_bytes, &part, stream));
   p.partial = (float *)part;
-  const int nunits = (d + 15) / 16;
-  const int last = h - 256 * (nblocks - 1), nfull = last == 256 ? nblocks : nblocks - 1;
-  if ((int64_t)nunits * nblocks > 8 * 65535ll) return fail(RQ_EUNSUPPORTED, "ervq increment over 16-bit codes: d=%d h=%d", d, h);
-  if (nfull > 0)
-    hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), dim3(grid, (nunits * nfull + 7) / 8), dim3(512), 0, stream, p, nunits, 0, nfull);
-  if (nfull < nblocks) {
-    const dim3 g3(grid, (nunits + 7) / 8);
-    if (last <= 64) hipLaunchKernelGGL((centers_mfma_kernel<4, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
-    else if (last <= 128) hipLaunchKernelGGL((centers_mfma_kernel<8, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
-    else hipLaunchKernelGGL((centers_mfma_kernel<16, int16_t>), g3, dim3(512), 0, stream, p, nunits, nfull, 1);
-  }
-  RQ_HIP(hipGetLastError());
-  float *red = p.partial + (size_t)grid * stride;
-  RQ_TRY(partials_reduce<float>(red, p.partial, stride, grid, h * d, stream));
-  RQ_TRY(partials_reduce<unsigned int>(reinterpret_cast<unsigned int *>(red + (size_t)h * d),
-                                       reinterpret_cast<const unsigned int *>(p.partial + (size_t)h * d), stride, grid, h, stream));
+  float *red = nullptr;
+  RQ_TRY(segment_sums_launch<Code>(p, pl, &red, stream));
   hipLaunchKernelGGL(ervq_increment_finish_kernel, dim3((h * d + 255) / 256), dim3(256), 0, stream, Cj, counts, red, h, d);
   RQ_HIP(hipGetLastError());
   return RQ_OK;
 }
+template int ervq_increment_launch(float *, unsigned int *, const float *, const uint8_t *, int64_t, int, int, int, int, int, hipStream_t);
+template int ervq_increment_launch(float *, unsigned int *, const float *, const int16_t *, int64_t, int, int, int, int, int, hipStream_t);
 
-int reconstruct_launch(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h,
-                       hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
-  if (m < 1 || m > 32 || d < m) return fail(RQ_EINVAL, "reconstruct: m=%d d=%d", m, d);
-  TrainParams p{};
-  p.codes = codes; p.C = const_cast<float *>(C); p.CB = CB; p.n = n; p.d = d; p.m = m; p.h = h;
-  split_offsets(p.off, d, m);
-  const int64_t total = n * d;
-  if (d > 8192) return fail(RQ_EUNSUPPORTED, "reconstruct: d=%d", d);
-  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(reconstruct_kernel<uint8_t>, dim3(grid), dim3(256), (size_t)d * 8, stream, p);
-  RQ_HIP(hipGetLastError());
-  return RQ_OK;
-}
-
-// CB[j][off_i + s] = C_i[codes[j][i]][s] from int16 codes (zero-based, read zero-extended), 1 <= h <= RQ_MAX_H16: a pure copy.
-// A code outside [0, h) is not read from C: that sub-space of the row is written as zeros.
-int reconstruct_h16_launch(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
+// CB[j][off_i + s] = C_i[codes[j][i]][s]: a pure copy.  Bytes: any h.  Code = int16_t (zero-based, read zero-extended), 1 <= h <=
+// RQ_MAX_H16: a code outside [0, h) is not read from C, that sub-space of the row is written as zeros.
+static int reconstruct_check(bool wide, int d, int m, int h) {
+  if (!wide) {
+    if (m < 1 || m > 32 || d < m) return fail(RQ_EINVAL, "reconstruct: m=%d d=%d", m, d);
+    if (d > 8192) return fail(RQ_EUNSUPPORTED, "reconstruct: d=%d", d);
+    return RQ_OK;
+  }
   if (m < 1 || m > 32 || h < 1 || h > RQ_MAX_H16)
     return fail(RQ_EUNSUPPORTED, "reconstruct over 16-bit codes covers m <= 32, h <= %d (got m=%d h=%d)", RQ_MAX_H16, m, h);
   if (d < m) return fail(RQ_EINVAL, "reconstruct: d=%d < m=%d", d, m);
   if (d > 8192 || (int64_t)h * d >= (1ll << 31)) return fail(RQ_EUNSUPPORTED, "reconstruct: d=%d h=%d", d, h);
+  return RQ_OK;
+}
+
+template <class Code>
+int reconstruct_launch(float *CB, const Code *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(reconstruct_check(sizeof(Code) == 2, d, m, h));
   TrainParams p{};
   p.codes = reinterpret_cast<const uint8_t *>(codes); p.C = const_cast<float *>(C); p.CB = CB; p.n = n; p.d = d; p.m = m; p.h = h;
   split_offsets(p.off, d, m);
   const unsigned grid = (unsigned)std::min<int64_t>((n * d + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(reconstruct_kernel<int16_t>, dim3(grid), dim3(256), (size_t)d * 8, stream, p);
+  hipLaunchKernelGGL(reconstruct_kernel<Code>, dim3(grid), dim3(256), (size_t)d * 8, stream, p);
   RQ_HIP(hipGetLastError());
   return RQ_OK;
 }
+template int reconstruct_launch(float *, const uint8_t *, const float *, int64_t, int, int, int, hipStream_t);
+template int reconstruct_launch(float *, const int16_t *, const float *, int64_t, int, int, int, hipStream_t);
 
 int qerror_launch(double *acc_dev, const float *X, const float *CB, int64_t n, int d, int num_cu,
                   hipStream_t stream) {

@@ -265,22 +265,14 @@ static int repick_unused(float *dCsub, const float *dCassigned, const float *dX,
 
 // What the training loops below take from the width of a code: the byte kernels at h <= 256, their 16-bit forms above (DESIGN.md
 // section 4.19).  One loop, instantiated twice; the byte instantiation launches what the loops launched before there was a second.
+// Encode, update_centers and reconstruct are templates / one overload set over the code type (rq_internal.h) and are called by
+// name; CodeOps holds the steps whose two forms really differ.
 struct RefillScratch {      // device refill: n doubles on the device and their host copy, made by the first refill of a call
   DevMem dtc;
   std::vector<double> tc;
 };
 template <class Code> struct CodeOps;
 template <> struct CodeOps<uint8_t> {
-  static int encode(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu, hipStream_t s) {
-    return encode_launch(codes, X, C, n, d, m, h, num_cu, s);
-  }
-  static int update(float *C, unsigned int *counts, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, int num_cu,
-                    hipStream_t s) {
-    return update_centers_launch(C, counts, X, codes, n, d, m, h, num_cu, s);
-  }
-  static int reconstruct(float *CB, const uint8_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t s) {
-    return reconstruct_launch(CB, codes, C, n, d, m, h, s);
-  }
   // emptied centres are rare at h <= 256: the host form
   static int refill(float *dCsub, const float *dCassigned, const float *dX, int64_t n, int d, int col0, int sub, const uint8_t *codes,
                     int cstride, int ci, int h, const std::vector<int> &unused, Rng &rng, RefillScratch &) {
@@ -303,16 +295,6 @@ template <> struct CodeOps<uint8_t> {
   }
 };
 template <> struct CodeOps<int16_t> {
-  static int encode(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu, hipStream_t s) {
-    return encode_h16_launch(codes, X, C, n, d, m, h, num_cu, s);
-  }
-  static int update(float *C, unsigned int *counts, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, int num_cu,
-                    hipStream_t s) {
-    return update_centers_h16_launch(C, counts, X, codes, n, d, m, h, num_cu, s);
-  }
-  static int reconstruct(float *CB, const int16_t *codes, const float *C, int64_t n, int d, int m, int h, hipStream_t s) {
-    return reconstruct_h16_launch(CB, codes, C, n, d, m, h, s);
-  }
   // emptied centres are routine at h in the thousands: costs on the device, the n costs come down per draw (same rule, same draws)
   static int refill(float *dCsub, const float *dCassigned, const float *dX, int64_t n, int d, int col0, int sub, const int16_t *codes,
                     int cstride, int ci, int h, const std::vector<int> &unused, Rng &rng, RefillScratch &rs) {
@@ -373,14 +355,14 @@ static int train_pq_loop(float *dC, Code *dcodes, const float *dX, int64_t n, in
   int iters_done = 0;
   prof.loop_begin();
   for (int it = 0; it < niter; ++it) {
-    RQ_PH(TP_ENCODE, RQ_TRY(Ops::encode(cur, dX, dC, n, d, m, h, di.num_cu, nullptr)));
+    RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(cur, dX, dC, n, d, m, h, di.num_cu, nullptr)));
     prof.start();
     if (it > 0)
       RQ_TRY(codes_changed_launch(dchg_p, reinterpret_cast<const uint8_t *>(cur), reinterpret_cast<const uint8_t *>(prev),
                                   (size_t)n * m * sizeof(Code), nullptr));
     prof.stop(TP_CONVERGE);
     RQ_HIP(hipMemcpyAsync(dCold.p, dC, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
-    RQ_PH(TP_CENTERS, RQ_TRY(Ops::update(dC, dcnt_p, dX, cur, n, d, m, h, di.num_cu, nullptr)));
+    RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch<Code>(dC, dcnt_p, dX, cur, n, d, m, h, di.num_cu, nullptr)));
     prof.start();
     RQ_HIP(hipMemcpy(back.data(), dcc.p, chg_at + 8, hipMemcpyDeviceToHost));
     unsigned long long changed = 1;
@@ -400,7 +382,7 @@ static int train_pq_loop(float *dC, Code *dcodes, const float *dX, int64_t n, in
     std::swap(cur, prev);
   }
   prof.loop_end(iters_done);      // the final encode overwrites every code: which of the two buffers the loop ended on is moot
-  RQ_PH(TP_ENCODE, RQ_TRY(Ops::encode(dcodes, dX, dC, n, d, m, h, di.num_cu, nullptr)));
+  RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(dcodes, dX, dC, n, d, m, h, di.num_cu, nullptr)));
   return RQ_OK;
 }
 
@@ -445,7 +427,7 @@ static int train_pq_host(float *C, int16_t *B1, double *error, const float *X, i
     RQ_PH(TP_QERROR, RQ_TRY(Ops::qerror_codes(dacc.as<double>(), dX.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
   } else {
     RQ_TRY(dCB.alloc((size_t)n * d * 4));
-    RQ_PH(TP_RECONSTRUCT, RQ_TRY(Ops::reconstruct(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr)));
+    RQ_PH(TP_RECONSTRUCT, RQ_TRY(reconstruct_launch<Code>(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr)));
     RQ_PH(TP_QERROR, RQ_TRY(qerror_launch(dacc.as<double>(), dX.as<float>(), dCB.as<float>(), n, d, di.num_cu, nullptr)));
   }
   int16_t *out16 = nullptr;
@@ -487,12 +469,12 @@ static int train_rvq_host(float *C, int16_t *B1, double *error, const float *X, 
     RQ_TRY(seed_centers(dCi.as<float>(), dXr.as<float>(), n, d, 1, h, off1, rng));
     prev.clear();
     for (int it = 0; it < niter; ++it) {
-      RQ_TRY(Ops::encode(dstage.as<Code>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
+      RQ_TRY(encode_launch(dstage.as<Code>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
       RQ_HIP(hipMemcpy(cur.data(), dstage.p, (size_t)n * sizeof(Code), hipMemcpyDeviceToHost));
       if (!prev.empty() && prev == cur) break;   // assignments stable: Lloyd has converged
       prev = cur;
       RQ_HIP(hipMemcpyAsync(dCold.p, dCi.p, (size_t)h * d * 4, hipMemcpyDeviceToDevice, nullptr));
-      RQ_TRY(Ops::update(dCi.as<float>(), dcnt.as<unsigned int>(), dXr.as<float>(), dstage.as<Code>(), n, d, 1, h, di.num_cu,
+      RQ_TRY(update_centers_launch<Code>(dCi.as<float>(), dcnt.as<unsigned int>(), dXr.as<float>(), dstage.as<Code>(), n, d, 1, h, di.num_cu,
                          nullptr));
       RQ_HIP(hipMemcpy(counts.data(), dcnt.p, (size_t)h * 4, hipMemcpyDeviceToHost));
       std::vector<int> unused;                   // centres that lost all their points: re-drawn like Clustering.kmeans does
@@ -502,7 +484,7 @@ static int train_rvq_host(float *C, int16_t *B1, double *error, const float *X, 
         RQ_TRY(Ops::refill(dCi.as<float>(), dCold.as<float>(), dXr.as<float>(), n, d, 0, d, dstage.as<Code>(), 1, 0, h, unused, rng, rs));
     }
     // the assignments of the final centres (what quantize_rvq would return for this stage), then the residual
-    RQ_TRY(Ops::encode(dstage.as<Code>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
+    RQ_TRY(encode_launch(dstage.as<Code>(), dXr.as<float>(), dCi.as<float>(), n, d, 1, h, di.num_cu, nullptr));
     RQ_TRY(residual_launch<Code>(dXr.as<float>(), dXr.as<float>(), dCi.as<float>(), dstage.as<Code>(), 1, dcodes.as<Code>(), nullptr,
                                  n, d, m, i, nullptr));
     RQ_HIP(hipMemcpy(C + (size_t)i * h * d, dCi.p, (size_t)h * d * 4, hipMemcpyDeviceToHost));
@@ -556,8 +538,8 @@ static int train_opq_host(float *C, int16_t *B1, float *R, float *obj, const flo
   RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX.as<float>(), d, n, di.num_cu, nullptr));
   if (C0) RQ_HIP(hipMemcpy(dC.p, C0, (size_t)h * d * 4, hipMemcpyHostToDevice));
   else RQ_TRY(init_centers(dC.as<float>(), dRX.as<float>(), n, d, m, h, off, rng));
-  RQ_TRY(Ops::encode(dcodes.as<Code>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
-  if (!fused_cb) RQ_TRY(Ops::reconstruct(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr));
+  RQ_TRY(encode_launch(dcodes.as<Code>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  if (!fused_cb) RQ_TRY(reconstruct_launch<Code>(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr));
   prof.stop(TP_INIT);
   std::vector<float> Gf((size_t)d * d);
   std::vector<double> Vwarm;   // empty on the first iteration: cold start
@@ -631,10 +613,10 @@ static int train_opq_host(float *C, int16_t *B1, float *R, float *obj, const flo
     prof.stop(TP_SVD);
     RQ_HIP(hipStreamWaitEvent(nullptr, side.done, 0));      // the objective has read RX, C (and CB)
     RQ_PH(TP_ROTATE, RQ_TRY(rotate_launch(dRX.as<float>(), dR.as<float>(), dX.as<float>(), d, n, di.num_cu, nullptr)));
-    RQ_PH(TP_CENTERS, RQ_TRY(Ops::update(dC.as<float>(), dcnt.as<unsigned int>(), dRX.as<float>(), dcodes.as<Code>(), n, d,
+    RQ_PH(TP_CENTERS, RQ_TRY(update_centers_launch<Code>(dC.as<float>(), dcnt.as<unsigned int>(), dRX.as<float>(), dcodes.as<Code>(), n, d,
                                  m, h, di.num_cu, nullptr)));
-    RQ_PH(TP_ENCODE, RQ_TRY(Ops::encode(dcodes.as<Code>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
-    if (!fused_cb) RQ_PH(TP_RECONSTRUCT, RQ_TRY(Ops::reconstruct(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr)));
+    RQ_PH(TP_ENCODE, RQ_TRY(encode_launch(dcodes.as<Code>(), dRX.as<float>(), dC.as<float>(), n, d, m, h, di.num_cu, nullptr)));
+    if (!fused_cb) RQ_PH(TP_RECONSTRUCT, RQ_TRY(reconstruct_launch<Code>(dCB.as<float>(), dcodes.as<Code>(), dC.as<float>(), n, d, m, h, nullptr)));
   }
   prof.loop_end(niter + 1);
   {

@@ -21,7 +21,7 @@ the first 4114 of 143 169 689 rows encoded and the rest untouched.  residual_lau
 aq_norms_launch (16 work-items per row: 2^28 rows) and the code-widening kernels now cut their rows into launches of at most
 2^31 work-items; test_encode_rvq_scalar_epilogue_all_rows and test_norms_past_the_work_items_of_one_launch pin it.
 
-Section 11 takes the slice planner of the wide centre update (update_centers_h16_launch) to its two caps -- 2^23 rows and 2^30
+Section 11 takes the slice planner of the wide centre update (update_centers_launch<int16_t>) to its two caps -- 2^23 rows and 2^30
 bytes of X per slice -- and to its refusal; those arrays are 0.5 and 2.1 GB, the limits are the planner's, not an index width.
 
 A GPU test skips only when the device has less free memory than the test needs (never on an MI355X: the file peaks at
@@ -744,7 +744,7 @@ def test_row_limits_are_refused_before_any_access(rq):
 
 
 # ---- 11. the slice planner of the wide centre update at its limits ----------------------------------------------------------------------------------
-# update_centers_h16_launch (rq_train.hip) cuts the rows into `grid` slices: want = min(ceil(CUs / code blocks), ceil(n / 1024)),
+# update_centers_launch<int16_t> (rq_train.hip) cuts the rows into `grid` slices: want = min(ceil(CUs / code blocks), ceil(n / 1024)),
 # raised to least = ceil(n / cap) with cap = min(2^23 - 1 rows (f32 counters), 2^30 bytes of X (32-bit buffer offsets)), capped by
 # most = the slices whose partial sums ((grid + 1) x (h d + m h) floats, allocated 1.25x) fit 2 GiB; least > most is refused.  The
 # library does not name its grid, so the cases below restate the planner and assert that the cap, not `want`, decides.
@@ -756,7 +756,7 @@ H16_SCRATCH = 2 << 30
 
 
 def _h16_plan(n, d, m, h):
-    """(want, least, most, grid) of update_centers_h16_launch for the device's CU count."""
+    """(want, least, most, grid) of update_centers_launch<int16_t> for the device's CU count."""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     nblocks = (h + 255) // 256
@@ -856,7 +856,7 @@ def test_update_centers_wide_byte_cap_forces_a_third_slice(rq, bases):
 
 def test_update_centers_wide_refuses_a_slice_that_does_not_fit(rq):
     """d = 8192, m = 1, h = 32767: ONE slice of partial sums is 1.07 GB and the reduced slice behind it as much again, past the
-    2 GiB of scratch (most = 0 slices): RQ_EUNSUPPORTED naming the shape.  update_centers_h16_launch makes that test before
+    2 GiB of scratch (most = 0 slices): RQ_EUNSUPPORTED naming the shape.  update_centers_launch<int16_t> makes that test before
     it asks for its workspace or launches anything (read in rq_train.hip), so small sentinel-filled arrays are safe."""
     import torch
     n, d, m, h = 100, 8192, 1, 32767
