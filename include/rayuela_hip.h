@@ -573,6 +573,45 @@ void rq_dataset_free(rq_dataset *ds);
 /* RX = R' * X (src/OPQ.jl:26, src/Linscan.jl:102). */
 int rq_rotate_T(float *RX, const float *R, const float *X, int d, int64_t n);
 
+/* ---- exact k-nearest-neighbour ground truth.  There is no reference function: the reference only
+ * READS ground truth, from the *_groundtruth.ivecs / gt files of src/read_datasets.jl, and consumes it in eval_recall
+ * (src/Linscan.jl:196-234); every experiment_* driver takes it as `gt`.  These entries produce it on the device.
+ *
+ * Base X [n][d] (f32, or u8 widened exactly), queries Q [nq][d] f32, every operation rounded on its own (no contraction):
+ *   D32(i, q): acc = +0; for s = 0..d-1: t = x[s] - q[s]; acc = acc + t * t   in f32 -- the arithmetic of linscan_cq's table
+ *              (deps/src/linscan_aqd_pairwise_byte.cpp:124-131) with the base as one codebook of n entries
+ *   D64(i, q): the same loop on the values widened to f64, in f64
+ * rq_knn_f32 (stage 1 alone): the k smallest (D32, id) pairs in lexicographic order, any 1 <= k <= n, keys packed as the scans pack
+ *   them and the scans' "Non-finite inputs" rules unchanged: a NaN distance is never a neighbour, -0 becomes +0, a short list ends
+ *   in the padding pair (distance bits 0x7FFFFFFF, id 0xFFFFFFFF + id_base).
+ * rq_knn / rq_knn_bytes / rq_dataset_knn (the ground truth): the k smallest (D64, id) pairs in lexicographic order, 1 <= k <=
+ *   RQ_KNN_MAX_K, dists f64, ids u32 + id_base; a pair whose D64 is NaN is never a neighbour; a list with fewer than k such rows
+ *   ends in the scans' padding id with distance +Inf.  For EVERY input: stage 1 is only a filter with a proven bound,
+ *   |D32 - D64| <= gamma D64 + delta, gamma = 2 (d + 3) 2^-24, delta = d 2^-125 (finite inputs, no f32 overflow).  Per query the
+ *   k' = min(n, k + max(32, k / 4)) stage-1 candidates are evaluated in f64; with T64 the k-th smallest D64 among them and L the
+ *   D32 of the last candidate (+Inf taken as FLT_MAX) the query is certified iff k' == n, or the candidate list ran out of
+ *   comparable rows, or L > T64 (1 + gamma) + delta in f64, strictly.  A query that is not certified is rerun with k' <- min(n, 4 k')
+ *   until it is; past k' = 4096 the D64 values go to the host and std::partial_sort finishes the query.
+ * The host-pointer forms upload the whole base (out-of-memory status if it does not fit); rq_dataset_knn runs in place on a
+ * resident base of either kind.  Synchronous on the calling thread's current device.  nq <= 0: RQ_OK.  A NULL pointer, k outside
+ * [1, n], a bad id_base, d < 1, n >= 2^31: RQ_EINVAL; k > RQ_KNN_MAX_K in the f64 entries: RQ_EUNSUPPORTED; on any error no output
+ * byte is written.
+ * rq_last_knn_stats: [0] queries, [1] candidates evaluated in f64, [2] queries widened at least once, [3] widening rounds,
+ *   [4] queries finished on the host, [5] row chunks, [6..7] 0.  rq_last_knn_timing: ms of upload, keys, select, fold, rerank,
+ *   widen, download of the calling thread's last call.  rq_knn_plan (host only): out[0] k' of the first round, [1] rows per
+ *   chunk, [2] row chunks, [3] queries per batch, [4] scratch bytes of a batch, [5] 1 when the test hook rq_test_knn_chunk_rows set [1]. */
+#define RQ_KNN_MAX_K 1024
+int rq_knn_f32(float *dists, uint32_t *ids, const float *base, const float *queries, int64_t n, int64_t nq, int d, int k,
+               int id_base);
+int rq_knn(double *dists, uint32_t *ids, const float *base, const float *queries, int64_t n, int64_t nq, int d, int k,
+           int id_base);
+int rq_knn_bytes(double *dists, uint32_t *ids, const uint8_t *base, const float *queries, int64_t n, int64_t nq, int d, int k,
+                 int id_base);
+int rq_dataset_knn(rq_dataset *ds, double *dists, uint32_t *ids, const float *queries, int64_t nq, int k, int id_base);
+int rq_last_knn_stats(uint64_t *out8);
+int rq_last_knn_timing(double *ms, int cap);
+int rq_knn_plan(int64_t n, int64_t nq, int d, int k, int64_t *out, int cap);
+
 /* ---- device-pointer entry points: asynchronous on `stream` (a hipStream_t, NULL = default).
  * All pointers are device pointers on the current device, 16-byte aligned. ------------------ */
 int rq_dev_encode_pq(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m,
@@ -936,6 +975,10 @@ int rq_test_scratch_report(void *of_stream, int64_t *bytes, int *differs, int ca
  * [5] of them launched together with 16 tiles, [6] the tile count (4, 8 or 16) of the ragged last block, 0 if there is none,
  * [7] bytes asked of the WS_TMP scratch slot. */
 int rq_centers_plan(int64_t n, int d, int m, int h, int num_cu, int code_bytes, int cstride, int64_t *out, int cap);
+/* KNN_CHUNK_ROWS of the ground-truth entries (rq_knn*): rows > 0 makes every later call of this process split the base into
+ * chunks of `rows` rows (rq_knn_plan reports it, out[5] = 1), so that a test can run the fold of per-chunk lists on a small base;
+ * rows <= 0 gives the planner its choice back.  No answer depends on it (tests/test_gpu_knn.py).  Returns the previous value. */
+int64_t rq_test_knn_chunk_rows(int64_t rows);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@ export quantize_pq, quantize_opq, quantize_rvq, linscan_pq, linscan_opq, linscan
 export quantize_ervq, train_ervq
 export quantize_competitiveq
 export get_norms_codebook, quantize_norms
+export groundtruth
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
@@ -107,6 +108,37 @@ function quantize_opq(X::Matrix{Float32}, R::Matrix{Float32}, C::Vector{Matrix{F
     (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
     B, X, R, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
   return B
+end
+
+"""
+    groundtruth(Xb::Matrix{Float32}, Xq::Matrix{Float32}, k=1) -> ids, dists
+    groundtruth(Xb::Matrix{UInt8}, Xq::Matrix{Float32}, k=1)   -> ids, dists
+The exact `k` nearest columns of `Xb` for every column of `Xq`: `ids` is a k x nq `Matrix{Int32}` of one-based ids, nearest first and
+ties by id -- what the `*_groundtruth.ivecs` files of src/read_datasets.jl hold and `eval_recall` (src/Linscan.jl:196-234) takes --
+and `dists` the squared distances accumulated coordinate by coordinate in Float64.  The reference has no such function.
+"""
+function groundtruth(Xb::Matrix{Float32}, Xq::Matrix{Float32}, k::Integer=1)
+  d, n  = size(Xb)
+  nq    = size(Xq, 2)
+  @assert size(Xq, 1) == d
+  dists = Matrix{Float64}(undef, k, nq)
+  ids   = Matrix{UInt32}(undef, k, nq)
+  _check(ccall((:rq_knn, librayuela_hip), Cint,
+    (Ptr{Cdouble}, Ptr{UInt32}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Int64, Cint, Cint, Cint),
+    dists, ids, Xb, Xq, Int64(n), Int64(nq), Cint(d), Cint(k), Cint(1)))
+  return convert(Matrix{Int32}, ids), dists
+end
+
+function groundtruth(Xb::Matrix{UInt8}, Xq::Matrix{Float32}, k::Integer=1)
+  d, n  = size(Xb)
+  nq    = size(Xq, 2)
+  @assert size(Xq, 1) == d
+  dists = Matrix{Float64}(undef, k, nq)
+  ids   = Matrix{UInt32}(undef, k, nq)
+  _check(ccall((:rq_knn_bytes, librayuela_hip), Cint,
+    (Ptr{Cdouble}, Ptr{UInt32}, Ptr{UInt8}, Ptr{Cfloat}, Int64, Int64, Cint, Cint, Cint),
+    dists, ids, Xb, Xq, Int64(n), Int64(nq), Cint(d), Cint(k), Cint(1)))
+  return convert(Matrix{Int32}, ids), dists
 end
 
 """

@@ -30,6 +30,7 @@ from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_
                       linscan_lsq_u16, linscan_cq_u16, linscan_lsq_cbnorms_u16)
 
 from .index import Index, Dataset  # noqa: F401,E402
+from .knn import groundtruth, knn_f64, knn_f32, knn_plan, last_knn_stats, last_knn_timing  # noqa: F401,E402
 from . import h5results  # noqa: F401,E402  (libhdf5 is looked up lazily, on first use)
 from . import datasets  # noqa: F401,E402
 
@@ -39,4 +40,4 @@ __all__ = ["quantize_pq", "quantize_opq", "linscan_pq", "linscan_opq", "linscan_
            "update_codebooks_fast_bin", "quantize_chainq", "train_chainq", "update_codebooks_chain_bin", "get_cbdims_chain",
            "quantize_competitiveq", "quantize_competitiveq_u8", "quantize_competitiveq_u16",
            "quantize_ervq", "train_ervq", "ervq_update_codebook", "last_ervq_timing",
-           "eval_recall", "splitarray", "get_norms_codebook", "quantize_norms"]
+           "eval_recall", "groundtruth", "knn_f64", "knn_f32", "splitarray", "get_norms_codebook", "quantize_norms"]

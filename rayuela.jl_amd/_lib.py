@@ -177,6 +177,14 @@ SIGNATURES = {
     "rq_test_fill_scratch": (_i32, [_i32, _vp]),
     "rq_test_scratch_report": (_i32, [_vp, _vp, _vp, _i32]),
     "rq_centers_plan": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "rq_knn_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32]),
+    "rq_knn": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32]),
+    "rq_knn_bytes": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32]),
+    "rq_dataset_knn": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32]),
+    "rq_last_knn_stats": (_i32, [_vp]),
+    "rq_last_knn_timing": (_i32, [_vp, _i32]),
+    "rq_knn_plan": (_i32, [_i64, _i64, _i32, _i32, _vp, _i32]),
+    "rq_test_knn_chunk_rows": (_i64, [_i64]),
 }
 
 _LIB = None

@@ -1475,6 +1475,16 @@ static rq_dataset *dataset_upload(const void *X, int64_t n, int d, int esz) {
   }
   return reinterpret_cast<rq_dataset *>(ds);
 }
+extern "C++" {
+namespace rq {
+bool dataset_view(const rq_dataset *handle, DatasetView *out) {
+  const rq_dataset_impl *ds = reinterpret_cast<const rq_dataset_impl *>(handle);
+  if (!ds) return false;
+  *out = DatasetView{ds->X, ds->n, ds->d, ds->esz, ds->device};
+  return true;
+}
+}  // namespace rq
+}  // extern "C++"
 rq_dataset *rq_dataset_upload(const float *X, int64_t n, int d) { return dataset_upload(X, n, d, 4); }
 // a byte base stays bytes on the device: 1e9 x 128 is 128 GB, which one MI355X holds; as f32 it is 512 GB
 // (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167)

@@ -379,6 +379,9 @@ int widen_bytes_launch(float *out, const uint8_t *in, size_t nelem, hipStream_t 
 int encode_bytes_launch(uint8_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h,
                         int num_cu, hipStream_t stream);
 int rotate_bytes_launch(float *RX, const float *R, const uint8_t *X, int d, int64_t n, int num_cu, hipStream_t stream);
+// what a resident dataset (rq_dataset_upload[_bytes], rq_api.hip) holds, for the entries of other files (rq_knn.hip)
+struct DatasetView { const void *X; int64_t n; int d, esz, device; };   // esz 4: f32 rows, 1: byte rows
+RQ_LOCAL bool dataset_view(const rq_dataset *handle, DatasetView *out);
 
 // ---- training reductions (rq_train.hip) --------------------------------------------------------
 // Code: uint8_t (1 <= h <= 256; reconstruct: any h) or int16_t (zero-based, read zero-extended, 1 <= h <=

@@ -5,12 +5,22 @@
 experiment_lsq_cuda and experiment_lsq_cuda_query_base (src/LSQ_GPU.jl:322-467).
 train -> encode the base -> ADC search -> recall, every O(n) step on the device.  The norms leg of the additive quantizers
 (get_norms_codebook, quantize_norms) runs on the device in the LSQ drivers and, with norms="device", in the RVQ, ERVQ and SR
-drivers; their default norms="host" keeps the two numpy helpers below."""
+drivers; their default norms="host" keeps the two numpy helpers below.  Every driver takes gt=None for "compute the ground
+truth": the exact nearest neighbour of each query in the set the driver searches (Xb, or Xt in the *_query_base drivers)."""
 import numpy as np
 
 from .Linscan import eval_recall, linscan_opq, linscan_opq_u16, linscan_pq, linscan_pq_u16
 from .OPQ import quantize_opq, train_opq
 from .PQ import quantize_pq, train_pq
+from .knn import groundtruth
+
+
+def _gt(gt, X, Xq):
+    """The ground truth of a driver: what the caller read from a file, or (gt=None) the exact nearest row of the searched set
+    X per query, one-based, computed on the device (knn.groundtruth; the reference can only read it, src/read_datasets.jl)."""
+    if gt is not None:
+        return gt
+    return groundtruth(X, Xq, 1)[0][:, 0]
 
 
 def _qerror(X, B, C, R=None):
@@ -41,14 +51,14 @@ def experiment_pq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     if V:
         print("Error in base is %e" % base_error)
     dists, idx = _scan_pq(B_base, Xq, C, h, m, knn)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xb, Xq), idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
 
 
 def experiment_pq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0):
     C, B, train_error = train_pq(Xt, m, h, niter, V, seed=seed)
     dists, idx = _scan_pq(B, Xq, C, h, m, knn)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xt, Xq), idx, knn, verbose=V)
     return C, B, train_error, recall
 
 
@@ -61,14 +71,14 @@ def experiment_opq(Xt, Xb, Xq, gt, m, h, init, niter=25, knn=1000, V=False, seed
     if V:
         print("Error in base is %e" % base_error)
     dists, idx = _scan_pq(B_base, Xq, C, h, m, knn, R)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xb, Xq), idx, knn, verbose=V)
     return C, B, R, train_error, B_base, recall
 
 
 def experiment_opq_query_base(Xt, Xq, gt, m, h, init, niter=25, knn=1000, V=False, seed=0):
     C, B, R, train_error = train_opq(Xt, m, h, niter, init, V, seed=seed)
     dists, idx = _scan_pq(B, Xq, C, h, m, knn, R)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xt, Xq), idx, knn, verbose=V)
     return C, B, R, train_error, recall
 
 
@@ -160,7 +170,7 @@ def experiment_rvq(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, V=False, seed=0, no
     C, B, train_error = train_rvq(Xt, m, h, niter, V, seed=seed)
     B_base, _ = quantize_rvq(Xb, C, V)
     dists, idx = _search_base(B, C, h, seed, B_base, Xq, knn, norms)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xb, Xq), idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
 
 
@@ -171,7 +181,7 @@ def experiment_rvq_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, V=False, see
     _check_norms_arg(norms)
     C, B, train_error = train_rvq(Xt, m, h, niter, V, seed=seed)
     dists, idx = _search_train(B, C, h, seed, Xq, knn, norms)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xt, Xq), idx, knn, verbose=V)
     return C, B, train_error, recall
 
 
@@ -206,7 +216,7 @@ def experiment_ervq(Xt, *args, V=False, seed=0, norms="host"):
     if V:
         print("Error in base is %e" % _qerror_aq(Xb, B_base, C))
     dists, idx = _search_base(B, C, h, seed, B_base, Xq, knn, norms)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xb, Xq), idx, knn, verbose=V)
     return C, B, train_error, B_base, recall
 
 
@@ -237,7 +247,7 @@ def experiment_ervq_query_base(Xt, *args, V=False, seed=0, norms="host"):
         C, B, _ = train_rvq(Xt, m, h, niter, V, seed=seed)
     C, B, train_error = train_ervq(Xt, B, C, m, h, niter, V, seed=seed)
     dists, idx = _search_train(B, C, h, seed, Xq, knn, norms)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xt, Xq), idx, knn, verbose=V)
     return C, B, train_error, recall
 
 
@@ -270,7 +280,7 @@ def experiment_sr_cuda_query_base(Xt, Xq, gt, m, h, niter=25, knn=1000, nsplits_
     C, B, train_error = train_sr_cuda(Xt, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, sr_method, schedule, p,
                                       nsplits_train, V, seed=seed)
     dists, idx = _search_train(B, C, h, seed, Xq, knn, norms)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xt, Xq), idx, knn, verbose=V)
     res = (C, B, R, train_error, recall)
     return res if given else (res, opq_error)
 
@@ -298,7 +308,7 @@ def experiment_sr_cuda(Xt, Xb, Xq, gt, m, h, niter=25, knn=1000, nsplits_train=1
     if V:
         print("Error in base is %e" % objs[-1])
     dists, idx = _search_base(B, C, h, seed, B_base, Xq, knn, norms)
-    recall = eval_recall(gt, idx, knn, verbose=V)
+    recall = eval_recall(_gt(gt, Xb, Xq), idx, knn, verbose=V)
     return C, B, R, train_error, B_base, recall
 
 
@@ -341,7 +351,7 @@ def experiment_lsq_cuda(Xt, *args, V=False, seed=0, niter_init=25):
     if V:
         print("Error in base is %e" % objs[-1])
     dists, idx = _search_base(B, C, h, seed, B_base, Xq, int(o["knn"]), "device", 100)
-    recall = eval_recall(gt, idx, int(o["knn"]), verbose=V)
+    recall = eval_recall(_gt(gt, Xb, Xq), idx, int(o["knn"]), verbose=V)
     return C, B, R, train_error, B_base, recall
 
 
@@ -385,6 +395,6 @@ def experiment_lsq_cuda_query_base(Xt, *args, V=False, seed=0):
     C, B, train_error = train_lsq_cuda(Xt, m, h, R, B, C, o["niter"], o["ilsiter"], o["icmiter"], o["randord"], o["npert"],
                                        o["nsplits_train"], V, seed=seed)
     dists, idx = _search_train(B, C, h, seed, Xq, int(o["knn"]), "device", 100)
-    recall = eval_recall(gt, idx, int(o["knn"]), verbose=V)
+    recall = eval_recall(_gt(gt, Xt, Xq), idx, int(o["knn"]), verbose=V)
     res = (C, B, R, train_error, recall)
     return res if full else (res, opq_error)

@@ -109,6 +109,19 @@ class Dataset:
                                                 None if Rp is None else Rp.ctypes.data, Cc.ctypes.data, m, h))
         return out
 
+    def knn(self, Xq, k=1, id_base=0):
+        """The exact k nearest rows of this base per query (rq_dataset_knn; see knn.groundtruth): (dists float64 [nq][k],
+        ids uint32 [nq][k]), the base staying where it is."""
+        Xq = _as_f32(Xq, "Xq")
+        if Xq.ndim != 2 or Xq.shape[1] != self.d:
+            raise ValueError("queries must be (nq, %d)" % self.d)
+        nq = Xq.shape[0]
+        dists = np.empty((nq, k), dtype=np.float64)
+        ids = np.empty((nq, k), dtype=np.uint32)
+        _lib.check(_lib.lib().rq_dataset_knn(self._h, dists.ctypes.data, ids.ctypes.data, Xq.ctypes.data, nq, int(k),
+                                             int(id_base)))
+        return dists, ids
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().rq_dataset_free(self._h)
