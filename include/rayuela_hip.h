@@ -492,8 +492,10 @@ int rq_encode_rvq_wide(int16_t *codes, const float *X, const float *codebooks, i
  * ((T[0][b0] + T[1][b1]) + ...) + T[m-1][b_{m-1}] (:78-87), answer: the k smallest (dist, id) pairs in lexicographic order (:91-97),
  * exact for every 1 <= k <= n -- at h = 256 bit for bit the answer of the byte scans.  One path for every k: a packed key per row
  * and query, then the select / sort chain of the bulk top-k (rq_dev_linscan), in query batches inside the same 2 GiB of scratch
- * per device and stream (8 n + 16 k bytes per query, plus the tables); a single query that needs more fails with the
- * out-of-memory error (above about 2.1e8 rows).  The non-finite contract above holds unchanged.  codes [n][m] int16, centers
+ * per device and stream (8 n + 16 k bytes per query, plus the tables); a base whose keys do not fit for a single query (above
+ * about 2.1e8 rows) goes through in row slices whose sorted lists are folded into a running list -- the same answer, bit for
+ * bit (rq_scan_wide_slices) -- and the out-of-memory error is left for a k whose lists alone exceed the budget.  The non-finite
+ * contract above holds unchanged.  codes [n][m] int16, centers
  * [m][h][d/m], 1 <= m <= 32, d % m == 0, 1 <= k <= n < 2^31.  code_base: 0 (zero-based) or 1 (Julia's Matrix{Int16}), as in the
  * wide encodes.  A code outside [0, h) (after code_base): the host entries validate the codes on the device before any output is
  * written and return RQ_EINVAL naming the first bad row (the reference's InexactError of convert(Matrix{UInt8}, B .- 1),
@@ -570,6 +572,24 @@ rq_dataset *rq_dataset_upload(const float *X, int64_t n, int d);
 rq_dataset *rq_dataset_upload_bytes(const uint8_t *X, int64_t n, int d);
 int rq_dataset_encode(rq_dataset *ds, uint8_t *codes, int16_t *codes1, const float *R, const float *C, int m, int h);
 void rq_dataset_free(rq_dataset *ds);
+/* ---- byte rows and resident bases with more than 256 codewords per codebook: the contract of
+ * rq_encode_pq_wide / rq_encode_opq_wide -- codes [n][m] int16, code_base 0 or 1, 1 <= h <= RQ_MAX_H16, 1 <= m <= 32, the same
+ * statuses, no output byte written on error -- on UInt8 rows as they lie in a bvecs file (src/xvecs_read.jl:14-52; the reference
+ * widens on the host, src/read_datasets.jl:148-167).  The codes are bit for bit those of the f32 wide entry on the widened
+ * matrix: PQ at h > 256 runs the streaming kernel with a byte loader (X at any byte alignment; rq_last_encode_kernel keeps
+ * naming "encode_h16_kernel"), OPQ rotates chunks of max(32768, 2^25 / d) byte rows into scratch and encodes them as f32, and
+ * h <= 256 runs the kernels of rq_encode_{pq,opq}_bytes and widens their codes.  The host-pointer entries upload in the double-
+ * buffered chunks of the byte calls above. */
+/* quantize_pq on UInt8 data, up to RQ_MAX_H16 codewords per sub-codebook (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167;
+ * src/PQ.jl:18-48). */
+int rq_encode_pq_bytes_wide(int16_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, int code_base);
+/* quantize_opq on UInt8 data, up to RQ_MAX_H16 codewords per sub-codebook (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167;
+ * src/OPQ.jl:19-27). */
+int rq_encode_opq_bytes_wide(int16_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                             int code_base);
+/* rq_dataset_encode with up to RQ_MAX_H16 codewords per sub-codebook, on a resident base of either kind (rq_dataset_upload,
+ * rq_dataset_upload_bytes): R == NULL -> quantize_pq (src/PQ.jl:18-48), else quantize_opq (src/OPQ.jl:19-27). */
+int rq_dataset_encode_wide(rq_dataset *ds, int16_t *codes, const float *R, const float *C, int m, int h, int code_base);
 /* RX = R' * X (src/OPQ.jl:26, src/Linscan.jl:102). */
 int rq_rotate_T(float *RX, const float *R, const float *X, int d, int64_t n);
 
@@ -698,6 +718,16 @@ int rq_dev_aq_lut_wide(float *lut, const float *codebooks, const float *queries,
  * heap array, deps/src/linscan_aqd.cpp:58).  out[0] queries per gather (4, 2 or 1), out[1] 1: the table of a query group is in
  * LDS, 0: gathered from global memory, out[2] queries per group, out[3] LDS bytes.  cap >= 4. */
 int rq_scan_wide_plan(int m, int h, int *out, int cap);
+/* Host-only: how rq_dev_linscan_wide / rq_dev_linscan_aq_wide (and every entry built on them) take a base of n rows and nq queries
+ * through the 2 GiB scratch budget (no reference counterpart: deps/src/linscan_aqd.cpp:78-97 keeps one heap per query on the host).
+ * A base whose 8 n bytes of keys fit for one query is one slice and launches what it always did.  A longer one is cut into row
+ * slices: per slice the keys kernel and the select chain, then a fold of the slice's sorted list into the running one (P = 2
+ * merge); keys are (dist, global id) pairs, so the answer is bit for bit that of an unsliced scan.  The slice is the longest for
+ * which one query group (rq_scan_wide_plan's out[2]; the nq queries when fewer) fits, evened out over the slices.
+ * out[0] rows per slice (the last may be shorter), [1] slices, [2] queries per batch, [3] scratch bytes of a batch, [4] 1 when
+ * the test hook rq_test_scan_wide_slice_rows forced [0].  cap >= 5.  The out-of-memory status is left where one slice of one
+ * query group plus 32 k bytes of lists do not fit (very large k); bad shapes: RQ_EINVAL / RQ_EUNSUPPORTED as the scan gives. */
+int rq_scan_wide_slices(int64_t n, int64_t nq, int m, int h, int k, int64_t *out, int cap);
 /* Bank-aware row order of a resident base (round 4, csrc/rq_order.hip).  No reference counterpart: the reference scans
  * rows in arrival order (deps/src/linscan_aqd.cpp:78-89); the result of the scan -- the k smallest (dist, id) pairs, :91-97
  * -- does not depend on the order rows are visited in, so this is a data-layout choice in HBM, invisible in the answer.
@@ -879,6 +909,21 @@ int rq_index_search_opq(rq_index *ix, float *dists, uint32_t *ids, const float *
                         const float *R_host, int64_t nq, int k, int id_base);
 int rq_index_info(rq_index *ix, int64_t *out, int cap);
 void rq_index_destroy(rq_index *ix);
+/* The index over 16-bit codes: codebooks of 1 <= h <= RQ_MAX_H16 codewords, centers [m][h][d/m], 1 <= m <= 32 (else NULL with
+ * rq_last_error set).  The reference has no scan above 256 codewords (deps/src/linscan_aqd.cpp:58,67 hard-wire 256 entries
+ * per table); a search is its arithmetic (:66-97) with h entries per table, as rq_linscan_pq_wide states it.
+ *   rq_index_create[_sharded]_wide  as rq_index_create[_sharded]; the handle is searched, inspected and destroyed through
+ *                                   rq_index_search[_opq], rq_index_info and rq_index_destroy, every shard by the scan of
+ *                                   rq_dev_linscan_wide (row slices above the scratch budget, see rq_scan_wide_slices), lists
+ *                                   exchanged and merged exactly as for a byte index: the answer is bit for bit that of one
+ *                                   rq_dev_linscan_wide over the whole base.  Rows stay in arrival order.
+ *   rq_index_set_codes_wide         codes [n][m] int16, code_base 0 or 1 (subtracted on the device).  Every shard is uploaded
+ *                                   and checked on the device before the loaded base is replaced: a code outside [0, h) after
+ *                                   code_base is RQ_EINVAL naming the first such row, and the index keeps the base it had.
+ * rq_index_set_codes_wide on a byte index, rq_index_set_codes[_synth] on a wide one: RQ_EINVAL. */
+rq_index *rq_index_create_wide(int m, int h, int d, const float *centers_host);
+rq_index *rq_index_create_sharded_wide(int m, int h, int d, const float *centers_host, const int *devices, int ndev);
+int rq_index_set_codes_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset);
 
 /* Threading: every entry point may be called from any host thread.  Library scratch is keyed by
  * (device, stream) and the launch sequences of one device are serialised internally, so concurrent
@@ -979,6 +1024,11 @@ int rq_centers_plan(int64_t n, int d, int m, int h, int num_cu, int code_bytes, 
  * chunks of `rows` rows (rq_knn_plan reports it, out[5] = 1), so that a test can run the fold of per-chunk lists on a small base;
  * rows <= 0 gives the planner its choice back.  No answer depends on it (tests/test_gpu_knn.py).  Returns the previous value. */
 int64_t rq_test_knn_chunk_rows(int64_t rows);
+/* The same for the scans over 16-bit codes: rows > 0 makes every later rq_dev_linscan_wide / rq_dev_linscan_aq_wide of this
+ * process (and the host and index entries built on them) cut the base into slices of `rows` rows (rq_scan_wide_slices reports
+ * it, out[4] = 1), so that a test can run the fold of per-slice lists on a small base; rows <= 0 gives the planner its choice
+ * back.  No answer depends on it (tests/test_gpu_scan_wide_slices.py).  Returns the previous value. */
+int64_t rq_test_scan_wide_slice_rows(int64_t rows);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ export groundtruth
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
-export HipIndex, set_codes!, set_codes_synth!, search, HipDataset, quantize
+export HipIndex, HipIndexU16, set_codes!, set_codes_synth!, search, HipDataset, quantize
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
 # call, linscan_pq / linscan_opq below shard B row-wise over those devices inside the library (per-device scan,
@@ -154,6 +154,14 @@ function quantize_pq(X::Matrix{UInt8}, C::Vector{Matrix{Float32}}, V::Bool=false
   h    = size(C[1], 2)
   B    = _result(Int16, m, n)
   if V print("Encoding on $m codebooks with librayuela_hip... ") end
+  if h > 256      # rq_encode_pq_bytes_wide: the 16-bit codes of the widened rows, from the bytes
+    code_base = 1
+    _check(ccall((:rq_encode_pq_bytes_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{UInt8}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+      B, X, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h), Cint(code_base)))
+    if V println("done") end
+    return B
+  end
   _check(ccall((:rq_encode_pq_bytes_i16, librayuela_hip), Cint,
     (Ptr{Int16}, Ptr{UInt8}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
     B, X, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
@@ -166,6 +174,13 @@ function quantize_opq(X::Matrix{UInt8}, R::Matrix{Float32}, C::Vector{Matrix{Flo
   m    = length(C)
   h    = size(C[1], 2)
   B    = _result(Int16, m, n)
+  if h > 256      # rq_encode_opq_bytes_wide
+    code_base = 1
+    _check(ccall((:rq_encode_opq_bytes_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
+      B, X, R, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h), Cint(code_base)))
+    return B
+  end
   _check(ccall((:rq_encode_opq_bytes_i16, librayuela_hip), Cint,
     (Ptr{Int16}, Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
     B, X, R, _cat_codebooks(C), Int64(n), Cint(d), Cint(m), Cint(h)))
@@ -702,7 +717,9 @@ function set_codes_synth!(ix::HipIndex, n::Integer, seed::Integer; id_offset::In
   return ix
 end
 
-function search(ix::HipIndex, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,Matrix{Cfloat}}=nothing)
+search(ix::HipIndex, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,Matrix{Cfloat}}=nothing) = _index_search(ix, X, k, R)
+
+function _index_search(ix, X::Matrix{Cfloat}, k::Int, R::Union{Nothing,Matrix{Cfloat}})    # ix: HipIndex or HipIndexU16
   d, nq = size(X)
   dists = Matrix{Cfloat}(undef, k, nq)
   res   = Matrix{Cuint}(undef, k, nq)
@@ -718,8 +735,44 @@ function search(ix::HipIndex, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,
 end
 
 """
+    HipIndexU16(C, d; devices=nothing)
+`HipIndex` over 16-bit codes: `C` holds m codebooks of `d/m`-by-h centers with any 1 <= h <= 32767 (1 <= m <= 32).
+`set_codes!` takes `Matrix{Int16}` (m-by-n) ZERO-based, or any other integer matrix ONE-based; `search` returns what
+`linscan_pq` / `linscan_opq` over such codes return (k-by-nq `dists`, ONE-based `idx`).
+"""
+mutable struct HipIndexU16
+  h::Ptr{Cvoid}
+  m::Int
+  d::Int
+  function HipIndexU16(C::Vector{Matrix{Cfloat}}, d::Int; devices::Union{Nothing,Vector{<:Integer}}=nothing)
+    m = length(C)
+    h = size(C[1], 2)
+    cen = cat(C..., dims=3)
+    ptr = devices === nothing ?
+      ccall((:rq_index_create_wide, librayuela_hip), Ptr{Cvoid}, (Cint, Cint, Cint, Ptr{Cfloat}), Cint(m), Cint(h), Cint(d), cen) :
+      ccall((:rq_index_create_sharded_wide, librayuela_hip), Ptr{Cvoid}, (Cint, Cint, Cint, Ptr{Cfloat}, Ptr{Cint}, Cint),
+            Cint(m), Cint(h), Cint(d), cen, convert(Vector{Cint}, devices), Cint(length(devices)))
+    ptr == C_NULL && error("rq_index_create_wide: " * unsafe_string(ccall((:rq_last_error, librayuela_hip), Cstring, ())))
+    ix = new(ptr, m, d)
+    finalizer(x -> (x.h != C_NULL && ccall((:rq_index_destroy, librayuela_hip), Cvoid, (Ptr{Cvoid},), x.h); x.h = C_NULL), ix)
+    return ix
+  end
+end
+
+function set_codes!(ix::HipIndexU16, B::Matrix{Int16}; code_base::Integer=0, id_offset::Integer=0)
+  _check(ccall((:rq_index_set_codes_wide, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{Int16}, Int64, Cint, UInt32),
+               ix.h, B, Int64(size(B, 2)), Cint(code_base), UInt32(id_offset)))
+  return ix
+end
+set_codes!(ix::HipIndexU16, B::Matrix{T}; id_offset::Integer=0) where T <: Integer =
+  set_codes!(ix, convert(Matrix{Int16}, B); code_base=1, id_offset=id_offset)
+
+search(ix::HipIndexU16, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,Matrix{Cfloat}}=nothing) = _index_search(ix, X, k, R)
+
+"""
     HipDataset(X)
 `X` (d-by-n) uploaded once; `quantize(ds, C)` == `quantize_pq(X, C)`, `quantize(ds, C; R=R)` == `quantize_opq(X, R, C)`.
+`X::Matrix{UInt8}` (bvecs data) stays bytes on the device.  Codebooks of more than 256 codewords take rq_dataset_encode_wide.
 """
 mutable struct HipDataset
   h::Ptr{Cvoid}
@@ -732,11 +785,26 @@ mutable struct HipDataset
     finalizer(x -> (x.h != C_NULL && ccall((:rq_dataset_free, librayuela_hip), Cvoid, (Ptr{Cvoid},), x.h); x.h = C_NULL), ds)
     return ds
   end
+  function HipDataset(X::Matrix{UInt8})
+    d, n = size(X)
+    h = ccall((:rq_dataset_upload_bytes, librayuela_hip), Ptr{Cvoid}, (Ptr{UInt8}, Int64, Cint), X, Int64(n), Cint(d))
+    h == C_NULL && error("rq_dataset_upload_bytes: " * unsafe_string(ccall((:rq_last_error, librayuela_hip), Cstring, ())))
+    ds = new(h, n)
+    finalizer(x -> (x.h != C_NULL && ccall((:rq_dataset_free, librayuela_hip), Cvoid, (Ptr{Cvoid},), x.h); x.h = C_NULL), ds)
+    return ds
+  end
 end
 
 function quantize(ds::HipDataset, C::Vector{Matrix{Float32}}; R::Union{Nothing,Matrix{Float32}}=nothing)
   m, h = length(C), size(C[1], 2)
   B = Matrix{Int16}(undef, m, ds.n)
+  if h > 256
+    code_base = 1
+    _check(ccall((:rq_dataset_encode_wide, librayuela_hip), Cint,
+      (Ptr{Cvoid}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Cint, Cint, Cint),
+      ds.h, B, R === nothing ? C_NULL : R, _cat_codebooks(C), Cint(m), Cint(h), Cint(code_base)))
+    return B
+  end
   _check(ccall((:rq_dataset_encode, librayuela_hip), Cint,
     (Ptr{Cvoid}, Ptr{Cuchar}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Cint, Cint),
     ds.h, C_NULL, B, R === nothing ? C_NULL : R, _cat_codebooks(C), Cint(m), Cint(h)))

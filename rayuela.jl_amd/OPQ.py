@@ -10,7 +10,8 @@ def quantize_opq(X, R, C, V=False):
 
     R : (d, d) float32, the memory image of Julia's d-by-d rotation (so R_numpy[i, k] == R_julia[k, i]).
     X : (n, d) float32, or (n, d) uint8 (bvecs data): the codes of X.astype(float32), rotated and encoded from the bytes.
-    Returns (n, m) int16 ONE-based codes.  256 < h <= 32767 (float32 X only) takes rq_encode_opq_wide.
+    Returns (n, m) int16 ONE-based codes.  256 < h <= 32767 (float32 X only) takes rq_encode_opq_wide; byte rows under such
+    codebooks go through quantize_opq_u16.
     """
     X = _as_f32_or_u8(X, "X")
     R = _as_f32(R, "R")
@@ -32,8 +33,10 @@ def quantize_opq(X, R, C, V=False):
 
 
 def quantize_opq_u16(X, R, C):
-    """Same encode for any 1 <= h <= 32767, returning zero-based codes viewed as uint16 (rq_encode_opq_wide, code_base 0)."""
-    X = _as_f32(X, "X")
+    """Same encode for any 1 <= h <= 32767, returning zero-based codes viewed as uint16 (rq_encode_opq_wide, code_base 0).
+    X float32, or uint8 (bvecs data): the codes of X.astype(float32), rotated and encoded from the bytes
+    (rq_encode_opq_bytes_wide)."""
+    X = _as_f32_or_u8(X, "X")
     R = _as_f32(R, "R")
     n, d = X.shape
     if R.shape != (d, d):
@@ -43,7 +46,9 @@ def quantize_opq_u16(X, R, C):
     check_wide_h(h)
     Cc = cat_codebooks(C)
     B = _lib.result_empty((n, m), np.int16)
-    _lib.check(_lib.lib().rq_encode_opq_wide(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data, n, d, m, h, 0))
+    L = _lib.lib()
+    encode = L.rq_encode_opq_bytes_wide if X.dtype == np.uint8 else L.rq_encode_opq_wide
+    _lib.check(encode(B.ctypes.data, X.ctypes.data, R.ctypes.data, Cc.ctypes.data, n, d, m, h, 0))
     return B.view(np.uint16)
 
 

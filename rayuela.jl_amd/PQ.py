@@ -13,6 +13,7 @@ def quantize_pq(X, C, V=False):
     C : list of m arrays (h, sub_i) float32 -- memory images of the sub_i-by-h codebooks
     Returns B : (n, m) int16, ONE-based codes (memory image of Julia's m-by-n Matrix{Int16}).
     256 < h <= 32767 codewords per codebook (float32 X only) take rq_encode_pq_wide; the return type is the same.
+    Byte rows under such codebooks go through quantize_pq_u16.
     """
     X = _as_f32_or_u8(X, "X")
     n, d = X.shape
@@ -52,8 +53,9 @@ def quantize_pq_u8(X, C):
 
 
 def quantize_pq_u16(X, C):
-    """Same encode for any 1 <= h <= 32767, returning zero-based codes viewed as uint16 (rq_encode_pq_wide, code_base 0)."""
-    X = _as_f32(X, "X")
+    """Same encode for any 1 <= h <= 32767, returning zero-based codes viewed as uint16 (rq_encode_pq_wide, code_base 0).
+    X float32, or uint8 (bvecs data): the codes of X.astype(float32), encoded from the bytes (rq_encode_pq_bytes_wide)."""
+    X = _as_f32_or_u8(X, "X")
     n, d = X.shape
     m = len(C)
     h = np.asarray(C[0]).shape[0]
@@ -62,7 +64,9 @@ def quantize_pq_u16(X, C):
     if Cc.size != h * d:
         raise ValueError("codebooks do not tile the %d dimensions of X" % d)
     B = _lib.result_empty((n, m), np.int16)
-    _lib.check(_lib.lib().rq_encode_pq_wide(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h, 0))
+    L = _lib.lib()
+    encode = L.rq_encode_pq_bytes_wide if X.dtype == np.uint8 else L.rq_encode_pq_wide
+    _lib.check(encode(B.ctypes.data, X.ctypes.data, Cc.ctypes.data, n, d, m, h, 0))
     return B.view(np.uint16)
 
 

@@ -103,6 +103,9 @@ SIGNATURES = {
     "rq_dataset_upload_bytes": (_vp, [_vp, _i64, _i32]),
     "rq_dataset_encode": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),
     "rq_dataset_free": (None, [_vp]),
+    "rq_encode_pq_bytes_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_encode_opq_bytes_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
+    "rq_dataset_encode_wide": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     "rq_rotate_T": (_i32, [_vp, _vp, _vp, _i32, _i64]),
     "rq_dev_encode_pq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "rq_dev_encode_pq_filter_w": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
@@ -132,6 +135,7 @@ SIGNATURES = {
     "rq_dev_quantize_norms_wide": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rq_get_norms_codebook_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _u64, _i32]),
     "rq_scan_wide_plan": (_i32, [_i32, _i32, _vp, _i32]),
+    "rq_scan_wide_slices": (_i32, [_i64, _i64, _i32, _i32, _i32, _vp, _i32]),
     "rq_scan_row_width": (_i32, [_i32]),
     "rq_order_bytes": (_i64, [_i64, _i32]),
     "rq_order_plan": (_i32, [_i64, _i32, _vp, _i32]),
@@ -159,6 +163,9 @@ SIGNATURES = {
     "rq_index_create_sharded": (_vp, [_i32, _i32, _vp, _vp, _i32]),
     "rq_index_set_codes": (_i32, [_vp, _vp, _i64, _u32]),
     "rq_index_set_codes_synth": (_i32, [_vp, _i64, _u64, _u32]),
+    "rq_index_create_wide": (_vp, [_i32, _i32, _i32, _vp]),
+    "rq_index_create_sharded_wide": (_vp, [_i32, _i32, _i32, _vp, _vp, _i32]),
+    "rq_index_set_codes_wide": (_i32, [_vp, _vp, _i64, _i32, _u32]),
     "rq_index_search_opq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32]),
     "rq_index_info": (_i32, [_vp, _vp, _i32]),
     "rq_release_workspaces": (_i32, []),
@@ -185,6 +192,7 @@ SIGNATURES = {
     "rq_last_knn_timing": (_i32, [_vp, _i32]),
     "rq_knn_plan": (_i32, [_i64, _i64, _i32, _i32, _vp, _i32]),
     "rq_test_knn_chunk_rows": (_i64, [_i64]),
+    "rq_test_scan_wide_slice_rows": (_i64, [_i64]),
 }
 
 _LIB = None
@@ -251,6 +259,15 @@ def scan_wide_plan(m, h):
     out = (C.c_int * 4)()
     check(lib().rq_scan_wide_plan(m, h, C.cast(out, C.c_void_p), 4))
     return dict(zip(("qpg", "in_lds", "qg", "lds_bytes"), [int(x) for x in out]))
+
+
+def scan_wide_slices(n, nq, m, h, k):
+    """How the scan over 16-bit codes takes n rows and nq queries through its scratch budget (host code only,
+    rq_scan_wide_slices): dict of rows (per slice), slices, batch (queries), bytes (scratch of a batch) and forced (1: the test
+    hook rq_test_scan_wide_slice_rows set rows)."""
+    out = (C.c_int64 * 5)()
+    check(lib().rq_scan_wide_slices(n, nq, m, h, k, C.cast(out, C.c_void_p), 5))
+    return dict(zip(("rows", "slices", "batch", "bytes", "forced"), [int(x) for x in out]))
 
 
 def order_cache_stats():

@@ -966,8 +966,8 @@ static int host_linscan_aq(float *dists, uint32_t *ids, const uint8_t *codes, co
 // esz = 4: X is f32 [n][d].  esz = 1: X is uint8 [n][d] (bvecs: src/xvecs_read.jl:14-52; the reference widens on the host,
 // src/read_datasets.jl:148-167) -- the SAME rows per chunk, so an upload is 32 MiB where f32 moves 128 MiB, and the chunk
 // is rotated / encoded from bytes (encode_bytes_launch; its f32 scratch is bounded by the chunk).
-// wide_base >= 0 (f32 rows only): the *_wide entry points -- the same pipeline with 16-bit codes on the device
-// (encode_h16_launch per chunk), codes1 = zero-based codes + wide_base, the addition on the device.
+// wide_base >= 0: the *_wide entry points -- the same pipeline with 16-bit codes on the device (encode_h16_launch per chunk;
+// byte rows: encode_h16_bytes_launch), codes1 = zero-based codes + wide_base, the addition on the device.
 static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int esz, const float *R, const float *C,
                             int64_t n, int d, int m, int h, double *t_h2d, double *t_tail, int wide_base = -1) {
   const bool wide = wide_base >= 0;
@@ -1010,7 +1010,10 @@ static int encode_host_rows(uint8_t *codes, int16_t *codes1, const void *X, int 
     RQ_HIP(hipEventRecord(ev.up[b], xs));
     *t_h2d += t1.ms();
     RQ_HIP(hipStreamWaitEvent(cs, ev.up[b], 0));
-    if (esz == 1) {
+    if (esz == 1 && wide) {
+      RQ_TRY(encode_h16_bytes_launch(d16.as<int16_t>() + (size_t)r0 * m, dX[b].as<uint8_t>(), R ? dR.as<float>() : nullptr,
+                                     dC.as<float>(), nr, d, m, h, di.num_cu, cs));
+    } else if (esz == 1) {
       RQ_TRY(encode_bytes_launch(dcodes.as<uint8_t>() + (size_t)r0 * m, dX[b].as<uint8_t>(), R ? dR.as<float>() : nullptr,
                                  dC.as<float>(), nr, d, m, h, di.num_cu, cs));
     } else {
@@ -1536,6 +1539,49 @@ int rq_dataset_encode(rq_dataset *handle, uint8_t *codes, int16_t *codes1, const
   return RQ_OK;
 }
 
+static int wide_check(const char *who, bool null_arg, int64_t n, int d, int m, int h, int mmax, bool pq, int code_base);
+// quantize_pq / quantize_opq of a resident base of either kind with 1 <= h <= RQ_MAX_H16 codewords per codebook
+int rq_dataset_encode_wide(rq_dataset *handle, int16_t *codes, const float *R, const float *C, int m, int h, int code_base) {
+  rq_dataset_impl *ds = reinterpret_cast<rq_dataset_impl *>(handle);
+  RQ_TRY(wide_check("rq_dataset_encode_wide", !ds || !codes || !C, ds ? ds->n : 0, ds ? ds->d : 1, m, h, 32, true, code_base));
+  Timer tt;
+  SavedDevice saved;
+  RQ_HIP(hipSetDevice(ds->device));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  const int d = ds->d;
+  const int64_t n = ds->n;
+  DevBuf dC, dR, d16;
+  RQ_TRY(dC.alloc((size_t)h * d * 4)); RQ_TRY(d16.alloc((size_t)n * m * 2));
+  RQ_HIP(hipMemcpy(dC.p, C, (size_t)h * d * 4, hipMemcpyHostToDevice));
+  if (R) {
+    RQ_TRY(dR.alloc((size_t)d * d * 4));
+    RQ_HIP(hipMemcpy(dR.p, R, (size_t)d * d * 4, hipMemcpyHostToDevice));
+  }
+  if (ds->esz == 1) {
+    RQ_TRY(encode_h16_bytes_launch(d16.as<int16_t>(), reinterpret_cast<const uint8_t *>(ds->X), R ? dR.as<float>() : nullptr,
+                                   dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  } else {
+    const float *src = ds->X;
+    if (R) {
+      if (!ds->RX) RQ_HIP(hipMalloc((void **)&ds->RX, (size_t)n * d * 4));
+      RQ_TRY(rotate_launch(ds->RX, dR.as<float>(), ds->X, d, n, di.num_cu, nullptr));
+      src = ds->RX;
+    }
+    RQ_TRY(encode_h16_launch(d16.as<int16_t>(), src, dC.as<float>(), n, d, m, h, di.num_cu, nullptr));
+  }
+  RQ_TRY(add_base_codes_launch(d16.as<int16_t>(), n * m, code_base, nullptr));
+  RQ_HIP(hipDeviceSynchronize());
+  g_t_h2d = 0;
+  g_t_kernel = tt.ms();
+  Timer t3;
+  RQ_HIP(hipMemcpy(codes, d16.p, (size_t)n * m * 2, hipMemcpyDeviceToHost));
+  g_t_d2h = t3.ms();
+  g_t_total = tt.ms();
+  return RQ_OK;
+}
+
 void rq_dataset_free(rq_dataset *handle) {
   rq_dataset_impl *ds = reinterpret_cast<rq_dataset_impl *>(handle);
   if (!ds) return;
@@ -1728,6 +1774,18 @@ int rq_encode_opq_wide(int16_t *codes, const float *X, const float *R, const flo
   RQ_TRY(wide_check("rq_encode_opq_wide", !codes || !X || !R || !C, n, d, m, h, 32, true, code_base));
   return host_encode(nullptr, codes, X, R, C, n, d, m, h, 4, code_base);
 }
+// byte rows (bvecs) with up to RQ_MAX_H16 codewords per codebook: the codes of rq_encode_{pq,opq}_wide on the widened rows
+int rq_encode_pq_bytes_wide(int16_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, int code_base) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_encode_pq_bytes_wide", !codes || !X || !C, n, d, m, h, 32, true, code_base));
+  return host_encode(nullptr, codes, X, nullptr, C, n, d, m, h, 1, code_base);
+}
+int rq_encode_opq_bytes_wide(int16_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                             int code_base) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(wide_check("rq_encode_opq_bytes_wide", !codes || !X || !R || !C, n, d, m, h, 32, true, code_base));
+  return host_encode(nullptr, codes, X, R, C, n, d, m, h, 1, code_base);
+}
 int rq_encode_rvq_wide(int16_t *codes, const float *X, const float *codebooks, int64_t n, int d, int m, int h, int code_base,
                        uint32_t *counts, float *Xr_out) {
   if (n <= 0) return RQ_OK;
@@ -1854,6 +1912,15 @@ int rq_scan_wide_plan(int m, int h, int *out, int cap) {
   scan_h16_plan(m, h, out);
   return RQ_OK;
 }
+int rq_scan_wide_slices(int64_t n, int64_t nq, int m, int h, int k, int64_t *out, int cap) {
+  if (!out || cap < 5) return fail(RQ_EINVAL, "rq_scan_wide_slices: out needs 5 entries");
+  if (m < 1 || m > 32) return fail(RQ_EUNSUPPORTED, "rq_scan_wide_slices covers 1 <= m <= 32; got m=%d", m);
+  if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "rq_scan_wide_slices: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
+  if (n < 1 || n >= (1LL << 31) || nq < 1 || k < 1 || k > n) return fail(RQ_EINVAL, "rq_scan_wide_slices: bad shape");
+  for (int i = 5; i < cap; ++i) out[i] = 0;
+  return scan_h16_slices(n, nq, m, h, k, out);
+}
+int64_t rq_test_scan_wide_slice_rows(int64_t rows) { return scan_h16_force_slice_rows(rows); }
 
 // host-only: what update_centers (cstride == 0) / the ERVQ increment (cstride > 0) would launch for this shape (tests; no device)
 int rq_centers_plan(int64_t n, int d, int m, int h, int num_cu, int code_bytes, int cstride, int64_t *out, int cap) {

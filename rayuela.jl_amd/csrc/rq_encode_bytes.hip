@@ -11,6 +11,10 @@
 //   OPQ, d in {32, 64, 96, 128}        rotate_kernel_v2 of rq_encode.hip with the byte row loader (RowsU8) writes f32 R'X of a
 //                                      chunk of rows into scratch; the f32 encode reads it
 //   everything else                    widen_bytes_kernel writes the f32 rows of a chunk into scratch; the f32 launch follows
+// More than 256 codewords per codebook (16-bit codes, encode_h16_bytes_launch below):
+//   PQ                                 encode_h16_kernel<uint8_t> of rq_encode_h16.hip: the streaming kernel with a byte loader
+//   OPQ                                R'X of a chunk into scratch as above, then the f32 streaming kernel on that chunk
+//   h <= 256 through the wide entries  the byte paths above into scratch, widened: the codes of the uint8 entries bit for bit
 // The scratch (WS_TMP of the stream) holds bytes_chunk_rows(d) = max(32768, 2^25 / d) rows -- at most 128 MiB per buffer --
 // whatever n is.  All row offsets are size_t: n d exceeds 2^32 for the bases this is for.
 #include "rq_encode_split.h"
@@ -96,6 +100,34 @@ int encode_bytes_launch(uint8_t *codes, const uint8_t *X, const float *R, const 
     if (R) RQ_TRY(rotate_bytes_piece(rows, R, xb, d, nr, num_cu, stream, wide));
     else RQ_TRY(widen_bytes_launch(rows, xb, (size_t)nr * d, stream));
     RQ_TRY(encode_launch(codes + (size_t)r0 * m, rows, C, nr, d, m, h, num_cu, stream));
+  }
+  return RQ_OK;
+}
+
+// codes [n][m] int16 zero-based of byte rows, 1 <= h <= RQ_MAX_H16; R null: quantize_pq, else quantize_opq.  On `stream`.
+int encode_h16_bytes_launch(int16_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                            int num_cu, hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(h16_encode_check(d, m, h));
+  if (h <= 256) {
+    void *tmp = nullptr;
+    RQ_TRY(workspace(WS_H16_CODES, (size_t)n * m, &tmp, stream));
+    RQ_TRY(encode_bytes_launch((uint8_t *)tmp, X, R, C, n, d, m, h, num_cu, stream));
+    return convert_codes_launch(codes, (const uint8_t *)tmp, n * m, 0, stream);
+  }
+  if (!R) return encode_h16_u8_launch(codes, X, C, n, d, m, h, num_cu, stream);
+  // the chunk loop of encode_bytes_launch: R'X of a chunk in scratch, the f32 wide encode on it
+  const int64_t chunk = std::min<int64_t>(n, bytes_chunk_rows(d));
+  const size_t buf = ((size_t)chunk * d * sizeof(float) + 255) & ~(size_t)255;
+  const bool two = !rotate_bytes_covers(d);
+  void *tmp = nullptr;
+  RQ_TRY(workspace(WS_TMP, buf * (two ? 2 : 1), &tmp, stream));
+  float *rows = (float *)tmp;
+  float *wide = two ? (float *)((unsigned char *)tmp + buf) : nullptr;
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t nr = std::min(chunk, n - r0);
+    RQ_TRY(rotate_bytes_piece(rows, R, X + (size_t)r0 * d, d, nr, num_cu, stream, wide));
+    RQ_TRY(encode_h16_launch(codes + (size_t)r0 * m, rows, C, nr, d, m, h, num_cu, stream));
   }
   return RQ_OK;
 }

@@ -14,6 +14,11 @@
 //   X                every wavefront stages the 32 x 16 slice of its own tile.  A sub-space of at most 16 dimensions (the PQ
 //                    shapes) is one chunk, and the staged slice then serves all codeword blocks: X is read once.  Wider
 //                    sub-spaces re-read their slices once per codeword block (h / 256 reads of X, from L2).
+//                    Row = uint8_t (bvecs rows): the same slice from BYTES -- lane (row l / 2, dimensions
+//                    8 (l & 1) .. + 7) takes one piece of up to 8 bytes with the widest loads X, d and the splitarray offsets
+//                    and widths allow (all may be odd: down to single bytes) and widens it in registers (v_cvt_f32_ubyte*,
+//                    exact) when the tile is stored.  The staged tile holds the very floats the f32 loader stages from
+//                    the widened matrix, and nothing after the tile knows the difference.
 // After the last k-chunk of a block the block's winner (clamped value, global index) is folded into the wavefront's running
 // pair per vector.  Blocks come in ascending order and the pair is replaced on a strict '<' only, so a codeword duplicated at
 // k and k + 256 loses to the lower index; the pair starts at (+Inf, 0), so a row of +Inf values gets index 0.
@@ -26,13 +31,14 @@
 namespace rq {
 
 struct H16Params {
-  const float *X;    // [n][d]
+  const void *X;     // [n][d] float, or uint8_t at any byte alignment (encode_h16_kernel<uint8_t>)
   const float *C;    // concat of [h][sub_i]
   const float *sa;   // [m][h] |c_k|^2
   int16_t *codes;    // [n][m], zero-based
   int64_t n;
   int d, m, h;
   int off[33];       // splitarray offsets (src/utils.jl:179-203)
+  int xal;           // byte rows: the load width 8, 4, 2 or 1 (see x_load_bytes)
 };
 
 constexpr int H16_NT = 8;      // tiles of 32 codewords per block
@@ -51,7 +57,10 @@ __global__ __launch_bounds__(256) void h16_norms_kernel(float *sa, const float *
   sa[idx] = acc;
 }
 
+template <class Row>
 __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
+  constexpr bool BYTES = std::is_same<Row, uint8_t>::value;
+  static_assert(BYTES || std::is_same<Row, float>::value, "rows are float or uint8_t");
   constexpr int NT = H16_NT, KC = H16_KC, NWAVES = H16_NW;
   constexpr int CHUNK = NT * KC * 64;                  // floats per staged codebook chunk
   constexpr int PER = CHUNK / (NWAVES * 64);           // ... per thread
@@ -61,6 +70,7 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
   constexpr int XSTR = DIMS + 1;                       // padded row stride of the staged X tile
   constexpr int BUF = CHUNK + H16_BLOCK;               // one half of the double buffer: chunk + the block's norms
   static_assert(CHUNK % (NWAVES * 64) == 0 && 64 % DIMS == 0 && NWAVES * 64 >= H16_BLOCK, "chunk split");
+  static_assert(!BYTES || DIMS == 16, "the byte loader gives a lane 8 of a row's 16 dimensions");
   __shared__ __attribute__((aligned(16))) float cb0[2 * BUF];
   __shared__ float xs_all[NWAVES * 32 * XSTR];
   const int m = p.m, h = p.h, d = p.d;
@@ -94,7 +104,51 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
     int64_t gr = (tg * NWAVES + wave) * 32 + u * RPI + xrow_in;
     if (gr >= p.n) gr = p.n - 1;
     const int sdim = c * DIMS + xdim;
-    return sdim < sub ? p.X[gr * d + p.off[i] + sdim] : 0.0f;
+    return sdim < sub ? static_cast<const float *>(p.X)[gr * d + p.off[i] + sdim] : 0.0f;
+  };
+  // the same slice of byte rows: lane -> (row lane / 2, dimensions 8 (lane & 1) .. + 7).  The piece starts at
+  // X + row d + off_i + 16 c + 8 (lane & 1) and is nb = min(8, what is left of the sub-space) bytes long.  p.xal (host: the
+  // largest power of two <= 8 that divides X, d and every sub-space offset and width, so also every piece's address and
+  // length) is the load width, uniform over the launch: 1 dwordx2, 2 dwords, 4 ushorts or 8 ubytes, each predicated on lying
+  // inside the piece -- nothing outside it is read.  The loads land RAW in r[]: packing and widening wait until the tile is
+  // stored, behind the MFMAs, so that no ALU op makes the wavefront wait for them (or for the codebook chunk prefetched with
+  // them) before the matrix work.
+  const int brow = lane >> 1, bdim = 8 * (lane & 1);
+  const int xal = p.xal;
+  auto x_load_bytes = [&](int64_t tg, int i, int c, uint32_t (&r)[8]) {
+    const int sub = p.off[i + 1] - p.off[i];
+    int64_t gr = (tg * NWAVES + wave) * 32 + brow;
+    if (gr >= p.n) gr = p.n - 1;
+    const int s0 = c * DIMS + bdim;
+    const int nb = sub - s0;           // bytes of the piece that exist (<= 0: none; >= 8: all)
+    const uint8_t *src = static_cast<const uint8_t *>(p.X) + (size_t)gr * d + p.off[i] + s0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) r[q] = 0u;
+    if (xal >= 8) {
+      if (nb > 0) { const uint2 v = *reinterpret_cast<const uint2 *>(src); r[0] = v.x; r[1] = v.y; }
+    } else if (xal == 4) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) if (4 * q < nb) r[q] = *reinterpret_cast<const uint32_t *>(src + 4 * q);
+    } else if (xal == 2) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) if (2 * q < nb) r[q] = *reinterpret_cast<const uint16_t *>(src + 2 * q);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) if (q < nb) r[q] = src[q];
+    }
+  };
+  auto x_store_bytes = [&](const uint32_t (&r)[8]) {
+    uint32_t w[2];
+    if (xal >= 4) { w[0] = r[0]; w[1] = r[1]; }
+    else if (xal == 2) { w[0] = r[0] | (r[1] << 16); w[1] = r[2] | (r[3] << 16); }
+    else {
+      w[0] = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24);
+      w[1] = r[4] | (r[5] << 8) | (r[6] << 16) | (r[7] << 24);
+    }
+    float x[8];
+    bytes_f32<8>(w, x);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) xs[brow * XSTR + bdim + s] = x[s];
   };
 
   const int64_t ntiles = (p.n + 31) / 32;
@@ -105,8 +159,14 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
 #pragma unroll
   for (int u = 0; u < PER; ++u) cb0[tid + u * NWAVES * 64] = cb_load(0, 0, 0, tid + u * NWAVES * 64);
   if (tid < H16_BLOCK) cb0[CHUNK + sa_slot] = sa_load(0, 0);
+  if constexpr (BYTES) {
+    uint32_t r[8];
+    x_load_bytes(tg, 0, 0, r);
+    x_store_bytes(r);
+  } else {
 #pragma unroll
-  for (int u = 0; u < XL; ++u) xs[(u * RPI + xrow_in) * XSTR + xdim] = x_load(tg, 0, 0, u);
+    for (int u = 0; u < XL; ++u) xs[(u * RPI + xrow_in) * XSTR + xdim] = x_load(tg, 0, 0, u);
+  }
   __syncthreads();
 
   f32x16 acc[NT];
@@ -136,13 +196,17 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
       if (blk == 0) { run_v = INF; run_i = 0; }
     }
     float nxt[PER], xn[XL], nsa = INF;
+    uint32_t xw[8];                          // byte rows: the lane's raw loads of the next slice, in place of xn
     if (more) {
 #pragma unroll
       for (int u = 0; u < PER; ++u) nxt[u] = cb_load(ni, nblk, nc, tid + u * NWAVES * 64);
       nsa = sa_load(ni, nblk);
       if (newx) {
+        if constexpr (BYTES) x_load_bytes(ntg, ni, nc, xw);
+        else {
 #pragma unroll
-        for (int u = 0; u < XL; ++u) xn[u] = x_load(ntg, ni, nc, u);
+          for (int u = 0; u < XL; ++u) xn[u] = x_load(ntg, ni, nc, u);
+        }
       }
     }
     const float *cb = cb0 + (size_t)buf * BUF + lane;
@@ -223,9 +287,12 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
 #pragma unroll
       for (int u = 0; u < PER; ++u) dstb[tid + u * NWAVES * 64] = nxt[u];
       if (tid < H16_BLOCK) dstb[CHUNK + sa_slot] = nsa;
-      if (newx) {
+      if (newx) {                                                                     // this wave's own tile
+        if constexpr (BYTES) x_store_bytes(xw);
+        else {
 #pragma unroll
-        for (int u = 0; u < XL; ++u) xs[(u * RPI + xrow_in) * XSTR + xdim] = xn[u];   // this wave's own tile
+          for (int u = 0; u < XL; ++u) xs[(u * RPI + xrow_in) * XSTR + xdim] = xn[u];
+        }
       }
     }
     __syncthreads();
@@ -236,21 +303,26 @@ __global__ __launch_bounds__(H16_NW * 64) void encode_h16_kernel(H16Params p) {
 
 // codes [n][m] int16 zero-based.  h <= 256: the kernels of rq_encode.hip into scratch, widened (the u8 entry points' codes by
 // construction); above: the norms pass and encode_h16_kernel.  Everything on `stream`.
-int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
-                      hipStream_t stream) {
-  if (n <= 0) return RQ_OK;
+int h16_encode_check(int d, int m, int h) {
   if (m < 1 || m > 32) return fail(RQ_EUNSUPPORTED, "wide encode covers 1 <= m <= 32; got m=%d", m);
   if (h < 1 || h > RQ_MAX_H16) return fail(RQ_EUNSUPPORTED, "wide encode emits Int16 codes: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
   if (d < m) return fail(RQ_EINVAL, "d=%d < m=%d", d, m);
-  if (h <= 256) {
-    void *tmp = nullptr;
-    RQ_TRY(workspace(WS_H16_CODES, (size_t)n * m, &tmp, stream));
-    RQ_TRY(encode_launch((uint8_t *)tmp, X, C, n, d, m, h, num_cu, stream));
-    return convert_codes_launch(codes, (const uint8_t *)tmp, n * m, 0, stream);
-  }
+  return RQ_OK;
+}
+
+// the norms pass and encode_h16_kernel<Row> (h > 256) on rows X [n][d] of Row
+template <class Row>
+static int h16_stream_launch(int16_t *codes, const Row *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                             hipStream_t stream) {
   H16Params p;
   p.X = X; p.C = C; p.codes = codes; p.n = n; p.d = d; p.m = m; p.h = h;
   split_offsets(p.off, d, m);
+  p.xal = 8;
+  if (std::is_same<Row, uint8_t>::value) {
+    uint32_t mix = (uint32_t)(uintptr_t)X | (uint32_t)d | 8u;
+    for (int i = 0; i < m; ++i) mix |= (uint32_t)p.off[i] | (uint32_t)(p.off[i + 1] - p.off[i]);
+    p.xal = (int)(mix & (0u - mix));
+  }
   void *sa = nullptr;
   RQ_TRY(workspace(WS_H16_SA, (size_t)m * h * sizeof(float), &sa, stream));
   p.sa = (const float *)sa;
@@ -258,10 +330,32 @@ int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n,
   RQ_HIP(hipGetLastError());
   const int64_t ngroups = ((n + 31) / 32 + H16_NW - 1) / H16_NW;
   const int grid = (int)std::min<int64_t>(num_cu, ngroups);
-  hipLaunchKernelGGL(encode_h16_kernel, dim3(grid), dim3(H16_NW * 64), 0, stream, p);
+  hipLaunchKernelGGL(encode_h16_kernel<Row>, dim3(grid), dim3(H16_NW * 64), 0, stream, p);
   RQ_HIP(hipGetLastError());
   note_encode_h16_kernel();
   return RQ_OK;
+}
+
+int encode_h16_launch(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                      hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(h16_encode_check(d, m, h));
+  if (h <= 256) {
+    void *tmp = nullptr;
+    RQ_TRY(workspace(WS_H16_CODES, (size_t)n * m, &tmp, stream));
+    RQ_TRY(encode_launch((uint8_t *)tmp, X, C, n, d, m, h, num_cu, stream));
+    return convert_codes_launch(codes, (const uint8_t *)tmp, n * m, 0, stream);
+  }
+  return h16_stream_launch<float>(codes, X, C, n, d, m, h, num_cu, stream);
+}
+
+// quantize_pq of BYTE rows at h > 256 (rq_encode_bytes.hip routes h <= 256 and the OPQ chunks): X at any byte alignment
+int encode_h16_u8_launch(int16_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                         hipStream_t stream) {
+  if (n <= 0) return RQ_OK;
+  RQ_TRY(h16_encode_check(d, m, h));
+  if (h <= 256) return fail(RQ_EINVAL, "encode_h16_u8_launch is the h > 256 path; got h=%d", h);
+  return h16_stream_launch<uint8_t>(codes, X, C, n, d, m, h, num_cu, stream);
 }
 
 // quantize_rvq (src/RVQ.jl:18-66) with 16-bit codes on resident data: stage_codes is n int16 of scratch, counts [m][h] or NULL

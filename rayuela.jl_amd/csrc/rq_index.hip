@@ -125,7 +125,8 @@ struct IxDev {          // one per DISTINCT device of the index
 struct IxShard {
   int dev = 0;          // index into devs
   int64_t row0 = 0, n = 0;
-  uint8_t *codes = nullptr;   // the shard's rows -- in bank-aware order when perm != nullptr (rq_order.hip)
+  uint8_t *codes = nullptr;   // the shard's rows -- in bank-aware order when perm != nullptr (rq_order.hip); a wide index
+                              // (rq_index_create_wide) keeps int16 rows here, in arrival order
   const uint32_t *perm = nullptr;   // position -> row of the shard (inside the `codes` allocation)
   uint64_t *keys = nullptr;   // [nq][k] sorted keys of the last search (shards off the root device)
   size_t keys_cap = 0;
@@ -149,6 +150,8 @@ using namespace rq;
 
 struct rq_index {
   int m = 0, d = 0;
+  int h = 256;          // codewords per codebook; wide: int16 codes scanned by dev_linscan_wide
+  bool wide = false;
   int64_t n = 0;
   uint32_t id_offset = 0;
   std::vector<IxDev> devs;
@@ -206,14 +209,18 @@ static void index_free(rq_index *ix) {
   delete ix;
 }
 
-static int index_build(rq_index *ix, int m, int d, const float *centers_host, const int *devices, int ndev) {
+static int index_build(rq_index *ix, int m, int d, const float *centers_host, const int *devices, int ndev, int h = 256,
+                       bool wide = false) {
+  if (wide && (m < 1 || m > 32)) return fail(RQ_EUNSUPPORTED, "wide index covers 1 <= m <= 32; got m=%d", m);
+  if (wide && (h < 1 || h > RQ_MAX_H16))
+    return fail(RQ_EUNSUPPORTED, "wide index holds Int16 codes: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
   if (m < 1 || d < m || d % m) return fail(RQ_EINVAL, "index: scan needs d %% m == 0 (src/Linscan.jl:23); got d=%d m=%d", d, m);
   if (!centers_host) return fail(RQ_EINVAL, "index: centers is NULL");
   if (ndev < 1 || ndev > 64) return fail(RQ_EINVAL, "index: 1 <= number of shards <= 64, got %d", ndev);
   int visible = 0;
   if (hipGetDeviceCount(&visible) != hipSuccess || visible < 1) { (void)hipGetLastError(); return fail(RQ_ENODEVICE, "no HIP device visible"); }
-  ix->m = m; ix->d = d;
-  const size_t ce = (size_t)m * 256 * (d / m) * 4;
+  ix->m = m; ix->d = d; ix->h = h; ix->wide = wide;
+  const size_t ce = (size_t)m * h * (d / m) * 4;
   for (int s = 0; s < ndev; ++s) {
     const int dev = devices[s];
     if (dev < 0 || dev >= visible || dev >= 16) return fail(RQ_EINVAL, "index: device %d not in [0, %d)", dev, std::min(visible, 16));
@@ -292,6 +299,7 @@ static void shard_bounds(rq_index *ix, int64_t n) {
 template <class Fill>
 static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
   if (!ix) return fail(RQ_EINVAL, "index is NULL");
+  if (ix->wide) return fail(RQ_EINVAL, "index: a wide index takes its codes through rq_index_set_codes_wide");
   if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
   // same bound as dev_linscan: the last id must stay below 0xFFFFFFFF (that id is the padding key KEY_MAX's)
   if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "index: row ids overflow uint32 (id_offset + n must be <= 2^32 - 1)");
@@ -339,6 +347,68 @@ static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
   for (auto &dv : ix->devs) {
     RQ_HIP(hipSetDevice(dv.device));
     RQ_HIP(hipStreamSynchronize(dv.stream));
+  }
+  ix->n = n;
+  ix->id_offset = id_offset;
+  return RQ_OK;
+}
+
+// The wide form of index_set: int16 rows, no row order.  Every shard's new rows are uploaded to a fresh allocation and checked
+// there (prepare_codes_h16_kernel: zero-based in place, the first row with a code outside [0, h)) BEFORE anything of the index
+// is replaced, so a refused base leaves the loaded one answering as before.  Old and new rows are resident together until then.
+static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset) {
+  const char *who = "rq_index_set_codes_wide";
+  if (!ix) return fail(RQ_EINVAL, "index is NULL");
+  if (!ix->wide) return fail(RQ_EINVAL, "%s: a byte index takes its codes through rq_index_set_codes", who);
+  if (!codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
+  if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "index: row ids overflow uint32 (id_offset + n must be <= 2^32 - 1)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  SavedDevice saved;
+  const int m = ix->m, h = ix->h;
+  const int64_t P = (int64_t)ix->shards.size(), per = n / P, extra = n % P;
+  if (per + (extra ? 1 : 0) >= (1LL << 31))
+    return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)(per + 1));
+  std::vector<int16_t *> fresh((size_t)P, nullptr);
+  auto drop = [&]() {
+    for (int64_t s = 0; s < P; ++s)
+      if (fresh[(size_t)s] && hipSetDevice(ix->devs[ix->shards[(size_t)s].dev].device) == hipSuccess) (void)hipFree(fresh[(size_t)s]);
+    (void)hipGetLastError();
+  };
+  int rc = RQ_OK;
+  int64_t row = 0;
+  for (int64_t s = 0; s < P && rc == RQ_OK; ++s) {
+    const int64_t sn = per + (s < extra ? 1 : 0), row0 = row;
+    row += sn;
+    if (sn == 0) continue;
+    IxDev &dv = ix->devs[ix->shards[(size_t)s].dev];
+    rc = [&]() -> int {
+      RQ_HIP(hipSetDevice(dv.device));
+      RQ_HIP(hipMalloc((void **)&fresh[(size_t)s], (size_t)sn * m * 2));
+      DevMem flag;
+      RQ_TRY(flag.alloc(8));
+      RQ_HIP(hipMemcpyAsync(fresh[(size_t)s], codes_host + (size_t)row0 * m, (size_t)sn * m * 2, hipMemcpyHostToDevice, dv.stream));
+      RQ_TRY(prepare_codes_h16_launch(fresh[(size_t)s], flag.as<unsigned long long>(), sn, m, h, code_base, dv.stream));
+      unsigned long long first_bad = 0;
+      RQ_HIP(hipMemcpyAsync(&first_bad, flag.p, 8, hipMemcpyDeviceToHost, dv.stream));
+      RQ_HIP(hipStreamSynchronize(dv.stream));
+      if (first_bad != ~0ull)      // shards are checked in row order: this is the first bad row of the base
+        return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d]; the index keeps the base it had", who,
+                    (unsigned long long)row0 + first_bad, code_base, h - 1 + code_base);
+      return RQ_OK;
+    }();
+  }
+  if (rc != RQ_OK) { drop(); return rc; }
+  shard_bounds(ix, n);
+  for (int64_t s = 0; s < P; ++s) {
+    IxShard &sh = ix->shards[(size_t)s];
+    IxDev &dv = ix->devs[sh.dev];
+    RQ_HIP(hipSetDevice(dv.device));
+    if (sh.codes) { RQ_HIP(hipStreamSynchronize(dv.stream)); RQ_HIP(hipFree(sh.codes)); }
+    sh.codes = reinterpret_cast<uint8_t *>(fresh[(size_t)s]);
+    fresh[(size_t)s] = nullptr;
+    sh.perm = nullptr;
   }
   ix->n = n;
   ix->id_offset = id_offset;
@@ -408,8 +478,13 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
     IxShard &s = ix->shards[0];
     ScanBase sb0;
     sb0.perm = s.perm;
-    RQ_TRY(dev_linscan(ix->dd, ix->di, nullptr, s.codes, root.centers, R_host ? root.queries_rot : root.queries, s.n, nq, m,
-                       d, k, ix->id_offset, id_base, root.stream, LUT_PQ, nullptr, &sb0));
+    if (ix->wide)
+      RQ_TRY(dev_linscan_wide(ix->dd, ix->di, nullptr, reinterpret_cast<const int16_t *>(s.codes), root.centers,
+                              R_host ? root.queries_rot : root.queries, s.n, nq, m, ix->h, d, k, ix->id_offset, id_base,
+                              root.stream));
+    else
+      RQ_TRY(dev_linscan(ix->dd, ix->di, nullptr, s.codes, root.centers, R_host ? root.queries_rot : root.queries, s.n, nq, m,
+                         d, k, ix->id_offset, id_base, root.stream, LUT_PQ, nullptr, &sb0));
   } else {
     RQ_TRY(grow((void **)&ix->gathered, &ix->gathered_cap, (size_t)P * cnt * 8));
     RQ_TRY(grow((void **)&ix->inter, &ix->inter_cap, (size_t)P * cnt * 8));
@@ -452,8 +527,12 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
         const float *qs = (R_host ? dv.queries_rot : dv.queries) + (size_t)q0 * d;
         ScanBase sbs;
         sbs.perm = s.perm;
-        RQ_TRY(dev_linscan(nullptr, nullptr, dst, s.codes, dv.centers, qs, s.n, nqc, m, d, k_local,
-                           (uint32_t)(ix->id_offset + (uint64_t)s.row0), 0, dv.stream, LUT_PQ, nullptr, &sbs));
+        if (ix->wide)
+          RQ_TRY(dev_linscan_wide(nullptr, nullptr, dst, reinterpret_cast<const int16_t *>(s.codes), dv.centers, qs, s.n, nqc, m,
+                                  ix->h, d, k_local, (uint32_t)(ix->id_offset + (uint64_t)s.row0), 0, dv.stream));
+        else
+          RQ_TRY(dev_linscan(nullptr, nullptr, dst, s.codes, dv.centers, qs, s.n, nqc, m, d, k_local,
+                             (uint32_t)(ix->id_offset + (uint64_t)s.row0), 0, dv.stream, LUT_PQ, nullptr, &sbs));
         if (k_local < k)
           RQ_HIP(hipMemcpy2DAsync(out, (size_t)k * 8, dst, (size_t)k_local * 8, (size_t)k_local * 8, (size_t)nqc,
                                   hipMemcpyDeviceToDevice, dv.stream));
@@ -610,6 +689,24 @@ rq_index *rq_index_create_sharded(int m, int d, const float *centers_host, const
   SavedDevice saved;
   if (index_build(ix, m, d, centers_host, devices, ndev) != RQ_OK) { index_free(ix); return nullptr; }
   return ix;
+}
+
+rq_index *rq_index_create_sharded_wide(int m, int h, int d, const float *centers_host, const int *devices, int ndev) {
+  if (!devices) { fail(RQ_EINVAL, "index: devices is NULL"); return nullptr; }
+  rq_index *ix = new rq_index();
+  SavedDevice saved;
+  if (index_build(ix, m, d, centers_host, devices, ndev, h, true) != RQ_OK) { index_free(ix); return nullptr; }
+  return ix;
+}
+
+rq_index *rq_index_create_wide(int m, int h, int d, const float *centers_host) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); fail(RQ_ENODEVICE, "no device"); return nullptr; }
+  return rq_index_create_sharded_wide(m, h, d, centers_host, &dev, 1);
+}
+
+int rq_index_set_codes_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset) {
+  return index_set_wide(ix, codes_host, n, code_base, id_offset);
 }
 
 rq_index *rq_index_create(int m, int d, const float *centers_host) {

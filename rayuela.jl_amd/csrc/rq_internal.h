@@ -320,6 +320,10 @@ int prepare_codes_h16_launch(int16_t *codes, unsigned long long *first_bad, int6
 int check_codes_h16(const char *who, int16_t *codes, unsigned long long *flag, int64_t n, int m, int h, int code_base,
                     hipStream_t stream, const char *suffix = "");
 void scan_h16_plan(int m, int h, int out[4]);             // rq_scan_wide_plan
+// rq_scan_wide_slices: rows per slice, slices, queries per batch, WS_BULK bytes of a batch, 1 when the hook forced the slice
+// (host only; the out-of-memory status when not even one query fits); rq_test_scan_wide_slice_rows: returns the previous value
+int scan_h16_slices(int64_t n, int64_t nq, int m, int h, int k, int64_t out[5]);
+int64_t scan_h16_force_slice_rows(int64_t rows);
 // linscan_lsq / linscan_cq over 16-bit codes: codebooks [m * h][d]; lut_mode LUT_LSQ (dbnorms [n]) or LUT_CQ
 int dev_linscan_aq_wide(float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *codebooks,
                         const float *queries, const float *dbnorms, int64_t n, int64_t nq, int m, int h, int d, int k,
@@ -371,6 +375,14 @@ inline int encode_launch(int16_t *codes, const float *X, const float *C, int64_t
 int rvq_h16_encode_launch(int16_t *codes, float *Xr, int16_t *stage_codes, unsigned int *counts, const float *C, int64_t n,
                           int d, int m, int h, int num_cu, hipStream_t stream);
 int add_base_codes_launch(int16_t *codes, int64_t nelem, int base, hipStream_t stream);   // codes += base, in place
+// byte rows at 1 <= h <= RQ_MAX_H16: the checks of every wide encode; encode_h16_kernel<uint8_t> (PQ, h > 256
+// only); and the router of rq_encode_bytes.hip -- R null: quantize_pq, else quantize_opq through chunks of R'X in WS_TMP; h <= 256:
+// the uint8 byte paths widened.  X at any byte alignment, codes zero-based [n][m].
+int h16_encode_check(int d, int m, int h);
+int encode_h16_u8_launch(int16_t *codes, const uint8_t *X, const float *C, int64_t n, int d, int m, int h, int num_cu,
+                         hipStream_t stream);
+int encode_h16_bytes_launch(int16_t *codes, const uint8_t *X, const float *R, const float *C, int64_t n, int d, int m, int h,
+                            int num_cu, hipStream_t stream);
 void note_encode_h16_kernel();          // rq_last_encode_kernel: "encode_h16_kernel"
 // ---- byte rows (rq_encode_bytes.hip): X uint8 [n][d] on the device, any alignment ------------------------------------------
 int64_t bytes_chunk_rows(int d);      // rows per upload chunk / per piece of f32 scratch: max(32768, 2^25 / d)

@@ -12,9 +12,14 @@
 // (adc_keys_h16_kernel<.., HAS_NORM = true>): deps/src/linscan_aqd_pairwise_byte.cpp:14-94, :97-176 with int16 codes.
 // per batch of queries, everything on the caller's stream; the batch is sized so that keys + tables + the chain's scratch fit
 // the BULK_SCRATCH_BYTES budget of WS_BULK.
+// A base whose 8 n bytes of keys do not fit that budget for one query goes through in ROW SLICES: per
+// slice the keys kernel and the select chain give the slice's sorted list of k keys (KEY_MAX behind a slice shorter than k),
+// which bulk_merge folds into the running list at P = 2 -- the scheme of knn_stage1 (rq_knn.hip).  Keys are (dist, global id)
+// pairs in a total order, so the answer is bit for bit that of the unsliced scan.
 #include "rq_internal.h"
 #include "rq_aq_lut_h16.h"
 #include "rq_topk.h"
+#include <atomic>
 
 namespace rq {
 
@@ -157,7 +162,8 @@ struct H16KeyParams {
   const int16_t *codes;     // [n][m], 2-byte aligned at least
   const float *tab;         // [groups][gstride]: entry e of group g holds QPG queries
   const float *dbnorms;     // [n], HAS_NORM only: added to the row's sum last (linscan_aqd_pairwise_byte.cpp:74)
-  uint64_t *keys;           // [nb][n]
+  uint64_t *keys;           // [nb][ld]
+  size_t ld;                // keys per query: n, or max(slice rows, k) when the rows go through in slices
   size_t gstride;
   uint32_t n, nb;
   int m, h;
@@ -249,7 +255,7 @@ __global__ __launch_bounds__(1024) void adc_keys_h16_kernel(H16KeyParams p) {
     const uint32_t kid = row + p.id_offset;
 #pragma unroll
     for (int q = 0; q < QPG; ++q)
-      if (q0 + q < p.nb) p.keys[(size_t)(q0 + q) * p.n + row] = (bad || acc[q] != acc[q]) ? KEY_MAX : make_key(acc[q], kid);
+      if (q0 + q < p.nb) p.keys[(size_t)(q0 + q) * p.ld + row] = (bad || acc[q] != acc[q]) ? KEY_MAX : make_key(acc[q], kid);
   }
 }
 
@@ -307,6 +313,82 @@ static int64_t h16_batch(const H16Plan &pl, int64_t nq, int64_t n, int k) {
   return lo;
 }
 
+// ---- row slices -------------------------------------------------------------------------------------------------------------
+static std::atomic<int64_t> g_h16_slice_rows{0};     // rq_test_scan_wide_slice_rows: > 0 overrides the planner's slice
+
+struct H16Slices {
+  int64_t rows, slices, batch;     // rows per slice (the last may be shorter), slices, queries per batch; batch 0: does not fit
+  size_t ld, bytes;                // keys per query of a slice: max(rows, k); WS_BULK bytes of a batch
+  int forced, sliced;
+};
+
+// WS_BULK of a sliced batch.  The chain's scratch comes FIRST and is exactly what bulk_merge asks of the slot for nb queries:
+// the fold lays its own scratch out from the start of the slot, over the slice's select scratch (idle by then) and nothing else.
+// Behind it: the slice's keys, the tables, then the running list, the slice's list (adjacent: the interleave reads them as two
+// shards) and the interleaved pair -- 32 k bytes of lists per query.
+static size_t h16_sliced_front(int64_t nb, int k) { return align256((size_t)nb * sel_bytes_per_query((uint32_t)k) + 6 * 256); }
+
+static size_t h16_sliced_bytes(const H16Plan &pl, int64_t nb, size_t ld, int k) {
+  const size_t groups = (size_t)((nb + pl.qg - 1) / pl.qg);
+  return h16_sliced_front(nb, k) + align256((size_t)nb * ld * 8) + align256(groups * pl.gstride * 4) +
+         2 * align256((size_t)nb * k * 8) + align256((size_t)nb * 2 * k * 8);
+}
+
+// Host only.  A call whose whole base fits for one query is not sliced (it launches what it always did) unless the test hook
+// forces a slice length.  Else the slice is the longest for which one query group (pl.qg queries: one table gather serves them
+// all), or the nq queries if they are fewer, fits the budget, evened out over the slices; the batch is then what fits.
+static H16Slices h16_slices(const H16Plan &pl, int64_t n, int64_t nq, int k) {
+  H16Slices sl;
+  const size_t cap = bulk_usable();
+  const int64_t forced = g_h16_slice_rows.load();
+  sl.forced = forced > 0;
+  if (!sl.forced) {
+    const int64_t nb = h16_batch(pl, nq, n, k);
+    if (nb >= 1) {
+      sl.rows = n; sl.slices = 1; sl.batch = nb; sl.ld = (size_t)n; sl.bytes = h16_scan_bytes(pl, nb, n, k); sl.sliced = 0;
+      return sl;
+    }
+  }
+  sl.sliced = 1;
+  int64_t rows;
+  if (sl.forced) rows = std::min<int64_t>(n, forced);
+  else {
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(nq, pl.qg));
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {         // the bytes do not fall as the slice grows
+      const int64_t mid = lo + (hi - lo + 1) / 2;
+      if (h16_sliced_bytes(pl, want, (size_t)std::max<int64_t>(mid, k), k) <= cap) lo = mid;
+      else hi = mid - 1;
+    }
+    rows = lo;
+  }
+  if (rows < 1) { sl.rows = sl.slices = sl.batch = 0; sl.ld = sl.bytes = 0; return sl; }
+  sl.slices = (n + rows - 1) / rows;
+  if (!sl.forced) rows = (n + sl.slices - 1) / sl.slices;
+  sl.rows = rows;
+  sl.ld = (size_t)std::max<int64_t>(rows, k);
+  int64_t lo = 0, hi = std::min<int64_t>(std::max<int64_t>(nq, 1), BK_MAX_NB);
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    if (h16_sliced_bytes(pl, mid, sl.ld, k) <= cap) lo = mid;
+    else hi = mid - 1;
+  }
+  sl.batch = lo;
+  sl.bytes = lo ? h16_sliced_bytes(pl, lo, sl.ld, k) : 0;
+  return sl;
+}
+
+int scan_h16_slices(int64_t n, int64_t nq, int m, int h, int k, int64_t out[5]) {
+  const H16Slices sl = h16_slices(h16_plan(m, h), n, nq, k);
+  out[0] = sl.rows; out[1] = sl.slices; out[2] = sl.batch; out[3] = (int64_t)sl.bytes; out[4] = sl.forced;
+  if (sl.batch < 1)
+    return fail_hip(hipErrorOutOfMemory, "wide scan: one query needs more than the BULK_SCRATCH_BYTES budget of scratch",
+                    __FILE__, __LINE__);
+  return RQ_OK;
+}
+
+int64_t scan_h16_force_slice_rows(int64_t rows) { return g_h16_slice_rows.exchange(rows > 0 ? rows : 0); }
+
 int linscan_wide_check(const char *who, bool null_arg, int64_t n, int m, int h, int d, int k, uint32_t id_offset, int id_base,
                        bool full_dim) {
   if (null_arg) return fail(RQ_EINVAL, "%s: NULL argument", who);
@@ -328,12 +410,14 @@ template <int QPG, bool IN_LDS, bool HAS_NORM = false>
 static int h16_scan(const H16Plan &pl, float *dists, uint32_t *ids, uint64_t *keys, const int16_t *codes, const float *centers,
                     const float *queries, int64_t n, int64_t nq, int m, int h, int d, int k, uint32_t id_offset, int id_base,
                     int num_cu, hipStream_t stream, int lut_mode = LUT_PQ, const float *dbnorms = nullptr) {
-  const int64_t nbmax = h16_batch(pl, nq, n, k);
+  const H16Slices sl = h16_slices(pl, n, nq, k);
+  const int64_t nbmax = sl.batch;
   if (nbmax < 1)
     return fail_hip(hipErrorOutOfMemory, "wide scan: one query needs more than the BULK_SCRATCH_BYTES budget of scratch",
                     __FILE__, __LINE__);
   void *ws = nullptr;
-  RQ_TRY(workspace(WS_BULK, h16_scan_bytes(pl, nbmax, n, k), &ws, stream));
+  // (sized once for the whole call: the folds below ask the slot for less and so never move it under these pointers)
+  RQ_TRY(workspace(WS_BULK, sl.bytes, &ws, stream));
   char name[64];
   snprintf(name, sizeof(name), "adc_keys_h16_kernel<%d, %s%s>", QPG, IN_LDS ? "true" : "false", HAS_NORM ? ", true" : "");
   set_last_scan_kernel(name);
@@ -345,6 +429,68 @@ static int h16_scan(const H16Plan &pl, float *dists, uint32_t *ids, uint64_t *ke
   const int threads = pl.lds_bytes > 80 * 1024 ? 1024 : 512;
   const uintptr_t al = (uintptr_t)codes | (uintptr_t)(2 * m);
   const int vec = (al & 15) == 0 ? 16 : (al & 7) == 0 ? 8 : (al & 3) == 0 ? 4 : 2;
+  if (sl.sliced) {
+    const size_t ld = sl.ld;
+    for (int64_t q0 = 0; q0 < nq; q0 += nbmax) {
+      const int64_t nb = std::min(nbmax, nq - q0);
+      const uint32_t gy = (uint32_t)((nb + QPG - 1) / QPG);
+      const int64_t want = std::max<int64_t>(1, (2LL * num_cu + gy - 1) / gy);
+      unsigned char *at = (unsigned char *)ws;
+      unsigned char *const front = at; at += h16_sliced_front(nb, k);
+      uint64_t *const kbuf = (uint64_t *)at; at += align256((size_t)nb * ld * 8);
+      float *tab = (float *)at; at += align256((size_t)gy * pl.gstride * 4);
+      const size_t lstride = align256((size_t)nb * k * 8) / 8;
+      uint64_t *const run = (uint64_t *)at, *const part = run + lstride, *const pair = part + lstride;
+      if (lut_mode == LUT_PQ) RQ_TRY(lut_h16_groups<QPG>(tab, centers, queries + (size_t)q0 * d, nb, m, h, d / m, pl.gstride, stream));
+      else RQ_TRY(aq_lut_h16_groups<QPG>(tab, centers, queries + (size_t)q0 * d, nb, m, h, d, pl.gstride, lut_mode, stream));
+      float *const od = dists ? dists + (size_t)q0 * k : nullptr;
+      uint32_t *const oi = ids ? ids + (size_t)q0 * k : nullptr;
+      uint64_t *const ok = keys ? keys + (size_t)q0 * k : nullptr;
+      for (int64_t c = 0; c < sl.slices; ++c) {
+        const int64_t r0 = c * sl.rows, nr = std::min(sl.rows, n - r0);
+        const bool last = c + 1 == sl.slices;
+        const int16_t *cs = codes + (size_t)r0 * m;
+        const uintptr_t al = (uintptr_t)cs | (uintptr_t)(2 * m);
+        const uint32_t gx = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(want, (nr + threads - 1) / threads));
+        H16KeyParams p;
+        p.codes = cs;
+        p.tab = tab;
+        p.dbnorms = dbnorms ? dbnorms + r0 : nullptr;
+        p.keys = kbuf;
+        p.ld = ld;
+        p.gstride = pl.gstride;
+        p.n = (uint32_t)nr; p.nb = (uint32_t)nb;
+        p.m = m; p.h = h;
+        p.vec = (al & 15) == 0 ? 16 : (al & 7) == 0 ? 8 : (al & 3) == 0 ? 4 : 2;
+        p.id_offset = id_offset + (uint32_t)r0;
+        p.rows_per_wg = (uint32_t)((nr + gx - 1) / gx);
+        // a slice shorter than k: the chain reads k keys per query, KEY_MAX from the slice's rows on
+        if (nr < k) RQ_HIP(hipMemsetAsync(kbuf, 0xFF, (size_t)nb * ld * 8, stream));
+        hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(threads), pl.lds_bytes, stream, p);
+        RQ_HIP(hipGetLastError());
+        unsigned char *sat = front;
+        BulkSel s;
+        s.src = kbuf;
+        s.ld = ld;
+        sel_layout(s, sat, nb, (uint32_t)k);
+        uint32_t hx;
+        sel_grid(s, (uint32_t)std::max<int64_t>(nr, k), nb, num_cu, &hx);
+        BulkOut o;
+        const bool direct = c == 0 && last;
+        o.dists = direct ? od : nullptr;
+        o.ids = direct ? oi : nullptr;
+        o.keys = direct ? ok : c == 0 ? run : part;
+        o.id_base = direct ? (uint32_t)id_base : 0u;
+        RQ_TRY(sel_run(s, hx, nb, o, stream));
+        if (c > 0) {
+          RQ_TRY(interleave_keys_launch(pair, run, nb, 2, k, lstride, stream));
+          if (last) RQ_TRY(bulk_merge(od, oi, ok, pair, nb, 2, k, id_base, stream));
+          else RQ_TRY(bulk_merge(nullptr, nullptr, run, pair, nb, 2, k, 0, stream));
+        }
+      }
+    }
+    return RQ_OK;
+  }
   for (int64_t q0 = 0; q0 < nq; q0 += nbmax) {
     const int64_t nb = std::min(nbmax, nq - q0);
     const uint32_t gy = (uint32_t)((nb + QPG - 1) / QPG);
@@ -358,6 +504,7 @@ static int h16_scan(const H16Plan &pl, float *dists, uint32_t *ids, uint64_t *ke
     p.tab = tab;
     p.dbnorms = dbnorms;
     p.gstride = pl.gstride;
+    p.ld = (size_t)n;
     p.n = (uint32_t)n; p.nb = (uint32_t)nb;
     p.m = m; p.h = h; p.vec = vec;
     p.id_offset = id_offset;

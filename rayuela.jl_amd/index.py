@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .Linscan import _centers, _codes_u8
+from .Linscan import _centers, _centers_wide, _codes_i16, _codes_u8
 from .utils import _as_f32
 
 EXCHANGE = {0: "none", 1: "peer", 2: "rccl"}
@@ -82,6 +82,45 @@ class Index:
         self.close()
 
 
+class IndexU16(Index):
+    """The index over 16-bit codes (rq_index_*_wide): codebooks of any 1 <= h <= 32767 codewords, 1 <= m <= 32.  search, info,
+    close and the context manager are Index's; a search returns what linscan_pq_u16 / linscan_opq_u16 return on the same
+    base, bit for bit."""
+
+    def __init__(self, C_list, d, devices=None):
+        """C_list: the m (h, d/m) codebooks; devices as for Index."""
+        m = len(C_list)
+        if m < 1 or m > 32:
+            raise ValueError("the scan over 16-bit codes covers 1 <= m <= 32 codebooks; got %d" % m)
+        if d % m:
+            raise ValueError("InexactError: Cint(d/m) with d=%d m=%d (src/Linscan.jl:23)" % (d, m))
+        self.m, self.d = m, d
+        cen = _centers_wide(C_list, m, d)
+        self.h = cen.shape[1]
+        lib = _lib.lib()
+        if devices is None:
+            self._h = lib.rq_index_create_wide(m, self.h, d, cen.ctypes.data)
+        else:
+            devs = (C.c_int * len(devices))(*[int(x) for x in devices])
+            self._h = lib.rq_index_create_sharded_wide(m, self.h, d, cen.ctypes.data, C.cast(devs, C.c_void_p), len(devices))
+        if not self._h:
+            raise _lib.RayuelaHipError("rq_index_create_wide: " + lib.rq_last_error().decode("utf-8", "replace"))
+        self.n = 0
+
+    def set_codes(self, B, id_offset=0):
+        """B (n, m): uint16 / int16 zero-based codes (what quantize_*_u16 and Dataset.quantize_u16 return), or another integer
+        dtype holding ONE-based codes (Linscan._codes_i16)."""
+        Bi, base = _codes_i16(B, self.h)
+        if Bi.shape[1] != self.m:
+            raise ValueError("codes must have m=%d columns" % self.m)
+        _lib.check(_lib.lib().rq_index_set_codes_wide(self._h, Bi.ctypes.data, Bi.shape[0], base, id_offset))
+        self.n = Bi.shape[0]
+        return self
+
+    def set_codes_synth(self, n, seed, id_offset=0):
+        raise NotImplementedError("synthetic bases are byte codes (Index.set_codes_synth)")
+
+
 class Dataset:
     """A base set resident on the device (rq_dataset_*): uploaded once, encoded as often as needed.  X float32, or uint8
     (bvecs data), which stays n * d bytes on the device and encodes to the codes of X.astype(float32)."""
@@ -108,6 +147,25 @@ class Dataset:
                                                 out.ctypes.data if one_based else None,
                                                 None if Rp is None else Rp.ctypes.data, Cc.ctypes.data, m, h))
         return out
+
+    def quantize_u16(self, C_list, R=None, one_based=False):
+        """quantize for codebooks of any 1 <= h <= 32767 codewords (rq_dataset_encode_wide), on a float32 or a uint8 base:
+        (n, m) zero-based codes viewed as uint16 (what quantize_pq_u16 / quantize_opq_u16 return and IndexU16.set_codes takes),
+        or int16 one-based like the reference's return value with one_based=True."""
+        from .utils import cat_codebooks, check_wide_h
+        m = len(C_list)
+        h = np.asarray(C_list[0]).shape[0]
+        check_wide_h(h)
+        Cc = np.ascontiguousarray(cat_codebooks(C_list), dtype=np.float32)
+        if Cc.size != h * self.d:
+            raise ValueError("codebooks do not tile the %d dimensions of the base" % self.d)
+        Rp = None if R is None else _as_f32(R, "R")
+        if Rp is not None and Rp.shape != (self.d, self.d):
+            raise ValueError("R must be %d x %d" % (self.d, self.d))
+        out = np.empty((self.n, m), dtype=np.int16)
+        _lib.check(_lib.lib().rq_dataset_encode_wide(self._h, out.ctypes.data, None if Rp is None else Rp.ctypes.data,
+                                                     Cc.ctypes.data, m, h, 1 if one_based else 0))
+        return out if one_based else out.view(np.uint16)
 
     def knn(self, Xq, k=1, id_base=0):
         """The exact k nearest rows of this base per query (rq_dataset_knn; see knn.groundtruth): (dists float64 [nq][k],

@@ -83,9 +83,11 @@ def quantize_bvecs(filename, C, R=None, bounds=None, rows_per_read=1 << 20, one_
     bvecs_read(bounds, filename), rows_per_read vectors at a time, and every piece is encoded from its bytes -- the reference
     reads the bytes and widens them to Float32 first (src/xvecs_read.jl:14-52, src/read_datasets.jl:148-167); the codes are
     the same.  R is None: quantize_pq, else quantize_opq.  bounds: None (all), n (first n) or (a, b) one-based inclusive.
-    Returns (n, m) uint8 zero-based codes (the scan's wire format), or int16 one-based with one_based=True."""
+    Returns (n, m) uint8 zero-based codes (the scan's wire format), or int16 one-based with one_based=True.  Codebooks of
+    256 < h <= 32767 codewords (rq_encode_{pq,opq}_bytes_wide) return int16 either way: zero-based (IndexU16.set_codes takes
+    them as they are), or one-based with one_based=True."""
     from . import _lib
-    from .utils import _as_f32, cat_codebooks
+    from .utils import _as_f32, cat_codebooks, check_wide_h
     if rows_per_read < 1:
         raise ValueError("rows_per_read must be positive")
     with open(filename, "rb") as f:
@@ -109,13 +111,19 @@ def quantize_bvecs(filename, C, R=None, bounds=None, rows_per_read=1 << 20, one_
     if Rc is not None and Rc.shape != (d, d):
         raise ValueError("R must be %d x %d" % (d, d))
     n = b - a + 1
-    out = np.empty((n, m), dtype=np.int16 if one_based else np.uint8)
+    wide = check_wide_h(h)
+    out = np.empty((n, m), dtype=np.int16 if one_based or wide else np.uint8)
     L = _lib.lib()
     for r0 in range(0, n, rows_per_read):
         nr = min(rows_per_read, n - r0)
         X = bvecs_read((a + r0, a + r0 + nr - 1), filename)
         dst = out[r0:r0 + nr]                       # (a contiguous block of rows of `out`)
-        if Rc is None:
+        if wide and Rc is None:
+            _lib.check(L.rq_encode_pq_bytes_wide(dst.ctypes.data, X.ctypes.data, Cc.ctypes.data, nr, d, m, h, int(one_based)))
+        elif wide:
+            _lib.check(L.rq_encode_opq_bytes_wide(dst.ctypes.data, X.ctypes.data, Rc.ctypes.data, Cc.ctypes.data, nr, d, m, h,
+                                                  int(one_based)))
+        elif Rc is None:
             encode = L.rq_encode_pq_bytes_i16 if one_based else L.rq_encode_pq_bytes
             _lib.check(encode(dst.ctypes.data, X.ctypes.data, Cc.ctypes.data, nr, d, m, h))
         else:
