@@ -267,8 +267,21 @@ int rq_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, 
 int rq_dev_encode_icm(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,
                       int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
                       int64_t t0, int nsplits, void *stream);
-/* milliseconds of this thread's last rq_encode_icm: unaries (hipEvent, summed over chunks) and the whole call */
+/* milliseconds of this thread's last rq_encode_icm / rq_encode_icm_wide: unaries (hipEvent, summed over chunks) and the whole call */
 int rq_last_icm_timing(double *unary_ms, double *total_ms);
+/* encoding_icm with 2 <= h <= RQ_MAX_H16 codewords per codebook: rq_encode_icm's contract word for word
+ * over codes [n][m] int16 in code_base .. code_base + h - 1 (code_base 0 or 1), host pointers.  A kernel of its own whose register
+ * use does not grow with h runs at EVERY h; at h <= 256 codes and costs are rq_encode_icm's bit for bit.  The tables must fit the
+ * scratch budget: with HS = 64 * ceil(h / 64), m*m*h*HS*4 + m*h*4 bytes of tables plus four rows of unaries (m*HS*4 bytes each)
+ * within 2 GiB -- (m, h) = (8, 2048) and (16, 1024) fit, (16, 2048) does not and returns RQ_EUNSUPPORTED.  Every other violation
+ * (m outside 1 .. 16, h outside the range above, a code out of range, ...) is RQ_EINVAL; every check runs before any work and no
+ * output byte is written on error.  There is no device-pointer form in the C ABI yet. */
+int rq_encode_icm_wide(int16_t *codes_out, const int16_t *codes_in, float *cost_out, const float *X, const float *C,
+                       int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
+                       int64_t t0, int nsplits, int code_base);
+/* rq_encode_icm_wide's shape rule and row chunks, no device touched: out[0 .. min(cap, 5) - 1] = {HS, bytes of the tables, bytes
+ * of one row's unaries, rows per chunk, chunks} (the last two 0 when n = 0).  Returns what rq_encode_icm_wide would for the shape. */
+int rq_icm_wide_plan(int64_t n, int d, int m, int h, int nsplits, int64_t *out, int cap);
 
 /* ---- LSQ codebook update: update_codebooks(X, B, h, V, "fastbin") (src/codebook_update.jl:235-277) ->
  * update_codebooks_fast_bin (:175-206) -> fast_bin_matmul (:96-170).  Contract in DESIGN.md section 2.

@@ -827,10 +827,40 @@ function _encode_icm!(out::Matrix{UInt8}, B0::Matrix{UInt8}, cost, X::Matrix{Flo
   return out
 end
 
+# More than 256 codewords per codebook (rq_encode_icm_wide, DESIGN.md section 4.24): the same contract over the reference's own
+# one-based Int16 codes, up to h = 32767 where the pair tables fit the scratch budget (icm_wide_plan says so without a device).
+function _encode_icm_wide!(out::Matrix{Int16}, B0::Matrix{Int16}, cost, X::Matrix{Float32}, C::Vector{Matrix{Float32}},
+                           ilsiter, icmiter, npert, randord, seed, t0, nsplits)
+  d, n = size(X)
+  m    = length(C)
+  h    = size(C[1], 2)
+  code_base = 1
+  _check(ccall((:rq_encode_icm_wide, librayuela_hip), Cint,
+    (Ptr{Int16}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Cint,
+     UInt64, Int64, Cint, Cint),
+    out, B0, cost === nothing ? C_NULL : cost, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(ilsiter),
+    Cint(icmiter), Cint(npert), Cint(randord ? 1 : 0), UInt64(seed), Int64(t0), Cint(nsplits), Cint(code_base)))
+  return out
+end
+
+# (HS, bytes of the tables, bytes of one row's unaries, rows per chunk, chunks) of an encode at h > 256; throws where it would
+function icm_wide_plan(n::Integer, d::Integer, m::Integer, h::Integer, nsplits::Integer=1)
+  out = Vector{Int64}(undef, 5)
+  cap = length(out)
+  _check(ccall((:rq_icm_wide_plan, librayuela_hip), Cint, (Int64, Cint, Cint, Cint, Cint, Ptr{Int64}, Cint),
+    Int64(n), Cint(d), Cint(m), Cint(h), Cint(nsplits), out, Cint(cap)))
+  return out
+end
+
 function encoding_icm(X::Matrix{Float32}, oldB::Matrix{Int16}, C::Vector{Matrix{Float32}}, ilsiter::Integer,
                       icmiter::Integer, randord::Bool, npert::Integer, cpp::Bool=true, V::Bool=false; seed::Integer=0)
   h = size(C[1], 2)
   cpp && h != 256 && throw(ArgumentError("encoding_icm with cpp=true requires h = 256 codewords; got h=$h"))
+  if h > 256
+    B = _encode_icm_wide!(similar(oldB), oldB, nothing, X, C, ilsiter, icmiter, npert, randord, seed, 0, 1)
+    copyto!(oldB, B)
+    return B
+  end
   B0  = convert(Matrix{UInt8}, oldB .- Int16(1))
   out = similar(B0)
   _encode_icm!(out, B0, nothing, X, C, ilsiter, icmiter, npert, randord, seed, 0, 1)
@@ -842,18 +872,23 @@ end
 function encode_icm_cuda(RX::Matrix{Float32}, B::Matrix{Int16}, C::Vector{Matrix{Float32}}, ilsiters::Vector{Int64},
                          icmiter::Integer, npert::Integer, randord::Bool, nsplits::Integer=2, V::Bool=false;
                          seed::Integer=0)
-  cur  = convert(Matrix{UInt8}, B .- Int16(1))
+  wide = size(C[1], 2) > 256
+  cur  = wide ? copy(B) : convert(Matrix{UInt8}, B .- Int16(1))
   cost = Vector{Float32}(undef, size(RX, 2))
   Bs   = Vector{Matrix{Int16}}(undef, length(ilsiters))
   objs = zeros(Float32, length(ilsiters))
   done = 0
   for stop in sort(unique(ilsiters))
     nxt = similar(cur)
-    _encode_icm!(nxt, cur, cost, RX, C, stop - done, icmiter, npert, randord, seed, done, nsplits)
+    if wide
+      _encode_icm_wide!(nxt, cur, cost, RX, C, stop - done, icmiter, npert, randord, seed, done, nsplits)
+    else
+      _encode_icm!(nxt, cur, cost, RX, C, stop - done, icmiter, npert, randord, seed, done, nsplits)
+    end
     cur, done = nxt, stop
     for (i, s) in enumerate(ilsiters)
       if s == stop
-        Bs[i]   = convert(Matrix{Int16}, cur) .+ Int16(1)
+        Bs[i]   = wide ? copy(cur) : convert(Matrix{Int16}, cur) .+ Int16(1)
         objs[i] = Float32(sum(Float64.(cost)) / length(cost))
       end
     end

@@ -1,7 +1,8 @@
 """Host mirror of the LSQ encoder: encoding_icm (src/LSQ.jl:272-302), encode_icm_cuda (src/LSQ_GPU.jl:218-264),
 veccost / qerror (src/qerrors.jl) for full-dimensional codebooks.
 
-Iterated local search around ICM on the device (rq_encode_icm); the contract is DESIGN.md section 2.  Codebooks C are an
+Iterated local search around ICM on the device (rq_encode_icm; rq_encode_icm_wide over 16-bit codes past 256 codewords per
+codebook); the contract is DESIGN.md section 2.  Codebooks C are an
 m-long list of (h, d) arrays (memory image of Julia's d-by-h matrices) or one (m, h, d) array; codes are (n, m) Int16
 one-based like the reference's m-by-n matrices.  Random numbers are counter-based (`seed`), keyed by the global row index
 and the ILS iteration, so results depend on neither nsplits nor checkpoints."""
@@ -10,9 +11,17 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32
+from .utils import MAX_H16, _as_f32
 
 MAX_M = 16
+SCRATCH_BYTES = 2 << 30      # ICM_SCRATCH_BYTES: the tables and one chunk's unaries, per device and stream
+
+
+def wide_fits(m, h):
+    """rq_encode_icm_wide's fit rule: the binaries [m][m][h][HS], the self-products [m][h] and four rows of unaries [m][HS]
+    (f32, HS = 64 * ceil(h / 64)) within the scratch budget."""
+    HS = 64 * ((h + 63) // 64)
+    return m * m * h * HS * 4 + m * h * 4 + 4 * m * HS * 4 <= SCRATCH_BYTES
 
 
 def _stack(C):
@@ -26,16 +35,20 @@ def _stack(C):
     return Cs
 
 
-def _check(X, Cs, codes0, ilsiter, icmiter, npert, nsplits, t0, one_based):
-    """Every argument check runs here, before the library (and the device) is touched."""
+def _check(X, Cs, codes0, ilsiter, icmiter, npert, nsplits, t0, one_based, wide=False):
+    """Every argument check runs here, before the library (and the device) is touched.  wide: the encoder over 16-bit codes
+    (2 <= h <= MAX_H16 and the tables within the scratch budget) instead of the byte one (h <= 256)."""
     n, d = X.shape
     m, h, d2 = Cs.shape
     if d2 != d:
         raise ValueError("codebooks are %d-dimensional, data is %d-dimensional" % (d2, d))
     if not 1 <= m <= MAX_M:
         raise ValueError("LSQ encoding covers 1 <= m <= %d codebooks; got m=%d" % (MAX_M, m))
-    if not 2 <= h <= 256:
-        raise ValueError("LSQ encoding covers 2 <= h <= 256 codewords; got h=%d" % h)
+    if not 2 <= h <= (MAX_H16 if wide else 256):
+        raise ValueError("LSQ encoding covers 2 <= h <= %d codewords; got h=%d" % (MAX_H16 if wide else 256, h))
+    if wide and not wide_fits(m, h):
+        raise ValueError("LSQ encoding keeps m*m*h*h pair products in %d bytes of scratch; m=%d, h=%d do not fit"
+                         % (SCRATCH_BYTES, m, h))
     for name, v in (("ilsiter", ilsiter), ("icmiter", icmiter), ("t0", t0)):
         if int(v) < 0:
             raise ValueError("%s must be >= 0; got %d" % (name, v))
@@ -67,20 +80,44 @@ def encode_icm_u8(X, codes0, C, ilsiter, icmiter, npert, randord, seed=0, t0=0, 
     return (out, cost) if with_cost else out
 
 
+def encode_icm_u16(X, codes0, C, ilsiter, icmiter, npert, randord, seed=0, t0=0, nsplits=1, with_cost=False):
+    """encode_icm_u8 over zero-based int16 codes for any 2 <= h <= 32767 whose tables fit (wide_fits): rq_encode_icm_wide, a kernel
+    of its own at every h.  At h <= 256 codes and costs equal encode_icm_u8's bit for bit."""
+    X = _as_f32(X, "X")
+    Cs = _stack(C)
+    n, d, m, h = _check(X, Cs, codes0, ilsiter, icmiter, npert, nsplits, t0, one_based=False, wide=True)
+    B = np.ascontiguousarray(codes0, dtype=np.int16)
+    out = np.empty((n, m), dtype=np.int16)
+    cost = np.empty(n, dtype=np.float32) if with_cost else None
+    _lib.check(_lib.lib().rq_encode_icm_wide(out.ctypes.data, B.ctypes.data, None if cost is None else cost.ctypes.data,
+                                             X.ctypes.data, Cs.ctypes.data, n, d, m, h, int(ilsiter), int(icmiter),
+                                             int(npert), 1 if randord else 0, int(seed) & ((1 << 64) - 1), int(t0),
+                                             int(nsplits), 0))
+    return (out, cost) if with_cost else out
+
+
+def _encode0(X, B1, Cs, *args, **kw):
+    """The mirrors' encode on ONE-based codes B1 -> zero-based codes (+ cost): the byte kernel at h <= 256, else the wide one."""
+    if Cs.shape[1] > 256:
+        return encode_icm_u16(X, (B1 - 1).astype(np.int16), Cs, *args, **kw)
+    return encode_icm_u8(X, (B1 - 1).astype(np.uint8), Cs, *args, **kw)
+
+
 def encoding_icm(X, oldB, C, ilsiter, icmiter, randord, npert, cpp=True, V=False, seed=0):
     """encoding_icm(X, oldB, C, ilsiter, icmiter, randord, npert, cpp=true, V=false) -> B     (src/LSQ.jl:272-302)
 
     X (n, d) float32, oldB (n, m) Int16 one-based, C m-long list of (h, d) codebooks.  Returns B (n, m) Int16 one-based
     and, like the reference, writes it into oldB too.  cpp=True requires h = 256 (the reference's C++ path is built
-    for H = 256); both settings run the same device kernel."""
+    for H = 256); both settings run the same device kernel.  cpp=False takes any 2 <= h <= 32767 whose tables fit
+    (wide_fits): past 256 codewords the encoder over 16-bit codes runs (rq_encode_icm_wide)."""
     X = _as_f32(X, "X")
     Cs = _stack(C)
     if not (isinstance(oldB, np.ndarray) and oldB.dtype == np.int16):
         raise TypeError("oldB must be an Int16 numpy array (it is updated in place)")
     if cpp and Cs.shape[1] != 256:
         raise ValueError("encoding_icm with cpp=true requires h = 256 codewords; got h=%d" % Cs.shape[1])
-    _check(X, Cs, oldB, ilsiter, icmiter, npert, 1, 0, one_based=True)
-    codes = encode_icm_u8(X, (oldB - 1).astype(np.uint8), Cs, ilsiter, icmiter, npert, randord, seed=seed)
+    _check(X, Cs, oldB, ilsiter, icmiter, npert, 1, 0, one_based=True, wide=Cs.shape[1] > 256)
+    codes = _encode0(X, oldB, Cs, ilsiter, icmiter, npert, randord, seed=seed)
     B = codes.astype(np.int16) + 1
     oldB[...] = B
     if V:
@@ -100,18 +137,19 @@ def encode_icm_cuda(RX, B, C, ilsiters, icmiter, npert, randord, nsplits=2, V=Fa
     if not its or min(its) < 1:
         raise ValueError("ilsiters must list positive iteration counts")
     B = np.asarray(B)
-    _check(X, Cs, B, max(its), icmiter, npert, nsplits, 0, one_based=True)
-    cur = (B - 1).astype(np.uint8)
+    _check(X, Cs, B, max(its), icmiter, npert, nsplits, 0, one_based=True, wide=Cs.shape[1] > 256)
+    cur = B
     Bs, objs = [None] * len(its), np.zeros(len(its), dtype=np.float32)
     done = 0
     for stop in sorted(set(its)):
-        cur, cost = encode_icm_u8(X, cur, Cs, stop - done, icmiter, npert, randord, seed=seed, t0=done,
-                                  nsplits=nsplits, with_cost=True)
+        cur, cost = _encode0(X, cur, Cs, stop - done, icmiter, npert, randord, seed=seed, t0=done, nsplits=nsplits,
+                             with_cost=True)
+        cur = cur.astype(np.int16) + 1
         done = stop
         obj = float(np.mean(cost, dtype=np.float64))
         for i, s in enumerate(its):
             if s == stop:
-                Bs[i] = cur.astype(np.int16) + 1
+                Bs[i] = cur.copy()
                 objs[i] = obj
         if V:
             print(" ILS iteration %d/%d done, qerror %e" % (stop, max(its), obj))
@@ -124,8 +162,8 @@ def veccost(X, B, C):
     X = _as_f32(X, "X")
     Cs = _stack(C)
     B = np.asarray(B)
-    _check(X, Cs, B, 0, 0, 0, 1, 0, one_based=True)
-    _, cost = encode_icm_u8(X, (B - 1).astype(np.uint8), Cs, 0, 0, 0, False, with_cost=True)
+    _check(X, Cs, B, 0, 0, 0, 1, 0, one_based=True, wide=Cs.shape[1] > 256)
+    _, cost = _encode0(X, B, Cs, 0, 0, 0, False, with_cost=True)
     return cost
 
 

@@ -80,6 +80,9 @@ SIGNATURES = {
     "rq_dev_encode_icm": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i64,
                                  _i32, _vp]),
     "rq_last_icm_timing": (_i32, [_vp, _vp]),
+    "rq_encode_icm_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i64, _i32,
+                                  _i32]),
+    "rq_icm_wide_plan": (_i32, [_i64, _i32, _i32, _i32, _i32, _vp, _i32]),
     "rq_update_codebooks_lsq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double]),
     "rq_dev_update_codebooks_lsq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _vp]),
     "rq_dev_lsq_normal_eq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _vp]),

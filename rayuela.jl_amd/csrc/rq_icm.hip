@@ -11,28 +11,13 @@
 //                      perturbation (counter-based splitmix64) and the veccost accept test run in the same kernel.
 // Every dot product is a k-ordered fmaf chain from +0; adds are unfused (-ffp-contract=off), so the codes equal the CPU
 // restatement tests/icm_oracle.py bit for bit.
-#include "rq_internal.h"
+#include "rq_icm_shared.h"
 
 #include <vector>
 
 namespace rq {
 
 namespace {
-
-constexpr int ICM_MAX_M = 16;                                    // the reference GPU kernel's local_codes[16]
-constexpr size_t ICM_SCRATCH_BYTES = (size_t)2 << 30;           // binaries + unaries of one chunk, per device and stream
-
-__host__ __device__ __forceinline__ uint64_t icm_z(uint64_t x) {   // splitmix64 (synth.splitmix64)
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// ((w >> 32) * range) >> 32: an integer in [0, range)
-__device__ __forceinline__ uint32_t icm_scale(uint64_t w, uint32_t range) {
-  return (uint32_t)(((w >> 32) * (uint64_t)range) >> 32);
-}
 
 // ---- binaries and self-products ----------------------------------------------------------------
 // block = one (j, k, b) row, thread = l.  j == k rows are never gathered and stay zero.
@@ -145,25 +130,6 @@ __device__ __forceinline__ void icm_load(float (&v)[E], const float *p) {
 #pragma unroll
     for (int e = 0; e < E; ++e) v[e] = p[e];
   }
-}
-
-// veccost (src/qerrors.jl:36-66): CB = sum_i C_i[b_i] (f32 adds from +0 in codebook order), then lane l sums (CB - x)^2
-// over dims l, l+64, ... in order from +0, and a fixed xor butterfly (32, 16, 8, 4, 2, 1) adds the 64 partial sums.
-template <int MB>
-__device__ __forceinline__ float icm_cost(const int (&b)[MB], const float *x, const float *C, int d, int m, int h,
-                                          int lane) {
-  float acc = 0.0f;
-  for (int t = lane; t < d; t += 64) {
-    float cb = 0.0f;
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-      if (i < m) cb = cb + C[((size_t)i * h + b[i]) * d + t];
-    const float df = cb - x[t];
-    acc = acc + df * df;
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-  return acc;
 }
 
 template <int MB, int E>
@@ -430,6 +396,11 @@ namespace {
 thread_local double g_icm_unary_ms = 0, g_icm_total_ms = 0;
 
 }  // namespace
+
+void icm_set_timing(double unary_ms, double total_ms) {
+  g_icm_unary_ms = unary_ms;
+  g_icm_total_ms = total_ms;
+}
 
 }  // namespace rq
 

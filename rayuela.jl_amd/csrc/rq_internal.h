@@ -484,8 +484,14 @@ int icm_check_args(const void *codes_out, const void *codes_in, const void *X, c
 int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,
                    int64_t n, int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed,
                    int64_t t0, int nsplits, hipStream_t stream, double *unary_ms);
+// the same at 2 <= h <= RQ_MAX_H16 over zero-based int16 codes (rq_icm_h16.hip), shape already checked by
+// rq_icm_wide_plan's rule.  phase_ms: null, or ICM_PH_N milliseconds added per phase (hipEvents; the call then waits for the stream)
+enum { ICM_PH_ILS = 0, ICM_PH_UNARY = 1, ICM_PH_N = 2 };
+int icm_encode_wide_dev(int16_t *codes_out, const int16_t *codes_in, float *cost_out, const float *X, const float *C, int64_t n,
+                        int d, int m, int h, int ilsiter, int icmiter, int npert, int randord, uint64_t seed, int64_t t0,
+                        int nsplits, hipStream_t stream, double *phase_ms);
 
-int icm_sqnorm_launch(float *sa, const float *C, int m, int h, int d, hipStream_t stream);                 // sa[i*h+k] = <c_ik, c_ik>
+int icm_sqnorm_launch(float *sa,const float *C, int m, int h, int d, hipStream_t stream);                 // sa[i*h+k] = <c_ik, c_ik>
 int icm_unary_launch(float *U, const float *X, const float *C, const float *sa, int64_t nrows, int d, int m, int h, int HS,
                      const int *rng, hipStream_t stream);   // U [nrows][m][HS]; rng [m][2]: codebook i is zero outside [lo, hi), or null
 // ---- LSQ codebook update (rq_lsq.hip): A [mh][mh], b [mh][d] f64; A <- its Cholesky factor, Y [mh][d] <- A^-1 Y ------------
