@@ -483,6 +483,32 @@ def _encode_icm(n, d, m, h, seed):
     return build
 
 
+def _encode_icm_dup_ties():
+    """Every conditioning step tied 64 ways (tests/icm_tie_cases.py, codeword l = codeword l % 4): the lowest copy must win."""
+    import icm_tie_cases as tc
+    case = tc.BYTE_LOW[2]
+    assert (case.m, case.h, case.P) == (4, 256, 4)
+    X, C, B0, b0, c0 = tc.expected(case)
+    n, d, m, h = case.n, case.d, case.m, case.h
+    ils, icm, npert, randord = case.args
+
+    def run(dev, out):
+        L = _L()
+        L.check(L.lib().rq_dev_encode_icm(out["codes"].data_ptr(), dev["B0"].data_ptr(), out["cost"].data_ptr(), dev["X"].data_ptr(),
+                                          dev["C"].data_ptr(), n, d, m, h, ils, icm, npert, 1 if randord else 0, tc.ILS_SEED, 0, 1,
+                                          _stream()))
+        return {"codes": out["codes"], "cost": out["cost"]}
+
+    def check(got):
+        assert got["codes"].max() < case.P, "a higher copy won"
+        bad = np.flatnonzero((got["codes"] != b0).any(axis=1))
+        assert bad.size == 0, "%d rows differ" % bad.size
+        assert _eq_bits(got["cost"], c0), "per-row costs differ"
+
+    return Case("rq_dev_encode_icm", {"X": X, "C": C, "B0": B0}, run, check,
+                outputs={"codes": ((n, m), np.uint8), "cost": ((n,), np.float32)})
+
+
 def _lsq_data(m, h, d, n):
     rng = np.random.default_rng(n + m)
     X = rng.standard_normal((n, d)).astype(np.float32)
@@ -614,6 +640,7 @@ CASES = {
     "qerror_codes": ("rq_dev_qerror_codes", _qerror_codes),
     "encode_icm_h64_range_check": ("rq_dev_encode_icm", _encode_icm(500, 64, 8, 64, 9)),
     "encode_icm_h256": ("rq_dev_encode_icm", _encode_icm(256, 32, 8, 256, 3)),
+    "encode_icm_dup_ties": ("rq_dev_encode_icm", _encode_icm_dup_ties),
     "lsq_normal_eq_h100": ("rq_dev_lsq_normal_eq", _lsq_normal_eq(4, 100, 33, 20_000)),
     "lsq_normal_eq_h256": ("rq_dev_lsq_normal_eq", _lsq_normal_eq(2, 256, 32, 20_000)),
     "update_codebooks_lsq_h100_range_check": ("rq_dev_update_codebooks_lsq", _update_codebooks_lsq(4, 100, 33, 20_000)),

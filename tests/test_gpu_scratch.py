@@ -14,10 +14,11 @@ What shows that the harness sees what it claims: after a fill rq_test_scratch_re
 the slots the case rewrote (printed per case), and over all cases every slot of the enum -- parsed from the header, so a 21st slot
 without a case fails -- is rewritten at least once, each case staying inside the slots DESIGN.md lists for its entry point.
 
-Measured on the MI355X: the 126 GPU tests of this file take 12.7 s together (65 stream cases, 37 host forms, 20 slots of leftovers,
-the shuffle, the controls); the slowest is the adc_lut case at 1.6 s, nearly all of it building its reference on the CPU, then
-quantize_chainq and encode_pq_filter_w at 0.7 s; most take 0.05-0.3 s.  No dependence on scratch content was found: every case and
-form passed under every fill, pairing and order."""
+Measured on the MI355X, in a run of the whole suite: the 129 GPU tests of this file take 9.6 s together (66 stream cases, 39 host
+forms, 20 slots of leftovers, the shuffle, the controls); the slowest are the two quantize_chainq cases at 0.6 s, then
+encode_pq_filter_w and the shuffle at 0.6 s; most take under 0.3 s.  (A case whose reference no earlier file of the run has built
+pays for it here: run alone, the adc_lut case takes 1.6 s, nearly all of it on the CPU.)  No dependence on scratch content was
+found: every case and form passed under every fill, pairing and order."""
 import functools
 import os
 import random
@@ -464,6 +465,28 @@ def _f_encode_icm():
     return _named(("B", "cost"), lambda: ti._gpu(X, C, B0, *args, seed=5, nsplits=2)), check
 
 
+def _f_encode_icm_wide(ties):
+    """rq_encode_icm_wide: the shape of tests/test_gpu_icm_wide.py's `inv` fixture, (101, 16, 4, 300), or the (4, 300, 256) case of
+    tests/icm_tie_cases.py, where a copy in the short last piece ties with its original.  The padding of U and binT past h = 300
+    keeps the fill."""
+    import icm_tie_cases as tc
+    import icm_wide_oracle as wo
+    import test_gpu_icm_wide as tw
+    if ties:
+        case = tc.WIDE_LOW[4]
+        assert (case.m, case.h, case.P) == (4, 300, 256)
+        X, C, B0, b0, c0 = tc.expected(case)
+        args, seed = case.args, tc.ILS_SEED
+    else:
+        X, C, B0 = tw._data(101, 16, 4, 300, seed=6)
+        args, seed = (4, 2, 2, True), 3
+        b0, c0 = wo.ils(_orc(), X, C, B0, *args, seed=seed)
+
+    def check(got):
+        tw._assert_same((got["B"], got["cost"]), (b0, c0))
+    return _named(("B", "cost"), lambda: tw._gpu(X, C, B0, *args, seed=seed, nsplits=2)), check
+
+
 def _f_chainq():
     """tests/test_gpu_chainq.py::test_codes_equal_the_restatement at (8, 256, 128, 257)."""
     import chain_oracle as co
@@ -697,6 +720,8 @@ HOST_FORMS = {
     "linscan_lsq_u16": lambda: _f_scan_aq_wide(True),
     "linscan_cq_u16": lambda: _f_scan_aq_wide(False),
     "encode_icm": _f_encode_icm,
+    "encode_icm_u16": lambda: _f_encode_icm_wide(False),
+    "encode_icm_u16_ties": lambda: _f_encode_icm_wide(True),
     "quantize_chainq": _f_chainq,
     "quantize_competitiveq_H1": lambda: _f_beam(1, False),
     "quantize_competitiveq_H4": lambda: _f_beam(4, False),
