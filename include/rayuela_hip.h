@@ -305,10 +305,35 @@ int rq_dev_lsq_normal_eq(double *A, double *b, const float *X, const uint8_t *co
  * of Julia's R, NULL = identity. */
 int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h,
                  int niter, int ilsiter, int icmiter, int npert, int randord, uint64_t seed, int nsplits);
-/* milliseconds of this thread's last rq_update_codebooks_lsq / rq_train_lsq by phase (hipEvents; the device entries leave
- * zeros), summed over a training call's updates: {counts, sort, b, assemble A, solve, other training work (R'X, the rotation
- * back, the obj means), encodes (training)}; cap entries written */
+/* milliseconds of this thread's last rq_update_codebooks_lsq[_wide] / rq_lsq_normal_eq_wide / rq_train_lsq[_wide] by phase
+ * (hipEvents; the device entries leave zeros), summed over a training call's updates: {counts, sort, b, assemble A, solve, other
+ * training work (R'X, the rotation back, the obj means, the code_base shifts), encodes (training)}; cap entries written */
 int rq_last_lsq_timing(double *ms, int cap);
+
+/* ---- the LSQ codebook update and training with 2 <= h <= RQ_MAX_H16 codewords per codebook: the
+ * contracts above word for word over codes [n][m] int16 in code_base .. code_base + h - 1 (code_base 0 or 1), host pointers.
+ * The int16 kernels run at EVERY h; at h <= 256 A, b, C, obj and the codes are those of the byte entries bit for bit.  The
+ * normal equations take m * h <= 16384 (A is then at most 2 GiB of f64, the u32 pair counts 1 GiB): a larger m * h returns
+ * RQ_EUNSUPPORTED.  Every other violation (m outside 1 .. 16, h outside the range above, n outside 0 .. 2^32 - 1, rho not finite
+ * and > 0, a null pointer, a code out of range, ...) is RQ_EINVAL.  Every check runs before any work and before a device is
+ * needed; no output byte is written on error.  There is no device-pointer form in the C ABI yet. */
+int rq_update_codebooks_lsq_wide(float *C, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, double rho,
+                                 int code_base);
+/* fast_bin_matmul alone: A [mh][mh] and b [mh][d] f64 as rq_dev_lsq_normal_eq defines them, and counts [m][h] = the rows per
+ * (codebook, code).  A may be NULL: then b and counts alone are produced, no mh x mh buffer is allocated and the m * h limit does
+ * not apply (any h <= RQ_MAX_H16 with m <= 16).  counts may be NULL. */
+int rq_lsq_normal_eq_wide(double *A, double *b, uint32_t *counts, const float *X, const int16_t *codes, int64_t n, int d, int m,
+                          int h, double rho, int code_base);
+/* rq_update_codebooks_lsq_wide's shape rule and sizes, no device touched: out[0 .. min(cap, 7) - 1] = {m * h, bytes of A, bytes
+ * of the pair counts, bytes of the sort scratch (tile histograms, segment bounds, per-code counts, row lists), tiles of 4096
+ * rows, Cholesky block steps (64 wide), 1 when rq_train_lsq_wide can run the shape too (rq_icm_wide_plan passes) else 0}.
+ * Returns what rq_update_codebooks_lsq_wide would for the shape; out is written on RQ_OK only. */
+int rq_lsq_wide_plan(int64_t n, int d, int m, int h, int64_t *out, int cap);
+/* rq_train_lsq over int16 codes: the same steps, the encodes through the encoder of rq_encode_icm_wide (ILS iterations
+ * e*ilsiter .. (e+1)*ilsiter - 1 of one `seed` stream for encode call e, so the result depends on neither nsplits nor the
+ * chunking).  The shape must pass rq_icm_wide_plan AND m * h <= 16384, else RQ_EUNSUPPORTED.  codes in and out carry code_base. */
+int rq_train_lsq_wide(float *C, int16_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h,
+                      int niter, int ilsiter, int icmiter, int npert, int randord, uint64_t seed, int nsplits, int code_base);
 
 /* ---- LSQ++: stochastic relaxations of LSQ (src/SR.jl, src/SR_perturbations.jl).  Contract in DESIGN.md section 2
  * ("SR noise").  The reference draws from Julia's global randn; here the noise is a counter-based standard normal

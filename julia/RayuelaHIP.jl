@@ -913,15 +913,72 @@ function update_codebooks_fast_bin(X::Matrix{Float32}, B::Matrix{Int16}, h::Inte
   return _split_codebooks(Cc, m, h)
 end
 
+# More than 256 codewords per codebook (rq_update_codebooks_lsq_wide, DESIGN.md section 4.25): the same contract over the
+# reference's own one-based Int16 codes, up to h = 32767 with m * h <= 16384 (lsq_wide_plan says so without a device).
+function _update_codebooks_wide(X::Matrix{Float32}, B::Matrix{Int16}, h::Integer, rho::Float64=1e-4)
+  d, n  = size(X)
+  m     = size(B, 1)
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  code_base = 1
+  _check(ccall((:rq_update_codebooks_lsq_wide, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Int16}, Int64, Cint, Cint, Cint, Cdouble, Cint),
+    Cc, X, B, Int64(n), Cint(d), Cint(m), Cint(h), Float64(rho), Cint(code_base)))
+  return _split_codebooks(Cc, m, h)
+end
+
+# fast_bin_matmul's A (mh x mh) and b (memory image [mh][d]: a d x mh matrix here) and the rows per (codebook, code) at any
+# h <= 32767 (rq_lsq_normal_eq_wide); with_A = false: b and the counts alone, for shapes past m * h = 16384
+function lsq_normal_eq_wide(X::Matrix{Float32}, B::Matrix{Int16}, h::Integer; rho::Float64=1e-4, with_A::Bool=true)
+  d, n   = size(X)
+  m      = size(B, 1)
+  A      = with_A ? Matrix{Float64}(undef, m * h, m * h) : nothing
+  b      = Matrix{Float64}(undef, d, m * h)
+  counts = Matrix{UInt32}(undef, h, m)
+  code_base = 1
+  _check(ccall((:rq_lsq_normal_eq_wide, librayuela_hip), Cint,
+    (Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt32}, Ptr{Cfloat}, Ptr{Int16}, Int64, Cint, Cint, Cint, Cdouble, Cint),
+    A === nothing ? C_NULL : A, b, counts, X, B, Int64(n), Cint(d), Cint(m), Cint(h), Float64(rho), Cint(code_base)))
+  return A, b, counts
+end
+
+# (m*h, bytes of A, bytes of the pair counts, bytes of the sort scratch, tiles, Cholesky block steps, train_lsq can run it) of an
+# update at h > 256; throws where rq_update_codebooks_lsq_wide would
+function lsq_wide_plan(n::Integer, d::Integer, m::Integer, h::Integer)
+  out = Vector{Int64}(undef, 7)
+  cap = length(out)
+  _check(ccall((:rq_lsq_wide_plan, librayuela_hip), Cint, (Int64, Cint, Cint, Cint, Ptr{Int64}, Cint),
+    Int64(n), Cint(d), Cint(m), Cint(h), out, Cint(cap)))
+  return out
+end
+
 function update_codebooks(X::Matrix{Float32}, B::Matrix{Int16}, h::Integer, V::Bool=false,
                           method::AbstractString="fastbin")
   method in ["fast", "fastbin", "lsmr", "lsqr", "naive"] || error("Codebook update method unknown")
   method == "fastbin" || throw(ArgumentError("codebook update method \"$method\" is not supported; only \"fastbin\" is"))
-  return update_codebooks_fast_bin(X, B, h, V)
+  h > 256 || return update_codebooks_fast_bin(X, B, h, V)
+  C = _update_codebooks_wide(X, B, h)
+  V && println("Doing fast bin codebook update... done.")
+  return C
+end
+
+function _train_lsq_wide(X::Matrix{Float32}, m, h, R::Matrix{Float32}, B::Matrix{Int16}, niter, ilsiter, icmiter, randord,
+                         npert, seed, nsplits)
+  d, n  = size(X)
+  codes = copy(B)
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  obj   = zeros(Float64, max(niter, 1))
+  code_base = 1
+  _check(ccall((:rq_train_lsq_wide, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Int16}, Ptr{Cdouble}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Cint,
+     Cint, UInt64, Cint, Cint),
+    Cc, codes, obj, X, R, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), Cint(ilsiter), Cint(icmiter), Cint(npert),
+    Cint(randord ? 1 : 0), UInt64(seed), Cint(nsplits), Cint(code_base)))
+  return _split_codebooks(Cc, m, h), codes, convert(Vector{Float32}, obj[1:niter])
 end
 
 function _train_lsq(X::Matrix{Float32}, m, h, R::Matrix{Float32}, B::Matrix{Int16}, niter, ilsiter, icmiter, randord,
                     npert, seed, nsplits)
+  h > 256 && return _train_lsq_wide(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits)
   d, n  = size(X)
   codes = convert(Matrix{UInt8}, B .- Int16(1))
   Cc    = Matrix{Float32}(undef, d, m * h)

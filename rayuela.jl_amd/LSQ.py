@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .codebook_update import MAX_MH
 from .utils import MAX_H16, _as_f32
 
 MAX_M = 16
@@ -195,18 +196,57 @@ def train_lsq_u8(X, codes0, m, h, R, niter, ilsiter, icmiter, randord, npert, se
     return C, codes, obj
 
 
+def _check_wide_train(X, B, m, h, ilsiter, icmiter, npert, nsplits, one_based):
+    """_check for the loop over 16-bit codes, and the update's own limit m * h <= MAX_MH"""
+    _check(X, np.broadcast_to(np.float32(0), (m, h, X.shape[1])), B, ilsiter, icmiter, npert, nsplits, 0, one_based=one_based,
+           wide=True)
+    if m * h > MAX_MH:
+        raise ValueError("the LSQ update solves m * h <= %d unknowns per dimension; got m=%d, h=%d" % (MAX_MH, m, h))
+
+
+def train_lsq_u16(X, codes0, m, h, R, niter, ilsiter, icmiter, randord, npert, seed=0, nsplits=1):
+    """train_lsq_u8 over zero-based int16 codes for any 2 <= h <= 32767 with m * h <= 16384 whose encoder tables fit (wide_fits):
+    rq_train_lsq_wide, the int16 kernels at every h.  At h <= 256 C and obj equal train_lsq_u8's bit for
+    bit, and so do the codes."""
+    X = _as_f32(X, "X")
+    n, d = X.shape
+    B = np.asarray(codes0)
+    _check_wide_train(X, B, m, h, ilsiter, icmiter, npert, nsplits, one_based=False)
+    if int(niter) < 0:
+        raise ValueError("niter must be >= 0; got %d" % niter)
+    if R is not None:
+        R = _as_f32(R, "R")
+        if R.shape != (d, d):
+            raise ValueError("R must be (d, d) = (%d, %d); got %s" % (d, d, R.shape))
+    codes = np.array(B, dtype=np.int16, order="C")
+    C = np.empty((m, h, d), dtype=np.float32)
+    obj = np.zeros(int(niter), dtype=np.float64)
+    _lib.check(_lib.lib().rq_train_lsq_wide(C.ctypes.data, codes.ctypes.data, obj.ctypes.data if niter else None,
+                                            X.ctypes.data, None if R is None else R.ctypes.data, n, d, m, h, int(niter),
+                                            int(ilsiter), int(icmiter), int(npert), 1 if randord else 0,
+                                            int(seed) & ((1 << 64) - 1), int(nsplits), 0))
+    return C, codes, obj
+
+
 def _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits, V, label):
     X = _as_f32(X, "X")
     B = np.asarray(B)
     if B.dtype != np.int16:
         raise TypeError("B must be an Int16 array of one-based codes")
     n, d = X.shape
-    _check(X, np.empty((m, h, d), np.float32), B, ilsiter, icmiter, npert, nsplits, 0, one_based=True)
+    wide = int(h) > 256
+    if wide:
+        _check_wide_train(X, B, m, h, ilsiter, icmiter, npert, nsplits, one_based=True)
+    else:
+        _check(X, np.empty((m, h, d), np.float32), B, ilsiter, icmiter, npert, nsplits, 0, one_based=True)
     if V:
         print("Training %s with %d codebooks, %d perturbations, %d icm iterations and random order = %s"
               % (label, m, npert, icmiter, bool(randord)))
-    C, codes, obj = train_lsq_u8(X, (B - 1).astype(np.uint8), m, h, R, niter, ilsiter, icmiter, randord, npert,
-                                 seed=seed, nsplits=nsplits)
+    if wide:      # past 256 codewords: the loop over 16-bit codes (rq_train_lsq_wide); h <= 256 stays on the byte loop
+        C, codes, obj = train_lsq_u16(X, B - 1, m, h, R, niter, ilsiter, icmiter, randord, npert, seed=seed, nsplits=nsplits)
+    else:
+        C, codes, obj = train_lsq_u8(X, (B - 1).astype(np.uint8), m, h, R, niter, ilsiter, icmiter, randord, npert,
+                                     seed=seed, nsplits=nsplits)
     if V:
         for it, o in enumerate(obj, 1):
             print("%3d %e " % (it, o))
@@ -219,7 +259,9 @@ def train_lsq(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, cpp=Tru
     X (n, d) float32, R (d, d) memory image of Julia's R (None = identity), B (n, m) Int16 one-based start codes; the C
     argument is ignored (the reference overwrites it, :348).  Returns C (m-long list of (h, d)), B (Int16 one-based) and
     obj (niter,) float32, obj[iter] = qerror before iteration iter's update (NaN when n = 0).  Like encoding_icm, the final codes are also
-    written into B.  cpp=True requires h = 256; both settings run the same device loop (rq_train_lsq)."""
+    written into B.  cpp=True requires h = 256; both settings run the same device loop (rq_train_lsq).  cpp=False takes any
+    2 <= h <= 32767 with m * h <= 16384 whose encoder tables fit (wide_fits): past 256 codewords the loop over 16-bit codes runs
+    (rq_train_lsq_wide)."""
     if not (isinstance(B, np.ndarray) and B.dtype == np.int16):
         raise TypeError("B must be an Int16 numpy array (it is updated in place)")
     if cpp and h != 256:
@@ -232,7 +274,8 @@ def train_lsq(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, cpp=Tru
 def train_lsq_cuda(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, nsplits=1, V=False, seed=0):
     """train_lsq_cuda(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, nsplits=1, V=false) -> C, B, obj
                                                                                           (src/LSQ_GPU.jl:267-319)
-    As train_lsq, but B is left untouched (encode_icm_cuda returns new codes); the result does not depend on nsplits."""
+    As train_lsq, but B is left untouched (encode_icm_cuda returns new codes); the result does not depend on nsplits.  Past 256
+    codewords the loop over 16-bit codes runs, as in train_lsq(cpp=False)."""
     return _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, seed, nsplits, V, "LSQ GPU")
 
 

@@ -88,6 +88,11 @@ SIGNATURES = {
     "rq_dev_lsq_normal_eq": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _vp]),
     "rq_train_lsq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i32]),
     "rq_last_lsq_timing": (_i32, [_vp, _i32]),
+    "rq_update_codebooks_lsq_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _i32]),
+    "rq_lsq_normal_eq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _i32]),
+    "rq_lsq_wide_plan": (_i32, [_i64, _i32, _i32, _i32, _vp, _i32]),
+    "rq_train_lsq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _i32,
+                                 _i32]),
     "rq_sr_std": (_i32, [_vp, _vp, _i64, _i32]),
     "rq_sr_perturb": (_i32, [_vp, _vp, _vp, C.c_double, _i64, _i32, _i32, _u64, _i64, _i64]),
     "rq_sr_schedule": (_i32, [_vp, _i32, _i64, _i64, C.c_double]),

@@ -13,20 +13,25 @@ import time
 import numpy as np
 
 from . import _lib
-from .utils import _as_f32, splitarray
+from .utils import MAX_H16, _as_f32, splitarray
 
 MAX_M = 16
+MAX_MH = 16384         # the update over 16-bit codes: A = (m h)^2 f64 within 2 GiB
 METHODS = ("fast", "fastbin", "lsmr", "lsqr", "naive")      # src/codebook_update.jl:242
 
 
-def _check_update(n, d, codes_shape, m, h, rho):
-    """Every argument check of the update runs here, before the library (and the device) is touched."""
+def _check_update(n, d, codes_shape, m, h, rho, wide=False):
+    """Every argument check of the update runs here, before the library (and the device) is touched.  wide: the update over
+    16-bit codes (2 <= h <= MAX_H16 and m * h <= MAX_MH) instead of the byte one (h <= 256)."""
     if len(codes_shape) != 2 or codes_shape[0] != n:
         raise ValueError("codes must be (n, m) with n = %d rows; got %s" % (n, tuple(codes_shape)))
     if not 1 <= m <= MAX_M:
         raise ValueError("the LSQ update covers 1 <= m <= %d codebooks; got m=%d" % (MAX_M, m))
-    if not 2 <= int(h) <= 256:
-        raise ValueError("the LSQ update covers 2 <= h <= 256 codewords; got h=%d" % h)
+    hmax = MAX_H16 if wide else 256
+    if not 2 <= int(h) <= hmax:
+        raise ValueError("the LSQ update covers 2 <= h <= %d codewords; got h=%d" % (hmax, h))
+    if wide and m * int(h) > MAX_MH:
+        raise ValueError("the LSQ update solves m * h <= %d unknowns per dimension; got m=%d, h=%d" % (MAX_MH, m, h))
     if d < 1:
         raise ValueError("d must be >= 1; got %d" % d)
     if n > 2 ** 32 - 1:
@@ -52,6 +57,22 @@ def update_codebooks_u8(X, codes, h, rho=1e-4):
     return C
 
 
+def update_codebooks_u16(X, codes, h, rho=1e-4):
+    """update_codebooks_u8 over zero-based int16 codes for any 2 <= h <= 32767 with m * h <= 16384: rq_update_codebooks_lsq_wide,
+    the int16 kernels at every h.  At h <= 256 the codebooks equal update_codebooks_u8's bit for bit."""
+    X = _as_f32(X, "X")
+    codes = np.asarray(codes)
+    n, d = X.shape
+    m = codes.shape[1] if codes.ndim == 2 else -1
+    rho = _check_update(n, d, codes.shape, m, h, rho, wide=True)
+    if codes.size and (codes.min() < 0 or codes.max() > h - 1):
+        raise ValueError("codes must be in 0..%d" % (h - 1))
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    C = np.empty((m, int(h), d), dtype=np.float32)
+    _lib.check(_lib.lib().rq_update_codebooks_lsq_wide(C.ctypes.data, X.ctypes.data, codes.ctypes.data, n, d, m, int(h), rho, 0))
+    return C
+
+
 def update_codebooks_fast_bin(X, B, h, V=False, rho=1e-4):
     """update_codebooks_fast_bin(X, B, h, V=false, rho=1e-4) -> C       (src/codebook_update.jl:175-206)
 
@@ -72,12 +93,25 @@ def update_codebooks_fast_bin(X, B, h, V=False, rho=1e-4):
 def update_codebooks(X, B, h, V=False, method="fastbin"):
     """update_codebooks(X, B, h, V=false, method="fastbin") -> C       (src/codebook_update.jl:235-277)
 
-    Only "fastbin" runs here; any other method raises ValueError naming it."""
+    Only "fastbin" runs here; any other method raises ValueError naming it.  Past 256 codewords per codebook the update over
+    16-bit codes runs (update_codebooks_u16: h <= 32767, m * h <= 16384); h <= 256 stays on update_codebooks_fast_bin."""
     if method not in METHODS:
         raise ValueError("Codebook update method unknown: %r" % (method,))
     if method != "fastbin":
         raise ValueError("codebook update method %r is not supported; only \"fastbin\" is" % (method,))
-    return update_codebooks_fast_bin(X, B, h, V)
+    if int(h) <= 256:
+        return update_codebooks_fast_bin(X, B, h, V)
+    X = _as_f32(X, "X")
+    B = np.asarray(B)
+    n, d = X.shape
+    m = B.shape[1] if B.ndim == 2 else -1
+    _check_update(n, d, B.shape, m, h, 1e-4, wide=True)
+    if B.size and (B.min() < 1 or B.max() > h):
+        raise ValueError("codes must be in 1..%d" % h)
+    C = update_codebooks_u16(X, B.astype(np.int16) - 1, h)
+    if V:
+        print("Doing fast bin codebook update... done.")
+    return list(C)
 
 
 def get_cbdims_chain(d, m):

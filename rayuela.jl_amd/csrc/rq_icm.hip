@@ -289,6 +289,14 @@ int host_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *w
   return RQ_OK;
 }
 
+int host_code_range(const int16_t *codes, int64_t n, int m, int h, int code_base, const char *who) {
+  for (int64_t e = 0; e < n * m; ++e)
+    if (codes[e] < code_base || codes[e] > h - 1 + code_base)
+      return fail(RQ_EINVAL, "%s: code %d at [%lld][%lld] is outside %d..%d", who, codes[e], (long long)(e / m), (long long)(e % m),
+                  code_base, h - 1 + code_base);
+  return RQ_OK;
+}
+
 int icm_check_args(const void *codes_out, const void *codes_in, const void *X, const void *C, int64_t n, int d, int m,
                    int h, int ilsiter, int icmiter, int npert, int64_t t0, int nsplits) {
   if (m < 1 || m > ICM_MAX_M) return fail(RQ_EINVAL, "encode_icm: m=%d outside 1..%d", m, ICM_MAX_M);

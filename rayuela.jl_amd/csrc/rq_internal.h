@@ -479,6 +479,8 @@ RQ_LOCAL int ervq_increment_launch(float *Cj, unsigned int *counts, const float 
 // ---- LSQ encoding (rq_icm.hip): argument checks, and the device body of rq_dev_encode_icm (codes already in range) -----
 int dev_code_range(const uint8_t *codes, int64_t n, int m, int h, hipStream_t stream, const char *who);   // codes [n][m] < h
 RQ_LOCAL int host_code_range(const uint8_t *codes, int64_t n, int m, int h, const char *who);   // on host codes; names the first one >= h
+// the same on host int16 codes: every code in code_base .. code_base + h - 1; names the first one outside
+RQ_LOCAL int host_code_range(const int16_t *codes, int64_t n, int m, int h, int code_base, const char *who);
 int icm_check_args(const void *codes_out, const void *codes_in, const void *X, const void *C, int64_t n, int d, int m,
                    int h, int ilsiter, int icmiter, int npert, int64_t t0, int nsplits);
 int icm_encode_dev(uint8_t *codes_out, const uint8_t *codes_in, float *cost_out, const float *X, const float *C,

@@ -10,6 +10,11 @@
 //   lsq_pair_kernel        pair counts of codebooks i < j into a u32 mh x mh matrix (integer atomics: exact, order-free)
 //   lsq_bsum_kernel        b[(i,a)][k] = sum over the rows of segment (i,a), ascending, in f64 from +0, lanes over k
 //   lsq_assemble_kernel    A = the full symmetric matrix, fl64(count + rho) on the diagonal
+// Past 256 codewords (int16 codes, 2 <= h <= RQ_MAX_H16) the sort is two stable passes of the same trio,
+// the low 8 bits of the code and then its high 7 bits over the first pass's list (an LSD radix sort: LDS stays at 256 counters),
+// and the segment bounds come from
+//   lsq_code_hist_kernel   cnt[i][a] = rows with code a in codebook i (integer atomics)
+//   lsq_segs_scan_kernel   per codebook: segs[i][0..h] = the exclusive scan of cnt[i]
 // The solve: blocked right-looking Cholesky A = L L' (NB = 64; one-workgroup diagonal factor, a row-per-thread panel
 // solve and an f64 SYRK/GEMM update of the trailing matrix), forward and back substitution with d right-hand sides,
 // then C = (float) A^-1 b in the [m][h][d] image rq_encode_icm reads.  Every sum runs in a fixed order and no float
@@ -31,19 +36,34 @@ constexpr int GT = 64;           // output tile of the GEMM update
 constexpr int KC = 32;           // K chunk of the GEMM update staged in LDS
 
 // ---- counting sort of the row ids by code, per codebook ------------------------------------------------------------
-__global__ __launch_bounds__(256) void lsq_tile_hist_kernel(uint32_t *th, const uint8_t *codes, int64_t n, int m, int h,
-                                                            int ntiles) {
+// The sort key of pass PASS: the code's low 8 bits, then its high 7 (a byte code has pass 0 only, and is its own key).
+template <int PASS, class Code>
+__device__ __forceinline__ int lsq_digit(Code c) {
+  return PASS == 0 ? ((int)c & 255) : ((int)c >> 8);
+}
+
+// Pass 0 takes the rows in their own order; pass 1 takes position p's row from pass 0's list `in` ([m][n], or null).
+// nd = the number of key values of the pass (h when h <= 256, else 256 and then ceil(h / 256)).
+template <class Code, int PASS>
+__global__ __launch_bounds__(256) void lsq_tile_hist_kernel(uint32_t *th, const Code *codes, const uint32_t *in, int64_t n, int m,
+                                                            int nd, int ntiles) {
   __shared__ uint32_t hist[256];
   const int tile = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
   hist[tid] = 0;
   __syncthreads();
+  const uint32_t *ids = PASS ? in + (size_t)i * n : nullptr;
   const int64_t r0 = (int64_t)tile * LSQ_TILE, r1 = std::min<int64_t>(n, r0 + LSQ_TILE);
-  for (int64_t r = r0 + tid; r < r1; r += 256) atomicAdd(&hist[codes[r * m + i]], 1u);
+  for (int64_t r = r0 + tid; r < r1; r += 256) {
+    const int64_t row = PASS ? (int64_t)ids[r] : r;
+    atomicAdd(&hist[lsq_digit<PASS>(codes[row * m + i])], 1u);
+  }
   __syncthreads();
-  if (tid < h) th[((size_t)i * h + tid) * ntiles + tile] = hist[tid];
+  if (tid < nd) th[((size_t)i * nd + tid) * ntiles + tile] = hist[tid];
 }
 
-// th[i] (h x ntiles, code-major) -> exclusive prefix sums in place; segs[i][a] = first slot of code a, segs[i][h] = n
+// th[i] (h x ntiles, code-major) -> exclusive prefix sums in place; SEGS: segs[i][a] = first slot of code a, segs[i][h] = n
+// (the passes of the wide sort scan their key values and leave segs to lsq_segs_scan_kernel)
+template <bool SEGS>
 __global__ __launch_bounds__(256) void lsq_scan_kernel(uint32_t *th, uint32_t *segs, int64_t n, int h, int ntiles) {
   __shared__ uint32_t part[256];
   const int i = blockIdx.x, tid = threadIdx.x;
@@ -67,30 +87,34 @@ __global__ __launch_bounds__(256) void lsq_scan_kernel(uint32_t *th, uint32_t *s
   for (int64_t j = beg; j < end; ++j) {
     const uint32_t v = t[j];
     t[j] = run;
-    if (j % ntiles == 0) segs[(size_t)i * (h + 1) + j / ntiles] = run;
+    if (SEGS && j % ntiles == 0) segs[(size_t)i * (h + 1) + j / ntiles] = run;
     run += v;
   }
-  if (tid == 0) segs[(size_t)i * (h + 1) + h] = (uint32_t)n;
+  if (SEGS && tid == 0) segs[(size_t)i * (h + 1) + h] = (uint32_t)n;
 }
 
 // Rows of a tile in passes of 256 (4 wavefronts x 64 lanes, ascending); a lane's slot = the code's running slot + the
 // counts of the same code in earlier wavefronts of the pass + its rank among the lanes of its wavefront with that code.
-__global__ __launch_bounds__(256) void lsq_scatter_kernel(uint32_t *sorted, const uint32_t *th, const uint8_t *codes,
-                                                          int64_t n, int m, int h, int ntiles) {
+// Stable, so pass 1 over pass 0's list leaves every (codebook, code) segment in ascending row order.
+template <class Code, int PASS>
+__global__ __launch_bounds__(256) void lsq_scatter_kernel(uint32_t *sorted, const uint32_t *th, const Code *codes,
+                                                          const uint32_t *in, int64_t n, int m, int nd, int ntiles) {
   __shared__ uint32_t run[256];
   __shared__ uint32_t wc[4][256];
   const int tile = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
-  if (tid < h) run[tid] = th[((size_t)i * h + tid) * ntiles + tile];
+  if (tid < nd) run[tid] = th[((size_t)i * nd + tid) * ntiles + tile];
   for (int q = 0; q < 4; ++q) wc[q][tid] = 0;
   __syncthreads();
   uint32_t *out = sorted + (size_t)i * n;
+  const uint32_t *ids = PASS ? in + (size_t)i * n : nullptr;
   const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const int64_t r0 = (int64_t)tile * LSQ_TILE, r1 = std::min<int64_t>(n, r0 + LSQ_TILE);
   for (int64_t p0 = r0; p0 < r1; p0 += 256) {
-    const int64_t r = p0 + tid;
-    const bool valid = r < r1;
-    const int c = valid ? (int)codes[r * m + i] : 0;
+    const int64_t p = p0 + tid;
+    const bool valid = p < r1;
+    const int64_t r = !valid ? 0 : PASS ? (int64_t)ids[p] : p;
+    const int c = valid ? lsq_digit<PASS>(codes[r * m + i]) : 0;
     uint64_t mask = __ballot(valid);
 #pragma unroll
     for (int bit = 0; bit < 8; ++bit) {
@@ -107,7 +131,7 @@ __global__ __launch_bounds__(256) void lsq_scatter_kernel(uint32_t *sorted, cons
       out[pos] = (uint32_t)r;
     }
     __syncthreads();
-    if (tid < h) {
+    if (tid < nd) {
       run[tid] += wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
       wc[0][tid] = wc[1][tid] = wc[2][tid] = wc[3][tid] = 0;
     }
@@ -115,8 +139,44 @@ __global__ __launch_bounds__(256) void lsq_scatter_kernel(uint32_t *sorted, cons
   }
 }
 
+// ---- the segment bounds past 256 codewords ---------------------------------------------------------------------------
+// cnt [m][h], zeroed by the caller; codes in range (checked before any work), so every index is inside cnt
+__global__ __launch_bounds__(256) void lsq_code_hist_kernel(uint32_t *cnt, const int16_t *codes, int64_t nelem, int m, int h) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nelem; e += (int64_t)gridDim.x * 256)
+    atomicAdd(&cnt[(size_t)(e % m) * h + (int)codes[e]], 1u);
+}
+
+// segs[i][a] = the rows of codebook i with a code below a, a = 0..h (segs[i][h] = n): a chunk of the codes per thread
+__global__ __launch_bounds__(256) void lsq_segs_scan_kernel(uint32_t *segs, const uint32_t *cnt, int64_t n, int h) {
+  __shared__ uint32_t part[256];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const uint32_t *c = cnt + (size_t)i * h;
+  uint32_t *out = segs + (size_t)i * (h + 1);
+  const int chunk = (h + 255) / 256, beg = std::min(h, tid * chunk), end = std::min(h, beg + chunk);
+  uint32_t s = 0;
+  for (int a = beg; a < end; ++a) s += c[a];
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t run = 0;
+    for (int q = 0; q < 256; ++q) {
+      const uint32_t v = part[q];
+      part[q] = run;
+      run += v;
+    }
+  }
+  __syncthreads();
+  uint32_t run = part[tid];
+  for (int a = beg; a < end; ++a) {
+    out[a] = run;
+    run += c[a];
+  }
+  if (tid == 0) out[h] = (uint32_t)n;
+}
+
 // ---- A -------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void lsq_pair_kernel(uint32_t *P, const uint8_t *codes, int64_t n, int m, int h) {
+template <class Code>
+__global__ __launch_bounds__(256) void lsq_pair_kernel(uint32_t *P, const Code *codes, int64_t n, int m, int h) {
   const int mh = m * h;
   for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
     int b[LSQ_MAX_M];
@@ -323,10 +383,11 @@ __global__ __launch_bounds__(1024) void lsq_mean_kernel(double *out, const float
   if (tid == 0) *out = part[0] / (double)n;
 }
 
+// hmax: 256 for the byte entries, RQ_MAX_H16 for the entries over int16 codes
 int lsq_check(const void *out0, const void *out1, const void *X, const void *codes, int64_t n, int d, int m, int h,
-              double rho, const char *who) {
+              double rho, const char *who, int hmax = 256) {
   if (m < 1 || m > LSQ_MAX_M) return fail(RQ_EINVAL, "%s: m=%d outside 1..%d", who, m, LSQ_MAX_M);
-  if (h < 2 || h > 256) return fail(RQ_EINVAL, "%s: h=%d outside 2..256", who, h);
+  if (h < 2 || h > hmax) return fail(RQ_EINVAL, "%s: h=%d outside 2..%d", who, h, hmax);
   if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
   if (n < 0 || n > (int64_t)UINT32_MAX)
     return fail(RQ_EINVAL, "%s: n=%lld outside 0..%u (the u32 counters)", who, (long long)n, UINT32_MAX);
@@ -342,43 +403,104 @@ int lsq_check(const void *out0, const void *out1, const void *X, const void *cod
 enum { PH_COUNT, PH_SORT, PH_B, PH_ASSEMBLE, PH_SOLVE, PH_OTHER, PH_ENCODE, PH_N };
 thread_local double g_lsq_ms[PH_N] = {0};
 
-// A [mh][mh], b [mh][d] f64 (device pointers; arguments checked, codes in range)
-int normal_eq_dev(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
-                  hipStream_t s, PhaseClock &clk) {
+// The limit of the entries over int16 codes: A is then at most 2 GiB of f64 (the library's per-slot scratch figure), the u32 pair
+// counts at most 1 GiB.  The byte entries stop at 16 * 256 = 4096.
+constexpr int LSQ_MAX_MH = 16384;
+
+// WS_LSQ_S of one call: pair counts | tile histograms | segment bounds | per-code counts (h > 256) | the sorted row lists
+struct LsqScratch {
+  int ntiles, nd;       // tiles of LSQ_TILE rows; key values of the first sort pass
+  size_t pair_bytes, th_bytes, seg_bytes, cnt_bytes, sort_bytes;
+  size_t total() const { return pair_bytes + th_bytes + seg_bytes + cnt_bytes + sort_bytes; }
+};
+
+// with_A false: b and the segments alone, no mh x mh buffer
+LsqScratch lsq_scratch(int64_t n, int m, int h, bool with_A) {
+  LsqScratch L;
+  const size_t mh = (size_t)m * h;
+  L.ntiles = (int)std::max<int64_t>(1, (n + LSQ_TILE - 1) / LSQ_TILE);
+  L.nd = std::min(h, 256);
+  L.pair_bytes = with_A ? mh * mh * 4 : 0;
+  L.th_bytes = (size_t)m * L.nd * L.ntiles * 4;
+  L.seg_bytes = ((size_t)m * (h + 1) * 4 + 255) & ~(size_t)255;
+  L.cnt_bytes = h > 256 ? (mh * 4 + 255) & ~(size_t)255 : 0;
+  L.sort_bytes = (size_t)m * n * 4 * (h > 256 ? 2 : 1);     // h > 256: one list per pass
+  return L;
+}
+
+// A [mh][mh], b [mh][d] f64 (device pointers; arguments checked, codes in range).  Code: uint8_t (h <= 256) or int16_t
+// (zero-based, h <= RQ_MAX_H16; at h <= 256 it queues what the byte instantiation queues).  A null (int16 entries only): b and
+// the segments alone.  *segs_out (may be null) <- the segment bounds [m][h + 1] in WS_LSQ_S.
+template <class Code>
+int normal_eq_dev(double *A, double *b, const float *X, const Code *codes, int64_t n, int d, int m, int h, double rho,
+                  hipStream_t s, PhaseClock &clk, const uint32_t **segs_out = nullptr) {
   const int mh = m * h;
-  const int ntiles = (int)std::max<int64_t>(1, (n + LSQ_TILE - 1) / LSQ_TILE);
-  const size_t pair_bytes = (size_t)mh * mh * 4, th_bytes = (size_t)m * h * ntiles * 4;
-  const size_t seg_bytes = ((size_t)m * (h + 1) * 4 + 255) & ~(size_t)255;
-  const size_t sort_bytes = (size_t)m * n * 4;
+  const LsqScratch L = lsq_scratch(n, m, h, A != nullptr);
+  const int ntiles = L.ntiles;
   void *ws = nullptr;
-  RQ_TRY(workspace(WS_LSQ_S, pair_bytes + th_bytes + seg_bytes + sort_bytes, &ws, s));
-  uint32_t *P = (uint32_t *)ws, *th = P + pair_bytes / 4, *segs = th + th_bytes / 4, *sorted = segs + seg_bytes / 4;
-  RQ_HIP(hipMemsetAsync(P, 0, pair_bytes, s));
-  RQ_HIP(hipMemsetAsync(th, 0, th_bytes, s));
-  if (n > 0 && m > 1) {
+  RQ_TRY(workspace(WS_LSQ_S, L.total(), &ws, s));
+  uint32_t *P = (uint32_t *)ws, *th = P + L.pair_bytes / 4, *segs = th + L.th_bytes / 4, *cnt = segs + L.seg_bytes / 4;
+  uint32_t *sorted = cnt + L.cnt_bytes / 4;
+  if (A) RQ_HIP(hipMemsetAsync(P, 0, L.pair_bytes, s));
+  RQ_HIP(hipMemsetAsync(th, 0, L.th_bytes, s));
+  if (A && n > 0 && m > 1) {
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL(lsq_pair_kernel, dim3(grid), dim3(256), 0, s, P, codes, n, m, h);
+    hipLaunchKernelGGL(lsq_pair_kernel<Code>, dim3(grid), dim3(256), 0, s, P, codes, n, m, h);
     RQ_HIP(hipGetLastError());
+  }
+  if constexpr (std::is_same<Code, int16_t>::value) {
+    if (h > 256) {
+      RQ_HIP(hipMemsetAsync(cnt, 0, L.cnt_bytes, s));
+      const int64_t nelem = n * m;
+      if (nelem > 0)
+        RQ_LAUNCH(lsq_code_hist_kernel, dim3((unsigned)std::min<int64_t>((nelem + 255) / 256, 8192)), dim3(256), 0, s, cnt, codes,
+                  nelem, m, h);
+    }
   }
   clk.mark(PH_COUNT);
-  if (n > 0) {
-    hipLaunchKernelGGL(lsq_tile_hist_kernel, dim3(ntiles, m), dim3(256), 0, s, th, codes, n, m, h, ntiles);
+  if (h <= 256) {
+    if (n > 0) {
+      hipLaunchKernelGGL((lsq_tile_hist_kernel<Code, 0>), dim3(ntiles, m), dim3(256), 0, s, th, codes, (const uint32_t *)nullptr, n,
+                         m, h, ntiles);
+      RQ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(lsq_scan_kernel<true>, dim3(m), dim3(256), 0, s, th, segs, n, h, ntiles);
     RQ_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(lsq_scan_kernel, dim3(m), dim3(256), 0, s, th, segs, n, h, ntiles);
-  RQ_HIP(hipGetLastError());
-  if (n > 0) {
-    hipLaunchKernelGGL(lsq_scatter_kernel, dim3(ntiles, m), dim3(256), 0, s, sorted, th, codes, n, m, h, ntiles);
-    RQ_HIP(hipGetLastError());
+    if (n > 0) {
+      hipLaunchKernelGGL((lsq_scatter_kernel<Code, 0>), dim3(ntiles, m), dim3(256), 0, s, sorted, th, codes,
+                         (const uint32_t *)nullptr, n, m, h, ntiles);
+      RQ_HIP(hipGetLastError());
+    }
+  } else if constexpr (std::is_same<Code, int16_t>::value) {
+    // LSD radix sort: the low 8 bits, then the high 7 over the first list; both passes are stable
+    uint32_t *list0 = sorted, *list1 = sorted + (size_t)m * n;
+    const int nd1 = (h + 255) >> 8;
+    if (n > 0) {
+      const uint32_t *none = nullptr;
+      RQ_LAUNCH((lsq_tile_hist_kernel<Code, 0>), dim3(ntiles, m), dim3(256), 0, s, th, codes, none, n, m, 256, ntiles);
+      RQ_LAUNCH(lsq_scan_kernel<false>, dim3(m), dim3(256), 0, s, th, (uint32_t *)nullptr, n, 256, ntiles);
+      RQ_LAUNCH((lsq_scatter_kernel<Code, 0>), dim3(ntiles, m), dim3(256), 0, s, list0, (const uint32_t *)th, codes, none, n, m,
+                256, ntiles);
+      RQ_LAUNCH((lsq_tile_hist_kernel<Code, 1>), dim3(ntiles, m), dim3(256), 0, s, th, codes, (const uint32_t *)list0, n, m, nd1,
+                ntiles);
+      RQ_LAUNCH(lsq_scan_kernel<false>, dim3(m), dim3(256), 0, s, th, (uint32_t *)nullptr, n, nd1, ntiles);
+      RQ_LAUNCH((lsq_scatter_kernel<Code, 1>), dim3(ntiles, m), dim3(256), 0, s, list1, (const uint32_t *)th, codes,
+                (const uint32_t *)list0, n, m, nd1, ntiles);
+    }
+    RQ_LAUNCH(lsq_segs_scan_kernel, dim3(m), dim3(256), 0, s, segs, (const uint32_t *)cnt, n, h);
+    sorted = list1;
   }
   clk.mark(PH_SORT);
   const int bt = d <= 64 ? 64 : d <= 128 ? 128 : 256;
   hipLaunchKernelGGL(lsq_bsum_kernel, dim3(mh), dim3(bt), 0, s, b, X, sorted, segs, n, d, h);
   RQ_HIP(hipGetLastError());
   clk.mark(PH_B);
-  hipLaunchKernelGGL(lsq_assemble_kernel, dim3((mh + 255) / 256, mh), dim3(256), 0, s, A, P, segs, m, h, rho);
-  RQ_HIP(hipGetLastError());
+  if (A) {
+    hipLaunchKernelGGL(lsq_assemble_kernel, dim3((mh + 255) / 256, mh), dim3(256), 0, s, A, P, segs, m, h, rho);
+    RQ_HIP(hipGetLastError());
+  }
   clk.mark(PH_ASSEMBLE);
+  if (segs_out) *segs_out = segs;
   return RQ_OK;
 }
 
@@ -416,7 +538,8 @@ int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
 }
 
 // C [m][h][d] f32 <- the fastbin update of (X, codes) (device pointers; arguments checked, codes in range)
-int update_dev(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho, hipStream_t s,
+template <class Code>
+int update_dev(float *C, const float *X, const Code *codes, int64_t n, int d, int m, int h, double rho, hipStream_t s,
                PhaseClock &clk) {
   const int mh = m * h;
   void *wa = nullptr, *wb = nullptr;
@@ -470,6 +593,112 @@ int lsq_mean_launch(double *out, const float *cost, int64_t n, hipStream_t s) {
   RQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, out, cost, n);
   return RQ_OK;
 }
+
+namespace {
+
+// the encoder of a training loop by code type: rq_icm.hip's over bytes, rq_icm_h16.hip's over int16 codes (no phase clock)
+int lsq_encode_dev(uint8_t *B, float *cost, const float *X, const float *C, int64_t n, int d, int m, int h, int ilsiter,
+                   int icmiter, int npert, int randord, uint64_t seed, int64_t t0, int nsplits, hipStream_t s) {
+  return icm_encode_dev(B, B, cost, X, C, n, d, m, h, ilsiter, icmiter, npert, randord, seed, t0, nsplits, s, nullptr);
+}
+int lsq_encode_dev(int16_t *B, float *cost, const float *X, const float *C, int64_t n, int d, int m, int h, int ilsiter,
+                   int icmiter, int npert, int randord, uint64_t seed, int64_t t0, int nsplits, hipStream_t s) {
+  return icm_encode_wide_dev(B, B, cost, X, C, n, d, m, h, ilsiter, icmiter, npert, randord, seed, t0, nsplits, s, nullptr);
+}
+
+// rq_train_lsq / rq_train_lsq_wide after their argument checks (src/LSQ.jl:345-371).  codes [n][m] on the host, in
+// code_base .. code_base + h - 1 (bytes: code_base 0); the loop runs on zero-based codes.
+template <class Code>
+int train_lsq_host(float *C, Code *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h, int niter,
+                   int ilsiter, int icmiter, int npert, int randord, uint64_t seed, int nsplits, int code_base) {
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  const int mh = m * h;
+  const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4, kb = (size_t)n * m * sizeof(Code);
+  DevMem dX, dRX, dR, dC, dC2, dcodes, dcost, dobj;
+  RQ_TRY(dX.alloc(xb));
+  RQ_TRY(dcodes.alloc(kb));
+  RQ_TRY(dC.alloc(cb));
+  RQ_TRY(dcost.alloc((size_t)n * 4));
+  RQ_TRY(dobj.alloc((size_t)(niter + 1) * 8));
+  if (n > 0) {
+    RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(dcodes.p, codes, kb, hipMemcpyHostToDevice));
+  }
+  const float *Xd = (const float *)dX.p;
+  Code *B = (Code *)dcodes.p;
+  float *Cd = (float *)dC.p, *cost = (float *)dcost.p;
+  double *objd = (double *)dobj.p;
+  const hipStream_t s = nullptr;
+  lsq_clock_reset();
+  PhaseClock clk(s, g_lsq_ms);
+  if constexpr (std::is_same<Code, int16_t>::value) {
+    if (code_base) {
+      RQ_TRY(add_base_codes_launch(B, n * m, -code_base, s));
+      clk.mark(PH_OTHER);
+    }
+  }
+  // C = update(R'X, B); C_i <- R C_i   (src/LSQ.jl:345-350)
+  if (R) {
+    RQ_TRY(upload_rotation(dR, dRX, R, Xd, n, d, di.num_cu, s));
+    RQ_TRY(dC2.alloc(cb));
+    const float *Rtd = dR.as<float>() + (size_t)d * d;
+    clk.mark(PH_OTHER);
+    RQ_TRY(update_dev((float *)dC2.p, (const float *)dRX.p, (const Code *)B, n, d, m, h, 1e-4, s, clk));
+    RQ_TRY(rotate_launch(Cd, Rtd, (const float *)dC2.p, d, mh, di.num_cu, s));
+    clk.mark(PH_OTHER);
+  } else {
+    RQ_TRY(update_dev(Cd, Xd, (const Code *)B, n, d, m, h, 1e-4, s, clk));
+  }
+  // encode call e runs ILS iterations e * ilsiter .. (e + 1) * ilsiter - 1 of one stream
+  RQ_TRY(lsq_encode_dev(B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed, 0, nsplits, s));
+  clk.mark(PH_ENCODE);
+  for (int it = 1; it <= niter; ++it) {
+    // obj[iter] = qerror(X, B, C): the mean of the previous encode's per-row costs (NaN when n = 0: a mean of no rows)
+    RQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, objd + (it - 1), (const float *)cost, n);
+    clk.mark(PH_OTHER);
+    RQ_TRY(update_dev(Cd, Xd, (const Code *)B, n, d, m, h, 1e-4, s, clk));
+    RQ_TRY(lsq_encode_dev(B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed, (int64_t)it * ilsiter, nsplits, s));
+    clk.mark(PH_ENCODE);
+  }
+  if constexpr (std::is_same<Code, int16_t>::value) {
+    if (code_base) {
+      RQ_TRY(add_base_codes_launch(B, n * m, code_base, s));
+      clk.mark(PH_OTHER);
+    }
+  }
+  clk.collect();
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(C, Cd, cb, hipMemcpyDeviceToHost));
+  if (n > 0) RQ_HIP(hipMemcpy(codes, B, kb, hipMemcpyDeviceToHost));
+  if (niter > 0) RQ_HIP(hipMemcpy(obj, objd, (size_t)niter * 8, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+// every check of the entries over int16 codes that needs no device: the shape, rho, the pointers and code_base (RQ_EINVAL), then
+// -- with_A -- m * h within LSQ_MAX_MH (RQ_EUNSUPPORTED)
+int lsq_wide_check(const void *out0, const void *out1, const void *X, const void *codes, int64_t n, int d, int m, int h, double rho,
+                   int code_base, bool with_A, const char *who) {
+  RQ_TRY(lsq_check(out0, out1, X, codes, n, d, m, h, rho, who, RQ_MAX_H16));
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  if (with_A && m * h > LSQ_MAX_MH)
+    return fail(RQ_EUNSUPPORTED, "%s: m * h = %d * %d exceeds %d (A would take %zu bytes of f64)", who, m, h, LSQ_MAX_MH,
+                (size_t)m * h * m * h * 8);
+  return RQ_OK;
+}
+
+// uploads the caller's int16 codes and makes them zero-based
+int upload_codes_h16(DevMem &dcodes, const int16_t *codes, int64_t n, int m, int code_base, hipStream_t s) {
+  RQ_TRY(dcodes.alloc((size_t)n * m * 2));
+  if (n > 0) {
+    RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m * 2, hipMemcpyHostToDevice));
+    if (code_base) RQ_TRY(add_base_codes_launch(dcodes.as<int16_t>(), n * m, -code_base, s));
+  }
+  return RQ_OK;
+}
+
+}  // namespace
 
 }  // namespace rq
 
@@ -538,58 +767,99 @@ extern "C" int rq_train_lsq(float *C, uint8_t *codes, double *obj, const float *
     return fail(RQ_EINVAL, "train_lsq: ilsiter * (niter + 1) overflows the ILS iteration counter");
   RQ_TRY(icm_check_args(codes, codes, X, C, n, d, m, h, ilsiter, icmiter, npert, 0, nsplits));
   RQ_TRY(host_code_range(codes, n, m, h, "train_lsq"));
+  return train_lsq_host<uint8_t>(C, codes, obj, X, R, n, d, m, h, niter, ilsiter, icmiter, npert, randord, seed, nsplits, 0);
+}
+
+// ---- 2 <= h <= RQ_MAX_H16 over int16 codes: the int16 instantiations at EVERY h, host pointers --------
+extern "C" int rq_lsq_wide_plan(int64_t n, int d, int m, int h, int64_t *out, int cap) {
+  if (!out || cap < 0) return fail(RQ_EINVAL, "rq_lsq_wide_plan: null pointer or negative cap");
+  RQ_TRY(lsq_wide_check(out, out, out, out, n, d, m, h, 1e-4, 0, true, "rq_lsq_wide_plan"));
+  const LsqScratch L = lsq_scratch(n, m, h, true);
+  const int64_t mh = (int64_t)m * h;
+  int64_t none = 0;
+  const int64_t train = rq_icm_wide_plan(n, d, m, h, 1, &none, 0) == RQ_OK ? 1 : 0;
+  const int64_t v[7] = {mh, mh * mh * 8, (int64_t)L.pair_bytes, (int64_t)(L.total() - L.pair_bytes), L.ntiles, (mh + NB - 1) / NB,
+                        train};
+  for (int q = 0; q < cap && q < 7; ++q) out[q] = v[q];
+  return RQ_OK;
+}
+
+extern "C" int rq_lsq_normal_eq_wide(double *A, double *b, uint32_t *counts, const float *X, const int16_t *codes, int64_t n,
+                                     int d, int m, int h, double rho, int code_base) {
+  const char *who = "lsq_normal_eq_wide";
+  RQ_TRY(lsq_wide_check(b, b, X, codes, n, d, m, h, rho, code_base, A != nullptr, who));
+  RQ_TRY(host_code_range(codes, n, m, h, code_base, who));
   DeviceInfo di;
   RQ_TRY(device_info(&di));
   DeviceLock call_lock;
-  const int mh = m * h;
-  const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4;
-  DevMem dX, dRX, dR, dC, dC2, dcodes, dcost, dobj;
-  RQ_TRY(dX.alloc(xb));
-  RQ_TRY(dcodes.alloc((size_t)n * m));
-  RQ_TRY(dC.alloc(cb));
-  RQ_TRY(dcost.alloc((size_t)n * 4));
-  RQ_TRY(dobj.alloc((size_t)(niter + 1) * 8));
-  if (n > 0) {
-    RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
-    RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
-  }
-  const float *Xd = (const float *)dX.p;
-  uint8_t *B = (uint8_t *)dcodes.p;
-  float *Cd = (float *)dC.p, *cost = (float *)dcost.p;
-  double *objd = (double *)dobj.p;
-  const hipStream_t s = nullptr;
+  const size_t mh = (size_t)m * h;
+  DevMem dX, dcodes, dA, db;
+  RQ_TRY(dX.alloc((size_t)n * d * 4));
+  if (A) RQ_TRY(dA.alloc(mh * mh * 8));
+  RQ_TRY(db.alloc(mh * d * 8));
+  if (n > 0) RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
+  RQ_TRY(upload_codes_h16(dcodes, codes, n, m, code_base, nullptr));
   lsq_clock_reset();
-  PhaseClock clk(s, g_lsq_ms);
-  // C = update(R'X, B); C_i <- R C_i   (src/LSQ.jl:345-350)
-  if (R) {
-    RQ_TRY(upload_rotation(dR, dRX, R, Xd, n, d, di.num_cu, s));
-    RQ_TRY(dC2.alloc(cb));
-    const float *Rtd = dR.as<float>() + (size_t)d * d;
-    clk.mark(PH_OTHER);
-    RQ_TRY(update_dev((float *)dC2.p, (const float *)dRX.p, B, n, d, m, h, 1e-4, s, clk));
-    RQ_TRY(rotate_launch(Cd, Rtd, (const float *)dC2.p, d, mh, di.num_cu, s));
-    clk.mark(PH_OTHER);
-  } else {
-    RQ_TRY(update_dev(Cd, Xd, B, n, d, m, h, 1e-4, s, clk));
-  }
-  // encode call e runs ILS iterations e * ilsiter .. (e + 1) * ilsiter - 1 of one stream
-  RQ_TRY(icm_encode_dev(B, B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed, 0, nsplits, s, nullptr));
-  clk.mark(PH_ENCODE);
-  for (int it = 1; it <= niter; ++it) {
-    // obj[iter] = qerror(X, B, C): the mean of the previous encode's per-row costs (NaN when n = 0: a mean of no rows)
-    RQ_LAUNCH(lsq_mean_kernel, dim3(1), dim3(1024), 0, s, objd + (it - 1), (const float *)cost, n);
-    clk.mark(PH_OTHER);
-    RQ_TRY(update_dev(Cd, Xd, B, n, d, m, h, 1e-4, s, clk));
-    RQ_TRY(icm_encode_dev(B, B, cost, Xd, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed,
-                          (int64_t)it * ilsiter, nsplits, s, nullptr));
-    clk.mark(PH_ENCODE);
-  }
+  PhaseClock clk(nullptr, g_lsq_ms);
+  const uint32_t *segs = nullptr;
+  RQ_TRY(normal_eq_dev(A ? dA.as<double>() : nullptr, db.as<double>(), (const float *)dX.p, (const int16_t *)dcodes.p, n, d, m, h,
+                       rho, nullptr, clk, &segs));
   clk.collect();
   RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(C, Cd, cb, hipMemcpyDeviceToHost));
-  if (n > 0) RQ_HIP(hipMemcpy(codes, B, (size_t)n * m, hipMemcpyDeviceToHost));
-  if (niter > 0) RQ_HIP(hipMemcpy(obj, objd, (size_t)niter * 8, hipMemcpyDeviceToHost));
+  if (A) RQ_HIP(hipMemcpy(A, dA.p, mh * mh * 8, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(b, db.p, mh * d * 8, hipMemcpyDeviceToHost));
+  if (counts) {   // the segment sizes
+    std::vector<uint32_t> sg((size_t)m * (h + 1));
+    RQ_HIP(hipMemcpy(sg.data(), segs, sg.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < m; ++i)
+      for (int a = 0; a < h; ++a) counts[(size_t)i * h + a] = sg[(size_t)i * (h + 1) + a + 1] - sg[(size_t)i * (h + 1) + a];
+  }
   return RQ_OK;
+}
+
+extern "C" int rq_update_codebooks_lsq_wide(float *C, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
+                                            double rho, int code_base) {
+  const char *who = "update_codebooks_lsq_wide";
+  RQ_TRY(lsq_wide_check(C, C, X, codes, n, d, m, h, rho, code_base, true, who));
+  RQ_TRY(host_code_range(codes, n, m, h, code_base, who));
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  DevMem dX, dcodes, dC;
+  RQ_TRY(dX.alloc((size_t)n * d * 4));
+  RQ_TRY(dC.alloc((size_t)m * h * d * 4));
+  if (n > 0) RQ_HIP(hipMemcpy(dX.p, X, (size_t)n * d * 4, hipMemcpyHostToDevice));
+  RQ_TRY(upload_codes_h16(dcodes, codes, n, m, code_base, nullptr));
+  lsq_clock_reset();
+  PhaseClock clk(nullptr, g_lsq_ms);
+  RQ_TRY(update_dev((float *)dC.p, (const float *)dX.p, (const int16_t *)dcodes.p, n, d, m, h, rho, nullptr, clk));
+  clk.collect();
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(C, dC.p, (size_t)m * h * d * 4, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+extern "C" int rq_train_lsq_wide(float *C, int16_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m,
+                                 int h, int niter, int ilsiter, int icmiter, int npert, int randord, uint64_t seed, int nsplits,
+                                 int code_base) {
+  const char *who = "train_lsq_wide";
+  RQ_TRY(lsq_check(C, codes ? codes : (const void *)C, X, codes, n, d, m, h, 1e-4, who, RQ_MAX_H16));
+  if (!codes) return fail(RQ_EINVAL, "%s: null codes", who);
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  if (niter < 0) return fail(RQ_EINVAL, "%s: niter=%d < 0", who, niter);
+  if (niter > 0 && !obj) return fail(RQ_EINVAL, "%s: null obj", who);
+  if (ilsiter < 0 || icmiter < 0) return fail(RQ_EINVAL, "%s: negative count (ilsiter=%d icmiter=%d)", who, ilsiter, icmiter);
+  if (npert < 0 || npert > m) return fail(RQ_EINVAL, "%s: npert=%d outside 0..m=%d", who, npert, m);
+  if ((int64_t)ilsiter * ((int64_t)niter + 1) > INT32_MAX)
+    return fail(RQ_EINVAL, "%s: ilsiter * (niter + 1) overflows the ILS iteration counter", who);
+  int64_t none = 0;
+  RQ_TRY(rq_icm_wide_plan(n, d, m, h, nsplits, &none, 0));   // nsplits, and the encoder's tables within its scratch
+  if (m * h > LSQ_MAX_MH)
+    return fail(RQ_EUNSUPPORTED, "%s: m * h = %d * %d exceeds %d (A would take %zu bytes of f64)", who, m, h, LSQ_MAX_MH,
+                (size_t)m * h * m * h * 8);
+  RQ_TRY(host_code_range(codes, n, m, h, code_base, who));
+  return train_lsq_host<int16_t>(C, codes, obj, X, R, n, d, m, h, niter, ilsiter, icmiter, npert, randord, seed, nsplits,
+                                 code_base);
 }
 
 extern "C" int rq_last_lsq_timing(double *ms, int cap) {
