@@ -410,8 +410,32 @@ int rq_dev_reconstruct_aq(float *CB, const uint8_t *codes, const float *C, int64
  * reported as RQ_EUNSUPPORTED. */
 int rq_train_chainq(float *C, uint8_t *codes, float *R, double *obj, const float *X, int64_t n, int d, int m, int h,
                     int niter);
-/* milliseconds of this thread's last host-pointer chain call by phase (hipEvents; the device entries leave zeros), summed
- * over a training call: {unaries, pair tables + self-products, forward pass + back trace, codebook updates, rotation work
+/* ---- chain quantization with 2 <= h <= RQ_MAX_H16 codewords per codebook: the contracts of
+ * rq_quantize_chainq, rq_update_codebooks_chain and rq_train_chainq word for word over codes [n][m] int16 in code_base ..
+ * code_base + h - 1 (code_base 0 or 1), host pointers; m as for the byte entries.  The int16 kernels run at EVERY h; at h <= 256
+ * the codes, C, R and obj are those of the byte entries bit for bit (on finite inputs; non-finite inputs give unspecified but
+ * in-range codes, as there).
+ * Shape rule of the encoder: with HS = 64 * ceil(h / 64), the tables take T = 2 * (m - 1) * h * HS * 4 + m * h * 4 bytes (both
+ * orientations of the m - 1 pair tables, and the self-products) and one row of unaries m * HS * 4 bytes; T plus 32 rows must fit
+ * 2 GiB, else RQ_EUNSUPPORTED; rows per chunk = min(ceil(n / nsplits), (2 GiB - T) / row bytes).  (m, h) = (8, 4096), (16, 2048)
+ * and (4, 8192) fit; (2, 16384) does not.  The update and training also need 2 h <= 16384 (one 2h x 2h f64 block is then at
+ * most 2 GiB; no (m h)^2 matrix is built), else RQ_EUNSUPPORTED; training keeps d <= 1024 and needs the encoder's rule.  Every
+ * other violation (m, h, d, n, nsplits, niter, rho, code_base out of range, a null pointer, a code outside its range) is
+ * RQ_EINVAL.  Every check runs before any work and before a device is needed; no output byte is written on error.  There is no
+ * device-pointer form of these entries in the C ABI yet. */
+int rq_quantize_chainq_wide(int16_t *codes, const float *X, const float *C, int64_t n, int d, int m, int h, int nsplits,
+                            int code_base);
+int rq_update_codebooks_chain_wide(float *C, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, double rho,
+                                   int code_base);
+int rq_train_chainq_wide(float *C, int16_t *codes, float *R, double *obj, const float *X, int64_t n, int d, int m, int h,
+                         int niter, int code_base);
+/* The shape rule and sizes of the entries above, no device touched: out[0 .. min(cap, 7) - 1] = {HS, table bytes T, bytes of one
+ * row's unaries, rows per chunk, chunks (both 0 when n = 0), bytes of the update's 2h x 2h f64 block, 1 when
+ * rq_update_codebooks_chain_wide AND rq_train_chainq_wide can run the shape (m >= 2, m - 1 <= d <= 1024, 2 h <= 16384) else 0}.
+ * Returns what rq_quantize_chainq_wide would for the shape; out is written on RQ_OK only. */
+int rq_chain_wide_plan(int64_t n, int d, int m, int h, int nsplits, int64_t *out, int cap);
+/* milliseconds of this thread's last host-pointer chain call (byte or int16 entries) by phase (hipEvents; the device entries
+ * leave zeros), summed over a training call: {unaries, pair tables + self-products, forward pass + back trace, codebook updates, rotation work
  * (R'X, reconstruction, qerror, X CB', polar factor)}; cap entries written */
 int rq_last_chainq_timing(double *ms, int cap);
 

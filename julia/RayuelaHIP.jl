@@ -1096,12 +1096,20 @@ end
 
 # ---- Chain quantization (src/ChainQ.jl:305-348, :373-431; src/codebook_update.jl:280-294, :367-412): the Viterbi
 # recursion, the chain-structured codebook update and the training loop run on the device (DESIGN.md section 2).  These
-# shims follow the LSQ ones above and, like them, have not been run (no Julia was available).
+# shims follow the LSQ ones above and, like them, have not been run (no Julia was available).  Past 256 codewords per codebook
+# they call the entries over Int16 codes (DESIGN.md section 4.26) with code_base = 1: Julia's own one-based codes go in and out.
 function quantize_chainq(X::Matrix{Float32}, C::Vector{Matrix{Float32}}, use_cuda::Bool=false, use_cpp::Bool=false)
   start_time = time_ns()
   d, n  = size(X)
   m     = length(C)
   h     = size(C[1], 2)
+  if h > 256
+    B = Matrix{Int16}(undef, m, n)
+    _check(ccall((:rq_quantize_chainq_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint),
+      B, X, hcat(C...), Int64(n), Cint(d), Cint(m), Cint(h), Cint(1), Cint(1)))
+    return B, (time_ns() - start_time) / 1e9
+  end
   codes = Matrix{UInt8}(undef, m, n)
   _check(ccall((:rq_quantize_chainq, librayuela_hip), Cint,
     (Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
@@ -1120,8 +1128,14 @@ function update_codebooks_chain_bin(X::Matrix{Float32}, B::Matrix{Int16}, h::Int
   start_time = time_ns()
   d, n  = size(X)
   m     = size(B, 1)
-  codes = convert(Matrix{UInt8}, B .- Int16(1))
   Cc    = Matrix{Float32}(undef, d, m * h)
+  if h > 256
+    _check(ccall((:rq_update_codebooks_chain_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Int16}, Int64, Cint, Cint, Cint, Cdouble, Cint),
+      Cc, X, B, Int64(n), Cint(d), Cint(m), Cint(h), Float64(rho), Cint(1)))
+    return _split_codebooks(Cc, m, h), (time_ns() - start_time) / 1e9
+  end
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
   _check(ccall((:rq_update_codebooks_chain, librayuela_hip), Cint,
     (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{UInt8}, Int64, Cint, Cint, Cint, Cdouble),
     Cc, X, codes, Int64(n), Cint(d), Cint(m), Cint(h), Float64(rho)))
@@ -1132,10 +1146,18 @@ function train_chainq(X::Matrix{Float32}, m::Integer, h::Integer, R::Matrix{Floa
                       C::Vector{Matrix{Float32}}, niter::Integer, V::Bool=false)
   V && println("Training a chain quantizer")
   d, n  = size(X)
-  codes = convert(Matrix{UInt8}, B .- Int16(1))
   Cc    = Matrix{Float32}(undef, d, m * h)
   Rn    = copy(R)
   obj   = zeros(Float64, niter + 1)
+  if h > 256
+    Bn = copy(B)
+    _check(ccall((:rq_train_chainq_wide, librayuela_hip), Cint,
+      (Ptr{Cfloat}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint),
+      Cc, Bn, Rn, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), Cint(1)))
+    V && for (it, o) in enumerate(obj); println("$(it - 1) $o"); end
+    return _split_codebooks(Cc, m, h), Bn, Rn, convert(Vector{Float32}, obj)
+  end
+  codes = convert(Matrix{UInt8}, B .- Int16(1))
   _check(ccall((:rq_train_chainq, librayuela_hip), Cint,
     (Ptr{Cfloat}, Ptr{UInt8}, Ptr{Cfloat}, Ptr{Cdouble}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint),
     Cc, codes, Rn, obj, X, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter)))

@@ -21,8 +21,8 @@ from .ERVQ import quantize_ervq, train_ervq, ervq_update_codebook, last_ervq_tim
 from .LSQ import encoding_icm, encode_icm_cuda, veccost, qerror, train_lsq, train_lsq_cuda  # noqa: F401,E402
 from .SR import apply_schedule, SR_C_perturb, SR_D_perturb, train_sr, train_sr_cuda  # noqa: F401,E402
 from .codebook_update import (update_codebooks, update_codebooks_fast_bin, update_codebooks_chain_bin,  # noqa: F401,E402
-                              get_cbdims_chain)
-from .ChainQ import quantize_chainq, train_chainq  # noqa: F401,E402
+                              update_codebooks_chain_bin_u16, get_cbdims_chain)
+from .ChainQ import quantize_chainq, quantize_chainq_u16, train_chainq, train_chainq_u16  # noqa: F401,E402
 from .CompetitiveQ import quantize_competitiveq, quantize_competitiveq_u8, quantize_competitiveq_u16, last_beam_timing  # noqa: F401,E402
 from . import CompetitiveQ  # noqa: F401,E402  (CompetitiveQ.encode: the reference's one-vector signature)
 from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_aqd_query, LsqIndex,  # noqa: F401

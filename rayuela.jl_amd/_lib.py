@@ -107,6 +107,10 @@ SIGNATURES = {
     "rq_dev_reconstruct_aq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "rq_train_chainq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
     "rq_last_chainq_timing": (_i32, [_vp, _i32]),
+    "rq_quantize_chainq_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "rq_update_codebooks_chain_wide": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, _i32]),
+    "rq_train_chainq_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32]),
+    "rq_chain_wide_plan": (_i32, [_i64, _i32, _i32, _i32, _i32, _vp, _i32]),
     "rq_dataset_upload": (_vp, [_vp, _i64, _i32]),
     "rq_dataset_upload_bytes": (_vp, [_vp, _i64, _i32]),
     "rq_dataset_encode": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32]),

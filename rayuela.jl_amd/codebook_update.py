@@ -17,6 +17,7 @@ from .utils import MAX_H16, _as_f32, splitarray
 
 MAX_M = 16
 MAX_MH = 16384         # the update over 16-bit codes: A = (m h)^2 f64 within 2 GiB
+MAX_CHAIN_H2 = 16384   # the chain update over 16-bit codes: one (2 h)^2 f64 block within 2 GiB
 METHODS = ("fast", "fastbin", "lsmr", "lsqr", "naive")      # src/codebook_update.jl:242
 
 
@@ -128,9 +129,17 @@ def get_cbdims_chain(d, m):
     return [sub[0]] + [range(sub[i - 1][0], sub[i][-1] + 1) for i in range(1, m - 1)] + [sub[-1]]
 
 
-def _check_chain_update(n, d, codes_shape, m, h, rho):
-    """Every argument check of the chain update runs here, before the library (and the device) is touched."""
-    rho = _check_update(n, d, codes_shape, m, h, rho)
+def _check_chain_update(n, d, codes_shape, m, h, rho, wide=False):
+    """Every argument check of the chain update runs here, before the library (and the device) is touched.  wide: the update
+    over 16-bit codes (2 <= h <= MAX_H16 and 2 h <= MAX_CHAIN_H2; no m * h limit, no (m h)^2 matrix is built)."""
+    if wide:
+        if not 2 <= int(h) <= MAX_H16:
+            raise ValueError("the chain update covers 2 <= h <= %d codewords; got h=%d" % (MAX_H16, h))
+        if 2 * int(h) > MAX_CHAIN_H2:
+            raise ValueError("the chain update solves 2 h <= %d unknowns per block; got h=%d" % (MAX_CHAIN_H2, h))
+        rho = _check_update(n, d, codes_shape, m, 2, rho)      # every check but h's
+    else:
+        rho = _check_update(n, d, codes_shape, m, h, rho)
     if m < 2:
         raise ValueError("the chain update needs m >= 2 codebooks; got m=%d" % m)
     if d < m - 1:
@@ -153,19 +162,42 @@ def update_codebooks_chain_u8(X, codes, h, rho=1e-4):
     return C
 
 
-def update_codebooks_chain_bin(X, B, h, V=False, rho=1e-4):
+def update_codebooks_chain_bin_u16(X, codes, h, rho=1e-4):
+    """update_codebooks_chain_u8 over zero-based 16-bit codes for any 2 <= h <= 8192 (rq_update_codebooks_chain_wide, the int16
+    kernels at every h).  At h <= 256 the codebooks equal update_codebooks_chain_u8's bit for bit."""
+    X = _as_f32(X, "X")
+    codes = np.asarray(codes)
+    n, d = X.shape
+    m = codes.shape[1] if codes.ndim == 2 else -1
+    rho = _check_chain_update(n, d, codes.shape, m, h, rho, wide=True)
+    if codes.size and (codes.min() < 0 or codes.max() > h - 1):
+        raise ValueError("codes must be in 0..%d" % (h - 1))
+    codes = np.ascontiguousarray(codes, dtype=np.int16)
+    C = np.empty((m, int(h), d), dtype=np.float32)
+    _lib.check(_lib.lib().rq_update_codebooks_chain_wide(C.ctypes.data, X.ctypes.data, codes.ctypes.data, n, d, m, int(h), rho, 0))
+    return C
+
+
+def update_codebooks_chain_bin(X, B, h, V=False, rho=1e-4, *, wide=False):
     """update_codebooks_chain_bin(X, B, h, V=false, rho=1e-4) -> C, elapsed       (src/codebook_update.jl:367-412)
 
-    X (n, d) float32, B (n, m) Int16 one-based.  Returns an m-long list of (h, d) float32 codebooks and the seconds spent."""
+    X (n, d) float32, B (n, m) Int16 one-based.  Returns an m-long list of (h, d) float32 codebooks and the seconds spent.
+
+    wide (keyword only, not in the reference): False keeps the byte contract, 2 <= h <= 256, and raises ValueError past it before
+    the library is touched -- callers and tests rely on that.  wide=True accepts 2 <= h <= 8192 and runs the update over 16-bit
+    codes at every h (update_codebooks_chain_bin_u16); the codebooks are the same wherever both run."""
     start = time.perf_counter()
     X = _as_f32(X, "X")
     B = np.asarray(B)
     n, d = X.shape
     m = B.shape[1] if B.ndim == 2 else -1
-    _check_chain_update(n, d, B.shape, m, h, rho)
+    _check_chain_update(n, d, B.shape, m, h, rho, wide=wide)
     if B.size and (B.min() < 1 or B.max() > h):
         raise ValueError("codes must be in 1..%d" % h)
-    C = update_codebooks_chain_u8(X, (B - 1).astype(np.uint8), h, rho)
+    if wide:
+        C = update_codebooks_chain_bin_u16(X, B.astype(np.int16) - np.int16(1), h, rho)
+    else:
+        C = update_codebooks_chain_u8(X, (B - 1).astype(np.uint8), h, rho)
     if V:
         print("Doing chain bin codebook update... done.")
     return list(C), time.perf_counter() - start

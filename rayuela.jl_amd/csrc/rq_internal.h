@@ -500,6 +500,10 @@ int icm_unary_launch(float *U, const float *X, const float *C, const float *sa, 
 int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h,
                          double rho, hipStream_t stream);
 int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t stream);
+// b [mh][d] f64 and *segs <- the segment bounds [m][h + 1] (device, in WS_LSQ_S) over zero-based int16 codes, 2 <= h <= RQ_MAX_H16:
+// the normal equations without their matrix, for the chain update past 256 codewords (rq_chain.hip)
+RQ_LOCAL int lsq_b_segs_wide_launch(double *b, const uint32_t **segs, const float *X, const int16_t *codes, int64_t n, int d, int m,
+                                    int h, double rho, hipStream_t stream);
 // C [m][h][d] f32 <- the fastbin update of (X, codes); *out <- the f64 mean of cost [n] (rq_train_lsq's obj); device pointers
 int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
                       hipStream_t stream);

@@ -570,6 +570,14 @@ int lsq_normal_eq_launch(double *A, double *b, const float *X, const uint8_t *co
 
 int lsq_spd_solve_launch(double *A, double *Y, int mh, int d, hipStream_t s) { return spd_solve_dev(A, Y, mh, d, s); }
 
+// b [mh][d] and the segment bounds [m][h + 1] (in WS_LSQ_S) alone, over zero-based int16 codes at any h <= RQ_MAX_H16: what the
+// chain update past 256 codewords needs of the normal equations (no mh x mh matrix); no phase clock.
+int lsq_b_segs_wide_launch(double *b, const uint32_t **segs, const float *X, const int16_t *codes, int64_t n, int d, int m, int h,
+                           double rho, hipStream_t s) {
+  PhaseClock clk(s, g_lsq_ms, false);
+  return normal_eq_dev<int16_t>(nullptr, b, X, codes, n, d, m, h, rho, s, clk, segs);
+}
+
 // The fastbin update and the obj mean for the SR training loop (rq_sr.hip), which keeps a phase clock of its own.
 int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
                       hipStream_t s) {

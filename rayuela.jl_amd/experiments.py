@@ -253,7 +253,8 @@ def experiment_ervq_query_base(Xt, *args, V=False, seed=0, norms="host"):
 
 def _sr_init(Xt, m, h, niter_init, chain, V, seed):
     """The initialisation of the LSQ++ drivers: train_opq "natural" (src/SR.jl:365, :391), then train_chainq (:397) where
-    the reference runs it.  Returns C, B, R, opq_error."""
+    the reference runs it.  Returns C, B, R, opq_error.  h > 256: train_opq and train_chainq both run over 16-bit codes, so the
+    start codes exist at any h <= 8192 (train_sr itself stays at h <= 256)."""
     from .ChainQ import train_chainq
     C, B, R, opq_error = train_opq(Xt, m, h, niter_init, "natural", V, seed=seed)
     if chain:
@@ -355,7 +356,7 @@ def experiment_lsq_cuda(Xt, *args, V=False, seed=0, niter_init=25):
     return C, B, R, train_error, B_base, recall
 
 
-def experiment_lsq_cuda_query_base(Xt, *args, V=False, seed=0):
+def experiment_lsq_cuda_query_base(Xt, *args, V=False, seed=0, **named):
     """experiment_lsq_cuda_query_base(Xt, B, C, R, Xq, gt, m, h, niter=25, ilsiter=8, icmiter=4, randord=true, npert=4,
                                    knn=1000, nsplits_train=1, V=false)                             (src/LSQ_GPU.jl:370-403)
     experiment_lsq_cuda_query_base(Xt, Xq, gt, m, h, niter=25, ilsiter=8, icmiter=4, randord=true, npert=4, init="natural",
@@ -365,7 +366,8 @@ def experiment_lsq_cuda_query_base(Xt, *args, V=False, seed=0):
     eval_recall.  The first method returns (C, B, R, train_error, recall).  The second starts from train_opq(init) then
     train_chainq and returns ((C, B, R, train_error, recall), opq_error).  Deviation: the reference's second method hands
     `niter, knn, nsplits_train, V` positionally to the first (:467), where they land in the slots niter, ilsiter, icmiter,
-    randord; here every argument is passed by meaning (ilsiter, icmiter, randord, npert included)."""
+    randord; here every argument is passed by meaning (ilsiter, icmiter, randord, npert included).  The optional arguments may
+    also be given by name.  h > 256: every step runs over 16-bit codes (train_opq, train_chainq, train_lsq_cuda, linscan_lsq_u16)."""
     from .ChainQ import train_chainq
     from .LSQ import train_lsq_cuda
     full = len(args) >= 7 and np.ndim(args[5]) == 0 and np.ndim(args[6]) == 0 and np.ndim(args[2]) > 0
@@ -382,9 +384,13 @@ def experiment_lsq_cuda_query_base(Xt, *args, V=False, seed=0):
         raise TypeError("experiment_lsq_cuda_query_base(Xt, [B, C, R,] Xq, gt, m, h, niter=25, ...)")
     if len(rest) > len(names):
         raise TypeError("experiment_lsq_cuda_query_base: too many arguments")
+    for key in named:
+        if key not in names or key in names[:len(rest)]:
+            raise TypeError("experiment_lsq_cuda_query_base: unexpected or repeated argument %r" % key)
     o = dict(niter=25, ilsiter=8, icmiter=4, randord=True, npert=4, init="natural", niter_opq=25, niter_chainq=25, knn=1000,
              nsplits_train=1, V=V)
     o.update(zip(names, rest))
+    o.update(named)
     V = bool(o["V"])
     opq_error = None
     if not full:
