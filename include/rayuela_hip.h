@@ -369,9 +369,29 @@ int rq_sr_schedule(double *scale, int schedule, int64_t iter, int64_t niter, dou
 int rq_train_sr(float *C, uint8_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h,
                 int niter, int ilsiter, int icmiter, int npert, int randord, int method, int schedule, double p,
                 int clean_update, uint64_t seed, int nsplits);
-/* milliseconds of this thread's last rq_train_sr by phase (hipEvents), summed over the call: {standard deviations,
- * perturbations, codebook updates, encodes, obj passes, other (the uploads, R'X, the rotation back)}; cap entries written */
+/* milliseconds of this thread's last rq_train_sr[_wide] by phase (hipEvents), summed over the call: {standard deviations,
+ * perturbations, codebook updates, encodes, obj passes, other (the uploads, R'X, the rotation back, the code_base shifts)}; cap
+ * entries written */
 int rq_last_sr_timing(double *ms, int cap);
+/* ---- LSQ++ with 2 <= h <= RQ_MAX_H16 codewords per codebook: rq_train_sr's contract word for word over
+ * codes [n][m] int16 in code_base .. code_base + h - 1 (code_base 0 or 1), host pointers.  The int16 kernels (the update of
+ * rq_update_codebooks_lsq_wide, the encoder of rq_encode_icm_wide) run at EVERY h; at h <= 256 C, codes and obj are rq_train_sr's
+ * bit for bit.  The shape rule is rq_train_lsq_wide's: it passes rq_icm_wide_plan AND m * h <= 16384, else RQ_EUNSUPPORTED.  Every
+ * other violation (m, h, d, n, niter, nsplits, method, schedule, p, code_base, a null pointer, a code out of range, RQ_SR_C with
+ * n < 2, the ILS counter overflow, an unknown bit in flags) is RQ_EINVAL.  Every check runs before any work and before a device
+ * is needed; no output byte is written on error.  The result depends on neither nsplits nor the chunking.
+ * With clean_update = 1 every step after the first opens with an update over the codes of the clean update that closed the step
+ * before.  flags = 0 does not repeat that work: RQ_SR_D's opening update has the same inputs, so C holds its result already and it
+ * is skipped; RQ_SR_C's has the same matrix B'B + rho I, so the Cholesky factor, the segment bounds and the sorted row lists are
+ * kept and only b = B'(noisy RX) and the two substitution sweeps run.  What is kept lives inside the one call.  RQ_SR_RECOMPUTE
+ * computes every update from scratch; both settings give the same bits. */
+#define RQ_SR_RECOMPUTE 1
+int rq_train_sr_wide(float *C, int16_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h,
+                     int niter, int ilsiter, int icmiter, int npert, int randord, int method, int schedule, double p,
+                     int clean_update, uint64_t seed, int nsplits, int code_base, int flags);
+/* the codebook updates of this thread's last rq_train_sr[_wide]: out[0 .. min(cap, 3) - 1] = {computed in full, computed from the
+ * kept Cholesky factor and row sort, skipped outright}; rq_train_sr computes every update in full */
+int rq_last_sr_stats(int64_t *out, int cap);
 
 /* ---- Chain quantization (src/ChainQ.jl).  Contract in DESIGN.md section 2 ("Chain quantization").
  * Layouts as for LSQ: X [n][d], C [m][h][d] (m full-dimensional codebooks, one codeword per row; a trained chain quantizer

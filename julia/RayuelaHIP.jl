@@ -1057,8 +1057,29 @@ function SR_D_perturb(C::Vector{Matrix{Float32}}, iter::Integer, niter::Integer,
   return C
 end
 
+# Past 256 codewords per codebook the loop runs over 16-bit codes (rq_train_sr_wide, DESIGN.md section 4.27): B goes in and comes
+# back one-based (code_base = 1); flags = 0 leaves out the codebook updates that would repeat work (the same bits either way).
+function _train_sr_wide(X::Matrix{Float32}, m, h, R::Matrix{Float32}, B::Matrix{Int16}, niter, ilsiter, icmiter, randord,
+                        npert, method, schedule, p, clean_update, seed, nsplits)
+  d, n  = size(X)
+  codes = copy(B)
+  Cc    = Matrix{Float32}(undef, d, m * h)
+  obj   = zeros(Float64, niter + 1)
+  code_base = 1
+  flags = 0
+  _check(ccall((:rq_train_sr_wide, librayuela_hip), Cint,
+    (Ptr{Cfloat}, Ptr{Int16}, Ptr{Cdouble}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Cint, Cint, Cint,
+     Cint, Cint, Cint, Cdouble, Cint, UInt64, Cint, Cint, Cint),
+    Cc, codes, obj, X, R, Int64(n), Cint(d), Cint(m), Cint(h), Cint(niter), Cint(ilsiter), Cint(icmiter), Cint(npert),
+    Cint(randord ? 1 : 0), Cint(_sr_kind(method)), Cint(schedule), Float64(p), Cint(clean_update ? 1 : 0), UInt64(seed),
+    Cint(nsplits), Cint(code_base), Cint(flags)))
+  return _split_codebooks(Cc, m, h), codes, convert(Vector{Float32}, obj)
+end
+
 function _train_sr(X::Matrix{Float32}, m, h, R::Matrix{Float32}, B::Matrix{Int16}, niter, ilsiter, icmiter, randord,
                    npert, method, schedule, p, clean_update, seed, nsplits)
+  h > 256 && return _train_sr_wide(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, method, schedule, p, clean_update,
+                                   seed, nsplits)
   d, n  = size(X)
   codes = convert(Matrix{UInt8}, B .- Int16(1))
   Cc    = Matrix{Float32}(undef, d, m * h)

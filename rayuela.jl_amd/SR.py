@@ -1,7 +1,8 @@
 """Host mirror of LSQ++, the stochastic relaxations of LSQ: apply_schedule, SR_D_perturb, SR_C_perturb
 (src/SR_perturbations.jl:4-73), train_sr (src/SR.jl:4-84) and train_sr_cuda (:88-176).
 
-The training loop is device-resident (rq_train_sr); the contract is DESIGN.md section 2 ("SR noise").  Layouts are LSQ's:
+The training loop is device-resident (rq_train_sr; rq_train_sr_wide over 16-bit codes past 256 codewords per codebook, DESIGN.md
+section 4.27); the contract is DESIGN.md section 2 ("SR noise").  Layouts are LSQ's:
 X (n, d) float32, codebooks an m-long list of (h, d) arrays, codes (n, m) Int16 one-based.  The reference draws its noise
 from Julia's global randn; here it is a counter-based standard normal variate keyed by (seed, method, perturbation call,
 global element index), so results depend on neither nsplits, the chunking nor the run."""
@@ -11,10 +12,11 @@ import math
 import numpy as np
 
 from . import _lib
-from .LSQ import _check, _stack
+from .LSQ import _check, _check_wide_train, _stack
 from .utils import _as_f32
 
 METHODS = ("SR_C", "SR_D")          # src/SR.jl:27; the C ABI's RQ_SR_C = 0, RQ_SR_D = 1
+SR_RECOMPUTE = 1                    # RQ_SR_RECOMPUTE: rq_train_sr_wide computes every codebook update from scratch
 _U64 = (1 << 64) - 1
 
 
@@ -145,11 +147,17 @@ def SR_D_perturb(C, iter, niter, schedule=1, p=0.5, seed=0, call=None):
     return out
 
 
-def _check_sr(X, B, m, h, R, niter, ilsiter, icmiter, npert, method, schedule, p, nsplits, one_based):
-    """Every argument check of the training loop runs here, before the library (and the device) is touched."""
+def _check_sr(X, B, m, h, R, niter, ilsiter, icmiter, npert, method, schedule, p, nsplits, one_based, wide=False):
+    """Every argument check of the training loop runs here, before the library (and the device) is touched.  wide: the loop
+    over 16-bit codes (LSQ._check_wide_train's shape rule) instead of the byte one (h <= 256)."""
     kind = _method(method)
+    if X.ndim != 2:
+        raise ValueError("X must be (n, d); got %s" % (X.shape,))
     n, d = X.shape
-    _check(X, np.empty((m, h, d), np.float32), B, ilsiter, icmiter, npert, nsplits, 0, one_based=one_based)
+    if wide:
+        _check_wide_train(X, B, m, h, ilsiter, icmiter, npert, nsplits, one_based=one_based)
+    else:
+        _check(X, np.empty((m, h, d), np.float32), B, ilsiter, icmiter, npert, nsplits, 0, one_based=one_based)
     if int(niter) < 1:
         raise ValueError("niter must be >= 1 (schedule 1 divides by it); got %d" % niter)
     for it in range(int(niter) + 1):
@@ -182,17 +190,44 @@ def train_sr_u8(X, codes0, m, h, R, niter, ilsiter, icmiter, randord, npert, met
     return C, codes, obj
 
 
+def train_sr_u16(X, codes0, m, h, R, niter, ilsiter, icmiter, randord, npert, method, schedule=1, p=0.5,
+                 clean_update=True, seed=0, nsplits=1, recompute=False):
+    """train_sr_u8 over zero-based int16 codes for any 2 <= h <= 32767 with m * h <= 16384 whose encoder tables fit
+    (LSQ.wide_fits): rq_train_sr_wide, the int16 kernels at every h.  At h <= 256 C, codes and obj equal
+    train_sr_u8's bit for bit.  With the clean update a step opens with an update over the codes the previous step closed with;
+    that repeated work is not done again unless recompute is set.  Both settings give the same bits (last_sr_stats counts)."""
+    X = np.ascontiguousarray(_as_f32(X, "X"))
+    B = np.asarray(codes0)
+    kind, R = _check_sr(X, B, m, h, R, niter, ilsiter, icmiter, npert, method, schedule, p, nsplits, one_based=False,
+                        wide=True)
+    n, d = X.shape
+    codes = np.array(B, dtype=np.int16, order="C")
+    C = np.empty((m, h, d), dtype=np.float32)
+    obj = np.zeros(int(niter) + 1, dtype=np.float64)
+    _lib.check(_lib.lib().rq_train_sr_wide(C.ctypes.data, codes.ctypes.data, obj.ctypes.data, X.ctypes.data,
+                                           None if R is None else R.ctypes.data, n, d, m, h, int(niter), int(ilsiter),
+                                           int(icmiter), int(npert), 1 if randord else 0, kind, int(schedule), float(p),
+                                           1 if clean_update else 0, int(seed) & _U64, int(nsplits), 0,
+                                           SR_RECOMPUTE if recompute else 0))
+    return C, codes, obj
+
+
 def _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, method, schedule, p, clean_update, seed, nsplits, V):
     X = _as_f32(X, "X")
     B = np.asarray(B)
     if B.dtype != np.int16:
         raise TypeError("B must be an Int16 array of one-based codes")
-    _check_sr(X, B, m, h, R, niter, ilsiter, icmiter, npert, method, schedule, p, nsplits, one_based=True)
+    wide = int(h) > 256
+    _check_sr(X, B, m, h, R, niter, ilsiter, icmiter, npert, method, schedule, p, nsplits, one_based=True, wide=wide)
     if V:
         print("Doing local search with %d codebooks, %d perturbations, %d icm iterations and random order = %s"
               % (m, npert, icmiter, bool(randord)))
-    C, codes, obj = train_sr_u8(X, (B - 1).astype(np.uint8), m, h, R, niter, ilsiter, icmiter, randord, npert, method,
-                                schedule, p, clean_update, seed=seed, nsplits=nsplits)
+    if wide:      # past 256 codewords: the loop over 16-bit codes (rq_train_sr_wide); h <= 256 stays on the byte loop
+        C, codes, obj = train_sr_u16(X, B - 1, m, h, R, niter, ilsiter, icmiter, randord, npert, method, schedule, p,
+                                     clean_update, seed=seed, nsplits=nsplits)
+    else:
+        C, codes, obj = train_sr_u8(X, (B - 1).astype(np.uint8), m, h, R, niter, ilsiter, icmiter, randord, npert, method,
+                                    schedule, p, clean_update, seed=seed, nsplits=nsplits)
     if V:
         for it, o in enumerate(obj, 1):
             print("%3d %e " % (it, o))
@@ -206,7 +241,9 @@ def train_sr(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, method, 
     the schedule is expected (:35, :66) and cannot run; its evident intent, schedule 1 with power p, is what runs here.
     No codebook update follows the encode of an iteration.  The C argument is ignored (the reference overwrites it).
     Returns C (m-long list of (h, d)), B (Int16 one-based, also written into the B passed in, as encoding_icm does)
-    and objarray (niter + 1,) float32.  cpp=True requires h = 256; both settings run the same device loop."""
+    and objarray (niter + 1,) float32.  cpp=True requires h = 256; both settings run the same device loop.  cpp=False takes
+    any 2 <= h <= 32767 with m * h <= 16384 whose encoder tables fit (LSQ.wide_fits): past 256 codewords the loop over 16-bit
+    codes runs (rq_train_sr_wide)."""
     if not (isinstance(B, np.ndarray) and B.dtype == np.int16):
         raise TypeError("B must be an Int16 numpy array (it is updated in place)")
     if cpp and h != 256:
@@ -221,7 +258,8 @@ def train_sr_cuda(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, met
     """train_sr_cuda(X, m, h, R, B, C, niter, ilsiter, icmiter, randord, npert, method, schedule, p=0.5, nsplits=1,
                      V=false) -> C, B, objarray                                                (src/SR.jl:88-176)
     As train_sr with the schedule (1, 2 or 3) chosen by the caller and a clean codebook update after every iteration's
-    encode (:166).  B is left untouched (encode_icm_cuda returns new codes); the result does not depend on nsplits."""
+    encode (:166).  B is left untouched (encode_icm_cuda returns new codes); the result does not depend on nsplits.  Past 256
+    codewords the loop over 16-bit codes runs, as in train_sr(cpp=False)."""
     return _train(X, m, h, R, B, niter, ilsiter, icmiter, randord, npert, method, schedule, p, True, seed, nsplits, V)
 
 
@@ -234,3 +272,14 @@ def last_sr_timing():
     out = (ctypes.c_double * 6)()
     _lib.check(_lib.lib().rq_last_sr_timing(ctypes.cast(out, ctypes.c_void_p), 6))
     return dict(zip(SR_PHASES, [float(v) for v in out]))
+
+
+SR_UPDATES = ["full", "reused", "skipped"]
+
+
+def last_sr_stats():
+    """The codebook updates of this thread's last training call (rq_last_sr_stats): computed in full, computed from the kept
+    Cholesky factor and row sort, skipped outright.  The byte loop computes every update in full."""
+    out = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.lib().rq_last_sr_stats(ctypes.cast(out, ctypes.c_void_p), 3))
+    return dict(zip(SR_UPDATES, [int(v) for v in out]))

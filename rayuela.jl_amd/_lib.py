@@ -99,6 +99,9 @@ SIGNATURES = {
     "rq_train_sr": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                            C.c_double, _i32, _u64, _i32]),
     "rq_last_sr_timing": (_i32, [_vp, _i32]),
+    "rq_train_sr_wide": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                C.c_double, _i32, _u64, _i32, _i32, _i32]),
+    "rq_last_sr_stats": (_i32, [_vp, _i32]),
     "rq_quantize_chainq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32]),
     "rq_dev_quantize_chainq": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "rq_chain_dims": (_i32, [_i32, _i32, _vp, _vp]),

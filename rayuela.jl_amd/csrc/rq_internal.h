@@ -508,6 +508,20 @@ RQ_LOCAL int lsq_b_segs_wide_launch(double *b, const uint32_t **segs, const floa
 int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n, int d, int m, int h, double rho,
                       hipStream_t stream);
 int lsq_mean_launch(double *out, const float *cost, int64_t n, hipStream_t stream);
+// What a full update over int16 codes leaves behind, for a second update over the SAME codes inside one call (rq_train_sr_wide;
+// DESIGN.md section 4.27): the Cholesky factor in WS_LSQ_A, the segment bounds and sorted row lists in WS_LSQ_S.  It names the two
+// buffers and their sizes; lsq_update_wide_launch uses it only while both are still those.
+struct LsqKept {
+  const void *a = nullptr, *s = nullptr;
+  size_t a_bytes = 0, s_bytes = 0;
+};
+// lsq_update_launch over zero-based int16 codes, 2 <= h <= RQ_MAX_H16.  again: the codes are those of the update that filled
+// *kept, so b alone is summed anew and the kept factor solves it (*reused <- true); else, or when *kept no longer holds, the full
+// update runs and refills *kept (*reused <- false).  Both give the same bits.
+RQ_LOCAL int lsq_update_wide_launch(float *C, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, double rho,
+                                    hipStream_t stream, LsqKept *kept, bool again, bool *reused);
+// the shape rule of rq_train_lsq_wide / rq_train_sr_wide: rq_icm_wide_plan passes and m * h <= 16384, else its status
+RQ_LOCAL int lsq_train_wide_shape(const char *who, int64_t n, int d, int m, int h, int nsplits);
 // the rotation of a training call (rq_train_lsq, rq_train_sr): dR <- R | R' ([d][d] each; R on the host), dRX [n][d] <- R'X
 RQ_LOCAL int upload_rotation(DevMem &dR, DevMem &dRX, const float *R, const float *X, int64_t n, int d, int num_cu, hipStream_t stream);
 }  // namespace rq

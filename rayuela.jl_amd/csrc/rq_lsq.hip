@@ -428,22 +428,37 @@ LsqScratch lsq_scratch(int64_t n, int m, int h, bool with_A) {
   return L;
 }
 
-// A [mh][mh], b [mh][d] f64 (device pointers; arguments checked, codes in range).  Code: uint8_t (h <= 256) or int16_t
-// (zero-based, h <= RQ_MAX_H16; at h <= 256 it queues what the byte instantiation queues).  A null (int16 entries only): b and
-// the segments alone.  *segs_out (may be null) <- the segment bounds [m][h + 1] in WS_LSQ_S.
+// Where the parts of WS_LSQ_S lie for one shape: a function of (n, m, h, with_A) and the buffer's address alone, so a later update
+// over the same codes finds the segment bounds and the sorted lists of an earlier one (update_again_dev)
+struct LsqLists {
+  uint32_t *P, *th, *segs, *cnt, *list0;
+  const uint32_t *sorted;   // the final lists [m][n]: list0, or the second pass's past 256 codewords
+};
+
+LsqLists lsq_lists(void *ws, const LsqScratch &L, int64_t n, int m, int h) {
+  LsqLists Q;
+  Q.P = (uint32_t *)ws;
+  Q.th = Q.P + L.pair_bytes / 4;
+  Q.segs = Q.th + L.th_bytes / 4;
+  Q.cnt = Q.segs + L.seg_bytes / 4;
+  Q.list0 = Q.cnt + L.cnt_bytes / 4;
+  Q.sorted = h > 256 ? Q.list0 + (size_t)m * n : Q.list0;
+  return Q;
+}
+
+// The part of the normal equations that the codes alone decide, up to the sort: the pair counts (A non-null), the segment bounds
+// and the sorted row lists, left in WS_LSQ_S.  Marks PH_COUNT and PH_SORT.
 template <class Code>
-int normal_eq_dev(double *A, double *b, const float *X, const Code *codes, int64_t n, int d, int m, int h, double rho,
-                  hipStream_t s, PhaseClock &clk, const uint32_t **segs_out = nullptr) {
-  const int mh = m * h;
-  const LsqScratch L = lsq_scratch(n, m, h, A != nullptr);
+int normal_eq_codes_dev(LsqLists *out, bool with_A, const Code *codes, int64_t n, int m, int h, hipStream_t s, PhaseClock &clk) {
+  const LsqScratch L = lsq_scratch(n, m, h, with_A);
   const int ntiles = L.ntiles;
   void *ws = nullptr;
   RQ_TRY(workspace(WS_LSQ_S, L.total(), &ws, s));
-  uint32_t *P = (uint32_t *)ws, *th = P + L.pair_bytes / 4, *segs = th + L.th_bytes / 4, *cnt = segs + L.seg_bytes / 4;
-  uint32_t *sorted = cnt + L.cnt_bytes / 4;
-  if (A) RQ_HIP(hipMemsetAsync(P, 0, L.pair_bytes, s));
+  const LsqLists Q = lsq_lists(ws, L, n, m, h);
+  uint32_t *P = Q.P, *th = Q.th, *segs = Q.segs, *cnt = Q.cnt, *sorted = Q.list0;
+  if (with_A) RQ_HIP(hipMemsetAsync(P, 0, L.pair_bytes, s));
   RQ_HIP(hipMemsetAsync(th, 0, L.th_bytes, s));
-  if (A && n > 0 && m > 1) {
+  if (with_A && n > 0 && m > 1) {
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(lsq_pair_kernel<Code>, dim3(grid), dim3(256), 0, s, P, codes, n, m, h);
     RQ_HIP(hipGetLastError());
@@ -488,24 +503,43 @@ int normal_eq_dev(double *A, double *b, const float *X, const Code *codes, int64
                 (const uint32_t *)list0, n, m, nd1, ntiles);
     }
     RQ_LAUNCH(lsq_segs_scan_kernel, dim3(m), dim3(256), 0, s, segs, (const uint32_t *)cnt, n, h);
-    sorted = list1;
   }
   clk.mark(PH_SORT);
-  const int bt = d <= 64 ? 64 : d <= 128 ? 128 : 256;
-  hipLaunchKernelGGL(lsq_bsum_kernel, dim3(mh), dim3(bt), 0, s, b, X, sorted, segs, n, d, h);
-  RQ_HIP(hipGetLastError());
-  clk.mark(PH_B);
-  if (A) {
-    hipLaunchKernelGGL(lsq_assemble_kernel, dim3((mh + 255) / 256, mh), dim3(256), 0, s, A, P, segs, m, h, rho);
-    RQ_HIP(hipGetLastError());
-  }
-  clk.mark(PH_ASSEMBLE);
-  if (segs_out) *segs_out = segs;
+  *out = Q;
   return RQ_OK;
 }
 
-// A <- its Cholesky factor (lower), Y [mh][d] <- A^-1 Y
-int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
+// b [mh][d] <- the segment sums of X over the sorted lists: the one part of the normal equations that reads X.  Marks PH_B.
+int normal_eq_b_dev(double *b, const float *X, const LsqLists &Q, int64_t n, int d, int m, int h, hipStream_t s, PhaseClock &clk) {
+  const int bt = d <= 64 ? 64 : d <= 128 ? 128 : 256;
+  hipLaunchKernelGGL(lsq_bsum_kernel, dim3(m * h), dim3(bt), 0, s, b, X, Q.sorted, (const uint32_t *)Q.segs, n, d, h);
+  RQ_HIP(hipGetLastError());
+  clk.mark(PH_B);
+  return RQ_OK;
+}
+
+// A [mh][mh], b [mh][d] f64 (device pointers; arguments checked, codes in range).  Code: uint8_t (h <= 256) or int16_t
+// (zero-based, h <= RQ_MAX_H16; at h <= 256 it queues what the byte instantiation queues).  A null (int16 entries only): b and
+// the segments alone.  *segs_out (may be null) <- the segment bounds [m][h + 1] in WS_LSQ_S.
+template <class Code>
+int normal_eq_dev(double *A, double *b, const float *X, const Code *codes, int64_t n, int d, int m, int h, double rho,
+                  hipStream_t s, PhaseClock &clk, const uint32_t **segs_out = nullptr) {
+  const int mh = m * h;
+  LsqLists Q;
+  RQ_TRY(normal_eq_codes_dev(&Q, A != nullptr, codes, n, m, h, s, clk));
+  RQ_TRY(normal_eq_b_dev(b, X, Q, n, d, m, h, s, clk));
+  if (A) {
+    hipLaunchKernelGGL(lsq_assemble_kernel, dim3((mh + 255) / 256, mh), dim3(256), 0, s, A, (const uint32_t *)Q.P,
+                       (const uint32_t *)Q.segs, m, h, rho);
+    RQ_HIP(hipGetLastError());
+  }
+  clk.mark(PH_ASSEMBLE);
+  if (segs_out) *segs_out = Q.segs;
+  return RQ_OK;
+}
+
+// A <- its Cholesky factor (lower)
+int spd_factor_dev(double *A, int mh, hipStream_t s) {
   for (int k = 0; k < mh; k += NB) {
     const int nb = std::min(NB, mh - k), rest = mh - k - nb;
     RQ_LAUNCH(lsq_chol_diag_kernel, dim3(1), dim3(256), 0, s, A, mh, k, nb);
@@ -517,10 +551,15 @@ int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
                 (const double *)pan, (int64_t)mh, (int64_t)1, (const double *)pan, (int64_t)mh, (int64_t)1, nb, 1);
     }
   }
+  return RQ_OK;
+}
+
+// Y [mh][d] <- (L L')^-1 Y with L the factor spd_factor_dev left in A: forward, then back substitution
+int spd_subst_dev(const double *A, double *Y, int mh, int d, hipStream_t s) {
   const unsigned cgrid = (unsigned)((d + 63) / 64), ntile = (unsigned)((d + GT - 1) / GT);
   for (int k = 0; k < mh; k += NB) {   // L y = b
     const int nb = std::min(NB, mh - k), rest = mh - k - nb;
-    RQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 1);
+    RQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, A, mh, d, k, nb, 1);
     if (rest > 0)
       RQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((rest + GT - 1) / GT)), dim3(256), 0, s,
                 Y + (size_t)(k + nb) * d, (int64_t)d, rest, d, (const double *)(A + (size_t)(k + nb) * mh + k),
@@ -528,13 +567,19 @@ int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
   }
   for (int k = ((mh - 1) / NB) * NB; k >= 0; k -= NB) {   // L' x = y
     const int nb = std::min(NB, mh - k);
-    RQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, (const double *)A, mh, d, k, nb, 0);
+    RQ_LAUNCH(lsq_trsv_block_kernel, dim3(cgrid), dim3(64), 0, s, Y, A, mh, d, k, nb, 0);
     if (k > 0)
       RQ_LAUNCH(lsq_gemm_sub_kernel, dim3(ntile, (unsigned)((k + GT - 1) / GT)), dim3(256), 0, s, Y, (int64_t)d, k, d,
                 (const double *)(A + (size_t)k * mh), (int64_t)1, (int64_t)mh, (const double *)(Y + (size_t)k * d),
                 (int64_t)1, (int64_t)d, nb, 0);
   }
   return RQ_OK;
+}
+
+// A <- its Cholesky factor (lower), Y [mh][d] <- A^-1 Y
+int spd_solve_dev(double *A, double *Y, int mh, int d, hipStream_t s) {
+  RQ_TRY(spd_factor_dev(A, mh, s));
+  return spd_subst_dev(A, Y, mh, d, s);
 }
 
 // C [m][h][d] f32 <- the fastbin update of (X, codes) (device pointers; arguments checked, codes in range)
@@ -552,6 +597,48 @@ int update_dev(float *C, const float *X, const Code *codes, int64_t n, int d, in
   RQ_LAUNCH(lsq_to_f32_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, s, C,
             (const double *)b, cnt);
   clk.mark(PH_SOLVE);
+  return RQ_OK;
+}
+
+// update_dev over int16 codes that also notes where it left the Cholesky factor (WS_LSQ_A) and the segment bounds and sorted
+// lists (WS_LSQ_S): what a second update over the SAME codes can start from (update_again_dev)
+int update_keep_dev(float *C, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, double rho, hipStream_t s,
+                    PhaseClock &clk, LsqKept *kept) {
+  *kept = LsqKept();
+  RQ_TRY(update_dev(C, X, codes, n, d, m, h, rho, s, clk));
+  const size_t mh = (size_t)m * h;
+  void *wa = nullptr, *ws = nullptr;
+  kept->a_bytes = mh * mh * 8;
+  kept->s_bytes = lsq_scratch(n, m, h, true).total();
+  RQ_TRY(workspace(WS_LSQ_A, kept->a_bytes, &wa, s));      // the buffers update_dev used: they hold these sizes already
+  RQ_TRY(workspace(WS_LSQ_S, kept->s_bytes, &ws, s));
+  kept->a = wa;
+  kept->s = ws;
+  return RQ_OK;
+}
+
+// C <- the fastbin update of (X, codes) for the codes of the update that filled `kept`: A = B'B + rho I is that update's, so its
+// factor, segment bounds and sorted lists stand; b alone is summed anew, then the two substitution sweeps.  *done = false (and
+// nothing queued) when either buffer is no longer the one `kept` names, at its size.
+int update_again_dev(bool *done, float *C, const float *X, int64_t n, int d, int m, int h, hipStream_t s, PhaseClock &clk,
+                     const LsqKept &kept) {
+  *done = false;
+  const int mh = m * h;
+  const LsqScratch L = lsq_scratch(n, m, h, true);
+  if (!kept.a || !kept.s || kept.a_bytes != (size_t)mh * mh * 8 || kept.s_bytes != L.total()) return RQ_OK;
+  void *wa = nullptr, *wb = nullptr, *ws = nullptr;
+  RQ_TRY(workspace(WS_LSQ_A, kept.a_bytes, &wa, s));
+  RQ_TRY(workspace(WS_LSQ_B, (size_t)mh * d * 8, &wb, s));
+  RQ_TRY(workspace(WS_LSQ_S, kept.s_bytes, &ws, s));
+  if (wa != kept.a || ws != kept.s) return RQ_OK;
+  double *b = (double *)wb;
+  RQ_TRY(normal_eq_b_dev(b, X, lsq_lists(ws, L, n, m, h), n, d, m, h, s, clk));
+  RQ_TRY(spd_subst_dev((const double *)wa, b, mh, d, s));
+  const int64_t cnt = (int64_t)mh * d;
+  RQ_LAUNCH(lsq_to_f32_kernel, dim3((unsigned)std::min<int64_t>((cnt + 255) / 256, 8192)), dim3(256), 0, s, C,
+            (const double *)b, cnt);
+  clk.mark(PH_SOLVE);
+  *done = true;
   return RQ_OK;
 }
 
@@ -583,6 +670,29 @@ int lsq_update_launch(float *C, const float *X, const uint8_t *codes, int64_t n,
                       hipStream_t s) {
   PhaseClock clk(s, g_lsq_ms, false);
   return update_dev(C, X, codes, n, d, m, h, rho, s, clk);
+}
+
+// The same over zero-based int16 codes at 2 <= h <= RQ_MAX_H16 (rq_train_sr_wide).  again == false: the full update, and *kept
+// <- what it left behind.  again == true: the codes are those of the update that filled *kept, so only b is summed anew
+// (update_again_dev); when *kept no longer holds, the full update runs instead.  *reused <- which of the two ran.
+int lsq_update_wide_launch(float *C, const float *X, const int16_t *codes, int64_t n, int d, int m, int h, double rho,
+                           hipStream_t s, LsqKept *kept, bool again, bool *reused) {
+  PhaseClock clk(s, g_lsq_ms, false);
+  *reused = false;
+  if (again) RQ_TRY(update_again_dev(reused, C, X, n, d, m, h, s, clk, *kept));
+  if (*reused) return RQ_OK;
+  return update_keep_dev(C, X, codes, n, d, m, h, rho, s, clk, kept);
+}
+
+// The shape rule of the training loops over int16 codes (rq_train_lsq_wide, rq_train_sr_wide), no device touched: nsplits and the
+// encoder's tables within its scratch (rq_icm_wide_plan's rule), then m * h within LSQ_MAX_MH (RQ_EUNSUPPORTED)
+int lsq_train_wide_shape(const char *who, int64_t n, int d, int m, int h, int nsplits) {
+  int64_t none = 0;
+  RQ_TRY(rq_icm_wide_plan(n, d, m, h, nsplits, &none, 0));
+  if (m * h > LSQ_MAX_MH)
+    return fail(RQ_EUNSUPPORTED, "%s: m * h = %d * %d exceeds %d (A would take %zu bytes of f64)", who, m, h, LSQ_MAX_MH,
+                (size_t)m * h * m * h * 8);
+  return RQ_OK;
 }
 
 int upload_rotation(DevMem &dR, DevMem &dRX, const float *R, const float *X, int64_t n, int d, int num_cu, hipStream_t s) {
@@ -860,11 +970,7 @@ extern "C" int rq_train_lsq_wide(float *C, int16_t *codes, double *obj, const fl
   if (npert < 0 || npert > m) return fail(RQ_EINVAL, "%s: npert=%d outside 0..m=%d", who, npert, m);
   if ((int64_t)ilsiter * ((int64_t)niter + 1) > INT32_MAX)
     return fail(RQ_EINVAL, "%s: ilsiter * (niter + 1) overflows the ILS iteration counter", who);
-  int64_t none = 0;
-  RQ_TRY(rq_icm_wide_plan(n, d, m, h, nsplits, &none, 0));   // nsplits, and the encoder's tables within its scratch
-  if (m * h > LSQ_MAX_MH)
-    return fail(RQ_EUNSUPPORTED, "%s: m * h = %d * %d exceeds %d (A would take %zu bytes of f64)", who, m, h, LSQ_MAX_MH,
-                (size_t)m * h * m * h * 8);
+  RQ_TRY(lsq_train_wide_shape(who, n, d, m, h, nsplits));
   RQ_TRY(host_code_range(codes, n, m, h, code_base, who));
   return train_lsq_host<int16_t>(C, codes, obj, X, R, n, d, m, h, niter, ilsiter, icmiter, npert, randord, seed, nsplits,
                                  code_base);

@@ -239,6 +239,163 @@ int sr_perturb_check(const void *Y, const void *X, const void *sigma, double sca
 enum { SR_STD, SR_PERTURB, SR_UPDATE, SR_ENCODE, SR_OBJ, SR_OTHER, SR_N };
 thread_local double g_sr_ms[SR_N] = {0};
 
+// Codebook updates of the calling thread's last training call (rq_last_sr_stats): computed in full, computed from the kept
+// Cholesky factor and row sort, skipped outright
+enum { SR_UPD_FULL, SR_UPD_REUSED, SR_UPD_SKIPPED, SR_UPD_N };
+thread_local int64_t g_sr_upd[SR_UPD_N] = {0};
+
+// the encoder of the loop by code type: rq_icm.hip's over bytes, rq_icm_h16.hip's over int16 codes
+int sr_encode_dev(uint8_t *B, float *cost, const float *X, const float *C, int64_t n, int d, int m, int h, int ilsiter, int icmiter,
+                  int npert, int randord, uint64_t seed, int64_t t0, int nsplits, hipStream_t s) {
+  return icm_encode_dev(B, B, cost, X, C, n, d, m, h, ilsiter, icmiter, npert, randord, seed, t0, nsplits, s, nullptr);
+}
+int sr_encode_dev(int16_t *B, float *cost, const float *X, const float *C, int64_t n, int d, int m, int h, int ilsiter, int icmiter,
+                  int npert, int randord, uint64_t seed, int64_t t0, int nsplits, hipStream_t s) {
+  return icm_encode_wide_dev(B, B, cost, X, C, n, d, m, h, ilsiter, icmiter, npert, randord, seed, t0, nsplits, s, nullptr);
+}
+
+// The codebook updates of one training call.  Over bytes every update is computed in full.  Over int16 codes (DESIGN.md section
+// 4.27) `clean` says that Cd holds update(RX, B) for the codes B as they are now and that `kept` is what that update left
+// behind: the trailing clean update sets it, every encode of a step clears it (the obj pass is a zero-iteration encode and
+// leaves the codes alone).  The state lives in this object, inside one call and under its DeviceLock.
+template <class Code>
+struct SrUpdates {
+  bool recompute;
+  bool clean = false;
+  LsqKept kept;
+  // C = update(X, B); same_x: X is the RX of the update that set `clean`
+  int run(float *C, const float *X, const Code *B, int64_t n, int d, int m, int h, bool same_x, hipStream_t s) {
+    if constexpr (std::is_same<Code, uint8_t>::value) {
+      g_sr_upd[SR_UPD_FULL] += 1;
+      return lsq_update_launch(C, X, B, n, d, m, h, 1e-4, s);
+    } else {
+      const bool again = clean && !recompute;
+      if (again && same_x) {   // the same inputs and a bitwise reproducible update: C holds the result already
+        g_sr_upd[SR_UPD_SKIPPED] += 1;
+        return RQ_OK;
+      }
+      bool reused = false;
+      RQ_TRY(lsq_update_wide_launch(C, X, B, n, d, m, h, 1e-4, s, &kept, again, &reused));
+      g_sr_upd[reused ? SR_UPD_REUSED : SR_UPD_FULL] += 1;
+      return RQ_OK;
+    }
+  }
+};
+
+// rq_train_sr / rq_train_sr_wide after their argument checks (src/SR.jl:88-176, :4-84).  codes [n][m] on the host, in code_base ..
+// code_base + h - 1 (bytes: code_base 0); the loop runs on zero-based codes.  scale[call]: the noise scale of perturbation call
+// `call` (call 0 is SR_C's iter 0 / SR_D's iter 1, call it is iter it).
+template <class Code>
+int train_sr_host(float *C, Code *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m, int h, int niter,
+                  int ilsiter, int icmiter, int npert, int randord, int method, const std::vector<double> &scale, int clean_update,
+                  uint64_t seed, int nsplits, int code_base, bool recompute) {
+  DeviceInfo di;
+  RQ_TRY(device_info(&di));
+  DeviceLock call_lock;
+  const int mh = m * h;
+  const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4, kb = (size_t)n * m * sizeof(Code);
+  DevMem dX, dRX, dR, dC, dC2, dnoisy, dcodes, dcost, dobj, dsig, dscr;
+  RQ_TRY(dX.alloc(xb));
+  RQ_TRY(dcodes.alloc(kb));
+  RQ_TRY(dC.alloc(cb));
+  RQ_TRY(dcost.alloc((size_t)n * 4));
+  RQ_TRY(dobj.alloc((size_t)(niter + 1) * 8));
+  RQ_TRY(dsig.alloc((size_t)d * 4));
+  RQ_TRY(dscr.alloc(sr_std_scratch_bytes(method == RQ_SR_C ? n : mh, d)));
+  if (method == RQ_SR_C) RQ_TRY(dnoisy.alloc(xb));
+  const hipStream_t s = nullptr;
+  for (int q = 0; q < SR_N; ++q) g_sr_ms[q] = 0;
+  for (int q = 0; q < SR_UPD_N; ++q) g_sr_upd[q] = 0;
+  PhaseClock clk(s, g_sr_ms);   // SR_OTHER: the uploads, R'X, the rotation back and the code_base shifts
+  if (n > 0) {
+    RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(dcodes.p, codes, kb, hipMemcpyHostToDevice));
+  }
+  const float *RX = (const float *)dX.p;
+  Code *B = (Code *)dcodes.p;
+  if constexpr (std::is_same<Code, int16_t>::value) {
+    if (code_base) RQ_TRY(add_base_codes_launch(B, n * m, -code_base, s));
+  }
+  float *Cd = (float *)dC.p, *cost = (float *)dcost.p, *sig = (float *)dsig.p, *noisy = (float *)dnoisy.p;
+  double *objd = (double *)dobj.p, *scr = (double *)dscr.p;
+  const float *Rtd = nullptr;
+  if (R) {   // RX = R'X   (src/SR.jl:115)
+    RQ_TRY(upload_rotation(dR, dRX, R, (const float *)dX.p, n, d, di.num_cu, s));
+    RQ_TRY(dC2.alloc(cb));
+    Rtd = dR.as<float>() + (size_t)d * d;
+    RX = (const float *)dRX.p;
+  }
+  clk.mark(SR_OTHER);
+  if (method == RQ_SR_C) {   // RX does not change: one standard deviation serves every call
+    RQ_TRY(sr_std_dev(sig, RX, n, d, 1.0, scr, s));
+    clk.mark(SR_STD);
+  }
+  SrUpdates<Code> upd{recompute};
+  // perturbation call `call`, then ILS iterations call * ilsiter .. of one `seed` stream   (src/SR.jl:118-134, :151-164)
+  auto step = [&](int call) -> int {
+    if (method == RQ_SR_C) {
+      RQ_TRY(sr_perturb_dev(noisy, RX, sig, scale[call], n, d, RQ_SR_C, seed, call, 0, s));
+      clk.mark(SR_PERTURB);
+      RQ_TRY(upd.run(Cd, noisy, B, n, d, m, h, false, s));
+      clk.mark(SR_UPDATE);
+    } else {
+      RQ_TRY(upd.run(Cd, RX, B, n, d, m, h, true, s));
+      clk.mark(SR_UPDATE);
+      RQ_TRY(sr_std_dev(sig, Cd, mh, d, (double)m, scr, s));   // std(cat(C..., dims=2), dims=2) ./ m
+      clk.mark(SR_STD);
+      RQ_TRY(sr_perturb_dev(Cd, Cd, sig, scale[call], mh, d, RQ_SR_D, seed, call, 0, s));
+      clk.mark(SR_PERTURB);
+    }
+    upd.clean = false;   // the encode moves the codes (and SR_D has perturbed Cd)
+    RQ_TRY(sr_encode_dev(B, cost, RX, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed, (int64_t)call * ilsiter, nsplits, s));
+    clk.mark(SR_ENCODE);
+    return RQ_OK;
+  };
+  // obj = qerror(RX, B, C) against the CURRENT C: a veccost pass (the zero-iteration encode) and its mean
+  auto objective = [&](int slot) -> int {
+    RQ_TRY(sr_encode_dev(B, cost, RX, Cd, n, d, m, h, 0, 0, 0, 0, seed, 0, nsplits, s));
+    RQ_TRY(lsq_mean_launch(objd + slot, cost, n, s));
+    clk.mark(SR_OBJ);
+    return RQ_OK;
+  };
+  RQ_TRY(step(0));
+  for (int it = 1; it <= niter; ++it) {
+    RQ_TRY(objective(it - 1));
+    RQ_TRY(step(it));
+    if (clean_update) {   // train_sr_cuda's trailing update (src/SR.jl:166); train_sr has none
+      RQ_TRY(upd.run(Cd, RX, B, n, d, m, h, true, s));
+      clk.mark(SR_UPDATE);
+      upd.clean = true;   // Cd = update(RX, B): what the next step opens with, over these codes
+    }
+  }
+  RQ_TRY(objective(niter));
+  if constexpr (std::is_same<Code, int16_t>::value) {
+    if (code_base) {
+      RQ_TRY(add_base_codes_launch(B, n * m, code_base, s));
+      clk.mark(SR_OTHER);
+    }
+  }
+  if (R) {   // C_i <- R C_i   (src/SR.jl:172)
+    RQ_HIP(hipMemcpyAsync(dC2.p, Cd, cb, hipMemcpyDeviceToDevice, s));
+    RQ_TRY(rotate_launch(Cd, Rtd, (const float *)dC2.p, d, mh, di.num_cu, s));
+    clk.mark(SR_OTHER);
+  }
+  clk.collect();
+  RQ_HIP(hipDeviceSynchronize());
+  RQ_HIP(hipMemcpy(C, Cd, cb, hipMemcpyDeviceToHost));
+  if (n > 0) RQ_HIP(hipMemcpy(codes, B, kb, hipMemcpyDeviceToHost));
+  RQ_HIP(hipMemcpy(obj, objd, (size_t)(niter + 1) * 8, hipMemcpyDeviceToHost));
+  return RQ_OK;
+}
+
+// the noise scale of every perturbation call: call 0 is SR_C's iter 0 / SR_D's iter 1, call it is iter it
+int sr_scales(std::vector<double> &scale, int niter, int method, int schedule, double p) {
+  scale.assign((size_t)niter + 1, 0.0);
+  for (int it = 0; it <= niter; ++it)
+    RQ_TRY(sr_schedule(&scale[it], schedule, it == 0 && method == RQ_SR_D ? 1 : it, niter, p));
+  return RQ_OK;
+}
+
 }  // namespace
 
 }  // namespace rq
@@ -304,95 +461,46 @@ extern "C" int rq_train_sr(float *C, uint8_t *codes, double *obj, const float *X
   if ((int64_t)ilsiter * ((int64_t)niter + 1) > INT32_MAX)
     return fail(RQ_EINVAL, "train_sr: ilsiter * (niter + 1) overflows the ILS iteration counter");
   RQ_TRY(icm_check_args(codes, codes, X, C, n, d, m, h, ilsiter, icmiter, npert, 0, nsplits));
-  // the noise scale of every perturbation call: call 0 is SR_C's iter 0 / SR_D's iter 1, call it is iter it
-  std::vector<double> scale((size_t)niter + 1);
-  for (int it = 0; it <= niter; ++it)
-    RQ_TRY(sr_schedule(&scale[it], schedule, it == 0 && method == RQ_SR_D ? 1 : it, niter, p));
+  std::vector<double> scale;
+  RQ_TRY(sr_scales(scale, niter, method, schedule, p));
   RQ_TRY(host_code_range(codes, n, m, h, "train_sr"));
-  DeviceInfo di;
-  RQ_TRY(device_info(&di));
-  DeviceLock call_lock;
-  const int mh = m * h;
-  const size_t xb = (size_t)n * d * 4, cb = (size_t)mh * d * 4;
-  DevMem dX, dRX, dR, dC, dC2, dnoisy, dcodes, dcost, dobj, dsig, dscr;
-  RQ_TRY(dX.alloc(xb));
-  RQ_TRY(dcodes.alloc((size_t)n * m));
-  RQ_TRY(dC.alloc(cb));
-  RQ_TRY(dcost.alloc((size_t)n * 4));
-  RQ_TRY(dobj.alloc((size_t)(niter + 1) * 8));
-  RQ_TRY(dsig.alloc((size_t)d * 4));
-  RQ_TRY(dscr.alloc(sr_std_scratch_bytes(method == RQ_SR_C ? n : mh, d)));
-  if (method == RQ_SR_C) RQ_TRY(dnoisy.alloc(xb));
-  const hipStream_t s = nullptr;
-  for (int q = 0; q < SR_N; ++q) g_sr_ms[q] = 0;
-  PhaseClock clk(s, g_sr_ms);   // SR_OTHER: the uploads, R'X and the rotation back
-  if (n > 0) {
-    RQ_HIP(hipMemcpy(dX.p, X, xb, hipMemcpyHostToDevice));
-    RQ_HIP(hipMemcpy(dcodes.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
-  }
-  const float *RX = (const float *)dX.p;
-  uint8_t *B = (uint8_t *)dcodes.p;
-  float *Cd = (float *)dC.p, *cost = (float *)dcost.p, *sig = (float *)dsig.p, *noisy = (float *)dnoisy.p;
-  double *objd = (double *)dobj.p, *scr = (double *)dscr.p;
-  const float *Rtd = nullptr;
-  if (R) {   // RX = R'X   (src/SR.jl:115)
-    RQ_TRY(upload_rotation(dR, dRX, R, (const float *)dX.p, n, d, di.num_cu, s));
-    RQ_TRY(dC2.alloc(cb));
-    Rtd = dR.as<float>() + (size_t)d * d;
-    RX = (const float *)dRX.p;
-  }
-  clk.mark(SR_OTHER);
-  if (method == RQ_SR_C) {   // RX does not change: one standard deviation serves every call
-    RQ_TRY(sr_std_dev(sig, RX, n, d, 1.0, scr, s));
-    clk.mark(SR_STD);
-  }
-  // perturbation call `call`, then ILS iterations call * ilsiter .. of one `seed` stream   (src/SR.jl:118-134, :151-164)
-  auto step = [&](int call) -> int {
-    if (method == RQ_SR_C) {
-      RQ_TRY(sr_perturb_dev(noisy, RX, sig, scale[call], n, d, RQ_SR_C, seed, call, 0, s));
-      clk.mark(SR_PERTURB);
-      RQ_TRY(lsq_update_launch(Cd, noisy, B, n, d, m, h, 1e-4, s));
-      clk.mark(SR_UPDATE);
-    } else {
-      RQ_TRY(lsq_update_launch(Cd, RX, B, n, d, m, h, 1e-4, s));
-      clk.mark(SR_UPDATE);
-      RQ_TRY(sr_std_dev(sig, Cd, mh, d, (double)m, scr, s));   // std(cat(C..., dims=2), dims=2) ./ m
-      clk.mark(SR_STD);
-      RQ_TRY(sr_perturb_dev(Cd, Cd, sig, scale[call], mh, d, RQ_SR_D, seed, call, 0, s));
-      clk.mark(SR_PERTURB);
-    }
-    RQ_TRY(icm_encode_dev(B, B, cost, RX, Cd, n, d, m, h, ilsiter, icmiter, npert, randord, seed,
-                          (int64_t)call * ilsiter, nsplits, s, nullptr));
-    clk.mark(SR_ENCODE);
-    return RQ_OK;
-  };
-  // obj = qerror(RX, B, C) against the CURRENT C: a veccost pass (the zero-iteration encode) and its mean
-  auto objective = [&](int slot) -> int {
-    RQ_TRY(icm_encode_dev(B, B, cost, RX, Cd, n, d, m, h, 0, 0, 0, 0, seed, 0, nsplits, s, nullptr));
-    RQ_TRY(lsq_mean_launch(objd + slot, cost, n, s));
-    clk.mark(SR_OBJ);
-    return RQ_OK;
-  };
-  RQ_TRY(step(0));
-  for (int it = 1; it <= niter; ++it) {
-    RQ_TRY(objective(it - 1));
-    RQ_TRY(step(it));
-    if (clean_update) {   // train_sr_cuda's trailing update (src/SR.jl:166); train_sr has none
-      RQ_TRY(lsq_update_launch(Cd, RX, B, n, d, m, h, 1e-4, s));
-      clk.mark(SR_UPDATE);
-    }
-  }
-  RQ_TRY(objective(niter));
-  if (R) {   // C_i <- R C_i   (src/SR.jl:172)
-    RQ_HIP(hipMemcpyAsync(dC2.p, Cd, cb, hipMemcpyDeviceToDevice, s));
-    RQ_TRY(rotate_launch(Cd, Rtd, (const float *)dC2.p, d, mh, di.num_cu, s));
-    clk.mark(SR_OTHER);
-  }
-  clk.collect();
-  RQ_HIP(hipDeviceSynchronize());
-  RQ_HIP(hipMemcpy(C, Cd, cb, hipMemcpyDeviceToHost));
-  if (n > 0) RQ_HIP(hipMemcpy(codes, B, (size_t)n * m, hipMemcpyDeviceToHost));
-  RQ_HIP(hipMemcpy(obj, objd, (size_t)(niter + 1) * 8, hipMemcpyDeviceToHost));
+  return train_sr_host<uint8_t>(C, codes, obj, X, R, n, d, m, h, niter, ilsiter, icmiter, npert, randord, method, scale, clean_update,
+                                seed, nsplits, 0, true);
+}
+
+// 2 <= h <= RQ_MAX_H16 over int16 codes: the int16 instantiation at EVERY h, host pointers
+extern "C" int rq_train_sr_wide(float *C, int16_t *codes, double *obj, const float *X, const float *R, int64_t n, int d, int m,
+                                int h, int niter, int ilsiter, int icmiter, int npert, int randord, int method, int schedule,
+                                double p, int clean_update, uint64_t seed, int nsplits, int code_base, int flags) {
+  const char *who = "train_sr_wide";
+  if (m < 1 || m > 16) return fail(RQ_EINVAL, "%s: m=%d outside 1..16", who, m);
+  if (h < 2 || h > RQ_MAX_H16) return fail(RQ_EINVAL, "%s: h=%d outside 2..%d", who, h, RQ_MAX_H16);
+  if (d < 1) return fail(RQ_EINVAL, "%s: d=%d < 1", who, d);
+  if (n < 0 || n > (int64_t)UINT32_MAX)
+    return fail(RQ_EINVAL, "%s: n=%lld outside 0..%u (the u32 counters)", who, (long long)n, UINT32_MAX);
+  if (!C || !codes || !obj) return fail(RQ_EINVAL, "%s: null output pointer", who);
+  if (n > 0 && !X) return fail(RQ_EINVAL, "%s: null pointer", who);
+  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
+  if (flags & ~RQ_SR_RECOMPUTE) return fail(RQ_EINVAL, "%s: flags=0x%x has an unknown bit (RQ_SR_RECOMPUTE = 1)", who, flags);
+  if (method != RQ_SR_C && method != RQ_SR_D) return fail(RQ_EINVAL, "%s: SR method %d unknown (0 = SR_C, 1 = SR_D)", who, method);
+  if (niter < 1) return fail(RQ_EINVAL, "%s: niter=%d < 1 (schedule 1 divides by it)", who, niter);
+  if (method == RQ_SR_C && n < 2)
+    return fail(RQ_EINVAL, "%s: SR_C needs n >= 2 rows for the standard deviation; got %lld", who, (long long)n);
+  if (ilsiter < 0 || icmiter < 0) return fail(RQ_EINVAL, "%s: negative count (ilsiter=%d icmiter=%d)", who, ilsiter, icmiter);
+  if (npert < 0 || npert > m) return fail(RQ_EINVAL, "%s: npert=%d outside 0..m=%d", who, npert, m);
+  if ((int64_t)ilsiter * ((int64_t)niter + 1) > INT32_MAX)
+    return fail(RQ_EINVAL, "%s: ilsiter * (niter + 1) overflows the ILS iteration counter", who);
+  std::vector<double> scale;
+  RQ_TRY(sr_scales(scale, niter, method, schedule, p));
+  RQ_TRY(lsq_train_wide_shape(who, n, d, m, h, nsplits));
+  RQ_TRY(host_code_range(codes, n, m, h, code_base, who));
+  return train_sr_host<int16_t>(C, codes, obj, X, R, n, d, m, h, niter, ilsiter, icmiter, npert, randord, method, scale,
+                                clean_update, seed, nsplits, code_base, (flags & RQ_SR_RECOMPUTE) != 0);
+}
+
+extern "C" int rq_last_sr_stats(int64_t *out, int cap) {
+  if (!out) return fail(RQ_EINVAL, "rq_last_sr_stats: null pointer");
+  for (int q = 0; q < cap && q < SR_UPD_N; ++q) out[q] = g_sr_upd[q];
   return RQ_OK;
 }
 

@@ -254,7 +254,8 @@ def experiment_ervq_query_base(Xt, *args, V=False, seed=0, norms="host"):
 def _sr_init(Xt, m, h, niter_init, chain, V, seed):
     """The initialisation of the LSQ++ drivers: train_opq "natural" (src/SR.jl:365, :391), then train_chainq (:397) where
     the reference runs it.  Returns C, B, R, opq_error.  h > 256: train_opq and train_chainq both run over 16-bit codes, so the
-    start codes exist at any h <= 8192 (train_sr itself stays at h <= 256)."""
+    start codes exist at any h <= 8192; train_sr_cuda then runs its own loop over 16-bit codes (rq_train_sr_wide) wherever
+    m * h <= 16384 and the encoder's tables fit."""
     from .ChainQ import train_chainq
     C, B, R, opq_error = train_opq(Xt, m, h, niter_init, "natural", V, seed=seed)
     if chain:
