@@ -1006,6 +1006,38 @@ void rq_index_destroy(rq_index *ix);
 rq_index *rq_index_create_wide(int m, int h, int d, const float *centers_host);
 rq_index *rq_index_create_sharded_wide(int m, int h, int d, const float *centers_host, const int *devices, int ndev);
 int rq_index_set_codes_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset);
+/* The additive-quantizer (AQ) kind of the same handle: linscan_lsq / linscan_cq (src/Linscan.jl:118-193) against a resident,
+ * row-sharded base, in both code widths.  Searched, inspected and destroyed through rq_index_search[_opq]
+ * (linscan_lsq rotates the queries by R first, src/Linscan.jl:126), rq_index_info and rq_index_destroy; lists are exchanged and
+ * merged exactly as for a PQ index.  For any shard count the answer is bit for bit that of ONE call over the whole base:
+ * rq_linscan_lsq / rq_linscan_cq (byte), rq_linscan_lsq_wide / rq_linscan_cq_wide / rq_linscan_lsq_cbnorms_wide (wide), their
+ * rules for NaN norms and non-finite queries and codebooks included.
+ *   rq_index_create_aq[_wide]     codebooks [m * h][d] = hcat(C...) as rq_linscan_lsq[_wide] take them (byte: h = 256); lut_mode 1 =
+ *                                 LSQ (T = -2<q, c>, plus the row norm), 2 = CQ (T = |q - c|^2), the values of rq_dev_linscan_aq.
+ *                                 1 <= m <= 64 (byte) or 32 (wide), 1 <= h <= RQ_MAX_H16, any d >= 1.  devices == NULL with
+ *                                 ndev == 0: one shard on the calling thread's current device; else one shard per entry, a
+ *                                 repeated device holding several logical shards.  NULL (rq_last_error set) on a bad argument.
+ *   rq_index_set_codes_aq[_wide]  replaces the base and its norms (n may differ between calls).  LSQ takes exactly one of dbnorms
+ *                                 [n] and cbnorms [hn] (hn <= 256 byte, <= RQ_MAX_H16 wide; wide needs h >= 2): with cbnorms every
+ *                                 shard computes dbnorms = cbnorms[quantize_norms(|sum_k C_k[b_k]|^2)] on its own device from its
+ *                                 own rows (the arithmetic of rq_lsq_prepare_cbnorms / rq_linscan_lsq_cbnorms_wide).  CQ takes
+ *                                 neither.  Anything else is RQ_EINVAL before any work, and the loaded base keeps answering.
+ *                                 Byte shards are prepared as rq_lsq_prepare prepares its base: rows padded to a tiled width,
+ *                                 bank-aware row order once (tuning INDEX_ORDER), norms by position, the LSQ pre-filter's norm
+ *                                 buffer built once; the previous base is freed first.  Wide shards follow
+ *                                 rq_index_set_codes_wide: uploaded and checked before the loaded base is replaced, the first bad
+ *                                 row named, the base it had (and its norms) kept.  id_offset + n <= 2^32 - 1, a shard < 2^31 rows.
+ *   rq_index_aq_info              out[0] lut_mode (0: a PQ index), [1] wide, [2] h, [3] shards, then two slots per shard (as many
+ *                                 shards as fit in cap): in bank-aware order, holds a prepared norm buffer.
+ * rq_index_set_codes[_wide|_synth] on an AQ index, the AQ setters on a PQ index or one of the other width: RQ_EINVAL naming the
+ * entry to call. */
+rq_index *rq_index_create_aq(int m, int d, const float *codebooks_host, int lut_mode, const int *devices, int ndev);
+rq_index *rq_index_create_aq_wide(int m, int h, int d, const float *codebooks_host, int lut_mode, const int *devices, int ndev);
+int rq_index_set_codes_aq(rq_index *ix, const uint8_t *codes_host, const float *dbnorms_host, const float *cbnorms_host,
+                          int hn, int64_t n, uint32_t id_offset);
+int rq_index_set_codes_aq_wide(rq_index *ix, const int16_t *codes_host, const float *dbnorms_host, const float *cbnorms_host,
+                               int hn, int64_t n, int code_base, uint32_t id_offset);
+int rq_index_aq_info(rq_index *ix, int64_t *out, int cap);
 
 /* Threading: every entry point may be called from any host thread.  Library scratch is keyed by
  * (device, stream) and the launch sequences of one device are serialised internally, so concurrent

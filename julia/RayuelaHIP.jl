@@ -25,7 +25,7 @@ export groundtruth
 export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bin, train_lsq, train_lsq_cuda
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
-export HipIndex, HipIndexU16, set_codes!, set_codes_synth!, search, HipDataset, quantize
+export HipIndex, HipIndexU16, HipAqIndex, HipAqIndexU16, set_codes!, set_codes_synth!, search, HipDataset, quantize
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
 # call, linscan_pq / linscan_opq below shard B row-wise over those devices inside the library (per-device scan,
@@ -768,6 +768,80 @@ set_codes!(ix::HipIndexU16, B::Matrix{T}; id_offset::Integer=0) where T <: Integ
   set_codes!(ix, convert(Matrix{Int16}, B); code_base=1, id_offset=id_offset)
 
 search(ix::HipIndexU16, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,Matrix{Cfloat}}=nothing) = _index_search(ix, X, k, R)
+
+"""
+    HipAqIndex(C; kind=:lsq, devices=nothing)
+    HipAqIndexU16(C; kind=:lsq, devices=nothing)
+The resident, row-sharded index of an additive quantizer: `C` holds m full-dimensional `d`-by-h codebooks (h = 256 for
+`HipAqIndex`, any 1 <= h <= 32767 and m <= 32 for `HipAqIndexU16`); `kind` is `:lsq` (`linscan_lsq`) or `:cq` (`linscan_cq`).
+`set_codes!(ix, B; dbnorms=..., cbnorms=...)` takes exactly one of the two for `:lsq` (with `cbnorms` the row norms are
+quantized on the devices), neither for `:cq`; `search(ix, X, k; R=R)` returns what `linscan_lsq(B, X, C, dbnorms, R, k)` /
+`linscan_cq(B, X, C, k)` return on the whole base (k-by-nq `dists`, ONE-based `idx`), bit for bit.
+"""
+mutable struct HipAqIndex
+  h::Ptr{Cvoid}
+  m::Int
+  d::Int
+  function HipAqIndex(C::Vector{Matrix{Cfloat}}; kind::Symbol=:lsq, devices::Union{Nothing,Vector{<:Integer}}=nothing)
+    m = length(C)
+    d = size(C[1], 1)
+    lut_mode = _aq_lut_mode(kind)
+    devs = devices === nothing ? Cint[] : convert(Vector{Cint}, devices)
+    ptr = ccall((:rq_index_create_aq, librayuela_hip), Ptr{Cvoid}, (Cint, Cint, Ptr{Cfloat}, Cint, Ptr{Cint}, Cint),
+                Cint(m), Cint(d), hcat(C...), Cint(lut_mode), devices === nothing ? C_NULL : devs, Cint(length(devs)))
+    ptr == C_NULL && error("rq_index_create_aq: " * unsafe_string(ccall((:rq_last_error, librayuela_hip), Cstring, ())))
+    ix = new(ptr, m, d)
+    finalizer(x -> (x.h != C_NULL && ccall((:rq_index_destroy, librayuela_hip), Cvoid, (Ptr{Cvoid},), x.h); x.h = C_NULL), ix)
+    return ix
+  end
+end
+
+mutable struct HipAqIndexU16
+  h::Ptr{Cvoid}
+  m::Int
+  d::Int
+  function HipAqIndexU16(C::Vector{Matrix{Cfloat}}; kind::Symbol=:lsq, devices::Union{Nothing,Vector{<:Integer}}=nothing)
+    m = length(C)
+    d, h = size(C[1])
+    lut_mode = _aq_lut_mode(kind)
+    devs = devices === nothing ? Cint[] : convert(Vector{Cint}, devices)
+    ptr = ccall((:rq_index_create_aq_wide, librayuela_hip), Ptr{Cvoid}, (Cint, Cint, Cint, Ptr{Cfloat}, Cint, Ptr{Cint}, Cint),
+                Cint(m), Cint(h), Cint(d), hcat(C...), Cint(lut_mode), devices === nothing ? C_NULL : devs, Cint(length(devs)))
+    ptr == C_NULL && error("rq_index_create_aq_wide: " * unsafe_string(ccall((:rq_last_error, librayuela_hip), Cstring, ())))
+    ix = new(ptr, m, d)
+    finalizer(x -> (x.h != C_NULL && ccall((:rq_index_destroy, librayuela_hip), Cvoid, (Ptr{Cvoid},), x.h); x.h = C_NULL), ix)
+    return ix
+  end
+end
+
+_aq_lut_mode(kind::Symbol) = kind === :lsq ? 1 : kind === :cq ? 2 : error("kind must be :lsq or :cq")
+_aq_norm_ptr(v::Union{Nothing,Vector{Cfloat}}) = v === nothing ? Ptr{Cfloat}(C_NULL) : pointer(v)
+
+function set_codes!(ix::HipAqIndex, B::Matrix{UInt8}; dbnorms::Union{Nothing,Vector{Cfloat}}=nothing,
+                    cbnorms::Union{Nothing,Vector{Cfloat}}=nothing, id_offset::Integer=0)      # B zero-based m-by-n
+  dbnorms === nothing || length(dbnorms) == size(B, 2) || error("dbnorms must have one entry per database row")
+  hn = cbnorms === nothing ? 0 : length(cbnorms)
+  GC.@preserve dbnorms cbnorms _check(ccall((:rq_index_set_codes_aq, librayuela_hip), Cint,
+    (Ptr{Cvoid}, Ptr{Cuchar}, Ptr{Cfloat}, Ptr{Cfloat}, Cint, Int64, UInt32),
+    ix.h, B, _aq_norm_ptr(dbnorms), _aq_norm_ptr(cbnorms), Cint(hn), Int64(size(B, 2)), UInt32(id_offset)))
+  return ix
+end
+set_codes!(ix::HipAqIndex, B::Matrix{T}; kwargs...) where T <: Integer = set_codes!(ix, convert(Matrix{UInt8}, B .- 1); kwargs...)
+
+function set_codes!(ix::HipAqIndexU16, B::Matrix{Int16}; dbnorms::Union{Nothing,Vector{Cfloat}}=nothing,
+                    cbnorms::Union{Nothing,Vector{Cfloat}}=nothing, code_base::Integer=0, id_offset::Integer=0)
+  dbnorms === nothing || length(dbnorms) == size(B, 2) || error("dbnorms must have one entry per database row")
+  hn = cbnorms === nothing ? 0 : length(cbnorms)
+  GC.@preserve dbnorms cbnorms _check(ccall((:rq_index_set_codes_aq_wide, librayuela_hip), Cint,
+    (Ptr{Cvoid}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Cint, Int64, Cint, UInt32),
+    ix.h, B, _aq_norm_ptr(dbnorms), _aq_norm_ptr(cbnorms), Cint(hn), Int64(size(B, 2)), Cint(code_base), UInt32(id_offset)))
+  return ix
+end
+set_codes!(ix::HipAqIndexU16, B::Matrix{T}; kwargs...) where T <: Integer =
+  set_codes!(ix, convert(Matrix{Int16}, B); code_base=1, kwargs...)
+
+search(ix::Union{HipAqIndex,HipAqIndexU16}, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,Matrix{Cfloat}}=nothing) =
+  _index_search(ix, X, k, R)
 
 """
     HipDataset(X)

@@ -181,6 +181,11 @@ SIGNATURES = {
     "rq_index_create_wide": (_vp, [_i32, _i32, _i32, _vp]),
     "rq_index_create_sharded_wide": (_vp, [_i32, _i32, _i32, _vp, _vp, _i32]),
     "rq_index_set_codes_wide": (_i32, [_vp, _vp, _i64, _i32, _u32]),
+    "rq_index_create_aq": (_vp, [_i32, _i32, _vp, _i32, _vp, _i32]),
+    "rq_index_create_aq_wide": (_vp, [_i32, _i32, _i32, _vp, _i32, _vp, _i32]),
+    "rq_index_set_codes_aq": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _u32]),
+    "rq_index_set_codes_aq_wide": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _u32]),
+    "rq_index_aq_info": (_i32, [_vp, _vp, _i32]),
     "rq_index_search_opq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32]),
     "rq_index_info": (_i32, [_vp, _vp, _i32]),
     "rq_release_workspaces": (_i32, []),

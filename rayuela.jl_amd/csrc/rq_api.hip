@@ -1234,16 +1234,89 @@ int rq_linscan_lsq(float *dists, uint32_t *ids, const uint8_t *codes, const floa
 }
 
 // ---- linscan_lsq over a PREPARED base: codes, norms, codebooks resident, the filter's O(n) preprocessing done once ---------
+extern "C++" {
+namespace rq {
+void aq_base_free(AqBase *b) {
+  if (b->codes) (void)hipFree(b->codes);
+  if (b->norms) (void)hipFree(b->norms);
+  if (b->normb) (void)hipFree(b->normb);
+  if (b->ordered) (void)hipFree(b->ordered);
+  *b = AqBase();
+}
+
+int aq_base_prepare(AqBase *b, const uint8_t *codes, const float *cb, const float *dbnorms, const float *cbnorms, int hn, int64_t n,
+                    int m, int d, bool lsq, hipStream_t stream) {
+  const int mp = scan_padded_m(m);
+  auto idle = [&]() { return stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize(); };
+  RQ_HIP(hipMalloc((void **)&b->codes, (size_t)n * mp));
+  if (lsq) RQ_HIP(hipMalloc((void **)&b->norms, (size_t)n * 4));
+  if (lsq && dbnorms) RQ_HIP(hipMemcpy(b->norms, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
+  {
+    DevBuf raw;
+    const uint8_t *rawc = b->codes;      // the [n][m] rows as uploaded
+    if (mp == m) {
+      RQ_HIP(hipMemcpy(b->codes, codes, (size_t)n * m, hipMemcpyHostToDevice));
+    } else {
+      RQ_TRY(raw.alloc((size_t)n * m));
+      RQ_HIP(hipMemcpy(raw.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
+      RQ_TRY(pad_codes_launch(b->codes, raw.as<uint8_t>(), n, m, mp, stream));
+      rawc = raw.as<uint8_t>();
+    }
+    if (lsq && !dbnorms) {
+      DevBuf dcbn, dsq;
+      RQ_TRY(dcbn.alloc((size_t)hn * 4)); RQ_TRY(dsq.alloc((size_t)n * 4));
+      RQ_HIP(hipMemcpy(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
+      RQ_TRY(aq_norms_launch(dsq.as<float>(), rawc, cb, n, d, m, 256, stream));
+      RQ_TRY(quantize_norms_launch((uint8_t *)nullptr, b->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, stream));
+    }
+    RQ_HIP(idle());       // before the scratch of this block goes back
+  }
+  // the base is resident: bank-aware row order once (rq_order.hip), norms permuted alike -- row_bias and the filter's
+  // norm bytes are indexed by POSITION in the kernel, ids come from perm
+  // (an ordered copy that cannot be allocated or built leaves the base in arrival order: slower gathers, same answer)
+  if (tuning("INDEX_ORDER", 1) && order_pays(n, 0, 0) && hipMalloc(&b->ordered, order_base_bytes(n, mp)) != hipSuccess) {
+    (void)hipGetLastError();      // out of memory: the base stays in arrival order
+    b->ordered = nullptr;
+  }
+  if (b->ordered) {
+    const int orc = order_base(&b->ocodes, &b->perm, b->ordered, b->codes, n, mp, ORDER_ONCE, stream);
+    if (is_oom(orc)) { forgive_oom(); b->perm = nullptr; }      // (the key scratch)
+    else if (orc != RQ_OK) return orc;                           // launch errors surface
+    if (b->perm) {
+      if (lsq) {
+        float *pn = nullptr;
+        RQ_HIP(hipMalloc((void **)&pn, (size_t)n * 4));
+        const int grc = gather_f32_launch(pn, b->norms, b->perm, n, stream);
+        if (grc != RQ_OK) { (void)hipFree(pn); return grc; }
+        RQ_HIP(idle());
+        RQ_HIP(hipFree(b->norms));
+        b->norms = pn;
+      } else {
+        RQ_HIP(idle());
+      }
+      RQ_HIP(hipFree(b->codes));
+      b->codes = nullptr;
+    } else {
+      RQ_HIP(hipFree(b->ordered));
+      b->ordered = nullptr;
+    }
+  }
+  if (lsq && (mp == 8 || mp == 16) && tuning("SCAN_FILTER", 1) && tuning("SCAN_FILTER_LSQ", 1)) {
+    RQ_HIP(hipMalloc((void **)&b->normb, lsq_norm_bytes(n)));
+    RQ_TRY(lsq_norm_prepare(b->normb, b->rows(), cb, b->norms, n, mp, m, d, stream));
+    RQ_HIP(idle());
+  }
+  return RQ_OK;
+}
+}  // namespace rq
+}  // extern "C++"
+
 struct rq_lsq_index_impl {
   int device = 0;
   int64_t n = 0;
   int m = 0, mp = 0, d = 0;
-  uint8_t *codes = nullptr;      // [n][mp] (zero-padded to a tiled row width)
-  float *cb = nullptr, *norms = nullptr;
-  uint8_t *normb = nullptr;      // prepared norm buffer (lsq_norm_bytes) or nullptr when the filter does not apply
-  void *ordered = nullptr;       // codes in bank-aware row order + perm (order_base), norms permuted alike; else nullptr
-  const uint8_t *ocodes = nullptr;
-  const uint32_t *perm = nullptr;
+  float *cb = nullptr;
+  AqBase base;      // [n][mp] rows (zero-padded to a tiled row width), norms and the prepared norm buffer
 };
 
 static void lsq_free(rq_lsq_index_impl *ix) {
@@ -1252,11 +1325,8 @@ static void lsq_free(rq_lsq_index_impl *ix) {
   const bool have = hipGetDevice(&cur) == hipSuccess;
   if (hipSetDevice(ix->device) == hipSuccess) {
     (void)hipDeviceSynchronize();
-    if (ix->codes) (void)hipFree(ix->codes);
     if (ix->cb) (void)hipFree(ix->cb);
-    if (ix->norms) (void)hipFree(ix->norms);
-    if (ix->normb) (void)hipFree(ix->normb);
-    if (ix->ordered) (void)hipFree(ix->ordered);
+    aq_base_free(&ix->base);
   }
   if (have) (void)hipSetDevice(cur);
   (void)hipGetLastError();
@@ -1283,63 +1353,9 @@ static rq_lsq_index *lsq_prepare(const uint8_t *codes, const float *codebooks, c
   rq_lsq_index_impl *ix = new rq_lsq_index_impl;
   ix->device = di.device; ix->n = n; ix->m = m; ix->mp = mp; ix->d = d;
   auto body = [&]() -> int {
-    RQ_HIP(hipMalloc((void **)&ix->codes, (size_t)n * mp));
     RQ_HIP(hipMalloc((void **)&ix->cb, (size_t)m * 256 * d * 4));
-    RQ_HIP(hipMalloc((void **)&ix->norms, (size_t)n * 4));
     RQ_HIP(hipMemcpy(ix->cb, codebooks, (size_t)m * 256 * d * 4, hipMemcpyHostToDevice));
-    if (dbnorms) RQ_HIP(hipMemcpy(ix->norms, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
-    {
-      DevBuf raw;
-      const uint8_t *rawc = ix->codes;      // the [n][m] rows as uploaded
-      if (mp == m) {
-        RQ_HIP(hipMemcpy(ix->codes, codes, (size_t)n * m, hipMemcpyHostToDevice));
-      } else {
-        RQ_TRY(raw.alloc((size_t)n * m));
-        RQ_HIP(hipMemcpy(raw.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
-        RQ_TRY(pad_codes_launch(ix->codes, raw.as<uint8_t>(), n, m, mp, nullptr));
-        rawc = raw.as<uint8_t>();
-      }
-      if (!dbnorms) {
-        DevBuf dcbn, dsq;
-        RQ_TRY(dcbn.alloc((size_t)hn * 4)); RQ_TRY(dsq.alloc((size_t)n * 4));
-        RQ_HIP(hipMemcpy(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
-        RQ_TRY(aq_norms_launch(dsq.as<float>(), rawc, ix->cb, n, d, m, 256, nullptr));
-        RQ_TRY(quantize_norms_launch((uint8_t *)nullptr, ix->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, nullptr));
-      }
-      RQ_HIP(hipDeviceSynchronize());       // before the scratch of this block goes back
-    }
-    // the base is resident: bank-aware row order once (rq_order.hip), norms permuted alike -- row_bias and the filter's
-    // norm bytes are indexed by POSITION in the kernel, ids come from perm
-    // (an ordered copy that cannot be allocated or built leaves the base in arrival order: slower gathers, same answer)
-    if (tuning("INDEX_ORDER", 1) && order_pays(n, 0, 0) && hipMalloc(&ix->ordered, order_base_bytes(n, mp)) != hipSuccess) {
-      (void)hipGetLastError();      // out of memory: the base stays in arrival order
-      ix->ordered = nullptr;
-    }
-    if (ix->ordered) {
-      const int orc = order_base(&ix->ocodes, &ix->perm, ix->ordered, ix->codes, n, mp, ORDER_ONCE, nullptr);
-      if (is_oom(orc)) { forgive_oom(); ix->perm = nullptr; }      // (the key scratch)
-      else if (orc != RQ_OK) return orc;                           // launch errors surface
-      if (ix->perm) {
-        float *pn = nullptr;
-        RQ_HIP(hipMalloc((void **)&pn, (size_t)n * 4));
-        RQ_TRY(gather_f32_launch(pn, ix->norms, ix->perm, n, nullptr));
-        RQ_HIP(hipDeviceSynchronize());
-        RQ_HIP(hipFree(ix->norms));
-        ix->norms = pn;
-        RQ_HIP(hipFree(ix->codes));
-        ix->codes = nullptr;
-      } else {
-        RQ_HIP(hipFree(ix->ordered));
-        ix->ordered = nullptr;
-      }
-    }
-    const uint8_t *cur = ix->perm ? ix->ocodes : ix->codes;
-    if ((mp == 8 || mp == 16) && tuning("SCAN_FILTER", 1) && tuning("SCAN_FILTER_LSQ", 1)) {
-      RQ_HIP(hipMalloc((void **)&ix->normb, lsq_norm_bytes(n)));
-      RQ_TRY(lsq_norm_prepare(ix->normb, cur, ix->cb, ix->norms, n, mp, m, d, nullptr));
-      RQ_HIP(hipDeviceSynchronize());
-    }
-    return RQ_OK;
+    return aq_base_prepare(&ix->base, codes, ix->cb, dbnorms, cbnorms, hn, n, m, d, true, nullptr);
   };
   if (body() != RQ_OK) { lsq_free(ix); return nullptr; }
   return reinterpret_cast<rq_lsq_index *>(ix);
@@ -1379,11 +1395,11 @@ int rq_lsq_search(rq_lsq_index *handle, float *dists, uint32_t *ids, const float
   RQ_TRY(q.stage(queries, R, nq, d, di.num_cu));
   ScanBase sb;      // (the bulk path of dev_linscan branches off before it reads the norm buffer)
   sb.padded = true;
-  sb.norm_prepared = ix->normb;
-  sb.perm = ix->perm;
+  sb.norm_prepared = ix->base.normb;
+  sb.perm = ix->base.perm;
   RQ_TRY(deliver(dists, ids, nq, k, [&](float *dd, uint32_t *di_, int64_t q0, int64_t nqc, hipStream_t stream) {
-    return dev_linscan(dd, di_, nullptr, ix->perm ? ix->ocodes : ix->codes, ix->cb, q.p + (size_t)q0 * d, ix->n, nqc, ix->m, d, k,
-                       0, id_base, stream, LUT_LSQ, ix->norms, &sb);
+    return dev_linscan(dd, di_, nullptr, ix->base.rows(), ix->cb, q.p + (size_t)q0 * d, ix->n, nqc, ix->m, d, k,
+                       0, id_base, stream, LUT_LSQ, ix->base.norms, &sb);
   }));
   g_t_total = tt.ms();
   return RQ_OK;

@@ -22,6 +22,9 @@
 // A device may appear several times in the device list: every occurrence is one LOGICAL shard (that is
 // how the sharded path is tested on a one-GPU box, and how a base of >= 2^31 rows fits one device).
 // librccl is dlopen()ed on first use, so the library has no link-time dependency on it.
+//
+// The same handle serves the additive quantizers (rq_index_create_aq[_wide]): full-dimensional codebooks,
+// per-shard row norms for linscan_lsq, the shard scans of rq_linscan_lsq / rq_linscan_cq and their forms over 16-bit codes.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 #include <stdlib.h>
@@ -128,6 +131,8 @@ struct IxShard {
   uint8_t *codes = nullptr;   // the shard's rows -- in bank-aware order when perm != nullptr (rq_order.hip); a wide index
                               // (rq_index_create_wide) keeps int16 rows here, in arrival order
   const uint32_t *perm = nullptr;   // position -> row of the shard (inside the `codes` allocation)
+  float *norms = nullptr;     // AQ index, LSQ: the shard's row norms (dbnorms [row0, row0 + n)) -- BY POSITION when perm != nullptr
+  uint8_t *normb = nullptr;   // byte LSQ shard: the pre-filter's prepared norm buffer (lsq_norm_prepare), where the filter applies
   uint64_t *keys = nullptr;   // [nq][k] sorted keys of the last search (shards off the root device)
   size_t keys_cap = 0;
   uint64_t *tmp = nullptr;    // [nq][k_local] when the shard holds fewer than k rows
@@ -152,6 +157,8 @@ struct rq_index {
   int m = 0, d = 0;
   int h = 256;          // codewords per codebook; wide: int16 codes scanned by dev_linscan_wide
   bool wide = false;
+  int lut_mode = LUT_PQ;      // LUT_LSQ / LUT_CQ: an additive-quantizer index (rq_index_create_aq[_wide]) --
+                              // `centers` are full-dimensional codebooks [m * h][d], an LSQ shard carries its row norms
   int64_t n = 0;
   uint32_t id_offset = 0;
   std::vector<IxDev> devs;
@@ -181,6 +188,8 @@ static void index_free(rq_index *ix) {
   for (auto &s : ix->shards) {
     if (hipSetDevice(ix->devs[s.dev].device) != hipSuccess) continue;
     if (s.codes) (void)hipFree(s.codes);
+    if (s.norms) (void)hipFree(s.norms);
+    if (s.normb) (void)hipFree(s.normb);
     if (s.keys) (void)hipFree(s.keys);
     if (s.tmp) (void)hipFree(s.tmp);
   }
@@ -210,17 +219,19 @@ static void index_free(rq_index *ix) {
 }
 
 static int index_build(rq_index *ix, int m, int d, const float *centers_host, const int *devices, int ndev, int h = 256,
-                       bool wide = false) {
+                       bool wide = false, int lut_mode = LUT_PQ) {
   if (wide && (m < 1 || m > 32)) return fail(RQ_EUNSUPPORTED, "wide index covers 1 <= m <= 32; got m=%d", m);
   if (wide && (h < 1 || h > RQ_MAX_H16))
     return fail(RQ_EUNSUPPORTED, "wide index holds Int16 codes: 1 <= h <= %d; got h=%d", RQ_MAX_H16, h);
-  if (m < 1 || d < m || d % m) return fail(RQ_EINVAL, "index: scan needs d %% m == 0 (src/Linscan.jl:23); got d=%d m=%d", d, m);
+  // (an AQ index has full-dimensional codebooks: any d >= 1, checked by its create entries)
+  if (lut_mode == LUT_PQ && (m < 1 || d < m || d % m))
+    return fail(RQ_EINVAL, "index: scan needs d %% m == 0 (src/Linscan.jl:23); got d=%d m=%d", d, m);
   if (!centers_host) return fail(RQ_EINVAL, "index: centers is NULL");
   if (ndev < 1 || ndev > 64) return fail(RQ_EINVAL, "index: 1 <= number of shards <= 64, got %d", ndev);
   int visible = 0;
   if (hipGetDeviceCount(&visible) != hipSuccess || visible < 1) { (void)hipGetLastError(); return fail(RQ_ENODEVICE, "no HIP device visible"); }
-  ix->m = m; ix->d = d; ix->h = h; ix->wide = wide;
-  const size_t ce = (size_t)m * h * (d / m) * 4;
+  ix->m = m; ix->d = d; ix->h = h; ix->wide = wide; ix->lut_mode = lut_mode;
+  const size_t ce = (size_t)m * h * (lut_mode == LUT_PQ ? d / m : d) * 4;
   for (int s = 0; s < ndev; ++s) {
     const int dev = devices[s];
     if (dev < 0 || dev >= visible || dev >= 16) return fail(RQ_EINVAL, "index: device %d not in [0, %d)", dev, std::min(visible, 16));
@@ -299,6 +310,8 @@ static void shard_bounds(rq_index *ix, int64_t n) {
 template <class Fill>
 static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
   if (!ix) return fail(RQ_EINVAL, "index is NULL");
+  if (ix->lut_mode != LUT_PQ)
+    return fail(RQ_EINVAL, "index: an additive-quantizer index takes its codes through rq_index_set_codes_aq%s", ix->wide ? "_wide" : "");
   if (ix->wide) return fail(RQ_EINVAL, "index: a wide index takes its codes through rq_index_set_codes_wide");
   if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
   // same bound as dev_linscan: the last id must stay below 0xFFFFFFFF (that id is the padding key KEY_MAX's)
@@ -356,9 +369,85 @@ static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
 // The wide form of index_set: int16 rows, no row order.  Every shard's new rows are uploaded to a fresh allocation and checked
 // there (prepare_codes_h16_kernel: zero-based in place, the first row with a code outside [0, h)) BEFORE anything of the index
 // is replaced, so a refused base leaves the loaded one answering as before.  Old and new rows are resident together until then.
-static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset) {
-  const char *who = "rq_index_set_codes_wide";
+// What the AQ setters refuse before any work: the wrong kind or width of index, and a norm argument that does not fit lut_mode.
+static int aq_set_check(const char *who, rq_index *ix, bool wide, const void *codes_host, const float *dbnorms, const float *cbnorms,
+                        int hn) {
   if (!ix) return fail(RQ_EINVAL, "index is NULL");
+  if (ix->lut_mode == LUT_PQ)
+    return fail(RQ_EINVAL, "%s: a PQ index takes its codes through rq_index_set_codes%s", who, ix->wide ? "_wide" : "");
+  if (ix->wide != wide)
+    return fail(RQ_EINVAL, "%s: a %s index takes its codes through rq_index_set_codes_aq%s", who, ix->wide ? "wide" : "byte",
+                ix->wide ? "_wide" : "");
+  if (!codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
+  if (ix->lut_mode == LUT_CQ) {
+    if (dbnorms || cbnorms) return fail(RQ_EINVAL, "%s: a CQ index takes no norms (T = |q - c|^2 holds them)", who);
+    return RQ_OK;
+  }
+  if (!dbnorms == !cbnorms) return fail(RQ_EINVAL, "%s: an LSQ index takes exactly one of dbnorms [n] and cbnorms [hn]", who);
+  if (cbnorms) {
+    const int hn_max = wide ? RQ_MAX_H16 : 256;
+    if (hn < 1 || hn > hn_max) return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, hn, hn_max);
+    if (ix->h < 2) return fail(RQ_EINVAL, "%s: the norms need 2 <= h; got h=%d", who, ix->h);   // (rq_linscan_lsq_cbnorms_wide's rule)
+  }
+  return RQ_OK;
+}
+
+// rq_index_set_codes_aq: every shard is prepared the way rq_lsq_prepare prepares its one base (aq_base_prepare, rq_api.hip) --
+// rows padded to a tiled width, bank-aware order once, the shard's norms gathered through the shard's own perm, the LSQ
+// pre-filter's norm buffer built once.  Byte codes cannot be out of range, so nothing is refused after the first shard is touched;
+// the previous base is freed first (a base and its replacement need not fit together).  An error half-way (a device fault, no
+// memory for a shard) leaves the index without codes.
+static int index_set_aq(rq_index *ix, const uint8_t *codes_host, const float *dbnorms, const float *cbnorms, int hn, int64_t n,
+                        uint32_t id_offset) {
+  RQ_TRY(aq_set_check("rq_index_set_codes_aq", ix, false, codes_host, dbnorms, cbnorms, hn));
+  if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
+  if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "index: row ids overflow uint32 (id_offset + n must be <= 2^32 - 1)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  SavedDevice saved;
+  const int64_t P = (int64_t)ix->shards.size();
+  if (n / P + (n % P ? 1 : 0) >= (1LL << 31))
+    return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)(n / P + 1));
+  ix->n = 0;
+  for (auto &s : ix->shards) {
+    IxDev &dv = ix->devs[s.dev];
+    RQ_HIP(hipSetDevice(dv.device));
+    if (s.codes) RQ_HIP(hipStreamSynchronize(dv.stream));
+    AqBase old;
+    old.codes = s.codes; old.norms = s.norms; old.normb = s.normb;
+    aq_base_free(&old);
+    s.codes = nullptr; s.norms = nullptr; s.normb = nullptr; s.perm = nullptr;
+  }
+  shard_bounds(ix, n);
+  for (auto &s : ix->shards) {
+    if (s.n == 0) continue;
+    IxDev &dv = ix->devs[s.dev];
+    RQ_HIP(hipSetDevice(dv.device));
+    DeviceLock prepare_lock;      // scratch lookup + launches of this device, like a scan
+    AqBase b;
+    const int rc = aq_base_prepare(&b, codes_host + (size_t)s.row0 * ix->m, dv.centers, dbnorms ? dbnorms + s.row0 : nullptr, cbnorms,
+                                   hn, s.n, ix->m, ix->d, ix->lut_mode == LUT_LSQ, dv.stream);
+    (void)release_stream_workspace(dv.stream);    // the order's key scratch is not needed again
+    if (rc != RQ_OK) { (void)hipStreamSynchronize(dv.stream); aq_base_free(&b); return rc; }
+    s.codes = b.perm ? (uint8_t *)b.ordered : b.codes;      // (order_base puts the ordered rows first in its allocation)
+    s.perm = b.perm;
+    s.norms = b.norms;
+    s.normb = b.normb;
+  }
+  ix->n = n;
+  ix->id_offset = id_offset;
+  return RQ_OK;
+}
+
+// The wide forms.  `aq`: rq_index_set_codes_aq_wide -- an LSQ shard's norms are uploaded (dbnorms) or computed from the shard's own
+// validated rows on the shard's device (cbnorms: aq_norms_launch + quantize_norms_launch, the arithmetic of
+// rq_linscan_lsq_cbnorms_wide) into a fresh allocation too, and replace the old ones together with the rows.
+static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset, bool aq = false,
+                          const float *dbnorms = nullptr, const float *cbnorms = nullptr, int hn = 0) {
+  const char *who = aq ? "rq_index_set_codes_aq_wide" : "rq_index_set_codes_wide";
+  if (aq) RQ_TRY(aq_set_check(who, ix, true, codes_host, dbnorms, cbnorms, hn));
+  if (!ix) return fail(RQ_EINVAL, "index is NULL");
+  if (!aq && ix->lut_mode != LUT_PQ)
+    return fail(RQ_EINVAL, "%s: an additive-quantizer index takes its codes through rq_index_set_codes_aq%s", who, ix->wide ? "_wide" : "");
   if (!ix->wide) return fail(RQ_EINVAL, "%s: a byte index takes its codes through rq_index_set_codes", who);
   if (!codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
   if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
@@ -370,10 +459,16 @@ static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, in
   const int64_t P = (int64_t)ix->shards.size(), per = n / P, extra = n % P;
   if (per + (extra ? 1 : 0) >= (1LL << 31))
     return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)(per + 1));
+  const bool lsq = aq && ix->lut_mode == LUT_LSQ;
   std::vector<int16_t *> fresh((size_t)P, nullptr);
+  std::vector<float *> fresh_norms((size_t)P, nullptr);
   auto drop = [&]() {
-    for (int64_t s = 0; s < P; ++s)
-      if (fresh[(size_t)s] && hipSetDevice(ix->devs[ix->shards[(size_t)s].dev].device) == hipSuccess) (void)hipFree(fresh[(size_t)s]);
+    for (int64_t s = 0; s < P; ++s) {
+      if (!fresh[(size_t)s] && !fresh_norms[(size_t)s]) continue;
+      if (hipSetDevice(ix->devs[ix->shards[(size_t)s].dev].device) != hipSuccess) continue;
+      if (fresh[(size_t)s]) (void)hipFree(fresh[(size_t)s]);
+      if (fresh_norms[(size_t)s]) (void)hipFree(fresh_norms[(size_t)s]);
+    }
     (void)hipGetLastError();
   };
   int rc = RQ_OK;
@@ -396,6 +491,23 @@ static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, in
       if (first_bad != ~0ull)      // shards are checked in row order: this is the first bad row of the base
         return fail(RQ_EINVAL, "%s: row %llu holds a code outside [%d, %d]; the index keeps the base it had", who,
                     (unsigned long long)row0 + first_bad, code_base, h - 1 + code_base);
+      if (!lsq) return RQ_OK;
+      // the shard's norms, from rows that are zero-based and in range by now
+      float *nrm = nullptr;
+      RQ_HIP(hipMalloc((void **)&nrm, (size_t)sn * 4));
+      fresh_norms[(size_t)s] = nrm;
+      if (dbnorms) {
+        RQ_HIP(hipMemcpyAsync(nrm, dbnorms + row0, (size_t)sn * 4, hipMemcpyHostToDevice, dv.stream));
+        RQ_HIP(hipStreamSynchronize(dv.stream));
+        return RQ_OK;
+      }
+      DevMem dcbn;
+      RQ_TRY(dcbn.alloc((size_t)hn * 4));
+      RQ_HIP(hipMemcpyAsync(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice, dv.stream));
+      DeviceLock norms_lock;
+      RQ_TRY(aq_norms_launch(nrm, fresh[(size_t)s], dv.centers, sn, ix->d, m, h, dv.stream));
+      RQ_TRY(quantize_norms_launch((int16_t *)nullptr, nrm, nrm, dcbn.as<float>(), sn, hn, dv.stream));
+      RQ_HIP(hipStreamSynchronize(dv.stream));      // before the table goes back
       return RQ_OK;
     }();
   }
@@ -409,6 +521,9 @@ static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, in
     sh.codes = reinterpret_cast<uint8_t *>(fresh[(size_t)s]);
     fresh[(size_t)s] = nullptr;
     sh.perm = nullptr;
+    if (sh.norms) RQ_HIP(hipFree(sh.norms));
+    sh.norms = fresh_norms[(size_t)s];
+    fresh_norms[(size_t)s] = nullptr;
   }
   ix->n = n;
   ix->id_offset = id_offset;
@@ -474,17 +589,27 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
   RQ_HIP(hipSetDevice(root.device));
   RQ_TRY(grow((void **)&ix->dd, &ix->dd_cap, ob));
   RQ_TRY(grow((void **)&ix->di, &ix->di_cap, ob));
+  // one shard's scan on its device's stream (the device is current), by (wide, lut_mode): dists + ids, or sorted keys
+  auto scan_shard = [&](IxShard &s, IxDev &dv, float *sd, uint32_t *si, uint64_t *sk, const float *qs, int64_t nqs, int ks,
+                        uint32_t id_off, int base) -> int {
+    if (ix->wide) {
+      const int16_t *c16 = reinterpret_cast<const int16_t *>(s.codes);
+      if (ix->lut_mode != LUT_PQ)
+        return dev_linscan_aq_wide(sd, si, sk, c16, dv.centers, qs, s.norms, s.n, nqs, m, ix->h, d, ks, ix->lut_mode, id_off, base,
+                                   dv.stream);
+      return dev_linscan_wide(sd, si, sk, c16, dv.centers, qs, s.n, nqs, m, ix->h, d, ks, id_off, base, dv.stream);
+    }
+    ScanBase sb;
+    sb.perm = s.perm;
+    if (ix->lut_mode != LUT_PQ) {       // an AQ shard is an aq_base_prepare base: padded rows, the norm buffer where the filter applies
+      sb.padded = true;
+      sb.norm_prepared = s.normb;
+    }
+    return dev_linscan(sd, si, sk, s.codes, dv.centers, qs, s.n, nqs, m, d, ks, id_off, base, dv.stream, ix->lut_mode, s.norms, &sb);
+  };
   if (P == 1) {
-    IxShard &s = ix->shards[0];
-    ScanBase sb0;
-    sb0.perm = s.perm;
-    if (ix->wide)
-      RQ_TRY(dev_linscan_wide(ix->dd, ix->di, nullptr, reinterpret_cast<const int16_t *>(s.codes), root.centers,
-                              R_host ? root.queries_rot : root.queries, s.n, nq, m, ix->h, d, k, ix->id_offset, id_base,
-                              root.stream));
-    else
-      RQ_TRY(dev_linscan(ix->dd, ix->di, nullptr, s.codes, root.centers, R_host ? root.queries_rot : root.queries, s.n, nq, m,
-                         d, k, ix->id_offset, id_base, root.stream, LUT_PQ, nullptr, &sb0));
+    RQ_TRY(scan_shard(ix->shards[0], root, ix->dd, ix->di, nullptr, R_host ? root.queries_rot : root.queries, nq, k, ix->id_offset,
+                      id_base));
   } else {
     RQ_TRY(grow((void **)&ix->gathered, &ix->gathered_cap, (size_t)P * cnt * 8));
     RQ_TRY(grow((void **)&ix->inter, &ix->inter_cap, (size_t)P * cnt * 8));
@@ -525,14 +650,7 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
         uint64_t *out = (remote(si) ? s.keys : ix->gathered + (size_t)si * cnt) + (size_t)q0 * k;   // root shards: in place
         uint64_t *dst = k_local < k ? s.tmp + (size_t)q0 * k_local : out;
         const float *qs = (R_host ? dv.queries_rot : dv.queries) + (size_t)q0 * d;
-        ScanBase sbs;
-        sbs.perm = s.perm;
-        if (ix->wide)
-          RQ_TRY(dev_linscan_wide(nullptr, nullptr, dst, reinterpret_cast<const int16_t *>(s.codes), dv.centers, qs, s.n, nqc, m,
-                                  ix->h, d, k_local, (uint32_t)(ix->id_offset + (uint64_t)s.row0), 0, dv.stream));
-        else
-          RQ_TRY(dev_linscan(nullptr, nullptr, dst, s.codes, dv.centers, qs, s.n, nqc, m, d, k_local,
-                             (uint32_t)(ix->id_offset + (uint64_t)s.row0), 0, dv.stream, LUT_PQ, nullptr, &sbs));
+        RQ_TRY(scan_shard(s, dv, nullptr, nullptr, dst, qs, nqc, k_local, (uint32_t)(ix->id_offset + (uint64_t)s.row0), 0));
         if (k_local < k)
           RQ_HIP(hipMemcpy2DAsync(out, (size_t)k * 8, dst, (size_t)k_local * 8, (size_t)k_local * 8, (size_t)nqc,
                                   hipMemcpyDeviceToDevice, dv.stream));
@@ -707,6 +825,59 @@ rq_index *rq_index_create_wide(int m, int h, int d, const float *centers_host) {
 
 int rq_index_set_codes_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset) {
   return index_set_wide(ix, codes_host, n, code_base, id_offset);
+}
+
+// rq_index_create_aq[_wide]: devices == NULL with ndev == 0 is one shard on the calling thread's current device
+static rq_index *index_create_aq(const char *who, int m, int h, int d, const float *codebooks_host, int lut_mode, const int *devices,
+                                 int ndev, bool wide) {
+  const int m_max = wide ? 32 : 64;
+  if (m < 1 || m > m_max) { fail(RQ_EINVAL, "%s: 1 <= m <= %d; got m=%d", who, m_max, m); return nullptr; }
+  if (h < 1 || h > RQ_MAX_H16) { fail(RQ_EINVAL, "%s: 1 <= h <= %d; got h=%d", who, RQ_MAX_H16, h); return nullptr; }
+  if (d < 1) { fail(RQ_EINVAL, "%s: d=%d must be >= 1", who, d); return nullptr; }
+  if (lut_mode != LUT_LSQ && lut_mode != LUT_CQ) { fail(RQ_EINVAL, "%s: lut_mode must be 1 (LSQ) or 2 (CQ); got %d", who, lut_mode); return nullptr; }
+  if (!codebooks_host) { fail(RQ_EINVAL, "%s: codebooks is NULL", who); return nullptr; }
+  if ((devices == nullptr) != (ndev == 0)) { fail(RQ_EINVAL, "%s: devices and ndev must be given together", who); return nullptr; }
+  int dev = 0;
+  if (!devices) {
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); fail(RQ_ENODEVICE, "no device"); return nullptr; }
+    devices = &dev;
+    ndev = 1;
+  }
+  rq_index *ix = new rq_index();
+  SavedDevice saved;
+  if (index_build(ix, m, d, codebooks_host, devices, ndev, h, wide, lut_mode) != RQ_OK) { index_free(ix); return nullptr; }
+  return ix;
+}
+
+rq_index *rq_index_create_aq(int m, int d, const float *codebooks_host, int lut_mode, const int *devices, int ndev) {
+  return index_create_aq("rq_index_create_aq", m, 256, d, codebooks_host, lut_mode, devices, ndev, false);
+}
+
+rq_index *rq_index_create_aq_wide(int m, int h, int d, const float *codebooks_host, int lut_mode, const int *devices, int ndev) {
+  return index_create_aq("rq_index_create_aq_wide", m, h, d, codebooks_host, lut_mode, devices, ndev, true);
+}
+
+int rq_index_set_codes_aq(rq_index *ix, const uint8_t *codes_host, const float *dbnorms_host, const float *cbnorms_host, int hn,
+                          int64_t n, uint32_t id_offset) {
+  return index_set_aq(ix, codes_host, dbnorms_host, cbnorms_host, hn, n, id_offset);
+}
+
+int rq_index_set_codes_aq_wide(rq_index *ix, const int16_t *codes_host, const float *dbnorms_host, const float *cbnorms_host, int hn,
+                               int64_t n, int code_base, uint32_t id_offset) {
+  return index_set_wide(ix, codes_host, n, code_base, id_offset, true, dbnorms_host, cbnorms_host, hn);
+}
+
+int rq_index_aq_info(rq_index *ix, int64_t *out, int cap) {
+  if (!ix || !out || cap < 4) return fail(RQ_EINVAL, "rq_index_aq_info: bad arguments");
+  out[0] = ix->lut_mode;
+  out[1] = ix->wide ? 1 : 0;
+  out[2] = ix->h;
+  out[3] = (int64_t)ix->shards.size();
+  for (size_t s = 0; s < ix->shards.size() && 4 + 2 * (int)s + 1 < cap; ++s) {
+    out[4 + 2 * s] = ix->shards[s].perm != nullptr;
+    out[5 + 2 * s] = ix->shards[s].normb != nullptr;
+  }
+  return RQ_OK;
 }
 
 rq_index *rq_index_create(int m, int d, const float *centers_host) {

@@ -221,6 +221,24 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
                 const float *queries, int64_t n, int64_t nq, int m, int d, int k, uint32_t id_offset,
                 int id_base, hipStream_t stream, int lut_mode = LUT_PQ, const float *row_bias = nullptr,
                 const ScanBase *base = nullptr);
+// One resident base of byte codes of an additive quantizer (h = 256) on the current device, as dev_linscan wants it: rows padded to
+// scan_padded_m(m), in bank-aware order when that pays (INDEX_ORDER / order_pays), the LSQ norms BY POSITION (gathered through
+// perm) and the pre-filter's norm buffer prepared once.  rq_lsq_prepare holds one, an AQ index handle one per shard (rq_index.hip).
+struct AqBase {
+  uint8_t *codes = nullptr;      // [n][mp] in arrival order; freed once the ordered copy stands
+  float *norms = nullptr;        // LSQ: [n]
+  uint8_t *normb = nullptr;      // prepared norm buffer (lsq_norm_bytes) or nullptr where the filter does not apply
+  void *ordered = nullptr;       // order_base's allocation: ocodes + perm
+  const uint8_t *ocodes = nullptr;
+  const uint32_t *perm = nullptr;
+  const uint8_t *rows() const { return perm ? ocodes : codes; }
+};
+// codes [n][m], dbnorms [n] and cbnorms [hn] are HOST arrays, cb [m * 256][d] is on the device.  LSQ (lsq = true) takes dbnorms, or
+// (dbnorms null) computes cbnorms[quantize_norms(|sum_k C_k[b_k]|^2)] from the uploaded rows; CQ takes neither.  Launches go to
+// `stream`, which is idle when the call returns; on an error *b holds what was allocated so far (aq_base_free).
+int aq_base_prepare(AqBase *b, const uint8_t *codes, const float *cb, const float *dbnorms, const float *cbnorms, int hn, int64_t n,
+                    int m, int d, bool lsq, hipStream_t stream);
+void aq_base_free(AqBase *b);
 bool order_pays(int64_t n, int64_t nq, int k);                          // SCAN_ORDER / ORDER_MIN_ROWS / ORDER_MIN_NQ / ORDER_MAX_K
 size_t order_base_bytes(int64_t n, int mp);
 // `batch` of the order planner: the number of queries of the ONE scan the ordering serves (the greedy balance runs only where

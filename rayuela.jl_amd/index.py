@@ -121,6 +121,141 @@ class IndexU16(Index):
         raise NotImplementedError("synthetic bases are byte codes (Index.set_codes_synth)")
 
 
+AQ_KINDS = {"lsq": 1, "cq": 2}      # lut_mode of rq_index_create_aq (the values of rq_dev_linscan_aq)
+
+
+class AqIndex(Index):
+    """The index of an additive quantizer over byte codes (rq_index_create_aq, h = 256): LSQ / LSQ++ codes with their database
+    norms (kind="lsq") or ChainQ-style codes searched with T = |q - c|^2 (kind="cq"), resident on one device or row-sharded like
+    Index.  search returns what linscan_lsq / linscan_cq return on the whole base, bit for bit; close and the context manager are
+    Index's."""
+
+    WIDE = False
+    M_MAX = 64
+    HN_MAX = 256
+
+    def __init__(self, C_list, kind="lsq", devices=None):
+        """C_list: the m (256, d) full-dimensional codebooks; devices as for Index."""
+        cb = self._check_create(C_list, kind)
+        lib = _lib.lib()
+        devs, ndev = None, 0
+        if devices is not None:
+            ndev = len(devices)
+            devs = C.cast((C.c_int * ndev)(*[int(x) for x in devices]), C.c_void_p)
+        if self.WIDE:
+            self._h = lib.rq_index_create_aq_wide(self.m, self.h, self.d, cb.ctypes.data, AQ_KINDS[kind], devs, ndev)
+        else:
+            self._h = lib.rq_index_create_aq(self.m, self.d, cb.ctypes.data, AQ_KINDS[kind], devs, ndev)
+        if not self._h:
+            raise _lib.RayuelaHipError("rq_index_create_aq: " + lib.rq_last_error().decode("utf-8", "replace"))
+        self.n = 0
+
+    def _check_create(self, C_list, kind):
+        """Shape checks of the constructor (no library call): sets m, h, d, kind; returns hcat(C...) [m*h][d] float32."""
+        if kind not in AQ_KINDS:
+            raise ValueError("kind must be 'lsq' or 'cq'; got %r" % (kind,))
+        m = len(C_list)
+        if m < 1 or m > self.M_MAX:
+            raise ValueError("the %s AQ index covers 1 <= m <= %d codebooks; got %d" % ("wide" if self.WIDE else "byte", self.M_MAX, m))
+        first = np.asarray(C_list[0])
+        if first.ndim != 2 or first.shape[1] < 1:
+            raise ValueError("codebooks must be (h, d) matrices; got %s" % (first.shape,))
+        d = first.shape[1]
+        if self.WIDE:
+            from .Linscan import _hcat_wide
+            cb = _hcat_wide(C_list, d)
+            h = cb.shape[1]
+        else:
+            from .Linscan import _hcat
+            cb = _hcat(C_list, m, d)
+            h = 256
+        self.m, self.h, self.d, self.kind = m, h, d, kind
+        return cb
+
+    def _check_norms(self, n, dbnorms, cbnorms):
+        """(dbnorms [n] f32 or None, cbnorms [hn] f32 or None) as the library wants them, or ValueError (no library call)."""
+        if self.kind == "cq":
+            if dbnorms is not None or cbnorms is not None:
+                raise ValueError("a CQ index takes no norms")
+            return None, None
+        if (dbnorms is None) == (cbnorms is None):
+            raise ValueError("an LSQ index takes exactly one of dbnorms and cbnorms")
+        if dbnorms is not None:
+            nrm = np.ascontiguousarray(dbnorms, dtype=np.float32)
+            if nrm.shape != (n,):
+                raise ValueError("dbnorms must have one entry per database row")
+            return nrm, None
+        cbn = np.ascontiguousarray(_as_f32(cbnorms, "cbnorms").reshape(-1))
+        if cbn.shape[0] < 1 or cbn.shape[0] > self.HN_MAX:
+            raise ValueError("cbnorms must hold 1..%d entries; got %d" % (self.HN_MAX, cbn.shape[0]))
+        return None, cbn
+
+    def _check_codes(self, B):
+        Bu = _codes_u8(B)
+        if Bu.ndim != 2 or Bu.shape[1] != self.m:
+            raise ValueError("codes must be (n, m=%d)" % self.m)
+        if Bu.shape[0] < 1:
+            raise ValueError("codes must hold at least one row")
+        return Bu, 0
+
+    def set_codes(self, B, dbnorms=None, cbnorms=None, id_offset=0):
+        """B (n, m): uint8 zero-based codes, or another integer dtype holding ONE-based codes.  kind="lsq" takes exactly one of
+        dbnorms (n,) and cbnorms (hn <= 256,): with cbnorms, dbnorms = cbnorms[quantize_norms(B, C, cbnorms)] is computed on the
+        devices.  kind="cq" takes neither.  Replaces the previous base and its norms."""
+        Bc, base = self._check_codes(B)
+        n = Bc.shape[0]
+        nrm, cbn = self._check_norms(n, dbnorms, cbnorms)
+        pn = None if nrm is None else nrm.ctypes.data
+        pc = None if cbn is None else cbn.ctypes.data
+        hn = 0 if cbn is None else cbn.shape[0]
+        if self.WIDE:
+            _lib.check(_lib.lib().rq_index_set_codes_aq_wide(self._h, Bc.ctypes.data, pn, pc, hn, n, base, id_offset))
+        else:
+            _lib.check(_lib.lib().rq_index_set_codes_aq(self._h, Bc.ctypes.data, pn, pc, hn, n, id_offset))
+        self.n = n
+        return self
+
+    def set_codes_synth(self, n, seed, id_offset=0):
+        raise NotImplementedError("synthetic bases are PQ codes (Index.set_codes_synth)")
+
+    def search(self, X, k=10000, R=None, id_base=1):
+        """linscan_lsq(B, X, C, dbnorms, R, k) / linscan_cq(B, X, C, k) against the resident base: (dists, idx)."""
+        if R is not None and np.shape(R) != (self.d, self.d):
+            raise ValueError("R must be (d, d) = (%d, %d)" % (self.d, self.d))
+        if np.ndim(X) != 2:
+            raise ValueError("queries must be an (nq, d) matrix")
+        return Index.search(self, X, k, R, id_base)
+
+    def info(self):
+        """Index.info() plus kind, h and per shard: ordered (rows in bank-aware order) and prepared (holds the LSQ pre-filter's
+        norm buffer)."""
+        out = Index.info(self)
+        aq = (C.c_int64 * 132)()
+        _lib.check(_lib.lib().rq_index_aq_info(self._h, C.cast(aq, C.c_void_p), 132))
+        P = int(aq[3])
+        out.update(kind={1: "lsq", 2: "cq"}.get(int(aq[0]), "pq"), wide=bool(aq[1]), h=int(aq[2]),
+                   ordered=[bool(aq[4 + 2 * i]) for i in range(min(P, 64))],
+                   prepared=[bool(aq[5 + 2 * i]) for i in range(min(P, 64))])
+        return out
+
+
+class AqIndexU16(AqIndex):
+    """AqIndex over 16-bit codes (rq_index_create_aq_wide): codebooks of any 1 <= h <= 32767 codewords, 1 <= m <= 32.  search
+    returns what linscan_lsq_u16 / linscan_cq_u16 / linscan_lsq_cbnorms_u16 return on the whole base, bit for bit."""
+
+    WIDE = True
+    M_MAX = 32
+    HN_MAX = 32767
+
+    def _check_codes(self, B):
+        Bi, base = _codes_i16(B, self.h)
+        if Bi.shape[1] != self.m:
+            raise ValueError("codes must be (n, m=%d)" % self.m)
+        if Bi.shape[0] < 1:
+            raise ValueError("codes must hold at least one row")
+        return Bi, base
+
+
 class Dataset:
     """A base set resident on the device (rq_dataset_*): uploaded once, encoded as often as needed.  X float32, or uint8
     (bvecs data), which stays n * d bytes on the device and encodes to the codes of X.astype(float32)."""
