@@ -479,6 +479,80 @@ int order_base(const uint8_t **out_codes, const uint32_t **out_perm, void *dst, 
   return RQ_OK;
 }
 
+// The base is resident for many searches: its rows go in bank-aware order ONCE (rq_order.hip; the scan's table gathers then hit
+// distinct LDS columns, keys still carry the original row numbers through perm), the norms are permuted alike -- row_bias and the
+// filter's norm bytes are indexed by POSITION in the kernel.  Costs 4 bytes per row for perm; the arrival-order copy is freed.
+int resident_order(ResidentBase *b, int64_t n, int mp, hipStream_t stream) {
+  if (!tuning("INDEX_ORDER", 1) || !order_pays(n, 0, 0)) return RQ_OK;
+  auto idle = [&]() { return stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize(); };
+  void *ord = nullptr;
+  float *pn = nullptr;      // the norms by position
+  const uint8_t *oc = nullptr;
+  const uint32_t *op = nullptr;
+  const int rc = [&]() -> int {
+    RQ_HIP(hipMalloc(&ord, order_base_bytes(n, mp)));
+    RQ_TRY(order_base(&oc, &op, ord, b->rows(), n, mp, ORDER_ONCE, stream));
+    if (!op) return RQ_OK;      // too few rows for a key: nothing was queued, the base stays as it is
+    if (b->norms) {
+      RQ_HIP(hipMalloc((void **)&pn, (size_t)n * 4));
+      RQ_TRY(gather_f32_launch(pn, b->norms, op, n, stream));
+    }
+    RQ_HIP(idle());
+    return RQ_OK;
+  }();
+  if (rc == RQ_OK && op) {
+    (void)hipFree(b->mem);
+    b->mem = ord; b->rowp = oc; b->perm = op;
+    if (pn) { (void)hipFree(b->norms); b->norms = pn; }
+    return RQ_OK;
+  }
+  if (rc != RQ_OK) (void)idle();      // what was queued may still write the copies
+  if (ord) (void)hipFree(ord);
+  if (pn) (void)hipFree(pn);
+  // only "no memory" is forgiven (set_codes does not fail for want of memory for an optimisation); a launch or synchronisation
+  // error of the ordering kernels is a device fault and is returned (it used to be swallowed and reported as RQ_OK)
+  if (is_oom(rc)) { forgive_oom(); return RQ_OK; }
+  return rc;
+}
+
+int aq_base_prepare(ResidentBase *b, const uint8_t *codes, const float *cb, const float *dbnorms, const float *cbnorms, int hn,
+                    int64_t n, int m, int d, bool lsq, hipStream_t stream) {
+  const int mp = scan_padded_m(m);
+  auto idle = [&]() { return stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize(); };
+  uint8_t *rows = nullptr;      // [n][mp] in arrival order
+  RQ_HIP(hipMalloc((void **)&rows, (size_t)n * mp));
+  b->adopt_rows(rows);
+  if (lsq) RQ_HIP(hipMalloc((void **)&b->norms, (size_t)n * 4));
+  if (lsq && dbnorms) RQ_HIP(hipMemcpy(b->norms, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
+  {
+    DevBuf raw;
+    const uint8_t *rawc = rows;      // the [n][m] rows as uploaded
+    if (mp == m) {
+      RQ_HIP(hipMemcpy(rows, codes, (size_t)n * m, hipMemcpyHostToDevice));
+    } else {
+      RQ_TRY(raw.alloc((size_t)n * m));
+      RQ_HIP(hipMemcpy(raw.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
+      RQ_TRY(pad_codes_launch(rows, raw.as<uint8_t>(), n, m, mp, stream));
+      rawc = raw.as<uint8_t>();
+    }
+    if (lsq && !dbnorms) {
+      DevBuf dcbn, dsq;
+      RQ_TRY(dcbn.alloc((size_t)hn * 4)); RQ_TRY(dsq.alloc((size_t)n * 4));
+      RQ_HIP(hipMemcpy(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
+      RQ_TRY(aq_norms_launch(dsq.as<float>(), rawc, cb, n, d, m, 256, stream));
+      RQ_TRY(quantize_norms_launch((uint8_t *)nullptr, b->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, stream));
+    }
+    RQ_HIP(idle());       // before the scratch of this block goes back
+  }
+  RQ_TRY(resident_order(b, n, mp, stream));
+  if (lsq && (mp == 8 || mp == 16) && tuning("SCAN_FILTER", 1) && tuning("SCAN_FILTER_LSQ", 1)) {
+    RQ_HIP(hipMalloc((void **)&b->normb, lsq_norm_bytes(n)));
+    RQ_TRY(lsq_norm_prepare(b->normb, b->rows(), cb, b->norms, n, mp, m, d, stream));
+    RQ_HIP(idle());
+  }
+  return RQ_OK;
+}
+
 // The uncached in-call order: a scratch copy ordered by every call.  It writes the buffer of the kept order, so that one is
 // declared unbuilt first (in stream order).
 static int order_in_call(const uint8_t **ocodes, const uint32_t **operm, const uint8_t *codes, int64_t n, int mp, int64_t nq,
@@ -1234,89 +1308,12 @@ int rq_linscan_lsq(float *dists, uint32_t *ids, const uint8_t *codes, const floa
 }
 
 // ---- linscan_lsq over a PREPARED base: codes, norms, codebooks resident, the filter's O(n) preprocessing done once ---------
-extern "C++" {
-namespace rq {
-void aq_base_free(AqBase *b) {
-  if (b->codes) (void)hipFree(b->codes);
-  if (b->norms) (void)hipFree(b->norms);
-  if (b->normb) (void)hipFree(b->normb);
-  if (b->ordered) (void)hipFree(b->ordered);
-  *b = AqBase();
-}
-
-int aq_base_prepare(AqBase *b, const uint8_t *codes, const float *cb, const float *dbnorms, const float *cbnorms, int hn, int64_t n,
-                    int m, int d, bool lsq, hipStream_t stream) {
-  const int mp = scan_padded_m(m);
-  auto idle = [&]() { return stream ? hipStreamSynchronize(stream) : hipDeviceSynchronize(); };
-  RQ_HIP(hipMalloc((void **)&b->codes, (size_t)n * mp));
-  if (lsq) RQ_HIP(hipMalloc((void **)&b->norms, (size_t)n * 4));
-  if (lsq && dbnorms) RQ_HIP(hipMemcpy(b->norms, dbnorms, (size_t)n * 4, hipMemcpyHostToDevice));
-  {
-    DevBuf raw;
-    const uint8_t *rawc = b->codes;      // the [n][m] rows as uploaded
-    if (mp == m) {
-      RQ_HIP(hipMemcpy(b->codes, codes, (size_t)n * m, hipMemcpyHostToDevice));
-    } else {
-      RQ_TRY(raw.alloc((size_t)n * m));
-      RQ_HIP(hipMemcpy(raw.p, codes, (size_t)n * m, hipMemcpyHostToDevice));
-      RQ_TRY(pad_codes_launch(b->codes, raw.as<uint8_t>(), n, m, mp, stream));
-      rawc = raw.as<uint8_t>();
-    }
-    if (lsq && !dbnorms) {
-      DevBuf dcbn, dsq;
-      RQ_TRY(dcbn.alloc((size_t)hn * 4)); RQ_TRY(dsq.alloc((size_t)n * 4));
-      RQ_HIP(hipMemcpy(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice));
-      RQ_TRY(aq_norms_launch(dsq.as<float>(), rawc, cb, n, d, m, 256, stream));
-      RQ_TRY(quantize_norms_launch((uint8_t *)nullptr, b->norms, dsq.as<float>(), dcbn.as<float>(), n, hn, stream));
-    }
-    RQ_HIP(idle());       // before the scratch of this block goes back
-  }
-  // the base is resident: bank-aware row order once (rq_order.hip), norms permuted alike -- row_bias and the filter's
-  // norm bytes are indexed by POSITION in the kernel, ids come from perm
-  // (an ordered copy that cannot be allocated or built leaves the base in arrival order: slower gathers, same answer)
-  if (tuning("INDEX_ORDER", 1) && order_pays(n, 0, 0) && hipMalloc(&b->ordered, order_base_bytes(n, mp)) != hipSuccess) {
-    (void)hipGetLastError();      // out of memory: the base stays in arrival order
-    b->ordered = nullptr;
-  }
-  if (b->ordered) {
-    const int orc = order_base(&b->ocodes, &b->perm, b->ordered, b->codes, n, mp, ORDER_ONCE, stream);
-    if (is_oom(orc)) { forgive_oom(); b->perm = nullptr; }      // (the key scratch)
-    else if (orc != RQ_OK) return orc;                           // launch errors surface
-    if (b->perm) {
-      if (lsq) {
-        float *pn = nullptr;
-        RQ_HIP(hipMalloc((void **)&pn, (size_t)n * 4));
-        const int grc = gather_f32_launch(pn, b->norms, b->perm, n, stream);
-        if (grc != RQ_OK) { (void)hipFree(pn); return grc; }
-        RQ_HIP(idle());
-        RQ_HIP(hipFree(b->norms));
-        b->norms = pn;
-      } else {
-        RQ_HIP(idle());
-      }
-      RQ_HIP(hipFree(b->codes));
-      b->codes = nullptr;
-    } else {
-      RQ_HIP(hipFree(b->ordered));
-      b->ordered = nullptr;
-    }
-  }
-  if (lsq && (mp == 8 || mp == 16) && tuning("SCAN_FILTER", 1) && tuning("SCAN_FILTER_LSQ", 1)) {
-    RQ_HIP(hipMalloc((void **)&b->normb, lsq_norm_bytes(n)));
-    RQ_TRY(lsq_norm_prepare(b->normb, b->rows(), cb, b->norms, n, mp, m, d, stream));
-    RQ_HIP(idle());
-  }
-  return RQ_OK;
-}
-}  // namespace rq
-}  // extern "C++"
-
 struct rq_lsq_index_impl {
   int device = 0;
   int64_t n = 0;
   int m = 0, mp = 0, d = 0;
   float *cb = nullptr;
-  AqBase base;      // [n][mp] rows (zero-padded to a tiled row width), norms and the prepared norm buffer
+  ResidentBase base;      // [n][mp] rows (zero-padded to a tiled row width), norms and the prepared norm buffer
 };
 
 static void lsq_free(rq_lsq_index_impl *ix) {
@@ -1326,7 +1323,7 @@ static void lsq_free(rq_lsq_index_impl *ix) {
   if (hipSetDevice(ix->device) == hipSuccess) {
     (void)hipDeviceSynchronize();
     if (ix->cb) (void)hipFree(ix->cb);
-    aq_base_free(&ix->base);
+    ix->base.free();
   }
   if (have) (void)hipSetDevice(cur);
   (void)hipGetLastError();

@@ -25,6 +25,14 @@
 //
 // The same handle serves the additive quantizers (rq_index_create_aq[_wide]): full-dimensional codebooks,
 // per-shard row norms for linscan_lsq, the shard scans of rq_linscan_lsq / rq_linscan_cq and their forms over 16-bit codes.
+//
+// What a shard keeps on its device is one ResidentBase (rq_internal.h), freed in one place (its free()) and
+// ordered in one place (resident_order, rq_api.hip).  The three setters open alike (set_open: every refusal on the arguments, the
+// row split computed without writing the index) and replace the loaded base by one of two rules (index_replace_base):
+//   rq_index_set_codes[_synth], _aq     the loaded base is freed FIRST (a base and its replacement need not fit together), then
+//                                       the shards are built one by one; an error half-way leaves "index has no codes"
+//   rq_index_set_codes_wide, _aq_wide   the new rows (and norms) are validated in fresh allocations first and replace the loaded
+//                                       ones together; a refused base leaves the loaded one answering
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 #include <stdlib.h>
@@ -128,11 +136,8 @@ struct IxDev {          // one per DISTINCT device of the index
 struct IxShard {
   int dev = 0;          // index into devs
   int64_t row0 = 0, n = 0;
-  uint8_t *codes = nullptr;   // the shard's rows -- in bank-aware order when perm != nullptr (rq_order.hip); a wide index
-                              // (rq_index_create_wide) keeps int16 rows here, in arrival order
-  const uint32_t *perm = nullptr;   // position -> row of the shard (inside the `codes` allocation)
-  float *norms = nullptr;     // AQ index, LSQ: the shard's row norms (dbnorms [row0, row0 + n)) -- BY POSITION when perm != nullptr
-  uint8_t *normb = nullptr;   // byte LSQ shard: the pre-filter's prepared norm buffer (lsq_norm_prepare), where the filter applies
+  ResidentBase base;    // the shard's rows (a wide index keeps int16 rows, in arrival order), perm, and for an LSQ shard the norms
+                        // of rows [row0, row0 + n) and the prepared norm buffer (rq_internal.h)
   uint64_t *keys = nullptr;   // [nq][k] sorted keys of the last search (shards off the root device)
   size_t keys_cap = 0;
   uint64_t *tmp = nullptr;    // [nq][k_local] when the shard holds fewer than k rows
@@ -187,9 +192,7 @@ static void index_free(rq_index *ix) {
       if (ix->comms[i]) (void)g_rccl.CommDestroy(ix->comms[i]);
   for (auto &s : ix->shards) {
     if (hipSetDevice(ix->devs[s.dev].device) != hipSuccess) continue;
-    if (s.codes) (void)hipFree(s.codes);
-    if (s.norms) (void)hipFree(s.norms);
-    if (s.normb) (void)hipFree(s.normb);
+    s.base.free();
     if (s.keys) (void)hipFree(s.keys);
     if (s.tmp) (void)hipFree(s.tmp);
   }
@@ -296,65 +299,95 @@ static int index_build(rq_index *ix, int m, int d, const float *centers_host, co
   return RQ_OK;
 }
 
-static void shard_bounds(rq_index *ix, int64_t n) {
-  const int64_t P = (int64_t)ix->shards.size(), per = n / P, extra = n % P;
+// The split of a base of n rows over P shards: shard s holds rows [row0, row0 + n), the first n % P shards one row more than the
+// rest.  Nothing of an index is written: a setter commits the bounds (index_replace_base) once it can no longer refuse the call.
+struct RowSpan { int64_t row0 = 0, n = 0; };
+static std::vector<RowSpan> shard_bounds(size_t P, int64_t n) {
+  std::vector<RowSpan> split(P);
+  const int64_t per = n / (int64_t)P, extra = n % (int64_t)P;
   int64_t row = 0;
-  for (int64_t s = 0; s < P; ++s) {
-    ix->shards[s].row0 = row;
-    ix->shards[s].n = per + (s < extra ? 1 : 0);
-    row += ix->shards[s].n;
+  for (size_t s = 0; s < P; ++s) {
+    split[s].row0 = row;
+    split[s].n = per + ((int64_t)s < extra ? 1 : 0);
+    row += split[s].n;
   }
+  return split;
 }
 
-// (re)allocate every shard's code array for a base of n rows; fill(shard, stream) queues the upload / generator
-template <class Fill>
-static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
+// The opening of the three setters: everything a call is refused for on its arguments, with nothing of the index written and no
+// device touched.  aq, wide: the kind and the row width of index that the setter serves (the message names the setter of the index
+// that was passed); who: the entry's name in its messages -- null for rq_index_set_codes[_synth], which say "index" and have looked
+// at their codes themselves.  *split: the rows of every shard.
+static int set_open(std::vector<RowSpan> *split, rq_index *ix, const char *who, bool aq, bool wide, const void *codes_host,
+                    const float *dbnorms, const float *cbnorms, int hn, int64_t n, uint32_t id_offset, int code_base) {
   if (!ix) return fail(RQ_EINVAL, "index is NULL");
-  if (ix->lut_mode != LUT_PQ)
-    return fail(RQ_EINVAL, "index: an additive-quantizer index takes its codes through rq_index_set_codes_aq%s", ix->wide ? "_wide" : "");
-  if (ix->wide) return fail(RQ_EINVAL, "index: a wide index takes its codes through rq_index_set_codes_wide");
+  const bool ix_aq = ix->lut_mode != LUT_PQ;
+  if (ix_aq != aq || ix->wide != wide)      // the kind before the width
+    return fail(RQ_EINVAL, "%s: %s index takes its codes through rq_index_set_codes%s%s", who ? who : "index",
+                ix_aq != aq ? (ix_aq ? "an additive-quantizer" : "a PQ") : (ix->wide ? "a wide" : "a byte"), ix_aq ? "_aq" : "",
+                ix->wide ? "_wide" : "");
+  if (who && !codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
+  // a norm argument that does not fit lut_mode
+  if (ix->lut_mode == LUT_CQ && (dbnorms || cbnorms)) return fail(RQ_EINVAL, "%s: a CQ index takes no norms (T = |q - c|^2 holds them)", who);
+  if (ix->lut_mode == LUT_LSQ) {
+    if (!dbnorms == !cbnorms) return fail(RQ_EINVAL, "%s: an LSQ index takes exactly one of dbnorms [n] and cbnorms [hn]", who);
+    const int hn_max = wide ? RQ_MAX_H16 : 256;
+    if (cbnorms && (hn < 1 || hn > hn_max)) return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, hn, hn_max);
+    if (cbnorms && ix->h < 2) return fail(RQ_EINVAL, "%s: the norms need 2 <= h; got h=%d", who, ix->h);   // (rq_linscan_lsq_cbnorms_wide's rule)
+  }
+  if (wide && code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
   if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
   // same bound as dev_linscan: the last id must stay below 0xFFFFFFFF (that id is the padding key KEY_MAX's)
   if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "index: row ids overflow uint32 (id_offset + n must be <= 2^32 - 1)");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  SavedDevice saved;
-  shard_bounds(ix, n);
-  for (auto &s : ix->shards)
-    if (s.n >= (1LL << 31)) return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)s.n);
-  for (auto &s : ix->shards) {
+  *split = shard_bounds(ix->shards.size(), n);
+  if (split->front().n >= (1LL << 31))      // (the first shard is a largest one)
+    return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)split->front().n);
+  return RQ_OK;
+}
+
+// The loaded base goes and the new row bounds stand: the index reports "index has no codes" until its setter has seen every shard
+// stand and sets ix->n.  fresh == nullptr (the byte setters): the shards are left empty, to be built one by one -- a base and its
+// replacement need not fit together, and an error half-way (a device fault, no memory for a shard) leaves the index without codes.
+// Else (the wide setter) every shard takes over its validated replacement.
+static int index_replace_base(rq_index *ix, const std::vector<RowSpan> &split, std::vector<ResidentBase> *fresh = nullptr) {
+  ix->n = 0;
+  for (size_t i = 0; i < ix->shards.size(); ++i) {
+    IxShard &s = ix->shards[i];
     IxDev &dv = ix->devs[s.dev];
     RQ_HIP(hipSetDevice(dv.device));
-    if (s.codes) { RQ_HIP(hipStreamSynchronize(dv.stream)); RQ_HIP(hipFree(s.codes)); s.codes = nullptr; }
-    s.perm = nullptr;
+    if (s.base.mem) RQ_HIP(hipStreamSynchronize(dv.stream));
+    s.base.free();
+    s.row0 = split[i].row0;
+    s.n = split[i].n;
+    if (fresh) std::swap(s.base, (*fresh)[i]);
+  }
+  return RQ_OK;
+}
+
+// rq_index_set_codes[_synth]: every shard's rows are allocated for a base of n rows; fill(rows, row0, n, stream) queues the upload /
+// generator of the shard's rows.  Replace rule: index_replace_base's.
+template <class Fill>
+static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
+  std::vector<RowSpan> split;
+  RQ_TRY(set_open(&split, ix, nullptr, false, false, nullptr, nullptr, nullptr, 0, n, id_offset, 0));
+  std::lock_guard<std::mutex> lk(ix->mu);
+  SavedDevice saved;
+  RQ_TRY(index_replace_base(ix, split));
+  for (auto &s : ix->shards) {
     if (s.n == 0) continue;
-    RQ_HIP(hipMalloc((void **)&s.codes, (size_t)s.n * ix->m));
-    RQ_TRY(fill(s, dv.stream));
-    // The base is resident for many searches: put its rows in bank-aware order ONCE (rq_order.hip; the scan's table gathers
-    // then hit distinct LDS columns, keys still carry the original row numbers through perm).  Rows of a tiled width only;
-    // other widths are padded and ordered per search.  Costs 4 bytes per row for perm; the arrival-order copy is freed.
-    if (tuning("INDEX_ORDER", 1) && scan_padded_m(ix->m) == ix->m && order_pays(s.n, 0, 0)) {
+    IxDev &dv = ix->devs[s.dev];
+    RQ_HIP(hipSetDevice(dv.device));
+    uint8_t *rows = nullptr;
+    RQ_HIP(hipMalloc((void **)&rows, (size_t)s.n * ix->m));
+    s.base.adopt_rows(rows);
+    RQ_TRY(fill(rows, s.row0, s.n, dv.stream));
+    // Rows of a tiled width are ordered once, here; other widths are not padded now: they are padded and ordered per search.
+    if (scan_padded_m(ix->m) == ix->m) {
       DeviceLock order_lock;      // scratch lookup + launches of this device, like a scan
-      // (an ordered copy that cannot be ALLOCATED leaves the shard in arrival order: slower gathers, the same answer;
-      // set_codes does not fail for want of memory for an optimisation)
-      void *ord = nullptr;
-      const uint8_t *oc = nullptr;
-      const uint32_t *op = nullptr;
-      int rc = RQ_OK;
-      if (hipMalloc(&ord, order_base_bytes(s.n, ix->m)) != hipSuccess) { (void)hipGetLastError(); rc = (int)hipErrorOutOfMemory; ord = nullptr; }
-      if (rc == RQ_OK) rc = order_base(&oc, &op, ord, s.codes, s.n, ix->m, ORDER_ONCE, dv.stream);
-      if (rc == RQ_OK) { hipError_t e = hipStreamSynchronize(dv.stream); if (e != hipSuccess) rc = fail_hip(e, "order sync", __FILE__, __LINE__); }
-      if (rc == RQ_OK && op) {
-        RQ_HIP(hipFree(s.codes));
-        s.codes = (uint8_t *)ord;
-        s.perm = op;
-      } else {
-        if (ord) (void)hipFree(ord);
-        // only "no memory" is forgiven; a launch or synchronisation error of the ordering kernels is a device fault and is
-        // returned (it used to be swallowed and reported as RQ_OK)
-        if (is_oom(rc)) forgive_oom();
-        else if (rc != RQ_OK) { (void)release_stream_workspace(dv.stream); return rc; }
-      }
-      (void)release_stream_workspace(dv.stream);    // the key scratch (4 bytes per row + the histogram) is not needed again
+      const int rc = resident_order(&s.base, s.n, ix->m, dv.stream);
+      // the key scratch (4 bytes per row + the histogram) is not needed again
+      if (rc != RQ_OK || s.base.perm) (void)release_stream_workspace(dv.stream);
+      RQ_TRY(rc);
     }
   }
   for (auto &dv : ix->devs) {
@@ -366,125 +399,68 @@ static int index_set(rq_index *ix, int64_t n, uint32_t id_offset, Fill fill) {
   return RQ_OK;
 }
 
-// The wide form of index_set: int16 rows, no row order.  Every shard's new rows are uploaded to a fresh allocation and checked
-// there (prepare_codes_h16_kernel: zero-based in place, the first row with a code outside [0, h)) BEFORE anything of the index
-// is replaced, so a refused base leaves the loaded one answering as before.  Old and new rows are resident together until then.
-// What the AQ setters refuse before any work: the wrong kind or width of index, and a norm argument that does not fit lut_mode.
-static int aq_set_check(const char *who, rq_index *ix, bool wide, const void *codes_host, const float *dbnorms, const float *cbnorms,
-                        int hn) {
-  if (!ix) return fail(RQ_EINVAL, "index is NULL");
-  if (ix->lut_mode == LUT_PQ)
-    return fail(RQ_EINVAL, "%s: a PQ index takes its codes through rq_index_set_codes%s", who, ix->wide ? "_wide" : "");
-  if (ix->wide != wide)
-    return fail(RQ_EINVAL, "%s: a %s index takes its codes through rq_index_set_codes_aq%s", who, ix->wide ? "wide" : "byte",
-                ix->wide ? "_wide" : "");
-  if (!codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
-  if (ix->lut_mode == LUT_CQ) {
-    if (dbnorms || cbnorms) return fail(RQ_EINVAL, "%s: a CQ index takes no norms (T = |q - c|^2 holds them)", who);
-    return RQ_OK;
-  }
-  if (!dbnorms == !cbnorms) return fail(RQ_EINVAL, "%s: an LSQ index takes exactly one of dbnorms [n] and cbnorms [hn]", who);
-  if (cbnorms) {
-    const int hn_max = wide ? RQ_MAX_H16 : 256;
-    if (hn < 1 || hn > hn_max) return fail(RQ_EINVAL, "%s: hn=%d outside 1..%d", who, hn, hn_max);
-    if (ix->h < 2) return fail(RQ_EINVAL, "%s: the norms need 2 <= h; got h=%d", who, ix->h);   // (rq_linscan_lsq_cbnorms_wide's rule)
-  }
-  return RQ_OK;
-}
-
 // rq_index_set_codes_aq: every shard is prepared the way rq_lsq_prepare prepares its one base (aq_base_prepare, rq_api.hip) --
 // rows padded to a tiled width, bank-aware order once, the shard's norms gathered through the shard's own perm, the LSQ
-// pre-filter's norm buffer built once.  Byte codes cannot be out of range, so nothing is refused after the first shard is touched;
-// the previous base is freed first (a base and its replacement need not fit together).  An error half-way (a device fault, no
-// memory for a shard) leaves the index without codes.
+// pre-filter's norm buffer built once.  Byte codes cannot be out of range, so nothing is refused after the first shard is touched.
+// Replace rule: index_replace_base's.
 static int index_set_aq(rq_index *ix, const uint8_t *codes_host, const float *dbnorms, const float *cbnorms, int hn, int64_t n,
                         uint32_t id_offset) {
-  RQ_TRY(aq_set_check("rq_index_set_codes_aq", ix, false, codes_host, dbnorms, cbnorms, hn));
-  if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
-  if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "index: row ids overflow uint32 (id_offset + n must be <= 2^32 - 1)");
+  std::vector<RowSpan> split;
+  RQ_TRY(set_open(&split, ix, "rq_index_set_codes_aq", true, false, codes_host, dbnorms, cbnorms, hn, n, id_offset, 0));
   std::lock_guard<std::mutex> lk(ix->mu);
   SavedDevice saved;
-  const int64_t P = (int64_t)ix->shards.size();
-  if (n / P + (n % P ? 1 : 0) >= (1LL << 31))
-    return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)(n / P + 1));
-  ix->n = 0;
-  for (auto &s : ix->shards) {
-    IxDev &dv = ix->devs[s.dev];
-    RQ_HIP(hipSetDevice(dv.device));
-    if (s.codes) RQ_HIP(hipStreamSynchronize(dv.stream));
-    AqBase old;
-    old.codes = s.codes; old.norms = s.norms; old.normb = s.normb;
-    aq_base_free(&old);
-    s.codes = nullptr; s.norms = nullptr; s.normb = nullptr; s.perm = nullptr;
-  }
-  shard_bounds(ix, n);
+  RQ_TRY(index_replace_base(ix, split));
   for (auto &s : ix->shards) {
     if (s.n == 0) continue;
     IxDev &dv = ix->devs[s.dev];
     RQ_HIP(hipSetDevice(dv.device));
     DeviceLock prepare_lock;      // scratch lookup + launches of this device, like a scan
-    AqBase b;
-    const int rc = aq_base_prepare(&b, codes_host + (size_t)s.row0 * ix->m, dv.centers, dbnorms ? dbnorms + s.row0 : nullptr, cbnorms,
-                                   hn, s.n, ix->m, ix->d, ix->lut_mode == LUT_LSQ, dv.stream);
+    const int rc = aq_base_prepare(&s.base, codes_host + (size_t)s.row0 * ix->m, dv.centers, dbnorms ? dbnorms + s.row0 : nullptr,
+                                   cbnorms, hn, s.n, ix->m, ix->d, ix->lut_mode == LUT_LSQ, dv.stream);
     (void)release_stream_workspace(dv.stream);    // the order's key scratch is not needed again
-    if (rc != RQ_OK) { (void)hipStreamSynchronize(dv.stream); aq_base_free(&b); return rc; }
-    s.codes = b.perm ? (uint8_t *)b.ordered : b.codes;      // (order_base puts the ordered rows first in its allocation)
-    s.perm = b.perm;
-    s.norms = b.norms;
-    s.normb = b.normb;
+    if (rc != RQ_OK) { (void)hipStreamSynchronize(dv.stream); s.base.free(); return rc; }
   }
   ix->n = n;
   ix->id_offset = id_offset;
   return RQ_OK;
 }
 
-// The wide forms.  `aq`: rq_index_set_codes_aq_wide -- an LSQ shard's norms are uploaded (dbnorms) or computed from the shard's own
-// validated rows on the shard's device (cbnorms: aq_norms_launch + quantize_norms_launch, the arithmetic of
-// rq_linscan_lsq_cbnorms_wide) into a fresh allocation too, and replace the old ones together with the rows.
+// The wide forms of index_set / index_set_aq: int16 rows, no row order.  Every shard's new rows are uploaded to a fresh allocation
+// and checked there (prepare_codes_h16_kernel: zero-based in place, the first row with a code outside [0, h)) BEFORE anything of the
+// index is replaced, so a refused base leaves the loaded one answering as before.  Old and new rows are resident together until then.
+// `aq`: rq_index_set_codes_aq_wide -- an LSQ shard's norms are uploaded (dbnorms) or computed from the shard's own validated rows on
+// the shard's device (cbnorms: aq_norms_launch + quantize_norms_launch, the arithmetic of rq_linscan_lsq_cbnorms_wide) into a fresh
+// allocation too, and replace the old ones together with the rows.
 static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, int code_base, uint32_t id_offset, bool aq = false,
                           const float *dbnorms = nullptr, const float *cbnorms = nullptr, int hn = 0) {
   const char *who = aq ? "rq_index_set_codes_aq_wide" : "rq_index_set_codes_wide";
-  if (aq) RQ_TRY(aq_set_check(who, ix, true, codes_host, dbnorms, cbnorms, hn));
-  if (!ix) return fail(RQ_EINVAL, "index is NULL");
-  if (!aq && ix->lut_mode != LUT_PQ)
-    return fail(RQ_EINVAL, "%s: an additive-quantizer index takes its codes through rq_index_set_codes_aq%s", who, ix->wide ? "_wide" : "");
-  if (!ix->wide) return fail(RQ_EINVAL, "%s: a byte index takes its codes through rq_index_set_codes", who);
-  if (!codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
-  if (code_base != 0 && code_base != 1) return fail(RQ_EINVAL, "%s: code_base must be 0 or 1; got %d", who, code_base);
-  if (n < 1) return fail(RQ_EINVAL, "index: n=%lld must be >= 1", (long long)n);
-  if ((uint64_t)id_offset + (uint64_t)n > 0xFFFFFFFFull) return fail(RQ_EINVAL, "index: row ids overflow uint32 (id_offset + n must be <= 2^32 - 1)");
+  std::vector<RowSpan> split;
+  RQ_TRY(set_open(&split, ix, who, aq, true, codes_host, dbnorms, cbnorms, hn, n, id_offset, code_base));
   std::lock_guard<std::mutex> lk(ix->mu);
   SavedDevice saved;
   const int m = ix->m, h = ix->h;
-  const int64_t P = (int64_t)ix->shards.size(), per = n / P, extra = n % P;
-  if (per + (extra ? 1 : 0) >= (1LL << 31))
-    return fail(RQ_EUNSUPPORTED, "index: a shard of %lld rows exceeds 2^31-1; use more shards", (long long)(per + 1));
+  const size_t P = ix->shards.size();
   const bool lsq = aq && ix->lut_mode == LUT_LSQ;
-  std::vector<int16_t *> fresh((size_t)P, nullptr);
-  std::vector<float *> fresh_norms((size_t)P, nullptr);
+  std::vector<ResidentBase> fresh(P);
   auto drop = [&]() {
-    for (int64_t s = 0; s < P; ++s) {
-      if (!fresh[(size_t)s] && !fresh_norms[(size_t)s]) continue;
-      if (hipSetDevice(ix->devs[ix->shards[(size_t)s].dev].device) != hipSuccess) continue;
-      if (fresh[(size_t)s]) (void)hipFree(fresh[(size_t)s]);
-      if (fresh_norms[(size_t)s]) (void)hipFree(fresh_norms[(size_t)s]);
-    }
+    for (size_t s = 0; s < P; ++s)
+      if (fresh[s].mem && hipSetDevice(ix->devs[ix->shards[s].dev].device) == hipSuccess) fresh[s].free();
     (void)hipGetLastError();
   };
   int rc = RQ_OK;
-  int64_t row = 0;
-  for (int64_t s = 0; s < P && rc == RQ_OK; ++s) {
-    const int64_t sn = per + (s < extra ? 1 : 0), row0 = row;
-    row += sn;
+  for (size_t s = 0; s < P && rc == RQ_OK; ++s) {
+    const int64_t sn = split[s].n, row0 = split[s].row0;
     if (sn == 0) continue;
-    IxDev &dv = ix->devs[ix->shards[(size_t)s].dev];
+    IxDev &dv = ix->devs[ix->shards[s].dev];
     rc = [&]() -> int {
       RQ_HIP(hipSetDevice(dv.device));
-      RQ_HIP(hipMalloc((void **)&fresh[(size_t)s], (size_t)sn * m * 2));
+      int16_t *rows = nullptr;
+      RQ_HIP(hipMalloc((void **)&rows, (size_t)sn * m * 2));
+      fresh[s].adopt_rows(rows);
       DevMem flag;
       RQ_TRY(flag.alloc(8));
-      RQ_HIP(hipMemcpyAsync(fresh[(size_t)s], codes_host + (size_t)row0 * m, (size_t)sn * m * 2, hipMemcpyHostToDevice, dv.stream));
-      RQ_TRY(prepare_codes_h16_launch(fresh[(size_t)s], flag.as<unsigned long long>(), sn, m, h, code_base, dv.stream));
+      RQ_HIP(hipMemcpyAsync(rows, codes_host + (size_t)row0 * m, (size_t)sn * m * 2, hipMemcpyHostToDevice, dv.stream));
+      RQ_TRY(prepare_codes_h16_launch(rows, flag.as<unsigned long long>(), sn, m, h, code_base, dv.stream));
       unsigned long long first_bad = 0;
       RQ_HIP(hipMemcpyAsync(&first_bad, flag.p, 8, hipMemcpyDeviceToHost, dv.stream));
       RQ_HIP(hipStreamSynchronize(dv.stream));
@@ -495,7 +471,7 @@ static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, in
       // the shard's norms, from rows that are zero-based and in range by now
       float *nrm = nullptr;
       RQ_HIP(hipMalloc((void **)&nrm, (size_t)sn * 4));
-      fresh_norms[(size_t)s] = nrm;
+      fresh[s].norms = nrm;
       if (dbnorms) {
         RQ_HIP(hipMemcpyAsync(nrm, dbnorms + row0, (size_t)sn * 4, hipMemcpyHostToDevice, dv.stream));
         RQ_HIP(hipStreamSynchronize(dv.stream));
@@ -505,26 +481,14 @@ static int index_set_wide(rq_index *ix, const int16_t *codes_host, int64_t n, in
       RQ_TRY(dcbn.alloc((size_t)hn * 4));
       RQ_HIP(hipMemcpyAsync(dcbn.p, cbnorms, (size_t)hn * 4, hipMemcpyHostToDevice, dv.stream));
       DeviceLock norms_lock;
-      RQ_TRY(aq_norms_launch(nrm, fresh[(size_t)s], dv.centers, sn, ix->d, m, h, dv.stream));
+      RQ_TRY(aq_norms_launch(nrm, rows, dv.centers, sn, ix->d, m, h, dv.stream));
       RQ_TRY(quantize_norms_launch((int16_t *)nullptr, nrm, nrm, dcbn.as<float>(), sn, hn, dv.stream));
       RQ_HIP(hipStreamSynchronize(dv.stream));      // before the table goes back
       return RQ_OK;
     }();
   }
+  if (rc == RQ_OK) rc = index_replace_base(ix, split, &fresh);
   if (rc != RQ_OK) { drop(); return rc; }
-  shard_bounds(ix, n);
-  for (int64_t s = 0; s < P; ++s) {
-    IxShard &sh = ix->shards[(size_t)s];
-    IxDev &dv = ix->devs[sh.dev];
-    RQ_HIP(hipSetDevice(dv.device));
-    if (sh.codes) { RQ_HIP(hipStreamSynchronize(dv.stream)); RQ_HIP(hipFree(sh.codes)); }
-    sh.codes = reinterpret_cast<uint8_t *>(fresh[(size_t)s]);
-    fresh[(size_t)s] = nullptr;
-    sh.perm = nullptr;
-    if (sh.norms) RQ_HIP(hipFree(sh.norms));
-    sh.norms = fresh_norms[(size_t)s];
-    fresh_norms[(size_t)s] = nullptr;
-  }
   ix->n = n;
   ix->id_offset = id_offset;
   return RQ_OK;
@@ -593,19 +557,20 @@ int index_search(rq_index *ix, float *dists, uint32_t *ids, const float *queries
   auto scan_shard = [&](IxShard &s, IxDev &dv, float *sd, uint32_t *si, uint64_t *sk, const float *qs, int64_t nqs, int ks,
                         uint32_t id_off, int base) -> int {
     if (ix->wide) {
-      const int16_t *c16 = reinterpret_cast<const int16_t *>(s.codes);
+      const int16_t *c16 = s.base.rows16();
       if (ix->lut_mode != LUT_PQ)
-        return dev_linscan_aq_wide(sd, si, sk, c16, dv.centers, qs, s.norms, s.n, nqs, m, ix->h, d, ks, ix->lut_mode, id_off, base,
+        return dev_linscan_aq_wide(sd, si, sk, c16, dv.centers, qs, s.base.norms, s.n, nqs, m, ix->h, d, ks, ix->lut_mode, id_off, base,
                                    dv.stream);
       return dev_linscan_wide(sd, si, sk, c16, dv.centers, qs, s.n, nqs, m, ix->h, d, ks, id_off, base, dv.stream);
     }
     ScanBase sb;
-    sb.perm = s.perm;
+    sb.perm = s.base.perm;
     if (ix->lut_mode != LUT_PQ) {       // an AQ shard is an aq_base_prepare base: padded rows, the norm buffer where the filter applies
       sb.padded = true;
-      sb.norm_prepared = s.normb;
+      sb.norm_prepared = s.base.normb;
     }
-    return dev_linscan(sd, si, sk, s.codes, dv.centers, qs, s.n, nqs, m, d, ks, id_off, base, dv.stream, ix->lut_mode, s.norms, &sb);
+    return dev_linscan(sd, si, sk, s.base.rows(), dv.centers, qs, s.n, nqs, m, d, ks, id_off, base, dv.stream, ix->lut_mode,
+                       s.base.norms, &sb);
   };
   if (P == 1) {
     RQ_TRY(scan_shard(ix->shards[0], root, ix->dd, ix->di, nullptr, R_host ? root.queries_rot : root.queries, nq, k, ix->id_offset,
@@ -874,8 +839,8 @@ int rq_index_aq_info(rq_index *ix, int64_t *out, int cap) {
   out[2] = ix->h;
   out[3] = (int64_t)ix->shards.size();
   for (size_t s = 0; s < ix->shards.size() && 4 + 2 * (int)s + 1 < cap; ++s) {
-    out[4 + 2 * s] = ix->shards[s].perm != nullptr;
-    out[5 + 2 * s] = ix->shards[s].normb != nullptr;
+    out[4 + 2 * s] = ix->shards[s].base.perm != nullptr;
+    out[5 + 2 * s] = ix->shards[s].base.normb != nullptr;
   }
   return RQ_OK;
 }
@@ -888,15 +853,15 @@ rq_index *rq_index_create(int m, int d, const float *centers_host) {
 
 int rq_index_set_codes(rq_index *ix, const uint8_t *codes_host, int64_t n, uint32_t id_offset) {
   if (!codes_host) return fail(RQ_EINVAL, "index: codes is NULL");
-  return index_set(ix, n, id_offset, [&](IxShard &s, hipStream_t stream) -> int {
-    RQ_HIP(hipMemcpyAsync(s.codes, codes_host + (size_t)s.row0 * ix->m, (size_t)s.n * ix->m, hipMemcpyHostToDevice, stream));
+  return index_set(ix, n, id_offset, [&](uint8_t *rows, int64_t row0, int64_t sn, hipStream_t stream) -> int {
+    RQ_HIP(hipMemcpyAsync(rows, codes_host + (size_t)row0 * ix->m, (size_t)sn * ix->m, hipMemcpyHostToDevice, stream));
     return RQ_OK;
   });
 }
 
 int rq_index_set_codes_synth(rq_index *ix, int64_t n, uint64_t seed, uint32_t id_offset) {
-  return index_set(ix, n, id_offset, [&](IxShard &s, hipStream_t stream) -> int {
-    return synth_codes_launch(s.codes, s.n, ix->m, seed, s.row0, stream);
+  return index_set(ix, n, id_offset, [&](uint8_t *rows, int64_t row0, int64_t sn, hipStream_t stream) -> int {
+    return synth_codes_launch(rows, sn, ix->m, seed, row0, stream);
   });
 }
 

@@ -221,24 +221,39 @@ int dev_linscan(float *dists, uint32_t *ids, uint64_t *keys, const uint8_t *code
                 const float *queries, int64_t n, int64_t nq, int m, int d, int k, uint32_t id_offset,
                 int id_base, hipStream_t stream, int lut_mode = LUT_PQ, const float *row_bias = nullptr,
                 const ScanBase *base = nullptr);
-// One resident base of byte codes of an additive quantizer (h = 256) on the current device, as dev_linscan wants it: rows padded to
-// scan_padded_m(m), in bank-aware order when that pays (INDEX_ORDER / order_pays), the LSQ norms BY POSITION (gathered through
-// perm) and the pre-filter's norm buffer prepared once.  rq_lsq_prepare holds one, an AQ index handle one per shard (rq_index.hip).
-struct AqBase {
-  uint8_t *codes = nullptr;      // [n][mp] in arrival order; freed once the ordered copy stands
-  float *norms = nullptr;        // LSQ: [n]
-  uint8_t *normb = nullptr;      // prepared norm buffer (lsq_norm_bytes) or nullptr where the filter does not apply
-  void *ordered = nullptr;       // order_base's allocation: ocodes + perm
-  const uint8_t *ocodes = nullptr;
-  const uint32_t *perm = nullptr;
-  const uint8_t *rows() const { return perm ? ocodes : codes; }
+// One base resident on one device: what survives its preparation.  Every shard of an index handle embeds one (rq_index.hip: PQ and
+// AQ, byte and int16 rows) and rq_lsq_prepare holds one.  The arrival-order rows that exist only while an ordered copy is built are
+// a local of resident_order, not a member: no pointer here means different allocations on different paths.
+struct ResidentBase {
+  void *mem = nullptr;              // the ONE rows allocation: the rows as they arrived, or order_base's [ordered rows | perm]
+  const void *rowp = nullptr;       // the rows inside mem
+  const uint32_t *perm = nullptr;   // inside mem: position -> row when the rows are in bank-aware order (rq_order.hip), else null
+  float *norms = nullptr;           // LSQ: [n] row norms -- BY POSITION when perm != nullptr
+  uint8_t *normb = nullptr;         // byte LSQ: the pre-filter's prepared norm buffer (lsq_norm_bytes) where the filter applies
+  const uint8_t *rows() const { return static_cast<const uint8_t *>(rowp); }
+  const int16_t *rows16() const { return static_cast<const int16_t *>(rowp); }   // a wide base: int16 rows, perm null
+  void adopt_rows(void *allocation) { mem = allocation; rowp = allocation; perm = nullptr; }   // rows in arrival order
+  // the base's device is current and no queued work reads the base
+  void free() {
+    if (mem) (void)hipFree(mem);
+    if (norms) (void)hipFree(norms);
+    if (normb) (void)hipFree(normb);
+    *this = ResidentBase();
+  }
 };
+// Puts a resident base of [n][mp] byte rows (mp a tiled width) in bank-aware order ONCE, where that pays (INDEX_ORDER /
+// order_pays): the rows allocation becomes order_base's, the norms (when the base has any) are gathered through perm, the
+// arrival-order rows are freed.  No memory for the ordered copy, the key scratch or the gathered norms leaves the base in arrival
+// order -- slower gathers, the same answer -- and the call succeeds (forgive_oom); any other error is returned with the base as it
+// was.  The caller holds the DeviceLock and releases the stream's workspace (the key scratch) when it has no further use for it.
+int resident_order(ResidentBase *b, int64_t n, int mp, hipStream_t stream);
+// One resident base of byte codes of an additive quantizer (h = 256) on the current device, as dev_linscan wants it: rows padded to
+// scan_padded_m(m), ordered by resident_order (at every width), the pre-filter's norm buffer prepared once.
 // codes [n][m], dbnorms [n] and cbnorms [hn] are HOST arrays, cb [m * 256][d] is on the device.  LSQ (lsq = true) takes dbnorms, or
 // (dbnorms null) computes cbnorms[quantize_norms(|sum_k C_k[b_k]|^2)] from the uploaded rows; CQ takes neither.  Launches go to
-// `stream`, which is idle when the call returns; on an error *b holds what was allocated so far (aq_base_free).
-int aq_base_prepare(AqBase *b, const uint8_t *codes, const float *cb, const float *dbnorms, const float *cbnorms, int hn, int64_t n,
-                    int m, int d, bool lsq, hipStream_t stream);
-void aq_base_free(AqBase *b);
+// `stream`, which is idle when the call returns; on an error *b holds what was allocated so far (b->free()).
+int aq_base_prepare(ResidentBase *b, const uint8_t *codes, const float *cb, const float *dbnorms, const float *cbnorms, int hn,
+                    int64_t n, int m, int d, bool lsq, hipStream_t stream);
 bool order_pays(int64_t n, int64_t nq, int k);                          // SCAN_ORDER / ORDER_MIN_ROWS / ORDER_MIN_NQ / ORDER_MAX_K
 size_t order_base_bytes(int64_t n, int mp);
 // `batch` of the order planner: the number of queries of the ONE scan the ordering serves (the greedy balance runs only where

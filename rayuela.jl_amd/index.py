@@ -13,6 +13,15 @@ from .utils import _as_f32
 EXCHANGE = {0: "none", 1: "peer", 2: "rccl"}
 
 
+def _devices_arg(devices):
+    """devices (None, or a list of device ordinals, one shard per entry) as the create calls take it: (int array as a
+    pointer, or None; count).  No library call."""
+    if devices is None:
+        return None, 0
+    ndev = len(devices)
+    return C.cast((C.c_int * ndev)(*[int(x) for x in devices]), C.c_void_p), ndev
+
+
 class Index:
     def __init__(self, C_list, d, devices=None):
         """C_list: the m (256, d/m) codebooks; devices: None (current device) or a list of device ordinals,
@@ -20,12 +29,12 @@ class Index:
         m = len(C_list)
         self.m, self.d = m, d
         cen = _centers(C_list, m, d)
+        devs, ndev = _devices_arg(devices)
         lib = _lib.lib()
-        if devices is None:
+        if devs is None:
             self._h = lib.rq_index_create(m, d, cen.ctypes.data)
         else:
-            devs = (C.c_int * len(devices))(*[int(x) for x in devices])
-            self._h = lib.rq_index_create_sharded(m, d, cen.ctypes.data, C.cast(devs, C.c_void_p), len(devices))
+            self._h = lib.rq_index_create_sharded(m, d, cen.ctypes.data, devs, ndev)
         if not self._h:
             raise _lib.RayuelaHipError("rq_index_create: " + lib.rq_last_error().decode("utf-8", "replace"))
         self.n = 0
@@ -97,12 +106,12 @@ class IndexU16(Index):
         self.m, self.d = m, d
         cen = _centers_wide(C_list, m, d)
         self.h = cen.shape[1]
+        devs, ndev = _devices_arg(devices)
         lib = _lib.lib()
-        if devices is None:
+        if devs is None:
             self._h = lib.rq_index_create_wide(m, self.h, d, cen.ctypes.data)
         else:
-            devs = (C.c_int * len(devices))(*[int(x) for x in devices])
-            self._h = lib.rq_index_create_sharded_wide(m, self.h, d, cen.ctypes.data, C.cast(devs, C.c_void_p), len(devices))
+            self._h = lib.rq_index_create_sharded_wide(m, self.h, d, cen.ctypes.data, devs, ndev)
         if not self._h:
             raise _lib.RayuelaHipError("rq_index_create_wide: " + lib.rq_last_error().decode("utf-8", "replace"))
         self.n = 0
@@ -137,11 +146,8 @@ class AqIndex(Index):
     def __init__(self, C_list, kind="lsq", devices=None):
         """C_list: the m (256, d) full-dimensional codebooks; devices as for Index."""
         cb = self._check_create(C_list, kind)
+        devs, ndev = _devices_arg(devices)
         lib = _lib.lib()
-        devs, ndev = None, 0
-        if devices is not None:
-            ndev = len(devices)
-            devs = C.cast((C.c_int * ndev)(*[int(x) for x in devices]), C.c_void_p)
         if self.WIDE:
             self._h = lib.rq_index_create_aq_wide(self.m, self.h, self.d, cb.ctypes.data, AQ_KINDS[kind], devs, ndev)
         else:

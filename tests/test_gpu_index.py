@@ -1,6 +1,7 @@
 """GPU parity tests of the multi-device index behind the C ABI (rq_index_*): a base cut into several
 shards -- here LOGICAL shards of the one GPU the box has, the same code path as distinct devices up to the
 transport -- must return exactly what one scan of the whole base returns: ids and distance bits."""
+import functools
 import os
 
 import numpy as np
@@ -146,6 +147,63 @@ def test_index_argument_errors(rq):
         ix.set_codes(g["codes"], id_offset=2 ** 32 - 1 - n)
         dists, ids = ix.search(g["queries"], 10, id_base=0)
         assert np.array_equal(ids, g["ids_K10"] + np.uint32(2 ** 32 - 1 - n)) and _eq_bits(dists, g["dists_K10"])
+
+
+REPLACE_N, REPLACE_NQ, REPLACE_K = 12_345, 16, 50
+
+
+@functools.lru_cache(maxsize=None)
+def _replace_base(m):
+    """Random codebooks and queries and REPLACE_N rows of synth.random_codes; shared, never written to.  d = 32, except that
+    m = 5 takes d = 40: linscan_pq and the index need d % m == 0 (src/Linscan.jl:23)."""
+    import rayuela_jl_amd.synth as synth
+    d = 32 if 32 % m == 0 else 8 * m
+    rng = np.random.default_rng(100 + m)
+    C = [rng.standard_normal((256, d // m)).astype(np.float32) for _ in range(m)]
+    q = rng.standard_normal((REPLACE_NQ, d)).astype(np.float32)
+    return dict(C=C, d=d, q=q, codes=synth.random_codes(REPLACE_N, m, seed=REPLACE_N + m))
+
+
+def _ordered_flags(ix):
+    """Per shard: are the rows in bank-aware order?  (rq_index_aq_info answers for PQ indexes too.)"""
+    import ctypes as C
+    from rayuela_jl_amd import _lib
+    aq = (C.c_int64 * 132)()
+    _lib.check(_lib.lib().rq_index_aq_info(ix._h, C.cast(aq, C.c_void_p), 132))
+    return [bool(aq[4 + 2 * i]) for i in range(int(aq[3]))]
+
+
+@pytest.mark.parametrize("m", [8, 5])
+def test_replacing_the_base_twice(rq, m):
+    """The PQ setter replaces a base: 12_345 rows (shards of 4115 rows: ordered at m = 8, a tiled width), then 777 (259-row shards,
+    too few for a key: arrival order), then 9_000 (ordered again).  m = 5 is an untiled width, which is never ordered at set time.
+    After each set_codes the index reports the new split and flags, and answers like ONE linscan_pq over the same rows."""
+    b = _replace_base(m)
+    with switches(ORDER_MIN_ROWS=1):
+        with rq.Index(b["C"], b["d"], devices=[0, 0, 0]) as ix:
+            for n in (REPLACE_N, 777, 9_000):
+                codes = b["codes"][:n]
+                got = ix.set_codes(codes).search(b["q"], REPLACE_K)
+                info = ix.info()
+                assert info["n"] == n and info["rows_per_shard"] == [n // 3 + (s < n % 3) for s in range(3)], info
+                assert _ordered_flags(ix) == [m == 8 and n // 3 >= 1024] * 3, (m, n)
+                ref = rq.linscan_pq(codes, b["q"], b["C"], 8 * m, REPLACE_K)
+                assert np.array_equal(got[1], ref[1]) and _eq_bits(got[0], ref[0]), (m, n)
+
+
+def test_refused_set_leaves_bounds_and_base(rq):
+    """A set call that is refused on its arguments (one shard of 2^31 rows) writes nothing of the index: n, the row bounds and
+    the loaded base stay.  The bounds are asserted BEFORE the second search -- with the refused call's bounds the scan would run
+    over the 12_345-row allocation as if it held 2^31 rows."""
+    b = _replace_base(8)
+    with rq.Index(b["C"], b["d"]) as ix:
+        first = ix.set_codes(b["codes"]).search(b["q"], REPLACE_K)
+        with pytest.raises(rq.RayuelaHipError, match=r"exceeds 2\^31-1; use more shards"):
+            ix.set_codes_synth(2 ** 31, 7)
+        info = ix.info()
+        assert info["n"] == REPLACE_N and info["rows_per_shard"] == [REPLACE_N], info
+        again = ix.search(b["q"], REPLACE_K)
+    assert np.array_equal(first[1], again[1]) and _eq_bits(first[0], again[0])
 
 
 def test_env_single_device_restores_the_callers_device(rq, monkeypatch):
