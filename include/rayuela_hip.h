@@ -1039,6 +1039,44 @@ int rq_index_set_codes_aq_wide(rq_index *ix, const int16_t *codes_host, const fl
                                int hn, int64_t n, int code_base, uint32_t id_offset);
 int rq_index_aq_info(rq_index *ix, int64_t *out, int cap);
 
+/* IVFADC (Jegou, Douze, Schmid, PAMI 2011): a coarse quantizer in front of the ADC scan, so that a search reads nprobe lists
+ * instead of the whole base.  One device (the calling thread's current one at creation), byte codes with
+ * h = 256 tables as rq_linscan_pq, host pointers, synchronous.  The reference has no inverted file; every value is arithmetic this
+ * header already pins:
+ *   coarse value   v(x, j) = max(fl(fl(sa_j + sb) - 2 g_j), 0) for coarse centroid j, the encode's distance (k-ordered fmaf chains)
+ *   list(x)        the first-index argmin of v(x, .): rq_encode_pq_wide with m = 1 and h = nlist (a NaN value counts as 0 there)
+ *   probes         the nprobe smallest (v(q, j), j): ties to the lower list, a NaN value behind every number
+ *   distance       to a row of probed list p: the table and sum of rq_linscan_pq (deps/src/linscan_aqd.cpp:66-74, 85-87) for the
+ *                  query q' = q - Q[p] (one f32 subtraction per element) when by_residual, else q; a NaN distance is no neighbour
+ *   answer         the k smallest (dist, id) over the probed lists, ascending; behind them (NaN, 0xFFFFFFFF + id_base)
+ * With by_residual = 0 and nprobe = nlist the answer is bit for bit rq_linscan_pq's over the same codes, for any lists.
+ *   rq_ivf_create     coarse [nlist][d], centers [m][256][d / m]; d % m == 0, 1 <= m <= 64, 1 <= nlist <= RQ_MAX_H16, by_residual
+ *                     0 or 1; NULL (rq_last_error set) otherwise
+ *   rq_ivf_build      X [n][d]: assigns, takes residuals (by_residual: x - Q[list(x)], RVQ's stage epilogue), encodes
+ *                     (rq_encode_pq; m <= 32) and groups on the device, X in row chunks (tuning IVF_BUILD_ROWS).  Rows are grouped
+ *                     by list, inside a list in ascending id; the id of row i is i + id_offset; n + id_offset <= 2^32 - 1.  The
+ *                     loaded base is replaced only when the call has succeeded
+ *   rq_ivf_set_codes  the same from precomputed lists [n] (each < nlist, else RQ_EINVAL before anything is replaced) and codes
+ *                     [n][m] zero-based
+ *   rq_ivf_search     1 <= nprobe <= nlist, 1 <= k (any k: a short union is padded), id_base 0 or 1; dists / ids [nq][k].  A query
+ *                     whose keys (the nprobe largest lists, or k) do not fit the bulk scratch budget: RQ_EUNSUPPORTED.  No base
+ *                     loaded: RQ_EINVAL.  Tuning IVF_SEGMENT_ROWS (4096): the longest run of one list a workgroup scans;
+ *                     IVF_BATCH_QUERIES: a cap on the query batch; no answer depends on either
+ *   rq_ivf_get_lists  offsets [nlist + 1], row_ids [n] (id_offset included) and codes [n][m] in grouped order; NULL skips one
+ *   rq_ivf_info       out[0] rows, [1] nlist, [2] m, [3] d, [4] by_residual, [5] the largest list, [6] empty lists; of the last
+ *                     search: [7] keys per query (ld), [8] queries per batch, [9] work items, [10] rows scanned
+ *   rq_ivf_last_timing  milliseconds (hipEvents) of the last search: [0] probe selection, [1] item list (with its read-back),
+ *                     [2] keys kernel, [3] select chain */
+typedef struct rq_ivf rq_ivf;
+rq_ivf *rq_ivf_create(int d, int nlist, const float *coarse_host, int m, const float *centers_host, int by_residual);
+int rq_ivf_build(rq_ivf *ix, const float *X_host, int64_t n, uint32_t id_offset);
+int rq_ivf_set_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset);
+int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k, int id_base);
+int rq_ivf_get_lists(rq_ivf *ix, int64_t *offsets, uint32_t *row_ids, uint8_t *codes);
+int rq_ivf_info(rq_ivf *ix, int64_t *out, int cap);
+int rq_ivf_last_timing(rq_ivf *ix, double *ms, int cap);
+void rq_ivf_destroy(rq_ivf *ix);
+
 /* Threading: every entry point may be called from any host thread.  Library scratch is keyed by
  * (device, stream) and the launch sequences of one device are serialised internally, so concurrent
  * calls on different streams or devices do not interfere; at most 8 distinct streams per device may

@@ -26,6 +26,7 @@ export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bi
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
 export HipIndex, HipIndexU16, HipAqIndex, HipAqIndexU16, set_codes!, set_codes_synth!, search, HipDataset, quantize
+export HipIvfIndex, build!, train_ivfpq
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
 # call, linscan_pq / linscan_opq below shard B row-wise over those devices inside the library (per-device scan,
@@ -768,6 +769,77 @@ set_codes!(ix::HipIndexU16, B::Matrix{T}; id_offset::Integer=0) where T <: Integ
   set_codes!(ix, convert(Matrix{Int16}, B); code_base=1, id_offset=id_offset)
 
 search(ix::HipIndexU16, X::Matrix{Cfloat}, k::Int=10000; R::Union{Nothing,Matrix{Cfloat}}=nothing) = _index_search(ix, X, k, R)
+
+"""
+    HipIvfIndex(Q, C; by_residual=true)
+IVFADC (Jegou et al., PAMI 2011; no counterpart in the reference): `Q` holds the `d`-by-nlist coarse centroids (1 <= nlist <= 32767),
+`C` the m `d/m`-by-256 codebooks of the encoded vector -- the residual `x - Q[:, list(x)]` with `by_residual`, else `x`.
+`build!(ix, X; id_offset=0)` assigns, encodes and groups the columns of `X` on the device; `search(ix, X, nprobe, k)` scans the
+`nprobe` nearest lists of every query and returns k-by-nq `dists` and ONE-based `idx`, a union of fewer than k rows ending in
+`(NaN, 0)`.  `train_ivfpq(X, nlist, m)` gives `Q` and `C`.  include/rayuela_hip.h states the arithmetic.
+"""
+mutable struct HipIvfIndex
+  h::Ptr{Cvoid}
+  m::Int
+  d::Int
+  nlist::Int
+  function HipIvfIndex(Q::Matrix{Cfloat}, C::Vector{Matrix{Cfloat}}; by_residual::Bool=true)
+    d, nlist = size(Q)
+    m = length(C)
+    d % m == 0 || error("d=$d is not a multiple of m=$m")
+    cen = cat(C..., dims=3)
+    h = ccall((:rq_ivf_create, librayuela_hip), Ptr{Cvoid}, (Cint, Cint, Ptr{Cfloat}, Cint, Ptr{Cfloat}, Cint),
+              Cint(d), Cint(nlist), Q, Cint(m), cen, Cint(by_residual))
+    h == C_NULL && error("rq_ivf_create: " * unsafe_string(ccall((:rq_last_error, librayuela_hip), Cstring, ())))
+    ix = new(h, m, d, nlist)
+    finalizer(x -> (x.h != C_NULL && ccall((:rq_ivf_destroy, librayuela_hip), Cvoid, (Ptr{Cvoid},), x.h); x.h = C_NULL), ix)
+    return ix
+  end
+end
+
+function build!(ix::HipIvfIndex, X::Matrix{Cfloat}; id_offset::Integer=0)
+  d, n = size(X)
+  d == ix.d || error("X must have d=$(ix.d) rows")
+  _check(ccall((:rq_ivf_build, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Int64, UInt32),
+               ix.h, X, Int64(n), UInt32(id_offset)))
+  return ix
+end
+
+function search(ix::HipIvfIndex, X::Matrix{Cfloat}, nprobe::Int, k::Int)
+  d, nq = size(X)
+  d == ix.d || error("queries must have d=$(ix.d) rows")
+  1 <= nprobe <= ix.nlist || error("1 <= nprobe <= nlist=$(ix.nlist); got $nprobe")
+  dists = Matrix{Cfloat}(undef, k, nq)
+  res   = Matrix{Cuint}(undef, k, nq)
+  id_base = 1
+  _check(ccall((:rq_ivf_search, librayuela_hip), Cint,
+    (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cuint}, Ptr{Cfloat}, Int64, Cint, Cint, Cint),
+    ix.h, dists, res, X, Int64(nq), Cint(nprobe), Cint(k), Cint(id_base)))
+  return dists, res
+end
+
+"""
+    train_ivfpq(X, nlist, m; niter=25, seed=0, by_residual=true) -> Q, C
+`Q` = the nlist centroids of `train_pq(X, 1, nlist)`; `C` = `train_pq` with 256 codewords on the residuals `x - Q[:, list(x)]`
+(one stage of `quantize_rvq`, taken from rq_encode_rvq_wide), or on `X` itself without `by_residual`.
+"""
+function train_ivfpq(X::Matrix{Float32}, nlist::Integer, m::Integer; niter::Integer=25, seed::Integer=0, by_residual::Bool=true)
+  d, n = size(X)
+  Cq, _, _ = train_pq(X, 1, nlist, niter; seed=seed)
+  Q = Cq[1]
+  Xe = X
+  if by_residual
+    Xe = Matrix{Float32}(undef, d, n)
+    B = Matrix{Int16}(undef, 1, n)
+    h = nlist
+    code_base = 1
+    _check(ccall((:rq_encode_rvq_wide, librayuela_hip), Cint,
+      (Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, Cint, Ptr{UInt32}, Ptr{Cfloat}),
+      B, X, Q, Int64(n), Cint(d), Cint(1), Cint(h), Cint(code_base), C_NULL, Xe))
+  end
+  C, _, _ = train_pq(Xe, m, 256, niter; seed=seed + 1)
+  return Q, C
+end
 
 """
     HipAqIndex(C; kind=:lsq, devices=nothing)

@@ -186,6 +186,14 @@ SIGNATURES = {
     "rq_index_set_codes_aq": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _u32]),
     "rq_index_set_codes_aq_wide": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _u32]),
     "rq_index_aq_info": (_i32, [_vp, _vp, _i32]),
+    "rq_ivf_create": (_vp, [_i32, _i32, _vp, _i32, _vp, _i32]),
+    "rq_ivf_build": (_i32, [_vp, _vp, _i64, _u32]),
+    "rq_ivf_set_codes": (_i32, [_vp, _vp, _vp, _i64, _u32]),
+    "rq_ivf_search": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_ivf_get_lists": (_i32, [_vp, _vp, _vp, _vp]),
+    "rq_ivf_info": (_i32, [_vp, _vp, _i32]),
+    "rq_ivf_last_timing": (_i32, [_vp, _vp, _i32]),
+    "rq_ivf_destroy": (None, [_vp]),
     "rq_index_search_opq": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32]),
     "rq_index_info": (_i32, [_vp, _vp, _i32]),
     "rq_release_workspaces": (_i32, []),

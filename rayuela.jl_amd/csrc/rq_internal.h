@@ -334,6 +334,13 @@ void sel_grid(BulkSel &s, uint32_t cnt, int64_t nb, int num_cu, uint32_t *hx);  
 int sel_run(const BulkSel &s, uint32_t hx, int64_t nb, const BulkOut &o, hipStream_t stream);
 int merge_launch(float *dists, uint32_t *ids, uint64_t *keys_out, const uint64_t *keys_in, int64_t nq,
                  int P, int K, int id_base, hipStream_t stream);
+// ---- IVFADC (rq_ivf.hip) --------------------------------------------------------------------------------
+// The rq_ivf handle shares no entry with other files; it is built from the ones declared here: encode_h16_launch at m = 1 (the
+// list of a row), residual_launch (x - Q[list]), encode_launch and pad_codes_launch (the codes), and the chain above (sel_layout /
+// sel_grid / sel_run) three times -- as the stable sort that groups rows by list, as the probe selection (k = nprobe over one key
+// per list) and as the top-k over the keys of the probed lists.  One item of a search: rows [row0, row0 + nrows) of `list`, scanned
+// for batch query q with their keys written from offset koff of the query's row of the key buffer.
+struct IvfItem { uint32_t q, list, row0, nrows, koff; };
 // ---- ADC scan over 16-bit codes (rq_scan_h16.hip): codes [n][m] int16 zero-based, centers [m][h][d/m] ----
 // every argument check of rq_dev_linscan_wide / rq_linscan_*_wide (`who` names the entry point); no device work
 // full_dim: the additive-quantizer entries (codebooks [m * h][d], section 4.20) -- any d >= 1 instead of d % m == 0

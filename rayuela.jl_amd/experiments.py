@@ -82,6 +82,25 @@ def experiment_opq_query_base(Xt, Xq, gt, m, h, init, niter=25, knn=1000, V=Fals
     return C, B, R, train_error, recall
 
 
+def experiment_ivfpq(Xt, Xb, Xq, gt=None, nlist=1024, m=8, nprobes=(1, 8, 32), niter=25, knn=100, by_residual=True, V=False,
+                     seed=0):
+    """IVFADC (IVF.py; no counterpart in the reference): train the coarse centroids and the codebooks on Xt, build the index on
+    Xb, search Xq once per nprobe.  Returns Q, C and {nprobe: recall curve of eval_recall} -- recall against the exact nearest
+    neighbour, so it is bounded by the share of queries whose neighbour lies in a probed list."""
+    from .IVF import IvfIndex, train_ivfpq
+    Q, C = train_ivfpq(Xt, nlist, m, niter=niter, seed=seed, by_residual=by_residual)
+    truth = _gt(gt, Xb, Xq)
+    recall = {}
+    with IvfIndex(Q, C, by_residual=by_residual) as ix:
+        ix.build(Xb)
+        for nprobe in nprobes:
+            if V:
+                print("nprobe = %d" % nprobe)
+            _, idx = ix.search(Xq, nprobe, knn)
+            recall[nprobe] = eval_recall(truth, idx, knn, verbose=V)
+    return Q, C, recall
+
+
 def _norms_codebook(B, C, h=256, seed=0):
     """get_norms_codebook (src/utils.jl:4-26): norms of the reconstructions, quantised by a 1-D k-means
     (rq_train_pq with d = m = 1).  Returns (norms_codes one-based, norms_codebook (h,))."""
