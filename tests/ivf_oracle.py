@@ -13,6 +13,9 @@ against those functions where they apply.
   probes         a NaN U stays NaN and sorts behind every number, +Inf included; ties go to the lower list
   distance       oracle.adc_distances(codes of the list, C, q - Q[p] or q); a NaN distance is no neighbour; -0 counts as +0
   answer         the k smallest (dist, id), ids + id_base; then (PAD_BITS, 0xFFFFFFFF + id_base)
+
+search() is take(ranked()): ranked orders the comparable rows of every query once, take cuts any k and id_base off that order;
+search_tiled evaluates the distinct queries of a tiling once.  tests/test_ivf_oracle.py holds the three to one another.
 """
 import numpy as np
 
@@ -75,34 +78,52 @@ def build(X, Q, centers, by_residual, id_offset=0):
     return group(lists, codes, _f32(Q).shape[0], id_offset), (lists, enc, codes)
 
 
-def search(grouped, Q, centers, by_residual, Xq, nprobe, k, id_base=1):
-    """(dists [nq][k] f32, ids [nq][k] u32) of the restated search over a grouped base."""
+def ranked(grouped, Q, centers, by_residual, Xq, nprobe):
+    """Per query the comparable rows of its nprobe nearest lists in answer order: a list of (dist f32, ids u32 without id_base),
+    ascending (dist, id).  Every k and id_base of one (queries, nprobe) cuts its answer off these (take)."""
     offsets, ids, codes = grouped
     Q, centers, Xq = _f32(Q), _f32(centers), _f32(Xq)
-    nq = Xq.shape[0]
     order = probe_order(Xq, Q)[:, :nprobe]
-    out_d = np.full((nq, k), PAD_BITS, dtype=np.uint32)
-    out_i = np.full((nq, k), (PAD_ID + id_base) & 0xFFFFFFFF, dtype=np.uint32)
-    for q in range(nq):
-        dd, ii = [], []
-        for p in order[q]:
+    sizes = np.diff(offsets)
+    out = []
+    for q in range(Xq.shape[0]):
+        dd, ii = [np.empty(0, dtype=np.float32)], [np.empty(0, dtype=np.uint32)]
+        for p in order[q][sizes[order[q]] > 0]:
             b, e = int(offsets[p]), int(offsets[p + 1])
-            if e == b:
-                continue
             with np.errstate(invalid="ignore", over="ignore"):
                 qp = (Xq[q] - Q[p]).astype(np.float32) if by_residual else Xq[q]
             dd.append(oracle.adc_distances(codes[b:e], centers, qp))
             ii.append(ids[b:e])
-        if not dd:
-            continue
         dist = np.concatenate(dd) + np.float32(0)          # -0 counts as +0
         idv = np.concatenate(ii)
         keep = ~np.isnan(dist)
         dist, idv = dist[keep], idv[keep]
-        top = np.lexsort((idv, dist))[:k]
-        out_d[q, :top.size] = dist[top].view(np.uint32)
-        out_i[q, :top.size] = ((idv[top].astype(np.int64) + id_base) & 0xFFFFFFFF).astype(np.uint32)
+        top = np.lexsort((idv, dist))
+        out.append((dist[top], idv[top]))
+    return out
+
+
+def take(rows, k, id_base=1):
+    """(dists [nq][k] f32, ids [nq][k] u32): the first k entries of every query of ranked(), ids + id_base, then the padding."""
+    out_d = np.full((len(rows), k), PAD_BITS, dtype=np.uint32)
+    out_i = np.full((len(rows), k), (PAD_ID + id_base) & 0xFFFFFFFF, dtype=np.uint32)
+    for q, (dist, idv) in enumerate(rows):
+        c = min(k, dist.size)
+        out_d[q, :c] = dist[:c].view(np.uint32)
+        out_i[q, :c] = ((idv[:c].astype(np.int64) + id_base) & 0xFFFFFFFF).astype(np.uint32)
     return out_d.view(np.float32), out_i
+
+
+def search(grouped, Q, centers, by_residual, Xq, nprobe, k, id_base=1):
+    """(dists [nq][k] f32, ids [nq][k] u32) of the restated search over a grouped base."""
+    return take(ranked(grouped, Q, centers, by_residual, Xq, nprobe), k, id_base)
+
+
+def search_tiled(grouped, Q, centers, by_residual, Xd, tile, nprobe, k, id_base=1):
+    """search() for the queries Xd[tile]: a query's answer depends on no other query, so each distinct one is evaluated once."""
+    dists, ids = search(grouped, Q, centers, by_residual, Xd, nprobe, k, id_base)
+    tile = np.asarray(tile, dtype=np.int64)
+    return dists[tile], ids[tile]
 
 
 def union_sizes(grouped, Q, Xq, nprobe):
@@ -110,3 +131,9 @@ def union_sizes(grouped, Q, Xq, nprobe):
     offsets = grouped[0]
     sizes = np.diff(offsets)
     return sizes[probe_order(Xq, Q)[:, :nprobe]].sum(axis=1)
+
+
+def item_counts(grouped, Q, Xq, nprobe, segment):
+    """work items of every query: one per `segment` rows, or part of that, of each probed list (IVF_SEGMENT_ROWS)"""
+    sizes = np.diff(grouped[0])
+    return (-(-sizes // segment))[probe_order(Xq, Q)[:, :nprobe]].sum(axis=1)

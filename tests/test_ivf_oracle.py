@@ -90,6 +90,33 @@ def test_probe_order_on_equal_centroids_and_nan():
     assert np.all(ivf.lists_of(Xq, Q) <= 1)
 
 
+def test_tiled_search_and_one_ranking_for_every_k_equal_the_plain_search(oracle):
+    """The helpers of the GPU tests with many queries or many k: search_tiled on a tiling of distinct queries and take() off one
+    ranked() list are the plain search of the tiled queries, padding included; item_counts and union_sizes by hand."""
+    X, Q, centers, Xq = _small()
+    Xq = Xq.copy()
+    Xq[3, 2] = np.nan                        # a query without a comparable row: padding from slot 0
+    tile = np.random.default_rng(4).integers(0, Xq.shape[0], 23)
+    tile[:5] = np.arange(5)
+    for by_residual in (True, False):
+        grouped, _ = ivf.build(X, Q, centers, by_residual, id_offset=9)
+        for nprobe in (1, 2, 6):
+            rows = ivf.ranked(grouped, Q, centers, by_residual, Xq, nprobe)
+            for k, id_base in ((1, 0), (7, 1), (X.shape[0] + 2, 1)):
+                plain = ivf.search(grouped, Q, centers, by_residual, Xq[tile], nprobe, k, id_base)
+                tiled = ivf.search_tiled(grouped, Q, centers, by_residual, Xq, tile, nprobe, k, id_base)
+                cut = ivf.take(rows, k, id_base)
+                assert np.array_equal(plain[1], tiled[1]) and np.array_equal(_bits(plain[0]), _bits(tiled[0]))
+                assert np.array_equal(plain[1], cut[1][tile]) and np.array_equal(_bits(plain[0]), _bits(cut[0][tile]))
+                assert np.all(_bits(plain[0])[tile == 3] == ivf.PAD_BITS)
+            sizes = np.diff(grouped[0])
+            probes = ivf.probe_order(Xq, Q)[:, :nprobe]
+            for seg in (1, 7, 4096):
+                want = [sum(-(-int(sizes[p]) // seg) for p in probes[q]) for q in range(Xq.shape[0])]
+                assert ivf.item_counts(grouped, Q, Xq, nprobe, seg).tolist() == want
+            assert ivf.union_sizes(grouped, Q, Xq, nprobe).tolist() == [int(sizes[probes[q]].sum()) for q in range(Xq.shape[0])]
+
+
 def test_mirror_argument_checks_raise_before_the_library(rq):
     from rayuela_jl_amd.IVF import IvfIndex
     Q = np.zeros((4, 12), dtype=np.float32)
