@@ -1058,19 +1058,48 @@ int rq_index_aq_info(rq_index *ix, int64_t *out, int cap);
  *                     loaded base is replaced only when the call has succeeded
  *   rq_ivf_set_codes  the same from precomputed lists [n] (each < nlist, else RQ_EINVAL before anything is replaced) and codes
  *                     [n][m] zero-based
+ *   rq_ivf_build_bytes  rq_ivf_build on uint8 rows (bvecs).  A byte row MEANS the row widened to float (exact), then everything
+ *                     as for float rows: lists, residuals and codes are bit for bit those of the widened matrix.  The bytes
+ *                     travel as bytes: lists from rq_encode_pq_wide's byte form, x - Q[list] written as float straight from the
+ *                     bytes (by_residual) or the codes from rq_encode_pq_bytes (no float copy of the chunk exists).  X_host at
+ *                     any byte alignment, any d; no shape takes another route here (the byte encode's own routing by sub-space
+ *                     width applies inside it)
+ *   rq_ivf_add, rq_ivf_add_bytes, rq_ivf_add_codes   rq_ivf_build / _build_bytes / _set_codes for a batch that goes BEHIND the
+ *                     loaded base instead of replacing it.  After any sequence of one build (or set_codes) and any number of adds,
+ *                     the loaded base is the one that a single rq_ivf_build / rq_ivf_set_codes over the concatenated rows would
+ *                     load, provided that call gives row i of a piece the id i + id_offset of that piece: the same offsets, the
+ *                     same row_ids and the same code bytes in rq_ivf_get_lists, so every search answers with the same bits.
+ *                       ids      an add takes its own id_offset, at least the NEXT ID: the largest id loaded plus one (0 for an
+ *                                index with no base).  Gaps are allowed (shards of a file carry their file positions); a smaller
+ *                                id_offset is RQ_EINVAL and the message names both numbers.  So ids still ascend inside a list,
+ *                                which the search contract rests on; added rows go behind the loaded rows of their list
+ *                       limits   rows loaded + n <= 2^32 - 1 (offsets are uint32) and id_offset + n <= 2^32 - 1; m <= 32 for the
+ *                                row forms, m <= 64 for rq_ivf_add_codes; each refused before any work
+ *                       empty    an add on a handle with no base is a build (any id_offset)
+ *                       failure  the loaded base is replaced only when the call has succeeded: after a refused argument, a
+ *                                failed allocation or a list id >= nlist (RQ_EINVAL naming the row) the old base answers
+ *                       cost     one add rewrites the base once (4 + mp bytes per loaded row read and written, mp the tiled row
+ *                                width) into fresh allocations; temporaries are sized by the batch.  A search from another
+ *                                thread sees the base before or after an add, never a mixture
  *   rq_ivf_search     1 <= nprobe <= nlist, 1 <= k (any k: a short union is padded), id_base 0 or 1; dists / ids [nq][k].  A query
  *                     whose keys (the nprobe largest lists, or k) do not fit the bulk scratch budget: RQ_EUNSUPPORTED.  No base
  *                     loaded: RQ_EINVAL.  Tuning IVF_SEGMENT_ROWS (4096): the longest run of one list a workgroup scans;
  *                     IVF_BATCH_QUERIES: a cap on the query batch; no answer depends on either
  *   rq_ivf_get_lists  offsets [nlist + 1], row_ids [n] (id_offset included) and codes [n][m] in grouped order; NULL skips one
  *   rq_ivf_info       out[0] rows, [1] nlist, [2] m, [3] d, [4] by_residual, [5] the largest list, [6] empty lists; of the last
- *                     search: [7] keys per query (ld), [8] queries per batch, [9] work items, [10] rows scanned
+ *                     search: [7] keys per query (ld), [8] queries per batch, [9] work items, [10] rows scanned; [11] the next id
+ *                     (0 with no base)
  *   rq_ivf_last_timing  milliseconds (hipEvents) of the last search: [0] probe selection, [1] item list (with its read-back),
- *                     [2] keys kernel, [3] select chain */
+ *                     [2] keys kernel, [3] select chain; of the last successful build / set_codes / add: [4] uploads, assignment
+ *                     and encode, [5] grouping (sorts, bounds, offsets), [6] the carry of the loaded rows, [7] placement */
 typedef struct rq_ivf rq_ivf;
 rq_ivf *rq_ivf_create(int d, int nlist, const float *coarse_host, int m, const float *centers_host, int by_residual);
 int rq_ivf_build(rq_ivf *ix, const float *X_host, int64_t n, uint32_t id_offset);
 int rq_ivf_set_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset);
+int rq_ivf_build_bytes(rq_ivf *ix, const uint8_t *X_host, int64_t n, uint32_t id_offset);
+int rq_ivf_add(rq_ivf *ix, const float *X_host, int64_t n, uint32_t id_offset);
+int rq_ivf_add_bytes(rq_ivf *ix, const uint8_t *X_host, int64_t n, uint32_t id_offset);
+int rq_ivf_add_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset);
 int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k, int id_base);
 int rq_ivf_get_lists(rq_ivf *ix, int64_t *offsets, uint32_t *row_ids, uint8_t *codes);
 int rq_ivf_info(rq_ivf *ix, int64_t *out, int cap);

@@ -26,7 +26,7 @@ export encoding_icm, encode_icm_cuda, update_codebooks, update_codebooks_fast_bi
 export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
 export HipIndex, HipIndexU16, HipAqIndex, HipAqIndexU16, set_codes!, set_codes_synth!, search, HipDataset, quantize
-export HipIvfIndex, build!, train_ivfpq
+export HipIvfIndex, build!, add!, add_codes!, train_ivfpq
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
 # call, linscan_pq / linscan_opq below shard B row-wise over those devices inside the library (per-device scan,
@@ -802,6 +802,56 @@ function build!(ix::HipIvfIndex, X::Matrix{Cfloat}; id_offset::Integer=0)
   d == ix.d || error("X must have d=$(ix.d) rows")
   _check(ccall((:rq_ivf_build, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Int64, UInt32),
                ix.h, X, Int64(n), UInt32(id_offset)))
+  return ix
+end
+
+function build!(ix::HipIvfIndex, X::Matrix{UInt8}; id_offset::Integer=0)
+  d, n = size(X)
+  d == ix.d || error("X must have d=$(ix.d) rows")
+  _check(ccall((:rq_ivf_build_bytes, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int64, UInt32),
+               ix.h, X, Int64(n), UInt32(id_offset)))
+  return ix
+end
+
+# the least id_offset an add may take: the largest id loaded plus one, 0 for an index with no base
+function _ivf_next_id(ix::HipIvfIndex)
+  out = zeros(Int64, 12)
+  cap = length(out)
+  _check(ccall((:rq_ivf_info, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{Int64}, Cint), ix.h, out, Cint(cap)))
+  return out[12]
+end
+
+"""
+    add!(ix, X; id_offset=nothing)
+    add_codes!(ix, lists, B; id_offset=nothing)
+Put the columns of `X` (`Matrix{Cfloat}` or `Matrix{UInt8}`), or rows given as zero-based `lists` and m-by-n zero-based codes `B`,
+BEHIND the loaded base of a `HipIvfIndex`: afterwards the index holds what one `build!` of all columns would have loaded.
+`id_offset` (`nothing`: the next id) must not lie below the largest id loaded plus one; gaps are allowed.
+"""
+function add!(ix::HipIvfIndex, X::Matrix{Cfloat}; id_offset::Union{Nothing,Integer}=nothing)
+  d, n = size(X)
+  d == ix.d || error("X must have d=$(ix.d) rows")
+  id_offset = id_offset === nothing ? _ivf_next_id(ix) : id_offset
+  _check(ccall((:rq_ivf_add, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Int64, UInt32),
+               ix.h, X, Int64(n), UInt32(id_offset)))
+  return ix
+end
+
+function add!(ix::HipIvfIndex, X::Matrix{UInt8}; id_offset::Union{Nothing,Integer}=nothing)
+  d, n = size(X)
+  d == ix.d || error("X must have d=$(ix.d) rows")
+  id_offset = id_offset === nothing ? _ivf_next_id(ix) : id_offset
+  _check(ccall((:rq_ivf_add_bytes, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Int64, UInt32),
+               ix.h, X, Int64(n), UInt32(id_offset)))
+  return ix
+end
+
+function add_codes!(ix::HipIvfIndex, lists::Vector{UInt32}, B::Matrix{UInt8}; id_offset::Union{Nothing,Integer}=nothing)
+  m, n = size(B)
+  (m == ix.m && length(lists) == n) || error("codes must be m=$(ix.m) by n=$(length(lists))")
+  id_offset = id_offset === nothing ? _ivf_next_id(ix) : id_offset
+  _check(ccall((:rq_ivf_add_codes, librayuela_hip), Cint, (Ptr{Cvoid}, Ptr{UInt32}, Ptr{UInt8}, Int64, UInt32),
+               ix.h, lists, B, Int64(n), UInt32(id_offset)))
   return ix
 end
 

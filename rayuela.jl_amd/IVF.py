@@ -8,11 +8,14 @@ import numpy as np
 
 from . import _lib
 from .Linscan import _centers, _codes_u8
-from .utils import _as_f32
+from .utils import _as_f32, _as_f32_or_u8
 
 MAX_NLIST = 32767     # RQ_MAX_H16
-INFO_KEYS = ("n", "nlist", "m", "d", "by_residual", "largest_list", "empty_lists", "ld", "batch", "items", "rows_scanned")
-TIMING_KEYS = ("probe_ms", "items_ms", "keys_ms", "select_ms")
+INFO_KEYS = ("n", "nlist", "m", "d", "by_residual", "largest_list", "empty_lists", "ld", "batch", "items", "rows_scanned",
+             "next_id")
+TIMING_KEYS = ("probe_ms", "items_ms", "keys_ms", "select_ms",
+               # of the last build / set_codes / add: uploads + assignment + encode, grouping, carry of the loaded rows, placement
+               "load_encode_ms", "load_group_ms", "load_carry_ms", "load_place_ms")
 
 
 class IvfIndex:
@@ -31,6 +34,7 @@ class IvfIndex:
         cen = _centers(C_list, m, d)
         self.nlist, self.d, self.m, self.by_residual = nlist, d, m, bool(by_residual)
         self.n = 0
+        self.next_id = 0      # the largest id loaded plus one: the least id_offset an add may take
         lib = _lib.lib()
         self._h = lib.rq_ivf_create(d, nlist, Q.ctypes.data, m, cen.ctypes.data, int(self.by_residual))
         if not self._h:
@@ -42,6 +46,7 @@ class IvfIndex:
         the library is called) and nothing else.  What the tests use where there is no device."""
         ix = cls.__new__(cls)
         ix.nlist, ix.d, ix.m, ix.by_residual, ix.n, ix._h = nlist, d, m, bool(by_residual), 0, None
+        ix.next_id = 0
         return ix
 
     @staticmethod
@@ -51,34 +56,84 @@ class IvfIndex:
         if id_offset < 0 or n + id_offset > 0xFFFFFFFF:
             raise ValueError("n + id_offset must stay below 2^32; got %d + %d" % (n, id_offset))
 
-    def build(self, X, id_offset=0):
-        """Assign, take residuals, encode and group the rows of X (n, d) on the device; the id of row i is i + id_offset."""
-        X = _as_f32(X, "X")
+    def _rows(self, X):
+        """X as the library takes it: float32, or uint8 rows, which stay bytes (any other dtype: TypeError)."""
+        X = _as_f32_or_u8(X, "X")
         if X.ndim != 2 or X.shape[1] != self.d:
             raise ValueError("X must be (n, d=%d)" % self.d)
+        return X
+
+    def _check_add(self, n, id_offset):
+        """The id rule and the limits of an add behind self.n loaded rows; returns the id_offset to use (None: the next id)."""
+        if id_offset is None:
+            id_offset = self.next_id if self.n else 0
+        self._check_id_offset(n, id_offset)
+        if self.n:
+            if id_offset < self.next_id:
+                raise ValueError("id_offset=%d lies below the next id %d (ids ascend inside a list; gaps are allowed)"
+                                 % (id_offset, self.next_id))
+            if self.n + n > 0xFFFFFFFF:
+                raise ValueError("%d rows loaded + %d exceed 2^32 - 1 (offsets are uint32)" % (self.n, n))
+        return int(id_offset)
+
+    def _loaded(self, n, id_offset, added):
+        self.n = self.n + n if added else n
+        self.next_id = id_offset + n
+        return self
+
+    def build(self, X, id_offset=0):
+        """Assign, take residuals, encode and group the rows of X (n, d) on the device; the id of row i is i + id_offset.  X is
+        float32, or uint8 (bvecs): then the bytes travel as bytes and mean the rows widened to float32."""
+        X = self._rows(X)
         if self.m > 32:
             raise ValueError("build encodes with 1 <= m <= 32 codebooks; got %d (set_codes takes codes)" % self.m)
         self._check_id_offset(X.shape[0], id_offset)
-        _lib.check(_lib.lib().rq_ivf_build(self._h, X.ctypes.data, X.shape[0], id_offset))
-        self.n = X.shape[0]
-        return self
+        entry = _lib.lib().rq_ivf_build_bytes if X.dtype == np.uint8 else _lib.lib().rq_ivf_build
+        _lib.check(entry(self._h, X.ctypes.data, X.shape[0], id_offset))
+        return self._loaded(X.shape[0], id_offset, False)
 
-    def set_codes(self, lists, B, id_offset=0):
-        """lists (n,): the list of every row, each in [0, nlist); B (n, m): uint8 zero-based codes, or another integer dtype
-        holding ONE-based codes.  Replaces the base."""
+    def add(self, X, id_offset=None):
+        """Put the rows of X (float32 or uint8) BEHIND the loaded base: afterwards the index holds what one build of all rows
+        would have loaded.  id_offset (None: the next id, info()["next_id"]) must not lie below the next id; gaps are allowed.
+        On an index with no base this is a build."""
+        X = self._rows(X)
+        if self.m > 32:
+            raise ValueError("add encodes with 1 <= m <= 32 codebooks; got %d (add_codes takes codes)" % self.m)
+        id_offset = self._check_add(X.shape[0], id_offset)
+        entry = _lib.lib().rq_ivf_add_bytes if X.dtype == np.uint8 else _lib.lib().rq_ivf_add
+        _lib.check(entry(self._h, X.ctypes.data, X.shape[0], id_offset))
+        return self._loaded(X.shape[0], id_offset, True)
+
+    def _lists_codes(self, lists, B):
         lists = np.asarray(lists)
         if lists.ndim != 1 or not np.issubdtype(lists.dtype, np.integer):
             raise ValueError("lists must be a vector of integers")
         Bu = _codes_u8(B)
         if Bu.ndim != 2 or Bu.shape != (lists.shape[0], self.m):
             raise ValueError("codes must be (n, m) = (%d, %d); got %s" % (lists.shape[0], self.m, Bu.shape))
-        self._check_id_offset(Bu.shape[0], id_offset)
+        return lists, Bu
+
+    def _list_range(self, lists):
         if lists.min() < 0 or lists.max() >= self.nlist:
             raise ValueError("a list id lies outside [0, %d)" % self.nlist)
-        lu = np.ascontiguousarray(lists, dtype=np.uint32)
+        return np.ascontiguousarray(lists, dtype=np.uint32)
+
+    def set_codes(self, lists, B, id_offset=0):
+        """lists (n,): the list of every row, each in [0, nlist); B (n, m): uint8 zero-based codes, or another integer dtype
+        holding ONE-based codes.  Replaces the base."""
+        lists, Bu = self._lists_codes(lists, B)
+        self._check_id_offset(Bu.shape[0], id_offset)
+        lu = self._list_range(lists)
         _lib.check(_lib.lib().rq_ivf_set_codes(self._h, lu.ctypes.data, Bu.ctypes.data, Bu.shape[0], id_offset))
-        self.n = Bu.shape[0]
-        return self
+        return self._loaded(Bu.shape[0], id_offset, False)
+
+    def add_codes(self, lists, B, id_offset=None):
+        """set_codes for rows that go BEHIND the loaded base (see add)."""
+        lists, Bu = self._lists_codes(lists, B)
+        id_offset = self._check_add(Bu.shape[0], id_offset)
+        lu = self._list_range(lists)
+        _lib.check(_lib.lib().rq_ivf_add_codes(self._h, lu.ctypes.data, Bu.ctypes.data, Bu.shape[0], id_offset))
+        return self._loaded(Bu.shape[0], id_offset, True)
 
     def search(self, Xq, nprobe, k, id_base=1):
         """The k nearest rows of the nprobe nearest lists per query: (dists (nq, k) float32 ascending, ids (nq, k) uint32); a
@@ -101,9 +156,11 @@ class IvfIndex:
 
     def lists(self):
         """(offsets (nlist + 1,) int64, ids (n,) uint32 with id_offset, codes (n, m) uint8) in grouped order."""
+        n = (C.c_int64 * 1)()               # the library's own count: the base may have been loaded through the C entries
+        _lib.check(_lib.lib().rq_ivf_info(self._h, C.cast(n, C.c_void_p), 1))
         offsets = np.empty(self.nlist + 1, dtype=np.int64)
-        ids = np.empty(self.n, dtype=np.uint32)
-        codes = np.empty((self.n, self.m), dtype=np.uint8)
+        ids = np.empty(int(n[0]), dtype=np.uint32)
+        codes = np.empty((int(n[0]), self.m), dtype=np.uint8)
         _lib.check(_lib.lib().rq_ivf_get_lists(self._h, offsets.ctypes.data, ids.ctypes.data, codes.ctypes.data))
         return offsets, ids, codes
 

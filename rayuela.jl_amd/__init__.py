@@ -8,7 +8,7 @@ ABI with `ccall` live in julia/.  No CPU fallback exists: without the HIP librar
 from ._lib import RayuelaHipError, lib, lib_path, set_tuning, reset_tuning, last_timing  # noqa: F401
 from .utils import splitarray, cat_codebooks, get_norms_codebook, quantize_norms, aq_norms  # noqa: F401
 from .xvecs import (fvecs_read, ivecs_read, bvecs_read, fvecs_write, ivecs_write, bvecs_write,  # noqa: F401
-                    quantize_bvecs)
+                    quantize_bvecs, ivf_add_bvecs, ivf_add_fvecs)
 from .PQ import quantize_pq, quantize_pq_u8, quantize_pq_u16  # noqa: F401
 from .OPQ import quantize_opq, quantize_opq_u16, rotate  # noqa: F401
 from .RVQ import quantize_rvq, quantize_rvq_u8, quantize_rvq_u16  # noqa: F401

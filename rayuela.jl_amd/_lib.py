@@ -189,6 +189,10 @@ SIGNATURES = {
     "rq_ivf_create": (_vp, [_i32, _i32, _vp, _i32, _vp, _i32]),
     "rq_ivf_build": (_i32, [_vp, _vp, _i64, _u32]),
     "rq_ivf_set_codes": (_i32, [_vp, _vp, _vp, _i64, _u32]),
+    "rq_ivf_build_bytes": (_i32, [_vp, _vp, _i64, _u32]),
+    "rq_ivf_add": (_i32, [_vp, _vp, _i64, _u32]),
+    "rq_ivf_add_bytes": (_i32, [_vp, _vp, _i64, _u32]),
+    "rq_ivf_add_codes": (_i32, [_vp, _vp, _vp, _i64, _u32]),
     "rq_ivf_search": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
     "rq_ivf_get_lists": (_i32, [_vp, _vp, _vp, _vp]),
     "rq_ivf_info": (_i32, [_vp, _vp, _i32]),

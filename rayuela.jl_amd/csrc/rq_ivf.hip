@@ -20,8 +20,16 @@
 //   4. sel_run (k)                                       dists / ids, (NaN, 0xFFFFFFFF + id_base) behind the comparable rows
 // The build groups rows with the same chain: keys (list << 32 | row) of a piece of rows, sorted by sel_run with k = the piece, are
 // the piece in (list, row) order; pieces are placed one behind the other inside every list, so a list holds its rows in ascending id.
+// An add takes its batch through the same steps with temporaries sized by the batch; the loaded base enters
+// ivf_offsets_kernel as the piece in front of all others, ivf_carry_kernel<MP> moves its rows to their new places (a constant shift
+// per list) and ivf_place_kernel<MP> puts the batch's rows behind them.  The new base is a fresh allocation, adopted when the last
+// kernel has finished; a build is an add to nothing and launches what it launched before there were adds.  Byte rows (bvecs) are
+// uploaded as bytes: lists through encode_h16_bytes_launch, then x - Q[list] written as f32 straight from the bytes
+// (ivf_residual_bytes_kernel) or, without residuals, the codes through encode_bytes_launch.
 #include "rq_internal.h"
+#include "rq_ivf_rules.h"
 #include "rq_topk.h"
+#include "rq_encode_split.h"
 
 #include <mutex>
 
@@ -244,15 +252,18 @@ __global__ __launch_bounds__(IVF_T) void ivf_bounds_kernel(uint32_t *first, uint
 }
 
 // one workgroup: off [nlist + 1] = exclusive scan of the list sizes over all pieces; base [P][nlist] = where piece p's rows of
-// list l begin: off[l] + the rows of l in the pieces before p
+// list l begin: off[l] + the rows of l in the pieces before p.  off_old (null: none) is the loaded base of an add, the piece in
+// front of all others: list l keeps its off_old[l + 1] - off_old[l] rows first, the pieces of the batch go behind them
 __global__ __launch_bounds__(1024) void ivf_offsets_kernel(uint32_t *off, uint32_t *base, const uint32_t *first,
-                                                           const uint32_t *last, int P, int nlist) {
+                                                           const uint32_t *last, const uint32_t *off_old, int P, int nlist) {
   __shared__ unsigned long long part[1024];
   const int per = (nlist + 1023) / 1024;
   const int b = min(nlist, (int)threadIdx.x * per), e = min(nlist, b + per);
   unsigned long long sum = 0;
-  for (int l = b; l < e; ++l)
+  for (int l = b; l < e; ++l) {
+    if (off_old) sum += off_old[l + 1] - off_old[l];
     for (int p = 0; p < P; ++p) sum += last[(size_t)p * nlist + l] - first[(size_t)p * nlist + l];
+  }
   part[threadIdx.x] = sum;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -264,6 +275,7 @@ __global__ __launch_bounds__(1024) void ivf_offsets_kernel(uint32_t *off, uint32
   uint32_t run = (uint32_t)part[threadIdx.x];
   for (int l = b; l < e; ++l) {
     off[l] = run;
+    if (off_old) run += off_old[l + 1] - off_old[l];
     for (int p = 0; p < P; ++p) {
       base[(size_t)p * nlist + l] = run;
       run += last[(size_t)p * nlist + l] - first[(size_t)p * nlist + l];
@@ -290,6 +302,86 @@ __global__ __launch_bounds__(IVF_T) void ivf_place_kernel(uint8_t *codes_out, ui
   for (int i = 0; i < MP / (int)sizeof(W); ++i) dst[i] = src[i];
 }
 
+// ---- adding to a loaded base ----------------------------------------------------------------------------------------------------
+// The owner of position j of a grouped base: the LAST list l with off[l] <= j.  Empty lists make runs of equal offsets, and of a
+// run only its last list holds rows.  Needs off[lo] <= j < off[hi]; ends with off[lo] <= j < off[lo + 1], so lo is that list.
+__device__ __forceinline__ uint32_t ivf_owner(const uint32_t *off, uint32_t lo, uint32_t hi, uint32_t j) {
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// An add moves every loaded row -- its id and its MP code bytes -- from off_old[l] + r to off_new[l] + r.  The grid runs over rows,
+// so a list that holds a large share of the base costs what its rows cost.  A workgroup takes IVF_T * IVF_CARRY_ROWS consecutive
+// rows: two threads find the lists of its first and last row in all of off_old (a chain of dependent loads, paid once per
+// workgroup), every row is then searched only between them -- not at all when the workgroup lies inside one list, else over a few
+// words that are in L1 / L2.  Thread t takes rows t, t + IVF_T, ...: a wavefront reads and writes consecutive rows.  A row is
+// copied in words of min(MP, 16) bytes: both bases are hipMalloc'ed and a row begins at a multiple of MP.
+constexpr int IVF_CARRY_ROWS = 8;
+template <int MP>
+__global__ __launch_bounds__(IVF_T) void ivf_carry_kernel(uint8_t *__restrict__ codes_out, uint32_t *__restrict__ ids_out,
+                                                          const uint8_t *__restrict__ codes_in, const uint32_t *__restrict__ ids_in,
+                                                          const uint32_t *__restrict__ off_old, const uint32_t *__restrict__ off_new,
+                                                          uint64_t n_old, size_t n_new, int nlist) {
+  __shared__ uint32_t span[2];
+  const uint64_t j0 = (uint64_t)blockIdx.x * (IVF_T * IVF_CARRY_ROWS);
+  if (threadIdx.x < 2) {
+    const uint64_t je = j0 + IVF_T * IVF_CARRY_ROWS < n_old ? j0 + IVF_T * IVF_CARRY_ROWS : n_old;
+    span[threadIdx.x] = ivf_owner(off_old, 0u, (uint32_t)nlist, (uint32_t)(threadIdx.x == 0 ? j0 : je - 1));
+  }
+  __syncthreads();
+  const uint32_t l0 = span[0], l1 = span[1];
+  using W = typename std::conditional<MP >= 16, uint4, typename std::conditional<MP == 8, uint2,
+            typename std::conditional<MP == 4, uint32_t, uint16_t>::type>::type>::type;
+#pragma unroll
+  for (int i = 0; i < IVF_CARRY_ROWS; ++i) {
+    const uint64_t j = j0 + (uint64_t)i * IVF_T + threadIdx.x;
+    if (j >= n_old) return;
+    const uint32_t l = l0 == l1 ? l0 : ivf_owner(off_old, l0, l1 + 1u, (uint32_t)j);
+    const size_t dest = (size_t)off_new[l] + (size_t)((uint32_t)j - off_old[l]);
+    if (dest >= n_new) return;                 // (cannot happen: off_new holds every list's loaded rows)
+    ids_out[dest] = ids_in[j];
+    const W *src = reinterpret_cast<const W *>(codes_in + (size_t)j * MP);
+    W *dst = reinterpret_cast<W *>(codes_out + dest * MP);
+#pragma unroll
+    for (int w = 0; w < MP / (int)sizeof(W); ++w) dst[w] = src[w];
+  }
+}
+
+// out[row][:] = float(X[row][:]) - Q[list(row)][:] from byte rows: one f32 subtraction per element, residual_kernel's arithmetic
+// on the widened row (u8 -> f32 is exact).  One thread per 8 elements of a row (fewer at its end), loaded 8 bytes at a time down
+// to single bytes by the alignment of X and d (byte_align / load_bytes, as the byte encode reads rows); out is 16-byte aligned
+__global__ __launch_bounds__(IVF_T) void ivf_residual_bytes_kernel(float *out, const uint8_t *X, const float *__restrict__ Q,
+                                                                   const int16_t *lists, int64_t n, int d) {
+  const int per = (d + 7) / 8;
+  const int64_t e = (int64_t)blockIdx.x * IVF_T + threadIdx.x;
+  if (e >= n * per) return;
+  const int64_t row = e / per;
+  const int i0 = (int)(e - row * per) * 8;
+  const int nb = min(8, d - i0);
+  const uint32_t list = (uint32_t)(uint16_t)lists[row];
+  uint32_t w[2];
+  float x[8];
+  load_bytes<8>(X + (size_t)row * d + i0, byte_align(X, d, 8), nb, w);
+  bytes_f32<8>(w, x);
+  float *o = out + (size_t)row * d + i0;
+  const float *c = Q + (size_t)list * d + i0;
+  if ((d & 3) == 0) {       // nb is 4 or 8, and o / c are 16-byte aligned
+    const float4 v = *reinterpret_cast<const float4 *>(c);
+    *reinterpret_cast<float4 *>(o) = make_float4(x[0] - v.x, x[1] - v.y, x[2] - v.z, x[3] - v.w);
+    if (nb == 8) {
+      const float4 u = *reinterpret_cast<const float4 *>(c + 4);
+      *reinterpret_cast<float4 *>(o + 4) = make_float4(x[4] - u.x, x[5] - u.y, x[6] - u.z, x[7] - u.w);
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+      if (s < nb) o[s] = x[s] - c[s];
+  }
+}
+
 }  // namespace rq
 
 using namespace rq;
@@ -301,6 +393,7 @@ struct rq_ivf {
   float *coarse = nullptr, *sa = nullptr, *centers = nullptr;     // device
   // the loaded base (device): rows grouped by list
   int64_t n = 0;
+  uint64_t next_id = 0;            // the largest id loaded plus one: the least id_offset an add may take
   uint8_t *codes = nullptr;        // [n][mp]
   uint32_t *ids = nullptr;         // [n]: row + id_offset
   uint32_t *off = nullptr;         // [nlist + 1]
@@ -309,6 +402,7 @@ struct rq_ivf {
   // the last search
   int64_t s_ld = 0, s_batch = 0, s_items = 0, s_rows = 0;
   double s_ms[4] = {0, 0, 0, 0};
+  double l_ms[4] = {0, 0, 0, 0};   // the last build / set_codes / add: encode (with its uploads), grouping, carry, place
   std::mutex mu;
 };
 
@@ -325,13 +419,22 @@ struct IvfBase {                   // what a build or set_codes makes before it 
   }
 };
 
-int ivf_range_check(const char *who, const rq_ivf *ix, int64_t n, uint32_t id_offset) {
-  if (n < 1) return fail(RQ_EINVAL, "%s: n=%lld rows", who, (long long)n);
-  if ((uint64_t)n + (uint64_t)id_offset > 0xFFFFFFFFull)
-    return fail(RQ_EINVAL, "%s: n + id_offset = %llu exceeds 2^32 - 1 (ids are uint32, 0xFFFFFFFF marks padding)", who,
-                (unsigned long long)((uint64_t)n + id_offset));
-  (void)ix;
-  return RQ_OK;
+// the id rule and the limits (rq_ivf_rules.h) of a call that loads n rows; `loaded` rows stay in front of them (0: it replaces)
+int ivf_rule_check(const char *who, const rq_ivf *ix, int64_t loaded, int64_t n, uint32_t id_offset) {
+  switch (ivf_load_rule(loaded, ix->next_id, n, id_offset)) {
+    case IVF_OK: return RQ_OK;
+    case IVF_NO_ROWS: return fail(RQ_EINVAL, "%s: n=%lld rows", who, (long long)n);
+    case IVF_ID_RANGE:
+      return fail(RQ_EINVAL, "%s: n + id_offset = %llu exceeds 2^32 - 1 (ids are uint32, 0xFFFFFFFF marks padding)", who,
+                  (unsigned long long)((uint64_t)n + id_offset));
+    case IVF_ID_ORDER:
+      return fail(RQ_EINVAL, "%s: id_offset=%u lies below the next id %llu (ids ascend inside a list; gaps are allowed)", who,
+                  id_offset, (unsigned long long)ix->next_id);
+    case IVF_ROW_RANGE:
+      return fail(RQ_EINVAL, "%s: %lld rows loaded + n=%lld exceed 2^32 - 1 (offsets are uint32)", who, (long long)loaded,
+                  (long long)n);
+  }
+  return RQ_EINVAL;
 }
 
 template <int MP>
@@ -350,27 +453,43 @@ int64_t ivf_piece_rows(int64_t n) {
   return forced > 0 ? std::min<int64_t>(rows, forced) : rows;
 }
 
-// lists [n] (device, every entry < nlist) and arrival-order codes [n][mp] -> the grouped base in *nb (allocated here)
-int ivf_group(rq_ivf *ix, IvfBase *nb, const uint32_t *lists, const uint8_t *codes_arr, int64_t n, uint32_t id_offset,
-              hipStream_t stream) {
+template <int MP>
+int ivf_carry_launch(uint8_t *codes_out, uint32_t *ids_out, const rq_ivf *ix, const uint32_t *off_new, size_t n_new,
+                     hipStream_t stream) {
+  RQ_LAUNCH(ivf_carry_kernel<MP>, dim3((uint32_t)(((uint64_t)ix->n + IVF_T * IVF_CARRY_ROWS - 1) / (IVF_T * IVF_CARRY_ROWS))),
+            dim3(IVF_T), 0, stream, codes_out, ids_out,
+            ix->codes, ix->ids, ix->off, off_new, (uint64_t)ix->n, n_new, ix->nlist);
+  return RQ_OK;
+}
+
+// milliseconds of the last load (rq_ivf_last_timing [4..7])
+enum { IVF_MS_ENCODE = 0, IVF_MS_GROUP = 1, IVF_MS_CARRY = 2, IVF_MS_PLACE = 3 };
+
+// lists [n] (device, every entry < nlist) and arrival-order codes [n][mp] of a batch -> the grouped base in *nb (allocated here).
+// carry: the loaded base of ix goes in front, list by list (an add); else the batch alone is the base (a build), and no launch
+// differs from what a build made before there were adds.
+int ivf_group(rq_ivf *ix, IvfBase *nb, const uint32_t *lists, const uint8_t *codes_arr, int64_t n, uint32_t id_offset, bool carry,
+              PhaseClock &clock, hipStream_t stream) {
   const int nlist = ix->nlist, mp = ix->mp;
+  const int64_t total = n + (carry ? ix->n : 0);
   const int64_t piece = ivf_piece_rows(n);
-  const int P = (int)((n + piece - 1) / piece);
+  const int P = (int)ivf_piece_count(n, piece);
   DevMem sorted, first, last, base;
   RQ_TRY(sorted.alloc((size_t)n * 4));
   RQ_TRY(first.alloc((size_t)P * nlist * 4));
   RQ_TRY(last.alloc((size_t)P * nlist * 4));
   RQ_TRY(base.alloc((size_t)P * nlist * 4));
-  RQ_HIP(hipMalloc((void **)&nb->codes, (size_t)n * mp));
-  RQ_HIP(hipMalloc((void **)&nb->ids, (size_t)n * 4));
+  RQ_HIP(hipMalloc((void **)&nb->codes, (size_t)total * mp));
+  RQ_HIP(hipMalloc((void **)&nb->ids, (size_t)total * 4));
   RQ_HIP(hipMalloc((void **)&nb->off, (size_t)(nlist + 1) * 4));
   RQ_HIP(hipMemsetAsync(first.p, 0, (size_t)P * nlist * 4, stream));
   RQ_HIP(hipMemsetAsync(last.p, 0, (size_t)P * nlist * 4, stream));
   void *ws = nullptr;
   RQ_TRY(workspace(WS_BULK, ivf_align((size_t)piece * 8) + sel_bytes_per_query((uint32_t)piece) + 16 * 256, &ws, stream));
   for (int p = 0; p < P; ++p) {
-    const int64_t r0 = (int64_t)p * piece;
-    const uint32_t cnt = (uint32_t)std::min<int64_t>(piece, n - r0);
+    int64_t r0;
+    uint32_t cnt;
+    ivf_piece_span(n, piece, p, &r0, &cnt);
     unsigned char *at = (unsigned char *)ws;
     uint64_t *keys = (uint64_t *)at; at += ivf_align((size_t)cnt * 8);
     RQ_LAUNCH(ivf_group_keys_kernel, dim3((cnt + IVF_T - 1) / IVF_T), dim3(IVF_T), 0, stream, keys, lists, (uint32_t)r0, cnt);
@@ -386,27 +505,40 @@ int ivf_group(rq_ivf *ix, IvfBase *nb, const uint32_t *lists, const uint8_t *cod
               last.as<uint32_t>() + (size_t)p * nlist, sorted.as<uint32_t>() + r0, lists, cnt);
   }
   RQ_LAUNCH(ivf_offsets_kernel, dim3(1), dim3(1024), 0, stream, nb->off, base.as<uint32_t>(), first.as<uint32_t>(),
-            last.as<uint32_t>(), P, nlist);
+            last.as<uint32_t>(), carry ? (const uint32_t *)ix->off : nullptr, P, nlist);
+  clock.mark(IVF_MS_GROUP);
+  if (carry) {
+    int rc = RQ_EUNSUPPORTED;
+    switch (mp) {
+#define RQ_IVF_CASE(MP) case MP: rc = ivf_carry_launch<MP>(nb->codes, nb->ids, ix, nb->off, (size_t)total, stream); break;
+      RQ_IVF_CASE(2) RQ_IVF_CASE(4) RQ_IVF_CASE(8) RQ_IVF_CASE(16) RQ_IVF_CASE(32) RQ_IVF_CASE(64)
+#undef RQ_IVF_CASE
+    }
+    RQ_TRY(rc);
+    clock.mark(IVF_MS_CARRY);
+  }
   for (int p = 0; p < P; ++p) {
-    const int64_t r0 = (int64_t)p * piece;
-    const uint32_t cnt = (uint32_t)std::min<int64_t>(piece, n - r0);
+    int64_t r0;
+    uint32_t cnt;
+    ivf_piece_span(n, piece, p, &r0, &cnt);
     const uint32_t *srt = sorted.as<uint32_t>() + r0, *fp = first.as<uint32_t>() + (size_t)p * nlist,
                    *bp = base.as<uint32_t>() + (size_t)p * nlist;
     int rc = RQ_EUNSUPPORTED;
     switch (mp) {
 #define RQ_IVF_CASE(MP) \
-      case MP: rc = ivf_place_launch<MP>(nb->codes, nb->ids, codes_arr, srt, lists, fp, bp, cnt, id_offset, (size_t)n, stream); break;
+      case MP: rc = ivf_place_launch<MP>(nb->codes, nb->ids, codes_arr, srt, lists, fp, bp, cnt, id_offset, (size_t)total, stream); break;
       RQ_IVF_CASE(2) RQ_IVF_CASE(4) RQ_IVF_CASE(8) RQ_IVF_CASE(16) RQ_IVF_CASE(32) RQ_IVF_CASE(64)
 #undef RQ_IVF_CASE
     }
     RQ_TRY(rc);
   }
+  clock.mark(IVF_MS_PLACE);
   RQ_HIP(hipStreamSynchronize(stream));
   return RQ_OK;
 }
 
 // the new base replaces the loaded one: host copies of the offsets, the sizes largest first
-int ivf_adopt(rq_ivf *ix, IvfBase *nb, int64_t n) {
+int ivf_adopt(rq_ivf *ix, IvfBase *nb, int64_t n, uint64_t next_id) {
   std::vector<uint32_t> off((size_t)ix->nlist + 1);
   RQ_HIP(hipMemcpy(off.data(), nb->off, off.size() * 4, hipMemcpyDeviceToHost));
   if ((int64_t)off[ix->nlist] != n) return fail(RQ_EINVAL, "rq_ivf: grouped %u of %lld rows", off[ix->nlist], (long long)n);
@@ -416,11 +548,118 @@ int ivf_adopt(rq_ivf *ix, IvfBase *nb, int64_t n) {
   ix->codes = nb->codes; ix->ids = nb->ids; ix->off = nb->off;
   nb->codes = nullptr; nb->ids = nullptr; nb->off = nullptr;
   ix->n = n;
+  ix->next_id = next_id;
   ix->h_off.assign(off.begin(), off.end());
   ix->h_desc.resize(ix->nlist);
   for (int l = 0; l < ix->nlist; ++l) ix->h_desc[l] = ix->h_off[l + 1] - ix->h_off[l];
   std::sort(ix->h_desc.begin(), ix->h_desc.end(), [](int64_t a, int64_t b) { return a > b; });
   return RQ_OK;
+}
+
+// what every load ends with: group the batch (behind the loaded base when carry), adopt the result, keep the phase times; after
+// a failure the base that was loaded answers
+int ivf_finish(rq_ivf *ix, const uint32_t *lists, const uint8_t *codes_arr, int64_t n, uint32_t id_offset, bool carry,
+               PhaseClock &clock, double *ms, hipStream_t stream) {
+  IvfBase nb;
+  int rc = ivf_group(ix, &nb, lists, codes_arr, n, id_offset, carry, clock, stream);
+  if (rc == RQ_OK) rc = ivf_adopt(ix, &nb, n + (carry ? ix->n : 0), (uint64_t)id_offset + (uint64_t)n);
+  if (rc != RQ_OK) { (void)hipStreamSynchronize(stream); nb.drop(); return rc; }
+  clock.collect();
+  for (int i = 0; i < 4; ++i) ix->l_ms[i] = ms[i];
+  return RQ_OK;
+}
+
+// rq_ivf_build[_bytes] (append = false) and rq_ivf_add[_bytes]: X_host [n][d] of esz bytes per element (4: float, 1: uint8)
+int ivf_load_rows(const char *who, rq_ivf *ix, const void *X_host, int esz, int64_t n, uint32_t id_offset, bool append) {
+  if (!ix || !X_host) return fail(RQ_EINVAL, "%s: NULL argument", who);
+  std::lock_guard<std::mutex> guard(ix->mu);
+  const bool carry = append && ix->codes && ix->n > 0;
+  RQ_TRY(ivf_rule_check(who, ix, carry ? ix->n : 0, n, id_offset));
+  if (ix->m > 32)
+    return fail(RQ_EUNSUPPORTED, "%s: the encode covers 1 <= m <= 32; got m=%d (%s takes codes)", who, ix->m,
+                append ? "rq_ivf_add_codes" : "rq_ivf_set_codes");
+  SavedDevice saved;
+  RQ_HIP(hipSetDevice(ix->device));
+  DeviceLock lock;
+  hipStream_t stream = nullptr;
+  const int d = ix->d, m = ix->m, mp = ix->mp;
+  const bool bytes = esz == 1;
+  int64_t chunk = std::max<int64_t>(32768, ((int64_t)1 << 26) / d);
+  const int forced = ivf_knob("IVF_BUILD_ROWS", 0);
+  if (forced > 0) chunk = forced;
+  chunk = std::min(chunk, n);
+  DevMem dX, dB, d16, d8, lists, arr;
+  if (!bytes || ix->by_residual) RQ_TRY(dX.alloc((size_t)chunk * d * 4));     // byte rows without residuals: no float copy
+  if (bytes) RQ_TRY(dB.alloc((size_t)chunk * d));
+  RQ_TRY(d16.alloc((size_t)chunk * 2));
+  RQ_TRY(d8.alloc((size_t)chunk * m));
+  RQ_TRY(lists.alloc((size_t)n * 4));
+  RQ_TRY(arr.alloc((size_t)n * mp));
+  double ms[4] = {0, 0, 0, 0};
+  PhaseClock clock(stream, ms);
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t nr = std::min(chunk, n - r0);
+    uint8_t *out = m == mp ? arr.as<uint8_t>() + (size_t)r0 * mp : d8.as<uint8_t>();
+    if (bytes) {
+      RQ_HIP(hipMemcpyAsync(dB.p, (const uint8_t *)X_host + (size_t)r0 * d, (size_t)nr * d, hipMemcpyHostToDevice, stream));
+      RQ_TRY(encode_h16_bytes_launch(d16.as<int16_t>(), dB.as<uint8_t>(), nullptr, ix->coarse, nr, d, 1, ix->nlist, ix->num_cu, stream));
+    } else {
+      RQ_HIP(hipMemcpyAsync(dX.p, (const float *)X_host + (size_t)r0 * d, (size_t)nr * d * 4, hipMemcpyHostToDevice, stream));
+      RQ_TRY(encode_h16_launch(d16.as<int16_t>(), dX.as<float>(), ix->coarse, nr, d, 1, ix->nlist, ix->num_cu, stream));
+    }
+    RQ_LAUNCH(ivf_widen_lists_kernel, dim3((uint32_t)((nr + IVF_T - 1) / IVF_T)), dim3(IVF_T), 0, stream,
+              lists.as<uint32_t>() + r0, d16.as<int16_t>(), nr);
+    if (bytes && !ix->by_residual) {
+      RQ_TRY(encode_bytes_launch(out, dB.as<uint8_t>(), nullptr, ix->centers, nr, d, m, 256, ix->num_cu, stream));
+    } else {
+      if (bytes) {
+        const int64_t threads = nr * ((d + 7) / 8);
+        RQ_LAUNCH(ivf_residual_bytes_kernel, dim3((uint32_t)((threads + IVF_T - 1) / IVF_T)), dim3(IVF_T), 0, stream, dX.as<float>(),
+                  dB.as<uint8_t>(), ix->coarse, d16.as<int16_t>(), nr, d);
+      } else if (ix->by_residual) {
+        RQ_TRY(residual_launch<int16_t>(dX.as<float>(), dX.as<float>(), ix->coarse, d16.as<int16_t>(), 1, nullptr, nullptr, nr, d, 1, 0,
+                                        stream));
+      }
+      RQ_TRY(encode_launch(out, dX.as<float>(), ix->centers, nr, d, m, 256, ix->num_cu, stream));
+    }
+    if (m != mp) RQ_TRY(pad_codes_launch(arr.as<uint8_t>() + (size_t)r0 * mp, d8.as<uint8_t>(), nr, m, mp, stream));
+    clock.mark(IVF_MS_ENCODE);
+    RQ_HIP(hipStreamSynchronize(stream));      // the chunk buffer is reused
+  }
+  return ivf_finish(ix, lists.as<uint32_t>(), arr.as<uint8_t>(), n, id_offset, carry, clock, ms, stream);
+}
+
+// rq_ivf_set_codes (append = false) and rq_ivf_add_codes
+int ivf_load_codes(const char *who, rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset,
+                   bool append) {
+  if (!ix || !lists_host || !codes_host) return fail(RQ_EINVAL, "%s: NULL argument", who);
+  RQ_TRY(ivf_rule_check(who, ix, 0, n, id_offset));      // what needs no state, so that the scan below reads n valid entries ...
+  for (int64_t i = 0; i < n; ++i)                        // ... and runs before the mutex: searches go on meanwhile
+    if (lists_host[i] >= (uint32_t)ix->nlist)
+      return fail(RQ_EINVAL, "%s: row %lld names list %d outside [0, %d)", who, (long long)i, (int)lists_host[i], ix->nlist);
+  std::lock_guard<std::mutex> guard(ix->mu);
+  const bool carry = append && ix->codes && ix->n > 0;
+  RQ_TRY(ivf_rule_check(who, ix, carry ? ix->n : 0, n, id_offset));
+  SavedDevice saved;
+  RQ_HIP(hipSetDevice(ix->device));
+  DeviceLock lock;
+  hipStream_t stream = nullptr;
+  const int m = ix->m, mp = ix->mp;
+  DevMem lists, raw, arr;
+  RQ_TRY(lists.alloc((size_t)n * 4));
+  RQ_TRY(arr.alloc((size_t)n * mp));
+  double ms[4] = {0, 0, 0, 0};
+  PhaseClock clock(stream, ms);
+  RQ_HIP(hipMemcpyAsync(lists.p, lists_host, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+  if (m == mp) {
+    RQ_HIP(hipMemcpyAsync(arr.p, codes_host, (size_t)n * m, hipMemcpyHostToDevice, stream));
+  } else {
+    RQ_TRY(raw.alloc((size_t)n * m));
+    RQ_HIP(hipMemcpyAsync(raw.p, codes_host, (size_t)n * m, hipMemcpyHostToDevice, stream));
+    RQ_TRY(pad_codes_launch(arr.as<uint8_t>(), raw.as<uint8_t>(), n, m, mp, stream));
+  }
+  clock.mark(IVF_MS_ENCODE);
+  return ivf_finish(ix, lists.as<uint32_t>(), arr.as<uint8_t>(), n, id_offset, carry, clock, ms, stream);
 }
 
 // scratch of a batch of nb queries: what survives both phases, then the larger of the probe selection and the scan
@@ -493,77 +732,27 @@ void rq_ivf_destroy(rq_ivf *ix) {
 }
 
 int rq_ivf_build(rq_ivf *ix, const float *X_host, int64_t n, uint32_t id_offset) {
-  if (!ix || !X_host) return fail(RQ_EINVAL, "rq_ivf_build: NULL argument");
-  RQ_TRY(ivf_range_check("rq_ivf_build", ix, n, id_offset));
-  if (ix->m > 32) return fail(RQ_EUNSUPPORTED, "rq_ivf_build: the encode covers 1 <= m <= 32; got m=%d (rq_ivf_set_codes takes codes)", ix->m);
-  std::lock_guard<std::mutex> guard(ix->mu);
-  SavedDevice saved;
-  RQ_HIP(hipSetDevice(ix->device));
-  DeviceLock lock;
-  hipStream_t stream = nullptr;
-  const int d = ix->d, m = ix->m, mp = ix->mp;
-  int64_t chunk = std::max<int64_t>(32768, ((int64_t)1 << 26) / d);
-  const int forced = ivf_knob("IVF_BUILD_ROWS", 0);
-  if (forced > 0) chunk = forced;
-  chunk = std::min(chunk, n);
-  DevMem dX, d16, d8, lists, arr;
-  RQ_TRY(dX.alloc((size_t)chunk * d * 4));
-  RQ_TRY(d16.alloc((size_t)chunk * 2));
-  RQ_TRY(d8.alloc((size_t)chunk * m));
-  RQ_TRY(lists.alloc((size_t)n * 4));
-  RQ_TRY(arr.alloc((size_t)n * mp));
-  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-    const int64_t nr = std::min(chunk, n - r0);
-    RQ_HIP(hipMemcpyAsync(dX.p, X_host + (size_t)r0 * d, (size_t)nr * d * 4, hipMemcpyHostToDevice, stream));
-    RQ_TRY(encode_h16_launch(d16.as<int16_t>(), dX.as<float>(), ix->coarse, nr, d, 1, ix->nlist, ix->num_cu, stream));
-    RQ_LAUNCH(ivf_widen_lists_kernel, dim3((uint32_t)((nr + IVF_T - 1) / IVF_T)), dim3(IVF_T), 0, stream,
-              lists.as<uint32_t>() + r0, d16.as<int16_t>(), nr);
-    if (ix->by_residual)
-      RQ_TRY(residual_launch<int16_t>(dX.as<float>(), dX.as<float>(), ix->coarse, d16.as<int16_t>(), 1, nullptr, nullptr, nr, d, 1, 0,
-                                      stream));
-    if (m == mp) {
-      RQ_TRY(encode_launch(arr.as<uint8_t>() + (size_t)r0 * mp, dX.as<float>(), ix->centers, nr, d, m, 256, ix->num_cu, stream));
-    } else {
-      RQ_TRY(encode_launch(d8.as<uint8_t>(), dX.as<float>(), ix->centers, nr, d, m, 256, ix->num_cu, stream));
-      RQ_TRY(pad_codes_launch(arr.as<uint8_t>() + (size_t)r0 * mp, d8.as<uint8_t>(), nr, m, mp, stream));
-    }
-    RQ_HIP(hipStreamSynchronize(stream));      // the chunk buffer is reused
-  }
-  IvfBase nb;
-  int rc = ivf_group(ix, &nb, lists.as<uint32_t>(), arr.as<uint8_t>(), n, id_offset, stream);
-  if (rc == RQ_OK) rc = ivf_adopt(ix, &nb, n);
-  if (rc != RQ_OK) { (void)hipStreamSynchronize(stream); nb.drop(); }
-  return rc;
+  return ivf_load_rows("rq_ivf_build", ix, X_host, 4, n, id_offset, false);
+}
+
+int rq_ivf_build_bytes(rq_ivf *ix, const uint8_t *X_host, int64_t n, uint32_t id_offset) {
+  return ivf_load_rows("rq_ivf_build_bytes", ix, X_host, 1, n, id_offset, false);
 }
 
 int rq_ivf_set_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset) {
-  if (!ix || !lists_host || !codes_host) return fail(RQ_EINVAL, "rq_ivf_set_codes: NULL argument");
-  RQ_TRY(ivf_range_check("rq_ivf_set_codes", ix, n, id_offset));
-  for (int64_t i = 0; i < n; ++i)
-    if (lists_host[i] >= (uint32_t)ix->nlist)
-      return fail(RQ_EINVAL, "rq_ivf_set_codes: row %lld names list %d outside [0, %d)", (long long)i, (int)lists_host[i], ix->nlist);
-  std::lock_guard<std::mutex> guard(ix->mu);
-  SavedDevice saved;
-  RQ_HIP(hipSetDevice(ix->device));
-  DeviceLock lock;
-  hipStream_t stream = nullptr;
-  const int m = ix->m, mp = ix->mp;
-  DevMem lists, raw, arr;
-  RQ_TRY(lists.alloc((size_t)n * 4));
-  RQ_TRY(arr.alloc((size_t)n * mp));
-  RQ_HIP(hipMemcpyAsync(lists.p, lists_host, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-  if (m == mp) {
-    RQ_HIP(hipMemcpyAsync(arr.p, codes_host, (size_t)n * m, hipMemcpyHostToDevice, stream));
-  } else {
-    RQ_TRY(raw.alloc((size_t)n * m));
-    RQ_HIP(hipMemcpyAsync(raw.p, codes_host, (size_t)n * m, hipMemcpyHostToDevice, stream));
-    RQ_TRY(pad_codes_launch(arr.as<uint8_t>(), raw.as<uint8_t>(), n, m, mp, stream));
-  }
-  IvfBase nb;
-  int rc = ivf_group(ix, &nb, lists.as<uint32_t>(), arr.as<uint8_t>(), n, id_offset, stream);
-  if (rc == RQ_OK) rc = ivf_adopt(ix, &nb, n);
-  if (rc != RQ_OK) { (void)hipStreamSynchronize(stream); nb.drop(); }
-  return rc;
+  return ivf_load_codes("rq_ivf_set_codes", ix, lists_host, codes_host, n, id_offset, false);
+}
+
+int rq_ivf_add(rq_ivf *ix, const float *X_host, int64_t n, uint32_t id_offset) {
+  return ivf_load_rows("rq_ivf_add", ix, X_host, 4, n, id_offset, true);
+}
+
+int rq_ivf_add_bytes(rq_ivf *ix, const uint8_t *X_host, int64_t n, uint32_t id_offset) {
+  return ivf_load_rows("rq_ivf_add_bytes", ix, X_host, 1, n, id_offset, true);
+}
+
+int rq_ivf_add_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset) {
+  return ivf_load_codes("rq_ivf_add_codes", ix, lists_host, codes_host, n, id_offset, true);
 }
 
 int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k, int id_base) {
@@ -719,16 +908,16 @@ int rq_ivf_info(rq_ivf *ix, int64_t *out, int cap) {
   std::lock_guard<std::mutex> guard(ix->mu);
   int64_t empty = 0;
   for (int64_t s : ix->h_desc) empty += s == 0;
-  const int64_t v[11] = {ix->codes ? ix->n : 0, ix->nlist, ix->m, ix->d, ix->by_residual, ix->h_desc.empty() ? 0 : ix->h_desc[0], empty,
-                         ix->s_ld, ix->s_batch, ix->s_items, ix->s_rows};
-  for (int i = 0; i < cap && i < 11; ++i) out[i] = v[i];
+  const int64_t v[12] = {ix->codes ? ix->n : 0, ix->nlist, ix->m, ix->d, ix->by_residual, ix->h_desc.empty() ? 0 : ix->h_desc[0], empty,
+                         ix->s_ld, ix->s_batch, ix->s_items, ix->s_rows, ix->codes ? (int64_t)ix->next_id : 0};
+  for (int i = 0; i < cap && i < 12; ++i) out[i] = v[i];
   return RQ_OK;
 }
 
 int rq_ivf_last_timing(rq_ivf *ix, double *ms, int cap) {
   if (!ix || !ms || cap < 1) return fail(RQ_EINVAL, "rq_ivf_last_timing: NULL argument");
   std::lock_guard<std::mutex> guard(ix->mu);
-  for (int i = 0; i < cap && i < 4; ++i) ms[i] = ix->s_ms[i];
+  for (int i = 0; i < cap && i < 8; ++i) ms[i] = i < 4 ? ix->s_ms[i] : ix->l_ms[i - 4];
   return RQ_OK;
 }
 

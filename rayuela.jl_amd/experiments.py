@@ -83,16 +83,23 @@ def experiment_opq_query_base(Xt, Xq, gt, m, h, init, niter=25, knn=1000, V=Fals
 
 
 def experiment_ivfpq(Xt, Xb, Xq, gt=None, nlist=1024, m=8, nprobes=(1, 8, 32), niter=25, knn=100, by_residual=True, V=False,
-                     seed=0):
+                     seed=0, add_rows=None):
     """IVFADC (IVF.py; no counterpart in the reference): train the coarse centroids and the codebooks on Xt, build the index on
     Xb, search Xq once per nprobe.  Returns Q, C and {nprobe: recall curve of eval_recall} -- recall against the exact nearest
-    neighbour, so it is bounded by the share of queries whose neighbour lies in a probed list."""
+    neighbour, so it is bounded by the share of queries whose neighbour lies in a probed list.  add_rows: load Xb in adds of that
+    many rows instead of one build; the loaded base, and so every curve, is the same."""
     from .IVF import IvfIndex, train_ivfpq
     Q, C = train_ivfpq(Xt, nlist, m, niter=niter, seed=seed, by_residual=by_residual)
     truth = _gt(gt, Xb, Xq)
     recall = {}
     with IvfIndex(Q, C, by_residual=by_residual) as ix:
-        ix.build(Xb)
+        if add_rows is None:
+            ix.build(Xb)
+        else:
+            if add_rows < 1:
+                raise ValueError("add_rows must be positive")
+            for r0 in range(0, Xb.shape[0], int(add_rows)):
+                ix.add(Xb[r0:r0 + int(add_rows)])
         for nprobe in nprobes:
             if V:
                 print("nprobe = %d" % nprobe)

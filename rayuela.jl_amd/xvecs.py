@@ -130,3 +130,41 @@ def quantize_bvecs(filename, C, R=None, bounds=None, rows_per_read=1 << 20, one_
             encode = L.rq_encode_opq_bytes_i16 if one_based else L.rq_encode_opq_bytes
             _lib.check(encode(dst.ctypes.data, X.ctypes.data, Rc.ctypes.data, Cc.ctypes.data, nr, d, m, h))
     return out
+
+
+def _ivf_add_xvecs(ix, filename, bounds, rows_per_read, read, itemsize):
+    if rows_per_read < 1:
+        raise ValueError("rows_per_read must be positive")
+    with open(filename, "rb") as f:
+        d = int(np.fromfile(f, dtype="<i4", count=1)[0])
+        f.seek(0, 2)
+        vecnum = f.tell() // (4 + d * itemsize)
+    if bounds is None:
+        a, b = 1, vecnum
+    elif isinstance(bounds, (int, np.integer)):
+        a, b = 1, int(bounds)
+    else:
+        a, b = int(bounds[0]), int(bounds[1])
+    if a < 1 or b > vecnum or b < a:
+        raise ValueError("%s holds %d vectors, asked for %d..%d" % (filename, vecnum, a, b))
+    if d != ix.d:
+        raise ValueError("%s holds vectors of %d dimensions, the index takes d=%d" % (filename, d, ix.d))
+    n = b - a + 1
+    for r0 in range(0, n, rows_per_read):
+        nr = min(rows_per_read, n - r0)
+        ix.add(read((a + r0, a + r0 + nr - 1), filename), id_offset=a - 1 + r0)
+    return n
+
+
+def ivf_add_bvecs(ix, filename, bounds=None, rows_per_read=1 << 20):
+    """Add the vectors of a .bvecs file (bigann_base.bvecs) to the IvfIndex ix: the file is read piecewise with
+    bvecs_read(bounds, filename), rows_per_read vectors at a time, and every piece is added from its bytes with its file
+    position as id_offset -- the id of a vector is its ZERO-based position in the file whatever rows_per_read and bounds are, so
+    shards of a file can be added in ascending order.  bounds: None (all), n (first n) or (a, b) one-based inclusive.  Returns
+    the number of vectors added."""
+    return _ivf_add_xvecs(ix, filename, bounds, rows_per_read, bvecs_read, 1)
+
+
+def ivf_add_fvecs(ix, filename, bounds=None, rows_per_read=1 << 20):
+    """ivf_add_bvecs for a .fvecs file (float32 vectors)."""
+    return _ivf_add_xvecs(ix, filename, bounds, rows_per_read, fvecs_read, 4)
