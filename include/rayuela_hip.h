@@ -714,6 +714,40 @@ int rq_last_knn_stats(uint64_t *out8);
 int rq_last_knn_timing(double *ms, int cap);
 int rq_knn_plan(int64_t n, int64_t nq, int d, int k, int64_t *out, int cap);
 
+/* ---- exact re-ranking of search candidates on a resident base.  The reference has no such step: its
+ * searches return neighbours ranked by the quantized distance and eval_recall (src/Linscan.jl:196-234) takes them as they come.
+ * Faiss calls this step "refine" (IVFADC+R).
+ *
+ * Base X [n][d] resident (rq_dataset_upload[_bytes]: f32, or u8 widened exactly), queries Q [nq][d] f32 (host), candidates
+ * cand [nq][ldc] u32 (host) of which the first kc per query count; ldc >= kc, and what lies behind kc is never read.
+ *   row        r = (c - id_base - id_offset) mod 2^32; the candidate is valid iff r < n, everything else is skipped -- so is the
+ *              scans' padding id 0xFFFFFFFF + id_base, which is never valid because n + id_offset <= 2^32 - 1 is required
+ *   distance   D32(r, q) exactly as the section "exact k-nearest-neighbour" above defines it: one accumulator per pair walks
+ *              s = 0..d-1 in order from +0, every operation rounded on its own
+ *   answer     per query the k smallest (D32, r) pairs in lexicographic order among the valid candidates, ids r + id_offset +
+ *              id_base; the scans' "Non-finite inputs" rules unchanged (a NaN distance is never a neighbour, -0 becomes +0, +Inf
+ *              distances order by id); a list with fewer than k such pairs ends in the padding pair (distance bits 0x7FFFFFFF,
+ *              id 0xFFFFFFFF + id_base).  A candidate id given twice appears twice: there is NO dedupe.  With cand = all n ids the
+ *              answer is rq_knn_f32's.
+ *   errors     checked before any work and before any output byte is written: a NULL pointer, k < 1, kc < k, ldc < kc, kc >= 2^31,
+ *              a bad id_base, n + id_offset > 2^32 - 1: RQ_EINVAL; one query whose keys (and, past 4096 candidates, select
+ *              scratch) do not fit the bulk scratch budget: RQ_EUNSUPPORTED; nq <= 0: RQ_OK.
+ * rq_dataset_rerank: the contract above, synchronous on the dataset's device.
+ * rq_ivf_search_refine (declared with the rq_ivf entries below): rq_ivf_search with kc in place of k, its sorted top-kc keys
+ *   re-ranked on the device against `ds` without a host round trip.  By definition it equals rq_dataset_rerank over the ids
+ *   rq_ivf_search(..., k = kc, id_base) returns, bit for bit; id_offset is the id of row 0 of `ds` (the id_offset the rows were
+ *   loaded with).  ds on another device than ix, or ds.d != ix.d: RQ_EINVAL.
+ * rq_last_rerank_timing: ms of [0] upload, [1] keys, [2] select, [3] download of the calling thread's last call ([1], [2] alone
+ *   after rq_ivf_search_refine).  rq_last_rerank_stats: [0] queries, [1] candidates, [2] valid candidates, [3] batches, [4] the
+ *   select path (0: one workgroup per query sorts in LDS, kc <= 4096; 1: the select chain of the bulk top-k), [5] keys per query
+ *   row, [6..7] 0.  rq_rerank_plan (host only): out[0] queries per batch (0: one query does not fit), [1] scratch bytes of a
+ *   batch, [2] the select path, [3] keys per query row, [4] 1 when the test hook rq_test_rerank_limits set the batch. */
+int rq_dataset_rerank(rq_dataset *ds, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, const uint32_t *cand_host,
+                      int64_t kc, int64_t ldc, int k, uint32_t id_offset, int id_base);
+int rq_last_rerank_timing(double *ms, int cap);
+int rq_last_rerank_stats(uint64_t *out8);
+int rq_rerank_plan(int64_t n, int64_t nq, int d, int64_t kc, int k, int64_t *out, int cap);
+
 /* ---- device-pointer entry points: asynchronous on `stream` (a hipStream_t, NULL = default).
  * All pointers are device pointers on the current device, 16-byte aligned. ------------------ */
 int rq_dev_encode_pq(uint8_t *codes, const float *X, const float *C, int64_t n, int d, int m,
@@ -1101,6 +1135,9 @@ int rq_ivf_add(rq_ivf *ix, const float *X_host, int64_t n, uint32_t id_offset);
 int rq_ivf_add_bytes(rq_ivf *ix, const uint8_t *X_host, int64_t n, uint32_t id_offset);
 int rq_ivf_add_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *codes_host, int64_t n, uint32_t id_offset);
 int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k, int id_base);
+/* the search with kc candidates per query, re-ranked by the exact distance to the rows of ds ("exact re-ranking" above) */
+int rq_ivf_search_refine(rq_ivf *ix, rq_dataset *ds, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe,
+                         int k, int kc, uint32_t id_offset, int id_base);
 int rq_ivf_get_lists(rq_ivf *ix, int64_t *offsets, uint32_t *row_ids, uint8_t *codes);
 int rq_ivf_info(rq_ivf *ix, int64_t *out, int cap);
 int rq_ivf_last_timing(rq_ivf *ix, double *ms, int cap);
@@ -1210,6 +1247,11 @@ int64_t rq_test_knn_chunk_rows(int64_t rows);
  * it, out[4] = 1), so that a test can run the fold of per-slice lists on a small base; rows <= 0 gives the planner its choice
  * back.  No answer depends on it (tests/test_gpu_scan_wide_slices.py).  Returns the previous value. */
 int64_t rq_test_scan_wide_slice_rows(int64_t rows);
+/* The re-ranking entries: lds_kc > 0 makes every later call of this process sort at most lds_kc (<= 4096) candidates per query in
+ * LDS and send longer lists through the select chain; batch_queries > 0 caps the queries per batch of rq_dataset_rerank
+ * (rq_rerank_plan reports both, out[4] = 1 for the batch).  Values <= 0 give the planner its choice back.  No answer depends on
+ * either (tests/test_gpu_rerank.py).  Returns the previous pair as lds_kc * 2^32 + batch_queries. */
+int64_t rq_test_rerank_limits(int64_t lds_kc, int64_t batch_queries);
 
 #ifdef __cplusplus
 }

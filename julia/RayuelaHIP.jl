@@ -27,6 +27,7 @@ export train_sr, train_sr_cuda, SR_C_perturb, SR_D_perturb
 export quantize_chainq, train_chainq, update_codebooks_chain_bin, get_cbdims_chain
 export HipIndex, HipIndexU16, HipAqIndex, HipAqIndexU16, set_codes!, set_codes_synth!, search, HipDataset, quantize
 export HipIvfIndex, build!, add!, add_codes!, train_ivfpq
+export rerank, search_refine
 
 # Multi-GPU without touching a call site: with ENV["RAYUELA_HIP_DEVICES"] = "0,1,2,3" (or "all") set before the
 # call, linscan_pq / linscan_opq below shard B row-wise over those devices inside the library (per-device scan,
@@ -1005,6 +1006,53 @@ function quantize(ds::HipDataset, C::Vector{Matrix{Float32}}; R::Union{Nothing,M
     (Ptr{Cvoid}, Ptr{Cuchar}, Ptr{Int16}, Ptr{Cfloat}, Ptr{Cfloat}, Cint, Cint),
     ds.h, C_NULL, B, R === nothing ? C_NULL : R, _cat_codebooks(C), Cint(m), Cint(h)))
   return B
+end
+
+"""
+    rerank(ds, X, cand, k; id_offset=0) -> dists, ids
+The candidates of a search (`cand`, kc-by-nq ONE-based `UInt32` ids as `search` returns them) ordered by their exact Float32
+distance to the rows of the resident `ds`: the `k` nearest per query, k-by-nq.  Column i of the uploaded matrix has id
+`i + id_offset`.  Ids outside the base (the searches' padding id among them) are skipped, an id given twice appears twice, and
+a short list ends in the padding pair (rq_dataset_rerank).
+"""
+function rerank(ds::HipDataset, X::Matrix{Cfloat}, cand::Matrix{UInt32}, k::Integer; id_offset::Integer=0)
+  kc, nq = size(cand)
+  size(X, 2) == nq || error("one column of candidates per query")
+  1 <= k <= kc || error("1 <= k <= kc=$kc; got $k")
+  dists = Matrix{Cfloat}(undef, k, nq)
+  res   = Matrix{Cuint}(undef, k, nq)
+  ldc = kc
+  id_base = 1
+  _check(ccall((:rq_dataset_rerank, librayuela_hip), Cint,
+    (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cuint}, Ptr{Cfloat}, Int64, Ptr{Cuint}, Int64, Int64, Cint, UInt32, Cint),
+    ds.h, dists, res, X, Int64(nq), cand, Int64(kc), Int64(ldc), Cint(k), UInt32(id_offset), Cint(id_base)))
+  return dists, res
+end
+
+"""
+    search_refine(ix, ds, X, nprobe, k, kc; id_offset=0)    # HipIvfIndex: on the device, no host round trip
+    search_refine(ix, ds, X, k, kc; R=nothing)               # HipIndex / HipIndexU16 / HipAqIndex / HipAqIndexU16
+`search` with `kc` candidates per query, re-ranked by `rerank(ds, X, cand, k)`: bit for bit that composition.  The queries are
+re-ranked unrotated against the unrotated base.
+"""
+function search_refine(ix::HipIvfIndex, ds::HipDataset, X::Matrix{Cfloat}, nprobe::Int, k::Int, kc::Int; id_offset::Integer=0)
+  d, nq = size(X)
+  d == ix.d || error("queries must have d=$(ix.d) rows")
+  1 <= nprobe <= ix.nlist || error("1 <= nprobe <= nlist=$(ix.nlist); got $nprobe")
+  1 <= k <= kc || error("1 <= k <= kc=$kc; got $k")
+  dists = Matrix{Cfloat}(undef, k, nq)
+  res   = Matrix{Cuint}(undef, k, nq)
+  id_base = 1
+  _check(ccall((:rq_ivf_search_refine, librayuela_hip), Cint,
+    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cuint}, Ptr{Cfloat}, Int64, Cint, Cint, Cint, UInt32, Cint),
+    ix.h, ds.h, dists, res, X, Int64(nq), Cint(nprobe), Cint(k), Cint(kc), UInt32(id_offset), Cint(id_base)))
+  return dists, res
+end
+
+function search_refine(ix::Union{HipIndex,HipIndexU16,HipAqIndex,HipAqIndexU16}, ds::HipDataset, X::Matrix{Cfloat}, k::Int, kc::Int;
+                       R::Union{Nothing,Matrix{Cfloat}}=nothing)
+  _, cand = R === nothing ? search(ix, X, kc) : search(ix, X, kc; R=R)
+  return rerank(ds, X, convert(Matrix{UInt32}, cand), k)
 end
 
 # ---- LSQ encoding (src/LSQ.jl:272-302, src/LSQ_GPU.jl:218-264): ILS around ICM on the device (rq_encode_icm) ----------

@@ -154,6 +154,26 @@ class IvfIndex:
                                             int(id_base)))
         return dists, ids
 
+    def search_refine(self, Xq, ds, nprobe, k, kc, id_offset=0, id_base=1):
+        """search(Xq, nprobe, kc) re-ranked on the device by the exact float32 distance to the rows of the resident Dataset ds
+        (rq_ivf_search_refine; Dataset.rerank states the contract): row i of ds has id i + id_offset.  Equals
+        ds.rerank(Xq, self.search(Xq, nprobe, kc, id_base)[1], k, id_offset, id_base) bit for bit, without the host round trip."""
+        Xq = _as_f32(Xq, "Xq")
+        if Xq.ndim != 2 or Xq.shape[1] != self.d:
+            raise ValueError("queries must be (nq, d=%d)" % self.d)
+        if nprobe < 1 or nprobe > self.nlist:
+            raise ValueError("1 <= nprobe <= nlist=%d; got %d" % (self.nlist, nprobe))
+        if not 1 <= k <= kc:
+            raise ValueError("1 <= k <= kc; got k=%d, kc=%d" % (k, kc))
+        if id_base not in (0, 1):
+            raise ValueError("id_base must be 0 or 1")
+        nq = Xq.shape[0]
+        dists = _lib.result_empty((nq, k), np.float32)
+        ids = _lib.result_empty((nq, k), np.uint32)
+        _lib.check(_lib.lib().rq_ivf_search_refine(self._h, ds._h, dists.ctypes.data, ids.ctypes.data, Xq.ctypes.data, nq, int(nprobe),
+                                                   int(k), int(kc), int(id_offset), int(id_base)))
+        return dists, ids
+
     def lists(self):
         """(offsets (nlist + 1,) int64, ids (n,) uint32 with id_offset, codes (n, m) uint8) in grouped order."""
         n = (C.c_int64 * 1)()               # the library's own count: the base may have been loaded through the C entries

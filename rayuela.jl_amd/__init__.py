@@ -32,6 +32,7 @@ from .Linscan import (linscan_pq, linscan_opq, linscan_lsq, linscan_cq, linscan_
 from .index import Index, IndexU16, AqIndex, AqIndexU16, Dataset  # noqa: F401,E402
 from .IVF import IvfIndex, train_ivfpq  # noqa: F401,E402
 from .knn import groundtruth, knn_f64, knn_f32, knn_plan, last_knn_stats, last_knn_timing  # noqa: F401,E402
+from .knn import rerank_plan, last_rerank_stats, last_rerank_timing  # noqa: F401,E402
 from . import h5results  # noqa: F401,E402  (libhdf5 is looked up lazily, on first use)
 from . import datasets  # noqa: F401,E402
 

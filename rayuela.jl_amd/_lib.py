@@ -194,6 +194,7 @@ SIGNATURES = {
     "rq_ivf_add_bytes": (_i32, [_vp, _vp, _i64, _u32]),
     "rq_ivf_add_codes": (_i32, [_vp, _vp, _vp, _i64, _u32]),
     "rq_ivf_search": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32]),
+    "rq_ivf_search_refine": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _u32, _i32]),
     "rq_ivf_get_lists": (_i32, [_vp, _vp, _vp, _vp]),
     "rq_ivf_info": (_i32, [_vp, _vp, _i32]),
     "rq_ivf_last_timing": (_i32, [_vp, _vp, _i32]),
@@ -224,6 +225,11 @@ SIGNATURES = {
     "rq_last_knn_timing": (_i32, [_vp, _i32]),
     "rq_knn_plan": (_i32, [_i64, _i64, _i32, _i32, _vp, _i32]),
     "rq_test_knn_chunk_rows": (_i64, [_i64]),
+    "rq_dataset_rerank": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _u32, _i32]),
+    "rq_last_rerank_timing": (_i32, [_vp, _i32]),
+    "rq_last_rerank_stats": (_i32, [_vp]),
+    "rq_rerank_plan": (_i32, [_i64, _i64, _i32, _i64, _i32, _vp, _i32]),
+    "rq_test_rerank_limits": (_i64, [_i64, _i64]),
     "rq_test_scan_wide_slice_rows": (_i64, [_i64]),
 }
 

@@ -434,6 +434,38 @@ int rotate_bytes_launch(float *RX, const float *R, const uint8_t *X, int d, int6
 // what a resident dataset (rq_dataset_upload[_bytes], rq_api.hip) holds, for the entries of other files (rq_knn.hip)
 struct DatasetView { const void *X; int64_t n; int d, esz, device; };   // esz 4: f32 rows, 1: byte rows
 RQ_LOCAL bool dataset_view(const rq_dataset *handle, DatasetView *out);
+// ---- exact re-ranking of candidates (rq_rerank.hip) ---------------------------------------------------
+// One batch of nb queries on the device: candidate i of query q is the word cand[q * ldc + i * cstep] (cstep 1: ids with id_base
+// and id_offset on them; cstep 2: the low words of packed keys, id_base 0 on them), its row is that word - id_base - id_offset.
+// dists / ids [nb][k] (device) <- the k smallest (D32, row) pairs, ids + id_offset + id_base.  scratch: rerank_scratch_bytes()
+// bytes that nothing else uses until the stream has run the call; nvalid_host [nb] <- every query's candidates inside the base,
+// once the stream has been waited for.  The clock gets one mark behind the keys (ph_keys) and one behind the selection (ph_select).
+struct RerankCall {
+  DatasetView base;
+  const float *Q = nullptr;
+  const uint32_t *cand = nullptr;
+  size_t ldc = 0;
+  uint32_t cstep = 1;
+  int64_t nb = 0, kc = 0;
+  int k = 0;
+  uint32_t id_offset = 0;
+  int id_base = 0;
+  float *dists = nullptr;
+  uint32_t *ids = nullptr;
+  void *scratch = nullptr;
+  uint32_t *nvalid_host = nullptr;      // [nb]
+  bool chain = false;                   // rerank_chain(kc), read once per call: the scratch was sized with this value
+  int ph_keys = 0, ph_select = 0;
+};
+RQ_LOCAL size_t rerank_scratch_bytes(int64_t nb, int64_t kc, int k, bool chain);
+RQ_LOCAL bool rerank_chain(int64_t kc);      // does kc take the select chain (else the LDS sort)?
+RQ_LOCAL int rerank_device(const RerankCall &c, hipStream_t stream, PhaseClock &clk, int num_cu);
+// every argument check the entries share (`who` names the entry); no device work
+RQ_LOCAL int rerank_check(const char *who, bool null_arg, int64_t n, int64_t kc, int64_t ldc, int k, uint32_t id_offset, int id_base);
+// rq_last_rerank_stats / rq_last_rerank_timing of the calling thread: start a call, add its keys / select ms, add its counters
+RQ_LOCAL void rerank_clear();
+RQ_LOCAL void rerank_add_ms(double keys_ms, double select_ms);
+RQ_LOCAL void rerank_note(int64_t nq, int64_t kc, int64_t batches, unsigned long long valid, int chain);
 
 // ---- training reductions (rq_train.hip) --------------------------------------------------------
 // Code: uint8_t (1 <= h <= 256; reconstruct: any h) or int16_t (zero-based, read zero-extended, 1 <= h <=

@@ -18,6 +18,8 @@
 //   3. ivf_fill_kernel + ivf_keys_kernel<MP>             a workgroup per item: q' = q - Q[list], the m x 256 table in LDS, its rows'
 //                  keys at the item's offset of keys [nb][ld]; the slots behind a query's last row hold KEY_MAX
 //   4. sel_run (k)                                       dists / ids, (NaN, 0xFFFFFFFF + id_base) behind the comparable rows
+// rq_ivf_search_refine runs the same body with kc in place of k: step 4 leaves its sorted keys on the
+// device and rerank_device (rq_rerank.hip) orders them by the exact distance to the rows of a resident dataset.
 // The build groups rows with the same chain: keys (list << 32 | row) of a piece of rows, sorted by sel_run with k = the piece, are
 // the piece in (list, row) order; pieces are placed one behind the other inside every list, so a list holds its rows in ascending id.
 // An add takes its batch through the same steps with temporaries sized by the batch; the loaded base enters
@@ -401,7 +403,7 @@ struct rq_ivf {
   std::vector<int64_t> h_desc;     // the list sizes, largest first
   // the last search
   int64_t s_ld = 0, s_batch = 0, s_items = 0, s_rows = 0;
-  double s_ms[4] = {0, 0, 0, 0};
+  double s_ms[6] = {0, 0, 0, 0, 0, 0};   // the last search: its four phases, then the keys and the selection of a refinement
   double l_ms[4] = {0, 0, 0, 0};   // the last build / set_codes / add: encode (with its uploads), grouping, carry, place
   std::mutex mu;
 };
@@ -664,11 +666,20 @@ int ivf_load_codes(const char *who, rq_ivf *ix, const uint32_t *lists_host, cons
 
 // scratch of a batch of nb queries: what survives both phases, then the larger of the probe selection and the scan
 struct IvfPlan {
-  size_t keep, phase1, phase2;
-  size_t total() const { return keep + std::max(phase1, phase2); }
+  size_t keep, phase1, phase2, phase3;
+  size_t total() const { return keep + std::max(std::max(phase1, phase2), phase3); }
 };
-IvfPlan ivf_bytes(int64_t nb, int nlist, int nprobe, int k, size_t ld, size_t items_per_query) {
+// what rq_ivf_search_refine adds to a search: the dataset the candidates are re-ranked on, and the k of the answer (the search
+// itself then runs with kc in place of k and hands its sorted keys to rerank_device, whose scratch is a third phase)
+struct IvfRefine {
+  DatasetView base;
+  int k;
+  uint32_t id_offset;
+  bool chain;          // rerank_chain(kc), read once per call
+};
+IvfPlan ivf_bytes(int64_t nb, int nlist, int nprobe, int k, size_t ld, size_t items_per_query, const IvfRefine *rf) {
   IvfPlan pl;
+  pl.phase3 = rf ? rerank_scratch_bytes(nb, k, rf->k, rf->chain) : 0;
   pl.keep = 3 * ivf_align((size_t)nb * nprobe * 4) + 3 * ivf_align((size_t)nb * 4) + 256;
   pl.phase1 = ivf_align((size_t)nb * nlist * 8) + (size_t)nb * sel_bytes_per_query((uint32_t)nprobe) + 16 * 256;
   pl.phase2 = ivf_align((size_t)nb * items_per_query * sizeof(IvfItem)) + ivf_align((size_t)nb * ld * 8) +
@@ -683,6 +694,10 @@ int ivf_keys_launch(const IvfKeyParams &p, uint32_t nitems, hipStream_t stream) 
   RQ_LAUNCH_LDS(ivf_keys_kernel<MP>, dim3(nitems), dim3(IVF_T), lds, stream, p);
   return RQ_OK;
 }
+
+// rq_ivf_search (rf null) and rq_ivf_search_refine: k is the k of the index's own top-k (kc of a refinement)
+int ivf_search_body(const char *who, rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k,
+                    int id_base, const IvfRefine *rf);
 
 }  // namespace
 
@@ -756,13 +771,39 @@ int rq_ivf_add_codes(rq_ivf *ix, const uint32_t *lists_host, const uint8_t *code
 }
 
 int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k, int id_base) {
-  if (!ix || !dists || !ids || !queries_host) return fail(RQ_EINVAL, "rq_ivf_search: NULL argument");
+  return ivf_search_body("rq_ivf_search", ix, dists, ids, queries_host, nq, nprobe, k, id_base, nullptr);
+}
+
+int rq_ivf_search_refine(rq_ivf *ix, rq_dataset *ds, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe,
+                         int k, int kc, uint32_t id_offset, int id_base) {
+  rerank_clear();
+  IvfRefine rf;
+  if (!ix || !dataset_view(ds, &rf.base)) return fail(RQ_EINVAL, "rq_ivf_search_refine: NULL argument");
   if (nq <= 0) return RQ_OK;
-  if (nprobe < 1 || nprobe > ix->nlist) return fail(RQ_EINVAL, "rq_ivf_search: 1 <= nprobe <= nlist=%d; got nprobe=%d", ix->nlist, nprobe);
-  if (k < 1) return fail(RQ_EINVAL, "rq_ivf_search: k=%d", k);
-  if (id_base != 0 && id_base != 1) return fail(RQ_EINVAL, "rq_ivf_search: id_base must be 0 or 1; got %d", id_base);
+  RQ_TRY(rerank_check("rq_ivf_search_refine", !dists || !ids || !queries_host, rf.base.n, kc, kc, k, id_offset, id_base));
+  if (rf.base.device != ix->device)
+    return fail(RQ_EINVAL, "rq_ivf_search_refine: the dataset is on device %d, the index on device %d", rf.base.device, ix->device);
+  if (rf.base.d != ix->d) return fail(RQ_EINVAL, "rq_ivf_search_refine: the dataset has d=%d, the index d=%d", rf.base.d, ix->d);
+  rf.k = k;
+  rf.id_offset = id_offset;
+  rf.chain = rerank_chain(kc);
+  return ivf_search_body("rq_ivf_search_refine", ix, dists, ids, queries_host, nq, nprobe, kc, id_base, &rf);
+}
+
+}  // extern "C"
+
+namespace {
+
+int ivf_search_body(const char *who, rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_host, int64_t nq, int nprobe, int k,
+                    int id_base, const IvfRefine *rf) {
+  if (!ix || !dists || !ids || !queries_host) return fail(RQ_EINVAL, "%s: NULL argument", who);
+  if (nq <= 0) return RQ_OK;
+  if (nprobe < 1 || nprobe > ix->nlist) return fail(RQ_EINVAL, "%s: 1 <= nprobe <= nlist=%d; got nprobe=%d", who, ix->nlist, nprobe);
+  if (k < 1) return fail(RQ_EINVAL, "%s: k=%d", who, k);
+  if (id_base != 0 && id_base != 1) return fail(RQ_EINVAL, "%s: id_base must be 0 or 1; got %d", who, id_base);
   std::lock_guard<std::mutex> guard(ix->mu);
-  if (!ix->codes || ix->n < 1) return fail(RQ_EINVAL, "rq_ivf_search: the index holds no base (rq_ivf_build / rq_ivf_set_codes)");
+  if (!ix->codes || ix->n < 1) return fail(RQ_EINVAL, "%s: the index holds no base (rq_ivf_build / rq_ivf_set_codes)", who);
+  const int kout = rf ? rf->k : k;       // entries per query of dists / ids
   SavedDevice saved;
   RQ_HIP(hipSetDevice(ix->device));
   DeviceLock lock;
@@ -783,19 +824,23 @@ int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_
   int64_t lo = 0, hi = cap;
   while (lo < hi) {               // the largest batch whose scratch fits
     const int64_t mid = (lo + hi + 1) / 2;
-    if (ivf_bytes(mid, nlist, nprobe, k, ld_bound, items_bound).total() <= bulk_usable()) lo = mid;
+    if (ivf_bytes(mid, nlist, nprobe, k, ld_bound, items_bound, rf).total() <= bulk_usable()) lo = mid;
     else hi = mid - 1;
   }
   const int64_t nbmax = lo;
   if (nbmax < 1)
-    return fail(RQ_EUNSUPPORTED, "rq_ivf_search: one query's keys (up to %zu, k=%d) need more than the BULK_SCRATCH_BYTES budget of scratch",
+    return fail(RQ_EUNSUPPORTED, "%s: one query's keys (up to %zu, k=%d) need more than the BULK_SCRATCH_BYTES budget of scratch", who,
                 ld_bound, k);
   void *ws = nullptr;
-  RQ_TRY(workspace(WS_BULK, ivf_bytes(nbmax, nlist, nprobe, k, ld_bound, items_bound).total(), &ws, stream));
-  DevMem dq, dd, di;
+  RQ_TRY(workspace(WS_BULK, ivf_bytes(nbmax, nlist, nprobe, k, ld_bound, items_bound, rf).total(), &ws, stream));
+  DevMem dq, dd, di, dk;
   RQ_TRY(dq.alloc((size_t)nbmax * d * 4));
-  RQ_TRY(dd.alloc((size_t)nbmax * k * 4));
-  RQ_TRY(di.alloc((size_t)nbmax * k * 4));
+  RQ_TRY(dd.alloc((size_t)nbmax * kout * 4));
+  RQ_TRY(di.alloc((size_t)nbmax * kout * 4));
+  if (rf) RQ_TRY(dk.alloc((size_t)nbmax * k * 8));      // the sorted top-kc keys of step 4: the candidates
+  unsigned long long valid = 0;
+  int64_t batches = 0;
+  std::vector<uint32_t> hv(rf ? (size_t)nbmax : 0);
   ix->s_ld = 0; ix->s_batch = nbmax; ix->s_items = 0; ix->s_rows = 0;
   for (double &t : ix->s_ms) t = 0;
   for (int64_t q0 = 0; q0 < nq; q0 += nbmax) {
@@ -836,7 +881,7 @@ int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_
     const unsigned long long nitems = hs[0];
     const size_t ld = std::max<size_t>((size_t)hs[1], (size_t)k);
     if (ld > ld_bound || nitems > (unsigned long long)nb * items_bound || nitems >= (1ull << 31))
-      return fail(RQ_EINVAL, "rq_ivf_search: %llu items, %zu keys per query exceed the plan (%zu, %zu)", nitems, ld,
+      return fail(RQ_EINVAL, "%s: %llu items, %zu keys per query exceed the plan (%zu, %zu)", who, nitems, ld,
                   (size_t)nb * items_bound, ld_bound);
     at = phase;
     IvfItem *items = (IvfItem *)at; at += ivf_align((size_t)nb * items_bound * sizeof(IvfItem));
@@ -869,20 +914,44 @@ int rq_ivf_search(rq_ivf *ix, float *dists, uint32_t *ids, const float *queries_
       uint32_t hx;
       sel_grid(s, (uint32_t)ld, nb, ix->num_cu, &hx);
       BulkOut o;
-      o.dists = dd.as<float>(); o.ids = di.as<uint32_t>(); o.keys = nullptr; o.id_base = (uint32_t)id_base;
+      if (rf) { o.dists = nullptr; o.ids = nullptr; o.keys = dk.as<uint64_t>(); o.id_base = 0; }
+      else { o.dists = dd.as<float>(); o.ids = di.as<uint32_t>(); o.keys = nullptr; o.id_base = (uint32_t)id_base; }
       RQ_TRY(sel_run(s, hx, nb, o, stream));
     }
     clock.mark(3);
-    RQ_HIP(hipMemcpyAsync(dists + (size_t)q0 * k, dd.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, stream));
-    RQ_HIP(hipMemcpyAsync(ids + (size_t)q0 * k, di.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, stream));
+    if (rf) {   // 5. the candidates by their exact distance: the phase scratch is free again (one stream)
+      RerankCall c;
+      c.base = rf->base;
+      c.Q = dq.as<float>();
+      c.cand = dk.as<uint32_t>(); c.ldc = 2 * (size_t)k; c.cstep = 2;
+      c.nb = nb; c.kc = k; c.k = kout; c.id_offset = rf->id_offset; c.id_base = id_base;
+      c.dists = dd.as<float>(); c.ids = di.as<uint32_t>();
+      c.scratch = phase;
+      c.nvalid_host = hv.data();
+      c.chain = rf->chain;
+      c.ph_keys = 4; c.ph_select = 5;
+      RQ_TRY(rerank_device(c, stream, clock, ix->num_cu));
+    }
+    RQ_HIP(hipMemcpyAsync(dists + (size_t)q0 * kout, dd.p, (size_t)nb * kout * 4, hipMemcpyDeviceToHost, stream));
+    RQ_HIP(hipMemcpyAsync(ids + (size_t)q0 * kout, di.p, (size_t)nb * kout * 4, hipMemcpyDeviceToHost, stream));
     RQ_HIP(hipStreamSynchronize(stream));
     clock.collect();
+    if (rf) for (int64_t b = 0; b < nb; ++b) valid += hv[(size_t)b];
+    ++batches;
     ix->s_ld = std::max<int64_t>(ix->s_ld, (int64_t)ld);
     ix->s_items += (int64_t)nitems;
     ix->s_rows += (int64_t)hs[2];
   }
+  if (rf) {
+    rerank_add_ms(ix->s_ms[4], ix->s_ms[5]);
+    rerank_note(nq, k, batches, valid, rf->chain);
+  }
   return RQ_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int rq_ivf_get_lists(rq_ivf *ix, int64_t *offsets, uint32_t *row_ids, uint8_t *codes) {
   if (!ix) return fail(RQ_EINVAL, "rq_ivf_get_lists: NULL index");

@@ -83,16 +83,25 @@ def experiment_opq_query_base(Xt, Xq, gt, m, h, init, niter=25, knn=1000, V=Fals
 
 
 def experiment_ivfpq(Xt, Xb, Xq, gt=None, nlist=1024, m=8, nprobes=(1, 8, 32), niter=25, knn=100, by_residual=True, V=False,
-                     seed=0, add_rows=None):
+                     seed=0, add_rows=None, refine=None):
     """IVFADC (IVF.py; no counterpart in the reference): train the coarse centroids and the codebooks on Xt, build the index on
     Xb, search Xq once per nprobe.  Returns Q, C and {nprobe: recall curve of eval_recall} -- recall against the exact nearest
     neighbour, so it is bounded by the share of queries whose neighbour lies in a probed list.  add_rows: load Xb in adds of that
-    many rows instead of one build; the loaded base, and so every curve, is the same."""
+    many rows instead of one build; the loaded base, and so every curve, is the same.  refine=kc: Xb is uploaded as a Dataset and
+    every search also runs as search_refine with kc candidates; a fourth return value {nprobe: {"adc": {1: r, 10: r, 100: r},
+    "refined": {...}}} then holds recall@1 / 10 / 100 (the share of queries whose exact nearest neighbour is among the first R
+    answers) without and with the refinement.  refine=None (the default) returns the three values it always returned."""
+    from contextlib import ExitStack
     from .IVF import IvfIndex, train_ivfpq
+    from .index import Dataset
+    if refine is not None and refine < knn:
+        raise ValueError("refine must be at least knn=%d candidates; got %d" % (knn, refine))
     Q, C = train_ivfpq(Xt, nlist, m, niter=niter, seed=seed, by_residual=by_residual)
     truth = _gt(gt, Xb, Xq)
-    recall = {}
-    with IvfIndex(Q, C, by_residual=by_residual) as ix:
+    recall, refined = {}, {}
+    with ExitStack() as stack:
+        ds = stack.enter_context(Dataset(Xb)) if refine is not None else None
+        ix = stack.enter_context(IvfIndex(Q, C, by_residual=by_residual))
         if add_rows is None:
             ix.build(Xb)
         else:
@@ -105,7 +114,19 @@ def experiment_ivfpq(Xt, Xb, Xq, gt=None, nlist=1024, m=8, nprobes=(1, 8, 32), n
                 print("nprobe = %d" % nprobe)
             _, idx = ix.search(Xq, nprobe, knn)
             recall[nprobe] = eval_recall(truth, idx, knn, verbose=V)
+            if ds is not None:
+                _, idr = ix.search_refine(Xq, ds, nprobe, knn, int(refine))
+                refined[nprobe] = {"adc": _recall_at(truth, idx, knn), "refined": _recall_at(truth, idr, knn)}
+    if refine is not None:
+        return Q, C, recall, refined
     return Q, C, recall
+
+
+def _recall_at(truth, idx, knn, ranks=(1, 10, 100)):
+    """{R: share of queries whose exact nearest neighbour (truth, one-based) is among the first R answers}, R <= knn"""
+    t = np.asarray(truth).reshape(len(idx), -1)[:, 0].astype(np.int64)
+    ids = np.asarray(idx).astype(np.int64)
+    return {R: float((ids[:, :R] == t[:, None]).any(axis=1).mean()) for R in ranks if R <= knn}
 
 
 def _norms_codebook(B, C, h=256, seed=0):

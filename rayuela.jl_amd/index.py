@@ -70,6 +70,15 @@ class Index:
                                                R.ctypes.data, nq, k, id_base))
         return dists, idx
 
+    def search_refine(self, X, ds, k, kc, R=None, id_base=1):
+        """search(k=kc) re-ranked by the exact distance to the rows of the resident Dataset ds (Dataset.rerank): (dists (nq, k)
+        float32, ids (nq, k) uint32).  The queries are re-ranked unrotated against the unrotated base; row i of ds is row i of
+        the codes AND has id i: a handle whose codes were loaded with an id_offset is not supported here (its ids would name
+        other rows of ds, or none) -- call ds.rerank(X, cand, k, id_offset=...) on the result of search yourself.  Inherited by
+        every index class, sharded handles included."""
+        _, cand = self.search(X, k=kc, R=R, id_base=id_base)
+        return ds.rerank(X, cand, k, id_offset=0, id_base=id_base)
+
     def info(self):
         out = (C.c_int64 * 68)()
         _lib.check(_lib.lib().rq_index_info(self._h, C.cast(out, C.c_void_p), 68))
@@ -319,6 +328,32 @@ class Dataset:
         ids = np.empty((nq, k), dtype=np.uint32)
         _lib.check(_lib.lib().rq_dataset_knn(self._h, dists.ctypes.data, ids.ctypes.data, Xq.ctypes.data, nq, int(k),
                                              int(id_base)))
+        return dists, ids
+
+    def rerank(self, Xq, cand, k, id_offset=0, id_base=1):
+        """The candidates of a search ordered by their exact float32 distance to the rows of this base (rq_dataset_rerank):
+        cand (nq, kc) uint32 ids as a search returned them (id_base and id_offset on them; columns of a wider array are taken in
+        place), of which the k nearest per query come back as (dists (nq, k) float32 ascending, ids (nq, k) uint32).  Ids outside
+        the base -- the searches' padding id among them -- are skipped, an id given twice appears twice, and a list with fewer
+        than k valid candidates ends in (NaN, 0xFFFFFFFF + id_base)."""
+        Xq = _as_f32(Xq, "Xq")
+        if Xq.ndim != 2 or Xq.shape[1] != self.d:
+            raise ValueError("queries must be (nq, %d)" % self.d)
+        cand = np.asarray(cand)
+        if cand.dtype != np.uint32 or cand.ndim != 2 or cand.shape[0] != Xq.shape[0]:
+            raise ValueError("cand must be uint32 (nq, kc)")
+        if cand.shape[1] and (cand.strides[1] != 4 or cand.strides[0] % 4 or cand.strides[0] < 4 * cand.shape[1]):
+            cand = np.ascontiguousarray(cand)
+        nq, kc = cand.shape
+        ldc = cand.strides[0] // 4 if nq > 1 and kc else kc
+        if not 1 <= k <= kc:
+            raise ValueError("1 <= k <= kc=%d; got %d" % (kc, k))
+        if id_base not in (0, 1):
+            raise ValueError("id_base must be 0 or 1")
+        dists = _lib.result_empty((nq, k), np.float32)
+        ids = _lib.result_empty((nq, k), np.uint32)
+        _lib.check(_lib.lib().rq_dataset_rerank(self._h, dists.ctypes.data, ids.ctypes.data, Xq.ctypes.data, nq, cand.ctypes.data,
+                                                kc, ldc, int(k), int(id_offset), int(id_base)))
         return dists, ids
 
     def close(self):

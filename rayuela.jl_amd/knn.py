@@ -87,3 +87,37 @@ def knn_plan(n, nq, d, k):
     out = (C.c_int64 * 6)()
     _lib.check(_lib.lib().rq_knn_plan(int(n), int(nq), int(d), int(k), C.cast(out, C.c_void_p), 6))
     return dict(zip(["candidates", "chunk_rows", "chunks", "batch", "scratch_bytes", "forced"], [int(x) for x in out]))
+
+
+RERANK_STATS = ["queries", "candidates", "valid", "batches", "chain", "keys_per_query"]
+RERANK_PHASES = ["upload", "keys", "select", "download"]
+
+
+def last_rerank_stats():
+    """Counters of this thread's last re-ranking call (rq_last_rerank_stats; Dataset.rerank, IvfIndex.search_refine): queries,
+    candidates, candidates inside the base, batches, the select path (0: sorted in LDS, 1: the select chain), keys per query row."""
+    out = (C.c_uint64 * 8)()
+    _lib.check(_lib.lib().rq_last_rerank_stats(C.cast(out, C.c_void_p)))
+    return dict(zip(RERANK_STATS, [int(x) for x in out[:6]]))
+
+
+def last_rerank_timing():
+    """Phase clock of this thread's last re-ranking call (rq_last_rerank_timing), in ms."""
+    out = (C.c_double * 4)()
+    _lib.check(_lib.lib().rq_last_rerank_timing(C.cast(out, C.c_void_p), 4))
+    return dict(zip(RERANK_PHASES, [float(x) for x in out]))
+
+
+def rerank_limits(lds_kc=0, batch_queries=0):
+    """Test hook, not for callers (rq_test_rerank_limits): the most candidates per query that are sorted in LDS and a cap on the
+    queries per batch; 0 gives the planner its choice back.  Returns the previous (lds_kc, batch_queries)."""
+    prev = int(_lib.lib().rq_test_rerank_limits(int(lds_kc), int(batch_queries)))
+    return prev >> 32, prev & 0xFFFFFFFF
+
+
+def rerank_plan(n, nq, d, kc, k):
+    """The planner's decision (host code only, rq_rerank_plan): queries per batch, scratch bytes of a batch, the select path, keys
+    per query row, and whether the test hook rerank_limits set the batch."""
+    out = (C.c_int64 * 5)()
+    _lib.check(_lib.lib().rq_rerank_plan(int(n), int(nq), int(d), int(kc), int(k), C.cast(out, C.c_void_p), 5))
+    return dict(zip(["batch", "scratch_bytes", "chain", "keys_per_query", "forced"], [int(x) for x in out]))
